@@ -8,8 +8,15 @@ weights) on a spike matrix already resident in HBM.  Workload a
 every GPU count: standard_glm, N=128 neurons, T=600 s at 1 ms bins (C3, the
 configuration the north-star target is quoted on), synthetic Poisson spikes.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (headline, ms_per_step, and the roofline of
+the HIP events sampled inside the timed region).  --dump-outputs DIR writes the ll and gradient of the last timed step
+as DIR/ll.npy and DIR/grad.npy (float64; the inputs are seeded, so two builds can be compared output for output).
+--full adds everything else behind the timed region: the A/B loops, the narrow-shard step, the MAP / MCMC / stimulus
+secondaries, the PMC traffic figures, the CPU baselines and, on N > 1 ranks, the neuron-sharded step, the sharded MAP
+sweep and the check of the sharded evaluation against the single-rank one (the --no-* options prune that set).
 
 `python bench.py --gpus N` with N > 1 and no launcher (WORLD_SIZE unset) starts the N ranks itself: the parent --
 before torch or HIP are touched -- builds the library, spawns N fresh `python bench.py ...` processes with
@@ -47,6 +54,33 @@ def make_workload(N, T, dt, seed):
     nT = int(round(T / dt))
     S = np.minimum(rng.poisson(20.0 * dt, size=(nT, N)), 10).astype(np.uint8)
     return S
+
+
+def make_theta(N, P, seed=99):
+    """Parameters of every neuron (bias | impulse weights), seeded like the workload."""
+    rng = np.random.default_rng(seed)
+    theta = np.zeros((N, P))
+    theta[:, 0] = 20.0 + 0.1 * rng.standard_normal(N)
+    theta[:, 1:] = 0.5 * rng.standard_normal((N, P - 1))
+    return theta
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write every array as out_dir/<name>.npy in float64.  When the total would exceed `limit`, the 2-D arrays keep
+    every k-th row (k fixed by the sizes alone), so that two runs with the same arguments write the same rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = dict((k, np.ascontiguousarray(v, dtype=np.float64)) for k, v in arrays.items())
+    rows = max([a.shape[0] for a in arrays.values() if a.ndim >= 2] or [1])
+    stride = 1
+    while stride < rows and sum((a[::stride] if a.ndim >= 2 else a).nbytes for a in arrays.values()) > limit:
+        stride += 1
+    arrays = dict((k, a[::stride] if a.ndim >= 2 else a) for k, a in arrays.items())
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return arrays
 
 
 def standard_ibasis(R=200):
@@ -572,10 +606,14 @@ def main():
     ap.add_argument('--no-stim', action='store_true', help='skip the secondary stimulus stress-variant measurement (config 5)')
     ap.add_argument('--no-stim-map', action='store_true',
                     help='skip the MAP sweep of the stress variant inside the stimulus block')
-    ap.add_argument('--stim-map', action='store_true', help='(accepted for older scripts: the sweep is part of the default run)')
+    ap.add_argument('--stim-map', action='store_true', help='(accepted for older scripts: the sweep is part of --full)')
     ap.add_argument('--no-ab', action='store_true',
                     help='skip the A/B loops after the timed region (in-kernel features, all-f64 epilogue): profiler '
                          'passes use it so that per-kernel averages and counters describe the headline kernel only')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every measurement and check beyond the headline (see the module docstring)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write the ll and gradient of the last timed step as DIR/<name>.npy (rank 0)')
     ap.add_argument('--shard', choices=['time', 'neurons'], default='time')
     # dev-only: exercise the N>1 code path on a 1-GPU box (all ranks on cuda:0, gloo collectives)
     ap.add_argument('--debug-single-device', action='store_true')
@@ -596,7 +634,7 @@ def main():
     import __graft_entry__ as ge
     if rank == 0:
         ge.build_hip()
-        if not args.no_cpu_baseline and not multi:
+        if args.full and not args.no_cpu_baseline and not multi:
             ge.build_oracle()
 
     import torch
@@ -639,10 +677,7 @@ def main():
     ib = standard_ibasis()
     R, B = ib.shape
     P = 1 + N * B
-    rng = np.random.default_rng(99)
-    theta = np.zeros((N, P))
-    theta[:, 0] = 20.0 + 0.1 * rng.standard_normal(N)
-    theta[:, 1:] = 0.5 * rng.standard_normal((N, N * B))
+    theta = make_theta(N, P)
     Weff = np.ones((N, N))
 
     from theano_pyglm_amd import parallel as PL
@@ -737,6 +772,13 @@ def main():
                          device='cpu' if args.debug_single_device else 'cuda')
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller, before any loop of --full reuses the buffers (time shards: the
+        # all-reduced population; neuron shards: this rank's rows and the gathered population ll)
+        outs = {'ll': d_ll.cpu().numpy(), 'grad': d_grad.cpu().numpy()}
+        if pop_ll[0] is not None:
+            outs['population_ll'] = pop_ll[0].cpu().numpy()
+        dump_outputs(args.dump_outputs, outs)
 
     info = dev.info(n_lo, n_hi)
     n_timed, kern_ms, call_ms = dev.timing_summary(reset=True)
@@ -753,7 +795,7 @@ def main():
     shard_neurons = None
     # ranks that exchanged over RCCL (backend nccl); a gloo run (--debug-single-device) reports 'ranks' only
     rccl_ranks = (dist.get_world_size() if dist.get_backend() == 'nccl' else 0) if multi else 1
-    if multi and args.shard == 'time' and world > 1:
+    if args.full and multi and args.shard == 'time' and world > 1:
         # the split north_star names, measured behind the timed region: post-synaptic neurons block-partitioned
         # (parallel_coord_descent.py:137-147), every rank on the whole recording, all-gather of the ll shards per step
         a, b = PL.shard_bounds(N, rank, world)
@@ -794,7 +836,7 @@ def main():
         t_lo, t_hi = PL.time_shard_bounds(nT, rank, world)
         dev.set_time_range(t_lo, t_hi)
     alt = None
-    if not multi and not args.f32_features and info['kernel_version'] == 5 and not args.no_ab:
+    if args.full and not multi and not args.f32_features and info['kernel_version'] == 5 and not args.no_ab:
         # the same evaluation with the features regenerated from the spike events inside the kernel
         # (the north star's fused filter kernel, PGL_OPT_KERNEL=3) -- reported beside the headline
         dev.set_option(_lib.OPT_KERNEL, 3)
@@ -813,7 +855,7 @@ def main():
                "frac": info['flops'] / (alt_ms * 1e-3) / 1e12 / F64_MFMA_PEAK_TFLOPS}
         dev.set_option(_lib.OPT_KERNEL, 0)
     allf64 = None
-    if not multi and not args.f32_features and not args.no_ab:
+    if args.full and not multi and not args.f32_features and not args.no_ab:
         # the same evaluation with the all-f64 rate epilogue (PGL_OPT_EPI_F64: no single-precision exp(-x)
         # correction), so that the effect of that term is visible beside every headline number
         dev.set_option(_lib.OPT_EPI_F64, 1)
@@ -838,7 +880,7 @@ def main():
     achieved = info['flops'] / (kern_ms * 1e-3) / 1e12
     ll_host = d_ll.cpu().numpy()
     assert np.all(np.isfinite(ll_host)), "non-finite ll"
-    if multi:
+    if args.full and multi:
         # the sharded evaluation must equal the single-rank evaluation of the whole recording
         if args.shard == 'time':
             ll_pop = ll_host                                   # all-reduced: full ll of all N neurons
@@ -855,7 +897,7 @@ def main():
 
     # N > 1: the MAP sweep under the same (time) sharding, on every rank, behind the timed region
     map_sharded = None
-    if multi and world > 1 and args.shard == 'time' and not args.no_map:
+    if args.full and multi and world > 1 and args.shard == 'time' and not args.no_map:
         dev.set_stream(None)
         try:
             map_sharded = map_wall_clock_sharded(S, N, dt, local_rank, rank, world)
@@ -863,7 +905,7 @@ def main():
             map_sharded = {"error": "%s: %s" % (type(e).__name__, e)}
         dev.set_stream(bench_stream.cuda_stream)
     narrow = None
-    if not multi and N == 128 and not args.f32_features and not args.no_ab:
+    if args.full and not multi and N == 128 and not args.f32_features and not args.no_ab:
         narrow = narrow_shard_steps(dev, theta, d_Weff, N, P)
     if rank == 0:
         out = {
@@ -929,7 +971,7 @@ def main():
             out["collective_backend"] = dist.get_backend()
         if shard_neurons is not None:
             out["sharding_neurons"] = shard_neurons
-        if not multi and N == 128 and nT == 600000 and not args.f32_features:
+        if args.full and not multi and N == 128 and nT == 600000 and not args.f32_features:
             tr = pmc_traffic(['void k_fused5<18, 22, 1', 'void k_fused5<18, 22, 2'])
             if tr is not None:
                 out["roofline"]["traffic"] = tr[1]
@@ -937,17 +979,17 @@ def main():
             mb = pmc_mfma_busy(['void k_fused5<18, 22, 1', 'void k_fused5<18, 22, 2'])
             if mb is not None:
                 out["roofline"]["mfma_busy_pmc"] = mb
-        if not multi and not args.no_map and not args.f32_features:
+        if args.full and not multi and not args.no_map and not args.f32_features:
             out["secondary"] = map_wall_clock(S, N, dt)
         if map_sharded is not None:
             out["secondary"] = map_sharded
         if narrow is not None:
             out["secondary_narrow_shard"] = narrow
-        if not multi and not args.no_mcmc and not args.f32_features:
+        if args.full and not multi and not args.no_mcmc and not args.f32_features:
             out["secondary_mcmc"] = mcmc_inner_ll(S, N, dt)
-        if not multi and not args.no_stim and not args.f32_features:
+        if args.full and not multi and not args.no_stim and not args.f32_features:
             out["secondary_stim"] = stim_stress(with_map=not args.no_stim_map)
-        if not multi and not args.no_cpu_baseline:
+        if args.full and not multi and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(S, ib, theta, Weff, dt, sample_bins=min(nT, 300000))
         # RCCL prints a banner through C stdio: flush it first so that the JSON line is the last line of stdout
         sys.stdout.flush()

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -56,3 +57,21 @@ def test_self_launch_takes_the_other_ranks_down_when_one_fails(tmp_path):
     assert bench.self_launch(3, script=str(script), argv=['fail']) == 5
     assert time.time() - t0 < 30.0
     assert bench.self_launch(3, script=str(script), argv=['ok']) == 0
+
+
+def test_dump_outputs_writes_float64_within_the_size_limit(tmp_path):
+    """--dump-outputs: every array lands as <name>.npy in float64; above the size limit the 2-D arrays keep every k-th
+    row (the same rows in every run) and the files stay within the limit."""
+    sys.path.insert(0, ROOT)
+    import bench
+    ll = np.arange(10.0)
+    grad = np.arange(1000.0).reshape(100, 10)
+    bench.dump_outputs(str(tmp_path / 'all'), {'ll': ll, 'grad': grad.astype(np.float32)})
+    for name, a in (('ll', ll), ('grad', grad)):
+        b = np.load(tmp_path / 'all' / (name + '.npy'))
+        assert b.dtype == np.float64 and np.array_equal(b, a)
+    limit = ll.nbytes + 30 * grad[0].nbytes
+    bench.dump_outputs(str(tmp_path / 'cut'), {'ll': ll, 'grad': grad}, limit=limit)
+    b = np.load(tmp_path / 'cut' / 'grad.npy')
+    assert np.array_equal(b, grad[::4]) and np.array_equal(np.load(tmp_path / 'cut' / 'll.npy'), ll)
+    assert b.nbytes + ll.nbytes <= limit

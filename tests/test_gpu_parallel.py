@@ -214,6 +214,47 @@ def test_rccl_collectives_execute_on_a_one_rank_group():
     assert np.isclose(lpt, lpr, rtol=1e-10) and np.isfinite(lpy)
 
 
+def test_bench_plain_run_dumps_the_outputs_of_its_last_timed_step(tmp_path):
+    """A plain `bench.py` run prints the headline without the blocks of --full, and --dump-outputs writes the ll and
+    gradient of its last timed step: the same arrays bit for bit in a second run, equal to oracle/glm_blocked.c on the
+    bench's seeded inputs."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    import bench
+    from oracle import c_oracle as CO
+    N, T, dt = 64, 60.0, 0.001
+    env = dict((k, v) for k, v in os.environ.items()
+               if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'))
+    dumps = []
+    for run in range(2):
+        out = tmp_path / ('run%d' % run)
+        r = subprocess.run([sys.executable, 'bench.py', '--steps', '3', '--warmup', '1', '--seconds', str(T),
+                            '--neurons', str(N), '--dump-outputs', str(out)], cwd=root, env=env, capture_output=True,
+                           text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        rec = json.loads(r.stdout.strip().splitlines()[-1])
+        assert rec['steps'] == 3 and rec['n_gpus'] == 1 and rec['unit'] == 'evals/s' and rec['dtype'] == 'f64'
+        assert rec['ms_per_step'] > 0 and np.isclose(rec['value'], 1e3 / rec['ms_per_step'])
+        assert not set(rec) & {'secondary', 'secondary_mcmc', 'secondary_stim', 'secondary_narrow_shard', 'cpu_baseline'}
+        assert sorted(os.listdir(out)) == ['grad.npy', 'll.npy']
+        dumps.append((np.load(out / 'll.npy'), np.load(out / 'grad.npy')))
+    (ll, g), (ll2, g2) = dumps
+    assert np.array_equal(ll, ll2) and np.array_equal(g, g2)
+    S = bench.make_workload(N, T, dt, seed=1234 + 3)
+    ib = bench.standard_ibasis()
+    theta = bench.make_theta(N, 1 + N * ib.shape[1])
+    assert ll.dtype == g.dtype == np.float64 and ll.shape == (N,) and g.shape == theta.shape
+    fS = CO.features(S, ib)
+    ll0, g0 = CO.ll_grad_blocked(S, fS, theta, np.ones((N, N)), 'explinear', dt, threads=4)
+    assert np.allclose(ll, ll0, rtol=1e-10, atol=0), np.max(np.abs(ll - ll0) / np.abs(ll0))
+    for n in range(N):
+        assert np.max(np.abs(g[n] - g0[n])) / np.max(np.abs(g0[n])) < 1e-9, n
+
+
 def test_bench_multi_rank_path_on_rccl_one_rank():
     """bench.py's N > 1 code path (process group on nccl bound to the rank's GPU, barrier, all-reduce of the packed
     (ll, grad) block resp. all-gather of the ll shards on the bench stream, MAX over ranks, per-rank gather) executes
@@ -225,8 +266,8 @@ def test_bench_multi_rank_path_on_rccl_one_rank():
     for shard in ('time', 'neurons'):
         env = dict(os.environ, MASTER_ADDR='127.0.0.1', MASTER_PORT=str(_free_port()))
         r = subprocess.run([sys.executable, 'bench.py', '--rccl-selftest', '--shard', shard, '--steps', '4', '--warmup', '1',
-                            '--seconds', '60', '--neurons', '64'], cwd=root, env=env, capture_output=True, text=True,
-                           timeout=400)
+                            '--seconds', '60', '--neurons', '64', '--full'], cwd=root, env=env, capture_output=True,
+                           text=True, timeout=400)
         assert r.returncode == 0, r.stderr[-2000:]
         rec = json.loads(r.stdout.strip().splitlines()[-1])
         assert rec['n_gpus'] == 1 and rec['steps'] == 4 and rec['value'] > 0
@@ -245,7 +286,8 @@ def test_bench_self_launches_its_ranks():
     env = dict((k, v) for k, v in os.environ.items()
                if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'))
     r = subprocess.run([sys.executable, 'bench.py', '--gpus', '2', '--debug-single-device', '--steps', '3', '--warmup', '1',
-                        '--seconds', '60', '--neurons', '64'], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+                        '--seconds', '60', '--neurons', '64', '--full'], cwd=root, env=env, capture_output=True, text=True,
+                       timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = json.loads(r.stdout.strip().splitlines()[-1])
     assert rec['n_gpus'] == 2 and rec['ranks'] == 2 and rec['steps'] == 3 and rec['value'] > 0
@@ -276,8 +318,8 @@ def test_bench_eight_ranks_uneven_neuron_shards_on_one_gpu():
                if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'))
     for extra in ([], ['--shard', 'neurons']):
         r = subprocess.run([sys.executable, 'bench.py', '--gpus', '8', '--debug-single-device', '--steps', '2', '--warmup', '1',
-                            '--seconds', '30', '--neurons', '100'] + extra, cwd=root, env=env, capture_output=True, text=True,
-                           timeout=900)
+                            '--seconds', '30', '--neurons', '100', '--full'] + extra, cwd=root, env=env,
+                           capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-3000:]
         rec = json.loads(r.stdout.strip().splitlines()[-1])
         assert rec['n_gpus'] == 8 and rec['ranks'] == 8 and rec['rccl_ranks'] == 0 and rec['value'] > 0

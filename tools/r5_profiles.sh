@@ -9,7 +9,7 @@ has() { [[ "$SEL" == *" $1 "* ]]; }
 if has bench; then
 echo "== bench under rocprofv3 (kernel trace + PMC passes), then the default line un-profiled"
 bash tools/profile_bench.sh r05 --no-stim > $R/profile_bench.log 2>&1; cp profiles/r05_* $R/ 2>/dev/null; tail -3 $R/profile_bench.log
-python3 bench.py 2>/dev/null | tail -1 > $R/r05_bench_default_line.json; cut -c1-600 $R/r05_bench_default_line.json
+python3 bench.py --full 2>/dev/null | tail -1 > $R/r05_bench_default_line.json; cut -c1-600 $R/r05_bench_default_line.json
 fi
 if has configs; then
 echo "== config table"
@@ -62,9 +62,9 @@ echo "== time shards and neuron shards on one GPU"
 fi
 if has ranks; then
 echo "== bench.py --gpus N starting its own ranks on the one GPU (gloo)"
-python3 bench.py --gpus 2 --debug-single-device --steps 10 --warmup 3 2>/dev/null | tail -1 | tee $R/r05_self_launch_two_ranks.json | cut -c1-300
-python3 bench.py --gpus 8 --debug-single-device --steps 4 --warmup 1 --neurons 100 --seconds 30 2>/dev/null | tail -1 | tee $R/r05_self_launch_eight_ranks_uneven.json | cut -c1-300
-for sh in time neurons; do python3 bench.py --rccl-selftest --shard $sh --steps 20 --warmup 3 2>/dev/null | tail -1; done | tee $R/r05_rccl_selftest.jsonl | cut -c1-300
+python3 bench.py --full --gpus 2 --debug-single-device --steps 10 --warmup 3 2>/dev/null | tail -1 | tee $R/r05_self_launch_two_ranks.json | cut -c1-300
+python3 bench.py --full --gpus 8 --debug-single-device --steps 4 --warmup 1 --neurons 100 --seconds 30 2>/dev/null | tail -1 | tee $R/r05_self_launch_eight_ranks_uneven.json | cut -c1-300
+for sh in time neurons; do python3 bench.py --full --rccl-selftest --shard $sh --steps 20 --warmup 3 2>/dev/null | tail -1; done | tee $R/r05_rccl_selftest.jsonl | cut -c1-300
 fi
 if has tests; then
 echo "== GPU test suite"

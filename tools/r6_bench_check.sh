@@ -1,7 +1,7 @@
 #!/bin/bash
 # bench.py: the default line and the two-rank code path on one GPU (gloo), summarised
 cd "$GRAFT_REPO_ROOT"; R=gpurun_out/r6; mkdir -p $R
-python3 bench.py --gpus 2 --debug-single-device --steps 10 --warmup 3 2>$R/bench_two_ranks.err | tail -1 > $R/bench_two_ranks.json
+python3 bench.py --full --gpus 2 --debug-single-device --steps 10 --warmup 3 2>$R/bench_two_ranks.err | tail -1 > $R/bench_two_ranks.json
 python3 - <<PY
 import json
 try:
@@ -10,7 +10,7 @@ try:
 except Exception as e:
     print("two ranks failed:", e); print(open("$R/bench_two_ranks.err").read()[-1500:])
 PY
-python3 bench.py 2>$R/bench_default.err | tail -1 > $R/bench_default.json
+python3 bench.py --full 2>$R/bench_default.err | tail -1 > $R/bench_default.json
 python3 - <<PY
 import json
 try:
