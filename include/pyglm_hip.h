@@ -78,6 +78,9 @@ typedef struct pgl_context* pgl_handle;
                                 * (doubles of update history per row that one workgroup walks; default 65536), else the split
                                 * form with the multi-workgroup history kernels; 0 = always split */
 
+#define PGL_OPT_RECORD_KERNELS 96 /* dev / test: 1 = every ll(+grad) evaluation and pgl_gibbs_prepare_all records the fused kernel
+                                   * instantiations it launches, in launch order (pgl_last_kernels); 0 (default) = off */
+
 /* Development switches (not part of the drop-in surface; results stay valid unless stated): 95 = 2 keeps the narrow post
  * blocks of a wide population off the one-image-buffer form of k_fused6 and the block-ring kernel k_fused8 (they run on
  * k_fused2); 97 = waves per block of
@@ -328,13 +331,21 @@ int pgl_timing_summary(pgl_handle h, int reset, int* n_launches, double* mean_fu
 int pgl_set_stream(pgl_handle h, void* stream);
 
 /* Dev / test: dry run of the kernel dispatch, no device needed -- the names (as in the code object) of the fused kernel
- * instantiations an evaluation of `count` neurons from n_lo of a population of this shape would launch, one per line.
+ * instantiations an evaluation of `count` neurons from n_lo of a population of this shape would launch, one per line in
+ * launch order (the evaluation's own launch sequence, enqueued on a context without a device; a kernel launched in the
+ * forward and again in the backward phase of the 3-phase path is listed twice).
  * stim: 0 none / dense stimulus columns, 1 separable by the tap-rate kernels, 2 separable at the frame rate (stimulus
  * current inside the fused forward where that form exists), 3 at the frame rate through the slab.  path: 0 ll+grad,
  * 1 ll only, 2 the forward launches of pgl_gibbs_prepare_all.  The reference has no counterpart (Theano picks its own
  * C implementations); tests hold every reachable instantiation to zero bytes of scratch. */
 int pgl_plan_kernels(int N, int B, int R, int Dstim, long long nT, int stim, int n_lo, int count, int path, int opt_kernel,
                      int opt_f32, char* out, int cap);
+
+/* The fused kernel instantiations the handle's last pgl_ll_grad / pgl_ll_grad_dev / pgl_ll_grad_list_dev /
+ * pgl_gibbs_prepare_all call launched, one per line in `out`, in launch order and in the format of pgl_plan_kernels
+ * (which enqueues the same launch sequence on a device-less context).  Needs PGL_OPT_RECORD_KERNELS = 1 on the handle
+ * (PGL_ERR_STATE otherwise).  Dev / test entry point: tests compare it with the dry run. */
+int pgl_last_kernels(pgl_handle h, char* out, int cap);
 
 /* Launch geometry and algorithmic work of the fused kernel for [n_lo,n_hi):
  * info[0]=blocks, [1]=threads/block, [2]=time chunks, [3]=k-tiles(16 rows),

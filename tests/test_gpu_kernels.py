@@ -98,6 +98,25 @@ def test_f32_feature_staging():
     _check(p, f32=True, ll_rtol=1e-8, g_rtol=1e-6)
 
 
+def test_two_pass_kernel_wide_stimulus_few_impulse_columns():
+    """Regression (dispatch sweep): pass 2 of the on-the-fly two-pass kernel (k_fused3, PGL_OPT_KERNEL = 3) staged every
+    stimulus column into its half-width tile, also the first C0 - Kimp ones that belong to pass 1.  With fewer impulse
+    columns than the first half holds and more stimulus columns than a half-tile row, those landed at negative offsets in
+    the previous row's high columns: the gradient of the later stimulus weights was off by tens of percent, ll exact."""
+    from theano_pyglm_amd import _lib
+    for N, B, kind in ((2, 1, 'exp'), (5, 5, 'explinear')):
+        p = H.Problem(N, 3000, H.std_ibasis()[:, :B], kind=kind, Dstim=200, seed=40 + N, weighted=True, w_scale=0.02)
+        assert _lib.plan_kernels(N, B=B, R=200, Dstim=200, nT=3000, opt_kernel=3)[0].startswith('k_fused3<')
+        dev = p.device()
+        dev.set_option(_lib.OPT_KERNEL, 3)
+        ll, g = dev.ll_grad(p.theta, p.Weff)
+        ll0, g0 = p.oracle_ll_grad()
+        assert np.allclose(ll, ll0, rtol=LL_RTOL, atol=0), (N, ll, ll0)
+        assert H.rel_err(g[:, 1:201], g0[:, 1:201]) < G_RTOL, (N, H.rel_err(g[:, 1:201], g0[:, 1:201]))
+        assert H.rel_err(g, g0) < G_RTOL
+        dev.close()
+
+
 def test_high_rate_overflows_staging():
     """> 16 events per neuron per window: the global-memory fallback of the event staging."""
     p = H.Problem(8, 1500, H.std_ibasis(), seed=10, rate_hz=400.0, bias_mu=3.0, w_scale=0.05)

@@ -22,6 +22,7 @@ OPT_GIBBS_KERNEL = 4
 OPT_EPI_F64 = 5
 OPT_TIMING = 6
 OPT_BFGS_MERGE = 7
+OPT_RECORD_KERNELS = 96             # dev / test: DeviceGlm.last_kernels() lists the fused launches of the last evaluation
 
 # every symbol include/pyglm_hip.h declares (tests check the .so exports all of them)
 SYMBOLS = [
@@ -33,7 +34,7 @@ SYMBOLS = [
     'pgl_timing_summary', 'pgl_set_stream',
     'pgl_set_stimulus_separable', 'pgl_ll_grad_list_dev', 'pgl_gibbs_prepare_all', 'pgl_gibbs_ll_cols', 'pgl_gibbs_update_cols', 'pgl_gibbs_currents',
     'pgl_bfgs_state_doubles', 'pgl_bfgs_init_dev', 'pgl_bfgs_trial_dev', 'pgl_bfgs_objective_dev',
-    'pgl_bfgs_linesearch_dev', 'pgl_bfgs_hmul_dev', 'pgl_bfgs_hmul_hist_dev', 'pgl_bfgs_update_dev', 'pgl_bfgs_step_dev', 'pgl_plan_kernels', 'pgl_leading_singular_pairs',
+    'pgl_bfgs_linesearch_dev', 'pgl_bfgs_hmul_dev', 'pgl_bfgs_hmul_hist_dev', 'pgl_bfgs_update_dev', 'pgl_bfgs_step_dev', 'pgl_plan_kernels', 'pgl_last_kernels', 'pgl_leading_singular_pairs',
 ]
 
 
@@ -149,6 +150,8 @@ def load():
     if hasattr(lib, 'pgl_plan_kernels'):
         lib.pgl_plan_kernels.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_char_p, C.c_int]
+    if hasattr(lib, 'pgl_last_kernels'):
+        lib.pgl_last_kernels.argtypes = [vp, C.c_char_p, C.c_int]
     lib.pgl_simulate.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_double, vp, vp, vp,
                                  C.c_int64, C.c_uint64, vp, vp]
     for name in SYMBOLS:
@@ -407,6 +410,13 @@ class DeviceGlm(object):
         a, b = C.c_double(), C.c_double()
         _chk(self.lib.pgl_last_timing(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def last_kernels(self):
+        """The fused kernel instantiations the last ll_grad / gibbs_prepare_all call launched, in launch order, as
+        plan_kernels names them (pgl_last_kernels); needs set_option(OPT_RECORD_KERNELS, 1)."""
+        buf = C.create_string_buffer(16384)
+        _chk(self.lib.pgl_last_kernels(self.h, buf, 16384))
+        return [ln for ln in buf.value.decode().splitlines() if ln]
 
     def timing_summary(self, reset=True):
         """(n_launches, mean fused-kernel ms, mean whole-call ms) since the last reset."""

@@ -19,6 +19,12 @@ static int fail(int code, const std::string& msg)
     g_err = msg;
     return code;
 }
+// Names of the fused kernel instantiations an evaluation launches, as the code object's demangled symbol reads (dry_record):
+//  g_dry -- dry run of the dispatch (pgl_plan_kernels): the evaluation is enqueued on a context without a device, the
+//           launch_* templates record what they would launch and launch nothing, every other device operation is skipped;
+//  g_rec -- PGL_OPT_RECORD_KERNELS: a real evaluation records what it launches (pgl_last_kernels).
+static thread_local std::vector<std::string>* g_dry = nullptr;
+static thread_local std::vector<std::string>* g_rec = nullptr;
 #define HIPCHK(expr)                                                                         \
     do {                                                                                     \
         hipError_t e_ = (expr);                                                              \
@@ -94,6 +100,8 @@ struct pgl_context {
     size_t pin_args_cap = 0;
     int opt_f32 = 0, opt_nchunks = 0, opt_dbg = 0, opt_kernel = 0, opt_ptw = 0, opt_gibbs = 0, opt_finw = 0, opt_sb6 = 0, opt_epi64 = 0, opt_timing = 1, opt_slice_cols = 0, opt_hlp = 0, opt_pbmajor = 0;
     int opt_img32 = 0;                   // PGL_OPT_FEATURE_F32 = 2: f32 resident blocks for the narrow-shard kernel (k_fused8<.., 1>)
+    int opt_record = 0;                  // PGL_OPT_RECORD_KERNELS: last_kernels holds the fused launches of the last evaluation
+    std::vector<std::string> last_kernels;
     long long call_no = 0;               // evaluations enqueued since the last pgl_set_option(PGL_OPT_TIMING)
     int64_t t_lo = 0, t_hi = 0;          // evaluated time range [t_lo, t_hi) (pgl_set_time_range)
     bool timing_valid = false;
@@ -107,6 +115,7 @@ struct pgl_context {
 
 static int ensure(DevBuf& b, size_t bytes)
 {
+    if (g_dry) return PGL_OK;
     if (bytes <= b.cap && b.p) return PGL_OK;
     if (b.p) (void)hipFree(b.p);
     b.p = nullptr;
@@ -508,11 +517,12 @@ static int make_plan(const pgl_context* h, int n_lo, int n_hi, const Slice& sl, 
 // Dry run of the dispatch (pgl_plan_kernels): when g_dry is set the launch_* templates record the name of the kernel
 // instantiation they would launch (as the code object's demangled symbol reads) and launch nothing.  The recorded set
 // over a grid of shapes is the set of instantiations the dispatcher can reach: tests/test_capi_symbols.py holds every
-// one of them to zero bytes of scratch, tools/reachable_kernels.py diffs it against the built library.
-static thread_local std::vector<std::string>* g_dry = nullptr;
+// one of them to zero bytes of scratch, tools/reachable_kernels.py diffs it against the built library.  When g_rec is set
+// instead (a real evaluation with PGL_OPT_RECORD_KERNELS), the name is recorded the same way and the launch goes ahead:
+// returns true when the caller must NOT launch.
 static bool dry_record(const char* fam, std::initializer_list<int> args, const char* tail = nullptr)
 {
-    if (!g_dry) return false;
+    if (!g_dry && !g_rec) return false;
     std::string n = std::string(fam) + "<";
     bool first = true;
     for (int a : args) {
@@ -522,8 +532,8 @@ static bool dry_record(const char* fam, std::initializer_list<int> args, const c
     }
     if (tail) n += std::string(", ") + tail;
     n += ">";
-    g_dry->push_back(n);
-    return true;
+    (g_dry ? g_dry : g_rec)->push_back(n);
+    return g_dry != nullptr;
 }
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) costs several microseconds of host time: it is issued once per
@@ -575,10 +585,10 @@ static hipError_t launch_fused2_k(const Plan& pl, const FusedParams& fp, hipStre
 template <int KTH>
 static hipError_t launch_fused3_t(const Plan& pl, const FusedParams& fp, hipStream_t s)
 {
-    if (g_dry) {
+    if (g_dry || g_rec) {
         dry_record("k_fused3", {KTH, PGL_CAP, 1});
         if (fp.want_grad) dry_record("k_fused3", {KTH, PGL_CAP, 2});
-        return hipSuccess;
+        if (g_dry) return hipSuccess;
     }
     auto k1 = k_fused3<KTH, PGL_CAP, 1>;
     auto k2 = k_fused3<KTH, PGL_CAP, 2>;
@@ -611,10 +621,10 @@ static hipError_t launch_fused3(const Plan& pl, const FusedParams& fp, hipStream
 template <int KTL, int KTH, int XIN = 0, int HLP = 0>
 static hipError_t launch_fused5_t(const Plan& pl, const FusedParams& fp, hipStream_t s, int pass)
 {
-    if (g_dry) {
+    if (g_dry || g_rec) {
         if (pass != 2) dry_record("k_fused5", {KTL, KTH, 1, XIN, 0, HLP});
         if (pass != 1 && fp.want_grad) dry_record("k_fused5", {KTL, KTH, 2, 0, 0, HLP});
-        return hipSuccess;
+        if (g_dry) return hipSuccess;
     }
     auto k1 = k_fused5<KTL, KTH, 1, XIN, 0, HLP>;
     auto k2 = k_fused5<KTL, KTH, 2, 0, 0, HLP>;
@@ -683,11 +693,11 @@ template <int KTL, int KTH, int HLP = 0>
 static hipError_t launch_fused5_wide_t(const Plan& pl, const FusedParams& fp, hipStream_t s, int mode)
 {
     const size_t lds2h = (size_t)2 * pgl_img_bytes(KTH) + 256, lds2l = (size_t)2 * pgl_img_bytes(KTL) + 256;
-    if (g_dry) {
+    if (g_dry || g_rec) {
         if (mode <= 1) dry_record("k_fused5", {KTL, KTH, 1, mode == 0 ? 2 : 3, 0, HLP});
         else if (mode == 2) dry_record("k_fused5", {KTL, KTH, 1, 1, 0, HLP});
         else dry_record("k_fused5", {KTL, KTH, 2, 0, mode == 4 ? 1 : 0, HLP});
-        return hipSuccess;
+        if (g_dry) return hipSuccess;
     }
     hipError_t e = hipSuccess;
     if (mode == 0) {
@@ -828,6 +838,10 @@ static hipError_t launch_fused6(const Plan& pl, const FusedParams& fp, hipStream
 // workgroups per CU of the k_fused6 instantiation a plan selects (registers and LDS), cached per shape
 static int fused6_wg_per_cu(const Plan& pl)
 {
+    // dry run (pgl_plan_kernels): no device to ask -- the default, and neither read nor written to the cache, so that the
+    // answer does not depend on what real evaluations of this process have cached.  (Occupancy sets the number of time
+    // chunks only, never which instantiation a plan launches: the dry run's names hold on any device.)
+    if (g_dry) return (pl.nw6 == 4) ? 2 : 1;
     // occupancy is a property of the kernel and the architecture (every device of a node is the same gfx950 part)
     static int cache[2][11][5][3][9];          // [sb6][KTW][PTW][mt][nw6]; 0 = not asked yet
     static std::mutex mu;
@@ -1088,6 +1102,7 @@ int pgl_set_option(pgl_handle h, int option, int value)
     case 93: h->opt_slice_cols = value; return PGL_OK;      // dev: feature columns per slice of the 3-phase path (0 = 640)
     case 94: h->opt_sepf = value; return PGL_OK;            // dev: 2 = separable stimulus always by the tap-rate kernels, 3 = stimulus current through the slab, 4 = residual slab + k_sepf_bwd (no fused backward)
     case 95: h->opt_sb6 = value; return PGL_OK;              // dev: 2 = never the one-buffer / block-ring forms
+    case PGL_OPT_RECORD_KERNELS: h->opt_record = value ? 1 : 0; h->last_kernels.clear(); return PGL_OK;
     case PGL_OPT_KERNEL: h->opt_kernel = value; return PGL_OK;
     case PGL_OPT_GIBBS_KERNEL: h->opt_gibbs = value; return PGL_OK;
     case PGL_OPT_EPI_F64: h->opt_epi64 = value ? 1 : 0; return PGL_OK;
@@ -1472,6 +1487,7 @@ int pgl_set_stimulus_separable(pgl_handle h, const double* stim, int64_t Tstim, 
 static int sep_forward(pgl_handle h, const double* d_theta, int npost, double* X, int xs, int64_t t_lo, int64_t t_hi,
                        SepParams& sp)
 {
+    if (g_dry) return PGL_OK;                     // (dry run of the dispatch: no device)
     const int P = 1 + h->Dstim + h->Kimp;
     ENSURE(h->Yf, (size_t)npost * h->sepT * 8);
     int rc = launch_gemm_nt(h, d_theta + 1 + h->sepBt, P, (const double*)h->zf.p, h->sepBx, (double*)h->Yf.p,
@@ -1492,6 +1508,7 @@ static int sep_forward(pgl_handle h, const double* d_theta, int npost, double* X
 // w_x columns of d_grad
 static int sep_backward(pgl_handle h, const SepParams& sp, double* d_grad)
 {
+    if (g_dry) return PGL_OK;                     // (dry run of the dispatch: no device)
     const int npost = sp.npost, Rt = h->sepRt;
     const int nblk = (int)((sp.t_hi - sp.t_lo + PGL_SEP_TB - 1) / PGL_SEP_TB);
     ENSURE(h->spart, (size_t)nblk * npost * Rt * 8);
@@ -1544,6 +1561,7 @@ static int launch_sepf_any(pgl_handle h, int which, const SepfParams& sp)
 // npost rows of d_theta on the plan's tile range
 static int sepf_forward(pgl_handle h, const Plan& pl, const double* d_theta, SepfParams& sp, bool fused_fwd)
 {
+    if (g_dry) return PGL_OK;                     // (dry run of the dispatch: no device)
     const int P = 1 + h->Dstim + h->Kimp, ldy = pl.nPT * 16;
     ENSURE(h->YfT, (size_t)h->sepT * ldy * 8);
     // z_n[f] = (stim . basis_x)[f, :] . w_x[n]  ->  YfT[f][n]
@@ -1575,6 +1593,7 @@ static int sepf_forward(pgl_handle h, const Plan& pl, const double* d_theta, Sep
 // blocks of k_finalize sum
 static int sepf_backward(pgl_handle h, SepfParams& sp, double* d_grad, bool fused_bwd = false, int* nwt = nullptr)
 {
+    if (g_dry) return PGL_OK;                     // (dry run of the dispatch: no device)
     const long long nF = sp.F1 - sp.F0 + 1;
     ENSURE(h->QvT, (size_t)h->sepT * sp.ldy * 8);
     int rc = PGL_OK;
@@ -1772,6 +1791,7 @@ static bool plan_reads_theta(const Plan& pl)
 static int launch_prep(pgl_handle h, const Plan& pl, const Slice& sl, int n_lo, const double* d_theta,
                        const double* d_Weff)
 {
+    if (g_dry) return PGL_OK;                     // (dry run of the dispatch: no device)
     ENSURE(h->Wfrag, (size_t)pl.nPT * pl.KS * 64 * 8);
     ENSURE(h->bias, (size_t)pl.nPT * 16 * 8);
     const long long total = (long long)pl.nPT * pl.KS * 64;
@@ -1789,6 +1809,7 @@ static int launch_finalize_grad(pgl_handle h, const Plan& pl, const Slice& sl, i
                                 int kt0 = 0, int nkt = -1, hipStream_t stream = nullptr,
                                 const double* wtpart = nullptr, int nwt = 0, int ldy = 0)
 {
+    if (g_dry) return PGL_OK;                     // (dry run of the dispatch: no device)
     if (nkt < 0) nkt = pl.KT;
     if (!stream) stream = h->stream;
     const long long nfrag = (long long)pl.nPT * nkt * 256;
@@ -1822,6 +1843,7 @@ static hipError_t launch_any(const Plan& pl, const FusedParams& fp, hipStream_t 
 static int ensure_feature_images(pgl_handle h, int ktl, int kth, int tile0, int ntiles, const Slice* sl = nullptr,
                                  int slice_no = 0, int blk = 0)
 {
+    if (g_dry) return PGL_OK;                     // (dry run of the dispatch: no device)
     // kth == 0: one image per tile holding all ktl k-tiles (k_fused6; blk: as 2 KB blocks, k_fused8); else the L / H pair
     // of k_fused5.  sl: the images of ONE column slice of a wide population (key carries the slice number)
     const int key = (sl ? (slice_no + 1) << 16 : 0) | (blk ? img_key6(ktl, blk) : ktl << 8 | kth);
@@ -1930,14 +1952,33 @@ static int select_plans(const pgl_context* h, int n_lo, int n_hi, std::vector<Sl
     return PGL_OK;
 }
 
+// PGL_OPT_RECORD_KERNELS: the fused launches of one evaluation go to h->last_kernels while this lives
+struct KernelRecord {
+    explicit KernelRecord(pgl_context* h)
+    {
+        if (h->opt_record && !g_dry) {
+            h->last_kernels.clear();
+            g_rec = &h->last_kernels;
+        }
+    }
+    ~KernelRecord() { g_rec = nullptr; }
+};
+
 // Enqueue one evaluation on the handle's stream.  All pointers are device pointers.
 //  * one slice (N <= 128 and N*B + Dstim <= 640): prep + fused kernel + finalize;
 //  * otherwise the 3-phase path: per slice a forward-only launch accumulating the currents in
 //    Xbuf (nT x 16*nPT doubles), one elementwise pass Xbuf -> (ll, r), per slice a backward-only
 //    launch.  Same kernels, the F tile is simply generated twice per slice.
+// RULE: pgl_plan_kernels runs this function (and enqueue_gibbs_forward) with g_dry set on a context that has no device,
+// no stream and null buffers -- also inside processes that do have a GPU.  Every device operation on these paths must
+// therefore be skipped under g_dry: the launch_* templates record and return, ensure() allocates nothing, the helpers
+// (launch_prep, ensure_feature_images, launch_finalize_grad, sep_* / sepf_*) return at their top, and the few direct
+// launches / memsets here test g_dry themselves.  A device call added here needs the same guard.
+
 static int enqueue_ll_grad(pgl_handle h, int n_lo, int n_hi, const double* d_theta,
                            const double* d_Weff, double* d_ll, double* d_grad)
 {
+    KernelRecord record(h);
     std::vector<Slice> slices;
     std::vector<Plan> plans;
     bool sepf = false, sliced = false, wide = false;
@@ -1973,7 +2014,7 @@ static int enqueue_ll_grad(pgl_handle h, int n_lo, int n_hi, const double* d_the
                                : ensure_feature_images(h, pl.KT, 0, pl.tile0, pl.nTiles, nullptr, 0, (pl.version == 6 && pl.sb6 == 2) ? 1 + pl.img32 : 0);
         if (rc) return rc;
         if (rec) HIPCHK(hipEventRecord(h->ev[1], h->stream));
-        SepfParams sp;
+        SepfParams sp{};
         // up to four post tiles with the (5, 3) table: the stimulus current rides in the forward contraction
         // (beyond 13 k-tiles the five extra k-steps do not fit the registers: k_fused7<16, 4, 2> spills -- slab form there)
         const bool fused_fwd = pl.version == 7 && pl.KT <= 13 && h->sepA_ok && h->opt_sepf != 3;
@@ -1982,7 +2023,7 @@ static int enqueue_ll_grad(pgl_handle h, int n_lo, int n_hi, const double* d_the
         const bool fused_bwd = fused_fwd && d_grad && pl.KT <= 12 && h->opt_sepf != 4;
         rc = sepf_forward(h, pl, d_theta, sp, fused_fwd);
         if (rc) return rc;
-        if (fused_bwd) {
+        if (fused_bwd && !g_dry) {
             // pieces of the stimulus backward: one per frame base and chunk that holds tiles of it
             const long long q = h->sepq, M = h->sepM;
             const long long tE = (long long)pl.tile0 + pl.nTiles - 1;
@@ -2026,10 +2067,12 @@ static int enqueue_ll_grad(pgl_handle h, int n_lo, int n_hi, const double* d_the
             if (rc) return rc;
         } else {
             if (rec) HIPCHK(hipEventRecord(h->ev[2], h->stream));
-            hipLaunchKernelGGL(k_finalize_ll, dim3(pl.npost), dim3(256), 0, h->stream,
-                               (const double*)h->llpart.p, (const double*)h->gbpart.p, d_ll, d_grad, P,
-                               pl.npost, pl.nPT, pl.nChunks, pl.KSPLIT);
-            HIPCHK(hipGetLastError());
+            if (!g_dry) {
+                hipLaunchKernelGGL(k_finalize_ll, dim3(pl.npost), dim3(256), 0, h->stream,
+                                   (const double*)h->llpart.p, (const double*)h->gbpart.p, d_ll, d_grad, P,
+                                   pl.npost, pl.nPT, pl.nChunks, pl.KSPLIT);
+                HIPCHK(hipGetLastError());
+            }
         }
     } else if (!sliced) {
         const Plan& pl = plans[0];
@@ -2041,7 +2084,7 @@ static int enqueue_ll_grad(pgl_handle h, int n_lo, int n_hi, const double* d_the
             const bool fresh = need > h->Xbuf.cap || !h->Xbuf.p;
             ENSURE(h->Xbuf, need);
             // first touch of a fresh allocation costs ~8 % of an evaluation: pay it here, once
-            if (fresh) HIPCHK(hipMemsetAsync(h->Xbuf.p, 0, need, h->stream));
+            if (fresh && !g_dry) HIPCHK(hipMemsetAsync(h->Xbuf.p, 0, need, h->stream));
         }
         if (pl.version == 5) {
             rc = ensure_feature_images(h, pl.ktl, pl.kth, pl.tile0, pl.nTiles);
@@ -2082,10 +2125,12 @@ static int enqueue_ll_grad(pgl_handle h, int n_lo, int n_hi, const double* d_the
             rc = launch_finalize_grad(h, pl, slices[0], n_lo, d_Weff, d_ll, d_grad, true);
             if (rc) return rc;
         } else {
-            hipLaunchKernelGGL(k_finalize_ll, dim3(pl.npost), dim3(256), 0, h->stream,
-                               (const double*)h->llpart.p, (const double*)h->gbpart.p, d_ll, d_grad, P,
-                               pl.npost, pl.nPT, pl.nChunks, pl.KSPLIT);
-            HIPCHK(hipGetLastError());
+            if (!g_dry) {
+                hipLaunchKernelGGL(k_finalize_ll, dim3(pl.npost), dim3(256), 0, h->stream,
+                                   (const double*)h->llpart.p, (const double*)h->gbpart.p, d_ll, d_grad, P,
+                                   pl.npost, pl.nPT, pl.nChunks, pl.KSPLIT);
+                HIPCHK(hipGetLastError());
+            }
         }
     } else if (wide) {
         // a wide population on resident tiles: one image set, one set of Wmat fragments and up to three launches of the two-pass
@@ -2128,10 +2173,12 @@ static int enqueue_ll_grad(pgl_handle h, int n_lo, int n_hi, const double* d_the
             }
         } else {
             const Plan& pl = plans[S - 1];
-            hipLaunchKernelGGL(k_finalize_ll, dim3(pl.npost), dim3(256), 0, h->stream,
-                               (const double*)h->llpart.p, (const double*)h->gbpart.p, d_ll, d_grad, P,
-                               pl.npost, pl.nPT, pl.nChunks, pl.KSPLIT);
-            HIPCHK(hipGetLastError());
+            if (!g_dry) {
+                hipLaunchKernelGGL(k_finalize_ll, dim3(pl.npost), dim3(256), 0, h->stream,
+                                   (const double*)h->llpart.p, (const double*)h->gbpart.p, d_ll, d_grad, P,
+                                   pl.npost, pl.nPT, pl.nChunks, pl.KSPLIT);
+                HIPCHK(hipGetLastError());
+            }
         }
         if (rec) HIPCHK(hipEventRecord(h->ev[2], h->stream));
     } else {
@@ -2140,7 +2187,7 @@ static int enqueue_ll_grad(pgl_handle h, int n_lo, int n_hi, const double* d_the
         const long long row0 = (long long)p0.tile0 * 16;
         const long long row1 = std::min<long long>(h->nT, (long long)(p0.tile0 + p0.nTiles) * 16);
         ENSURE(h->Xbuf, (size_t)h->nT * xs * 8);
-        HIPCHK(hipMemsetAsync((double*)h->Xbuf.p + row0 * xs, 0, (size_t)(row1 - row0) * xs * 8, h->stream));
+        if (!g_dry) HIPCHK(hipMemsetAsync((double*)h->Xbuf.p + row0 * xs, 0, (size_t)(row1 - row0) * xs * 8, h->stream));
         if (rec) HIPCHK(hipEventRecord(h->ev[1], h->stream));
         SepParams sp;
         if (h->sep) {                                          // phase 0: X = I_stim (separable stimulus)
@@ -2156,7 +2203,7 @@ static int enqueue_ll_grad(pgl_handle h, int n_lo, int n_hi, const double* d_the
             hipError_t e = launch_any(plans[i], fp, h->stream);
             if (e != hipSuccess) return fail(PGL_ERR_HIP, std::string("forward launch: ") + hipGetErrorString(e));
         }
-        {                                                      // phase 2: X -> (ll, r)
+        if (!g_dry) {                                          // phase 2: X -> (ll, r)
             const int rows = 512;
             const long long nrows = h->t_hi - h->t_lo;
             const int nblk = (int)((nrows + rows - 1) / rows);
@@ -2485,6 +2532,19 @@ int pgl_set_stream(pgl_handle h, void* stream)
     return PGL_OK;
 }
 
+static int enqueue_gibbs_forward(pgl_handle h);
+
+int pgl_last_kernels(pgl_handle h, char* out, int cap)
+{
+    if (!h || !out || cap <= 0) return fail(PGL_ERR_ARG, "null argument");
+    if (!h->opt_record) return fail(PGL_ERR_STATE, "kernel recording is off (PGL_OPT_RECORD_KERNELS)");
+    std::string all;
+    for (const std::string& n : h->last_kernels) all += n + "\n";
+    if ((int)all.size() + 1 > cap) return fail(PGL_ERR_ARG, "output buffer too small");
+    std::memcpy(out, all.c_str(), all.size() + 1);
+    return PGL_OK;
+}
+
 // Dry run of the dispatch, no device needed: the fused kernel instantiations (names as in the code object) that an
 // ll(+grad) evaluation of `count` neurons starting at n_lo -- a range, or a list -- of a population of this shape would
 // launch, one per line in `out`.  stim: 0 none / dense stimulus columns (Dstim of them), 1 separable stimulus by the
@@ -2502,61 +2562,17 @@ int pgl_plan_kernels(int N, int B, int R, int Dstim, long long nT, int stim, int
     c.sep = stim >= 1; c.sepf = stim >= 2; c.sepA_ok = stim == 2; c.opt_sepf = 0;
     c.Ktot = c.Kimp + (c.sep ? 0 : Dstim);
     c.opt_kernel = opt_kernel; c.opt_f32 = (opt_f32 == 1) ? 1 : 0; c.opt_img32 = (opt_f32 == 2) ? 1 : 0;
+    c.opt_timing = 0;
+    // the evaluation itself, enqueued on the device-less context: the launch sequence is the one a real call takes
     std::vector<std::string> names;
+    double dummy = 0;
     g_dry = &names;
-    int rc = PGL_OK;
-    hipError_t e = hipSuccess;
-    FusedParams fp{};
-    std::vector<Slice> slices = make_slices(&c);
-    std::vector<Plan> plans;
-    if (path == 2) {
-        plans.assign(slices.size(), Plan());
-        for (size_t i = 0; i < slices.size() && rc == PGL_OK; ++i) {
-            rc = make_plan(&c, 0, N, slices[i], plans[i], false);
-            if (rc == PGL_OK) e = launch_any(plans[i], fp, nullptr);
-        }
-    } else {
-        const bool grad = path == 0;
-        fp.want_grad = grad;
-        bool sepf = false, sliced = false, wide = false;
-        rc = select_plans(&c, n_lo, n_lo + count, slices, plans, sepf, sliced, &wide);
-        if (rc == PGL_OK) {
-            const Plan& pl = plans[0];
-            if (wide) {
-                const size_t S = slices.size();
-                for (size_t i = 0; i < S && e == hipSuccess; ++i) {
-                    e = launch_fused5_wide(plans[i], fp, nullptr, i + 1 == S ? 2 : (i == 0 ? 0 : 1));
-                    if (e == hipSuccess && i + 1 == S && grad) e = launch_fused5_wide(plans[i], fp, nullptr, 3);
-                }
-                for (size_t i = 0; i + 1 < S && e == hipSuccess && grad; ++i) {
-                    e = launch_fused5_wide(plans[i], fp, nullptr, 4);
-                    if (e == hipSuccess) e = launch_fused5_wide(plans[i], fp, nullptr, 3);
-                }
-            } else if (sepf) {
-                if (pl.version == 5) {
-                    e = launch_fused5_xin(pl, fp, nullptr, 1);
-                    if (e == hipSuccess && grad) e = launch_fused5_xin(pl, fp, nullptr, 2);
-                } else {
-                    {
-                        const bool ff = pl.KT <= 13 && c.sepA_ok && c.opt_sepf != 3;
-                        e = launch_fused7_xio(pl, fp, nullptr, (ff && grad && pl.KT <= 12) ? 3 : (ff ? 2 : 1));
-                    }
-                }
-            } else if (!sliced) {
-                if (pl.version == 5 && grad) {
-                    e = launch_fused5(pl, fp, nullptr, 1);
-                    if (e == hipSuccess) e = launch_fused5(pl, fp, nullptr, 2);
-                } else {
-                    e = launch_any(pl, fp, nullptr);
-                }
-            } else {
-                for (size_t i = 0; i < slices.size() && e == hipSuccess; ++i) e = launch_any(plans[i], fp, nullptr);
-            }
-        }
-    }
+    const int rc = (path == 2) ? enqueue_gibbs_forward(&c)
+                               : enqueue_ll_grad(&c, n_lo, n_lo + count, nullptr, nullptr, &dummy, path == 0 ? &dummy : nullptr);
     g_dry = nullptr;
+    // (under g_dry nothing but a launch switch without a case for the plan fails with PGL_ERR_HIP)
+    if (rc == PGL_ERR_HIP) return fail(PGL_ERR_UNSUPPORTED, "no kernel instantiation for this plan");
     if (rc) return rc;
-    if (e != hipSuccess) return fail(PGL_ERR_UNSUPPORTED, "no kernel instantiation for this plan");
     std::string all;
     for (const std::string& n : names) all += n + "\n";
     if ((int)all.size() + 1 > cap) return fail(PGL_ERR_ARG, "output buffer too small");
@@ -2773,8 +2789,17 @@ int pgl_gibbs_prepare_all(pgl_handle h, const double* theta, const double* Weff)
     // the caller's (pageable) theta / Weff may be temporaries that die when this call returns: the uploads
     // must have left host memory by then, whatever the runtime does with pageable sources
     HIPCHK(hipStreamSynchronize(h->stream));
-    // forward-only launches of the K-split kernel: GX[t][n] = sum_slices F_s . W_s (stimulus columns
-    // included), the same phase 1 as the sliced ll+grad path
+    return enqueue_gibbs_forward(h);
+}
+
+// forward-only launches of the K-split kernel: GX[t][n] = sum_slices F_s . W_s (stimulus columns
+// included), the same phase 1 as the sliced ll+grad path; theta / Weff already in h->gtheta / h->Weff.
+// The dry run of the dispatch runs this too: the RULE above enqueue_ll_grad holds here.
+static int enqueue_gibbs_forward(pgl_handle h)
+{
+    KernelRecord record(h);
+    const int N = h->N;
+    int rc = PGL_OK;
     const std::vector<Slice> slices = make_slices(h);
     std::vector<Plan> plans(slices.size());
     size_t maxLL = 0;
@@ -2789,7 +2814,7 @@ int pgl_gibbs_prepare_all(pgl_handle h, const double* theta, const double* Weff)
     ENSURE(h->GX, (size_t)h->nT * xs * 8);
     const long long row0 = (long long)plans[0].tile0 * 16;
     const long long row1 = std::min<long long>(h->nT, (long long)(plans[0].tile0 + plans[0].nTiles) * 16);
-    HIPCHK(hipMemsetAsync((double*)h->GX.p + row0 * xs, 0, (size_t)(row1 - row0) * xs * 8, h->stream));
+    if (!g_dry) HIPCHK(hipMemsetAsync((double*)h->GX.p + row0 * xs, 0, (size_t)(row1 - row0) * xs * 8, h->stream));
     if (h->sep) {
         SepParams sp;
         rc = sep_forward(h, (const double*)h->gtheta.p, N, (double*)h->GX.p, xs, h->t_lo, h->t_hi, sp);

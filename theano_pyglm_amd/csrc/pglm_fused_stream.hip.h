@@ -773,10 +773,14 @@ __global__ __launch_bounds__(512, 2) void k_fused3(const FusedParams p)
 
     auto gen_half = [&](FT* Fdst, const int tile, const int cur) {
         const int t0 = tile * TT;
-        if (p.Dstim > 0) {
-            for (int id = tid; id < TT * p.Dstim; id += nthr) {
-                const int t = id / p.Dstim;
-                const int j = id % p.Dstim;
+        // the stimulus columns of this half only: with fewer than C0 impulse columns the first C0 - Kimp stimulus columns
+        // belong to pass 1 (written here they would land at negative offsets, in the previous row's high columns)
+        const int j0 = (C0 > p.Kimp) ? C0 - p.Kimp : 0;
+        const int nd = p.Dstim - j0;
+        if (nd > 0) {
+            for (int id = tid; id < TT * nd; id += nthr) {
+                const int t = id / nd;
+                const int j = j0 + id % nd;
                 const long long tg = (long long)t0 + t;
                 Fdst[t * rsfh + p.Kimp - C0 + j] = (tg < p.nT) ? p.fstim[tg * p.DsAll + p.ds0 + j] : 0.0;
             }
