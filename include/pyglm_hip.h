@@ -79,7 +79,8 @@ typedef struct pgl_context* pgl_handle;
                                 * form with the multi-workgroup history kernels; 0 = always split */
 
 #define PGL_OPT_RECORD_KERNELS 96 /* dev / test: 1 = every ll(+grad) evaluation and pgl_gibbs_prepare_all records the fused kernel
-                                   * instantiations it launches, in launch order (pgl_last_kernels); 0 (default) = off */
+                                   * instantiations it launches, in launch order (pgl_last_kernels), and so do pgl_hvp_prepare_* /
+                                   * pgl_hvp_apply_dev (k_hvp5 and the k_fused* launches around it); 0 (default) = off */
 
 /* Development switches (not part of the drop-in surface; results stay valid unless stated): 95 = 2 keeps the narrow post
  * blocks of a wide population off the one-image-buffer form of k_fused6 and the block-ring kernel k_fused8 (they run on
@@ -167,6 +168,35 @@ int pgl_ll_grad_dev(pgl_handle h, int n_lo, int n_hi, const double* d_theta,
 int pgl_ll_grad_list_dev(pgl_handle h, const int* d_idx, int count, const double* d_theta,
                          const double* d_Weff, double* d_ll, double* d_grad);
 int pgl_sync(pgl_handle h);
+
+/* Hessian-vector products of ll: hessian_rop_wrt_list (pyglm/utils/grads.py:68-95, T.Rop of the gradient) and the
+ * hessp that fmin_ncg takes in map.py:38-45.  With the feature row f_t = [1, fstim[t,:], Weff[n',n] fS[t,n',b]] and
+ * x_t = f_t . theta_n:
+ *     H_n . v = sum_t c_t f_t (f_t . v),    c_t = -dt lam''(x_t) + S[t,n] (log lam)''(x_t)
+ *     exp:        lam'' = e^x, (log lam)'' = 0
+ *     explinear:  lam'' = sig (1 - sig), (log lam)'' = sig (1 - sig) / lam - sig^2 / lam^2,  sig = 1 / (1 + e^-x)
+ * c depends on theta only, so the interface has two steps:
+ *   prepare: forward contraction with theta, c[t,n] of the listed rows over the handle's time range stays on the device
+ *            (all f64; nT * 16 ceil(rows / 16) doubles, the footprint of the residual slab).  Limits: exp -- x is
+ *            clamped at 709, c stays finite; explinear -- c -> 0 for x -> +inf and for x -> -inf (the limit of
+ *            (log lam)'' there, not the reference's 0/0 at lam == 0); a NaN current gives a NaN c.
+ *   apply:   hv = F^T . (c o (F . v)): rows as prepared, d_v (count, P) in, d_hv (count, P) out, both in the theta layout.
+ *            One forward contraction, one multiply per element, one backward contraction: 4 nT N^2 B flops and no
+ *            transcendental.  Calls of >= 65 neurons against one column slice run the fused kernel on resident feature
+ *            tiles (k_hvp5, then pass 2 of k_fused5; visible through pgl_last_kernels); every other population, range
+ *            or list runs the forward-only / backward-only launches of the 3-phase path around a row kernel.
+ * hv is H . v of ll itself: not negated, no prior.  The _dev forms are asynchronous on the handle's stream.
+ * pgl_set_time_range is honoured: the product is the partial sum over the range (all-reduce it like (ll, grad)).
+ * apply before prepare, after a changed time range or after new spikes / basis / stimulus: PGL_ERR_STATE.  A separable
+ * stimulus (pgl_set_stimulus_separable: the current is not linear in w_t, w_x) gives PGL_ERR_UNSUPPORTED.
+ * The handle keeps its own copy of Weff and of the neuron list between prepare and apply. */
+int pgl_hvp_prepare_dev(pgl_handle h, int n_lo, int n_hi, const double* d_theta, const double* d_Weff);
+int pgl_hvp_prepare_list_dev(pgl_handle h, const int* d_idx, int count, const double* d_theta, const double* d_Weff);
+int pgl_hvp_apply_dev(pgl_handle h, const double* d_v, double* d_hv);
+/* prepare + one apply with host pointers: theta, v, hv_out ((n_hi-n_lo), P), Weff (N,N).  A call that repeats the range,
+ * time range, theta and Weff of the previous pgl_hvp call (the products of one CG solve) skips the prepare. */
+int pgl_hvp(pgl_handle h, int n_lo, int n_hi, const double* theta, const double* v, const double* Weff, double* hv_out);
+
 /* The lock-step optimiser (inference/batched_bfgs.py) as row kernels on the handle's stream.  The reference calls
  * scipy.optimize.minimize(method="bfgs") neuron by neuron (coord_descent.py:161-204); these run the same algorithm --
  * BFGS from H = I, More'-Thuente strong-Wolfe line search with scipy's constants and first trial step

@@ -35,6 +35,7 @@ SYMBOLS = [
     'pgl_set_stimulus_separable', 'pgl_ll_grad_list_dev', 'pgl_gibbs_prepare_all', 'pgl_gibbs_ll_cols', 'pgl_gibbs_update_cols', 'pgl_gibbs_currents',
     'pgl_bfgs_state_doubles', 'pgl_bfgs_init_dev', 'pgl_bfgs_trial_dev', 'pgl_bfgs_objective_dev',
     'pgl_bfgs_linesearch_dev', 'pgl_bfgs_hmul_dev', 'pgl_bfgs_hmul_hist_dev', 'pgl_bfgs_update_dev', 'pgl_bfgs_step_dev', 'pgl_plan_kernels', 'pgl_last_kernels', 'pgl_leading_singular_pairs',
+    'pgl_hvp_prepare_dev', 'pgl_hvp_prepare_list_dev', 'pgl_hvp_apply_dev', 'pgl_hvp',
 ]
 
 
@@ -121,6 +122,11 @@ def load():
     lib.pgl_ll_grad_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.pgl_ll_grad_list_dev.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
     lib.pgl_sync.argtypes = [vp]
+    if hasattr(lib, 'pgl_hvp'):                               # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
+        lib.pgl_hvp_prepare_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp]
+        lib.pgl_hvp_prepare_list_dev.argtypes = [vp, vp, C.c_int, vp, vp]
+        lib.pgl_hvp_apply_dev.argtypes = [vp, vp, vp]
+        lib.pgl_hvp.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp]
     if hasattr(lib, 'pgl_bfgs_hmul_dev'):                     # (older dev A/B builds named by PYGLM_HIP_LIB lack it)
         lib.pgl_bfgs_state_doubles.argtypes = [C.c_int, C.c_int]
         lib.pgl_bfgs_init_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double]
@@ -354,6 +360,33 @@ class DeviceGlm(object):
         _chk(self.lib.pgl_ll_grad_list_dev(self.h, C.c_void_p(d_idx), int(count), C.c_void_p(d_theta),
                                            C.c_void_p(d_Weff), C.c_void_p(d_ll),
                                            C.c_void_p(d_grad) if d_grad else None))
+
+    # -- Hessian-vector products of ll (grads.py:68-95 hessian_rop_wrt_list) -------
+    def hvp_prepare(self, d_theta, d_Weff, n_lo=0, n_hi=None, d_idx=0, count=None):
+        """Curvature pass at theta (device pointers as integers; asynchronous): rows [n_lo, n_hi), or the `count` neurons
+        listed in d_idx (device int32 pointer).  The curvature stays on the device for hvp_apply."""
+        if d_idx:
+            _chk(self.lib.pgl_hvp_prepare_list_dev(self.h, C.c_void_p(d_idx), int(count), C.c_void_p(d_theta),
+                                                   C.c_void_p(d_Weff)))
+            return
+        n_hi = self.N if n_hi is None else n_hi
+        _chk(self.lib.pgl_hvp_prepare_dev(self.h, int(n_lo), int(n_hi), C.c_void_p(d_theta), C.c_void_p(d_Weff)))
+
+    def hvp_apply(self, d_v, d_hv):
+        """d_hv = H . d_v for the prepared rows, (rows, P) each, theta layout (device pointers; asynchronous)."""
+        _chk(self.lib.pgl_hvp_apply_dev(self.h, C.c_void_p(d_v), C.c_void_p(d_hv)))
+
+    def hvp(self, theta, v, Weff, n_lo=0, n_hi=None):
+        """H . v of ll for rows [n_lo, n_hi) with host arrays: theta, v (rows, P), Weff (N, N) -> (rows, P).  Repeated
+        calls with the same theta / Weff / range (a CG solve) reuse the curvature on the device."""
+        n_hi = self.N if n_hi is None else n_hi
+        npost = n_hi - n_lo
+        th = _f64(theta, (npost, self.P))
+        vv = _f64(v, (npost, self.P))
+        We = _f64(Weff, (self.N, self.N))
+        out = np.empty((npost, self.P))
+        _chk(self.lib.pgl_hvp(self.h, int(n_lo), int(n_hi), _ptr(th), _ptr(vv), _ptr(We), _ptr(out)))
+        return out
 
     # -- lock-step optimiser bookkeeping (device pointers as integers; asynchronous on the handle's stream) --
     def bfgs_state_doubles(self, M, P):

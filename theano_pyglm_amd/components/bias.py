@@ -38,6 +38,10 @@ class ConstantBias(Component):
     def grad_log_p(self, vars):
         return {'bias': np.array([-self._z(vars) / self.sig_bias])}
 
+    def hess_log_p_vec(self, vars, v):
+        """Hessian of log_p (bias.py:33) times v = {'bias': ..}: -v / sig_bias^2."""
+        return {'bias': -np.asarray(v['bias'], dtype=float).reshape(-1) / self.sig_bias ** 2}
+
     def get_state(self, vars=None):
         return {'bias': vars['bias']} if vars is not None else {}
 

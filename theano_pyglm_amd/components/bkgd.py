@@ -40,6 +40,9 @@ class NoStimulus(Component):
     def chain_grad(self, vars, g_flat):
         return {}
 
+    def hess_log_p_vec(self, vars, v):
+        return {}
+
     def preprocess_data(self, data):
         data['fstim'] = None
 
@@ -88,6 +91,10 @@ class BasisStimulus(Component):
 
     def grad_log_p(self, vars):
         return {'w_stim': -self.flat_weights(vars) / (0.01 ** 2)}
+
+    def hess_log_p_vec(self, vars, v):
+        """Hessian of log_p times v = {'w_stim': ..}: the constant diagonal -1/0.01^2."""
+        return {'w_stim': -np.asarray(v['w_stim'], dtype=float).reshape(-1) / (0.01 ** 2)}
 
     def get_state(self, vars=None):
         st = {'basis': self.ibasis}

@@ -85,6 +85,12 @@ class LinearBasisImpulses(_ImpulseBase):
         g = self.prior.grad_log_p(self.flat_weights(vars).reshape(self.N, self.B))
         return {'w_ir': np.asarray(g).reshape(-1)}
 
+    def hess_log_p_vec(self, vars, v):
+        """Hessian of log_p times v = {'w_ir': ..} (the prior's own product on the (N, B) groups)."""
+        hv = self.prior.hess_log_p_vec(self.flat_weights(vars).reshape(self.N, self.B),
+                                       np.asarray(v['w_ir'], dtype=float).reshape(self.N, self.B))
+        return {'w_ir': np.asarray(hv).reshape(-1)}
+
     def set_hyperparameters(self, model):
         if 'prior' in model:
             self.prior.set_hyperparameters(model['prior'])

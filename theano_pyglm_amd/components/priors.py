@@ -31,6 +31,10 @@ class Gaussian(Component):
     def grad_log_p(self, value):
         return -(np.asarray(value) - self.mu) / self.sigma ** 2
 
+    def hess_log_p_vec(self, value, v):
+        """Hessian of log_p times v: the constant diagonal -1/sigma^2."""
+        return -np.asarray(v, dtype=float) / self.sigma ** 2
+
     def set_hyperparameters(self, model):
         self.mu = model['mu']
         self.sigma = model['sigma']
@@ -59,6 +63,17 @@ class GroupLasso(Component):
         nrm = np.sqrt(np.sum(z ** 2, axis=1, keepdims=True))
         with np.errstate(invalid='ignore', divide='ignore'):
             return -self.lam * z / nrm / self.sigma
+
+    def hess_log_p_vec(self, value, v):
+        """The exact derivative of grad_log_p along v, per group (value, v: (groups, B)):
+        -lam/sigma^2 * (v/|z| - z (z.v)/|z|^3).  A zero group yields NaN like grad_log_p; callers zero a product
+        that holds one (the Newton-CG closure of coord_descent applies fit_glm's rule)."""
+        z = (np.asarray(value) - self.mu) / self.sigma
+        v = np.asarray(v, dtype=float)
+        nrm = np.sqrt(np.sum(z ** 2, axis=1, keepdims=True))
+        zv = np.sum(z * v, axis=1, keepdims=True)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            return -self.lam / self.sigma ** 2 * (v / nrm - z * zv / nrm ** 3)
 
     def set_hyperparameters(self, model):
         self.mu = model['mu']

@@ -111,6 +111,14 @@ struct pgl_context {
     double* flags_dev[4] = {nullptr, nullptr, nullptr, nullptr};
     int flags_next = 0;
     int opt_bfgs_merge = 65536;
+    // Hessian-vector products (pgl_hvp_prepare_* / pgl_hvp_apply_dev): the curvature c[t, n] of the prepared rows stays in
+    // Cbuf -- in the accumulator layout of the two-pass kernels' slab (hvp_fused) or as rows (nT, 16 * post tiles) -- with
+    // the handle's own copies of Weff and of the neuron list; hvp_ok falls with new spikes / basis / stimulus
+    bool hvp_ok = false, hvp_fused = false, hvp_list = false;
+    int hvp_n_lo = 0, hvp_count = 0;
+    int64_t hvp_t_lo = 0, hvp_t_hi = 0;
+    DevBuf Cbuf, hvp_idx, hvp_Weff, hvp_ll, hvp_v, hvp_out;
+    std::vector<double> hvp_host;        // pgl_hvp: theta and Weff of its last prepare (a CG solve repeats them: no new prepare)
 };
 
 static int ensure(DevBuf& b, size_t bytes)
@@ -140,6 +148,7 @@ static int find_img(const pgl_context* h, int key, int tile0, int ntiles)
 }
 static void invalidate_images(pgl_context* h)
 {
+    h->hvp_ok = false;                            // (new spikes / basis / stimulus: the prepared curvature is stale too)
     for (int i = 0; i < pgl_context::NIMG; ++i) h->imgs[i].key = 0;
 }
 // can a new image set of `want` bytes be placed (in a free slot, or over the least recently used one)?
@@ -747,6 +756,35 @@ static hipError_t launch_fused5_wide(const Plan& pl, const FusedParams& fp, hipS
     return hipErrorInvalidValue;
 }
 
+// fused apply / forward-only curvature pass of the Hessian-vector product on resident tiles (k_hvp5): the column pairs the
+// automatic dispatch gives a call of >= 65 neurons (pick_pair from 5 k-tiles on)
+template <int KTL, int KTH>
+static hipError_t launch_hvp5_t(const Plan& pl, const FusedParams& fp, const double* cslab, hipStream_t s, int fwo)
+{
+    if (dry_record("k_hvp5", {KTL, KTH, fwo})) return hipSuccess;
+    constexpr size_t lds = (size_t)2 * pgl_img_bytes(KTL) + pgl_img_bytes(KTH);
+    auto k0 = k_hvp5<KTL, KTH, 0>;
+    auto k1 = k_hvp5<KTL, KTH, 1>;
+    hipError_t e = ensure_dyn_lds(fwo ? k1 : k0, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(fwo ? k1 : k0, dim3(pl.blocks), dim3(512), lds, s, fp, cslab);
+    return hipGetLastError();
+}
+
+static hipError_t launch_hvp5(const Plan& pl, const FusedParams& fp, const double* cslab, hipStream_t s, int fwo)
+{
+    switch (pl.ktl << 8 | pl.kth) {
+    case 3 << 8 | 3: return launch_hvp5_t<3, 3>(pl, fp, cslab, s, fwo);
+    case 5 << 8 | 5: return launch_hvp5_t<5, 5>(pl, fp, cslab, s, fwo);
+    case 7 << 8 | 7: return launch_hvp5_t<7, 7>(pl, fp, cslab, s, fwo);
+    case 9 << 8 | 11: return launch_hvp5_t<9, 11>(pl, fp, cslab, s, fwo);
+    case 12 << 8 | 14: return launch_hvp5_t<12, 14>(pl, fp, cslab, s, fwo);
+    case 14 << 8 | 18: return launch_hvp5_t<14, 18>(pl, fp, cslab, s, fwo);
+    case PGL_SPLIT_L << 8 | (40 - PGL_SPLIT_L): return launch_hvp5_t<PGL_SPLIT_L, 40 - PGL_SPLIT_L>(pl, fp, cslab, s, fwo);
+    }
+    return hipErrorInvalidValue;
+}
+
 // Instantiations of the switch below that no plan of make_plan selects (tools/reachable_kernels.py: dry run of the
 // dispatch over a grid of shapes, with and without forcing options) are not built; tests/test_capi_symbols.py fails when a
 // reachable instantiation is missing from the library, so a change of make_plan shows up here.
@@ -1002,7 +1040,7 @@ static void launch_sepf(int which, const SepfParams& sp, hipStream_t s)
 extern "C" {
 
 const char* pgl_last_error(void) { return g_err.c_str(); }
-int pgl_version(void) { return 100; }
+int pgl_version(void) { return 101; }
 
 int pgl_device_count(void)
 {
@@ -1064,7 +1102,8 @@ int pgl_destroy(pgl_handle h)
                       &h->gbpart, &h->Xbuf, &h->imgs[0].buf, &h->imgs[1].buf, &h->imgs[2].buf, &h->imgs[3].buf, &h->imgs[4].buf, &h->imgs[5].buf, &h->imgs[6].buf, &h->imgs[7].buf, &h->IimpT, &h->Inet, &h->Istim, &h->tmpA, &h->tmpB, &h->tmpC,
                       &h->wsmall, &h->part, &h->outK, &h->lam, &h->wcol, &h->thetan, &h->GX, &h->gtheta,
                       &h->gargs, &h->gpart, &h->gout, &h->ghs, &h->gfs, &h->zf, &h->zfT, &h->sbt, &h->Yf, &h->Qb, &h->Qf,
-                      &h->spart, &h->sepC, &h->sepA, &h->sepAT, &h->sepD, &h->YfT, &h->Hb, &h->wpart, &h->QvT, &h->staA};
+                      &h->spart, &h->sepC, &h->sepA, &h->sepAT, &h->sepD, &h->YfT, &h->Hb, &h->wpart, &h->QvT, &h->staA,
+                      &h->Cbuf, &h->hvp_idx, &h->hvp_Weff, &h->hvp_ll, &h->hvp_v, &h->hvp_out};
     for (DevBuf* b : bufs) release(*b);
     for (int s = 0; s < pgl_context::NEV; ++s)
         for (int i = 0; i < 4; ++i)
@@ -2272,6 +2311,270 @@ int pgl_ll_grad_list_dev(pgl_handle h, const int* d_idx, int count, const double
     rc = enqueue_ll_grad(h, 0, count, d_theta, d_Weff, d_ll, d_grad);
     h->cur_pidx = nullptr;
     return rc;
+}
+
+// ---- Hessian-vector products of ll (hessian_rop_wrt_list, pyglm/utils/grads.py:68-95; the hessp of map.py:38-45) ----
+// The path of a product over the prepared rows: `fused` -- one column slice on the resident-tile two-pass plan (the class of
+// k_fused5: >= 5 post tiles, or >= 3 against a long row): k_hvp5 + pass 2 of k_fused5; else the 3-phase path on the
+// K-split kernel's forward-only / backward-only launches, one set per column slice, around the row kernels of
+// pglm_hvp.hip.h.  The g_dry RULE above enqueue_ll_grad holds on these paths too.
+static int hvp_select(const pgl_context* h, int n_lo, int n_hi, std::vector<Slice>& slices, std::vector<Plan>& plans, bool& fused)
+{
+    slices = make_slices(h);
+    plans.assign(slices.size(), Plan());
+    fused = slices.size() == 1 && !h->opt_f32 && (h->opt_kernel == 0 || h->opt_kernel == 4);
+    if (fused) {
+        int rc = make_plan(h, n_lo, n_hi, slices[0], plans[0], true);
+        if (rc) return rc;
+        fused = plans[0].version == 5 && plans[0].ktl >= 3;
+    }
+    for (size_t i = 0; i < slices.size() && !fused; ++i) {
+        int rc = make_plan(h, n_lo, n_hi, slices[i], plans[i], false);
+        if (rc) return rc;
+    }
+    return PGL_OK;
+}
+
+// theta -> c[t, n] of the rows [n_lo, n_hi) (or of the list h->cur_pidx) over the handle's time range, kept in h->Cbuf
+static int enqueue_hvp_prepare(pgl_handle h, int n_lo, int n_hi, const double* d_theta, const double* d_Weff)
+{
+    KernelRecord record(h);
+    std::vector<Slice> slices;
+    std::vector<Plan> plans;
+    bool fused = false;
+    int rc = hvp_select(h, n_lo, n_hi, slices, plans, fused);
+    if (rc) return rc;
+    // (the forward-only launches of the K-split kernel still write their -- unused -- ll partials)
+    size_t maxLL = 0;
+    for (const Plan& pl : plans) maxLL = std::max(maxLL, (size_t)pl.nChunks * pl.nPT * pl.KSPLIT * 64 * 8);
+    ENSURE(h->llpart, maxLL);
+    ENSURE(h->gbpart, maxLL);
+    const Plan& p0 = plans[0];
+    const int xs = p0.nPT * 16;
+    const long long row0 = (long long)p0.tile0 * 16;
+    long long total = 0;
+    double* cb = nullptr;
+    if (fused) {
+        total = (long long)p0.nTiles * p0.nPT * 256;
+        ENSURE(h->Cbuf, (size_t)total * 8);
+        cb = (double*)h->Cbuf.p;
+        rc = launch_prep(h, p0, slices[0], n_lo, d_theta, d_Weff);
+        if (rc) return rc;
+        rc = ensure_feature_images(h, p0.ktl, p0.kth, p0.tile0, p0.nTiles);
+        if (rc) return rc;
+        FusedParams fp;
+        fill_params(h, p0, slices[0], n_lo, false, 0, fp);
+        fp.Xbuf = cb;
+        hipError_t e = launch_hvp5(p0, fp, nullptr, h->stream, 1);
+        if (e != hipSuccess) return fail(PGL_ERR_HIP, std::string("curvature forward launch: ") + hipGetErrorString(e));
+    } else {
+        const long long row1 = std::min<long long>(h->nT, (long long)(p0.tile0 + p0.nTiles) * 16);
+        total = (row1 - row0) * xs;
+        ENSURE(h->Cbuf, (size_t)h->nT * xs * 8);
+        cb = (double*)h->Cbuf.p + row0 * xs;
+        if (!g_dry) HIPCHK(hipMemsetAsync(cb, 0, (size_t)total * 8, h->stream));
+        for (size_t i = 0; i < slices.size(); ++i) {          // X += F_s . W_s
+            rc = launch_prep(h, plans[i], slices[i], n_lo, d_theta, d_Weff);
+            if (rc) return rc;
+            FusedParams fp;
+            fill_params(h, plans[i], slices[i], n_lo, false, 1, fp);
+            fp.Xbuf = (double*)h->Cbuf.p;
+            fp.xstride = xs;
+            hipError_t e = launch_any(plans[i], fp, h->stream);
+            if (e != hipSuccess) return fail(PGL_ERR_HIP, std::string("curvature forward launch: ") + hipGetErrorString(e));
+        }
+    }
+    if (!g_dry) {                                              // x -> c in place
+        const int blocks = (int)std::min<long long>((total + 255) / 256, 8 * 1024);
+        hipLaunchKernelGGL(k_hvp_curv, dim3(blocks), dim3(256), 0, h->stream, cb, (const double*)h->bias.p,
+                           (const uint8_t*)h->S.p, h->N, n_lo, p0.npost, h->cur_pidx, xs, row0, (long long)h->t_hi, total,
+                           fused ? 1 : 0, h->nlin, h->dt);
+        HIPCHK(hipGetLastError());
+    }
+    h->hvp_fused = fused;
+    return PGL_OK;
+}
+
+// H . v of the prepared rows: d_hv (count, P) in the theta layout
+static int enqueue_hvp_apply(pgl_handle h, const double* d_v, double* d_hv)
+{
+    KernelRecord record(h);
+    const int n_lo = h->hvp_list ? 0 : h->hvp_n_lo, n_hi = n_lo + h->hvp_count;
+    const double* d_Weff = (const double*)h->hvp_Weff.p;
+    std::vector<Slice> slices;
+    std::vector<Plan> plans;
+    bool fused = false;
+    int rc = hvp_select(h, n_lo, n_hi, slices, plans, fused);
+    if (rc) return rc;
+    if (fused != h->hvp_fused) return fail(PGL_ERR_STATE, "the dispatch changed since pgl_hvp_prepare_*: prepare again");
+    size_t maxG = 0, maxLL = 0;
+    for (const Plan& pl : plans) {
+        maxG = std::max(maxG, (size_t)pl.nChunks * pl.nPT * pl.KT * 256 * 8);
+        maxLL = std::max(maxLL, (size_t)pl.nChunks * pl.nPT * pl.KSPLIT * 64 * 8);
+    }
+    ENSURE(h->llpart, maxLL);
+    ENSURE(h->gbpart, maxLL);
+    ENSURE(h->Gpart, maxG);
+    ENSURE(h->hvp_ll, (size_t)h->hvp_count * 8);               // (the reductions write an "ll" beside the bias component)
+    double* d_ll = (double*)h->hvp_ll.p;
+    const int P = 1 + h->Dstim + h->Kimp;
+    const Plan& p0 = plans[0];
+    if (fused) {
+        const size_t need = (size_t)p0.nTiles * p0.nPT * 256 * 8;
+        const bool fresh = need > h->Xbuf.cap || !h->Xbuf.p;
+        ENSURE(h->Xbuf, need);
+        if (fresh && !g_dry) HIPCHK(hipMemsetAsync(h->Xbuf.p, 0, need, h->stream));
+        rc = launch_prep(h, p0, slices[0], n_lo, d_v, d_Weff);
+        if (rc) return rc;
+        rc = ensure_feature_images(h, p0.ktl, p0.kth, p0.tile0, p0.nTiles);
+        if (rc) return rc;
+        FusedParams fp;
+        fill_params(h, p0, slices[0], n_lo, true, 0, fp);
+        // u = F . v, r = c * u, the L columns of F^T . r | the H columns from the residual slab | reduction of the partials
+        hipError_t e = launch_hvp5(p0, fp, (const double*)h->Cbuf.p, h->stream, 0);
+        if (e == hipSuccess) e = launch_fused5(p0, fp, h->stream, 2);
+        if (e != hipSuccess) return fail(PGL_ERR_HIP, std::string("apply launch: ") + hipGetErrorString(e));
+        return launch_finalize_grad(h, p0, slices[0], n_lo, d_Weff, d_ll, d_hv, true);
+    }
+    const int xs = p0.nPT * 16;
+    const long long row0 = (long long)p0.tile0 * 16;
+    const long long row1 = std::min<long long>(h->nT, (long long)(p0.tile0 + p0.nTiles) * 16);
+    ENSURE(h->Xbuf, (size_t)h->nT * xs * 8);
+    if (!g_dry) HIPCHK(hipMemsetAsync((double*)h->Xbuf.p + row0 * xs, 0, (size_t)(row1 - row0) * xs * 8, h->stream));
+    for (size_t i = 0; i < slices.size(); ++i) {              // phase 1: u += F_s . V_s
+        rc = launch_prep(h, plans[i], slices[i], n_lo, d_v, d_Weff);
+        if (rc) return rc;
+        FusedParams fp;
+        fill_params(h, plans[i], slices[i], n_lo, false, 1, fp);
+        hipError_t e = launch_any(plans[i], fp, h->stream);
+        if (e != hipSuccess) return fail(PGL_ERR_HIP, std::string("forward launch: ") + hipGetErrorString(e));
+    }
+    if (!g_dry) {                                              // phase 2: r = c * (u + v_bias)
+        const int rows = 512;
+        const long long nrows = h->t_hi - h->t_lo;
+        const int nblk = (int)((nrows + rows - 1) / rows);
+        ENSURE(h->tmpA, (size_t)nblk * p0.npost * 8);
+        ENSURE(h->tmpB, (size_t)nblk * p0.npost * 8);
+        dim3 grid((unsigned)nblk, (unsigned)((p0.npost + 255) / 256));
+        hipLaunchKernelGGL(k_hvp_rows_mul, grid, dim3(256), 0, h->stream, (double*)h->Xbuf.p, (const double*)h->Cbuf.p, xs,
+                           (const double*)h->bias.p, p0.npost, (long long)h->t_lo, (long long)h->t_hi, rows,
+                           (double*)h->tmpA.p, (double*)h->tmpB.p);
+        HIPCHK(hipGetLastError());
+        if (row1 > h->t_hi) {
+            hipLaunchKernelGGL(k_rows_zero, dim3(64), dim3(256), 0, h->stream, (double*)h->Xbuf.p, xs, (long long)h->t_hi, row1);
+            HIPCHK(hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_rows_reduce, dim3(p0.npost), dim3(64), 0, h->stream, (const double*)h->tmpA.p,
+                           (const double*)h->tmpB.p, nblk, p0.npost, P, d_ll, d_hv);
+        HIPCHK(hipGetLastError());
+    }
+    for (size_t i = 0; i < slices.size(); ++i) {              // phase 3: (H v)_s = F_s^T . r
+        rc = launch_prep(h, plans[i], slices[i], n_lo, d_v, d_Weff);      // only geometry / bias
+        if (rc) return rc;
+        FusedParams fp;
+        fill_params(h, plans[i], slices[i], n_lo, true, 2, fp);
+        hipError_t e = launch_any(plans[i], fp, h->stream);
+        if (e != hipSuccess) return fail(PGL_ERR_HIP, std::string("backward launch: ") + hipGetErrorString(e));
+        rc = launch_finalize_grad(h, plans[i], slices[i], n_lo, d_Weff, d_ll, d_hv);
+        if (rc) return rc;
+    }
+    return PGL_OK;
+}
+
+static int hvp_prepare_common(pgl_handle h, const int* d_idx, int n_lo, int count, const double* d_theta, const double* d_Weff)
+{
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if (!d_theta || !d_Weff) return fail(PGL_ERR_ARG, "null argument");
+    if (h->sep)
+        return fail(PGL_ERR_UNSUPPORTED, "Hessian-vector products with a separable stimulus (pgl_set_stimulus_separable): "
+                                         "the current is not linear in (w_t, w_x)");
+    HIPCHK(hipSetDevice(h->device));
+    h->hvp_ok = false;
+    h->hvp_host.clear();
+    // the apply has no Weff / list argument: the handle keeps its own copies
+    ENSURE(h->hvp_Weff, (size_t)h->N * h->N * 8);
+    HIPCHK(hipMemcpyAsync(h->hvp_Weff.p, d_Weff, (size_t)h->N * h->N * 8, hipMemcpyDeviceToDevice, h->stream));
+    if (d_idx) {
+        ENSURE(h->hvp_idx, (size_t)count * 4);
+        HIPCHK(hipMemcpyAsync(h->hvp_idx.p, d_idx, (size_t)count * 4, hipMemcpyDeviceToDevice, h->stream));
+        h->cur_pidx = (const int*)h->hvp_idx.p;
+    }
+    rc = enqueue_hvp_prepare(h, n_lo, n_lo + count, d_theta, (const double*)h->hvp_Weff.p);
+    h->cur_pidx = nullptr;
+    if (rc) return rc;
+    h->hvp_list = d_idx != nullptr;
+    h->hvp_n_lo = n_lo;
+    h->hvp_count = count;
+    h->hvp_t_lo = h->t_lo;
+    h->hvp_t_hi = h->t_hi;
+    h->hvp_ok = true;
+    return PGL_OK;
+}
+
+int pgl_hvp_prepare_dev(pgl_handle h, int n_lo, int n_hi, const double* d_theta, const double* d_Weff)
+{
+    if (!h) return fail(PGL_ERR_ARG, "null handle");
+    if (n_lo < 0 || n_hi > h->N || n_lo >= n_hi) return fail(PGL_ERR_ARG, "bad neuron range");
+    return hvp_prepare_common(h, nullptr, n_lo, n_hi - n_lo, d_theta, d_Weff);
+}
+
+int pgl_hvp_prepare_list_dev(pgl_handle h, const int* d_idx, int count, const double* d_theta, const double* d_Weff)
+{
+    if (!h || !d_idx) return fail(PGL_ERR_ARG, "null argument");
+    if (count <= 0 || count > h->N) return fail(PGL_ERR_ARG, "bad neuron count");
+    return hvp_prepare_common(h, d_idx, 0, count, d_theta, d_Weff);
+}
+
+int pgl_hvp_apply_dev(pgl_handle h, const double* d_v, double* d_hv)
+{
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if (!d_v || !d_hv) return fail(PGL_ERR_ARG, "null argument");
+    if (!h->hvp_ok) return fail(PGL_ERR_STATE, "pgl_hvp_prepare_* has not been called (or the data changed since)");
+    if (h->hvp_t_lo != h->t_lo || h->hvp_t_hi != h->t_hi)
+        return fail(PGL_ERR_STATE, "the time range changed since pgl_hvp_prepare_*");
+    HIPCHK(hipSetDevice(h->device));
+    h->cur_pidx = h->hvp_list ? (const int*)h->hvp_idx.p : nullptr;
+    rc = enqueue_hvp_apply(h, d_v, d_hv);
+    h->cur_pidx = nullptr;
+    return rc;
+}
+
+int pgl_hvp(pgl_handle h, int n_lo, int n_hi, const double* theta, const double* v, const double* Weff, double* hv_out)
+{
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if (!theta || !v || !Weff || !hv_out) return fail(PGL_ERR_ARG, "null argument");
+    if (n_lo < 0 || n_hi > h->N || n_lo >= n_hi) return fail(PGL_ERR_ARG, "bad neuron range");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t P = 1 + (size_t)h->Dstim + h->Kimp;
+    const size_t np = (size_t)(n_hi - n_lo);
+    ENSURE(h->theta, np * P * 8);
+    ENSURE(h->Weff, (size_t)h->N * h->N * 8);
+    ENSURE(h->hvp_v, np * P * 8);
+    ENSURE(h->hvp_out, np * P * 8);
+    HIPCHK(hipMemcpyAsync(h->hvp_v.p, v, np * P * 8, hipMemcpyHostToDevice, h->stream));
+    // the products of one CG solve share theta: the curvature of an identical (range, time range, theta, Weff) is kept
+    const size_t nW = (size_t)h->N * h->N;
+    const bool same = h->hvp_ok && !h->hvp_list && h->hvp_n_lo == n_lo && h->hvp_count == (int)np && h->hvp_t_lo == h->t_lo &&
+                      h->hvp_t_hi == h->t_hi && h->hvp_host.size() == np * P + nW &&
+                      std::memcmp(h->hvp_host.data(), theta, np * P * 8) == 0 &&
+                      std::memcmp(h->hvp_host.data() + np * P, Weff, nW * 8) == 0;
+    if (!same) {
+        h->hvp_host.clear();
+        HIPCHK(hipMemcpyAsync(h->theta.p, theta, np * P * 8, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->Weff.p, Weff, nW * 8, hipMemcpyHostToDevice, h->stream));
+        rc = pgl_hvp_prepare_dev(h, n_lo, n_hi, (const double*)h->theta.p, (const double*)h->Weff.p);
+        if (rc) return rc;
+        h->hvp_host.assign(theta, theta + np * P);
+        h->hvp_host.insert(h->hvp_host.end(), Weff, Weff + nW);
+    }
+    rc = pgl_hvp_apply_dev(h, (const double*)h->hvp_v.p, (double*)h->hvp_out.p);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(hv_out, h->hvp_out.p, np * P * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return PGL_OK;
 }
 
 // ---- lock-step BFGS bookkeeping kernels (inference/batched_bfgs.py) ----------------------------------------------

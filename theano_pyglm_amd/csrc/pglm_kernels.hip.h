@@ -18,12 +18,14 @@
 //   k_fused3                 the same two passes, F tile regenerated in LDS from the spike events
 //   k_fused2                 one pass, post tiles x K slices across the 8 waves (small post blocks,
 //                            the sliced path for N > 128, optional f32 feature tile)
+// Hessian-vector products H.v = F^T.(c o (F.v)) reuse the scheme with the epilogue swapped for one multiply (k_hvp5).
 #pragma once
 //
 // The kernels live in one header per family; this file is the translation unit's table of contents.
 #include "pglm_common.hip.h"
 #include "pglm_fused_stream.hip.h"
 #include "pglm_fused_resident.hip.h"
+#include "pglm_hvp.hip.h"
 #include "pglm_reduce.hip.h"
 #include "pglm_direct.hip.h"
 #include "pglm_gibbs.hip.h"

@@ -79,6 +79,32 @@ class Glm(Component):
                 'bkgd': self.bkgd_model.grad_log_p(xn['bkgd']),
                 'imp': self.imp_model.grad_log_p(xn['imp']), 'nlin': {}}
 
+    def hvp_packing(self):
+        """None when Hessian-vector products are served for this model: the packed per-neuron vector is a permutation of
+        the device's theta row (constant bias, no or basis stimulus, linear-basis impulses under a Gaussian or
+        group-lasso prior).  Else the name of the packing that is not -- its second-order chain terms (w_t (x) w_x,
+        |g| / sum|g|) are not implemented."""
+        from theano_pyglm_amd.components.bias import ConstantBias
+        from theano_pyglm_amd.components.bkgd import NoStimulus, BasisStimulus
+        from theano_pyglm_amd.components.impulse import LinearBasisImpulses
+        from theano_pyglm_amd.components.priors import Gaussian, GroupLasso
+        if not isinstance(self.bias_model, ConstantBias):
+            return type(self.bias_model).__name__
+        if not isinstance(self.bkgd_model, (NoStimulus, BasisStimulus)):
+            return type(self.bkgd_model).__name__
+        if not isinstance(self.imp_model, LinearBasisImpulses):
+            return type(self.imp_model).__name__
+        if not isinstance(self.imp_model.prior, (Gaussian, GroupLasso)):
+            return type(self.imp_model.prior).__name__
+        return None
+
+    def hess_log_prior_vec(self, xn, v):
+        """Hessian of log_prior(xn) times v (a dict shaped like the differentiable part of xn), shaped like
+        grad_log_prior; the counterpart of the prior terms inside hessian_rop_wrt_list (grads.py:68-95)."""
+        return {'n': {}, 'bias': self.bias_model.hess_log_p_vec(xn['bias'], v['bias']),
+                'bkgd': self.bkgd_model.hess_log_p_vec(xn['bkgd'], v.get('bkgd', {})),
+                'imp': self.imp_model.hess_log_p_vec(xn['imp'], v['imp']), 'nlin': {}}
+
     @property
     def Dstim(self):
         return self.bkgd_model.n_features

@@ -72,6 +72,38 @@ def prep_first_order_glm_inference(population):
     return glm_syms, nlp, grad_nlp
 
 
+def prep_second_order_glm_inference(population):
+    """The Rop branch of the reference's prep_first_order_glm_inference (parallel_coord_descent.py:62-63 with
+    grads.py:68-95 hessian_rop_wrt_list): returns hessp_nlp(x_glm_vec, p, x), the Hessian of the negative log
+    posterior of one neuron's packed GLM parameters times the packed vector p.  The likelihood part is one device
+    product per data sequence (the curvature of a repeated x_glm_vec stays on the device), the prior part numpy."""
+    glm_syms = population.glm_syms()
+    x0 = population.shape_vars()
+    nvars = population.extract_vars(x0, 0)
+    _, glm_shapes = packdict(get_vars(glm_syms, nvars['glm']))
+    bad = population.glm.hvp_packing()
+
+    def hessp_nlp(x_glm_vec, p, x):
+        if bad is not None:
+            raise ValueError("Hessian-vector products are not implemented for the %s packing" % bad)
+        glm = population.glm
+        set_vars(glm_syms, x['glm'], unpackdict(x_glm_vec, glm_shapes))
+        xn = x['glm']
+        n = int(xn['n'])
+        vd = unpackdict(np.asarray(p, dtype=float), glm_shapes)
+        hv, _ = packdict(get_vars(glm_syms, glm.hess_log_prior_vec(xn, vd)))
+        theta = glm.theta_row(xn)[None, :]
+        v_theta = glm.theta_row(vd)[None, :]
+        Weff = population.network.W_eff(x['net'])
+        for data in population.data_sequences:
+            population.set_data(data)
+            ht = population._handle(data).hvp(theta, v_theta, Weff, n, n + 1)
+            hv = hv + packdict(get_vars(glm_syms, glm.chain_grad(xn, ht[0])))[0]
+        return -1.0 * hv
+
+    return hessp_nlp
+
+
 def prep_first_order_network_inference(population):
     """coord_descent.py:84-132.  Only float network variables are optimised; for constant
     weights / complete graphs there are none and fit_network is a no-op (:141)."""
@@ -104,8 +136,15 @@ def fit_network(x, net_inf_prms):
         set_vars(net_syms, x['net'], unpackdict(res.x, shapes))
 
 
-def fit_glm(xn, n, glm_inf_prms, verbose=False, maxiter=225):
-    """coord_descent.py:161-204."""
+def fit_glm(xn, n, glm_inf_prms, verbose=False, maxiter=225, use_hessian=False, use_rop=False, hessp=None):
+    """coord_descent.py:161-204; with use_rop the Newton-CG fit of parallel_coord_descent.py:119-121 / map.py:38-45 on
+    hessp = prep_second_order_glm_inference(population).  Rop takes precedence over the dense Hessian
+    (parallel_coord_descent.py:75-76); use_hessian alone raises: the dense P x P Hessian is not built."""
+    if use_hessian and not use_rop:
+        raise NotImplementedError("use_hessian: the dense P x P Hessian is not built; use_rop=True runs Newton-CG on "
+                                  "Hessian-vector products")
+    if use_rop and hessp is None:
+        raise ValueError("use_rop=True needs hessp = prep_second_order_glm_inference(population)")
     glm_syms, glm_nll, g_glm_nll = glm_inf_prms
     x_glm_0, shapes = packdict(get_vars(glm_syms, xn['glm']))
 
@@ -128,8 +167,18 @@ def fit_glm(xn, n, glm_inf_prms, verbose=False, maxiter=225):
             print("Newton iter %d.\tNeuron %d. LL: %.1f" % (it[0], n, -1.0 * nll(x_curr)))
         it[0] += 1
 
-    res = opt.minimize(nll, x_glm_0, method="bfgs", jac=grad_nll,
-                       options={'disp': verbose, 'maxiter': maxiter}, callback=cbk)
+    def hessp_nll(v, p):
+        hv = hessp(v, p, xn)
+        if np.any(np.isnan(hv)):                       # fit_glm's rule for the gradient, applied to the product
+            hv = np.zeros_like(hv)
+        return hv
+
+    if use_rop:
+        res = opt.minimize(nll, x_glm_0, method="Newton-CG", jac=grad_nll, hessp=hessp_nll,
+                           options={'disp': verbose, 'maxiter': maxiter}, callback=cbk)
+    else:
+        res = opt.minimize(nll, x_glm_0, method="bfgs", jac=grad_nll,
+                           options={'disp': verbose, 'maxiter': maxiter}, callback=cbk)
     set_vars(glm_syms, xn['glm'], unpackdict(res.x, shapes))
     return res
 
@@ -230,10 +279,16 @@ def resolve_batched(population, batched):
     return batched
 
 
-def coord_descent(population, x0=None, maxiter=50, atol=1e-5, batched=None, verbose=False):
+def coord_descent(population, x0=None, maxiter=50, atol=1e-5, batched=None, verbose=False, use_rop=False):
     """coord_descent.py:206-266.  `batched`: see resolve_batched (None = automatic; batched=False is the
-    reference's sweep of N sequential scipy BFGS fits, kept for comparison)."""
+    reference's sweep of N sequential scipy BFGS fits, kept for comparison).  use_rop: the per-neuron fits of the
+    sequential sweep run Newton-CG on device Hessian-vector products (parallel_coord_descent.py:62-63); with
+    batched=None it selects that sweep."""
     N = population.model['N']
+    if use_rop and batched is None:
+        batched = False
+    if use_rop and batched:
+        raise ValueError("use_rop runs on the sequential sweep (batched=False)")
     batched = resolve_batched(population, batched)
     network = population.network
     if not isinstance(network.graph, CompleteGraphModel):
@@ -247,6 +302,7 @@ def coord_descent(population, x0=None, maxiter=50, atol=1e-5, batched=None, verb
         print("Initial LP=%.2f." % lp)
     net_inf_prms = prep_first_order_network_inference(population)
     glm_inf_prms = prep_first_order_glm_inference(population)
+    hessp = prep_second_order_glm_inference(population) if use_rop else None
     x = x0
     lp_prev = lp                                      # x is x0: the value just computed
     converged = False
@@ -261,7 +317,7 @@ def coord_descent(population, x0=None, maxiter=50, atol=1e-5, batched=None, verb
         else:
             for n in np.arange(N):
                 nvars = population.extract_vars(x, n)
-                fit_glm(nvars, n, glm_inf_prms, verbose=verbose)
+                fit_glm(nvars, n, glm_inf_prms, verbose=verbose, use_rop=use_rop, hessp=hessp)
                 x['glms'][n] = nvars['glm']
         fit_network(x, net_inf_prms)
         lp = population.compute_log_p(x)

@@ -21,7 +21,7 @@ from theano_pyglm_amd import _lib
 from theano_pyglm_amd.components.latent import LatentVariables
 from theano_pyglm_amd.components.network import Network
 from theano_pyglm_amd.glm import Glm
-from theano_pyglm_amd.utils.packvec import packdict, get_vars
+from theano_pyglm_amd.utils.packvec import packdict, unpackdict, get_vars
 from theano_pyglm_amd.utils.syms import from_shapes, differentiable, check_bound, compile_bound, compile_paths, check_paths
 
 
@@ -301,6 +301,39 @@ class Population(object):
                 gv, _ = packdict(get_vars(syms, self.glm.grad_log_prior(xn)))
                 grads[i] += gv
         return lps, grads
+
+    def compute_hvp_packed(self, vars, V, n_lo=0, n_hi=None, include_prior=True):
+        """For every neuron n in [n_lo, n_hi): the Hessian of (log_prior_n + sum_data ll_n) w.r.t. its packed parameter
+        vector, times row n of V (npost, P_packed) -- hessian_rop_wrt_list (grads.py:68-95) for all neurons of the range,
+        one curvature pass and one product on the device per data sequence.  Served where the packed vector is a
+        permutation of the theta row (Glm.hvp_packing); other packings raise ValueError."""
+        bad = self.glm.hvp_packing()
+        if bad is not None:
+            raise ValueError("Hessian-vector products are not implemented for the %s packing" % bad)
+        n_hi = self.N if n_hi is None else n_hi
+        syms = self.glm_syms()
+        V = np.asarray(V, dtype=float)
+        _, shapes = packdict(get_vars(syms, vars['glms'][n_lo]))
+        vds = [unpackdict(V[i], shapes) for i in range(n_hi - n_lo)]
+        # the packing is linear: the theta row of the direction is the direction in the device's layout
+        v_theta = self.glm.theta_rows(vds)
+        theta = self.theta_matrix(vars, n_lo, n_hi)
+        Weff = self.W_eff(vars)
+        out = np.zeros(V.shape)
+        for data in self.data_sequences:
+            self.set_data(data)
+            hv = self._handle(self._current).hvp(theta, v_theta, Weff, n_lo, n_hi)
+            for i, n in enumerate(range(n_lo, n_hi)):
+                out[i] += packdict(get_vars(syms, self.glm.chain_grad(vars['glms'][n], hv[i])))[0]
+        if include_prior:
+            for i, n in enumerate(range(n_lo, n_hi)):
+                out[i] += packdict(get_vars(syms, self.glm.hess_log_prior_vec(vars['glms'][n], vds[i])))[0]
+        return out
+
+    def compute_hvp(self, vars, n, v):
+        """Hessian of (glm.log_prior + sum_data glm.ll) of neuron n w.r.t. its packed parameter vector, times the packed
+        vector v -- the counterpart of compute_grad (minus coord_descent's hessp)."""
+        return self.compute_hvp_packed(vars, np.asarray(v, dtype=float)[None, :], n, n + 1)[0]
 
     def compute_grad(self, vars, n):
         """Gradient of (glm.log_prior + sum_data glm.ll) of neuron n w.r.t. its packed
