@@ -254,6 +254,42 @@ int pgl_bfgs_step_dev(pgl_handle h, double* d_state, int M, int P, const int* d_
                       int Kmax, double* d_ab, int hk_bound, double* d_H, int ld, const int* d_pos_next, double* d_Xt_next,
                       double* flags_out);
 
+/* Lock-step Newton-CG (inference/batched_newton_cg.py) as row kernels on the handle's stream: the algorithm of
+ * scipy.optimize.minimize(method='Newton-CG', jac=, hessp=) as fit_glm(use_rop=True) calls it per neuron
+ * (parallel_coord_descent.py:119-121 / map.py:38-45; restated in csrc/pglm_ncg.h with the places where it differs), for all
+ * M neurons of a range at once: every CG iteration is ONE pgl_hvp_apply_dev over all M rows, every line-search trial one
+ * pgl_ll_grad_list_dev of the rows still searching.  All optimiser state of M rows of P parameters lives in ONE device block
+ * of pgl_ncg_state_doubles(M, P) doubles (flags and counters stored as doubles), in this order:
+ *   (M,P) each: X, g, xsupi (the direction pk), ri, psupi, Xb, gb (best trial of the running search);
+ *   (M) each:   f, fprev, dri0, termcond, cgit, alphai, nit, nhev, nfev, status (-1 running, else scipy's 0 success,
+ *               1 maxiter, 2 precision loss, 3 CG failure), phase (0 CG, 1 line search, 2 finished), slope, alpha, fb,
+ *               alpha_acc, moved;  then the line-search state, (18, M).
+ * Rows are theta rows [bias, w_stim, w_ir]; the objective is f = -(ll + log prior), H v = -(H_ll v + H_prior v) with the
+ * priors of pgl_bfgs_objective_dev (same arguments) and fit_glm's NaN rules (objective NaN -> 1e16, a gradient or a
+ * product holding a NaN -> 0).  d_V (M, P) is the input of the next product, row by row (zero for every row whose CG does
+ * not run, so that its product is harmless); flags_out (NULL or M doubles of PINNED host memory) receives the phase of
+ * every row a kernel has advanced, written by the kernel itself.  A finished row is never written again.
+ *   init:        X in the state, (d_ll, d_grad) = ll and gradient at X by row (overwritten with f, g): start of the first
+ *                outer iteration (b, termcond, CG start, d_V); maxiter <= 0 ends every row with status 1.
+ *   cg_step:     d_hv (M, P) = the product of d_V just made (overwritten): prior term, sign, NaN rule, curvature and the
+ *                stop tests, CG update, next d_V; a row whose CG ends starts its line search (phase 1) or finishes.
+ *   trial:       Xt[j] = X[r] + alpha[r] pk[r], r = d_rows[j] (NULL: j), j < L.
+ *   search_step: (d_ll_f, d_grad_g) = evaluation of the trial points d_Xt of the L listed rows by list position
+ *                (overwritten): one More'-Thuente step per row; another trial -> d_Xt_next[d_pos_next[r]] (NULL: same
+ *                position; < 0: not listed; d_Xt_next NULL: none, use trial); accepted -> convergence test
+ *                (|alpha pk|_1 <= P * 1e-5: status 0) or the start of the next outer iteration as in init. */
+long long pgl_ncg_state_doubles(int M, int P);
+int pgl_ncg_init_dev(pgl_handle h, double* d_state, int M, int P, double* d_ll, double* d_grad, int prior_kind, double mu_b,
+                     double sg_b, double stim_sigma, double mu, double sigma, double lam, int maxiter, double* d_V,
+                     double* flags_out);
+int pgl_ncg_cg_step_dev(pgl_handle h, double* d_state, int M, int P, double* d_hv, int prior_kind, double mu_b, double sg_b,
+                        double stim_sigma, double mu, double sigma, double lam, double* d_V, double* flags_out);
+int pgl_ncg_trial_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, double* d_Xt);
+int pgl_ncg_search_step_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, const double* d_Xt,
+                            double* d_ll_f, double* d_grad_g, int prior_kind, double mu_b, double sg_b, double stim_sigma,
+                            double mu, double sigma, double lam, int maxiter, const int* d_pos_next, double* d_Xt_next,
+                            double* d_V, double* flags_out);
+
 /* convolve_with_basis(S, ibasis) (basis.py:201-236 via impulse.py:114-130):
  * fS_out (nT,N,B) row-major, float64. */
 int pgl_features(pgl_handle h, double* fS_out);

@@ -36,6 +36,7 @@ SYMBOLS = [
     'pgl_bfgs_state_doubles', 'pgl_bfgs_init_dev', 'pgl_bfgs_trial_dev', 'pgl_bfgs_objective_dev',
     'pgl_bfgs_linesearch_dev', 'pgl_bfgs_hmul_dev', 'pgl_bfgs_hmul_hist_dev', 'pgl_bfgs_update_dev', 'pgl_bfgs_step_dev', 'pgl_plan_kernels', 'pgl_last_kernels', 'pgl_leading_singular_pairs',
     'pgl_hvp_prepare_dev', 'pgl_hvp_prepare_list_dev', 'pgl_hvp_apply_dev', 'pgl_hvp',
+    'pgl_ncg_state_doubles', 'pgl_ncg_init_dev', 'pgl_ncg_cg_step_dev', 'pgl_ncg_trial_dev', 'pgl_ncg_search_step_dev',
 ]
 
 
@@ -140,6 +141,13 @@ def load():
         lib.pgl_bfgs_step_dev.argtypes = ([vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int] + [C.c_double] * 6 +
                                           [C.c_int, C.c_double, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int,
                                            vp, vp, vp])
+    if hasattr(lib, 'pgl_ncg_init_dev'):                      # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
+        lib.pgl_ncg_state_doubles.argtypes = [C.c_int, C.c_int]
+        lib.pgl_ncg_init_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int] + [C.c_double] * 6 + [C.c_int, vp, vp]
+        lib.pgl_ncg_cg_step_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int] + [C.c_double] * 6 + [vp, vp]
+        lib.pgl_ncg_trial_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp]
+        lib.pgl_ncg_search_step_dev.argtypes = ([vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int] +
+                                                [C.c_double] * 6 + [C.c_int, vp, vp, vp, vp])
     lib.pgl_features.argtypes = [vp, vp]
     lib.pgl_impulse_currents.argtypes = [vp, vp, vp]
     lib.pgl_state.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
@@ -164,7 +172,7 @@ def load():
         if 'PYGLM_HIP_LIB' in os.environ and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
-        if name == 'pgl_bfgs_state_doubles':
+        if name in ('pgl_bfgs_state_doubles', 'pgl_ncg_state_doubles'):
             fn.restype = C.c_longlong
         elif name not in ('pgl_last_error',):
             fn.restype = C.c_int
@@ -435,6 +443,32 @@ class DeviceGlm(object):
                                         int(max_trials), float(gtol), int(maxiter), 1 if init_scaling else 0, vp(d_hist),
                                         vp(d_coef), int(Kmax), vp(d_ab), int(hk_bound), vp(d_H), int(ld), vp(d_pos_next),
                                         vp(d_Xt_next), vp(flags_out)))
+
+    # -- lock-step Newton-CG row kernels (pgl_ncg_*; inference/batched_newton_cg.py).  prior: bfgs_objective_dev's tuple
+    def ncg_state_doubles(self, M, P):
+        return int(self.lib.pgl_ncg_state_doubles(int(M), int(P)))
+
+    def ncg_init_dev(self, d_state, M, P, d_ll, d_grad, prior, maxiter, d_V, flags_out=0):
+        _chk(self.lib.pgl_ncg_init_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_ll), C.c_void_p(d_grad),
+                                       int(prior[0]), *[float(z) for z in prior[1:]], int(maxiter), C.c_void_p(d_V),
+                                       C.c_void_p(flags_out) if flags_out else None))
+
+    def ncg_cg_step_dev(self, d_state, M, P, d_hv, prior, d_V, flags_out=0):
+        _chk(self.lib.pgl_ncg_cg_step_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_hv), int(prior[0]),
+                                          *[float(z) for z in prior[1:]], C.c_void_p(d_V),
+                                          C.c_void_p(flags_out) if flags_out else None))
+
+    def ncg_trial_dev(self, d_state, M, P, d_rows, L, d_Xt):
+        _chk(self.lib.pgl_ncg_trial_dev(self.h, C.c_void_p(d_state), int(M), int(P),
+                                        C.c_void_p(d_rows) if d_rows else None, int(L), C.c_void_p(d_Xt)))
+
+    def ncg_search_step_dev(self, d_state, M, P, d_rows, L, d_Xt, d_f, d_g, prior, maxiter, d_pos_next, d_Xt_next, d_V,
+                            flags_out=0):
+        vp = lambda a: C.c_void_p(a) if a else None
+        _chk(self.lib.pgl_ncg_search_step_dev(self.h, C.c_void_p(d_state), int(M), int(P), vp(d_rows), int(L),
+                                              C.c_void_p(d_Xt), C.c_void_p(d_f), C.c_void_p(d_g), int(prior[0]),
+                                              *[float(z) for z in prior[1:]], int(maxiter), vp(d_pos_next), vp(d_Xt_next),
+                                              C.c_void_p(d_V), vp(flags_out)))
 
     def sync(self):
         _chk(self.lib.pgl_sync(self.h))

@@ -1040,7 +1040,7 @@ static void launch_sepf(int which, const SepfParams& sp, hipStream_t s)
 extern "C" {
 
 const char* pgl_last_error(void) { return g_err.c_str(); }
-int pgl_version(void) { return 101; }
+int pgl_version(void) { return 102; }
 
 int pgl_device_count(void)
 {
@@ -2681,6 +2681,26 @@ int pgl_bfgs_update_dev(pgl_handle h, double* d_state, int M, int P, double gtol
     return PGL_OK;
 }
 
+// the address the device uses for a buffer of pinned host memory that a row kernel writes its flags into (looked up once)
+static int flags_device_pointer(pgl_handle h, double* flags_out, double** flags_dev)
+{
+    for (int i = 0; i < 4; ++i)
+        if (h->flags_host[i] == flags_out) {
+            *flags_dev = h->flags_dev[i];
+            return PGL_OK;
+        }
+    void* dp = nullptr;
+    if (hipHostGetDevicePointer(&dp, flags_out, 0) != hipSuccess || !dp) {
+        (void)hipGetLastError();
+        return fail(PGL_ERR_ARG, "flags_out must be pinned (page-locked, device-mapped) host memory");
+    }
+    *flags_dev = (double*)dp;
+    h->flags_host[h->flags_next] = flags_out;
+    h->flags_dev[h->flags_next] = *flags_dev;
+    h->flags_next = (h->flags_next + 1) & 3;
+    return PGL_OK;
+}
+
 // One whole iteration behind an evaluation (see k_bfgs_step): in ONE launch while the update history of a row is short
 // (hk_bound * P numbers, PGL_OPT_BFGS_MERGE), else as line search | k_bfgs_hdots | k_bfgs_hcomb | update (dense inverse
 // Hessians: line search | k_bfgs_hmul | update).
@@ -2701,21 +2721,7 @@ int pgl_bfgs_step_dev(pgl_handle h, double* d_state, int M, int P, const int* d_
         return fail(PGL_ERR_ARG, "H: leading dimension even and >= P, base 16-byte aligned");
     HIPCHK(hipSetDevice(h->device));
     double* flags_dev = nullptr;
-    if (flags_out) {                                         // pinned host memory: the address the device uses for it
-        for (int i = 0; i < 4 && !flags_dev; ++i)
-            if (h->flags_host[i] == flags_out) flags_dev = h->flags_dev[i];
-        if (!flags_dev) {
-            void* dp = nullptr;
-            if (hipHostGetDevicePointer(&dp, flags_out, 0) != hipSuccess || !dp) {
-                (void)hipGetLastError();
-                return fail(PGL_ERR_ARG, "flags_out must be pinned (page-locked, device-mapped) host memory");
-            }
-            flags_dev = (double*)dp;
-            h->flags_host[h->flags_next] = flags_out;
-            h->flags_dev[h->flags_next] = flags_dev;
-            h->flags_next = (h->flags_next + 1) & 3;
-        }
-    }
+    if (flags_out && flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
     const BfgsView v = pgl_bfgs_view(d_state, M, P);
     BfgsStepArgs a = bfgs_step_args(0);
     a.rows = d_rows; a.Xt = d_Xt; a.ft = d_ll_f; a.gt = d_grad_g;
@@ -2750,6 +2756,83 @@ int pgl_bfgs_step_dev(pgl_handle h, double* d_state, int M, int P, const int* d_
     }
     a.phases = PGL_STEP_UPDATE;
     hipLaunchKernelGGL(k_bfgs_step<256>, dim3(L), dim3(256), 0, h->stream, v, a);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+// ---- lock-step Newton-CG row kernels (inference/batched_newton_cg.py) --------------------------------------------------
+long long pgl_ncg_state_doubles(int M, int P) { return (long long)pgl_ncg_doubles(M, P); }
+
+static int ncg_prior(pgl_handle h, int P, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma,
+                     double lam, BfgsPrior& q)
+{
+    if (P != 1 + h->Dstim + h->Kimp) return fail(PGL_ERR_ARG, "rows must be theta rows [bias, w_stim, w_ir]");
+    if (prior_kind != 0 && prior_kind != 1) return fail(PGL_ERR_ARG, "prior kind: 0 Gaussian, 1 group lasso");
+    if (h->B > PGL_MAXB) return fail(PGL_ERR_UNSUPPORTED, "impulse basis too wide for the row kernels");
+    q.N = h->N; q.B = h->B; q.Dstim = h->Dstim; q.kind = prior_kind;
+    q.mu_b = mu_b; q.sg_b = sg_b; q.stim_sigma = stim_sigma; q.mu = mu; q.sigma = sigma; q.lam = lam;
+    return PGL_OK;
+}
+
+int pgl_ncg_init_dev(pgl_handle h, double* d_state, int M, int P, double* d_ll, double* d_grad, int prior_kind, double mu_b,
+                     double sg_b, double stim_sigma, double mu, double sigma, double lam, int maxiter, double* d_V,
+                     double* flags_out)
+{
+    if (!h || !d_state || !d_ll || !d_grad || !d_V || M <= 0 || P <= 0) return fail(PGL_ERR_ARG, "bad argument");
+    BfgsPrior q;
+    int rc = ncg_prior(h, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    double* flags_dev = nullptr;
+    if (flags_out && flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
+    hipLaunchKernelGGL(k_ncg_init, dim3(M), dim3(256), 0, h->stream, pgl_ncg_view(d_state, M, P), d_ll, d_grad, q, maxiter, d_V,
+                       flags_dev);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+int pgl_ncg_cg_step_dev(pgl_handle h, double* d_state, int M, int P, double* d_hv, int prior_kind, double mu_b, double sg_b,
+                        double stim_sigma, double mu, double sigma, double lam, double* d_V, double* flags_out)
+{
+    if (!h || !d_state || !d_hv || !d_V || M <= 0 || P <= 0) return fail(PGL_ERR_ARG, "bad argument");
+    BfgsPrior q;
+    int rc = ncg_prior(h, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    double* flags_dev = nullptr;
+    if (flags_out && flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
+    hipLaunchKernelGGL(k_ncg_cg_step, dim3(M), dim3(256), 0, h->stream, pgl_ncg_view(d_state, M, P), d_hv, q, d_V, flags_dev);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+int pgl_ncg_trial_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, double* d_Xt)
+{
+    if (!h || !d_state || !d_Xt || M <= 0 || P <= 0 || L <= 0 || L > M) return fail(PGL_ERR_ARG, "bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_ncg_trial, dim3(L), dim3(256), 0, h->stream, pgl_ncg_view(d_state, M, P), d_rows, d_Xt);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+int pgl_ncg_search_step_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, const double* d_Xt,
+                            double* d_ll_f, double* d_grad_g, int prior_kind, double mu_b, double sg_b, double stim_sigma,
+                            double mu, double sigma, double lam, int maxiter, const int* d_pos_next, double* d_Xt_next,
+                            double* d_V, double* flags_out)
+{
+    if (!h || !d_state || !d_Xt || !d_ll_f || !d_grad_g || !d_V || M <= 0 || P <= 0 || L <= 0 || L > M)
+        return fail(PGL_ERR_ARG, "bad argument");
+    if (d_Xt_next == d_Xt) return fail(PGL_ERR_ARG, "the next trial points need a buffer of their own");
+    NcgSearchArgs a;
+    memset(&a, 0, sizeof(a));
+    int rc = ncg_prior(h, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, a.q);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    double* flags_dev = nullptr;
+    if (flags_out && flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
+    a.rows = d_rows; a.Xt = d_Xt; a.ft = d_ll_f; a.gt = d_grad_g; a.maxiter = maxiter;
+    a.pos_next = d_pos_next; a.Xt_next = d_Xt_next; a.V = d_V; a.flags = flags_dev;
+    hipLaunchKernelGGL(k_ncg_search_step, dim3(L), dim3(256), 0, h->stream, pgl_ncg_view(d_state, M, P), a);
     HIPCHK(hipGetLastError());
     return PGL_OK;
 }

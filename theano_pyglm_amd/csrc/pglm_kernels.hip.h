@@ -31,3 +31,4 @@
 #include "pglm_gibbs.hip.h"
 #include "pglm_stim.hip.h"
 #include "pglm_bfgs.hip.h"
+#include "pglm_ncg.hip.h"

@@ -4,7 +4,8 @@ MAP fit on synthetic data -- counterpart of test/synth_map.py + test/synth_harne
     python -m theano_pyglm_amd.harness.synth_map -d data.pkl -r out_dir [-m standard_glm] [--sequential]
 
 The sweep over the neurons runs as the GPU lock-step optimizer by default (inference/batched_bfgs.py);
---sequential (batched=False) is the reference's loop of per-neuron scipy fits.
+--sequential (batched=False) is the reference's loop of per-neuron scipy fits; --newton-cg runs the sweep as the GPU
+lock-step Newton-CG optimizer on device Hessian-vector products (inference/batched_newton_cg.py; the reference's use_rop).
 """
 import argparse
 import os
@@ -33,13 +34,13 @@ def initialize_test_harness(model_name, data, data_dir=None):
     return popn, popn_true, x_true
 
 
-def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None):
+def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False):
     """test/synth_map.py:10-32."""
     popn, popn_true, x_true = initialize_test_harness(model_name, data, data_dir)
     x0 = popn.sample(rng)
     print("LL0: %f" % popn.compute_log_p(x0))
     t0 = time.time()
-    x_inf = coord_descent(popn, x0=x0, maxiter=1, batched=batched)
+    x_inf = coord_descent(popn, x0=x0, maxiter=1, batched=batched, use_rop=use_rop)
     wall = time.time() - t0
     ll_inf = popn.compute_log_p(x_inf)
     print("LL_inf: %f   (MAP wall-clock %.2f s)" % (ll_inf, wall))
@@ -56,11 +57,14 @@ def main():
     ap.add_argument('-r', '--resultsDir', default='.')
     ap.add_argument('--sequential', action='store_true', help='per-neuron scipy fits (the reference loop)')
     ap.add_argument('--batched', action='store_true', help='(deprecated, no-op: the GPU lock-step sweep is the default)')
+    ap.add_argument('--newton-cg', action='store_true',
+                    help='lock-step Newton-CG on device Hessian-vector products instead of lock-step BFGS '
+                         '(with --sequential: per-neuron scipy Newton-CG fits)')
     args = ap.parse_args()
     with open(args.dataFile, 'rb') as f:
         data = pickle.load(f)
     run_synth_test(args.model, data, args.resultsDir, os.path.dirname(args.dataFile),
-                   False if args.sequential else None)
+                   False if args.sequential else ('torch' if args.newton_cg else None), use_rop=args.newton_cg)
 
 
 if __name__ == '__main__':

@@ -283,12 +283,16 @@ def coord_descent(population, x0=None, maxiter=50, atol=1e-5, batched=None, verb
     """coord_descent.py:206-266.  `batched`: see resolve_batched (None = automatic; batched=False is the
     reference's sweep of N sequential scipy BFGS fits, kept for comparison).  use_rop: the per-neuron fits of the
     sequential sweep run Newton-CG on device Hessian-vector products (parallel_coord_descent.py:62-63); with
-    batched=None it selects that sweep."""
+    batched=None it selects that sweep.  use_rop with batched='torch' runs the sweep as ONE lock-step Newton-CG fit of all
+    neurons on the GPU (inference/batched_newton_cg.py); there is no numpy lock-step Newton: batched=True raises."""
     N = population.model['N']
     if use_rop and batched is None:
         batched = False
-    if use_rop and batched:
-        raise ValueError("use_rop runs on the sequential sweep (batched=False)")
+    if use_rop and batched and batched != 'torch':
+        raise ValueError("use_rop runs on the sequential sweep (batched=False) or the GPU lock-step sweep (batched='torch')")
+    if use_rop and batched == 'torch':
+        from theano_pyglm_amd.inference import batched_newton_cg
+        batched_newton_cg._check(population)                  # unsupported packing / time shard: before any device work
     batched = resolve_batched(population, batched)
     network = population.network
     if not isinstance(network.graph, CompleteGraphModel):
@@ -302,14 +306,16 @@ def coord_descent(population, x0=None, maxiter=50, atol=1e-5, batched=None, verb
         print("Initial LP=%.2f." % lp)
     net_inf_prms = prep_first_order_network_inference(population)
     glm_inf_prms = prep_first_order_glm_inference(population)
-    hessp = prep_second_order_glm_inference(population) if use_rop else None
+    hessp = prep_second_order_glm_inference(population) if use_rop and not batched else None
     x = x0
     lp_prev = lp                                      # x is x0: the value just computed
     converged = False
     it = 0
     while not converged and it < maxiter:
         it += 1
-        if batched == 'torch':
+        if batched == 'torch' and use_rop:
+            batched_newton_cg.fit_glms_newton_cg_torch(population, x, verbose=verbose)
+        elif batched == 'torch':
             from theano_pyglm_amd.inference.batched_bfgs import fit_glms_batched_torch
             fit_glms_batched_torch(population, x, verbose=verbose)
         elif batched:
