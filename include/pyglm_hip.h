@@ -402,13 +402,17 @@ int pgl_set_stream(pgl_handle h, void* stream);
  * forward and again in the backward phase of the 3-phase path is listed twice).
  * stim: 0 none / dense stimulus columns, 1 separable by the tap-rate kernels, 2 separable at the frame rate (stimulus
  * current inside the fused forward where that form exists), 3 at the frame rate through the slab.  path: 0 ll+grad,
- * 1 ll only, 2 the forward launches of pgl_gibbs_prepare_all.  The reference has no counterpart (Theano picks its own
- * C implementations); tests hold every reachable instantiation to zero bytes of scratch. */
+ * 1 ll only, 2 the forward launches of pgl_gibbs_prepare_all, 3 the launches of pgl_hvp_prepare_dev /
+ * pgl_hvp_prepare_list_dev over these neurons (k_hvp5<.., 1> or the forward-only K-split launches), 4 the launches of
+ * pgl_hvp_apply_dev after such a prepare (k_hvp5<.., 0> + pass 2 of k_fused5, or the forward-only and backward-only K-split
+ * launches of every column slice).  Paths 3 / 4 with stim >= 1 return PGL_ERR_UNSUPPORTED, as the calls themselves.
+ * The reference has no counterpart (Theano picks its own C implementations); tests hold every reachable instantiation to
+ * zero bytes of scratch. */
 int pgl_plan_kernels(int N, int B, int R, int Dstim, long long nT, int stim, int n_lo, int count, int path, int opt_kernel,
                      int opt_f32, char* out, int cap);
 
 /* The fused kernel instantiations the handle's last pgl_ll_grad / pgl_ll_grad_dev / pgl_ll_grad_list_dev /
- * pgl_gibbs_prepare_all call launched, one per line in `out`, in launch order and in the format of pgl_plan_kernels
+ * pgl_gibbs_prepare_all / pgl_hvp_prepare_* / pgl_hvp_apply_dev call launched, one per line in `out`, in launch order and in the format of pgl_plan_kernels
  * (which enqueues the same launch sequence on a device-less context).  Needs PGL_OPT_RECORD_KERNELS = 1 on the handle
  * (PGL_ERR_STATE otherwise).  Dev / test entry point: tests compare it with the dry run. */
 int pgl_last_kernels(pgl_handle h, char* out, int cap);

@@ -90,6 +90,18 @@ def test_dispatched_kernels_exist_and_use_no_scratch():
     assert not dead, "built but not reachable by any plan: %s" % dead
     spill = sorted((n, r['scratch'], r['spill_vgpr']) for n, r in built.items() if r['scratch'] > 0 or r['spill_vgpr'] > 0)
     assert not spill, "kernels with scratch / spilled VGPRs: %s" % spill
+    # the Hessian-vector paths (pgl_hvp_prepare_* / pgl_hvp_apply_dev: paths 3 / 4 of the dry run): every instantiation
+    # they reach is in the library, with no scratch and no spilled VGPRs; every k_hvp5 built is reachable
+    hauto, hreach, _ = RK.hvp_reachable_both()
+    assert len(hauto) >= 20 and set(hauto) <= set(hreach)
+    assert sum(n.startswith('k_hvp5<') for n in hreach) == 14
+    missing = sorted(n for n in hreach if n not in built)
+    assert not missing, "reachable by a Hessian-vector product but not built: %s" % missing
+    bad = sorted((n, built[n]['scratch'], built[n]['spill_vgpr']) for n in hreach
+                 if built[n]['scratch'] != 0 or built[n]['spill_vgpr'] != 0)
+    assert not bad, "Hessian-vector kernels with scratch / spilled VGPRs: %s" % bad
+    dead = sorted(n for n in built if n.startswith('k_hvp5<') and n not in hreach)
+    assert not dead, "k_hvp5 instantiations built but not reachable: %s" % dead
     # the named configurations dispatch to the kernels DESIGN.md names
     from theano_pyglm_amd import _lib
     assert _lib.plan_kernels(128, B=5, R=200, nT=600000) == ['k_fused5<18, 22, 1, 0, 0, 0>', 'k_fused5<18, 22, 2, 0, 0, 0>']

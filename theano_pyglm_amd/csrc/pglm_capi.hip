@@ -1040,7 +1040,7 @@ static void launch_sepf(int which, const SepfParams& sp, hipStream_t s)
 extern "C" {
 
 const char* pgl_last_error(void) { return g_err.c_str(); }
-int pgl_version(void) { return 102; }
+int pgl_version(void) { return 103; }
 
 int pgl_device_count(void)
 {
@@ -2935,7 +2935,9 @@ int pgl_last_kernels(pgl_handle h, char* out, int cap)
 // ll(+grad) evaluation of `count` neurons starting at n_lo -- a range, or a list -- of a population of this shape would
 // launch, one per line in `out`.  stim: 0 none / dense stimulus columns (Dstim of them), 1 separable stimulus by the
 // tap-rate kernels, 2 separable at the frame rate with the stimulus current inside the fused forward where that form
-// exists, 3 at the frame rate through the slab.  path: 0 ll+grad, 1 ll only, 2 the forward launches of pgl_gibbs_prepare_all.
+// exists, 3 at the frame rate through the slab.  path: 0 ll+grad, 1 ll only, 2 the forward launches of pgl_gibbs_prepare_all,
+// 3 the launches of pgl_hvp_prepare_*, 4 those of pgl_hvp_apply_dev after such a prepare (k_hvp5 and the fused kernels around
+// it; stim >= 1: PGL_ERR_UNSUPPORTED, as the real call).
 int pgl_plan_kernels(int N, int B, int R, int Dstim, long long nT, int stim, int n_lo, int count, int path, int opt_kernel,
                      int opt_f32, char* out, int cap)
 {
@@ -2952,9 +2954,24 @@ int pgl_plan_kernels(int N, int B, int R, int Dstim, long long nT, int stim, int
     // the evaluation itself, enqueued on the device-less context: the launch sequence is the one a real call takes
     std::vector<std::string> names;
     double dummy = 0;
-    g_dry = &names;
-    const int rc = (path == 2) ? enqueue_gibbs_forward(&c)
-                               : enqueue_ll_grad(&c, n_lo, n_lo + count, nullptr, nullptr, &dummy, path == 0 ? &dummy : nullptr);
+    int rc = PGL_OK;
+    if (path == 3 || path == 4) {
+        // pgl_hvp_prepare_* (3), pgl_hvp_apply_dev after such a prepare (4): the apply takes range and path from the prepare
+        if (c.sep) return fail(PGL_ERR_UNSUPPORTED, "Hessian-vector products with a separable stimulus");
+        std::vector<std::string> prep;
+        g_dry = (path == 3) ? &names : &prep;
+        rc = enqueue_hvp_prepare(&c, n_lo, n_lo + count, nullptr, nullptr);
+        if (rc == PGL_OK && path == 4) {
+            c.hvp_n_lo = n_lo;
+            c.hvp_count = count;
+            g_dry = &names;
+            rc = enqueue_hvp_apply(&c, nullptr, &dummy);
+        }
+    } else {
+        g_dry = &names;
+        rc = (path == 2) ? enqueue_gibbs_forward(&c)
+                         : enqueue_ll_grad(&c, n_lo, n_lo + count, nullptr, nullptr, &dummy, path == 0 ? &dummy : nullptr);
+    }
     g_dry = nullptr;
     // (under g_dry nothing but a launch switch without a case for the plan fails with PGL_ERR_HIP)
     if (rc == PGL_ERR_HIP) return fail(PGL_ERR_UNSUPPORTED, "no kernel instantiation for this plan");

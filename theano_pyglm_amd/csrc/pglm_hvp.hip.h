@@ -11,15 +11,17 @@
 // ---------------------------------------------------------------------------
 // c(x, s), all f64 (pgl_exp / pgl_log / pgl_rcp).
 //   exp:        c = -dt e^x, x clamped at 709 (the largest x with a finite e^x): c is always finite, a zero u = f . v
-//               never meets an infinite weight; x -> -inf gives c = -0.
+//               never meets an infinite weight; x -> -inf gives c = -0 (x clamped at -800 as well: pgl_exp(-inf) is NaN,
+//               k ln2 - inf in its range reduction).
 //   explinear:  lam = log(1 + e^x), sig = 1 / (1 + e^-x), with e = e^-|x| and inv = 1 / (1 + e):
 //               lam'' = sig (1 - sig) = e inv^2 (both signs of x),
 //               (log lam)'' = sig (1 - sig) / lam - sig^2 / lam^2 = sig / lam^2 . ((1 - sig) lam - sig)
 //                 x >= 0:  inv^2 (e lam - 1) / lam^2                                    (no cancellation: e lam << 1)
 //                 x <  0:  e inv^2 (lam - e) / lam^2, and for e < 1e-2 by the series of log1p (lam - e cancels and lam -> 0):
 //                          lam = e l(e), lam - e = -e^2 q(e) / 2  =>  -(e / 2) inv^2 q(e) / l(e)^2
-//               Limits: x -> +inf (x clamped at DBL_MAX): c = 0;  x -> -inf: e = 0, c = 0 (the reference's
-//               0/0 at lam == 0 is NOT reproduced: the limit of (log lam)'' is -e^x / 2 -> 0);  x = NaN: c = NaN.
+//               Limits (|x| clamped at 800 inside the exponential, see above): x -> +inf (x clamped at DBL_MAX): c = 0;
+//               x -> -inf: e = 0, c = 0 (the reference's 0/0 at lam == 0 is NOT reproduced: the limit of (log lam)'' is
+//               -e^x / 2 -> 0);  x = NaN: c = NaN.
 // ---------------------------------------------------------------------------
 template <typename CP>
 __device__ __forceinline__ double pgl_curvature(const double x, const double s, const int nlin, const double dt, const CP C)
@@ -27,7 +29,7 @@ __device__ __forceinline__ double pgl_curvature(const double x, const double s, 
     double c;
     if (nlin == 1) {
         const double xc = fmin(x, 1.7976931348623157e308);
-        const double e = pgl_exp(-fabs(xc), C);
+        const double e = pgl_exp(-fmin(fabs(x), 800.0), C);     // (e^-800 = 0; pgl_exp's range reduction makes inf - inf beyond)
         const double u = 1.0 + e;
         const double inv = pgl_rcp(u);
         const double i2 = inv * inv;
@@ -55,7 +57,7 @@ __device__ __forceinline__ double pgl_curvature(const double x, const double s, 
             c = fma(s, h, c);
         }
     } else {
-        c = -dt * pgl_exp(fmin(x, 709.0), C);
+        c = -dt * pgl_exp(fmax(fmin(x, 709.0), -800.0), C);
     }
     return (x != x) ? x : c;
 }
