@@ -11,6 +11,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 static thread_local std::string g_err;
@@ -19,9 +20,10 @@ static int fail(int code, const std::string& msg)
     g_err = msg;
     return code;
 }
-// Names of the fused kernel instantiations an evaluation launches, as the code object's demangled symbol reads (dry_record):
-//  g_dry -- dry run of the dispatch (pgl_plan_kernels): the evaluation is enqueued on a context without a device, the
-//           launch_* templates record what they would launch and launch nothing, every other device operation is skipped;
+// Names of the fused kernel instantiations an evaluation launches, as the code object's demangled symbol reads (dry_record,
+// pglm_launch.h):
+//  g_dry -- dry run of the dispatch (pgl_plan_kernels): the evaluation is enqueued on a context without a device,
+//           launch_kernel records what it would launch and launches nothing, every other device operation is skipped;
 //  g_rec -- PGL_OPT_RECORD_KERNELS: a real evaluation records what it launches (pgl_last_kernels).
 static thread_local std::vector<std::string>* g_dry = nullptr;
 static thread_local std::vector<std::string>* g_rec = nullptr;
@@ -171,728 +173,10 @@ static bool img_room(const pgl_context* h, size_t want)
         if (rc_ != PGL_OK) return rc_;           \
     } while (0)
 
-struct Plan {
-    int npost, nPT, wpb, nPB, KT, KS, rsf, RP, nTiles, nChunks, tilesPerChunk, blocks, threads;
-    int tile0;
-    int version, PTW, KTW, KSPLIT, cap; // version 2/3: K split over KSPLIT waves per post tile
-    int ktl, kth;                       // version 5: k-tiles of the L / H column parts
-    int hlp = 0;                        // version 5: 1 = idle waves of a 5- or 6-tile block help (k_fused5<.., HLP = 1>)
-    int pb_major = 0;                   // version 5, wide: post-block-major grid of one chunk per CU and post block
-    int mt;                             // version 6: 16-bin tiles per step
-    int nw6;                            // version 6: waves per workgroup (8, or 4 with two workgroups per CU)
-    int sb6 = 0;                        // version 6: 1 = one image buffer per workgroup (k_fused6 DB = 0), 2 = per-wave block
-                                        // rings on block-form images (k_fused8)
-    int img32 = 0;                      // ... whose blocks are stored as f32 (PGL_OPT_FEATURE_F32 = 2)
-    int nw7, wg7;                       // version 7: waves per workgroup (1, 2, 4), workgroups per CU
-    size_t lds7x = 0;                   // version 7: extra LDS of the separable-stimulus forms
-    size_t lds;
-    bool f32;
-};
-
-// A launch covers a slice of the feature columns: presynaptic neurons [np0, np0+Ns) and dense
-// stimulus columns [ds0, ds0+Ds).  One slice = everything when N <= 128 and N*B + Dstim <= 640
-// (the fused path); otherwise the 3-phase path runs forward / backward launches per slice.
-struct Slice {
-    int np0, Ns, ds0, Ds;
-};
-
-static std::vector<Slice> make_slices(const pgl_context* h, bool balanced = false)
-{
-    std::vector<Slice> out;
-    int maxNs = std::min(128, (h->opt_slice_cols > 0 ? h->opt_slice_cols : 640) / h->B);
-    // balanced: slices of equal width (N = 160: 80 + 80, not 128 + 32) -- every slice then has a long enough feature row for
-    // the two-pass kernel on resident tiles (the wide-population path).  The K-split kernel of the other sliced paths pads
-    // its rows to 5 / 10 / 20 / 40 k-tiles and is better off with full 640-column slices and a short last one.
-    if (balanced && h->N > maxNs) maxNs = (h->N + (h->N + maxNs - 1) / maxNs - 1) / ((h->N + maxNs - 1) / maxNs);
-    int ds_left = h->sep ? 0 : h->Dstim, ds0 = 0;      // a separable stimulus is not a set of feature columns
-    for (int np0 = 0; np0 < h->N; np0 += maxNs) {
-        Slice sl{np0, std::min(maxNs, h->N - np0), 0, 0};
-        if (np0 + sl.Ns >= h->N && ds_left > 0 && sl.Ns * h->B + ds_left <= 640) {
-            sl.ds0 = ds0; sl.Ds = ds_left; ds0 += ds_left; ds_left = 0;     // stimulus rides along
-        }
-        out.push_back(sl);
-    }
-    while (ds_left > 0) {
-        const int d = std::min(640, ds_left);
-        out.push_back(Slice{0, 0, ds0, d});
-        ds0 += d; ds_left -= d;
-    }
-    return out;
-}
-
-static const int kKTW[] = {1, 2, 3, 5, 7, 10, 20};
-static const int kKTH[] = {1, 2, 3, 5, 7, 10, 13, 16};         // k-tiles per half, two-pass kernel (on the fly)
-// resident-tile kernel: (L, H) k-tile pairs; pass 1 (forward + L columns of G) gets the smaller share
-#ifndef PGL_SPLIT_L
-#define PGL_SPLIT_L 18       // L / H k-tiles of the 40-k-tile (K = 640) split; measured: 18/22 (see docs/NOTEBOOK.md §4.1)
-#endif
-static const int kKTP[][2] = {{1, 1}, {2, 2}, {3, 3}, {5, 5}, {7, 7}, {9, 11}, {12, 14}, {14, 18},
-                              {PGL_SPLIT_L, 40 - PGL_SPLIT_L}};
-static bool pick_pair(int need, int& ktl, int& kth)
-{
-    for (const auto& pr : kKTP)
-        if (pr[0] + pr[1] >= need) {
-            ktl = pr[0];
-            kth = pr[1];
-            return true;
-        }
-    return false;
-}
-static size_t img_pair_bytes(int ktl, int kth) { return (size_t)pgl_img_bytes(ktl) + pgl_img_bytes(kth); }
-// one-part images (k_fused6 / 7), padded rows or the block form of k_fused8: slot key and bytes per tile
-// (blk: 0 padded rows, 1 blocks of 2 KB, 2 the same blocks stored as f32)
-static int img_key6(int kt, int blk) { return (blk ? 0x8000 : 0) | (blk == 2 ? 0x4000 : 0) | kt << 8; }
-static size_t img_bytes6(int kt, int blk) { return blk ? (size_t)kt * (blk == 2 ? 1024 : 2048) : (size_t)pgl_img_bytes(kt); }
-static constexpr int kRing8 = 8;            // k_fused8<5, kRing8>: blocks per wave
-static size_t lds_fused8(int slots) { return (size_t)8 * slots * 2048 + (size_t)(8 * 256 + 256 + 32 + 8 * 48) * 8; }
-
-static int fused6_wg_per_cu(const Plan& pl);
-
-static int make_plan(const pgl_context* h, int n_lo, int n_hi, const Slice& sl, Plan& pl,
-                     bool single_slice = true, bool force7 = false, bool wide = false)
-{
-    const bool hlp_ok = (single_slice || wide) && !force7;      // (the slab-input form of a separable stimulus has no helper variant)
-    if (n_lo < 0 || n_hi > h->N || n_lo >= n_hi) return fail(PGL_ERR_ARG, "bad neuron range");
-    pl.npost = n_hi - n_lo;
-    pl.nPT = (pl.npost + 15) / 16;
-    const int ktot_s = sl.Ns * h->B + sl.Ds;
-    const int need = std::max(1, (ktot_s + 15) / 16);
-    pl.f32 = h->opt_f32 != 0;
-    // version 2: f64 features, 8 waves (2 per SIMD), one workgroup per CU
-    // version 3: the same kernel with f32 features / basis taps (PGL_OPT_FEATURE_F32)
-    // version 1: the 4-wave kernel of the first round (PGL_OPT_KERNEL = 1)
-    // version 4: the two-pass kernel (one workgroup = 8 post tiles, no K split; PGL_OPT_KERNEL 0 = auto
-    //            for >= 5 post tiles, 3 = force, 2 = force version 2); f64 features, one slice only
-    pl.version = pl.f32 ? 3 : 2;
-    if (pl.version == 2 && single_slice && need >= 2) {
-        if (h->opt_kernel == 3) pl.version = 4;
-        // two-pass kernel on resident tiles from 5 post tiles on; from 3 when the feature row is too long for
-        // the resident K-split kernel (measured at K = 640: 64 neurons 2.05 ms against 2.33 ms of k_fused2; a 48-neuron
-        // list of a lock-step sweep at C3: 2.36 ms on k_fused2)
-        // (force7 with a feature row too long for k_fused7 (> 16 k-tiles: its G no longer fits the registers beside the
-        // epilogue) -- e.g. a short neuron list of a wide separable-stimulus population: the slab-input form of the two-pass
-        // kernel, whatever the number of post tiles)
-        else if (h->opt_kernel == 4 || (h->opt_kernel == 0 && (pl.nPT >= 5 || (pl.nPT >= 3 && need > 20))) ||
-                 (force7 && need > 16 && (h->opt_kernel == 0 || h->opt_kernel == 7)))
-            pl.version = 5;
-    }
-    // wide: one column slice of a wide population on the resident-tile two-pass kernel (select_plans has checked the
-    // row lengths and the memory)
-    if (wide) pl.version = 5;
-    pl.tile0 = (int)(h->t_lo / 16);
-    pl.nTiles = (int)((h->t_hi + 15) / 16) - pl.tile0;
-    pl.ktl = pl.kth = 0;
-    if (pl.version == 5 && !pick_pair(need, pl.ktl, pl.kth)) pl.version = 4;
-    if (pl.version == 5 && !wide && h->opt_kernel == 0 && find_img(h, pl.ktl << 8 | pl.kth, pl.tile0, pl.nTiles) < 0) {
-        // resident feature tiles need nTiles * (L + H image bytes) of HBM (3.1 GB at C3); in auto mode
-        // fall back to on-the-fly generation (version 4) when the device cannot spare them
-        if (!img_room(h, (size_t)pl.nTiles * img_pair_bytes(pl.ktl, pl.kth))) pl.version = 4;
-    }
-    // the in-kernel-feature two-pass kernel carries at most 16 k-tiles per half in its registers (k_fused3<20, ..> spilled
-    // 22 VGPRs): rows of 33-40 k-tiles go to the K-split kernel, which is as fast there (2.20 against 2.16 ms at N = 128)
-    if (pl.version == 4 && (need + 1) / 2 > 16) pl.version = 2;
-    pl.RP = h->Rk + 32;
-    if (pl.version == 3) {
-        while (pl.RP % 64 != 8) ++pl.RP;  // f32 table rows one 32-byte span apart (mod 256 B)
-    } else {
-        // bank spread of the per-basis table rows for ds_read_b128: the row-interleaved items of
-        // gen_items want the rows of b = 0..3 four 16-byte slots (64 B) apart
-        while (pl.RP % 32 != 8) ++pl.RP;
-    }
-    pl.cap = PGL_CAP;
-    if (pl.version == 5) {
-        pl.PTW = 8; pl.KSPLIT = 1; pl.KTW = pl.kth; pl.KT = pl.ktl + pl.kth; pl.wpb = 8;
-        pl.nPB = (pl.nPT + 7) / 8;
-    } else if (pl.version == 4) {
-        const int needh = (need + 1) / 2;
-        int kth = 0;
-        for (int k : kKTH)
-            if (k >= needh) {
-                kth = k;
-                break;
-            }
-        if (kth == 0) return fail(PGL_ERR_UNSUPPORTED, "slice exceeds 640 feature columns");
-        pl.PTW = 8; pl.KSPLIT = 1; pl.KTW = kth; pl.KT = 2 * kth; pl.wpb = 8;
-        pl.nPB = (pl.nPT + 7) / 8;
-    } else {
-        const int nw = 8;
-        const int maxptw = 4;
-        pl.PTW = (pl.nPT >= 3) ? 4 : pl.nPT;
-        pl.PTW = std::min(pl.PTW, maxptw);
-        if (h->opt_ptw == 1 || h->opt_ptw == 2 || h->opt_ptw == 4) pl.PTW = std::min(h->opt_ptw, pl.PTW);
-        pl.KSPLIT = nw / pl.PTW;
-        const int needw = (need + pl.KSPLIT - 1) / pl.KSPLIT;
-        pl.KTW = 0;
-        for (int k : kKTW)
-            if (k >= needw) {
-                pl.KTW = k;
-                break;
-            }
-        if (pl.KTW == 0 || pl.KTW * pl.KSPLIT > 40)
-            return fail(PGL_ERR_UNSUPPORTED,
-                        "slice of " + std::to_string(ktot_s) + " feature columns exceeds 640");
-        pl.KT = pl.KTW * pl.KSPLIT;
-        pl.wpb = nw;
-        pl.nPB = (pl.nPT + pl.PTW - 1) / pl.PTW;
-        // version 6: the K-split scheme on resident feature tiles (k_fused6) when two step buffers of
-        // whole-row images fit the LDS: short feature rows (C1, C2, C5).  Post blocks of one or two tiles
-        // run as 4-wave workgroups, two per CU (less padding of K, barrier waits overlap).
-        pl.mt = 0;
-        pl.nw6 = 8;
-        if (pl.version == 2 && single_slice && (h->opt_kernel == 0 || h->opt_kernel == 6) && h->opt_ptw == 0) {
-            int ptw6 = pl.PTW, nw6 = 8, ktw6 = pl.KTW;
-            if (pl.nPT <= 2) {
-                nw6 = 4;
-                ptw6 = pl.nPT;
-                const int needw6 = (need + nw6 / ptw6 - 1) / (nw6 / ptw6);
-                ktw6 = 0;
-                for (int k : kKTW)
-                    if (k >= needw6 && k <= 10) {
-                        ktw6 = k;
-                        break;
-                    }
-                if (ktw6 == 0) { nw6 = 8; ptw6 = pl.PTW; ktw6 = pl.KTW; }
-            }
-            const int kt6 = ktw6 * (nw6 / ptw6);
-            int mt6 = 0;
-            for (int mt = (nw6 == 4 ? 1 : 2); mt >= 1 && mt6 == 0; --mt) {
-                const size_t lds6 = (size_t)2 * mt * pgl_img_bytes(kt6) + (size_t)mt * nw6 * 2048 + 256 + (size_t)nw6 * 384;
-                const size_t cap = (nw6 == 4) ? 80 * 1024 : 160 * 1024;      // two 4-wave workgroups per CU
-                if (lds6 <= cap && (mt == 1 || pl.nTiles >= 4)) mt6 = mt;
-            }
-            if (mt6 == 0 && nw6 == 4) {                                      // does not fit twice: 8-wave form
-                nw6 = 8; ptw6 = pl.PTW; ktw6 = pl.KTW;
-                const int kt8 = ktw6 * (8 / ptw6);
-                for (int mt = 2; mt >= 1 && mt6 == 0; --mt) {
-                    const size_t lds6 = (size_t)2 * mt * pgl_img_bytes(kt8) + (size_t)mt * 8 * 2048 + 256 + (size_t)8 * 384;
-                    if (lds6 <= 160 * 1024 && (mt == 1 || pl.nTiles >= 4)) mt6 = mt;
-                }
-            }
-            pl.sb6 = 0;
-            if (mt6 == 0 && pl.nPT <= 2 && h->opt_sb6 != 2) {
-                // the row does not fit twice (K = 640: 81 KB per tile): two post tiles -> 8-wave form with ONE image buffer
-                // (<10,2>: 4-way K split); one post tile -> 8-way K split with a private block ring per wave (k_fused8<5, 8>)
-                nw6 = 8; ptw6 = pl.nPT;
-                const int needw8 = (need + 8 / ptw6 - 1) / (8 / ptw6);
-                ktw6 = (ptw6 == 1) ? 5 : 10;
-                const size_t lds1 = (size_t)pgl_img_bytes(ktw6 * (8 / ptw6)) + (size_t)8 * 2048 + 256 + (size_t)8 * 384;
-                if (needw8 <= ktw6 && needw8 > ktw6 / 2 && lds1 <= 160 * 1024) {
-                    mt6 = 1;
-                    // one post tile: every wave streams its own K slice through a private block ring (k_fused8) -- the
-                    // HBM stream never stops for the fragment read-out (0.615 against 0.665 ms for a 16-neuron shard of C3)
-                    pl.sb6 = (ptw6 == 1) ? 2 : 1;
-                }
-            }
-            if (mt6 > 0) {
-                const int ktall = ktw6 * (nw6 / ptw6);
-                bool ok = true;
-                pl.img32 = (pl.sb6 == 2 && h->opt_img32) ? 1 : 0;
-                const int blk6 = (pl.sb6 == 2) ? 1 + pl.img32 : 0;
-                if (h->opt_kernel == 0 && find_img(h, img_key6(ktall, blk6), pl.tile0, pl.nTiles) < 0)
-                    ok = img_room(h, (size_t)pl.nTiles * img_bytes6(ktall, blk6));
-                if (!ok) pl.sb6 = pl.img32 = 0;
-                if (ok) {
-                    pl.version = 6;
-                    pl.mt = mt6; pl.nw6 = nw6; pl.PTW = ptw6; pl.KTW = ktw6; pl.KSPLIT = nw6 / ptw6;
-                    pl.KT = ktall; pl.wpb = nw6;
-                    pl.nPB = (pl.nPT + pl.PTW - 1) / pl.PTW;
-                }
-            }
-        }
-    }
-    // version 7: no K split at all -- one wave per post tile carries the whole feature row (<= 20 k-tiles)
-    // through forward, epilogue and backward; small workgroups, several per CU (k_fused7)
-    static const int kKT7[] = {1, 2, 3, 5, 7, 10, 12, 13, 16};
-    pl.nw7 = 0;
-    pl.wg7 = 1;
-    // (measured, tools/small_shape_scan.py / config_table.py: 3-4 post tiles 46 TFLOP/s against 39 of the
-    // K-split kernel at C5; with 1-2 post tiles only 2-6 waves fit a CU and the 4-wave K-split form wins -- except one
-    // post tile of 4-5 k-tiles (N = 16 at B = 5: 0.065 against 0.083 ms, tools/shape_sweep.py).  Rows of 17-20 k-tiles
-    // (N = 52..64 at B = 5) stay with the K-split kernel: 160 registers of G beside the epilogue spill (9-108 VGPRs
-    // by variant) and k_fused6 is the faster one there anyway, 0.49 against 0.57 ms at N = 64)
-    if ((pl.version == 2 || pl.version == 6) && !pl.f32 && single_slice && pl.nPT <= 4 && need <= 16 &&
-        ((h->opt_kernel == 0 && (pl.nPT >= 3 || (pl.nPT == 1 && need >= 4 && need <= 5))) || h->opt_kernel == 7 || force7) &&
-        h->opt_ptw == 0) {
-        int kt7 = 0;
-        for (int k : kKT7)
-            if (k >= need) {
-                kt7 = k;
-                break;
-            }
-        const int nw7 = (pl.nPT >= 3 || force7) ? 4 : pl.nPT;       // force7: the slab-input form exists for 4 waves only
-        // (force7 = separable stimulus: + the per-wave accumulators of the fused stimulus backward, k_fused7<.., 3>)
-        const size_t lds7 = (size_t)2 * pgl_img_bytes(kt7) + 256 + (size_t)nw7 * 192 * 8 + (force7 ? (size_t)nw7 * 320 * 8 : 0);
-        bool ok = kt7 > 0 && lds7 <= 160 * 1024;
-        if (ok && h->opt_kernel == 0 && find_img(h, kt7 << 8, pl.tile0, pl.nTiles) < 0)
-            ok = img_room(h, (size_t)pl.nTiles * pgl_img_bytes(kt7));
-        if (ok) {
-            pl.version = 7;
-            pl.nw7 = nw7;
-            pl.wg7 = (int)std::max<size_t>(1, std::min<size_t>((size_t)160 * 1024 / lds7, (size_t)(8 / nw7)));
-            // one-wave workgroups: five to seven per CU put two waves on some SIMDs and one on the others -- the kernel ends
-            // with the doubly loaded SIMDs while the others idle (N = 16: exits spread over 28 .. 67 us); one wave per SIMD
-            // and longer chunks: 0.0876 -> 0.0828 ms per evaluation (tools/shape_sweep.py, chunk-count scan of round 6)
-            if (nw7 == 1 && pl.wg7 > 4 && pl.wg7 < 8) pl.wg7 = 4;
-            pl.PTW = nw7; pl.KSPLIT = 1; pl.KTW = kt7; pl.KT = kt7; pl.wpb = nw7;
-            pl.nPB = (pl.nPT + nw7 - 1) / nw7;
-            pl.mt = 0;
-            pl.lds7x = force7 ? (size_t)nw7 * 320 * 8 : 0;
-        }
-    }
-    pl.KS = pl.KT * 4;
-    const int kpad = pl.KT * 16;
-    pl.rsf = pl.f32 ? kpad + 4 : kpad + 2;
-    int wgPerCU = (pl.version == 7) ? pl.wg7 : 1;
-    if (pl.version == 6) {
-        // as many workgroups per CU as registers and LDS allow (4-wave form at C2: three)
-        pl.lds = (size_t)(pl.sb6 ? 1 : 2) * pl.mt * pgl_img_bytes(pl.KT) + (size_t)pl.mt * pl.nw6 * 2048 + 256 + (size_t)pl.nw6 * 384;
-        if (pl.sb6 == 2) pl.lds = lds_fused8(pl.img32 ? 5 : kRing8);
-        wgPerCU = (pl.sb6 == 2) ? 1 : fused6_wg_per_cu(pl);
-    }
-    int target = h->opt_nchunks > 0 ? h->opt_nchunks : std::max(1, wgPerCU * h->numCU / pl.nPB);
-    // a wide population whose last post block holds one to six tiles (N = 144, 160, 192, 200, 320 ..): with the post blocks of a
-    // chunk side by side, half the CUs (a third, ..) carry the light blocks and idle behind them (N = 160: 0.45 of the
-    // peak).  One chunk per CU and post block, post-block-major: the dispatcher hands every CU a full block first and a
-    // light one behind it -- balanced whatever the cost ratio (dev option 91 = 1: the chunk-major grid)
-    pl.pb_major = (wide && pl.version == 5 && pl.nPB > 1 && pl.nPT % 8 >= 1 && pl.nPT % 8 <= 6 && h->opt_nchunks == 0 &&
-                   h->opt_pbmajor != 1) ? 1 : 0;
-    if (pl.pb_major) target = h->numCU;
-    target = std::min(target, pl.nTiles);
-    if (h->opt_nchunks == 0 && wgPerCU > 1) {
-        // short recordings: a chunk keeps >= 8 tiles as long as every CU still gets a workgroup (per-chunk
-        // prologue, partial write-out and the reduction over chunks are paid per chunk)
-        // (one-wave workgroups -- a single post tile on k_fused7 -- have a light prologue and fill a SIMD each: chunks from
-        //  four tiles on, every SIMD a wave; N = 16, T = 60 s: 0.047 -> 0.042 ms per evaluation, T = 20 s: 0.035 -> 0.033)
-        const bool one_wave = pl.version == 7 && pl.nw7 == 1;
-        const int floor_t = std::min(std::max(1, (one_wave ? 4 : 1) * h->numCU / pl.nPB), pl.nTiles);
-        target = std::min(target, std::max(floor_t, pl.nTiles / (one_wave ? 4 : 8)));
-    }
-    pl.tilesPerChunk = (pl.nTiles + target - 1) / target;
-    pl.nChunks = (pl.nTiles + pl.tilesPerChunk - 1) / pl.tilesPerChunk;
-    pl.blocks = pl.nChunks * pl.nPB;
-    pl.threads = 64 * pl.wpb;
-    const size_t esz = pl.f32 ? 4 : 8;
-    size_t off = ((size_t)16 * pl.rsf * esz + 15) & ~(size_t)15;
-    if (pl.version == 5) {
-        pl.lds = (size_t)2 * pgl_img_bytes(pl.ktl) + pgl_img_bytes(pl.kth) + 256 + 8 * 192 * 8;   // + per-wave spike scratch
-        // the last block leaves waves without a post tile: they help (rows from 10 k-tiles on; dev option 92 = 1: never)
-        const int nb = pl.nPT % 8;
-        // (measured, r06_shape_sweep*.md / r06_shard_steps.txt: five or six tiles +7 .. 12 %; a light block of one or two tiles
-        //  at the end of a wide population +4 .. 5 %; three tiles of a single slice (a 48-neuron range of C3) +5 %, but -2 % as the
-        //  last block of a wide population, whose full blocks pay for the helper form; four tiles: the helpers share their
-        //  tile's SIMD, +-0)
-        const bool nb_ok = nb == 5 || nb == 6 || (wide ? (nb == 1 || nb == 2) : nb == 3);
-        pl.hlp = (hlp_ok && nb_ok && pl.ktl >= 5 && h->opt_hlp != 1) ? 1 : 0;
-        if (pl.hlp) pl.lds += 4 * 256 * 8;                                                         // + the helpers' partial currents
-        if (pl.lds > 160 * 1024) return fail(PGL_ERR_UNSUPPORTED, "LDS budget exceeded");
-        return PGL_OK;
-    }
-    if (pl.version == 7) {
-        pl.lds = (size_t)2 * pgl_img_bytes(pl.KT) + 256 + (size_t)pl.nw7 * 192 * 8 + pl.lds7x;
-        return PGL_OK;
-    }
-    if (pl.version == 6) {
-        pl.lds = (size_t)(pl.sb6 ? 1 : 2) * pl.mt * pgl_img_bytes(pl.KT) + (size_t)pl.mt * pl.nw6 * 2048 + 256 + (size_t)pl.nw6 * 384;
-        if (pl.sb6 == 2) pl.lds = lds_fused8(pl.img32 ? 5 : kRing8);
-        // chunks are whole steps of mt tiles
-        pl.tilesPerChunk = (pl.tilesPerChunk + pl.mt - 1) / pl.mt * pl.mt;
-        pl.nChunks = (pl.nTiles + pl.tilesPerChunk - 1) / pl.tilesPerChunk;
-        pl.blocks = pl.nChunks * pl.nPB;
-        return PGL_OK;
-    }
-    if (pl.version == 4) {
-        const int c0 = pl.KTW * 16;
-        const int rsfh = c0 + ((c0 % 32 == 0) ? 16 : 32);
-        off = std::max(off, (((size_t)2 * 16 * rsfh * 8) + 15) & ~(size_t)15);
-        off += (((size_t)2 * h->B * pl.RP * 8) + 15) & ~(size_t)15;
-        off += (size_t)sl.Ns * pl.cap * 8;
-        off += 2 * ((((size_t)2 * sl.Ns * 4) + 15) & ~(size_t)15);
-        off += (((size_t)sl.Ns * 4) + 15) & ~(size_t)15;
-        off += 256;
-        pl.lds = off;
-        if (pl.lds > 160 * 1024) return fail(PGL_ERR_UNSUPPORTED, "LDS budget exceeded");
-        return PGL_OK;
-    }
-    off += (((size_t)2 * h->B * pl.RP * esz) + 15) & ~(size_t)15;
-    off += (size_t)sl.Ns * pl.cap * 8;
-    off += 2 * ((((size_t)2 * sl.Ns * 4) + 15) & ~(size_t)15);
-    off += (((size_t)sl.Ns * 4) + 15) & ~(size_t)15;                       // ring-valid flags
-    off += (size_t)pl.wpb * 256 * 8 + (size_t)pl.PTW * 256 * 8 + 256;
-    pl.lds = off;
-    if (pl.lds > 160 * 1024) return fail(PGL_ERR_UNSUPPORTED, "LDS budget exceeded");
-    return PGL_OK;
-}
-
-// Dry run of the dispatch (pgl_plan_kernels): when g_dry is set the launch_* templates record the name of the kernel
-// instantiation they would launch (as the code object's demangled symbol reads) and launch nothing.  The recorded set
-// over a grid of shapes is the set of instantiations the dispatcher can reach: tests/test_capi_symbols.py holds every
-// one of them to zero bytes of scratch, tools/reachable_kernels.py diffs it against the built library.  When g_rec is set
-// instead (a real evaluation with PGL_OPT_RECORD_KERNELS), the name is recorded the same way and the launch goes ahead:
-// returns true when the caller must NOT launch.
-static bool dry_record(const char* fam, std::initializer_list<int> args, const char* tail = nullptr)
-{
-    if (!g_dry && !g_rec) return false;
-    std::string n = std::string(fam) + "<";
-    bool first = true;
-    for (int a : args) {
-        if (!first) n += ", ";
-        n += std::to_string(a);
-        first = false;
-    }
-    if (tail) n += std::string(", ") + tail;
-    n += ">";
-    (g_dry ? g_dry : g_rec)->push_back(n);
-    return g_dry != nullptr;
-}
-
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) costs several microseconds of host time: it is issued once per
-// kernel instantiation and device (and again only for a larger size), not on every launch -- the small configurations
-// are bound by the host's submission rate (tools/step_bench.py)
-template <typename K>
-static hipError_t ensure_dyn_lds(K kern, size_t bytes)
-{
-    static std::map<std::pair<const void*, int>, size_t> have;      // (kernel, device) -> size already granted
-    static std::mutex mu;                                           // ctypes drops the GIL: one handle per thread is legal
-    std::lock_guard<std::mutex> lock(mu);
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    size_t& h = have[std::make_pair(reinterpret_cast<const void*>(kern), dev)];
-    if (bytes <= h) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)bytes);
-    if (e == hipSuccess) h = bytes;
-    return e;
-}
-
-template <int KTW, int PTW, int NW, int CAP, typename FT>
-static hipError_t launch_fused2_t(const Plan& pl, const FusedParams& fp, hipStream_t s)
-{
-    if (dry_record("k_fused2", {KTW, PTW, NW, CAP}, sizeof(FT) == 4 ? "float" : "double")) return hipSuccess;
-    auto kern = k_fused2<KTW, PTW, NW, CAP, FT>;
-    hipError_t e = ensure_dyn_lds(kern, pl.lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(pl.blocks), dim3(NW * 64), pl.lds, s, fp);
-    return hipGetLastError();
-}
-
-template <int PTW, int NW, int CAP, typename FT>
-static hipError_t launch_fused2_k(const Plan& pl, const FusedParams& fp, hipStream_t s)
-{
-    constexpr int KSPLIT = NW / PTW;
-    switch (pl.KTW) {
-    case 1: return launch_fused2_t<1, PTW, NW, CAP, FT>(pl, fp, s);
-    case 2: return launch_fused2_t<2, PTW, NW, CAP, FT>(pl, fp, s);
-    case 3: return launch_fused2_t<3, PTW, NW, CAP, FT>(pl, fp, s);
-    case 5: return launch_fused2_t<5, PTW, NW, CAP, FT>(pl, fp, s);
-    case 7: if constexpr (7 * KSPLIT <= 40) return launch_fused2_t<7, PTW, NW, CAP, FT>(pl, fp, s); break;
-    case 10: if constexpr (10 * KSPLIT <= 40) return launch_fused2_t<10, PTW, NW, CAP, FT>(pl, fp, s); break;
-    case 20: if constexpr (20 * KSPLIT <= 40) return launch_fused2_t<20, PTW, NW, CAP, FT>(pl, fp, s); break;
-    }
-    return hipErrorInvalidValue;
-}
-
-template <int KTH>
-static hipError_t launch_fused3_t(const Plan& pl, const FusedParams& fp, hipStream_t s)
-{
-    if (g_dry || g_rec) {
-        dry_record("k_fused3", {KTH, PGL_CAP, 1});
-        if (fp.want_grad) dry_record("k_fused3", {KTH, PGL_CAP, 2});
-        if (g_dry) return hipSuccess;
-    }
-    auto k1 = k_fused3<KTH, PGL_CAP, 1>;
-    auto k2 = k_fused3<KTH, PGL_CAP, 2>;
-    hipError_t e = ensure_dyn_lds(k1, pl.lds);
-    if (e == hipSuccess) e = ensure_dyn_lds(k2, pl.lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k1, dim3(pl.blocks), dim3(512), pl.lds, s, fp);
-    e = hipGetLastError();
-    if (e != hipSuccess || !fp.want_grad) return e;
-    hipLaunchKernelGGL(k2, dim3(pl.blocks), dim3(512), pl.lds, s, fp);   // second pass: other half of G
-    return hipGetLastError();
-}
-
-static hipError_t launch_fused3(const Plan& pl, const FusedParams& fp, hipStream_t s)
-{
-    switch (pl.KTW) {
-    case 1: return launch_fused3_t<1>(pl, fp, s);
-    case 2: return launch_fused3_t<2>(pl, fp, s);
-    case 3: return launch_fused3_t<3>(pl, fp, s);
-    case 5: return launch_fused3_t<5>(pl, fp, s);
-    case 7: return launch_fused3_t<7>(pl, fp, s);
-    case 10: return launch_fused3_t<10>(pl, fp, s);
-    case 13: return launch_fused3_t<13>(pl, fp, s);
-    case 16: return launch_fused3_t<16>(pl, fp, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-// passes: 1, 2, or 0 = both back to back
-template <int KTL, int KTH, int XIN = 0, int HLP = 0>
-static hipError_t launch_fused5_t(const Plan& pl, const FusedParams& fp, hipStream_t s, int pass)
-{
-    if (g_dry || g_rec) {
-        if (pass != 2) dry_record("k_fused5", {KTL, KTH, 1, XIN, 0, HLP});
-        if (pass != 1 && fp.want_grad) dry_record("k_fused5", {KTL, KTH, 2, 0, 0, HLP});
-        if (g_dry) return hipSuccess;
-    }
-    auto k1 = k_fused5<KTL, KTH, 1, XIN, 0, HLP>;
-    auto k2 = k_fused5<KTL, KTH, 2, 0, 0, HLP>;
-    const size_t lds2 = (size_t)2 * pgl_img_bytes(KTH) + 256;
-    hipError_t e = ensure_dyn_lds(k1, pl.lds);
-    if (e == hipSuccess) e = ensure_dyn_lds(k2, lds2);
-    if (e != hipSuccess) return e;
-    if (pass != 2) {
-        hipLaunchKernelGGL(k1, dim3(pl.blocks), dim3(512), pl.lds, s, fp);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    if (pass != 1 && fp.want_grad) {
-        hipLaunchKernelGGL(k2, dim3(pl.blocks), dim3(512), lds2, s, fp);
-        e = hipGetLastError();
-    }
-    return e;
-}
-
-static hipError_t launch_fused5(const Plan& pl, const FusedParams& fp, hipStream_t s, int pass = 0)
-{
-    if (pl.hlp) {                                // blocks of five or six post tiles: the idle waves help (make_plan)
-        switch (pl.ktl << 8 | pl.kth) {
-        case 5 << 8 | 5: return launch_fused5_t<5, 5, 0, 1>(pl, fp, s, pass);
-        case 7 << 8 | 7: return launch_fused5_t<7, 7, 0, 1>(pl, fp, s, pass);
-        case 9 << 8 | 11: return launch_fused5_t<9, 11, 0, 1>(pl, fp, s, pass);
-        case 12 << 8 | 14: return launch_fused5_t<12, 14, 0, 1>(pl, fp, s, pass);
-        case 14 << 8 | 18: return launch_fused5_t<14, 18, 0, 1>(pl, fp, s, pass);
-        case PGL_SPLIT_L << 8 | (40 - PGL_SPLIT_L): return launch_fused5_t<PGL_SPLIT_L, 40 - PGL_SPLIT_L, 0, 1>(pl, fp, s, pass);
-        }
-        return hipErrorInvalidValue;
-    }
-    switch (pl.ktl << 8 | pl.kth) {
-    case 1 << 8 | 1: return launch_fused5_t<1, 1>(pl, fp, s, pass);
-    case 2 << 8 | 2: return launch_fused5_t<2, 2>(pl, fp, s, pass);
-    case 3 << 8 | 3: return launch_fused5_t<3, 3>(pl, fp, s, pass);
-    case 5 << 8 | 5: return launch_fused5_t<5, 5>(pl, fp, s, pass);
-    case 7 << 8 | 7: return launch_fused5_t<7, 7>(pl, fp, s, pass);
-    case 9 << 8 | 11: return launch_fused5_t<9, 11>(pl, fp, s, pass);
-    case 12 << 8 | 14: return launch_fused5_t<12, 14>(pl, fp, s, pass);
-    case 14 << 8 | 18: return launch_fused5_t<14, 18>(pl, fp, s, pass);
-    case PGL_SPLIT_L << 8 | (40 - PGL_SPLIT_L): return launch_fused5_t<PGL_SPLIT_L, 40 - PGL_SPLIT_L>(pl, fp, s, pass);
-    }
-    return hipErrorInvalidValue;
-}
-
-// slab-input form of pass 1 (separable stimulus at the frame rate, 65 .. 128 neurons: at least 5 post tiles of >= 2 bases)
-static hipError_t launch_fused5_xin(const Plan& pl, const FusedParams& fp, hipStream_t s, int pass = 0)
-{
-    switch (pl.ktl << 8 | pl.kth) {
-    case 5 << 8 | 5: return launch_fused5_t<5, 5, 1>(pl, fp, s, pass);
-    case 7 << 8 | 7: return launch_fused5_t<7, 7, 1>(pl, fp, s, pass);
-    case 9 << 8 | 11: return launch_fused5_t<9, 11, 1>(pl, fp, s, pass);
-    case 12 << 8 | 14: return launch_fused5_t<12, 14, 1>(pl, fp, s, pass);
-    case 14 << 8 | 18: return launch_fused5_t<14, 18, 1>(pl, fp, s, pass);
-    case PGL_SPLIT_L << 8 | (40 - PGL_SPLIT_L): return launch_fused5_t<PGL_SPLIT_L, 40 - PGL_SPLIT_L, 1>(pl, fp, s, pass);
-    }
-    return hipErrorInvalidValue;
-}
-
-// column slices of a wide population (N > 128 or more than 640 feature columns) on resident tiles.  mode 0: forward only,
-// the slice's partial currents written to the slab; 1: forward only, added to the slab; 2: the last slice -- pass 1 from the
-// slab (epilogue, residuals out, G of its L columns); 3: pass 2 on the H part; 4: pass 2 on the L part (the gradient of the
-// L columns of a slice whose pass 1 was forward only)
-template <int KTL, int KTH, int HLP = 0>
-static hipError_t launch_fused5_wide_t(const Plan& pl, const FusedParams& fp, hipStream_t s, int mode)
-{
-    const size_t lds2h = (size_t)2 * pgl_img_bytes(KTH) + 256, lds2l = (size_t)2 * pgl_img_bytes(KTL) + 256;
-    if (g_dry || g_rec) {
-        if (mode <= 1) dry_record("k_fused5", {KTL, KTH, 1, mode == 0 ? 2 : 3, 0, HLP});
-        else if (mode == 2) dry_record("k_fused5", {KTL, KTH, 1, 1, 0, HLP});
-        else dry_record("k_fused5", {KTL, KTH, 2, 0, mode == 4 ? 1 : 0, HLP});
-        if (g_dry) return hipSuccess;
-    }
-    hipError_t e = hipSuccess;
-    if (mode == 0) {
-        auto k = k_fused5<KTL, KTH, 1, 2, 0, HLP>;
-        if ((e = ensure_dyn_lds(k, pl.lds)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(pl.blocks), dim3(512), pl.lds, s, fp);
-    } else if (mode == 1) {
-        auto k = k_fused5<KTL, KTH, 1, 3, 0, HLP>;
-        if ((e = ensure_dyn_lds(k, pl.lds)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(pl.blocks), dim3(512), pl.lds, s, fp);
-    } else if (mode == 2) {
-        auto k = k_fused5<KTL, KTH, 1, 1, 0, HLP>;
-        if ((e = ensure_dyn_lds(k, pl.lds)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(pl.blocks), dim3(512), pl.lds, s, fp);
-    } else if (mode == 3) {
-        auto k = k_fused5<KTL, KTH, 2, 0, 0, HLP>;
-        if ((e = ensure_dyn_lds(k, lds2h)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(pl.blocks), dim3(512), lds2h, s, fp);
-    } else {
-        auto k = k_fused5<KTL, KTH, 2, 0, 1, HLP>;
-        if ((e = ensure_dyn_lds(k, lds2l)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(pl.blocks), dim3(512), lds2l, s, fp);
-    }
-    return hipGetLastError();
-}
-static hipError_t launch_fused5_wide(const Plan& pl, const FusedParams& fp, hipStream_t s, int mode)
-{
-    if (pl.hlp) {                                // the last post block holds one to six tiles: its idle waves help (make_plan)
-        switch (pl.ktl << 8 | pl.kth) {
-        case 5 << 8 | 5: return launch_fused5_wide_t<5, 5, 1>(pl, fp, s, mode);
-        case 7 << 8 | 7: return launch_fused5_wide_t<7, 7, 1>(pl, fp, s, mode);
-        case 9 << 8 | 11: return launch_fused5_wide_t<9, 11, 1>(pl, fp, s, mode);
-        case 12 << 8 | 14: return launch_fused5_wide_t<12, 14, 1>(pl, fp, s, mode);
-        case 14 << 8 | 18: return launch_fused5_wide_t<14, 18, 1>(pl, fp, s, mode);
-        case PGL_SPLIT_L << 8 | (40 - PGL_SPLIT_L): return launch_fused5_wide_t<PGL_SPLIT_L, 40 - PGL_SPLIT_L, 1>(pl, fp, s, mode);
-        }
-        return hipErrorInvalidValue;
-    }
-    switch (pl.ktl << 8 | pl.kth) {
-    case 5 << 8 | 5: return launch_fused5_wide_t<5, 5>(pl, fp, s, mode);
-    case 7 << 8 | 7: return launch_fused5_wide_t<7, 7>(pl, fp, s, mode);
-    case 9 << 8 | 11: return launch_fused5_wide_t<9, 11>(pl, fp, s, mode);
-    case 12 << 8 | 14: return launch_fused5_wide_t<12, 14>(pl, fp, s, mode);
-    case 14 << 8 | 18: return launch_fused5_wide_t<14, 18>(pl, fp, s, mode);
-    case PGL_SPLIT_L << 8 | (40 - PGL_SPLIT_L): return launch_fused5_wide_t<PGL_SPLIT_L, 40 - PGL_SPLIT_L>(pl, fp, s, mode);
-    }
-    return hipErrorInvalidValue;
-}
-
-// fused apply / forward-only curvature pass of the Hessian-vector product on resident tiles (k_hvp5): the column pairs the
-// automatic dispatch gives a call of >= 65 neurons (pick_pair from 5 k-tiles on)
-template <int KTL, int KTH>
-static hipError_t launch_hvp5_t(const Plan& pl, const FusedParams& fp, const double* cslab, hipStream_t s, int fwo)
-{
-    if (dry_record("k_hvp5", {KTL, KTH, fwo})) return hipSuccess;
-    constexpr size_t lds = (size_t)2 * pgl_img_bytes(KTL) + pgl_img_bytes(KTH);
-    auto k0 = k_hvp5<KTL, KTH, 0>;
-    auto k1 = k_hvp5<KTL, KTH, 1>;
-    hipError_t e = ensure_dyn_lds(fwo ? k1 : k0, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(fwo ? k1 : k0, dim3(pl.blocks), dim3(512), lds, s, fp, cslab);
-    return hipGetLastError();
-}
-
-static hipError_t launch_hvp5(const Plan& pl, const FusedParams& fp, const double* cslab, hipStream_t s, int fwo)
-{
-    switch (pl.ktl << 8 | pl.kth) {
-    case 3 << 8 | 3: return launch_hvp5_t<3, 3>(pl, fp, cslab, s, fwo);
-    case 5 << 8 | 5: return launch_hvp5_t<5, 5>(pl, fp, cslab, s, fwo);
-    case 7 << 8 | 7: return launch_hvp5_t<7, 7>(pl, fp, cslab, s, fwo);
-    case 9 << 8 | 11: return launch_hvp5_t<9, 11>(pl, fp, cslab, s, fwo);
-    case 12 << 8 | 14: return launch_hvp5_t<12, 14>(pl, fp, cslab, s, fwo);
-    case 14 << 8 | 18: return launch_hvp5_t<14, 18>(pl, fp, cslab, s, fwo);
-    case PGL_SPLIT_L << 8 | (40 - PGL_SPLIT_L): return launch_hvp5_t<PGL_SPLIT_L, 40 - PGL_SPLIT_L>(pl, fp, cslab, s, fwo);
-    }
-    return hipErrorInvalidValue;
-}
-
-// Instantiations of the switch below that no plan of make_plan selects (tools/reachable_kernels.py: dry run of the
-// dispatch over a grid of shapes, with and without forcing options) are not built; tests/test_capi_symbols.py fails when a
-// reachable instantiation is missing from the library, so a change of make_plan shows up here.
-constexpr bool fused6_built(int KTW, int PTW, int MT, int NW)
-{
-    if (NW == 4) return MT == 1 && ((PTW == 1 && KTW <= 3) || (PTW == 2 && KTW <= 7));
-    if (MT == 2) return PTW == 4 && KTW >= 2 && KTW <= 7;
-    // (four post tiles, one tile per step: the long-row form, and every row length on recordings of fewer than four tiles)
-    return (PTW == 1 && (KTW == 2 || KTW == 3)) || (PTW == 2 && (KTW == 5 || KTW == 7)) || (PTW == 4 && KTW >= 2);
-}
-constexpr bool fused7_built(int KT, int NWV, int XIO)
-{
-    return !(XIO == 0 && ((KT == 1 && NWV >= 2) || (KT == 2 && NWV == 4)));
-}
-
-// occ != nullptr: no launch, *occ = workgroups of this instantiation a CU holds with pl.lds bytes of LDS
-template <int KTW, int PTW, int MT, int NW, int DB = 1>
-static hipError_t launch_fused6_t(const Plan& pl, const FusedParams& fp, hipStream_t s, int* occ)
-{
-    constexpr size_t need = (size_t)(DB ? 2 : 1) * MT * pgl_img_bytes(KTW * (NW / PTW)) + (size_t)MT * NW * 2048 + 256 + (size_t)NW * 384;
-    if constexpr (need <= 160 * 1024 && KTW * 4 <= 40 && (DB == 0 || fused6_built(KTW, PTW, MT, NW))) {
-        auto kern = k_fused6<KTW, PTW, MT, NW, DB>;
-        if (!occ && dry_record("k_fused6", {KTW, PTW, MT, NW, DB})) return hipSuccess;
-        if (occ && g_dry) return hipErrorInvalidValue;           // (dry run: no device to ask; the caller's default holds)
-        hipError_t e = ensure_dyn_lds(kern, pl.lds);
-        if (e != hipSuccess) return e;
-        if (occ) return hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, kern, NW * 64, pl.lds);
-        hipLaunchKernelGGL(kern, dim3(pl.blocks), dim3(NW * 64), pl.lds, s, fp);
-        return hipGetLastError();
-    } else {
-        return hipErrorInvalidValue;
-    }
-}
-
-template <int PTW, int MT, int NW>
-static hipError_t launch_fused6_k(const Plan& pl, const FusedParams& fp, hipStream_t s, int* occ)
-{
-    switch (pl.KTW) {
-    case 1: return launch_fused6_t<1, PTW, MT, NW>(pl, fp, s, occ);
-    case 2: return launch_fused6_t<2, PTW, MT, NW>(pl, fp, s, occ);
-    case 3: return launch_fused6_t<3, PTW, MT, NW>(pl, fp, s, occ);
-    case 5: return launch_fused6_t<5, PTW, MT, NW>(pl, fp, s, occ);
-    case 7: return launch_fused6_t<7, PTW, MT, NW>(pl, fp, s, occ);
-    case 10: return launch_fused6_t<10, PTW, MT, NW>(pl, fp, s, occ);
-    }
-    return hipErrorInvalidValue;
-}
-
-static hipError_t launch_fused6(const Plan& pl, const FusedParams& fp, hipStream_t s, int* occ = nullptr)
-{
-    if (pl.nw6 == 4) {
-        switch (pl.PTW * 4 + pl.mt) {
-        case 1 * 4 + 1: return launch_fused6_k<1, 1, 4>(pl, fp, s, occ);
-        case 2 * 4 + 1: return launch_fused6_k<2, 1, 4>(pl, fp, s, occ);
-        }
-        return hipErrorInvalidValue;
-    }
-    if (pl.sb6 == 2) {                             // one post tile of a 25 .. 40 k-tile row: per-wave block rings
-        if (pl.mt != 1 || pl.PTW != 1 || pl.KTW != 5 || occ) return hipErrorInvalidValue;
-        if (dry_record("k_fused8", {5, kRing8, pl.img32})) return hipSuccess;
-        if (pl.img32) {
-            auto kern = k_fused8<5, kRing8, 1>;
-            hipError_t e = ensure_dyn_lds(kern, pl.lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kern, dim3(pl.blocks), dim3(512), pl.lds, s, fp);
-            return hipGetLastError();
-        }
-        auto kern = k_fused8<5, kRing8, 0>;
-        hipError_t e = ensure_dyn_lds(kern, pl.lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(pl.blocks), dim3(512), pl.lds, s, fp);
-        return hipGetLastError();
-    }
-    if (pl.sb6) {                                  // one image buffer: 640-column rows for two post tiles
-        if (pl.mt == 1 && pl.PTW == 2 && pl.KTW == 10) return launch_fused6_t<10, 2, 1, 8, 0>(pl, fp, s, occ);
-        return hipErrorInvalidValue;
-    }
-    switch (pl.PTW * 4 + pl.mt) {
-    case 1 * 4 + 1: return launch_fused6_k<1, 1, 8>(pl, fp, s, occ);
-    case 1 * 4 + 2: return launch_fused6_k<1, 2, 8>(pl, fp, s, occ);
-    case 2 * 4 + 1: return launch_fused6_k<2, 1, 8>(pl, fp, s, occ);
-    case 2 * 4 + 2: return launch_fused6_k<2, 2, 8>(pl, fp, s, occ);
-    case 4 * 4 + 1: return launch_fused6_k<4, 1, 8>(pl, fp, s, occ);
-    case 4 * 4 + 2: return launch_fused6_k<4, 2, 8>(pl, fp, s, occ);
-    }
-    return hipErrorInvalidValue;
-}
-
-// workgroups per CU of the k_fused6 instantiation a plan selects (registers and LDS), cached per shape
-static int fused6_wg_per_cu(const Plan& pl)
-{
-    // dry run (pgl_plan_kernels): no device to ask -- the default, and neither read nor written to the cache, so that the
-    // answer does not depend on what real evaluations of this process have cached.  (Occupancy sets the number of time
-    // chunks only, never which instantiation a plan launches: the dry run's names hold on any device.)
-    if (g_dry) return (pl.nw6 == 4) ? 2 : 1;
-    // occupancy is a property of the kernel and the architecture (every device of a node is the same gfx950 part)
-    static int cache[2][11][5][3][9];          // [sb6][KTW][PTW][mt][nw6]; 0 = not asked yet
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lock(mu);
-    int& c = cache[pl.sb6 ? 1 : 0][pl.KTW][pl.PTW][pl.mt][pl.nw6];
-    if (c == 0) {
-        int occ = 0;
-        FusedParams fp{};
-        if (launch_fused6(pl, fp, nullptr, &occ) != hipSuccess || occ < 1) occ = (pl.nw6 == 4) ? 2 : 1;
-        c = occ;
-    }
-    return c;
-}
+// the planner (Plan, Slice, the k-tile lists, make_plan, select_plans, hvp_select) and the launch layer (dry_record,
+// launch_kernel, dispatch, the launchers of the fused kernels): both need the context above
+#include "pglm_plan.h"
+#include "pglm_launch.h"
 
 // workgroups of k_gibbs_rate_cols a CU holds at `lds` bytes of dynamic LDS (occupancy query, cached per size)
 static int gibbs_rate_wg_per_cu(size_t lds)
@@ -908,113 +192,6 @@ static int gibbs_rate_wg_per_cu(size_t lds)
         c = occ;
     }
     return c;
-}
-
-template <int KT, int NWV, int XIO = 0>
-static hipError_t launch_fused7_t(const Plan& pl, const FusedParams& fp, hipStream_t s)
-{
-    if constexpr (fused7_built(KT, NWV, XIO)) {
-        if (dry_record("k_fused7", {KT, NWV, XIO})) return hipSuccess;
-        auto kern = k_fused7<KT, NWV, XIO>;
-        hipError_t e = ensure_dyn_lds(kern, pl.lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(pl.blocks), dim3(NWV * 64), pl.lds, s, fp);
-        return hipGetLastError();
-    } else {
-        return hipErrorInvalidValue;
-    }
-}
-
-template <int NWV>
-static hipError_t launch_fused7_k(const Plan& pl, const FusedParams& fp, hipStream_t s)
-{
-    switch (pl.KT) {
-    case 1: return launch_fused7_t<1, NWV>(pl, fp, s);
-    case 2: return launch_fused7_t<2, NWV>(pl, fp, s);
-    case 3: return launch_fused7_t<3, NWV>(pl, fp, s);
-    case 5: return launch_fused7_t<5, NWV>(pl, fp, s);
-    case 7: return launch_fused7_t<7, NWV>(pl, fp, s);
-    case 10: return launch_fused7_t<10, NWV>(pl, fp, s);
-    case 12: return launch_fused7_t<12, NWV>(pl, fp, s);
-    case 13: return launch_fused7_t<13, NWV>(pl, fp, s);
-    case 16: return launch_fused7_t<16, NWV>(pl, fp, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-// slab-input form (separable stimulus at the frame rate): 4-wave workgroups only
-static hipError_t launch_fused7_xio(const Plan& pl, const FusedParams& fp, hipStream_t s, int xio = 1)
-{
-    if (pl.nw7 != 4) return hipErrorInvalidValue;
-    if (xio == 3) {                              // ... and its backward inside the kernel as well (no residual slab)
-        switch (pl.KT) {
-        case 1: return launch_fused7_t<1, 4, 3>(pl, fp, s);
-        case 2: return launch_fused7_t<2, 4, 3>(pl, fp, s);
-        case 3: return launch_fused7_t<3, 4, 3>(pl, fp, s);
-        case 5: return launch_fused7_t<5, 4, 3>(pl, fp, s);
-        case 7: return launch_fused7_t<7, 4, 3>(pl, fp, s);
-        case 10: return launch_fused7_t<10, 4, 3>(pl, fp, s);
-        case 12: return launch_fused7_t<12, 4, 3>(pl, fp, s);
-        }
-        return hipErrorInvalidValue;
-    }
-    if (xio == 2) {                              // stimulus current inside the forward contraction
-        switch (pl.KT) {
-        case 1: return launch_fused7_t<1, 4, 2>(pl, fp, s);
-        case 2: return launch_fused7_t<2, 4, 2>(pl, fp, s);
-        case 3: return launch_fused7_t<3, 4, 2>(pl, fp, s);
-        case 5: return launch_fused7_t<5, 4, 2>(pl, fp, s);
-        case 7: return launch_fused7_t<7, 4, 2>(pl, fp, s);
-        case 10: return launch_fused7_t<10, 4, 2>(pl, fp, s);
-        case 12: return launch_fused7_t<12, 4, 2>(pl, fp, s);
-        case 13: return launch_fused7_t<13, 4, 2>(pl, fp, s);
-        }
-        return hipErrorInvalidValue;
-    }
-    switch (pl.KT) {
-    case 1: return launch_fused7_t<1, 4, 1>(pl, fp, s);
-    case 2: return launch_fused7_t<2, 4, 1>(pl, fp, s);
-    case 3: return launch_fused7_t<3, 4, 1>(pl, fp, s);
-    case 5: return launch_fused7_t<5, 4, 1>(pl, fp, s);
-    case 7: return launch_fused7_t<7, 4, 1>(pl, fp, s);
-    case 10: return launch_fused7_t<10, 4, 1>(pl, fp, s);
-    case 12: return launch_fused7_t<12, 4, 1>(pl, fp, s);
-    case 13: return launch_fused7_t<13, 4, 1>(pl, fp, s);
-    case 16: return launch_fused7_t<16, 4, 1>(pl, fp, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-static hipError_t launch_fused7(const Plan& pl, const FusedParams& fp, hipStream_t s)
-{
-    switch (pl.nw7) {
-    case 1: return launch_fused7_k<1>(pl, fp, s);
-    case 2: return launch_fused7_k<2>(pl, fp, s);
-    case 4: return launch_fused7_k<4>(pl, fp, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-static hipError_t launch_fused2(const Plan& pl, const FusedParams& fp, hipStream_t s)
-{
-    if (pl.version == 7) return launch_fused7(pl, fp, s);
-    if (pl.version == 6) return launch_fused6(pl, fp, s);
-    if (pl.version == 5) return launch_fused5(pl, fp, s);
-    if (pl.version == 4) return launch_fused3(pl, fp, s);
-    if (pl.version == 3) {
-        switch (pl.PTW) {
-        case 1: return launch_fused2_k<1, 8, PGL_CAP, float>(pl, fp, s);
-        case 2: return launch_fused2_k<2, 8, PGL_CAP, float>(pl, fp, s);
-        case 4: return launch_fused2_k<4, 8, PGL_CAP, float>(pl, fp, s);
-        }
-        return hipErrorInvalidValue;
-    }
-    switch (pl.PTW) {
-    case 1: return launch_fused2_k<1, 8, PGL_CAP, double>(pl, fp, s);
-    case 2: return launch_fused2_k<2, 8, PGL_CAP, double>(pl, fp, s);
-    case 4: return launch_fused2_k<4, 8, PGL_CAP, double>(pl, fp, s);
-    }
-    return hipErrorInvalidValue;
 }
 
 // separable stimulus at the frame rate: which = 0 forward, 1 backward, 2 finish
@@ -1870,11 +1047,6 @@ static int launch_finalize_grad(pgl_handle h, const Plan& pl, const Slice& sl, i
     return PGL_OK;
 }
 
-static hipError_t launch_any(const Plan& pl, const FusedParams& fp, hipStream_t s)
-{
-    return launch_fused2(pl, fp, s);
-}
-
 // Resident feature tiles (k_build_fimg) of the evaluated time range [tile0, tile0 + ntiles) for the
 // column split (ktl, kth): built on first use and after every change of spikes / basis / stimulus
 // features / time range.  A time-sharded rank (pgl_set_time_range) therefore builds and keeps only its
@@ -1921,75 +1093,6 @@ static int ensure_feature_images(pgl_handle h, int ktl, int kth, int tile0, int 
     return PGL_OK;
 }
 
-// The path an evaluation of neurons [n_lo, n_hi) (or of a list of n_hi - n_lo neurons) takes and its launch plans:
-//   sepf   -- separable stimulus at the frame rate: impulse columns on resident tiles (k_fused7 with the slab-input form up to
-//             four post tiles, the two-pass kernel from five on or when the feature row is too long for k_fused7), the
-//             stimulus current / its gradients by k_sepf_*; neuron lists are fine there (the stimulus kernels work on the
-//             listed rows, the fused kernel maps rows to neurons).  A kernel forced by PGL_OPT_KERNEL other than 7 / 4 keeps
-//             the stimulus on the 3-phase path it asks for;
-//   sliced -- the 3-phase path (more than one slice of feature columns, or a separable stimulus by the tap-rate kernels).
-// One function for enqueue_ll_grad, pgl_info and the dry run of the dispatch (pgl_plan_kernels).
-static int select_plans(const pgl_context* h, int n_lo, int n_hi, std::vector<Slice>& slices, std::vector<Plan>& plans,
-                        bool& sepf, bool& sliced, bool* wide_out = nullptr)
-{
-    slices = make_slices(h, wide_out != nullptr);
-    plans.assign(slices.size(), Plan());
-    if (wide_out) *wide_out = false;
-    // wide -- more than one slice of feature columns (N > 128 or more than 640 columns) with every slice on the resident-tile
-    //         two-pass kernel: forward-only passes of the first slices add their currents in the slab, the last slice runs
-    //         pass 1 from the slab, then the pass-2 kernels take the gradients of all column parts from the residuals.
-    //         Needs rows of 7 .. 40 k-tiles in every slice (equal-width slices see to that from B = 2 on), no separable
-    //         stimulus, f64 features, and the memory for one image set per slice; else the in-kernel-feature path below.
-    if (wide_out && slices.size() > 1 && slices.size() <= (size_t)pgl_context::NIMG && !h->sep && !h->opt_f32 &&
-        (h->opt_kernel == 0 || h->opt_kernel == 4)) {
-        bool ok = true;
-        size_t bytes = 0;
-        for (const Slice& sl : slices) {
-            const int need = (sl.Ns * h->B + sl.Ds + 15) / 16;
-            int ktl = 0, kth = 0;
-            if (sl.Ns <= 0 || need < 7 || need > 40 || !pick_pair(need, ktl, kth)) { ok = false; break; }
-            const int tile0 = (int)(h->t_lo / 16), nTiles = (int)((h->t_hi + 15) / 16) - tile0;
-            bytes += (size_t)nTiles * img_pair_bytes(ktl, kth);
-        }
-        if (ok && h->opt_kernel == 0) {
-            // the image sets that are not resident yet must fit (with the residual slab) into 90 % of the free memory
-            size_t free_b = 0, total_b = 0, have = 0;
-            for (int i = 0; i < pgl_context::NIMG; ++i)
-                if (h->imgs[i].key >> 16) have += h->imgs[i].buf.cap;
-            if (bytes > have && hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes - have > free_b / 10 * 9) ok = false;
-        }
-        if (ok) {
-            for (size_t i = 0; i < slices.size(); ++i) {
-                int rc = make_plan(h, n_lo, n_hi, slices[i], plans[i], false, false, true);
-                if (rc) return rc;
-                if (plans[i].version != 5) ok = false;
-            }
-        }
-        if (ok) {
-            sepf = false;
-            sliced = true;
-            *wide_out = true;
-            return PGL_OK;
-        }
-    }
-    if (wide_out) {
-        slices = make_slices(h);
-        plans.assign(slices.size(), Plan());
-    }
-    sepf = h->sep && h->sepf && h->opt_sepf != 2 && slices.size() == 1 && !h->opt_f32 &&
-           (h->opt_kernel == 0 || h->opt_kernel == 7 || h->opt_kernel == 4);
-    if (sepf) {
-        int rc = make_plan(h, n_lo, n_hi, slices[0], plans[0], true, true);
-        if (rc) return rc;
-        sepf = (plans[0].version == 7 && plans[0].nw7 == 4) || (plans[0].version == 5 && plans[0].ktl >= 5);
-    }
-    for (size_t i = 0; i < slices.size() && !sepf; ++i) {
-        int rc = make_plan(h, n_lo, n_hi, slices[i], plans[i], slices.size() == 1 && !h->sep);
-        if (rc) return rc;
-    }
-    sliced = !sepf && (slices.size() > 1 || h->sep);     // else the separable stimulus rides on the 3-phase path
-    return PGL_OK;
-}
 
 // PGL_OPT_RECORD_KERNELS: the fused launches of one evaluation go to h->last_kernels while this lives
 struct KernelRecord {
@@ -2008,11 +1111,139 @@ struct KernelRecord {
 //  * otherwise the 3-phase path: per slice a forward-only launch accumulating the currents in
 //    Xbuf (nT x 16*nPT doubles), one elementwise pass Xbuf -> (ll, r), per slice a backward-only
 //    launch.  Same kernels, the F tile is simply generated twice per slice.
-// RULE: pgl_plan_kernels runs this function (and enqueue_gibbs_forward) with g_dry set on a context that has no device,
-// no stream and null buffers -- also inside processes that do have a GPU.  Every device operation on these paths must
-// therefore be skipped under g_dry: the launch_* templates record and return, ensure() allocates nothing, the helpers
-// (launch_prep, ensure_feature_images, launch_finalize_grad, sep_* / sepf_*) return at their top, and the few direct
-// launches / memsets here test g_dry themselves.  A device call added here needs the same guard.
+// RULE: pgl_plan_kernels runs enqueue_ll_grad, enqueue_hvp_prepare / _apply and enqueue_gibbs_forward with g_dry set on a
+// context that has no device, no stream and null buffers -- also inside processes that do have a GPU.  Every device operation
+// on these paths must therefore be skipped under g_dry, and the guards live in the steps the evaluations are made of, not in
+// the evaluations: launch_kernel (pglm_launch.h) records and returns, ensure() allocates nothing, the steps below and
+// launch_prep, ensure_feature_images, launch_finalize_grad, sep_* / sepf_* return at their top or test g_dry at their one
+// device call.  What is left in the enqueue_* functions themselves: the timing events (never recorded by the dry run, whose
+// context has opt_timing = 0), the sepD sizing of the fused stimulus backward and the k_hvp_curv launch, each under its own
+// test of g_dry.  A device call added to an evaluation belongs in a step with such a guard.
+
+// ---- the steps of an evaluation ----
+// per-chunk partial buffers of the fused launches (a forward-only launch still writes its -- unused -- ll partials)
+static int ensure_partials(pgl_handle h, const std::vector<Plan>& plans, bool with_G)
+{
+    size_t maxG = 0, maxLL = 0;
+    for (const Plan& pl : plans) {
+        maxG = std::max(maxG, (size_t)pl.nChunks * pl.nPT * pl.KT * 256 * 8);
+        maxLL = std::max(maxLL, (size_t)pl.nChunks * pl.nPT * pl.KSPLIT * 64 * 8);
+    }
+    ENSURE(h->llpart, maxLL);
+    ENSURE(h->gbpart, maxLL);
+    if (with_G) ENSURE(h->Gpart, maxG);
+    return PGL_OK;
+}
+
+// rows of a row-major slab (nT x xs) the time tiles of a plan cover: [row0, row1), row1 past t_hi inside the last tile
+struct RowRange {
+    int xs;
+    long long row0, row1;
+};
+static RowRange row_range(const pgl_context* h, const Plan& p0)
+{
+    return RowRange{p0.nPT * 16, (long long)p0.tile0 * 16, std::min<long long>(h->nT, (long long)(p0.tile0 + p0.nTiles) * 16)};
+}
+static int zero_slab(pgl_handle h, double* X, const RowRange& rr)
+{
+    if (g_dry) return PGL_OK;
+    HIPCHK(hipMemsetAsync(X + rr.row0 * rr.xs, 0, (size_t)(rr.row1 - rr.row0) * rr.xs * 8, h->stream));
+    return PGL_OK;
+}
+
+// residual slab of the two-pass kernels (tile-major: 256 doubles per time and post tile)
+static int ensure_tile_slab(pgl_handle h, const Plan& pl)
+{
+    const size_t need = (size_t)pl.nTiles * pl.nPT * 256 * 8;
+    const bool fresh = need > h->Xbuf.cap || !h->Xbuf.p;
+    ENSURE(h->Xbuf, need);
+    // first touch of a fresh allocation costs ~8 % of an evaluation: pay it here, once
+    if (fresh && !g_dry) HIPCHK(hipMemsetAsync(h->Xbuf.p, 0, need, h->stream));
+    return PGL_OK;
+}
+
+// the resident feature tiles a single-slice plan reads: the L / H pair of k_fused5, one-part images of k_fused6 / 7 / 8
+static int ensure_plan_images(pgl_handle h, const Plan& pl)
+{
+    if (pl.version == 5) return ensure_feature_images(h, pl.ktl, pl.kth, pl.tile0, pl.nTiles);
+    if (pl.version == 6 || pl.version == 7)
+        return ensure_feature_images(h, pl.KT, 0, pl.tile0, pl.nTiles, nullptr, 0, (pl.version == 6 && pl.sb6 == 2) ? 1 + pl.img32 : 0);
+    return PGL_OK;
+}
+
+// ll (and d ll / d bias, when d_grad) from the per-chunk partials of an evaluation without a gradient
+static int launch_finalize_ll(pgl_handle h, const Plan& pl, double* d_ll, double* d_grad)
+{
+    if (g_dry) return PGL_OK;
+    hipLaunchKernelGGL(k_finalize_ll, dim3(pl.npost), dim3(256), 0, h->stream, (const double*)h->llpart.p,
+                       (const double*)h->gbpart.p, d_ll, d_grad, 1 + h->Dstim + h->Kimp, pl.npost, pl.nPT, pl.nChunks, pl.KSPLIT);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+// phase 1 of the 3-phase path: X += F_s . W_s, one forward-only launch per column slice into the slab X of row stride xs
+static int forward_slices(pgl_handle h, const std::vector<Slice>& slices, const std::vector<Plan>& plans, int n_lo,
+                          const double* d_theta, const double* d_Weff, double* X, int xs, const char* what)
+{
+    for (size_t i = 0; i < slices.size(); ++i) {
+        int rc = launch_prep(h, plans[i], slices[i], n_lo, d_theta, d_Weff);
+        if (rc) return rc;
+        FusedParams fp;
+        fill_params(h, plans[i], slices[i], n_lo, false, 1, fp);
+        fp.Xbuf = X;
+        fp.xstride = xs;
+        hipError_t e = launch_plan(plans[i], fp, h->stream);
+        if (e != hipSuccess) return fail(PGL_ERR_HIP, std::string(what) + hipGetErrorString(e));
+    }
+    return PGL_OK;
+}
+
+// phase 2: one elementwise pass over the rows of h->Xbuf in blocks of 512 rows -- X -> (ll, r) (k_rows_epilogue), or with the
+// curvature rows c of a Hessian-vector product r = c * (u + v_bias) (k_hvp_rows_mul) --, the rows past t_hi of the last tile
+// zeroed, the per-block sums reduced into d_ll and the bias component of d_out
+static int row_pass(pgl_handle h, const Plan& p0, const RowRange& rr, int n_lo, const double* c, double* d_ll, double* d_out)
+{
+    if (g_dry) return PGL_OK;
+    const int rows = 512;
+    const long long nrows = h->t_hi - h->t_lo;
+    const int nblk = (int)((nrows + rows - 1) / rows);
+    ENSURE(h->tmpA, (size_t)nblk * p0.npost * 8);
+    ENSURE(h->tmpB, (size_t)nblk * p0.npost * 8);
+    const dim3 grid((unsigned)nblk, (unsigned)((p0.npost + 255) / 256));
+    if (c)
+        hipLaunchKernelGGL(k_hvp_rows_mul, grid, dim3(256), 0, h->stream, (double*)h->Xbuf.p, c, rr.xs, (const double*)h->bias.p,
+                           p0.npost, (long long)h->t_lo, (long long)h->t_hi, rows, (double*)h->tmpA.p, (double*)h->tmpB.p);
+    else
+        hipLaunchKernelGGL(k_rows_epilogue, grid, dim3(256), 0, h->stream, (double*)h->Xbuf.p, rr.xs, (const double*)h->bias.p,
+                           (const uint8_t*)h->S.p, h->N, n_lo, p0.npost, (long long)h->t_lo, (long long)h->t_hi, rows, h->nlin,
+                           h->dt, (double*)h->tmpA.p, (double*)h->tmpB.p, h->cur_pidx);
+    HIPCHK(hipGetLastError());
+    if (rr.row1 > h->t_hi) {
+        hipLaunchKernelGGL(k_rows_zero, dim3(64), dim3(256), 0, h->stream, (double*)h->Xbuf.p, rr.xs, (long long)h->t_hi, rr.row1);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_rows_reduce, dim3(p0.npost), dim3(64), 0, h->stream, (const double*)h->tmpA.p,
+                       (const double*)h->tmpB.p, nblk, p0.npost, 1 + h->Dstim + h->Kimp, d_ll, d_out);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+// phase 3: G_s = F_s^T . r, per column slice a backward-only launch (d_theta: geometry / bias only) and its reduction
+static int backward_slices(pgl_handle h, const std::vector<Slice>& slices, const std::vector<Plan>& plans, int n_lo,
+                           const double* d_theta, const double* d_Weff, double* d_ll, double* d_out)
+{
+    for (size_t i = 0; i < slices.size(); ++i) {
+        int rc = launch_prep(h, plans[i], slices[i], n_lo, d_theta, d_Weff);
+        if (rc) return rc;
+        FusedParams fp;
+        fill_params(h, plans[i], slices[i], n_lo, true, 2, fp);
+        hipError_t e = launch_plan(plans[i], fp, h->stream);
+        if (e != hipSuccess) return fail(PGL_ERR_HIP, std::string("backward launch: ") + hipGetErrorString(e));
+        rc = launch_finalize_grad(h, plans[i], slices[i], n_lo, d_Weff, d_ll, d_out);
+        if (rc) return rc;
+    }
+    return PGL_OK;
+}
 
 static int enqueue_ll_grad(pgl_handle h, int n_lo, int n_hi, const double* d_theta,
                            const double* d_Weff, double* d_ll, double* d_grad)
@@ -2025,15 +1256,10 @@ static int enqueue_ll_grad(pgl_handle h, int n_lo, int n_hi, const double* d_the
         int rc = select_plans(h, n_lo, n_hi, slices, plans, sepf, sliced, &wide);
         if (rc) return rc;
     }
-    size_t maxG = 0, maxLL = 0;
-    for (const Plan& pl : plans) {
-        maxG = std::max(maxG, (size_t)pl.nChunks * pl.nPT * pl.KT * 256 * 8);
-        maxLL = std::max(maxLL, (size_t)pl.nChunks * pl.nPT * pl.KSPLIT * 64 * 8);
+    {
+        int rc = ensure_partials(h, plans, d_grad != nullptr);
+        if (rc) return rc;
     }
-    ENSURE(h->llpart, maxLL);
-    ENSURE(h->gbpart, maxLL);
-    if (d_grad) ENSURE(h->Gpart, maxG);
-    const int P = 1 + h->Dstim + h->Kimp;
 
     // HIP events of this evaluation (pgl_last_timing / pgl_timing_summary): every PGL_OPT_TIMING-th call only -- an
     // event between two kernels of a stream costs ~6 us of GPU idle time (the next dispatch waits for the marker:
@@ -2049,17 +1275,16 @@ static int enqueue_ll_grad(pgl_handle h, int n_lo, int n_hi, const double* d_the
         int rc = direct ? PGL_OK : launch_prep(h, pl, slices[0], n_lo, d_theta, d_Weff);
         if (rc) return rc;
         ENSURE(h->Xbuf, (size_t)pl.nTiles * pl.nPT * 256 * 8);
-        rc = (pl.version == 5) ? ensure_feature_images(h, pl.ktl, pl.kth, pl.tile0, pl.nTiles)
-                               : ensure_feature_images(h, pl.KT, 0, pl.tile0, pl.nTiles, nullptr, 0, (pl.version == 6 && pl.sb6 == 2) ? 1 + pl.img32 : 0);
+        rc = ensure_plan_images(h, pl);
         if (rc) return rc;
         if (rec) HIPCHK(hipEventRecord(h->ev[1], h->stream));
         SepfParams sp{};
         // up to four post tiles with the (5, 3) table: the stimulus current rides in the forward contraction
-        // (beyond 13 k-tiles the five extra k-steps do not fit the registers: k_fused7<16, 4, 2> spills -- slab form there)
-        const bool fused_fwd = pl.version == 7 && pl.KT <= 13 && h->sepA_ok && h->opt_sepf != 3;
-        // ... and its backward too (k_fused7<.., 3>: no residual slab, no k_sepf_bwd) up to 12 k-tiles (registers);
+        // (where that form is built, fused7_built: up to 13 k-tiles -- slab form beyond)
+        const bool fused_fwd = pl.version == 7 && fused7_built(pl.KT, pl.nw7, 2) && h->sepA_ok && h->opt_sepf != 3;
+        // ... and its backward too (k_fused7<.., 3>: no residual slab, no k_sepf_bwd) up to 12 k-tiles;
         // dev option 94 = 4 keeps the slab form
-        const bool fused_bwd = fused_fwd && d_grad && pl.KT <= 12 && h->opt_sepf != 4;
+        const bool fused_bwd = fused_fwd && d_grad && fused7_built(pl.KT, pl.nw7, 3) && h->opt_sepf != 4;
         rc = sepf_forward(h, pl, d_theta, sp, fused_fwd);
         if (rc) return rc;
         if (fused_bwd && !g_dry) {
@@ -2090,10 +1315,10 @@ static int enqueue_ll_grad(pgl_handle h, int n_lo, int n_hi, const double* d_the
         }
         hipError_t e = hipSuccess;
         if (pl.version == 5) {                   // pass 1 (slab in, residuals out) and, for the gradient, pass 2
-            e = launch_fused5_xin(pl, fp, h->stream, 1);
-            if (e == hipSuccess && d_grad) e = launch_fused5_xin(pl, fp, h->stream, 2);
+            e = launch_fused5(pl, fp, h->stream, 1, 1);
+            if (e == hipSuccess && d_grad) e = launch_fused5(pl, fp, h->stream, 2);
         } else {
-            e = launch_fused7_xio(pl, fp, h->stream, fused_bwd ? 3 : (fused_fwd ? 2 : 1));
+            e = launch_fused7(pl, fp, h->stream, fused_bwd ? 3 : (fused_fwd ? 2 : 1));
         }
         if (e != hipSuccess) return fail(PGL_ERR_HIP, std::string("fused launch: ") + hipGetErrorString(e));
         if (d_grad) {
@@ -2106,33 +1331,20 @@ static int enqueue_ll_grad(pgl_handle h, int n_lo, int n_hi, const double* d_the
             if (rc) return rc;
         } else {
             if (rec) HIPCHK(hipEventRecord(h->ev[2], h->stream));
-            if (!g_dry) {
-                hipLaunchKernelGGL(k_finalize_ll, dim3(pl.npost), dim3(256), 0, h->stream,
-                                   (const double*)h->llpart.p, (const double*)h->gbpart.p, d_ll, d_grad, P,
-                                   pl.npost, pl.nPT, pl.nChunks, pl.KSPLIT);
-                HIPCHK(hipGetLastError());
-            }
+            rc = launch_finalize_ll(h, pl, d_ll, d_grad);
+            if (rc) return rc;
         }
     } else if (!sliced) {
         const Plan& pl = plans[0];
         const bool direct = plan_reads_theta(pl);
         int rc = direct ? PGL_OK : launch_prep(h, pl, slices[0], n_lo, d_theta, d_Weff);
         if (rc) return rc;
-        if ((pl.version == 4 || pl.version == 5) && d_grad) {   // residual slab of the two-pass kernels
-            const size_t need = (size_t)pl.nTiles * pl.nPT * 256 * 8;
-            const bool fresh = need > h->Xbuf.cap || !h->Xbuf.p;
-            ENSURE(h->Xbuf, need);
-            // first touch of a fresh allocation costs ~8 % of an evaluation: pay it here, once
-            if (fresh && !g_dry) HIPCHK(hipMemsetAsync(h->Xbuf.p, 0, need, h->stream));
-        }
-        if (pl.version == 5) {
-            rc = ensure_feature_images(h, pl.ktl, pl.kth, pl.tile0, pl.nTiles);
+        if ((pl.version == 4 || pl.version == 5) && d_grad) {
+            rc = ensure_tile_slab(h, pl);
             if (rc) return rc;
         }
-        if (pl.version == 6 || pl.version == 7) {
-            rc = ensure_feature_images(h, pl.KT, 0, pl.tile0, pl.nTiles, nullptr, 0, (pl.version == 6 && pl.sb6 == 2) ? 1 + pl.img32 : 0);
-            if (rc) return rc;
-        }
+        rc = ensure_plan_images(h, pl);
+        if (rc) return rc;
         FusedParams fp;
         fill_params(h, pl, slices[0], n_lo, d_grad != nullptr, 0, fp);
         if (direct) {
@@ -2140,37 +1352,16 @@ static int enqueue_ll_grad(pgl_handle h, int n_lo, int n_hi, const double* d_the
             fp.Weff = d_Weff;
         }
         if (rec) HIPCHK(hipEventRecord(h->ev[1], h->stream));
-        if (pl.version == 5 && d_grad) {
-            // pass 1 | pass 2 | one reduction of all per-chunk partials.  (Until round 3 the first G half was reduced on a
-            // side stream "beside" pass 2: the dispatch timeline shows that reduction finishing ~14 us AFTER pass 2 --
-            // whatever the stream priority -- and holding up the second one, 42 us in all against 30 us for a single
-            // streaming pass over both halves; at full size the difference is below the noise.)
-            hipError_t e = launch_fused5(pl, fp, h->stream, 1);
-            if (e != hipSuccess) return fail(PGL_ERR_HIP, std::string("pass 1 launch: ") + hipGetErrorString(e));
-            e = launch_fused5(pl, fp, h->stream, 2);
-            if (e != hipSuccess) return fail(PGL_ERR_HIP, std::string("pass 2 launch: ") + hipGetErrorString(e));
-            if (rec) HIPCHK(hipEventRecord(h->ev[2], h->stream));
-            rc = launch_finalize_grad(h, pl, slices[0], n_lo, d_Weff, d_ll, d_grad, true);
-            if (rc) return rc;
-            if (rec) HIPCHK(hipEventRecord(h->ev[3], h->stream));
-            h->timing_valid = rec;
-            if (rec) ++h->ev_launches;
-            return PGL_OK;
-        }
-        hipError_t e = launch_any(pl, fp, h->stream);
+        // (the two-pass kernel on resident tiles: pass 1 | pass 2 | one reduction of all per-chunk partials.  Until round 3 the
+        // first G half was reduced on a side stream "beside" pass 2: the dispatch timeline shows that reduction finishing ~14 us
+        // AFTER pass 2 -- whatever the stream priority -- and holding up the second one, 42 us in all against 30 us for a single
+        // streaming pass over both halves; at full size the difference is below the noise.)
+        hipError_t e = launch_plan(pl, fp, h->stream);
         if (e != hipSuccess) return fail(PGL_ERR_HIP, std::string("fused launch: ") + hipGetErrorString(e));
         if (rec) HIPCHK(hipEventRecord(h->ev[2], h->stream));
-        if (d_grad) {                       // one launch: G reduction + (trailing blocks) ll reduction
-            rc = launch_finalize_grad(h, pl, slices[0], n_lo, d_Weff, d_ll, d_grad, true);
-            if (rc) return rc;
-        } else {
-            if (!g_dry) {
-                hipLaunchKernelGGL(k_finalize_ll, dim3(pl.npost), dim3(256), 0, h->stream,
-                                   (const double*)h->llpart.p, (const double*)h->gbpart.p, d_ll, d_grad, P,
-                                   pl.npost, pl.nPT, pl.nChunks, pl.KSPLIT);
-                HIPCHK(hipGetLastError());
-            }
-        }
+        // with a gradient one launch: G reduction + (trailing blocks) ll reduction
+        rc = d_grad ? launch_finalize_grad(h, pl, slices[0], n_lo, d_Weff, d_ll, d_grad, true) : launch_finalize_ll(h, pl, d_ll, d_grad);
+        if (rc) return rc;
     } else if (wide) {
         // a wide population on resident tiles: one image set, one set of Wmat fragments and up to three launches of the two-pass
         // kernel per column slice; currents and residuals travel in the slab
@@ -2211,72 +1402,33 @@ static int enqueue_ll_grad(pgl_handle h, int n_lo, int n_hi, const double* d_the
                 if (rc) return rc;
             }
         } else {
-            const Plan& pl = plans[S - 1];
-            if (!g_dry) {
-                hipLaunchKernelGGL(k_finalize_ll, dim3(pl.npost), dim3(256), 0, h->stream,
-                                   (const double*)h->llpart.p, (const double*)h->gbpart.p, d_ll, d_grad, P,
-                                   pl.npost, pl.nPT, pl.nChunks, pl.KSPLIT);
-                HIPCHK(hipGetLastError());
-            }
+            int rc = launch_finalize_ll(h, plans[S - 1], d_ll, d_grad);
+            if (rc) return rc;
         }
         if (rec) HIPCHK(hipEventRecord(h->ev[2], h->stream));
     } else {
         const Plan& p0 = plans[0];
-        const int xs = p0.nPT * 16;
-        const long long row0 = (long long)p0.tile0 * 16;
-        const long long row1 = std::min<long long>(h->nT, (long long)(p0.tile0 + p0.nTiles) * 16);
-        ENSURE(h->Xbuf, (size_t)h->nT * xs * 8);
-        if (!g_dry) HIPCHK(hipMemsetAsync((double*)h->Xbuf.p + row0 * xs, 0, (size_t)(row1 - row0) * xs * 8, h->stream));
+        const RowRange rr = row_range(h, p0);
+        ENSURE(h->Xbuf, (size_t)h->nT * rr.xs * 8);
+        double* X = (double*)h->Xbuf.p;
+        int rc = zero_slab(h, X, rr);
+        if (rc) return rc;
         if (rec) HIPCHK(hipEventRecord(h->ev[1], h->stream));
         SepParams sp;
         if (h->sep) {                                          // phase 0: X = I_stim (separable stimulus)
             if (h->cur_pidx) return fail(PGL_ERR_UNSUPPORTED, "neuron lists with a separable stimulus");
-            int rc = sep_forward(h, d_theta, p0.npost, (double*)h->Xbuf.p, xs, h->t_lo, h->t_hi, sp);
+            rc = sep_forward(h, d_theta, p0.npost, X, rr.xs, h->t_lo, h->t_hi, sp);
             if (rc) return rc;
         }
-        for (size_t i = 0; i < slices.size(); ++i) {          // phase 1: X += F_s . W_s
-            int rc = launch_prep(h, plans[i], slices[i], n_lo, d_theta, d_Weff);
+        rc = forward_slices(h, slices, plans, n_lo, d_theta, d_Weff, X, rr.xs, "forward launch: ");
+        if (rc) return rc;
+        rc = row_pass(h, p0, rr, n_lo, nullptr, d_ll, d_grad);                     // X -> (ll, r)
+        if (rc) return rc;
+        if (d_grad) {
+            rc = backward_slices(h, slices, plans, n_lo, d_theta, d_Weff, d_ll, d_grad);
             if (rc) return rc;
-            FusedParams fp;
-            fill_params(h, plans[i], slices[i], n_lo, false, 1, fp);
-            hipError_t e = launch_any(plans[i], fp, h->stream);
-            if (e != hipSuccess) return fail(PGL_ERR_HIP, std::string("forward launch: ") + hipGetErrorString(e));
-        }
-        if (!g_dry) {                                          // phase 2: X -> (ll, r)
-            const int rows = 512;
-            const long long nrows = h->t_hi - h->t_lo;
-            const int nblk = (int)((nrows + rows - 1) / rows);
-            ENSURE(h->tmpA, (size_t)nblk * p0.npost * 8);
-            ENSURE(h->tmpB, (size_t)nblk * p0.npost * 8);
-            dim3 grid((unsigned)nblk, (unsigned)((p0.npost + 255) / 256));
-            hipLaunchKernelGGL(k_rows_epilogue, grid, dim3(256), 0, h->stream, (double*)h->Xbuf.p, xs,
-                               (const double*)h->bias.p, (const uint8_t*)h->S.p, h->N, n_lo, p0.npost,
-                               (long long)h->t_lo, (long long)h->t_hi, rows, h->nlin, h->dt,
-                               (double*)h->tmpA.p, (double*)h->tmpB.p, h->cur_pidx);
-            HIPCHK(hipGetLastError());
-            if (row1 > h->t_hi) {
-                hipLaunchKernelGGL(k_rows_zero, dim3(64), dim3(256), 0, h->stream, (double*)h->Xbuf.p, xs,
-                                   (long long)h->t_hi, row1);
-                HIPCHK(hipGetLastError());
-            }
-            hipLaunchKernelGGL(k_rows_reduce, dim3(p0.npost), dim3(64), 0, h->stream,
-                               (const double*)h->tmpA.p, (const double*)h->tmpB.p, nblk, p0.npost, P,
-                               d_ll, d_grad);
-            HIPCHK(hipGetLastError());
-        }
-        if (d_grad) {                                          // phase 3: G_s += F_s^T . r
-            for (size_t i = 0; i < slices.size(); ++i) {
-                int rc = launch_prep(h, plans[i], slices[i], n_lo, d_theta, d_Weff);   // only geometry/bias
-                if (rc) return rc;
-                FusedParams fp;
-                fill_params(h, plans[i], slices[i], n_lo, true, 2, fp);
-                hipError_t e = launch_any(plans[i], fp, h->stream);
-                if (e != hipSuccess) return fail(PGL_ERR_HIP, std::string("backward launch: ") + hipGetErrorString(e));
-                rc = launch_finalize_grad(h, plans[i], slices[i], n_lo, d_Weff, d_ll, d_grad);
-                if (rc) return rc;
-            }
             if (h->sep) {
-                int rc = sep_backward(h, sp, d_grad);
+                rc = sep_backward(h, sp, d_grad);
                 if (rc) return rc;
             }
         }
@@ -2313,27 +1465,9 @@ int pgl_ll_grad_list_dev(pgl_handle h, const int* d_idx, int count, const double
     return rc;
 }
 
+
 // ---- Hessian-vector products of ll (hessian_rop_wrt_list, pyglm/utils/grads.py:68-95; the hessp of map.py:38-45) ----
-// The path of a product over the prepared rows: `fused` -- one column slice on the resident-tile two-pass plan (the class of
-// k_fused5: >= 5 post tiles, or >= 3 against a long row): k_hvp5 + pass 2 of k_fused5; else the 3-phase path on the
-// K-split kernel's forward-only / backward-only launches, one set per column slice, around the row kernels of
-// pglm_hvp.hip.h.  The g_dry RULE above enqueue_ll_grad holds on these paths too.
-static int hvp_select(const pgl_context* h, int n_lo, int n_hi, std::vector<Slice>& slices, std::vector<Plan>& plans, bool& fused)
-{
-    slices = make_slices(h);
-    plans.assign(slices.size(), Plan());
-    fused = slices.size() == 1 && !h->opt_f32 && (h->opt_kernel == 0 || h->opt_kernel == 4);
-    if (fused) {
-        int rc = make_plan(h, n_lo, n_hi, slices[0], plans[0], true);
-        if (rc) return rc;
-        fused = plans[0].version == 5 && plans[0].ktl >= 3;
-    }
-    for (size_t i = 0; i < slices.size() && !fused; ++i) {
-        int rc = make_plan(h, n_lo, n_hi, slices[i], plans[i], false);
-        if (rc) return rc;
-    }
-    return PGL_OK;
-}
+// (hvp_select, pglm_plan.h, picks the path; the g_dry RULE above enqueue_ll_grad holds on these paths too)
 
 // theta -> c[t, n] of the rows [n_lo, n_hi) (or of the list h->cur_pidx) over the handle's time range, kept in h->Cbuf
 static int enqueue_hvp_prepare(pgl_handle h, int n_lo, int n_hi, const double* d_theta, const double* d_Weff)
@@ -2344,14 +1478,10 @@ static int enqueue_hvp_prepare(pgl_handle h, int n_lo, int n_hi, const double* d
     bool fused = false;
     int rc = hvp_select(h, n_lo, n_hi, slices, plans, fused);
     if (rc) return rc;
-    // (the forward-only launches of the K-split kernel still write their -- unused -- ll partials)
-    size_t maxLL = 0;
-    for (const Plan& pl : plans) maxLL = std::max(maxLL, (size_t)pl.nChunks * pl.nPT * pl.KSPLIT * 64 * 8);
-    ENSURE(h->llpart, maxLL);
-    ENSURE(h->gbpart, maxLL);
+    rc = ensure_partials(h, plans, false);
+    if (rc) return rc;
     const Plan& p0 = plans[0];
-    const int xs = p0.nPT * 16;
-    const long long row0 = (long long)p0.tile0 * 16;
+    const RowRange rr = row_range(h, p0);
     long long total = 0;
     double* cb = nullptr;
     if (fused) {
@@ -2360,7 +1490,7 @@ static int enqueue_hvp_prepare(pgl_handle h, int n_lo, int n_hi, const double* d
         cb = (double*)h->Cbuf.p;
         rc = launch_prep(h, p0, slices[0], n_lo, d_theta, d_Weff);
         if (rc) return rc;
-        rc = ensure_feature_images(h, p0.ktl, p0.kth, p0.tile0, p0.nTiles);
+        rc = ensure_plan_images(h, p0);
         if (rc) return rc;
         FusedParams fp;
         fill_params(h, p0, slices[0], n_lo, false, 0, fp);
@@ -2368,26 +1498,18 @@ static int enqueue_hvp_prepare(pgl_handle h, int n_lo, int n_hi, const double* d
         hipError_t e = launch_hvp5(p0, fp, nullptr, h->stream, 1);
         if (e != hipSuccess) return fail(PGL_ERR_HIP, std::string("curvature forward launch: ") + hipGetErrorString(e));
     } else {
-        const long long row1 = std::min<long long>(h->nT, (long long)(p0.tile0 + p0.nTiles) * 16);
-        total = (row1 - row0) * xs;
-        ENSURE(h->Cbuf, (size_t)h->nT * xs * 8);
-        cb = (double*)h->Cbuf.p + row0 * xs;
-        if (!g_dry) HIPCHK(hipMemsetAsync(cb, 0, (size_t)total * 8, h->stream));
-        for (size_t i = 0; i < slices.size(); ++i) {          // X += F_s . W_s
-            rc = launch_prep(h, plans[i], slices[i], n_lo, d_theta, d_Weff);
-            if (rc) return rc;
-            FusedParams fp;
-            fill_params(h, plans[i], slices[i], n_lo, false, 1, fp);
-            fp.Xbuf = (double*)h->Cbuf.p;
-            fp.xstride = xs;
-            hipError_t e = launch_any(plans[i], fp, h->stream);
-            if (e != hipSuccess) return fail(PGL_ERR_HIP, std::string("curvature forward launch: ") + hipGetErrorString(e));
-        }
+        total = (rr.row1 - rr.row0) * rr.xs;
+        ENSURE(h->Cbuf, (size_t)h->nT * rr.xs * 8);
+        cb = (double*)h->Cbuf.p + rr.row0 * rr.xs;
+        rc = zero_slab(h, (double*)h->Cbuf.p, rr);
+        if (rc) return rc;
+        rc = forward_slices(h, slices, plans, n_lo, d_theta, d_Weff, (double*)h->Cbuf.p, rr.xs, "curvature forward launch: ");
+        if (rc) return rc;
     }
     if (!g_dry) {                                              // x -> c in place
         const int blocks = (int)std::min<long long>((total + 255) / 256, 8 * 1024);
         hipLaunchKernelGGL(k_hvp_curv, dim3(blocks), dim3(256), 0, h->stream, cb, (const double*)h->bias.p,
-                           (const uint8_t*)h->S.p, h->N, n_lo, p0.npost, h->cur_pidx, xs, row0, (long long)h->t_hi, total,
+                           (const uint8_t*)h->S.p, h->N, n_lo, p0.npost, h->cur_pidx, rr.xs, rr.row0, (long long)h->t_hi, total,
                            fused ? 1 : 0, h->nlin, h->dt);
         HIPCHK(hipGetLastError());
     }
@@ -2407,26 +1529,17 @@ static int enqueue_hvp_apply(pgl_handle h, const double* d_v, double* d_hv)
     int rc = hvp_select(h, n_lo, n_hi, slices, plans, fused);
     if (rc) return rc;
     if (fused != h->hvp_fused) return fail(PGL_ERR_STATE, "the dispatch changed since pgl_hvp_prepare_*: prepare again");
-    size_t maxG = 0, maxLL = 0;
-    for (const Plan& pl : plans) {
-        maxG = std::max(maxG, (size_t)pl.nChunks * pl.nPT * pl.KT * 256 * 8);
-        maxLL = std::max(maxLL, (size_t)pl.nChunks * pl.nPT * pl.KSPLIT * 64 * 8);
-    }
-    ENSURE(h->llpart, maxLL);
-    ENSURE(h->gbpart, maxLL);
-    ENSURE(h->Gpart, maxG);
+    rc = ensure_partials(h, plans, true);
+    if (rc) return rc;
     ENSURE(h->hvp_ll, (size_t)h->hvp_count * 8);               // (the reductions write an "ll" beside the bias component)
     double* d_ll = (double*)h->hvp_ll.p;
-    const int P = 1 + h->Dstim + h->Kimp;
     const Plan& p0 = plans[0];
     if (fused) {
-        const size_t need = (size_t)p0.nTiles * p0.nPT * 256 * 8;
-        const bool fresh = need > h->Xbuf.cap || !h->Xbuf.p;
-        ENSURE(h->Xbuf, need);
-        if (fresh && !g_dry) HIPCHK(hipMemsetAsync(h->Xbuf.p, 0, need, h->stream));
+        rc = ensure_tile_slab(h, p0);
+        if (rc) return rc;
         rc = launch_prep(h, p0, slices[0], n_lo, d_v, d_Weff);
         if (rc) return rc;
-        rc = ensure_feature_images(h, p0.ktl, p0.kth, p0.tile0, p0.nTiles);
+        rc = ensure_plan_images(h, p0);
         if (rc) return rc;
         FusedParams fp;
         fill_params(h, p0, slices[0], n_lo, true, 0, fp);
@@ -2436,49 +1549,17 @@ static int enqueue_hvp_apply(pgl_handle h, const double* d_v, double* d_hv)
         if (e != hipSuccess) return fail(PGL_ERR_HIP, std::string("apply launch: ") + hipGetErrorString(e));
         return launch_finalize_grad(h, p0, slices[0], n_lo, d_Weff, d_ll, d_hv, true);
     }
-    const int xs = p0.nPT * 16;
-    const long long row0 = (long long)p0.tile0 * 16;
-    const long long row1 = std::min<long long>(h->nT, (long long)(p0.tile0 + p0.nTiles) * 16);
-    ENSURE(h->Xbuf, (size_t)h->nT * xs * 8);
-    if (!g_dry) HIPCHK(hipMemsetAsync((double*)h->Xbuf.p + row0 * xs, 0, (size_t)(row1 - row0) * xs * 8, h->stream));
-    for (size_t i = 0; i < slices.size(); ++i) {              // phase 1: u += F_s . V_s
-        rc = launch_prep(h, plans[i], slices[i], n_lo, d_v, d_Weff);
-        if (rc) return rc;
-        FusedParams fp;
-        fill_params(h, plans[i], slices[i], n_lo, false, 1, fp);
-        hipError_t e = launch_any(plans[i], fp, h->stream);
-        if (e != hipSuccess) return fail(PGL_ERR_HIP, std::string("forward launch: ") + hipGetErrorString(e));
-    }
-    if (!g_dry) {                                              // phase 2: r = c * (u + v_bias)
-        const int rows = 512;
-        const long long nrows = h->t_hi - h->t_lo;
-        const int nblk = (int)((nrows + rows - 1) / rows);
-        ENSURE(h->tmpA, (size_t)nblk * p0.npost * 8);
-        ENSURE(h->tmpB, (size_t)nblk * p0.npost * 8);
-        dim3 grid((unsigned)nblk, (unsigned)((p0.npost + 255) / 256));
-        hipLaunchKernelGGL(k_hvp_rows_mul, grid, dim3(256), 0, h->stream, (double*)h->Xbuf.p, (const double*)h->Cbuf.p, xs,
-                           (const double*)h->bias.p, p0.npost, (long long)h->t_lo, (long long)h->t_hi, rows,
-                           (double*)h->tmpA.p, (double*)h->tmpB.p);
-        HIPCHK(hipGetLastError());
-        if (row1 > h->t_hi) {
-            hipLaunchKernelGGL(k_rows_zero, dim3(64), dim3(256), 0, h->stream, (double*)h->Xbuf.p, xs, (long long)h->t_hi, row1);
-            HIPCHK(hipGetLastError());
-        }
-        hipLaunchKernelGGL(k_rows_reduce, dim3(p0.npost), dim3(64), 0, h->stream, (const double*)h->tmpA.p,
-                           (const double*)h->tmpB.p, nblk, p0.npost, P, d_ll, d_hv);
-        HIPCHK(hipGetLastError());
-    }
-    for (size_t i = 0; i < slices.size(); ++i) {              // phase 3: (H v)_s = F_s^T . r
-        rc = launch_prep(h, plans[i], slices[i], n_lo, d_v, d_Weff);      // only geometry / bias
-        if (rc) return rc;
-        FusedParams fp;
-        fill_params(h, plans[i], slices[i], n_lo, true, 2, fp);
-        hipError_t e = launch_any(plans[i], fp, h->stream);
-        if (e != hipSuccess) return fail(PGL_ERR_HIP, std::string("backward launch: ") + hipGetErrorString(e));
-        rc = launch_finalize_grad(h, plans[i], slices[i], n_lo, d_Weff, d_ll, d_hv);
-        if (rc) return rc;
-    }
-    return PGL_OK;
+    // the 3-phase path: u += F_s . V_s | r = c * (u + v_bias) | (H v)_s = F_s^T . r
+    const RowRange rr = row_range(h, p0);
+    ENSURE(h->Xbuf, (size_t)h->nT * rr.xs * 8);
+    double* X = (double*)h->Xbuf.p;
+    rc = zero_slab(h, X, rr);
+    if (rc) return rc;
+    rc = forward_slices(h, slices, plans, n_lo, d_v, d_Weff, X, rr.xs, "forward launch: ");
+    if (rc) return rc;
+    rc = row_pass(h, p0, rr, n_lo, (const double*)h->Cbuf.p, d_ll, d_hv);
+    if (rc) return rc;
+    return backward_slices(h, slices, plans, n_lo, d_v, d_Weff, d_ll, d_hv);
 }
 
 static int hvp_prepare_common(pgl_handle h, const int* d_idx, int n_lo, int count, const double* d_theta, const double* d_Weff)
@@ -2973,7 +2054,7 @@ int pgl_plan_kernels(int N, int B, int R, int Dstim, long long nT, int stim, int
                          : enqueue_ll_grad(&c, n_lo, n_lo + count, nullptr, nullptr, &dummy, path == 0 ? &dummy : nullptr);
     }
     g_dry = nullptr;
-    // (under g_dry nothing but a launch switch without a case for the plan fails with PGL_ERR_HIP)
+    // (under g_dry nothing but a dispatch (pglm_launch.h) without an instantiation for the plan fails with PGL_ERR_HIP)
     if (rc == PGL_ERR_HIP) return fail(PGL_ERR_UNSUPPORTED, "no kernel instantiation for this plan");
     if (rc) return rc;
     std::string all;
@@ -3205,35 +2286,25 @@ static int enqueue_gibbs_forward(pgl_handle h)
     int rc = PGL_OK;
     const std::vector<Slice> slices = make_slices(h);
     std::vector<Plan> plans(slices.size());
-    size_t maxLL = 0;
     for (size_t i = 0; i < slices.size(); ++i) {
         rc = make_plan(h, 0, N, slices[i], plans[i], false);
         if (rc) return rc;
-        maxLL = std::max(maxLL, (size_t)plans[i].nChunks * plans[i].nPT * plans[i].KSPLIT * 64 * 8);
     }
-    ENSURE(h->llpart, maxLL);
-    ENSURE(h->gbpart, maxLL);
-    const int xs = plans[0].nPT * 16;
-    ENSURE(h->GX, (size_t)h->nT * xs * 8);
-    const long long row0 = (long long)plans[0].tile0 * 16;
-    const long long row1 = std::min<long long>(h->nT, (long long)(plans[0].tile0 + plans[0].nTiles) * 16);
-    if (!g_dry) HIPCHK(hipMemsetAsync((double*)h->GX.p + row0 * xs, 0, (size_t)(row1 - row0) * xs * 8, h->stream));
+    rc = ensure_partials(h, plans, false);
+    if (rc) return rc;
+    const RowRange rr = row_range(h, plans[0]);
+    ENSURE(h->GX, (size_t)h->nT * rr.xs * 8);
+    rc = zero_slab(h, (double*)h->GX.p, rr);
+    if (rc) return rc;
     if (h->sep) {
         SepParams sp;
-        rc = sep_forward(h, (const double*)h->gtheta.p, N, (double*)h->GX.p, xs, h->t_lo, h->t_hi, sp);
+        rc = sep_forward(h, (const double*)h->gtheta.p, N, (double*)h->GX.p, rr.xs, h->t_lo, h->t_hi, sp);
         if (rc) return rc;
     }
-    for (size_t i = 0; i < slices.size(); ++i) {
-        rc = launch_prep(h, plans[i], slices[i], 0, (const double*)h->gtheta.p, (const double*)h->Weff.p);
-        if (rc) return rc;
-        FusedParams fp;
-        fill_params(h, plans[i], slices[i], 0, false, 1, fp);
-        fp.Xbuf = (double*)h->GX.p;
-        fp.xstride = xs;
-        hipError_t e = launch_any(plans[i], fp, h->stream);
-        if (e != hipSuccess) return fail(PGL_ERR_HIP, std::string("forward launch: ") + hipGetErrorString(e));
-    }
-    h->gx_xs = xs;
+    rc = forward_slices(h, slices, plans, 0, (const double*)h->gtheta.p, (const double*)h->Weff.p, (double*)h->GX.p, rr.xs,
+                        "forward launch: ");
+    if (rc) return rc;
+    h->gx_xs = rr.xs;
     h->gx_t_lo = h->t_lo;
     h->gx_t_hi = h->t_hi;
     return PGL_OK;

@@ -1,5 +1,6 @@
-"""The set of fused kernel instantiations the dispatcher can reach, from a dry run of make_plan / the launch switches over
-a grid of shapes (pgl_plan_kernels: no GPU needed), against the instantiations in the built library:
+"""The set of fused kernel instantiations the dispatcher can reach, from a dry run of make_plan (csrc/pglm_plan.h) and the
+launchers (csrc/pglm_launch.h) over a grid of shapes (pgl_plan_kernels: no GPU needed), against the instantiations in the
+built library:
 
     python tools/reachable_kernels.py            # summary + instantiations no plan reaches + reachable ones with scratch
     python tools/reachable_kernels.py --emit-cases   # rewrite tests/dispatch_cases.json (one cheap case per instantiation)
