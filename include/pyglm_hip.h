@@ -80,7 +80,8 @@ typedef struct pgl_context* pgl_handle;
 
 #define PGL_OPT_RECORD_KERNELS 96 /* dev / test: 1 = every ll(+grad) evaluation and pgl_gibbs_prepare_all records the fused kernel
                                    * instantiations it launches, in launch order (pgl_last_kernels), and so do pgl_hvp_prepare_* /
-                                   * pgl_hvp_apply_dev (k_hvp5 and the k_fused* launches around it); 0 (default) = off */
+                                   * pgl_hvp_apply_dev (k_hvp5 and the k_fused* launches around it) and pgl_hess_dev (k_hess);
+                                   * 0 (default) = off */
 
 /* Development switches (not part of the drop-in surface; results stay valid unless stated): 95 = 2 keeps the narrow post
  * blocks of a wide population off the one-image-buffer form of k_fused6 and the block-ring kernel k_fused8 (they run on
@@ -196,6 +197,24 @@ int pgl_hvp_apply_dev(pgl_handle h, const double* d_v, double* d_hv);
 /* prepare + one apply with host pointers: theta, v, hv_out ((n_hi-n_lo), P), Weff (N,N).  A call that repeats the range,
  * time range, theta and Weff of the previous pgl_hvp call (the products of one CG solve) skips the prepare. */
 int pgl_hvp(pgl_handle h, int n_lo, int n_hi, const double* theta, const double* v, const double* Weff, double* hv_out);
+
+/* Dense Hessians of ll: hessian_wrt_list (pyglm/utils/grads.py:30-66), the default of the reference's parallel driver
+ * (parallel_coord_descent.py:62 use_hessian=True).  With f_t and c_t as above:
+ *     H_n = sum_t c_t f_t f_t^T
+ * for every row of the last pgl_hvp_prepare_dev / pgl_hvp_prepare_list_dev, from the curvature that prepare left on the
+ * device: one weighted Gram contraction over time on the f64 matrix cores (k_hess: nT P^2 flops per row over one triangle,
+ * against P applies of 4 nT N^2 B flops each for the same matrix from products), features built in LDS from the event
+ * lists, per-chunk partials reduced in a fixed order (deterministic).
+ *   d_H (count, P, ld), ld >= P, is the caller's (uninitialised is fine; columns P .. ld-1 are not written); rows and
+ *   columns in the theta layout.  Both triangles are stored, from the same registers: H[i][j] and H[j][i] hold the same bits.
+ * The result is the Hessian of ll itself: not negated, no prior.  Asynchronous on the handle's stream.  pgl_set_time_range
+ * is honoured: the result is the partial sum over the range.  Without a valid prepare (none yet, a changed time range, new
+ * spikes / basis / stimulus): PGL_ERR_STATE, as pgl_hvp_apply_dev; a separable stimulus: PGL_ERR_UNSUPPORTED; ld < P:
+ * PGL_ERR_ARG.  Needs count * (P / 64)^2 / 2 * 32 KB of scratch memory for the partials, at most 512 MB (more rows than fit
+ * run as several launches). */
+int pgl_hess_dev(pgl_handle h, double* d_H, int ld);
+/* prepare + pgl_hess_dev with host pointers: theta ((n_hi-n_lo), P), Weff (N,N), H_out ((n_hi-n_lo), P, P). */
+int pgl_hess(pgl_handle h, int n_lo, int n_hi, const double* theta, const double* Weff, double* H_out);
 
 /* The lock-step optimiser (inference/batched_bfgs.py) as row kernels on the handle's stream.  The reference calls
  * scipy.optimize.minimize(method="bfgs") neuron by neuron (coord_descent.py:161-204); these run the same algorithm --
@@ -405,14 +424,15 @@ int pgl_set_stream(pgl_handle h, void* stream);
  * 1 ll only, 2 the forward launches of pgl_gibbs_prepare_all, 3 the launches of pgl_hvp_prepare_dev /
  * pgl_hvp_prepare_list_dev over these neurons (k_hvp5<.., 1> or the forward-only K-split launches), 4 the launches of
  * pgl_hvp_apply_dev after such a prepare (k_hvp5<.., 0> + pass 2 of k_fused5, or the forward-only and backward-only K-split
- * launches of every column slice).  Paths 3 / 4 with stim >= 1 return PGL_ERR_UNSUPPORTED, as the calls themselves.
+ * launches of every column slice), 5 the k_hess launches of pgl_hess_dev after such a prepare (one per batch of rows).
+ * Paths 3 / 4 / 5 with stim >= 1 return PGL_ERR_UNSUPPORTED, as the calls themselves.
  * The reference has no counterpart (Theano picks its own C implementations); tests hold every reachable instantiation to
  * zero bytes of scratch. */
 int pgl_plan_kernels(int N, int B, int R, int Dstim, long long nT, int stim, int n_lo, int count, int path, int opt_kernel,
                      int opt_f32, char* out, int cap);
 
 /* The fused kernel instantiations the handle's last pgl_ll_grad / pgl_ll_grad_dev / pgl_ll_grad_list_dev /
- * pgl_gibbs_prepare_all / pgl_hvp_prepare_* / pgl_hvp_apply_dev call launched, one per line in `out`, in launch order and in the format of pgl_plan_kernels
+ * pgl_gibbs_prepare_all / pgl_hvp_prepare_* / pgl_hvp_apply_dev / pgl_hess_dev call launched, one per line in `out`, in launch order and in the format of pgl_plan_kernels
  * (which enqueues the same launch sequence on a device-less context).  Needs PGL_OPT_RECORD_KERNELS = 1 on the handle
  * (PGL_ERR_STATE otherwise).  Dev / test entry point: tests compare it with the dry run. */
 int pgl_last_kernels(pgl_handle h, char* out, int cap);

@@ -37,6 +37,7 @@ SYMBOLS = [
     'pgl_bfgs_linesearch_dev', 'pgl_bfgs_hmul_dev', 'pgl_bfgs_hmul_hist_dev', 'pgl_bfgs_update_dev', 'pgl_bfgs_step_dev', 'pgl_plan_kernels', 'pgl_last_kernels', 'pgl_leading_singular_pairs',
     'pgl_hvp_prepare_dev', 'pgl_hvp_prepare_list_dev', 'pgl_hvp_apply_dev', 'pgl_hvp',
     'pgl_ncg_state_doubles', 'pgl_ncg_init_dev', 'pgl_ncg_cg_step_dev', 'pgl_ncg_trial_dev', 'pgl_ncg_search_step_dev',
+    'pgl_hess_dev', 'pgl_hess',
 ]
 
 
@@ -128,6 +129,9 @@ def load():
         lib.pgl_hvp_prepare_list_dev.argtypes = [vp, vp, C.c_int, vp, vp]
         lib.pgl_hvp_apply_dev.argtypes = [vp, vp, vp]
         lib.pgl_hvp.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    if hasattr(lib, 'pgl_hess'):
+        lib.pgl_hess_dev.argtypes = [vp, vp, C.c_int]
+        lib.pgl_hess.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
     if hasattr(lib, 'pgl_bfgs_hmul_dev'):                     # (older dev A/B builds named by PYGLM_HIP_LIB lack it)
         lib.pgl_bfgs_state_doubles.argtypes = [C.c_int, C.c_int]
         lib.pgl_bfgs_init_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double]
@@ -396,6 +400,22 @@ class DeviceGlm(object):
         _chk(self.lib.pgl_hvp(self.h, int(n_lo), int(n_hi), _ptr(th), _ptr(vv), _ptr(We), _ptr(out)))
         return out
 
+    # -- dense Hessians of ll (grads.py:30-66 hessian_wrt_list) ---------------------
+    def hess(self, d_H, ld=None):
+        """d_H (rows, P, ld) = the Hessian of ll of every row of the last hvp_prepare, theta layout, both triangles (device
+        pointer; asynchronous).  ld >= P, default P; the padding columns are not written."""
+        _chk(self.lib.pgl_hess_dev(self.h, C.c_void_p(d_H), int(self.P if ld is None else ld)))
+
+    def hessian(self, theta, Weff, n_lo=0, n_hi=None):
+        """Hessian of ll for rows [n_lo, n_hi) with host arrays: theta (rows, P), Weff (N, N) -> (rows, P, P)."""
+        n_hi = self.N if n_hi is None else n_hi
+        npost = n_hi - n_lo
+        th = _f64(theta, (npost, self.P))
+        We = _f64(Weff, (self.N, self.N))
+        out = np.empty((npost, self.P, self.P))
+        _chk(self.lib.pgl_hess(self.h, int(n_lo), int(n_hi), _ptr(th), _ptr(We), _ptr(out)))
+        return out
+
     # -- lock-step optimiser bookkeeping (device pointers as integers; asynchronous on the handle's stream) --
     def bfgs_state_doubles(self, M, P):
         return int(self.lib.pgl_bfgs_state_doubles(int(M), int(P)))
@@ -479,7 +499,7 @@ class DeviceGlm(object):
         return a.value, b.value
 
     def last_kernels(self):
-        """The fused kernel instantiations the last ll_grad / gibbs_prepare_all call launched, in launch order, as
+        """The fused kernel instantiations the last ll_grad / gibbs_prepare_all / hvp_* / hess call launched, in launch order, as
         plan_kernels names them (pgl_last_kernels); needs set_option(OPT_RECORD_KERNELS, 1)."""
         buf = C.create_string_buffer(16384)
         _chk(self.lib.pgl_last_kernels(self.h, buf, 16384))

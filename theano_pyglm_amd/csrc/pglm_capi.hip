@@ -120,6 +120,7 @@ struct pgl_context {
     int hvp_n_lo = 0, hvp_count = 0;
     int64_t hvp_t_lo = 0, hvp_t_hi = 0;
     DevBuf Cbuf, hvp_idx, hvp_Weff, hvp_ll, hvp_v, hvp_out;
+    DevBuf hess_part, hess_out;          // pgl_hess_dev: chunk partials of k_hess; pgl_hess: the device copy of H_out
     std::vector<double> hvp_host;        // pgl_hvp: theta and Weff of its last prepare (a CG solve repeats them: no new prepare)
 };
 
@@ -217,7 +218,7 @@ static void launch_sepf(int which, const SepfParams& sp, hipStream_t s)
 extern "C" {
 
 const char* pgl_last_error(void) { return g_err.c_str(); }
-int pgl_version(void) { return 103; }
+int pgl_version(void) { return 104; }
 
 int pgl_device_count(void)
 {
@@ -280,7 +281,8 @@ int pgl_destroy(pgl_handle h)
                       &h->wsmall, &h->part, &h->outK, &h->lam, &h->wcol, &h->thetan, &h->GX, &h->gtheta,
                       &h->gargs, &h->gpart, &h->gout, &h->ghs, &h->gfs, &h->zf, &h->zfT, &h->sbt, &h->Yf, &h->Qb, &h->Qf,
                       &h->spart, &h->sepC, &h->sepA, &h->sepAT, &h->sepD, &h->YfT, &h->Hb, &h->wpart, &h->QvT, &h->staA,
-                      &h->Cbuf, &h->hvp_idx, &h->hvp_Weff, &h->hvp_ll, &h->hvp_v, &h->hvp_out};
+                      &h->Cbuf, &h->hvp_idx, &h->hvp_Weff, &h->hvp_ll, &h->hvp_v, &h->hvp_out,
+                      &h->hess_part, &h->hess_out};
     for (DevBuf* b : bufs) release(*b);
     for (int s = 0; s < pgl_context::NEV; ++s)
         for (int i = 0; i < 4; ++i)
@@ -1658,6 +1660,86 @@ int pgl_hvp(pgl_handle h, int n_lo, int n_hi, const double* theta, const double*
     return PGL_OK;
 }
 
+// ---- dense Hessians of ll (hessian_wrt_list, pyglm/utils/grads.py:30-66) ----
+// H_n = sum_t c[t, n] f_t f_t^T of the prepared rows, from the curvature the last prepare left in h->Cbuf: per launch of
+// hess_plan's rows the Gram contraction k_hess into chunk partials, then k_hess_reduce (chunk order, Weff, theta layout, both
+// triangles).  The g_dry RULE above enqueue_ll_grad holds here too.
+static int enqueue_hess(pgl_handle h, double* d_H, int ld)
+{
+    KernelRecord record(h);
+    HessPlan hp;
+    int rc = hess_plan(h, h->hvp_count, hp);
+    if (rc) return rc;
+    ENSURE(h->hess_part, hp.partBytes);
+    HessParams kp{};
+    kp.nT = h->nT; kp.t_hi = h->t_hi;
+    kp.N = h->N; kp.B = h->B; kp.R = h->Rk; kp.RP = hp.RP; kp.Dstim = h->Dstim; kp.Kimp = h->Kimp;
+    kp.K = h->Kimp + h->Dstim + 1;
+    kp.spk = (const int2*)h->spk.p; kp.wlo = (const int*)h->wlo.p; kp.whi = (const int*)h->whi.p;
+    kp.fstim = (const double*)h->fstim.p; kp.phi = (const double*)h->phi.p;
+    kp.C = (const double*)h->Cbuf.p;
+    kp.cxs = 16 * ((h->hvp_count + 15) / 16);
+    kp.tile0 = (int)(h->t_lo / 16);
+    kp.nTiles = (int)((h->t_hi + 15) / 16) - kp.tile0;
+    kp.nChunks = hp.nChunks; kp.tilesPerChunk = hp.tilesPerChunk;
+    kp.nPairs = hp.nPairs;
+    kp.part = (double*)h->hess_part.p;
+    for (int r0 = 0; r0 < h->hvp_count; r0 += hp.rowsPerLaunch) {
+        kp.r0 = r0;
+        kp.count = std::min(hp.rowsPerLaunch, h->hvp_count - r0);
+        kp.nGroups = (kp.count + 7) / 8;
+        const long long blocks = (long long)kp.nPairs * kp.nGroups * kp.nChunks;
+        if (blocks > 0x7fffffffLL) return fail(PGL_ERR_UNSUPPORTED, "dense Hessian: grid too large");
+        hipError_t e = launch_hess(kp, h->hvp_fused ? 1 : 0, (unsigned)blocks, hp.lds, h->stream);
+        if (e != hipSuccess) return fail(PGL_ERR_HIP, std::string("Hessian launch: ") + hipGetErrorString(e));
+        if (!g_dry) {
+            hipLaunchKernelGGL(k_hess_reduce, dim3(kp.nPairs, kp.count), dim3(256), 0, h->stream, kp,
+                               (const double*)h->hvp_Weff.p, h->hvp_list ? (const int*)h->hvp_idx.p : nullptr, h->hvp_n_lo, d_H, ld);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    return PGL_OK;
+}
+
+int pgl_hess_dev(pgl_handle h, double* d_H, int ld)
+{
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if (!d_H) return fail(PGL_ERR_ARG, "null argument");
+    if (h->sep)
+        return fail(PGL_ERR_UNSUPPORTED, "dense Hessians with a separable stimulus (pgl_set_stimulus_separable): "
+                                         "the current is not linear in (w_t, w_x)");
+    if (!h->hvp_ok) return fail(PGL_ERR_STATE, "pgl_hvp_prepare_* has not been called (or the data changed since)");
+    if (h->hvp_t_lo != h->t_lo || h->hvp_t_hi != h->t_hi)
+        return fail(PGL_ERR_STATE, "the time range changed since pgl_hvp_prepare_*");
+    if (ld < 1 + h->Dstim + h->Kimp) return fail(PGL_ERR_ARG, "ld < P");
+    HIPCHK(hipSetDevice(h->device));
+    return enqueue_hess(h, d_H, ld);
+}
+
+int pgl_hess(pgl_handle h, int n_lo, int n_hi, const double* theta, const double* Weff, double* H_out)
+{
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if (!theta || !Weff || !H_out) return fail(PGL_ERR_ARG, "null argument");
+    if (n_lo < 0 || n_hi > h->N || n_lo >= n_hi) return fail(PGL_ERR_ARG, "bad neuron range");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t P = 1 + (size_t)h->Dstim + h->Kimp;
+    const size_t np = (size_t)(n_hi - n_lo);
+    ENSURE(h->theta, np * P * 8);
+    ENSURE(h->Weff, (size_t)h->N * h->N * 8);
+    HIPCHK(hipMemcpyAsync(h->theta.p, theta, np * P * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->Weff.p, Weff, (size_t)h->N * h->N * 8, hipMemcpyHostToDevice, h->stream));
+    rc = pgl_hvp_prepare_dev(h, n_lo, n_hi, (const double*)h->theta.p, (const double*)h->Weff.p);
+    if (rc) return rc;
+    ENSURE(h->hess_out, np * P * P * 8);
+    rc = pgl_hess_dev(h, (double*)h->hess_out.p, (int)P);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(H_out, h->hess_out.p, np * P * P * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return PGL_OK;
+}
+
 // ---- lock-step BFGS bookkeeping kernels (inference/batched_bfgs.py) ----------------------------------------------
 long long pgl_bfgs_state_doubles(int M, int P) { return (long long)pgl_bfgs_doubles(M, P); }
 
@@ -2018,7 +2100,7 @@ int pgl_last_kernels(pgl_handle h, char* out, int cap)
 // tap-rate kernels, 2 separable at the frame rate with the stimulus current inside the fused forward where that form
 // exists, 3 at the frame rate through the slab.  path: 0 ll+grad, 1 ll only, 2 the forward launches of pgl_gibbs_prepare_all,
 // 3 the launches of pgl_hvp_prepare_*, 4 those of pgl_hvp_apply_dev after such a prepare (k_hvp5 and the fused kernels around
-// it; stim >= 1: PGL_ERR_UNSUPPORTED, as the real call).
+// it; stim >= 1: PGL_ERR_UNSUPPORTED, as the real call), 5 the k_hess launches of pgl_hess_dev after such a prepare.
 int pgl_plan_kernels(int N, int B, int R, int Dstim, long long nT, int stim, int n_lo, int count, int path, int opt_kernel,
                      int opt_f32, char* out, int cap)
 {
@@ -2036,17 +2118,17 @@ int pgl_plan_kernels(int N, int B, int R, int Dstim, long long nT, int stim, int
     std::vector<std::string> names;
     double dummy = 0;
     int rc = PGL_OK;
-    if (path == 3 || path == 4) {
-        // pgl_hvp_prepare_* (3), pgl_hvp_apply_dev after such a prepare (4): the apply takes range and path from the prepare
+    if (path == 3 || path == 4 || path == 5) {
+        // pgl_hvp_prepare_* (3), pgl_hvp_apply_dev (4) / pgl_hess_dev (5) after such a prepare: they take range and path from it
         if (c.sep) return fail(PGL_ERR_UNSUPPORTED, "Hessian-vector products with a separable stimulus");
         std::vector<std::string> prep;
         g_dry = (path == 3) ? &names : &prep;
         rc = enqueue_hvp_prepare(&c, n_lo, n_lo + count, nullptr, nullptr);
-        if (rc == PGL_OK && path == 4) {
+        if (rc == PGL_OK && path != 3) {
             c.hvp_n_lo = n_lo;
             c.hvp_count = count;
             g_dry = &names;
-            rc = enqueue_hvp_apply(&c, nullptr, &dummy);
+            rc = (path == 4) ? enqueue_hvp_apply(&c, nullptr, &dummy) : enqueue_hess(&c, &dummy, 1 + Dstim + c.Kimp);
         }
     } else {
         g_dry = &names;

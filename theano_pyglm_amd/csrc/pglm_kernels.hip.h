@@ -19,6 +19,7 @@
 //   k_fused2                 one pass, post tiles x K slices across the 8 waves (small post blocks,
 //                            the sliced path for N > 128, optional f32 feature tile)
 // Hessian-vector products H.v = F^T.(c o (F.v)) reuse the scheme with the epilogue swapped for one multiply (k_hvp5).
+// The dense Hessian H = F^T.diag(c).F is a contraction over time of its own (k_hess, pglm_hess.hip.h).
 #pragma once
 //
 // The kernels live in one header per family; this file is the translation unit's table of contents.
@@ -26,6 +27,7 @@
 #include "pglm_fused_stream.hip.h"
 #include "pglm_fused_resident.hip.h"
 #include "pglm_hvp.hip.h"
+#include "pglm_hess.hip.h"
 #include "pglm_reduce.hip.h"
 #include "pglm_direct.hip.h"
 #include "pglm_gibbs.hip.h"

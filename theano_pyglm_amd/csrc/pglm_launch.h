@@ -265,3 +265,11 @@ static hipError_t launch_plan(const Plan& pl, const FusedParams& fp, hipStream_t
     if (pl.version == 4) return launch_fused3(pl, fp, s);
     return launch_fused2(pl, fp, s);
 }
+
+// the weighted Gram contraction of the dense Hessian: slab = layout of the prepared curvature (0 rows, 1 accumulator-layout slab)
+static hipError_t launch_hess(const HessParams& hp, int slab, unsigned blocks, size_t lds, hipStream_t s)
+{
+    return dispatch(IntList<0, 1>{}, slab, [&](auto sl) -> hipError_t {
+        return launch_kernel(k_hess<PGL_CV(sl)>, "k_hess", {PGL_CV(sl)}, nullptr, dim3(blocks), dim3(512), lds, s, hp);
+    });
+}

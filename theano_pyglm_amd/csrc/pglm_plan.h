@@ -480,3 +480,39 @@ static int hvp_select(const pgl_context* h, int n_lo, int n_hi, std::vector<Slic
     }
     return PGL_OK;
 }
+
+// Geometry of the dense Hessian (k_hess, pglm_hess.hip.h) of `count` prepared rows: column blocks of 64 and their pairs
+// j <= i, the rows of one launch (eight per workgroup; the chunk partials of a launch, 32 KB per row and pair, stay within
+// a fixed budget -- more rows than that run as several launches over the same buffer), time chunks so that a launch has about
+// eight workgroups per CU when the pairs and rows alone do not give them.  Shape only: the dry run needs no device.
+struct HessPlan {
+    int nCB, nPairs, rowsPerLaunch, nChunks, tilesPerChunk, RP;
+    size_t lds, partBytes;
+};
+static int hess_plan(const pgl_context* h, int count, HessPlan& hp)
+{
+    const int K = h->Kimp + h->Dstim + 1;
+    hp.nCB = (K + PGL_HESS_CB - 1) / PGL_HESS_CB;
+    hp.nPairs = hp.nCB * (hp.nCB + 1) / 2;
+    hp.RP = h->Rk + 32;
+    while (hp.RP % 32 != 8) ++hp.RP;
+    hp.lds = (size_t)16 * PGL_HESS_LD * 8 + ((((size_t)2 * h->B * hp.RP * 8) + 15) & ~(size_t)15) +
+             (size_t)2 * PGL_HESS_NPB * PGL_CAP * 8 + (size_t)4 * PGL_HESS_NPB * 4;
+    if (hp.lds > 160 * 1024) return fail(PGL_ERR_UNSUPPORTED, "dense Hessian: the basis tables do not fit the LDS");
+    const size_t per = (size_t)hp.nPairs * 4096 * 8;           // partial bytes per row and chunk
+    const size_t budget = (size_t)512 << 20;
+    long long rows = std::max<long long>(1, (long long)(budget / per));
+    if (rows >= count) rows = count;
+    else if (rows >= 8) rows &= ~7LL;
+    hp.rowsPerLaunch = (int)rows;
+    const int tile0 = (int)(h->t_lo / 16), nTiles = (int)((h->t_hi + 15) / 16) - tile0;
+    const long long wgs = (long long)hp.nPairs * ((rows + 7) / 8);
+    long long chunks = (8LL * h->numCU + wgs - 1) / wgs;
+    chunks = std::min<long long>(chunks, std::max(1, nTiles / 8));
+    chunks = std::min<long long>(chunks, std::max<long long>(1, (long long)(budget / (per * rows))));
+    chunks = std::max<long long>(chunks, 1);
+    hp.tilesPerChunk = (int)((nTiles + chunks - 1) / chunks);
+    hp.nChunks = (nTiles + hp.tilesPerChunk - 1) / hp.tilesPerChunk;
+    hp.partBytes = per * (size_t)rows * hp.nChunks;
+    return PGL_OK;
+}

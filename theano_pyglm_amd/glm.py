@@ -105,6 +105,34 @@ class Glm(Component):
                 'bkgd': self.bkgd_model.hess_log_p_vec(xn['bkgd'], v.get('bkgd', {})),
                 'imp': self.imp_model.hess_log_p_vec(xn['imp'], v['imp']), 'nlin': {}}
 
+    def hess_log_prior(self, xn):
+        """Dense Hessian of log_prior(xn) w.r.t. the packed per-neuron vector, (P, P): the matrix whose columns are
+        hess_log_prior_vec of the unit vectors (the prior terms inside hessian_wrt_list, grads.py:30-66).  The served priors
+        are sums over single weights and over the B-weight groups of the impulse model, so B products recover every
+        column: product k probes element k of every impulse group (and, k = 0, every other weight) at once."""
+        from theano_pyglm_amd.utils.packvec import packdict, unpackdict, get_vars
+        from theano_pyglm_amd.utils.syms import differentiable
+        bad = self.hvp_packing()
+        if bad is not None:
+            raise ValueError("Hessian-vector products are not implemented for the %s packing" % bad)
+        syms =differentiable(self.get_variables())
+        w0, shapes = packdict(get_vars(syms, xn))
+        P = w0.size
+        where = unpackdict(np.arange(P), shapes)                # packed position of every variable's elements
+        imp = np.asarray(where['imp']['w_ir']).reshape(self.N, self.imp_model.B)
+        rest = np.setdiff1d(np.arange(P), imp.reshape(-1))
+        H = np.zeros((P, P))
+        for k in range(self.imp_model.B):
+            v = np.zeros(P)
+            v[imp[:, k]] = 1.0
+            if k == 0:
+                v[rest] = 1.0
+            hv = packdict(get_vars(syms, self.hess_log_prior_vec(xn, unpackdict(v, shapes))))[0]
+            H[imp, imp[:, k][:, None]] = hv[imp]                # rows of each group, column = its probed element
+            if k == 0:
+                H[rest, rest] = hv[rest]
+        return H
+
     @property
     def Dstim(self):
         return self.bkgd_model.n_features

@@ -335,6 +335,38 @@ class Population(object):
         vector v -- the counterpart of compute_grad (minus coord_descent's hessp)."""
         return self.compute_hvp_packed(vars, np.asarray(v, dtype=float)[None, :], n, n + 1)[0]
 
+    def compute_hessian_packed(self, vars, n_lo=0, n_hi=None, include_prior=True):
+        """For every neuron n in [n_lo, n_hi): the dense Hessian of (log_prior_n + sum_data ll_n) w.r.t. its packed parameter
+        vector, (npost, P, P) -- hessian_wrt_list (grads.py:30-66), the default of the reference's parallel driver
+        (parallel_coord_descent.py:62).  One curvature pass and one Gram contraction on the device per data sequence
+        (pgl_hess); the priors' Hessian is added on the host.  Served for the packings of compute_hvp_packed."""
+        bad = self.glm.hvp_packing()
+        if bad is not None:
+            raise ValueError("Hessian-vector products are not implemented for the %s packing" % bad)
+        n_hi = self.N if n_hi is None else n_hi
+        syms = self.glm_syms()
+        w0, shapes = packdict(get_vars(syms, vars['glms'][n_lo]))
+        P = w0.size
+        # the packed vector is a permutation of the theta row: packed position of every theta column
+        pi = np.rint(self.glm.theta_row(unpackdict(np.arange(P, dtype=float), shapes))).astype(int)
+        if P != self.glm.P or not np.array_equal(np.sort(pi), np.arange(P)):
+            raise ValueError("the packed vector is not a permutation of the theta row")
+        theta = self.theta_matrix(vars, n_lo, n_hi)
+        Weff = self.W_eff(vars)
+        out = np.zeros((n_hi - n_lo, P, P))
+        for data in self.data_sequences:
+            self.set_data(data)
+            out[:, pi[:, None], pi[None, :]] += self._handle(self._current).hessian(theta, Weff, n_lo, n_hi)
+        if include_prior:
+            for i, n in enumerate(range(n_lo, n_hi)):
+                out[i] += self.glm.hess_log_prior(vars['glms'][n])
+        return out
+
+    def compute_hessian(self, vars, n):
+        """Dense Hessian of (glm.log_prior + sum_data glm.ll) of neuron n w.r.t. its packed parameter vector, (P, P): the
+        matrix whose columns compute_hvp gives one at a time."""
+        return self.compute_hessian_packed(vars, n, n + 1)[0]
+
     def compute_grad(self, vars, n):
         """Gradient of (glm.log_prior + sum_data glm.ll) of neuron n w.r.t. its packed
         parameter vector -- minus coord_descent.grad_nlp (coord_descent.py:61-80)."""
