@@ -80,8 +80,8 @@ typedef struct pgl_context* pgl_handle;
 
 #define PGL_OPT_RECORD_KERNELS 96 /* dev / test: 1 = every ll(+grad) evaluation and pgl_gibbs_prepare_all records the fused kernel
                                    * instantiations it launches, in launch order (pgl_last_kernels), and so do pgl_hvp_prepare_* /
-                                   * pgl_hvp_apply_dev (k_hvp5 and the k_fused* launches around it) and pgl_hess_dev (k_hess);
-                                   * 0 (default) = off */
+                                   * pgl_hvp_apply_dev (k_hvp5 and the k_fused* launches around it), pgl_hess_dev (k_hess) and
+                                   * pgl_rescale_dev (the forward launches, then k_rescale_*); 0 (default) = off */
 
 /* Development switches (not part of the drop-in surface; results stay valid unless stated): 95 = 2 keeps the narrow post
  * blocks of a wide population off the one-image-buffer form of k_fused6 and the block-ring kernel k_fused8 (they run on
@@ -364,6 +364,32 @@ int pgl_gibbs_update_cols(pgl_handle h, int ncols, const int* n_post, const int*
                           const double* delta);
 int pgl_gibbs_currents(pgl_handle h, int n_post, double* x_out);
 
+/* Time-rescaling goodness of fit (Brown, Barbieri, Ventura, Kass & Frank 2002): under the true model the integrated
+ * intensity between consecutive spikes is Exp(1).  The reference has no counterpart; its result plots start from the
+ * rates of eval_state (population.py:88-120), one neuron and three (nT) host arrays per pgl_state call.  For neuron n over
+ * the handle's time range [t_lo, t_hi) (pgl_set_time_range is honoured):
+ *     lam_t = nlin(theta_n[0] + x[t,n]), x the bias-free total current of pgl_gibbs_prepare_all, all f64 (no
+ *             single-precision shortcut: the rate functions of the PGL_OPT_EPI_F64 = 1 epilogue);
+ *     event bins t_1 < ... < t_K: the bins of the range with S[t,n] >= 1 -- a bin with several spikes is ONE event
+ *             (the discrete-time correction of Haslinger, Pipa & Brown 2010 is not applied);
+ *     tau_k = dt * sum_{s = t_{k-1}+1 .. t_k} lam_s, k = 2 .. K: the interval before the first event of the range is
+ *             left-censored and dropped, so a neuron with K events gives max(K - 1, 0) intervals;
+ *     Lambda_n = dt * sum_{t in range} lam_t, the expected count.
+ * rescale_count: off_out (N + 1), host: off_out[n] = position of neuron n's first interval in the concatenated output,
+ *     off_out[N] = their number, for the current time range (from the host copy of the event lists; needs spikes only).
+ * rescale_dev:   device pointers, asynchronous on the handle's stream.  d_theta (N, P), d_Weff (N, N): the forward pass of
+ *     pgl_gibbs_prepare_all runs on them (and leaves its state, as that call does); d_off (N + 1) int64: the offsets of
+ *     rescale_count; d_tau (d_off[N], at least one double): tau of neuron n at d_off[n] ..; d_stats (N, 4): Lambda_n, K_n,
+ *     the number of event bins holding more than one spike, 0 (reserved).  A segmented sum over time behind the forward
+ *     launches (k_rescale_chunk / _scan / _finish: one read of the currents, no (nT, N) rate array), every sum in a fixed
+ *     order: two calls give the same bits.
+ * rescale:       the same with host pointers; tau_out holds off[N] doubles, stats_out (N, 4).
+ * Before pgl_set_spikes_* / pgl_set_basis: PGL_ERR_STATE; a NULL argument: PGL_ERR_ARG. */
+int pgl_rescale_count(pgl_handle h, int64_t* off_out);
+int pgl_rescale_dev(pgl_handle h, const double* d_theta, const double* d_Weff, double* d_tau, const int64_t* d_off,
+                    double* d_stats);
+int pgl_rescale(pgl_handle h, const double* theta, const double* Weff, double* tau_out, double* stats_out);
+
 /* Spike-triggered average, pyglm/utils/sta.py:6-85 (used by smart_init.py:28-98 and 100-158):
  *   A[i,l,d] = sum_t S[t,n_i] * istim[t-l,d] / sum_t S[t,n_i],  l = 0..L-1, terms with t-l < 0 dropped,
  * istim = np.interp of stim (Tstim,D) to the bin grid, divided by dt_stim/dt (sta.py:27-41).
@@ -424,7 +450,9 @@ int pgl_set_stream(pgl_handle h, void* stream);
  * 1 ll only, 2 the forward launches of pgl_gibbs_prepare_all, 3 the launches of pgl_hvp_prepare_dev /
  * pgl_hvp_prepare_list_dev over these neurons (k_hvp5<.., 1> or the forward-only K-split launches), 4 the launches of
  * pgl_hvp_apply_dev after such a prepare (k_hvp5<.., 0> + pass 2 of k_fused5, or the forward-only and backward-only K-split
- * launches of every column slice), 5 the k_hess launches of pgl_hess_dev after such a prepare (one per batch of rows).
+ * launches of every column slice), 5 the k_hess launches of pgl_hess_dev after such a prepare (one per batch of rows),
+ * 6 the launches of pgl_rescale_dev (those of path 2, then k_rescale_chunk<nlin>, k_rescale_scan, k_rescale_finish; the dry
+ * run's context has nlin = PGL_NLIN_EXP).
  * Paths 3 / 4 / 5 with stim >= 1 return PGL_ERR_UNSUPPORTED, as the calls themselves.
  * The reference has no counterpart (Theano picks its own C implementations); tests hold every reachable instantiation to
  * zero bytes of scratch. */
@@ -432,7 +460,7 @@ int pgl_plan_kernels(int N, int B, int R, int Dstim, long long nT, int stim, int
                      int opt_f32, char* out, int cap);
 
 /* The fused kernel instantiations the handle's last pgl_ll_grad / pgl_ll_grad_dev / pgl_ll_grad_list_dev /
- * pgl_gibbs_prepare_all / pgl_hvp_prepare_* / pgl_hvp_apply_dev / pgl_hess_dev call launched, one per line in `out`, in launch order and in the format of pgl_plan_kernels
+ * pgl_gibbs_prepare_all / pgl_hvp_prepare_* / pgl_hvp_apply_dev / pgl_hess_dev / pgl_rescale_dev call launched, one per line in `out`, in launch order and in the format of pgl_plan_kernels
  * (which enqueues the same launch sequence on a device-less context).  Needs PGL_OPT_RECORD_KERNELS = 1 on the handle
  * (PGL_ERR_STATE otherwise).  Dev / test entry point: tests compare it with the dry run. */
 int pgl_last_kernels(pgl_handle h, char* out, int cap);

@@ -23,6 +23,7 @@ OPT_EPI_F64 = 5
 OPT_TIMING = 6
 OPT_BFGS_MERGE = 7
 OPT_RECORD_KERNELS = 96             # dev / test: DeviceGlm.last_kernels() lists the fused launches of the last evaluation
+RESCALE_CHUNK = 256                 # bins per chunk of the rescaling kernels (PGL_RS_CHUNK): chunks start at t_lo + k * 256
 
 # every symbol include/pyglm_hip.h declares (tests check the .so exports all of them)
 SYMBOLS = [
@@ -38,6 +39,7 @@ SYMBOLS = [
     'pgl_hvp_prepare_dev', 'pgl_hvp_prepare_list_dev', 'pgl_hvp_apply_dev', 'pgl_hvp',
     'pgl_ncg_state_doubles', 'pgl_ncg_init_dev', 'pgl_ncg_cg_step_dev', 'pgl_ncg_trial_dev', 'pgl_ncg_search_step_dev',
     'pgl_hess_dev', 'pgl_hess',
+    'pgl_rescale_count', 'pgl_rescale_dev', 'pgl_rescale',
 ]
 
 
@@ -132,6 +134,10 @@ def load():
     if hasattr(lib, 'pgl_hess'):
         lib.pgl_hess_dev.argtypes = [vp, vp, C.c_int]
         lib.pgl_hess.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
+    if hasattr(lib, 'pgl_rescale'):
+        lib.pgl_rescale_count.argtypes = [vp, vp]
+        lib.pgl_rescale_dev.argtypes = [vp, vp, vp, vp, vp, vp]
+        lib.pgl_rescale.argtypes = [vp, vp, vp, vp, vp]
     if hasattr(lib, 'pgl_bfgs_hmul_dev'):                     # (older dev A/B builds named by PYGLM_HIP_LIB lack it)
         lib.pgl_bfgs_state_doubles.argtypes = [C.c_int, C.c_int]
         lib.pgl_bfgs_init_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double]
@@ -415,6 +421,32 @@ class DeviceGlm(object):
         out = np.empty((npost, self.P, self.P))
         _chk(self.lib.pgl_hess(self.h, int(n_lo), int(n_hi), _ptr(th), _ptr(We), _ptr(out)))
         return out
+
+    # -- time-rescaling goodness of fit (pgl_rescale*) ------------------------------
+    def rescale_count(self):
+        """(N + 1) int64 offsets of every neuron's rescaled intervals in the concatenated output, for the current time
+        range: a neuron with K event bins in the range has max(K - 1, 0) intervals."""
+        off = np.empty(self.N + 1, dtype=np.int64)
+        _chk(self.lib.pgl_rescale_count(self.h, _ptr(off)))
+        return off
+
+    def rescale_dev(self, d_theta, d_Weff, d_tau, d_off, d_stats):
+        """Device-pointer form (integers; asynchronous): d_theta (N, P), d_Weff (N, N), d_off (N + 1) int64 = rescale_count(),
+        d_tau (d_off[N]) out, d_stats (N, 4) out; see pgl_rescale_dev."""
+        _chk(self.lib.pgl_rescale_dev(self.h, C.c_void_p(d_theta), C.c_void_p(d_Weff), C.c_void_p(d_tau), C.c_void_p(d_off),
+                                      C.c_void_p(d_stats)))
+
+    def rescale(self, theta, Weff):
+        """Rescaled inter-event intervals of every neuron over the current time range with host arrays: theta (N, P), Weff
+        (N, N) -> (tau, off, stats): tau[off[n]:off[n + 1]] are neuron n's intervals, stats (N, 4) = expected count, event
+        bins, event bins holding more than one spike, 0."""
+        th = _f64(theta, (self.N, self.P))
+        We = _f64(Weff, (self.N, self.N))
+        off = self.rescale_count()
+        tau = np.empty(max(int(off[-1]), 1))
+        stats = np.empty((self.N, 4))
+        _chk(self.lib.pgl_rescale(self.h, _ptr(th), _ptr(We), _ptr(tau), _ptr(stats)))
+        return tau[:int(off[-1])], off, stats
 
     # -- lock-step optimiser bookkeeping (device pointers as integers; asynchronous on the handle's stream) --
     def bfgs_state_doubles(self, M, P):

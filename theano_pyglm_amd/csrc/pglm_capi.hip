@@ -121,6 +121,9 @@ struct pgl_context {
     int64_t hvp_t_lo = 0, hvp_t_hi = 0;
     DevBuf Cbuf, hvp_idx, hvp_Weff, hvp_ll, hvp_v, hvp_out;
     DevBuf hess_part, hess_out;          // pgl_hess_dev: chunk partials of k_hess; pgl_hess: the device copy of H_out
+    // time rescaling (pgl_rescale_dev): in-chunk sums at the events, chunk totals and their prefix; pgl_rescale: the device
+    // copies of its offsets and results
+    DevBuf rs_pre, rs_tot, rs_cum, rs_off, rs_tau, rs_stats;
     std::vector<double> hvp_host;        // pgl_hvp: theta and Weff of its last prepare (a CG solve repeats them: no new prepare)
 };
 
@@ -218,7 +221,7 @@ static void launch_sepf(int which, const SepfParams& sp, hipStream_t s)
 extern "C" {
 
 const char* pgl_last_error(void) { return g_err.c_str(); }
-int pgl_version(void) { return 104; }
+int pgl_version(void) { return 105; }
 
 int pgl_device_count(void)
 {
@@ -282,7 +285,7 @@ int pgl_destroy(pgl_handle h)
                       &h->gargs, &h->gpart, &h->gout, &h->ghs, &h->gfs, &h->zf, &h->zfT, &h->sbt, &h->Yf, &h->Qb, &h->Qf,
                       &h->spart, &h->sepC, &h->sepA, &h->sepAT, &h->sepD, &h->YfT, &h->Hb, &h->wpart, &h->QvT, &h->staA,
                       &h->Cbuf, &h->hvp_idx, &h->hvp_Weff, &h->hvp_ll, &h->hvp_v, &h->hvp_out,
-                      &h->hess_part, &h->hess_out};
+                      &h->hess_part, &h->hess_out, &h->rs_pre, &h->rs_tot, &h->rs_cum, &h->rs_off, &h->rs_tau, &h->rs_stats};
     for (DevBuf* b : bufs) release(*b);
     for (int s = 0; s < pgl_context::NEV; ++s)
         for (int i = 0; i < 4; ++i)
@@ -2082,6 +2085,7 @@ int pgl_set_stream(pgl_handle h, void* stream)
 }
 
 static int enqueue_gibbs_forward(pgl_handle h);
+static int enqueue_rescale(pgl_handle h, double* d_tau, const long long* d_off, double* d_stats);
 
 int pgl_last_kernels(pgl_handle h, char* out, int cap)
 {
@@ -2100,7 +2104,8 @@ int pgl_last_kernels(pgl_handle h, char* out, int cap)
 // tap-rate kernels, 2 separable at the frame rate with the stimulus current inside the fused forward where that form
 // exists, 3 at the frame rate through the slab.  path: 0 ll+grad, 1 ll only, 2 the forward launches of pgl_gibbs_prepare_all,
 // 3 the launches of pgl_hvp_prepare_*, 4 those of pgl_hvp_apply_dev after such a prepare (k_hvp5 and the fused kernels around
-// it; stim >= 1: PGL_ERR_UNSUPPORTED, as the real call), 5 the k_hess launches of pgl_hess_dev after such a prepare.
+// it; stim >= 1: PGL_ERR_UNSUPPORTED, as the real call), 5 the k_hess launches of pgl_hess_dev after such a prepare,
+// 6 the launches of pgl_rescale_dev (the forward launches of path 2, then the k_rescale_* kernels).
 int pgl_plan_kernels(int N, int B, int R, int Dstim, long long nT, int stim, int n_lo, int count, int path, int opt_kernel,
                      int opt_f32, char* out, int cap)
 {
@@ -2132,9 +2137,10 @@ int pgl_plan_kernels(int N, int B, int R, int Dstim, long long nT, int stim, int
         }
     } else {
         g_dry = &names;
-        rc = (path == 2) ? enqueue_gibbs_forward(&c)
+        rc = (path == 2 || path == 6) ? enqueue_gibbs_forward(&c)
                          : enqueue_ll_grad(&c, n_lo, n_lo + count, nullptr, nullptr, &dummy, path == 0 ? &dummy : nullptr);
     }
+    if (rc == PGL_OK && path == 6) rc = enqueue_rescale(&c, &dummy, nullptr, &dummy);
     g_dry = nullptr;
     // (under g_dry nothing but a dispatch (pglm_launch.h) without an instantiation for the plan fails with PGL_ERR_HIP)
     if (rc == PGL_ERR_HIP) return fail(PGL_ERR_UNSUPPORTED, "no kernel instantiation for this plan");
@@ -2798,6 +2804,127 @@ int pgl_leading_singular_pairs(pgl_handle h, const double* A, int n, int L, int 
         }
     }
     return done(PGL_OK);
+}
+
+// ---- time rescaling: integrated rate between consecutive events (pglm_rescale.hip.h) ---------------------------------
+// events of neuron n inside the handle's time range, from the host copy of the event lists
+static void rescale_event_range(const pgl_context* h, int n, int& lo, int& hi)
+{
+    const int2* evb = h->h_ev.data();
+    const auto before = [](const int2& e, int64_t t) { return (int64_t)e.x < t; };
+    const int2* b = evb + h->h_ptr[n];
+    const int2* e = evb + h->h_ptr[n + 1];
+    lo = (int)(std::lower_bound(b, e, h->t_lo, before) - evb);
+    hi = (int)(std::lower_bound(b, e, h->t_hi, before) - evb);
+}
+
+int pgl_rescale_count(pgl_handle h, int64_t* off_out)
+{
+    if (!h) return fail(PGL_ERR_ARG, "null handle");
+    if (!h->have_spikes) return fail(PGL_ERR_STATE, "pgl_set_spikes_* has not been called");
+    if (!off_out) return fail(PGL_ERR_ARG, "null argument");
+    off_out[0] = 0;
+    for (int n = 0; n < h->N; ++n) {
+        int lo, hi;
+        rescale_event_range(h, n, lo, hi);
+        off_out[n + 1] = off_out[n] + std::max(hi - lo - 1, 0);
+    }
+    return PGL_OK;
+}
+
+// the k_rescale_* launches behind a forward pass (GX of the handle's time range is on the stream).  The dry run of the
+// dispatch runs this too: the RULE above enqueue_ll_grad holds here.
+static int enqueue_rescale(pgl_handle h, double* d_tau, const long long* d_off, double* d_stats)
+{
+    struct Append {                                            // PGL_OPT_RECORD_KERNELS: behind the forward launches
+        explicit Append(pgl_context* h) { if (h->opt_record && !g_dry) g_rec = &h->last_kernels; }
+        ~Append() { g_rec = nullptr; }
+    } record(h);
+    const auto named = [](const std::string& name) {          // true: dry run, launch nothing
+        if (g_dry) g_dry->push_back(name);
+        else if (g_rec) g_rec->push_back(name);
+        return g_dry != nullptr;
+    };
+    const long long nchunks = (h->t_hi - h->t_lo + PGL_RS_CHUNK - 1) / PGL_RS_CHUNK;
+    const int xs = g_dry ? 16 * ((h->N + 15) / 16) : h->gx_xs;
+    ENSURE(h->rs_pre, (size_t)std::max<int64_t>(h->nnz, 1) * 8);
+    ENSURE(h->rs_tot, (size_t)nchunks * xs * 8);
+    ENSURE(h->rs_cum, (size_t)(nchunks + 1) * xs * 8);
+    RescaleParams p;
+    p.GX = (const double*)h->GX.p; p.theta = (const double*)h->gtheta.p;
+    p.spk = (const int2*)h->spk.p; p.wlo = (const int*)h->wlo.p; p.whi = (const int*)h->whi.p;
+    p.pre = (double*)h->rs_pre.p; p.tot = (double*)h->rs_tot.p; p.cum = (double*)h->rs_cum.p;
+    p.off = d_off; p.tau = d_tau; p.stats = d_stats;
+    p.t_lo = h->t_lo; p.t_hi = h->t_hi;
+    p.N = h->N; p.xs = xs; p.P = 1 + h->Dstim + h->Kimp; p.nnz = (int)h->nnz; p.nchunks = (int)nchunks;
+    p.dt = h->dt;
+    const unsigned blocks = (unsigned)((nchunks * xs + 255) / 256);
+    if (!named(h->nlin == PGL_NLIN_EXPLINEAR ? "k_rescale_chunk<1>" : "k_rescale_chunk<0>")) {
+        if (h->nlin == PGL_NLIN_EXPLINEAR) hipLaunchKernelGGL(k_rescale_chunk<1>, dim3(blocks), dim3(256), 0, h->stream, p);
+        else hipLaunchKernelGGL(k_rescale_chunk<0>, dim3(blocks), dim3(256), 0, h->stream, p);
+        HIPCHK(hipGetLastError());
+    }
+    if (!named("k_rescale_scan")) {
+        hipLaunchKernelGGL(k_rescale_scan, dim3((h->N + 15) / 16), dim3(16 * PGL_RS_SEGS), 0, h->stream, p);
+        HIPCHK(hipGetLastError());
+    }
+    if (!named("k_rescale_finish")) {
+        hipLaunchKernelGGL(k_rescale_finish, dim3(h->N), dim3(256), 0, h->stream, p);
+        HIPCHK(hipGetLastError());
+    }
+    return PGL_OK;
+}
+
+int pgl_rescale_dev(pgl_handle h, const double* d_theta, const double* d_Weff, double* d_tau, const int64_t* d_off,
+                    double* d_stats)
+{
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if (!d_theta || !d_Weff || !d_tau || !d_off || !d_stats) return fail(PGL_ERR_ARG, "null argument");
+    if ((h->t_hi - h->t_lo + PGL_RS_CHUNK - 1) / PGL_RS_CHUNK > 0x7fffffff / 2048)
+        return fail(PGL_ERR_UNSUPPORTED, "time range too long for the rescaling kernels");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t P = 1 + (size_t)h->Dstim + h->Kimp;
+    const int N = h->N;
+    ENSURE(h->gtheta, (size_t)N * P * 8);
+    ENSURE(h->Weff, (size_t)N * N * 8);
+    if (d_theta != h->gtheta.p)
+        HIPCHK(hipMemcpyAsync(h->gtheta.p, d_theta, (size_t)N * P * 8, hipMemcpyDeviceToDevice, h->stream));
+    if (d_Weff != h->Weff.p)
+        HIPCHK(hipMemcpyAsync(h->Weff.p, d_Weff, (size_t)N * N * 8, hipMemcpyDeviceToDevice, h->stream));
+    rc = enqueue_gibbs_forward(h);
+    if (rc) return rc;
+    return enqueue_rescale(h, d_tau, (const long long*)d_off, d_stats);
+}
+
+int pgl_rescale(pgl_handle h, const double* theta, const double* Weff, double* tau_out, double* stats_out)
+{
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if (!theta || !Weff || !tau_out || !stats_out) return fail(PGL_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t P = 1 + (size_t)h->Dstim + h->Kimp;
+    const int N = h->N;
+    std::vector<int64_t> off((size_t)N + 1);
+    rc = pgl_rescale_count(h, off.data());
+    if (rc) return rc;
+    const size_t ntau = (size_t)off[(size_t)N];
+    ENSURE(h->gtheta, (size_t)N * P * 8);
+    ENSURE(h->Weff, (size_t)N * N * 8);
+    ENSURE(h->rs_off, ((size_t)N + 1) * 8);
+    ENSURE(h->rs_tau, std::max<size_t>(ntau, 1) * 8);
+    ENSURE(h->rs_stats, (size_t)N * 4 * 8);
+    HIPCHK(hipMemcpyAsync(h->gtheta.p, theta, (size_t)N * P * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->Weff.p, Weff, (size_t)N * N * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->rs_off.p, off.data(), ((size_t)N + 1) * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));          // (pageable sources: see pgl_gibbs_prepare_all)
+    rc = pgl_rescale_dev(h, (const double*)h->gtheta.p, (const double*)h->Weff.p, (double*)h->rs_tau.p,
+                         (const int64_t*)h->rs_off.p, (double*)h->rs_stats.p);
+    if (rc) return rc;
+    if (ntau) HIPCHK(hipMemcpyAsync(tau_out, h->rs_tau.p, ntau * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(stats_out, h->rs_stats.p, (size_t)N * 4 * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return PGL_OK;
 }
 
 int pgl_state(pgl_handle h, int n, const double* theta_n, const double* Weff_col, double* lam_out,

@@ -34,3 +34,4 @@
 #include "pglm_stim.hip.h"
 #include "pglm_bfgs.hip.h"
 #include "pglm_ncg.hip.h"
+#include "pglm_rescale.hip.h"

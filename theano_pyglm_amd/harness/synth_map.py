@@ -6,6 +6,7 @@ MAP fit on synthetic data -- counterpart of test/synth_map.py + test/synth_harne
 The sweep over the neurons runs as the GPU lock-step optimizer by default (inference/batched_bfgs.py);
 --sequential (batched=False) is the reference's loop of per-neuron scipy fits; --newton-cg runs the sweep as the GPU
 lock-step Newton-CG optimizer on device Hessian-vector products (inference/batched_newton_cg.py; the reference's use_rop).
+--gof prints the time-rescaling KS table of the fitted model (inference/gof.py) after the fit.
 """
 import argparse
 import os
@@ -34,7 +35,7 @@ def initialize_test_harness(model_name, data, data_dir=None):
     return popn, popn_true, x_true
 
 
-def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False):
+def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False, gof=False):
     """test/synth_map.py:10-32."""
     popn, popn_true, x_true = initialize_test_harness(model_name, data, data_dir)
     x0 = popn.sample(rng)
@@ -47,6 +48,9 @@ def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, r
     if results_dir is not None:
         with open(os.path.join(results_dir, 'results.pkl'), 'wb') as f:
             pickle.dump(x_inf, f, protocol=-1)
+    if gof:
+        from theano_pyglm_amd.inference.gof import ks_time_rescaling, format_table
+        print(format_table(ks_time_rescaling(popn, x_inf)))
     return x_inf, ll_inf, wall
 
 
@@ -60,11 +64,13 @@ def main():
     ap.add_argument('--newton-cg', action='store_true',
                     help='lock-step Newton-CG on device Hessian-vector products instead of lock-step BFGS '
                          '(with --sequential: per-neuron scipy Newton-CG fits)')
+    ap.add_argument('--gof', action='store_true',
+                    help='after the fit: time-rescaling KS test of every neuron (rescaled inter-spike intervals against Exp(1))')
     args = ap.parse_args()
     with open(args.dataFile, 'rb') as f:
         data = pickle.load(f)
     run_synth_test(args.model, data, args.resultsDir, os.path.dirname(args.dataFile),
-                   False if args.sequential else ('torch' if args.newton_cg else None), use_rop=args.newton_cg)
+                   False if args.sequential else ('torch' if args.newton_cg else None), use_rop=args.newton_cg, gof=args.gof)
 
 
 if __name__ == '__main__':

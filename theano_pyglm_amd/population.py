@@ -372,6 +372,29 @@ class Population(object):
         parameter vector -- minus coord_descent.grad_nlp (coord_descent.py:61-80)."""
         return self.compute_lp_grad_packed(vars, n, n + 1)[1][0]
 
+    # -- goodness of fit -------------------------------------------------------------------
+    def compute_rescaled_intervals(self, vars):
+        """Time rescaling (Brown et al. 2002) of every neuron's spike train under `vars`: the integrated rate between
+        consecutive event bins, Exp(1) under the true model.  One forward pass and one segmented sum on the device per data
+        sequence (pgl_rescale); no rate array comes back to the host.  Returns (taus, stats): taus[n] the intervals of
+        neuron n, the data sequences one after the other (the interval before the first event of a sequence is censored);
+        stats (N, 4) summed over the sequences: expected count, event bins, event bins holding more than one spike, 0.
+        A bin with several spikes is one event; the discrete-time correction of Haslinger et al. (2010) is not applied."""
+        if self._time_shard is not None:
+            raise ValueError("rescaled intervals of a time-sharded population are not implemented")
+        self._check_vars(vars)
+        theta = self.theta_matrix(vars)
+        Weff = self.W_eff(vars)
+        parts = [[] for _ in range(self.N)]
+        stats = np.zeros((self.N, 4))
+        for data in self.data_sequences:
+            self.set_data(data)
+            tau, off, st = self._handle(self._current).rescale(theta, Weff)
+            for n in range(self.N):
+                parts[n].append(tau[off[n]:off[n + 1]])
+            stats += st
+        return [np.concatenate(p) if p else np.zeros(0) for p in parts], stats
+
     # -- state ---------------------------------------------------------------------------
     def eval_state(self, vars):
         """population.py:88-120: rates, currents and component state of every neuron."""
