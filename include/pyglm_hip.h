@@ -422,6 +422,51 @@ int pgl_simulate(int N, int64_t nT, int R, int nlin, double dt, double* X, const
                  const double* uniforms, int64_t n_uniforms, uint64_t seed, double* S,
                  int64_t* n_exceptions_out);
 
+/* Batched simulation: many independent spike trains (replicates) of one model, one workgroup per replicate on the device.
+ * The algorithm is pgl_simulate's; only the random numbers differ, because the reference's draw order (one draw per spiking
+ * neuron per round, in neuron order, from ONE stream) is serial by construction.  Here every neuron of every replicate has a
+ * stateless threshold stream of its own:
+ *
+ *     G      = 0x9e3779b97f4a7c15                                   (all arithmetic in uint64, wrapping)
+ *     mix(z) : z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9;  z = (z ^ (z >> 27)) * 0x94d049bb133111eb;  return z ^ (z >> 31)
+ *     z      = mix(mix(mix(mix(seed + G) + G * (r + 1)) + G * (n + 1)) + G * (k + 1))
+ *     u      = ((double)(z >> 11) + 0.5) * 2^-53                     (IEEE double operations, round to nearest)
+ *     thr    = -log(u)
+ *
+ * is the k-th threshold of neuron n in replicate (stream index) r: k = 0 is the initial one and k increases by one
+ * each time that neuron spikes.  u lies in (0, 1]: never 0; 1 (a zero threshold) once in 2^53 draws.  A neuron's
+ * thresholds do not depend on what the other neurons do.
+ * Per bin t: acc += nlin(X[t,:]) * dt; rounds while any acc > thr: S[t,n] += 1 for those neurons; a round that starts with some
+ * S[t,n] >= 10 is dropped and counted as an exception (the check sits after the increment and before the scatter, as in
+ * pgl_simulate); otherwise the spiking neurons' AW[n_pre,:,:] are added to X[t+1 : t+1+min(R, nT-t-1), :] in ascending
+ * n_pre, acc -= thr (clamped at 0) and a new threshold is drawn.
+ *
+ * simulate_streams: host reference of one replicate (no GPU needed).  X (nT, N) in/out as in pgl_simulate; S (nT, N) uint8
+ *     out; rep = the stream index r; closest_call_out (may be NULL) = the smallest |acc - thr| / thr over every comparison
+ *     the run made -- how far the run stayed from a spike decision that a last-place difference could flip.
+ * simulate_batch: replicates rep0 .. rep0 + n_rep - 1 on `device`; replicate i of a call uses stream index rep0 + i, so a
+ *     batch equals its replicates run one at a time.  Host arrays: X0 (nT, N) bias + stimulus current shared by all
+ *     replicates, AW (N, R, N) in the layout of pgl_simulate; S_out (n_rep, nT, N) uint8 and X_out (n_rep, nT, N) total
+ *     currents may be NULL; counts_out (n_rep, N) spikes per neuron; exceptions_out (n_rep).  N <= 1024.
+ *     The only state across bins is acc, thr and k per neuron and a ring of the next R bins of current (R x N doubles): in
+ *     LDS when it fits, else in a per-replicate global workspace.  flags bit 0 forces the global ring.  All arithmetic f64;
+ *     the sums have a fixed order: two calls give the same bits.
+ * simulate_batch_dev: the same with device pointers, asynchronous on `stream` (hipStream_t as void*, NULL = the null
+ *     stream); d_S / d_X may be NULL (counts alone come back); d_workspace holds n_rep * workspace_bytes_per_rep bytes and
+ *     may be NULL when the ring is in LDS.
+ * simulate_batch_plan: dry run of the ring placement (no GPU needed): ring_in_lds and the workspace bytes per replicate
+ *     (R * N * 8 for the global ring, 0 for LDS).
+ * Bad arguments: PGL_ERR_ARG; no visible device: PGL_ERR_HIP as pgl_create. */
+int pgl_simulate_streams(int N, int64_t nT, int R, int nlin, double dt, double* X, const double* AW, int rep,
+                         uint64_t seed, uint8_t* S, int64_t* n_exceptions_out, double* closest_call_out);
+int pgl_simulate_batch(int device, int N, int64_t nT, int R, int nlin, double dt, const double* X0, const double* AW,
+                       int n_rep, int rep0, uint64_t seed, int flags, uint8_t* S_out, double* X_out,
+                       int64_t* counts_out, int64_t* exceptions_out);
+int pgl_simulate_batch_dev(int device, int N, int64_t nT, int R, int nlin, double dt, const double* d_X0,
+                           const double* d_AW, int n_rep, int rep0, uint64_t seed, int flags, uint8_t* d_S, double* d_X,
+                           int64_t* d_counts, int64_t* d_exceptions, double* d_workspace, void* stream);
+int pgl_simulate_batch_plan(int N, int R, int flags, int* ring_in_lds, long long* workspace_bytes_per_rep);
+
 /* Timing of the most recent pgl_ll_grad[_dev] call, measured with HIP events on the
  * handle's stream: ms of the fused kernel alone and of the whole call (prep +
  * fused + finalize).  For the _dev form call after pgl_sync. */

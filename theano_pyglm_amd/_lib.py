@@ -40,6 +40,7 @@ SYMBOLS = [
     'pgl_ncg_state_doubles', 'pgl_ncg_init_dev', 'pgl_ncg_cg_step_dev', 'pgl_ncg_trial_dev', 'pgl_ncg_search_step_dev',
     'pgl_hess_dev', 'pgl_hess',
     'pgl_rescale_count', 'pgl_rescale_dev', 'pgl_rescale',
+    'pgl_simulate_streams', 'pgl_simulate_batch', 'pgl_simulate_batch_dev', 'pgl_simulate_batch_plan',
 ]
 
 
@@ -178,6 +179,14 @@ def load():
         lib.pgl_last_kernels.argtypes = [vp, C.c_char_p, C.c_int]
     lib.pgl_simulate.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_double, vp, vp, vp,
                                  C.c_int64, C.c_uint64, vp, vp]
+    if hasattr(lib, 'pgl_simulate_batch'):                    # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
+        lib.pgl_simulate_streams.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_double, vp, vp, C.c_int, C.c_uint64,
+                                             vp, vp, vp]
+        sim = [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_double, vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_int,
+               vp, vp, vp, vp]
+        lib.pgl_simulate_batch.argtypes = sim
+        lib.pgl_simulate_batch_dev.argtypes = sim + [vp, vp]
+        lib.pgl_simulate_batch_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
     for name in SYMBOLS:
         if 'PYGLM_HIP_LIB' in os.environ and not hasattr(lib, name):
             continue
@@ -226,6 +235,63 @@ def simulate(X0, AW, nlin, dt, uniforms=None, seed=0):
     _chk(lib.pgl_simulate(N, nT, R, int(kind), float(dt), _ptr(X), _ptr(AW), _ptr(u),
                           0 if u is None else u.size, int(seed), _ptr(S), C.byref(nexc)))
     return S, X, int(nexc.value)
+
+
+def _sim_args(X0, AW, nlin):
+    X0 = _f64(X0)
+    AW = _f64(AW)
+    if X0.ndim != 2 or AW.ndim != 3 or AW.shape[0] != X0.shape[1] or AW.shape[2] != X0.shape[1]:
+        raise ValueError("X0 must be (nT, N) and AW (N, R, N) [n_pre][tau][n_post]")
+    return X0, AW, int({'exp': NLIN_EXP, 'explinear': NLIN_EXPLINEAR}.get(nlin, nlin))
+
+
+def simulate_streams(X0, AW, nlin, dt, rep=0, seed=0):
+    """Host reference of one replicate on the per-neuron threshold streams (pgl_simulate_streams; needs no GPU).
+    X0 (nT, N), AW (N, R, N) as in simulate.  Returns (S uint8 (nT, N), X (nT, N), n_exceptions, closest_call)."""
+    lib = load()
+    X0, AW, kind = _sim_args(X0, AW, nlin)
+    X = X0.copy()
+    nT, N = X.shape
+    S = np.empty((nT, N), dtype=np.uint8)
+    nexc = C.c_int64(0)
+    closest = C.c_double(0.0)
+    _chk(lib.pgl_simulate_streams(N, nT, AW.shape[1], kind, float(dt), _ptr(X), _ptr(AW), int(rep), int(seed), _ptr(S),
+                                  C.byref(nexc), C.byref(closest)))
+    return S, X, int(nexc.value), float(closest.value)
+
+
+def simulate_batch_plan(N, R, flags=0):
+    """(ring_in_lds, workspace_bytes_per_rep) of pgl_simulate_batch for this shape: a dry run, needs no GPU."""
+    lds, ws = C.c_int(0), C.c_longlong(0)
+    _chk(load().pgl_simulate_batch_plan(int(N), int(R), int(flags), C.byref(lds), C.byref(ws)))
+    return bool(lds.value), int(ws.value)
+
+
+def simulate_batch(X0, AW, nlin, dt, n_rep, seed=0, rep0=0, flags=0, spikes=True, currents=False, device=0):
+    """n_rep replicates on the device (pgl_simulate_batch), stream indices rep0 .. rep0 + n_rep - 1.  Returns a dict:
+    S (n_rep, nT, N) uint8 or None, X (n_rep, nT, N) total currents or None, counts (n_rep, N), exceptions (n_rep)."""
+    lib = load()
+    X0, AW, kind = _sim_args(X0, AW, nlin)
+    nT, N = X0.shape
+    n_rep = int(n_rep)
+    S = np.empty((n_rep, nT, N), dtype=np.uint8) if spikes else None
+    X = np.empty((n_rep, nT, N)) if currents else None
+    counts = np.empty((n_rep, N), dtype=np.int64)
+    exc = np.empty(n_rep, dtype=np.int64)
+    _chk(lib.pgl_simulate_batch(int(device), N, nT, AW.shape[1], kind, float(dt), _ptr(X0), _ptr(AW), n_rep, int(rep0),
+                                int(seed), int(flags), _ptr(S), _ptr(X), _ptr(counts), _ptr(exc)))
+    return {'S': S, 'X': X, 'counts': counts, 'exceptions': exc}
+
+
+def simulate_batch_dev(N, nT, R, nlin, dt, d_X0, d_AW, n_rep, d_counts, d_exceptions, seed=0, rep0=0, flags=0, d_S=0, d_X=0,
+                       d_workspace=0, stream=0, device=0):
+    """Device-pointer form (integers, e.g. torch.Tensor.data_ptr(); asynchronous on `stream`, 0 = the null stream);
+    d_S / d_X = 0: counts and exceptions alone; see pgl_simulate_batch_dev."""
+    vp = lambda a: C.c_void_p(a) if a else None
+    kind = int({'exp': NLIN_EXP, 'explinear': NLIN_EXPLINEAR}.get(nlin, nlin))
+    _chk(load().pgl_simulate_batch_dev(int(device), int(N), int(nT), int(R), kind, float(dt), vp(d_X0), vp(d_AW), int(n_rep),
+                                       int(rep0), int(seed), int(flags), vp(d_S), vp(d_X), vp(d_counts), vp(d_exceptions),
+                                       vp(d_workspace), vp(stream)))
 
 
 class DeviceGlm(object):

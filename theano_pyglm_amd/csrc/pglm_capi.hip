@@ -218,6 +218,18 @@ static void launch_sepf(int which, const SepfParams& sp, hipStream_t s)
     }
 }
 
+// one workgroup per replicate (k_simulate, pglm_simulate.hip.h)
+template <int NLIN, bool RING_LDS>
+static int sim_launch(const SimParams& sp, int n_rep, int threads, size_t lds, hipStream_t s)
+{
+    if (lds > 65536)
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_simulate<NLIN, RING_LDS>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_simulate<NLIN, RING_LDS>), dim3(n_rep), dim3(threads), lds, s, sp);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
 extern "C" {
 
 const char* pgl_last_error(void) { return g_err.c_str(); }
@@ -2710,6 +2722,158 @@ int pgl_simulate(int N, int64_t nT, int R, int nlin, double dt, double* X, const
     }
     if (n_exceptions_out) *n_exceptions_out = n_exc;
     return PGL_OK;
+}
+
+// ---- batched simulation on per-neuron threshold streams (pglm_simulate.hip.h; the stream rule: include/pyglm_hip.h) ----
+// Host reference of one replicate: pgl_simulate's loop, the thresholds from the stateless streams.
+int pgl_simulate_streams(int N, int64_t nT, int R, int nlin, double dt, double* X, const double* AW, int rep,
+                         uint64_t seed, uint8_t* S, int64_t* n_exceptions_out, double* closest_call_out)
+{
+    if (N <= 0 || nT <= 0 || R <= 0 || rep < 0 || !X || !AW || !S) return fail(PGL_ERR_ARG, "bad argument");
+    if (nlin != PGL_NLIN_EXP && nlin != PGL_NLIN_EXPLINEAR) return fail(PGL_ERR_ARG, "unknown nonlinearity");
+    std::vector<double> acc(N, 0.0), thr(N);
+    std::vector<unsigned long long> key(N), k(N, 1);
+    std::vector<char> spk(N);
+    for (int n = 0; n < N; ++n) {
+        key[n] = pgl_sim_key(seed, (unsigned long long)rep, (unsigned long long)n);
+        thr[n] = -std::log(pgl_sim_uniform(key[n], 0));
+    }
+    std::memset(S, 0, (size_t)nT * N);
+    int64_t n_exc = 0;
+    double closest = __builtin_huge_val();
+    const auto compare = [&](int n) {                                    // acc > thr, and how close the call was
+        const double m = std::fabs(acc[n] - thr[n]) / thr[n];
+        if (m < closest) closest = m;
+        return acc[n] > thr[n];
+    };
+    for (int64_t t = 0; t < nT; ++t) {
+        double* Xt = X + (size_t)t * N;
+        uint8_t* St = S + (size_t)t * N;
+        int n_spk = 0;
+        for (int n = 0; n < N; ++n) {
+            acc[n] += host_nlin(Xt[n], nlin) * dt;
+            spk[n] = compare(n);
+            if (spk[n]) { St[n] += 1; ++n_spk; }
+        }
+        const int64_t t_imp = std::min<int64_t>(nT - t - 1, R);
+        while (n_spk > 0) {
+            bool capped = false;
+            for (int n = 0; n < N; ++n) capped = capped || (St[n] >= 10);
+            if (capped) { ++n_exc; break; }
+            for (int np = 0; np < N; ++np) {
+                if (!spk[np]) continue;
+                const double* aw = AW + (size_t)np * R * N;
+                for (int64_t i = 0; i < t_imp * N; ++i) Xt[N + i] += aw[i];
+            }
+            for (int n = 0; n < N; ++n) {
+                if (spk[n]) {
+                    acc[n] -= thr[n];
+                    thr[n] = -std::log(pgl_sim_uniform(key[n], k[n]++));
+                }
+                if (acc[n] < 0) acc[n] = 0;
+            }
+            n_spk = 0;
+            for (int n = 0; n < N; ++n) {
+                spk[n] = compare(n);
+                if (spk[n]) { St[n] += 1; ++n_spk; }
+            }
+        }
+    }
+    if (n_exceptions_out) *n_exceptions_out = n_exc;
+    if (closest_call_out) *closest_call_out = closest;
+    return PGL_OK;
+}
+
+static int sim_check(int N, int64_t nT, int R, int nlin, double dt, int n_rep, int rep0)
+{
+    if (N <= 0 || nT <= 0 || R <= 0 || n_rep <= 0 || rep0 < 0 || !(dt > 0)) return fail(PGL_ERR_ARG, "bad argument");
+    if (N > PGL_SIM_MAXN) return fail(PGL_ERR_ARG, "N > 1024 neurons");
+    if ((long long)R * N > (1 << 27)) return fail(PGL_ERR_ARG, "R * N too large");
+    if (nlin != PGL_NLIN_EXP && nlin != PGL_NLIN_EXPLINEAR) return fail(PGL_ERR_ARG, "unknown nonlinearity");
+    return PGL_OK;
+}
+
+int pgl_simulate_batch_plan(int N, int R, int flags, int* ring_in_lds, long long* workspace_bytes_per_rep)
+{
+    if (N <= 0 || N > PGL_SIM_MAXN || R <= 0 || (long long)R * N > (1 << 27)) return fail(PGL_ERR_ARG, "bad argument");
+    const long long bytes = (long long)R * N * 8;
+    const bool lds = !(flags & 1) && bytes <= PGL_SIM_LDS_MAX;
+    if (ring_in_lds) *ring_in_lds = lds ? 1 : 0;
+    if (workspace_bytes_per_rep) *workspace_bytes_per_rep = lds ? 0 : bytes;
+    return PGL_OK;
+}
+
+static int sim_device(int device)
+{
+    int ndev = 0;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (ndev <= 0) return fail(PGL_ERR_HIP, "no HIP device visible");
+    if (device < 0 || device >= ndev) return fail(PGL_ERR_ARG, "device index out of range");
+    HIPCHK(hipSetDevice(device));
+    return PGL_OK;
+}
+
+int pgl_simulate_batch_dev(int device, int N, int64_t nT, int R, int nlin, double dt, const double* d_X0,
+                           const double* d_AW, int n_rep, int rep0, uint64_t seed, int flags, uint8_t* d_S, double* d_X,
+                           int64_t* d_counts, int64_t* d_exceptions, double* d_workspace, void* stream)
+{
+    int rc = sim_check(N, nT, R, nlin, dt, n_rep, rep0);
+    if (rc) return rc;
+    if (!d_X0 || !d_AW || !d_counts || !d_exceptions) return fail(PGL_ERR_ARG, "null argument");
+    int lds = 0;
+    long long ws = 0;
+    pgl_simulate_batch_plan(N, R, flags, &lds, &ws);
+    if (!lds && !d_workspace) return fail(PGL_ERR_ARG, "the ring of this shape lives in global memory: d_workspace is NULL");
+    rc = sim_device(device);
+    if (rc) return rc;
+    SimParams sp;
+    sp.X0 = d_X0; sp.AW = d_AW; sp.ws = d_workspace; sp.S = d_S; sp.X = d_X;
+    sp.counts = (long long*)d_counts; sp.exc = (long long*)d_exceptions;
+    sp.nT = nT; sp.N = N; sp.R = R; sp.rep0 = rep0; sp.seed = seed; sp.dt = dt;
+    // threads: one per neuron at least; the scatter of a spike (R N additions) is shared by all of them
+    const int threads = (N <= 256 && (long long)R * N <= 16384) ? 256 : PGL_SIM_MAXN;
+    const size_t ring = (size_t)R * N * 8;
+    hipStream_t s = (hipStream_t)stream;
+    if (nlin == PGL_NLIN_EXPLINEAR)
+        return lds ? sim_launch<1, true>(sp, n_rep, threads, ring, s) : sim_launch<1, false>(sp, n_rep, threads, 0, s);
+    return lds ? sim_launch<0, true>(sp, n_rep, threads, ring, s) : sim_launch<0, false>(sp, n_rep, threads, 0, s);
+}
+
+int pgl_simulate_batch(int device, int N, int64_t nT, int R, int nlin, double dt, const double* X0, const double* AW,
+                       int n_rep, int rep0, uint64_t seed, int flags, uint8_t* S_out, double* X_out,
+                       int64_t* counts_out, int64_t* exceptions_out)
+{
+    int rc = sim_check(N, nT, R, nlin, dt, n_rep, rep0);
+    if (rc) return rc;
+    if (!X0 || !AW || !counts_out || !exceptions_out) return fail(PGL_ERR_ARG, "null argument");
+    rc = sim_device(device);
+    if (rc) return rc;
+    int lds = 0;
+    long long ws = 0;
+    pgl_simulate_batch_plan(N, R, flags, &lds, &ws);
+    const size_t nx = (size_t)nT * N, naw = (size_t)N * R * N, nout = (size_t)n_rep * nx;
+    DevBuf dX0, dAW, dS, dX, dC, dE, dW;
+    const auto done = [&](int r) {
+        release(dX0); release(dAW); release(dS); release(dX); release(dC); release(dE); release(dW);
+        return r;
+    };
+    if (ensure(dX0, nx * 8) || ensure(dAW, naw * 8) || ensure(dC, (size_t)n_rep * N * 8) || ensure(dE, (size_t)n_rep * 8) ||
+        (S_out && ensure(dS, nout)) || (X_out && ensure(dX, nout * 8)) || (!lds && ensure(dW, (size_t)n_rep * ws)))
+        return done(PGL_ERR_HIP);
+    if (hipMemcpy(dX0.p, X0, nx * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dAW.p, AW, naw * 8, hipMemcpyHostToDevice) != hipSuccess)
+        return done(fail(PGL_ERR_HIP, "simulate_batch: upload failed"));
+    rc = pgl_simulate_batch_dev(device, N, nT, R, nlin, dt, (const double*)dX0.p, (const double*)dAW.p, n_rep, rep0, seed,
+                                flags, (uint8_t*)dS.p, (double*)dX.p, (int64_t*)dC.p, (int64_t*)dE.p, (double*)dW.p, nullptr);
+    if (rc) return done(rc);
+    hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return done(fail(PGL_ERR_HIP, std::string("simulate_batch: ") + hipGetErrorString(e)));
+    if (hipMemcpy(counts_out, dC.p, (size_t)n_rep * N * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(exceptions_out, dE.p, (size_t)n_rep * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+        (S_out && hipMemcpy(S_out, dS.p, nout, hipMemcpyDeviceToHost) != hipSuccess) ||
+        (X_out && hipMemcpy(X_out, dX.p, nout * 8, hipMemcpyDeviceToHost) != hipSuccess))
+        return done(fail(PGL_ERR_HIP, "simulate_batch: download failed"));
+    return done(PGL_OK);
 }
 
 // Leading singular pairs of a batch of (L x D) matrices (k_lsp_*, pglm_stim.hip.h).  Host arrays; everything in between on

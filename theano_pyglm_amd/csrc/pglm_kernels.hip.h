@@ -20,6 +20,8 @@
 //                            the sliced path for N > 128, optional f32 feature tile)
 // Hessian-vector products H.v = F^T.(c o (F.v)) reuse the scheme with the epilogue swapped for one multiply (k_hvp5).
 // The dense Hessian H = F^T.diag(c).F is a contraction over time of its own (k_hess, pglm_hess.hip.h).
+// Simulation produces spikes instead of reading them: one workgroup per replicate runs the time loop (k_simulate,
+// pglm_simulate.hip.h).
 #pragma once
 //
 // The kernels live in one header per family; this file is the translation unit's table of contents.
@@ -35,3 +37,4 @@
 #include "pglm_bfgs.hip.h"
 #include "pglm_ncg.hip.h"
 #include "pglm_rescale.hip.h"
+#include "pglm_simulate.hip.h"

@@ -7,6 +7,7 @@ The sweep over the neurons runs as the GPU lock-step optimizer by default (infer
 --sequential (batched=False) is the reference's loop of per-neuron scipy fits; --newton-cg runs the sweep as the GPU
 lock-step Newton-CG optimizer on device Hessian-vector products (inference/batched_newton_cg.py; the reference's use_rop).
 --gof prints the time-rescaling KS table of the fitted model (inference/gof.py) after the fit.
+--ppc N prints the predictive spike-count table of N replicates simulated from the fitted model (inference/predictive.py).
 """
 import argparse
 import os
@@ -35,7 +36,7 @@ def initialize_test_harness(model_name, data, data_dir=None):
     return popn, popn_true, x_true
 
 
-def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False, gof=False):
+def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False, gof=False, ppc=0):
     """test/synth_map.py:10-32."""
     popn, popn_true, x_true = initialize_test_harness(model_name, data, data_dir)
     x0 = popn.sample(rng)
@@ -51,6 +52,9 @@ def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, r
     if gof:
         from theano_pyglm_amd.inference.gof import ks_time_rescaling, format_table
         print(format_table(ks_time_rescaling(popn, x_inf)))
+    if ppc:
+        from theano_pyglm_amd.inference import predictive
+        print(predictive.format_table(predictive.predictive_counts(popn, x_inf, ppc)))
     return x_inf, ll_inf, wall
 
 
@@ -66,11 +70,13 @@ def main():
                          '(with --sequential: per-neuron scipy Newton-CG fits)')
     ap.add_argument('--gof', action='store_true',
                     help='after the fit: time-rescaling KS test of every neuron (rescaled inter-spike intervals against Exp(1))')
+    ap.add_argument('--ppc', type=int, default=0, metavar='N',
+                    help='after the fit: predictive spike counts of N replicates simulated from the fitted model on the device')
     args = ap.parse_args()
     with open(args.dataFile, 'rb') as f:
         data = pickle.load(f)
     run_synth_test(args.model, data, args.resultsDir, os.path.dirname(args.dataFile),
-                   False if args.sequential else ('torch' if args.newton_cg else None), use_rop=args.newton_cg, gof=args.gof)
+                   False if args.sequential else ('torch' if args.newton_cg else None), use_rop=args.newton_cg, gof=args.gof, ppc=args.ppc)
 
 
 if __name__ == '__main__':

@@ -418,17 +418,14 @@ class Population(object):
         return state
 
     # -- simulation ------------------------------------------------------------------------
-    def simulate(self, vars, T_range, dt, stim, dt_stim, rng=None, verbose=False, native=True):
-        """population.py:233-389: integrate-and-fire thinning with exponential thresholds;
-        every spike adds A*W*impulse to X[t+1 : t+R+1] (351-353); <= 10 spikes per bin.
-        Seeded (the reference uses the global np.random).  native=True runs the time loop in the
-        C++ library (pgl_simulate, ~100x the Python loop, same draw order); native=False is the
-        line-by-line Python restatement kept for cross-checking."""
-        from theano_pyglm_amd.components.priors import _rng
-        r = _rng(rng)
+    def _simulation_inputs(self, vars, T_range, dt, stim, dt_stim, nT=None):
+        """population.py:252-282, shared by simulate and simulate_batch: X (nT, N) bias + stimulus current and
+        AW (n_pre, n_post, R) = A * W * impulse.  nT: the number of bins where the caller knows it (a recording's length);
+        default the reference's len(arange(T_start, T_stop, dt))."""
         T_start, T_stop = T_range
         N = self.N
-        nT = len(np.arange(T_start, T_stop, dt))
+        if nT is None:
+            nT = len(np.arange(T_start, T_stop, dt))
         X = np.zeros((nT, N))
         for n in range(N):
             X[:, n] = self.glm.bias_model.I_bias(vars['glms'][n]['bias'])
@@ -441,8 +438,49 @@ class Population(object):
         # imps[n_pre, n_post, :] (population.py:275-282)
         imps = np.array([self.glm.imp_model.impulse(vars['glms'][n]['imp']) for n in range(N)])
         imps = np.transpose(imps, axes=[1, 0, 2])
-        T_imp = imps.shape[2]
         AW = self.W_eff(vars)[:, :, None] * imps              # (n_pre, n_post, R)
+        return X, AW
+
+    def simulate_batch(self, vars, T_range, dt, stim, dt_stim, n_rep, seed=0, rep0=0, spikes=True, currents=False,
+                       device=True):
+        """n_rep independent spike trains of the model at `vars`: simulate's algorithm on per-neuron threshold streams
+        (the rule: include/pyglm_hip.h), one workgroup per replicate on the device (pgl_simulate_batch).  Replicate i
+        uses stream index rep0 + i, so a batch equals its replicates run one at a time.  Returns a dict: S
+        (n_rep, nT, N) uint8 (None unless spikes), X (n_rep, nT, N) total currents (None unless currents), counts
+        (n_rep, N) spikes per neuron, exceptions (n_rep).  device=False loops the host reference pgl_simulate_streams.
+        simulate keeps the reference's draw order; the two do not produce the same trains."""
+        X0, AW = self._simulation_inputs(vars, T_range, dt, stim, dt_stim)
+        AW = np.ascontiguousarray(np.transpose(AW, (0, 2, 1)))
+        kind = self.glm.nlin_model.kind
+        if device:
+            return _lib.simulate_batch(X0, AW, kind, dt, n_rep, seed=seed, rep0=rep0, spikes=spikes, currents=currents,
+                                       device=self.device)
+        nT, N = X0.shape
+        out = {'S': np.empty((n_rep, nT, N), dtype=np.uint8) if spikes else None,
+               'X': np.empty((n_rep, nT, N)) if currents else None,
+               'counts': np.empty((n_rep, N), dtype=np.int64), 'exceptions': np.empty(n_rep, dtype=np.int64)}
+        for i in range(n_rep):
+            S, X, n_exc, _ = _lib.simulate_streams(X0, AW, kind, dt, rep=rep0 + i, seed=seed)
+            if spikes:
+                out['S'][i] = S
+            if currents:
+                out['X'][i] = X
+            out['counts'][i] = S.sum(axis=0, dtype=np.int64)
+            out['exceptions'][i] = n_exc
+        return out
+
+    def simulate(self, vars, T_range, dt, stim, dt_stim, rng=None, verbose=False, native=True):
+        """population.py:233-389: integrate-and-fire thinning with exponential thresholds;
+        every spike adds A*W*impulse to X[t+1 : t+R+1] (351-353); <= 10 spikes per bin.
+        Seeded (the reference uses the global np.random).  native=True runs the time loop in the
+        C++ library (pgl_simulate, ~100x the Python loop, same draw order); native=False is the
+        line-by-line Python restatement kept for cross-checking."""
+        from theano_pyglm_amd.components.priors import _rng
+        r = _rng(rng)
+        N = self.N
+        X, AW = self._simulation_inputs(vars, T_range, dt, stim, dt_stim)
+        nT = X.shape[0]
+        T_imp = AW.shape[2]
         if native:
             # uniforms in the reference's draw order come from `rng`; the library continues with
             # its own generator if the pre-drawn stream runs out
