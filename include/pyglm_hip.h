@@ -309,6 +309,52 @@ int pgl_ncg_search_step_dev(pgl_handle h, double* d_state, int M, int P, const i
                             double mu, double sigma, double lam, int maxiter, const int* d_pos_next, double* d_Xt_next,
                             double* d_V, double* flags_out);
 
+/* Lock-step Hamiltonian Monte Carlo (inference/batched_hmc.py) as row kernels on the handle's stream: posterior samples of
+ * the theta rows [bias, w_stim, w_ir] of M neurons n_lo .. n_lo + M - 1 at once, one workgroup per row around ONE
+ * pgl_ll_grad_dev over all rows per leapfrog step.  The algorithm is Neal (2011) fig. 2 as inference/hmc.py: hmc_lockstep
+ * states it (restated in csrc/pglm_hmc.h) with a diagonal mass matrix:
+ *     U = -(ll + log prior), the priors of pgl_bfgs_objective_dev (same arguments).  A non-finite ll + log prior gives
+ *         U = +inf; a NaN or infinite entry of its gradient becomes 0; a transition that ends at a non-finite energy is
+ *         rejected (the rules of hmc_lockstep's callers, gibbs.py: _neg_lp_grad).
+ *     K = 1/2 sum_j p_j^2 minv_j;  d_minv (M, P) is the diagonal of the inverse mass matrix, NULL = identity.
+ *     transition t:  p_j = z_j / sqrt(minv_j);  H0 = U + K;  p -= step/2 grad U;  n_leapfrog times { q += step minv o p;
+ *         p -= step grad U(q) (step/2 the last time) };  H1 = U(q) + K(p);  accept iff H1 is finite and log u < H0 - H1.
+ * Random numbers are stateless, from the mix of pgl_simulate_batch:
+ *     G      = 0x9e3779b97f4a7c15                                   (all arithmetic in uint64, wrapping)
+ *     mix(z) : z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9;  z = (z ^ (z >> 27)) * 0x94d049bb133111eb;  return z ^ (z >> 31)
+ *     key    = mix(mix(mix(seed + G) + G * (n + 1)) + G * (t + 1))   n: NEURON index (n_lo + row), t: transition, from 0
+ *     U(k)   = ((double)(mix(key + G * (k + 1)) >> 11) + 0.5) * 2^-53                       in (0, 1]
+ *     u      = U(0)                                                   the accept uniform of (seed, n, t)
+ *     z_j    = sqrt(-2 log U(2 j + 1)) * cos(6.283185307179586 * U(2 j + 2))               component j (Box-Muller)
+ * The key holds the neuron index, not the row of the call: a chain over [n_lo, n_hi) equals the matching rows of a chain
+ * over [0, N).  Every sum over a row has a fixed order: two runs give the same bits.
+ * Step size: one per row.  While t < n_warmup, after the decision: factor = 1.02 if avg_accept > 0.9 else 0.98 (avg_accept
+ * before the update), avg_accept = 0.95 avg_accept + (1 - 0.95) accepted, step = clip(step * factor, 1e-3, 1)
+ * (adapt_step_size of inference/hmc.py); from t = n_warmup on it is frozen.  (The reference, gibbs.py:306-316, shares one
+ * step size among all neurons and adapts for ever.)
+ * All state of M rows of P parameters lives in ONE device block of pgl_hmc_state_doubles(M, P) doubles, in this order:
+ *   (M,P) each: q (the current point), p (momentum), q0 (start of the running transition), g (grad U at the last accepted
+ *               point);
+ *   (M) each:   U0 (U at the last accepted point), H0, step, avg_accept (starts at 0.9), n_accept (accepted transitions
+ *               among those with t >= n_warmup), t (completed transitions), acc (the last decision), neuron, seed_lo,
+ *               seed_hi (the 32-bit halves of the seed).
+ *   init:   q in the state, (d_ll, d_grad) = ll (M) and its gradient (M, P) at q (overwritten with U, grad U); t = 0.
+ *   begin:  draws the momentum, H0, the half kick and the first drift; d_Xt (M, P, not part of the state) = the points to
+ *           evaluate next.
+ *   leap:   (d_ll, d_grad) = the evaluation at d_Xt (overwritten).  last == 0: full kick, next drift into d_Xt.
+ *           last != 0: half kick, H1, accept or reject (on accept U and grad U of the new point are kept: the next
+ *           transition needs no evaluation), the step-size rule while t < n_warmup, t += 1, and, unless d_sample_out is
+ *           NULL, the rows' current points q into d_sample_out (M, P).
+ * One transition is n_leapfrog evaluations and n_leapfrog + 1 row launches; nothing has to be read back in between. */
+long long pgl_hmc_state_doubles(int M, int P);
+int pgl_hmc_init_dev(pgl_handle h, double* d_state, int M, int P, int n_lo, double* d_ll, double* d_grad, int prior_kind,
+                     double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam, double step0,
+                     uint64_t seed);
+int pgl_hmc_begin_dev(pgl_handle h, double* d_state, int M, int P, const double* d_minv, double* d_Xt);
+int pgl_hmc_leap_dev(pgl_handle h, double* d_state, int M, int P, const double* d_minv, double* d_ll, double* d_grad,
+                     int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam, int last,
+                     int n_warmup, double* d_Xt, double* d_sample_out);
+
 /* convolve_with_basis(S, ibasis) (basis.py:201-236 via impulse.py:114-130):
  * fS_out (nT,N,B) row-major, float64. */
 int pgl_features(pgl_handle h, double* fS_out);

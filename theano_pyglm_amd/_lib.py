@@ -38,6 +38,7 @@ SYMBOLS = [
     'pgl_bfgs_linesearch_dev', 'pgl_bfgs_hmul_dev', 'pgl_bfgs_hmul_hist_dev', 'pgl_bfgs_update_dev', 'pgl_bfgs_step_dev', 'pgl_plan_kernels', 'pgl_last_kernels', 'pgl_leading_singular_pairs',
     'pgl_hvp_prepare_dev', 'pgl_hvp_prepare_list_dev', 'pgl_hvp_apply_dev', 'pgl_hvp',
     'pgl_ncg_state_doubles', 'pgl_ncg_init_dev', 'pgl_ncg_cg_step_dev', 'pgl_ncg_trial_dev', 'pgl_ncg_search_step_dev',
+    'pgl_hmc_state_doubles', 'pgl_hmc_init_dev', 'pgl_hmc_begin_dev', 'pgl_hmc_leap_dev',
     'pgl_hess_dev', 'pgl_hess',
     'pgl_rescale_count', 'pgl_rescale_dev', 'pgl_rescale',
     'pgl_simulate_streams', 'pgl_simulate_batch', 'pgl_simulate_batch_dev', 'pgl_simulate_batch_plan',
@@ -159,6 +160,13 @@ def load():
         lib.pgl_ncg_trial_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp]
         lib.pgl_ncg_search_step_dev.argtypes = ([vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int] +
                                                 [C.c_double] * 6 + [C.c_int, vp, vp, vp, vp])
+    if hasattr(lib, 'pgl_hmc_init_dev'):                      # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
+        lib.pgl_hmc_state_doubles.argtypes = [C.c_int, C.c_int]
+        lib.pgl_hmc_init_dev.argtypes = ([vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int] + [C.c_double] * 6 +
+                                         [C.c_double, C.c_uint64])
+        lib.pgl_hmc_begin_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
+        lib.pgl_hmc_leap_dev.argtypes = ([vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int] + [C.c_double] * 6 +
+                                         [C.c_int, C.c_int, vp, vp])
     lib.pgl_features.argtypes = [vp, vp]
     lib.pgl_impulse_currents.argtypes = [vp, vp, vp]
     lib.pgl_state.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
@@ -191,7 +199,7 @@ def load():
         if 'PYGLM_HIP_LIB' in os.environ and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
-        if name in ('pgl_bfgs_state_doubles', 'pgl_ncg_state_doubles'):
+        if name in ('pgl_bfgs_state_doubles', 'pgl_ncg_state_doubles', 'pgl_hmc_state_doubles'):
             fn.restype = C.c_longlong
         elif name not in ('pgl_last_error',):
             fn.restype = C.c_int
@@ -587,6 +595,25 @@ class DeviceGlm(object):
                                               C.c_void_p(d_Xt), C.c_void_p(d_f), C.c_void_p(d_g), int(prior[0]),
                                               *[float(z) for z in prior[1:]], int(maxiter), vp(d_pos_next), vp(d_Xt_next),
                                               C.c_void_p(d_V), vp(flags_out)))
+
+    # -- lock-step HMC row kernels (pgl_hmc_*; inference/batched_hmc.py).  prior: bfgs_objective_dev's tuple; device pointers
+    def hmc_state_doubles(self, M, P):
+        return int(self.lib.pgl_hmc_state_doubles(int(M), int(P)))
+
+    def hmc_init_dev(self, d_state, M, P, n_lo, d_ll, d_grad, prior, step0, seed):
+        _chk(self.lib.pgl_hmc_init_dev(self.h, C.c_void_p(d_state), int(M), int(P), int(n_lo), C.c_void_p(d_ll),
+                                       C.c_void_p(d_grad), int(prior[0]), *[float(z) for z in prior[1:]], float(step0),
+                                       int(seed) & 0xffffffffffffffff))
+
+    def hmc_begin_dev(self, d_state, M, P, d_minv, d_Xt):
+        _chk(self.lib.pgl_hmc_begin_dev(self.h, C.c_void_p(d_state), int(M), int(P),
+                                        C.c_void_p(d_minv) if d_minv else None, C.c_void_p(d_Xt)))
+
+    def hmc_leap_dev(self, d_state, M, P, d_minv, d_ll, d_grad, prior, last, n_warmup, d_Xt, d_sample_out=0):
+        _chk(self.lib.pgl_hmc_leap_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_minv) if d_minv else None,
+                                       C.c_void_p(d_ll), C.c_void_p(d_grad), int(prior[0]), *[float(z) for z in prior[1:]],
+                                       1 if last else 0, int(n_warmup), C.c_void_p(d_Xt),
+                                       C.c_void_p(d_sample_out) if d_sample_out else None))
 
     def sync(self):
         _chk(self.lib.pgl_sync(self.h))

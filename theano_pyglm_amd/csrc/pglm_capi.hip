@@ -2015,6 +2015,49 @@ int pgl_ncg_search_step_dev(pgl_handle h, double* d_state, int M, int P, const i
     return PGL_OK;
 }
 
+// ---- lock-step HMC row kernels (inference/batched_hmc.py) --------------------------------------------------------------
+long long pgl_hmc_state_doubles(int M, int P) { return (long long)pgl_hmc_doubles(M, P); }
+
+int pgl_hmc_init_dev(pgl_handle h, double* d_state, int M, int P, int n_lo, double* d_ll, double* d_grad, int prior_kind,
+                     double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam, double step0,
+                     uint64_t seed)
+{
+    if (!h || !d_state || !d_ll || !d_grad || M <= 0 || P <= 0 || n_lo < 0 || n_lo + M > h->N || !(step0 > 0.0))
+        return fail(PGL_ERR_ARG, "bad argument");
+    BfgsPrior q;
+    int rc = ncg_prior(h, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_hmc_init, dim3(M), dim3(256), 0, h->stream, pgl_hmc_view(d_state, M, P), d_ll, d_grad, q, n_lo, step0,
+                       (unsigned long long)seed);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+int pgl_hmc_begin_dev(pgl_handle h, double* d_state, int M, int P, const double* d_minv, double* d_Xt)
+{
+    if (!h || !d_state || !d_Xt || M <= 0 || P <= 0) return fail(PGL_ERR_ARG, "bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_hmc_begin, dim3(M), dim3(256), 0, h->stream, pgl_hmc_view(d_state, M, P), d_minv, d_Xt);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+int pgl_hmc_leap_dev(pgl_handle h, double* d_state, int M, int P, const double* d_minv, double* d_ll, double* d_grad,
+                     int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam, int last,
+                     int n_warmup, double* d_Xt, double* d_sample_out)
+{
+    if (!h || !d_state || !d_ll || !d_grad || !d_Xt || M <= 0 || P <= 0) return fail(PGL_ERR_ARG, "bad argument");
+    BfgsPrior q;
+    int rc = ncg_prior(h, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_hmc_leap, dim3(M), dim3(256), 0, h->stream, pgl_hmc_view(d_state, M, P), d_minv, d_ll, d_grad, q,
+                       last ? 1 : 0, n_warmup, d_Xt, d_sample_out);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
 int pgl_sync(pgl_handle h)
 {
     if (!h) return fail(PGL_ERR_ARG, "null handle");

@@ -1,0 +1,175 @@
+// lock-step HMC row kernels: k_hmc_*
+// Part of pglm_kernels.hip.h (included from there, in order; one translation unit).
+#pragma once
+// ---------------------------------------------------------------------------
+// Lock-step Hamiltonian Monte Carlo (inference/batched_hmc.py): the chains of all M neurons of a range -- one workgroup
+// per neuron row -- around the one launch that does the work: a fused ll+grad evaluation of all rows per leapfrog step
+// (pgl_ll_grad_dev).  The algorithm, its random numbers and its decisions are pglm_hmc.h (Neal 2011 fig. 2 as
+// inference/hmc.py states it; compiled for the host by tests/csrc/hmc_host.c); these kernels own the vectors, the
+// fixed-order reductions (pgl_blk_sum: wave64 butterflies, then the four waves through LDS), the priors' part of U and
+// its gradient and the NaN rules.  All state lives in ONE device block of doubles laid out by pgl_hmc_view.  Every row
+// takes the same number of steps: no lists, no flags, nothing for the host to read before the chain has ended.
+// ---------------------------------------------------------------------------
+#include "pglm_hmc.h"
+
+struct HmcView {
+    int M, P;
+    double *q, *p, *q0, *g;                   // (M, P): point, momentum, start of the transition, grad U at the accepted point
+    double* sc;                               // (PGL_HMC_NSCAL, M): PglHmc, field-major
+};
+__host__ __device__ inline size_t pgl_hmc_doubles(int M, int P)
+{
+    return (size_t)M * P * PGL_HMC_NVEC + (size_t)M * PGL_HMC_NSCAL;
+}
+__host__ __device__ inline HmcView pgl_hmc_view(double* st, int M, int P)
+{
+    HmcView v;
+    const size_t MP = (size_t)M * P;
+    v.M = M; v.P = P;
+    v.q = st; v.p = st + MP; v.q0 = st + 2 * MP; v.g = st + 3 * MP;
+    v.sc = st + PGL_HMC_NVEC * MP;
+    return v;
+}
+#define PGL_HMC_FIELDS(F) F(U0, 0) F(H0, 1) F(step, 2) F(avg_accept, 3) F(n_accept, 4) F(t, 5) F(acc, 6) F(neuron, 7) \
+    F(seed_lo, 8) F(seed_hi, 9)
+__device__ __forceinline__ void pgl_hmc_load(const HmcView& v, int r, PglHmc* s)
+{
+#define PGL_HMC_LD(name, k) s->name = v.sc[(size_t)k * v.M + r];
+    PGL_HMC_FIELDS(PGL_HMC_LD)
+#undef PGL_HMC_LD
+}
+__device__ __forceinline__ void pgl_hmc_store(const HmcView& v, int r, const PglHmc* s)
+{
+#define PGL_HMC_ST(name, k) v.sc[(size_t)k * v.M + r] = s->name;
+    PGL_HMC_FIELDS(PGL_HMC_ST)
+#undef PGL_HMC_ST
+}
+
+// U = -(ll + log prior) and grad U of one row x = [bias, w_stim, w_ir] with the rules of pglm_hmc.h, in place: g (grad ll)
+// -> grad U; returns U in every thread.  Whole block of 256 threads; the log prior is summed in a fixed order.
+__device__ __forceinline__ double pgl_hmc_target_row(const double* __restrict__ x, double* __restrict__ g, const double ll,
+                                                     const BfgsPrior& q, double* red, const int tid)
+{
+    double lp = 0.0;
+    if (tid == 0) {
+        double d;
+        lp += pgl_hmc_prior_bias(x[0], q.mu_b, q.sg_b, &d);
+        g[0] = pgl_hmc_grad_elem(g[0], d);
+    }
+    for (int c = 1 + tid; c < 1 + q.Dstim; c += 256) {
+        double d;
+        lp += pgl_hmc_prior_stim(x[c], q.stim_sigma, &d);
+        g[c] = pgl_hmc_grad_elem(g[c], d);
+    }
+    const int o = 1 + q.Dstim;
+    for (int n = tid; n < q.N; n += 256)                                       // one presynaptic group per thread
+        lp += pgl_hmc_prior_group(q.kind, x + o + n * q.B, q.B, q.mu, q.sigma, q.lam, g + o + n * q.B);
+    const double lpt = pgl_blk_sum(lp, red);
+    return pgl_hmc_energy(ll, lpt);
+}
+
+// start of a chain: q of every row is in the state, (ll, grad) hold ll and its gradient at q, row by row (overwritten
+// with U and grad U)
+__global__ __launch_bounds__(256) void k_hmc_init(const HmcView v, double* __restrict__ ll, double* __restrict__ grad,
+                                                  const BfgsPrior q, const int n_lo, const double step0,
+                                                  const unsigned long long seed)
+{
+    __shared__ double red[12];
+    const int r = blockIdx.x, tid = threadIdx.x, P = v.P;
+    const size_t o = (size_t)r * P;
+    const double U = pgl_hmc_target_row(v.q + o, grad + o, ll[r], q, red, tid);
+    __syncthreads();                                                           // grad U of the row is in memory
+    for (int c = tid; c < P; c += 256) v.g[o + c] = grad[o + c];
+    if (tid == 0) {
+        PglHmc s;
+        pgl_hmc_init(&s, U, step0, n_lo + r, seed);
+        pgl_hmc_store(v, r, &s);
+        ll[r] = U;
+    }
+}
+
+// start of a transition: momentum, H0, the half kick with grad U at q, the first drift; Xt[row] = the point to evaluate
+__global__ __launch_bounds__(256) void k_hmc_begin(const HmcView v, const double* __restrict__ minv, double* __restrict__ Xt)
+{
+    __shared__ double red[12];
+    const int r = blockIdx.x, tid = threadIdx.x, P = v.P;
+    const size_t o = (size_t)r * P;
+    PglHmc s;
+    pgl_hmc_load(v, r, &s);
+    const pgl_hmc_u64 key = pgl_hmc_row_key(&s);
+    double ks = 0.0;
+    for (int c = tid; c < P; c += 256) {
+        const double mi = minv ? minv[o + c] : 1.0;
+        const double q0 = v.q[o + c];
+        double p = pgl_hmc_momentum(pgl_hmc_normal(key, (pgl_hmc_u64)c), mi);
+        ks += pgl_hmc_kinetic_elem(p, mi);
+        p = pgl_hmc_kick(p, 0.5, s.step, v.g[o + c]);
+        const double qn = pgl_hmc_drift(q0, s.step, mi, p);
+        v.q0[o + c] = q0;
+        v.p[o + c] = p;
+        v.q[o + c] = qn;
+        Xt[o + c] = qn;
+    }
+    ks = pgl_blk_sum(ks, red);
+    if (tid == 0) {
+        pgl_hmc_begin(&s, ks);
+        v.sc[(size_t)1 * v.M + r] = s.H0;
+    }
+}
+
+// One leapfrog step of every row after ONE evaluation of all rows at Xt = q: (ll, grad) come in and are turned into U,
+// grad U in place.  last == 0: full kick, next drift, Xt[row] = the next point.  last != 0: half kick, H1, the decision,
+// the step-size rule while t < n_warmup, t += 1, and the row's current point into sample_out[row] (null: none).
+__global__ __launch_bounds__(256) void k_hmc_leap(const HmcView v, const double* __restrict__ minv, double* __restrict__ ll,
+                                                  double* __restrict__ grad, const BfgsPrior q, const int last,
+                                                  const int n_warmup, double* __restrict__ Xt, double* __restrict__ sample_out)
+{
+    __shared__ double red[12];
+    __shared__ int dec;
+    const int r = blockIdx.x, tid = threadIdx.x, P = v.P;
+    const size_t o = (size_t)r * P;
+    const double U1 = pgl_hmc_target_row(v.q + o, grad + o, ll[r], q, red, tid);
+    __syncthreads();                                                           // grad U of the row is in memory
+    const double step = v.sc[(size_t)2 * v.M + r];
+    if (!last) {
+        for (int c = tid; c < P; c += 256) {
+            const double mi = minv ? minv[o + c] : 1.0;
+            const double p = pgl_hmc_kick(v.p[o + c], 1.0, step, grad[o + c]);
+            const double qn = pgl_hmc_drift(v.q[o + c], step, mi, p);
+            v.p[o + c] = p;
+            v.q[o + c] = qn;
+            Xt[o + c] = qn;
+        }
+        if (tid == 0) ll[r] = U1;
+        return;
+    }
+    double ks = 0.0;
+    for (int c = tid; c < P; c += 256) {
+        const double mi = minv ? minv[o + c] : 1.0;
+        const double p = pgl_hmc_kick(v.p[o + c], 0.5, step, grad[o + c]);
+        v.p[o + c] = p;
+        ks += pgl_hmc_kinetic_elem(p, mi);
+    }
+    ks = pgl_blk_sum(ks, red);
+    if (tid == 0) {
+        PglHmc s;
+        pgl_hmc_load(v, r, &s);
+        const double u = pgl_hmc_accept_uniform(pgl_hmc_row_key(&s));
+        dec = pgl_hmc_decide(&s, U1, ks, u, n_warmup);
+        pgl_hmc_store(v, r, &s);
+        ll[r] = U1;
+    }
+    __syncthreads();
+    const bool acc = dec != 0;
+    for (int c = tid; c < P; c += 256) {
+        double qc;
+        if (acc) {
+            qc = v.q[o + c];
+            v.g[o + c] = grad[o + c];
+        } else {
+            qc = v.q0[o + c];
+            v.q[o + c] = qc;
+        }
+        if (sample_out) sample_out[o + c] = qc;
+    }
+}

@@ -8,6 +8,9 @@ The sweep over the neurons runs as the GPU lock-step optimizer by default (infer
 lock-step Newton-CG optimizer on device Hessian-vector products (inference/batched_newton_cg.py; the reference's use_rop).
 --gof prints the time-rescaling KS table of the fitted model (inference/gof.py) after the fit.
 --ppc N prints the predictive spike-count table of N replicates simulated from the fitted model (inference/predictive.py).
+--hmc N draws N posterior samples of every neuron's parameters from the fit by lock-step HMC on the device
+(inference/batched_hmc.py) and prints the bias posterior mean +- sd per neuron, beside the Laplace standard error when
+the model's packing has one.
 """
 import argparse
 import os
@@ -36,7 +39,7 @@ def initialize_test_harness(model_name, data, data_dir=None):
     return popn, popn_true, x_true
 
 
-def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False, gof=False, ppc=0):
+def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False, gof=False, ppc=0, hmc=0):
     """test/synth_map.py:10-32."""
     popn, popn_true, x_true = initialize_test_harness(model_name, data, data_dir)
     x0 = popn.sample(rng)
@@ -55,7 +58,30 @@ def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, r
     if ppc:
         from theano_pyglm_amd.inference import predictive
         print(predictive.format_table(predictive.predictive_counts(popn, x_inf, ppc)))
+    if hmc:
+        print(hmc_bias_table(popn, x_inf, hmc))
     return x_inf, ll_inf, wall
+
+
+def hmc_bias_table(popn, x, n_draws):
+    """n_draws kept HMC draws from x: one line per neuron, bias posterior mean +- sd (and the Laplace standard error)."""
+    from theano_pyglm_amd.inference import batched_hmc
+    from theano_pyglm_amd.inference.laplace import laplace_glms
+    t0 = time.time()
+    res = batched_hmc.sample_glms_hmc(popn, x, n_draws, mass='laplace')
+    wall = time.time() - t0
+    s = batched_hmc.summarize(res['samples'][:, :, 0])
+    try:
+        se = [r['stderr_vec'][0] if r['pd'] else float('nan') for r in laplace_glms(popn, x)]
+    except ValueError:
+        se = None
+    lines = ["HMC: %d draws per neuron in %.2f s (%d ll+grad launches)" % (n_draws, wall, res['n_evals']),
+             "neuron   bias mean +- sd        ESS  accept   step" + ("   Laplace se" if se is not None else "")]
+    for n in range(popn.N):
+        ln = "%6d  %9.4f +- %-8.4f %6.0f  %6.2f  %6.4f" % (n, s['mean'][n], s['sd'][n], s['ess'][n], res['accept_rate'][n],
+                                                          res['step_sz'][n])
+        lines.append(ln + ("   %10.4f" % se[n] if se is not None else ""))
+    return "\n".join(lines)
 
 
 def main():
@@ -72,11 +98,13 @@ def main():
                     help='after the fit: time-rescaling KS test of every neuron (rescaled inter-spike intervals against Exp(1))')
     ap.add_argument('--ppc', type=int, default=0, metavar='N',
                     help='after the fit: predictive spike counts of N replicates simulated from the fitted model on the device')
+    ap.add_argument('--hmc', type=int, default=0, metavar='N',
+                    help='after the fit: N posterior draws per neuron by lock-step HMC on the device; prints the bias mean +- sd')
     args = ap.parse_args()
     with open(args.dataFile, 'rb') as f:
         data = pickle.load(f)
     run_synth_test(args.model, data, args.resultsDir, os.path.dirname(args.dataFile),
-                   False if args.sequential else ('torch' if args.newton_cg else None), use_rop=args.newton_cg, gof=args.gof, ppc=args.ppc)
+                   False if args.sequential else ('torch' if args.newton_cg else None), use_rop=args.newton_cg, gof=args.gof, ppc=args.ppc, hmc=args.hmc)
 
 
 if __name__ == '__main__':
