@@ -355,6 +355,56 @@ int pgl_hmc_leap_dev(pgl_handle h, double* d_state, int M, int P, const double* 
                      int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam, int last,
                      int n_warmup, double* d_Xt, double* d_sample_out);
 
+/* Annealed importance sampling (Neal 2001; inference/batched_ais.py) of the evidence log Z_n of every neuron given the
+ * network, as row kernels on the handle's stream, on top of the HMC moves above (restated nowhere: csrc/pglm_ais.h uses
+ * csrc/pglm_hmc.h).  The run covers R = K M rows: K particles of the M neurons n_lo .. n_lo + M - 1, particle-major -- row
+ * r = k M + i is particle particle0 + k of neuron n_lo + i -- so block k of any (R, P) array is the (M, P) theta block one
+ * pgl_ll_grad_dev(n_lo, n_lo + M) takes and returns.  Over a ladder 0 = beta_0 < ... < beta_J = 1 the target is
+ *     U_beta = -(beta ll + log prior),  grad U_beta = -(beta grad ll + grad log prior),  with the NaN rules above.
+ * Only the Gaussian priors are served (prior_kind 0: bias N(mu_b, sg_b), stimulus weights N(0, stim_sigma), impulse
+ * weights N(mu, sigma), all standard deviations positive): the start is an exact draw from the normalised prior.
+ * prior_kind 1 returns PGL_ERR_UNSUPPORTED.  Per row:
+ *     1. q_j = m_j + s_j z_j;  evaluate;  log w = 0.
+ *     2. for j = 1 .. J:  log w += (beta_j - beta_{j-1}) ll0, ll0 = ll at the current point -- the point that was sampled
+ *        under beta_{j-1} (a non-finite ll0 makes log w = -inf for good);  then the target becomes U_{beta_j}.
+ *     3. for j < J: transitions as above (n_leapfrog steps each) that leave prior x L^beta_j invariant.
+ * Random numbers: the formulas above with a seed per particle,
+ *     s_k  = mix(seed + G * (particle + 1))                            particle = particle0 + k;  -1 is allowed (a pilot)
+ *     key  = mix(mix(mix(s_k + G) + G * (n + 1)) + G * (t + 1))          n: NEURON index, t: transition number
+ *     t = 0: the prior draw, z_j of that key;  the moves are numbered t = 1, 2, ... across the whole ladder.
+ * So a run over neurons [a, b) equals the matching rows of a run over [0, N), particles [k0, k0 + K) equal the matching
+ * particles of a larger run, and two runs give the same bits.
+ * Step sizes: one per row.  adapt != 0: the rule above after EVERY transition (weights of such a run are not valid; it is
+ * how a pilot finds steps).  adapt == 0: a decision never changes the step; temper sets it from d_step_row.
+ * d_minv (M, P), NULL = identity: the diagonal inverse mass, shared by the particles of a neuron.
+ * All state of R rows lives in ONE device block of pgl_ais_state_doubles(R, P) doubles, in this order:
+ *   (R,P) each: q (the current point), p, q0 (start of the running transition), g (grad U_beta at the current point), gll
+ *               (grad ll at the current point), gu (grad U_beta along the running trajectory);
+ *   (R) each:   U0 (U_beta at the current point), H0, step, avg_accept, n_accept (accepted transitions with adapt == 0), t
+ *               (the next transition's number, from 1), acc (the last decision), neuron, seed_lo, seed_hi (halves of s_k),
+ *               ll0, lp0 (log likelihood and log prior -- constants dropped -- at the current point), beta, logw, particle.
+ *   init:   the prior draws into q and into d_Xt (R, P), the points to evaluate; log w = 0, beta = 0, every step = step0.
+ *   start:  (d_ll (R), d_grad (R, P)) = the evaluation at the draws (left as they are): ll0, lp0, gll.
+ *   temper: the weight increment for the change to beta, U0 and g of the new target from ll0, lp0, gll (no evaluation),
+ *           and, unless d_step_row is NULL, step of row r = d_step_row[r mod M] (M entries, one per neuron).
+ *   begin:  as pgl_hmc_begin_dev.
+ *   leap:   (d_ll, d_grad) = the evaluation at d_Xt (left as they are).  last == 0: full kick, next drift into d_Xt.
+ *           last != 0: half kick, H1, accept (ll, log prior, grad ll and grad U of the new point are kept) or reject,
+ *           t += 1; d_acc_out[r] += the decision and d_step_out[r] = the row's step after it (R entries each; NULL: none).
+ * One leapfrog step is K pgl_ll_grad_dev calls (one per particle block) and one row launch; nothing is read back. */
+long long pgl_ais_state_doubles(int R, int P);
+int pgl_ais_init_dev(pgl_handle h, double* d_state, int K, int M, int P, int n_lo, int particle0, int prior_kind, double mu_b,
+                     double sg_b, double stim_sigma, double mu, double sigma, double lam, double step0, uint64_t seed,
+                     double* d_Xt);
+int pgl_ais_start_dev(pgl_handle h, double* d_state, int K, int M, int P, const double* d_ll, const double* d_grad,
+                      int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam);
+int pgl_ais_temper_dev(pgl_handle h, double* d_state, int K, int M, int P, int prior_kind, double mu_b, double sg_b,
+                       double stim_sigma, double mu, double sigma, double lam, double beta, const double* d_step_row);
+int pgl_ais_begin_dev(pgl_handle h, double* d_state, int K, int M, int P, const double* d_minv, double* d_Xt);
+int pgl_ais_leap_dev(pgl_handle h, double* d_state, int K, int M, int P, const double* d_minv, const double* d_ll,
+                     const double* d_grad, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma,
+                     double lam, int last, int adapt, double* d_Xt, double* d_acc_out, double* d_step_out);
+
 /* convolve_with_basis(S, ibasis) (basis.py:201-236 via impulse.py:114-130):
  * fS_out (nT,N,B) row-major, float64. */
 int pgl_features(pgl_handle h, double* fS_out);

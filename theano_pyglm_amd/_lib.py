@@ -39,6 +39,8 @@ SYMBOLS = [
     'pgl_hvp_prepare_dev', 'pgl_hvp_prepare_list_dev', 'pgl_hvp_apply_dev', 'pgl_hvp',
     'pgl_ncg_state_doubles', 'pgl_ncg_init_dev', 'pgl_ncg_cg_step_dev', 'pgl_ncg_trial_dev', 'pgl_ncg_search_step_dev',
     'pgl_hmc_state_doubles', 'pgl_hmc_init_dev', 'pgl_hmc_begin_dev', 'pgl_hmc_leap_dev',
+    'pgl_ais_state_doubles', 'pgl_ais_init_dev', 'pgl_ais_start_dev', 'pgl_ais_temper_dev', 'pgl_ais_begin_dev',
+    'pgl_ais_leap_dev',
     'pgl_hess_dev', 'pgl_hess',
     'pgl_rescale_count', 'pgl_rescale_dev', 'pgl_rescale',
     'pgl_simulate_streams', 'pgl_simulate_batch', 'pgl_simulate_batch_dev', 'pgl_simulate_batch_plan',
@@ -167,6 +169,14 @@ def load():
         lib.pgl_hmc_begin_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
         lib.pgl_hmc_leap_dev.argtypes = ([vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int] + [C.c_double] * 6 +
                                          [C.c_int, C.c_int, vp, vp])
+    if hasattr(lib, 'pgl_ais_init_dev'):                      # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
+        lib.pgl_ais_state_doubles.argtypes = [C.c_int, C.c_int]
+        kmp = [vp, vp, C.c_int, C.c_int, C.c_int]
+        lib.pgl_ais_init_dev.argtypes = kmp + [C.c_int, C.c_int, C.c_int] + [C.c_double] * 6 + [C.c_double, C.c_uint64, vp]
+        lib.pgl_ais_start_dev.argtypes = kmp + [vp, vp, C.c_int] + [C.c_double] * 6
+        lib.pgl_ais_temper_dev.argtypes = kmp + [C.c_int] + [C.c_double] * 6 + [C.c_double, vp]
+        lib.pgl_ais_begin_dev.argtypes = kmp + [vp, vp]
+        lib.pgl_ais_leap_dev.argtypes = kmp + [vp, vp, vp, C.c_int] + [C.c_double] * 6 + [C.c_int, C.c_int, vp, vp, vp]
     lib.pgl_features.argtypes = [vp, vp]
     lib.pgl_impulse_currents.argtypes = [vp, vp, vp]
     lib.pgl_state.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
@@ -199,7 +209,7 @@ def load():
         if 'PYGLM_HIP_LIB' in os.environ and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
-        if name in ('pgl_bfgs_state_doubles', 'pgl_ncg_state_doubles', 'pgl_hmc_state_doubles'):
+        if name in ('pgl_bfgs_state_doubles', 'pgl_ncg_state_doubles', 'pgl_hmc_state_doubles', 'pgl_ais_state_doubles'):
             fn.restype = C.c_longlong
         elif name not in ('pgl_last_error',):
             fn.restype = C.c_int
@@ -614,6 +624,35 @@ class DeviceGlm(object):
                                        C.c_void_p(d_ll), C.c_void_p(d_grad), int(prior[0]), *[float(z) for z in prior[1:]],
                                        1 if last else 0, int(n_warmup), C.c_void_p(d_Xt),
                                        C.c_void_p(d_sample_out) if d_sample_out else None))
+
+    # -- annealed importance sampling row kernels (pgl_ais_*; inference/batched_ais.py).  K particles x M neurons, rows
+    # particle-major; prior: bfgs_objective_dev's tuple (Gaussian only); device pointers
+    def ais_state_doubles(self, R, P):
+        return int(self.lib.pgl_ais_state_doubles(int(R), int(P)))
+
+    def ais_init_dev(self, d_state, K, M, P, n_lo, particle0, prior, step0, seed, d_Xt):
+        _chk(self.lib.pgl_ais_init_dev(self.h, C.c_void_p(d_state), int(K), int(M), int(P), int(n_lo), int(particle0),
+                                       int(prior[0]), *[float(z) for z in prior[1:]], float(step0),
+                                       int(seed) & 0xffffffffffffffff, C.c_void_p(d_Xt)))
+
+    def ais_start_dev(self, d_state, K, M, P, d_ll, d_grad, prior):
+        _chk(self.lib.pgl_ais_start_dev(self.h, C.c_void_p(d_state), int(K), int(M), int(P), C.c_void_p(d_ll),
+                                        C.c_void_p(d_grad), int(prior[0]), *[float(z) for z in prior[1:]]))
+
+    def ais_temper_dev(self, d_state, K, M, P, prior, beta, d_step_row=0):
+        _chk(self.lib.pgl_ais_temper_dev(self.h, C.c_void_p(d_state), int(K), int(M), int(P), int(prior[0]),
+                                         *[float(z) for z in prior[1:]], float(beta),
+                                         C.c_void_p(d_step_row) if d_step_row else None))
+
+    def ais_begin_dev(self, d_state, K, M, P, d_minv, d_Xt):
+        _chk(self.lib.pgl_ais_begin_dev(self.h, C.c_void_p(d_state), int(K), int(M), int(P),
+                                        C.c_void_p(d_minv) if d_minv else None, C.c_void_p(d_Xt)))
+
+    def ais_leap_dev(self, d_state, K, M, P, d_minv, d_ll, d_grad, prior, last, adapt, d_Xt, d_acc_out=0, d_step_out=0):
+        vp = lambda a: C.c_void_p(a) if a else None
+        _chk(self.lib.pgl_ais_leap_dev(self.h, C.c_void_p(d_state), int(K), int(M), int(P), vp(d_minv), C.c_void_p(d_ll),
+                                       C.c_void_p(d_grad), int(prior[0]), *[float(z) for z in prior[1:]], 1 if last else 0,
+                                       1 if adapt else 0, C.c_void_p(d_Xt), vp(d_acc_out), vp(d_step_out)))
 
     def sync(self):
         _chk(self.lib.pgl_sync(self.h))

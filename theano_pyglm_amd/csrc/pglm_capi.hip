@@ -2058,6 +2058,89 @@ int pgl_hmc_leap_dev(pgl_handle h, double* d_state, int M, int P, const double* 
     return PGL_OK;
 }
 
+// ---- annealed importance sampling row kernels (inference/batched_ais.py) -----------------------------------------------
+long long pgl_ais_state_doubles(int R, int P) { return (long long)pgl_ais_doubles((size_t)(R > 0 ? R : 0), (size_t)(P > 0 ? P : 0)); }
+
+static int ais_prior(pgl_handle h, int K, int M, int P, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu,
+                     double sigma, double lam, BfgsPrior& q)
+{
+    if (K <= 0 || M <= 0 || P <= 0 || (long long)K * M > 0x7fffffffLL) return fail(PGL_ERR_ARG, "bad argument");
+    if (prior_kind == 1)
+        return fail(PGL_ERR_UNSUPPORTED, "annealed importance sampling starts from an exact prior draw: Gaussian priors only");
+    int rc = ncg_prior(h, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
+    if (rc) return rc;
+    if (!(sg_b > 0.0) || !(sigma > 0.0) || (h->Dstim > 0 && !(stim_sigma > 0.0)))
+        return fail(PGL_ERR_ARG, "the prior standard deviations must be positive");
+    return PGL_OK;
+}
+
+int pgl_ais_init_dev(pgl_handle h, double* d_state, int K, int M, int P, int n_lo, int particle0, int prior_kind, double mu_b,
+                     double sg_b, double stim_sigma, double mu, double sigma, double lam, double step0, uint64_t seed,
+                     double* d_Xt)
+{
+    if (!h || !d_state || !d_Xt || n_lo < 0 || M <= 0 || n_lo + M > h->N || particle0 < -1 || !(step0 > 0.0))
+        return fail(PGL_ERR_ARG, "bad argument");
+    BfgsPrior q;
+    int rc = ais_prior(h, K, M, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_ais_init, dim3(K * M), dim3(256), 0, h->stream, pgl_ais_view(d_state, K, M, P), d_Xt, q, n_lo,
+                       particle0, step0, (unsigned long long)seed);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+int pgl_ais_start_dev(pgl_handle h, double* d_state, int K, int M, int P, const double* d_ll, const double* d_grad,
+                      int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam)
+{
+    if (!h || !d_state || !d_ll || !d_grad) return fail(PGL_ERR_ARG, "bad argument");
+    BfgsPrior q;
+    int rc = ais_prior(h, K, M, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_ais_start, dim3(K * M), dim3(256), 0, h->stream, pgl_ais_view(d_state, K, M, P), d_ll, d_grad, q);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+int pgl_ais_temper_dev(pgl_handle h, double* d_state, int K, int M, int P, int prior_kind, double mu_b, double sg_b,
+                       double stim_sigma, double mu, double sigma, double lam, double beta, const double* d_step_row)
+{
+    if (!h || !d_state || !(beta >= 0.0 && beta <= 1.0)) return fail(PGL_ERR_ARG, "bad argument");
+    BfgsPrior q;
+    int rc = ais_prior(h, K, M, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_ais_temper, dim3(K * M), dim3(256), 0, h->stream, pgl_ais_view(d_state, K, M, P), q, beta, d_step_row);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+int pgl_ais_begin_dev(pgl_handle h, double* d_state, int K, int M, int P, const double* d_minv, double* d_Xt)
+{
+    if (!h || !d_state || !d_Xt || K <= 0 || M <= 0 || P <= 0 || (long long)K * M > 0x7fffffffLL)
+        return fail(PGL_ERR_ARG, "bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_ais_begin, dim3(K * M), dim3(256), 0, h->stream, pgl_ais_view(d_state, K, M, P), d_minv, d_Xt);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+int pgl_ais_leap_dev(pgl_handle h, double* d_state, int K, int M, int P, const double* d_minv, const double* d_ll,
+                     const double* d_grad, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma,
+                     double lam, int last, int adapt, double* d_Xt, double* d_acc_out, double* d_step_out)
+{
+    if (!h || !d_state || !d_ll || !d_grad || !d_Xt) return fail(PGL_ERR_ARG, "bad argument");
+    BfgsPrior q;
+    int rc = ais_prior(h, K, M, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_ais_leap, dim3(K * M), dim3(256), 0, h->stream, pgl_ais_view(d_state, K, M, P), d_minv, d_ll, d_grad, q,
+                       last ? 1 : 0, adapt ? 1 : 0, d_Xt, d_acc_out, d_step_out);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
 int pgl_sync(pgl_handle h)
 {
     if (!h) return fail(PGL_ERR_ARG, "null handle");

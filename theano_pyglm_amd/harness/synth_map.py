@@ -11,6 +11,9 @@ lock-step Newton-CG optimizer on device Hessian-vector products (inference/batch
 --hmc N draws N posterior samples of every neuron's parameters from the fit by lock-step HMC on the device
 (inference/batched_hmc.py) and prints the bias posterior mean +- sd per neuron, beside the Laplace standard error when
 the model's packing has one.
+--ais K estimates every neuron's log evidence given the network from the fit by annealed importance sampling with K
+particles on the device (inference/batched_ais.py; Gaussian impulse priors only) and prints log_Z + log_prior_norm +- se, the
+ESS and the Laplace log evidence beside it.
 """
 import argparse
 import os
@@ -39,7 +42,7 @@ def initialize_test_harness(model_name, data, data_dir=None):
     return popn, popn_true, x_true
 
 
-def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False, gof=False, ppc=0, hmc=0):
+def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False, gof=False, ppc=0, hmc=0, ais=0):
     """test/synth_map.py:10-32."""
     popn, popn_true, x_true = initialize_test_harness(model_name, data, data_dir)
     x0 = popn.sample(rng)
@@ -60,6 +63,8 @@ def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, r
         print(predictive.format_table(predictive.predictive_counts(popn, x_inf, ppc)))
     if hmc:
         print(hmc_bias_table(popn, x_inf, hmc))
+    if ais:
+        print(ais_evidence_table(popn, x_inf, ais))
     return x_inf, ll_inf, wall
 
 
@@ -84,6 +89,24 @@ def hmc_bias_table(popn, x, n_draws):
     return "\n".join(lines)
 
 
+def ais_evidence_table(popn, x, n_particles):
+    """AIS with n_particles particles per neuron from x: one line per neuron, log_Z + log_prior_norm +- se, the ESS and the
+    Laplace log evidence (both under the host priors, which drop their normalising constants)."""
+    from theano_pyglm_amd.inference import batched_ais
+    from theano_pyglm_amd.inference.laplace import laplace_glms
+    t0 = time.time()
+    res = batched_ais.ais_glms(popn, x, n_particles=n_particles, mass='laplace')
+    wall = time.time() - t0
+    lap = [r['log_evidence'] for r in laplace_glms(popn, x)]
+    lines = ["AIS: %d particles per neuron, %d temperatures in %.2f s (%d ll+grad launches)"
+             % (n_particles, len(res['betas']), wall, res['n_evals']),
+             "neuron   log evidence +- se           ESS      Laplace"]
+    for n in range(popn.N):
+        lines.append("%6d  %13.4f +- %-9.4f %6.1f  %11.4f" % (n, res['log_Z'][n] + res['log_prior_norm'][n], res['log_Z_se'][n],
+                                                             res['ess'][n], lap[n]))
+    return "\n".join(lines)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('-m', '--model', default='standard_glm')
@@ -100,11 +123,14 @@ def main():
                     help='after the fit: predictive spike counts of N replicates simulated from the fitted model on the device')
     ap.add_argument('--hmc', type=int, default=0, metavar='N',
                     help='after the fit: N posterior draws per neuron by lock-step HMC on the device; prints the bias mean +- sd')
+    ap.add_argument('--ais', type=int, default=0, metavar='K',
+                    help='after the fit: log evidence of every neuron given the network by annealed importance sampling with '
+                         'K particles on the device, beside the Laplace log evidence (Gaussian impulse priors only)')
     args = ap.parse_args()
     with open(args.dataFile, 'rb') as f:
         data = pickle.load(f)
     run_synth_test(args.model, data, args.resultsDir, os.path.dirname(args.dataFile),
-                   False if args.sequential else ('torch' if args.newton_cg else None), use_rop=args.newton_cg, gof=args.gof, ppc=args.ppc, hmc=args.hmc)
+                   False if args.sequential else ('torch' if args.newton_cg else None), use_rop=args.newton_cg, gof=args.gof, ppc=args.ppc, hmc=args.hmc, ais=args.ais)
 
 
 if __name__ == '__main__':
