@@ -15,12 +15,13 @@ pytestmark = pytest.mark.gpu
 DT = SH.DT
 #         case, n_rep, flags (bit 0: the ring in global memory)
 RUNS = [(name, n_rep, flags) for name in ('small_exp', 'small_expl') for n_rep in (1, 5) for flags in (0, 1)] + \
-       [('n70', 2, 0), ('n130', 2, 0), ('high_rate', 2, 0), ('high_rate', 2, 1), ('tail', 1, 0), ('tail', 1, 1)]
+       [('n70', 2, 0), ('n130', 2, 0), ('high_rate', 2, 0), ('high_rate', 2, 1), ('tail', 1, 0), ('tail', 1, 1)] + \
+       [(name, SH.CASES[name][5], flags) for name in sorted(SH.PLAN) for flags in sorted(SH.PLAN[name])]
 
 
 def _run(name, n_rep, flags=0, rep0=0, **kw):
     X0, AW, nlin, seed = SH.case(name)
-    return _lib.simulate_batch(X0, AW, nlin, DT, n_rep, seed=seed, rep0=rep0, flags=flags, currents=True, **kw)
+    return _lib.simulate_batch(X0, AW, nlin, SH.case_dt(name), n_rep, seed=seed, rep0=rep0, flags=flags, currents=True, **kw)
 
 
 def _check(out, name, i, rep):
@@ -38,6 +39,8 @@ def test_device_equals_host_reference(name, n_rep, flags):
     N, R = SH.CASES[name][:2]
     in_lds, _ = _lib.simulate_batch_plan(N, R, flags)
     assert in_lds == (flags == 0 and name != 'n130')
+    if name in SH.PLAN:
+        assert in_lds == SH.PLAN[name][flags][0]
     out = _run(name, n_rep, flags)
     for i in range(n_rep):
         _check(out, name, i, i)

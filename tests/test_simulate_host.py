@@ -84,16 +84,60 @@ CASES = {'small_exp':   (3,   7,   400, 'exp',        11,  5),
          'n70':         (70,  33,  2000, 'explinear', 13,  2),     # more neurons than a wave, no multiple of anything; LDS
          'n130':        (130, 200, 1500, 'explinear', 14,  2),     # global ring by size
          'high_rate':   (3,   7,   400, 'exp',        15,  2),     # multi-spike rounds and cap exceptions
-         'tail':        (3,   7,   400, 'explinear',  16,  1)}     # a spike inside the last R bins
+         'tail':        (3,   7,   400, 'explinear',  16,  1),     # a spike inside the last R bins
+         # the sweep: full waves inside one series of pgl_lambda_only (REGIME), launch shapes (PLAN), edges of the time loop
+         'n64_tail':    (64,  16,  300, 'explinear',  21,  1),
+         'n64_mid':     (64,  16,  300, 'explinear',  22,  1),
+         'n64_neg_mid': (64,  16,  300, 'explinear',  23,  1),
+         'n128_mixed_waves': (128, 16, 300, 'explinear', 24, 1),
+         'n65':         (65,  9,   300, 'explinear',  25,  1),     # one neuron in a second wave
+         'n1':          (1,   5,   400, 'explinear',  26,  2),
+         'lds_96k':     (96,  128, 300, 'explinear',  27,  1),     # 98304 B of LDS: above the 64 KiB a kernel gets unasked
+         'lds_1024thr': (96,  200, 300, 'explinear',  28,  1),     # 153600 B of LDS, R N > 16384: 1024 threads
+         'n300':        (300, 8,   200, 'explinear',  29,  1),     # N > 256: 1024 threads, five waves with neurons
+         'n1024':       (1024, 2,  60,  'explinear',  30,  1),     # every thread owns a neuron, all 16 ballot masks
+         'nt_lt_r':     (3,   7,   5,   'explinear',  31,  2),     # the recording is shorter than the ring
+         'nt1':         (3,   7,   1,   'explinear',  32,  2),
+         'r1':          (5,   1,   300, 'explinear',  33,  2)}
 SMALL = ('small_exp', 'small_expl', 'high_rate', 'tail')
+# currents of the regime cases: X0 uniform in [lo, hi] per wave of 64 neurons, coupling |AW| <= w, bin width dt.  The vote of
+# pgl_lambda_only: e^-|x| < e^-9.25 in every lane -> the tail series, < 0.1 (|x| > 2.3) -> the atanh series, else general;
+# a wave without a neuron-less lane (N a multiple of 64) takes a series only if the total currents X of all its neurons agree.
+#                 name: ([(lo, hi) per wave], w, dt, (min X, max X) asserted per wave: 0.5 clear of the vote thresholds)
+REGIME = {'n64_tail':    ([(11.0, 30.0)], 0.02, 0.001, [(9.75, 600.0)]),
+          'n64_mid':     ([(3.4, 8.1)], 0.01, 0.005, [(2.8, 8.75)]),
+          'n64_neg_mid': ([(-8.1, -3.4)], 0.01, 2.0, [(-8.75, -2.8)]),
+          'n128_mixed_waves': ([(11.0, 30.0), (3.4, 8.1)], 0.01, 0.002, [(9.75, 600.0), (2.8, 8.75)])}
+# the launch forms: name -> {flags: (ring in LDS, threads)}; threads = 256 if N <= 256 and R N <= 16384 else 1024
+# (pgl_simulate_batch_dev), the ring in LDS up to PGL_SIM_LDS_MAX bytes unless flag bit 0 is set
+LDS_MAX = 160 * 1024 - 1024
+PLAN = {'n64_tail': {0: (True, 256), 1: (False, 256)}, 'n64_mid': {0: (True, 256)}, 'n64_neg_mid': {0: (True, 256)},
+        'n128_mixed_waves': {0: (True, 256)}, 'n65': {0: (True, 256)}, 'n1': {0: (True, 256), 1: (False, 256)},
+        'lds_96k': {0: (True, 256), 1: (False, 256)}, 'lds_1024thr': {0: (True, 1024), 1: (False, 1024)},
+        'n300': {0: (True, 1024), 1: (False, 1024)}, 'n1024': {0: (True, 1024), 1: (False, 1024)},
+        'nt_lt_r': {0: (True, 256), 1: (False, 256)}, 'nt1': {0: (True, 256), 1: (False, 256)},
+        'r1': {0: (True, 256), 1: (False, 256)}}
+
+
+def case_dt(name):
+    return REGIME[name][2] if name in REGIME else DT
 
 
 @functools.lru_cache(maxsize=None)
 def case(name):
     """(X0 (nT, N), AW (N, R, N), nlin, seed) of a case; about 40 Hz per neuron at dt = 1 ms, signed coupling that decays
-    over the R taps."""
+    over the R taps.  The REGIME cases: currents inside one series per wave, weak coupling."""
     N, R, nT, nlin, seed, _ = CASES[name]
     rng = np.random.RandomState(1000 + seed)
+    if name in REGIME:
+        waves, w, _, _ = REGIME[name]
+        lo = np.repeat([a for a, _ in waves], 64)[None, :]
+        hi = np.repeat([b for _, b in waves], 64)[None, :]
+        X0 = lo + (hi - lo) * rng.rand(nT, N)
+        AW = w * (2.0 * rng.rand(N, R, N) - 1.0) * np.exp(-np.arange(R) / (0.3 * R))[None, :, None]
+        X0.setflags(write=False)
+        AW.setflags(write=False)
+        return X0, AW, nlin, seed
     rate = 40.0
     base = np.log(rate) if nlin == 'exp' else rate
     X0 = base + (0.3 if nlin == 'exp' else 10.0) * rng.randn(nT, N)
@@ -106,6 +150,8 @@ def case(name):
         AW *= 0.1
     if name == 'tail':
         X0[-3:] = 3000.0                                     # rate * dt = 3 in the last three bins (R = 7)
+    if name in ('nt_lt_r', 'nt1'):
+        X0 += 1500.0                                         # rate * dt = 1.5: spikes in every bin
     X0.setflags(write=False)
     AW.setflags(write=False)
     return X0, AW, nlin, seed
@@ -115,7 +161,7 @@ def case(name):
 def host_reference(name, rep):
     """(S, X, exceptions, closest_call) of pgl_simulate_streams; computed once, shared, read-only."""
     X0, AW, nlin, seed = case(name)
-    S, X, exc, closest = _lib.simulate_streams(X0, AW, nlin, DT, rep=rep, seed=seed)
+    S, X, exc, closest = _lib.simulate_streams(X0, AW, nlin, case_dt(name), rep=rep, seed=seed)
     S.setflags(write=False)
     X.setflags(write=False)
     return S, X, exc, closest
@@ -146,6 +192,58 @@ def test_cases_reach_what_they_are_for():
     assert not np.array_equal(host_reference('small_expl', 0)[0], host_reference('small_expl', 1)[0])
     X0, AW, nlin, seed = case('small_expl')
     assert not np.array_equal(_lib.simulate_streams(X0, AW, nlin, DT, rep=0, seed=seed + 1)[0], host_reference('small_expl', 0)[0])
+
+
+
+def test_regime_cases_stay_inside_their_series_and_spike():
+    """Every total current X of the host reference (X0 plus what the spikes added) lies inside the case's regime, per wave of
+    64 neurons, at least 0.5 from the vote thresholds 9.25 and 2.3 of pgl_lambda_only -- and the case spikes."""
+    for name, (waves, w, dt, want) in REGIME.items():
+        N = CASES[name][0]
+        assert N == 64 * len(waves)                                    # no lane without a neuron: the vote is the neurons'
+        for rep in range(CASES[name][5]):
+            S, X, exc, _ = host_reference(name, rep)
+            for i, (lo, hi) in enumerate(want):
+                Xw = X[:, 64 * i:64 * i + 64]
+                print(name, 'wave', i, 'X in [%.3f, %.3f]' % (Xw.min(), Xw.max()), 'spikes', int(S[:, 64 * i:64 * i + 64].sum()))
+                assert lo <= Xw.min() and Xw.max() <= hi, (name, i, Xw.min(), Xw.max())
+                assert S[:, 64 * i:64 * i + 64].sum() >= 30, name
+            assert np.any(X != case(name)[0])                          # the spikes did add to the currents
+    assert REGIME['n64_neg_mid'][3][0][1] < 0 < REGIME['n64_mid'][3][0][0]
+
+
+def test_edge_cases_reach_what_they_are_for():
+    S, X, _, _ = host_reference('nt_lt_r', 0)
+    N, R, nT = CASES['nt_lt_r'][:3]
+    assert nT < R and np.all(S[:4].sum(axis=1) > 0)                    # spikes in bins 0 .. 3: impulses cut by the end
+    assert np.any(X[1:] != case('nt_lt_r')[0][1:])
+    S, X, _, _ = host_reference('nt1', 0)
+    assert S.shape == (1, 3) and S.sum() > 0 and np.array_equal(X, case('nt1')[0])
+    for name in ('r1', 'n1', 'n65', 'n300', 'n1024', 'lds_96k', 'lds_1024thr'):
+        S, X, exc, _ = host_reference(name, 0)
+        assert S.sum() > 10 and np.any(X != case(name)[0]), name
+    assert host_reference('n65', 0)[0][:, 64].sum() > 0                # the neuron of the second wave spikes
+    assert host_reference('n1024', 0)[0].any(axis=0).reshape(16, 64).any(axis=1).all()     # a spike in each of the 16 waves
+    assert host_reference('n300', 0)[0][:, 256:].sum() > 0
+
+
+def test_plan_of_the_sweep_cases():
+    """Ring placement from pgl_simulate_batch_plan; the thread count by the documented rule of pgl_simulate_batch_dev (the
+    plan call does not return it)."""
+    for name, forms in PLAN.items():
+        N, R = CASES[name][:2]
+        ring = R * N * 8
+        for flags, (in_lds, threads) in forms.items():
+            assert _lib.simulate_batch_plan(N, R, flags) == (in_lds, 0 if in_lds else ring), (name, flags)
+            assert in_lds == (flags == 0 and ring <= LDS_MAX), (name, flags)
+            assert threads == (256 if N <= 256 and R * N <= 16384 else 1024), (name, flags)
+    N, R = CASES['lds_96k'][:2]
+    assert R * N * 8 == 98304 > 65536 and R * N <= 16384               # 256 threads, LDS beyond the default limit
+    N, R = CASES['lds_1024thr'][:2]
+    assert R * N * 8 == 153600 <= LDS_MAX and 16384 < R * N <= LDS_MAX // 8 == 20352
+    assert CASES['n300'][0] > 256 and CASES['n1024'][0] == 1024 and CASES['n65'][0] == 65 and CASES['n1'][0] == 1
+    assert CASES['r1'][1] == 1 and CASES['nt1'][2] == 1
+    assert set(PLAN) == set(CASES) - {'small_exp', 'small_expl', 'n70', 'n130', 'high_rate', 'tail'}
 
 
 def test_a_neurons_thresholds_do_not_depend_on_the_other_neurons():
