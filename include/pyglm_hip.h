@@ -355,6 +355,34 @@ int pgl_hmc_leap_dev(pgl_handle h, double* d_state, int M, int P, const double* 
                      int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam, int last,
                      int n_warmup, double* d_Xt, double* d_sample_out);
 
+/* Lock-step HMC with a DENSE mass matrix (inference/batched_hmc.py: mass = (M, P, P) or 'laplace_dense'; restated in
+ * csrc/pglm_hmc_dense.h).  The inverse mass matrix of row m is Sigma_m = W_m W_m^T, d_W (M, P, P) row-major with W_m lower
+ * triangular; only the entries j <= i are ever read (the strict upper triangle may hold anything).  The chain above runs
+ * in the whitened momentum r = W^T p, which is standard normal: the state block is pgl_hmc_state_doubles(M, P) with r in
+ * the place of p, pgl_hmc_init_dev starts it, and the random numbers, the target, the decision and the step-size rule are
+ * those above:
+ *     transition t:  r_j = z_j (the SAME draws as the diagonal chain);  H0 = U + 1/2 sum_j r_j^2;  r -= step/2 W^T grad U;
+ *         n_leapfrog times { q += step W r;  r -= step W^T grad U(q) (step/2 the last time) };  H1 = U(q) + 1/2 sum_j r_j^2.
+ * That is the algorithm above with M^-1 = Sigma; with W = diag(sqrt(minv)) it is the diagonal chain in exact arithmetic.
+ *   pgl_tri_matvec_dev:  d_y (M, P) = W_m d_x[m] (trans == 0) or W_m^T d_x[m] (trans != 0), every row m; d_y != d_x.  All
+ *           arithmetic in f64, no atomics; every output is summed in an order that depends on P alone, so a row of an
+ *           M-row call equals the one-row call bit for bit and two calls give the same bits.  One launch on a grid of
+ *           (tiles of 64 outputs, rows).
+ *   begin:  the momentum draw and H0, then the half kick and the first drift as epilogues of the two products: three
+ *           launches.  d_Xt (M, P) = the points to evaluate next.
+ *   leap:   (d_ll, d_grad) = the evaluation at d_Xt (overwritten with U, grad U).  last == 0: the kick and the next drift,
+ *           again inside the products: three launches.  last != 0: the half kick, then H1, accept or reject, the step-size
+ *           rule while t < n_warmup, t += 1 and d_sample_out as pgl_hmc_leap_dev: three launches.
+ *   d_work: pgl_hmc_dense_work_doubles(M, P) doubles of scratch for the calls.  Because no product is ever stored, that
+ *           is 0 and d_work may be NULL; the argument keeps the calls open to an unfused implementation.
+ * One transition is n_leapfrog evaluations and 3 (n_leapfrog + 1) small launches; nothing has to be read back in between. */
+long long pgl_hmc_dense_work_doubles(int M, int P);
+int pgl_tri_matvec_dev(pgl_handle h, const double* d_W, int M, int P, int trans, const double* d_x, double* d_y);
+int pgl_hmc_dense_begin_dev(pgl_handle h, double* d_state, int M, int P, const double* d_W, double* d_work, double* d_Xt);
+int pgl_hmc_dense_leap_dev(pgl_handle h, double* d_state, int M, int P, const double* d_W, double* d_work, double* d_ll,
+                           double* d_grad, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu,
+                           double sigma, double lam, int last, int n_warmup, double* d_Xt, double* d_sample_out);
+
 /* Annealed importance sampling (Neal 2001; inference/batched_ais.py) of the evidence log Z_n of every neuron given the
  * network, as row kernels on the handle's stream, on top of the HMC moves above (restated nowhere: csrc/pglm_ais.h uses
  * csrc/pglm_hmc.h).  The run covers R = K M rows: K particles of the M neurons n_lo .. n_lo + M - 1, particle-major -- row

@@ -39,6 +39,7 @@ SYMBOLS = [
     'pgl_hvp_prepare_dev', 'pgl_hvp_prepare_list_dev', 'pgl_hvp_apply_dev', 'pgl_hvp',
     'pgl_ncg_state_doubles', 'pgl_ncg_init_dev', 'pgl_ncg_cg_step_dev', 'pgl_ncg_trial_dev', 'pgl_ncg_search_step_dev',
     'pgl_hmc_state_doubles', 'pgl_hmc_init_dev', 'pgl_hmc_begin_dev', 'pgl_hmc_leap_dev',
+    'pgl_hmc_dense_work_doubles', 'pgl_tri_matvec_dev', 'pgl_hmc_dense_begin_dev', 'pgl_hmc_dense_leap_dev',
     'pgl_ais_state_doubles', 'pgl_ais_init_dev', 'pgl_ais_start_dev', 'pgl_ais_temper_dev', 'pgl_ais_begin_dev',
     'pgl_ais_leap_dev',
     'pgl_hess_dev', 'pgl_hess',
@@ -169,6 +170,12 @@ def load():
         lib.pgl_hmc_begin_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
         lib.pgl_hmc_leap_dev.argtypes = ([vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int] + [C.c_double] * 6 +
                                          [C.c_int, C.c_int, vp, vp])
+    if hasattr(lib, 'pgl_hmc_dense_leap_dev'):                # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
+        lib.pgl_hmc_dense_work_doubles.argtypes = [C.c_int, C.c_int]
+        lib.pgl_tri_matvec_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+        lib.pgl_hmc_dense_begin_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
+        lib.pgl_hmc_dense_leap_dev.argtypes = ([vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int] + [C.c_double] * 6 +
+                                               [C.c_int, C.c_int, vp, vp])
     if hasattr(lib, 'pgl_ais_init_dev'):                      # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
         lib.pgl_ais_state_doubles.argtypes = [C.c_int, C.c_int]
         kmp = [vp, vp, C.c_int, C.c_int, C.c_int]
@@ -209,7 +216,8 @@ def load():
         if 'PYGLM_HIP_LIB' in os.environ and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
-        if name in ('pgl_bfgs_state_doubles', 'pgl_ncg_state_doubles', 'pgl_hmc_state_doubles', 'pgl_ais_state_doubles'):
+        if name in ('pgl_bfgs_state_doubles', 'pgl_ncg_state_doubles', 'pgl_hmc_state_doubles', 'pgl_ais_state_doubles',
+                    'pgl_hmc_dense_work_doubles'):
             fn.restype = C.c_longlong
         elif name not in ('pgl_last_error',):
             fn.restype = C.c_int
@@ -624,6 +632,25 @@ class DeviceGlm(object):
                                        C.c_void_p(d_ll), C.c_void_p(d_grad), int(prior[0]), *[float(z) for z in prior[1:]],
                                        1 if last else 0, int(n_warmup), C.c_void_p(d_Xt),
                                        C.c_void_p(d_sample_out) if d_sample_out else None))
+
+    # -- the same chain with a dense mass matrix (pgl_hmc_dense_*): d_W (M, P, P) lower-triangular factors of the inverse
+    # mass matrices; d_work: hmc_dense_work_doubles(M, P) doubles (0: none)
+    def hmc_dense_work_doubles(self, M, P):
+        return int(self.lib.pgl_hmc_dense_work_doubles(int(M), int(P)))
+
+    def tri_matvec_dev(self, d_W, M, P, trans, d_x, d_y):
+        _chk(self.lib.pgl_tri_matvec_dev(self.h, C.c_void_p(d_W), int(M), int(P), 1 if trans else 0, C.c_void_p(d_x),
+                                         C.c_void_p(d_y)))
+
+    def hmc_dense_begin_dev(self, d_state, M, P, d_W, d_work, d_Xt):
+        _chk(self.lib.pgl_hmc_dense_begin_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_W),
+                                              C.c_void_p(d_work) if d_work else None, C.c_void_p(d_Xt)))
+
+    def hmc_dense_leap_dev(self, d_state, M, P, d_W, d_work, d_ll, d_grad, prior, last, n_warmup, d_Xt, d_sample_out=0):
+        _chk(self.lib.pgl_hmc_dense_leap_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_W),
+                                             C.c_void_p(d_work) if d_work else None, C.c_void_p(d_ll), C.c_void_p(d_grad),
+                                             int(prior[0]), *[float(z) for z in prior[1:]], 1 if last else 0, int(n_warmup),
+                                             C.c_void_p(d_Xt), C.c_void_p(d_sample_out) if d_sample_out else None))
 
     # -- annealed importance sampling row kernels (pgl_ais_*; inference/batched_ais.py).  K particles x M neurons, rows
     # particle-major; prior: bfgs_objective_dev's tuple (Gaussian only); device pointers

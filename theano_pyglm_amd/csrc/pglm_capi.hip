@@ -100,7 +100,7 @@ struct pgl_context {
     int64_t gx_t_lo = 0, gx_t_hi = 0;    // time range GX was prepared for
     unsigned char* pin_args = nullptr;   // pinned staging of the per-call column arguments / results
     size_t pin_args_cap = 0;
-    int opt_f32 = 0, opt_nchunks = 0, opt_dbg = 0, opt_kernel = 0, opt_ptw = 0, opt_gibbs = 0, opt_finw = 0, opt_sb6 = 0, opt_epi64 = 0, opt_timing = 1, opt_slice_cols = 0, opt_hlp = 0, opt_pbmajor = 0;
+    int opt_f32 = 0, opt_nchunks = 0, opt_dbg = 0, opt_kernel = 0, opt_ptw = 0, opt_gibbs = 0, opt_finw = 0, opt_sb6 = 0, opt_epi64 = 0, opt_timing = 1, opt_slice_cols = 0, opt_hlp = 0, opt_pbmajor = 0, opt_tri_rows = 0;
     int opt_img32 = 0;                   // PGL_OPT_FEATURE_F32 = 2: f32 resident blocks for the narrow-shard kernel (k_fused8<.., 1>)
     int opt_record = 0;                  // PGL_OPT_RECORD_KERNELS: last_kernels holds the fused launches of the last evaluation
     std::vector<std::string> last_kernels;
@@ -330,6 +330,7 @@ int pgl_set_option(pgl_handle h, int option, int value)
     case 99: h->opt_dbg = value; return PGL_OK;
     case 98: h->opt_ptw = value; return PGL_OK;
     case 97: if (value < 0 || value > 16) return fail(PGL_ERR_ARG, "finalize waves: 0 (auto) .. 16"); h->opt_finw = value; return PGL_OK;
+    case 90: h->opt_tri_rows = value; return PGL_OK;         // dev: 1 = the triangular products of the dense-mass HMC on one workgroup per row (A/B)
     case 91: h->opt_pbmajor = value; return PGL_OK;          // dev: 1 = chunk-major grid for wide populations (A/B)
     case 92: h->opt_hlp = value; return PGL_OK;              // dev: 1 = no helper waves in the two-pass kernel (A/B)
     case 93: h->opt_slice_cols = value; return PGL_OK;      // dev: feature columns per slice of the 3-phase path (0 = 640)
@@ -2054,6 +2055,69 @@ int pgl_hmc_leap_dev(pgl_handle h, double* d_state, int M, int P, const double* 
     HIPCHK(hipSetDevice(h->device));
     hipLaunchKernelGGL(k_hmc_leap, dim3(M), dim3(256), 0, h->stream, pgl_hmc_view(d_state, M, P), d_minv, d_ll, d_grad, q,
                        last ? 1 : 0, n_warmup, d_Xt, d_sample_out);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+// ---- lock-step HMC with a dense mass matrix (inference/batched_hmc.py: mass = (M, P, P) or 'laplace_dense') -------------
+// The kick and the drift are epilogues of the products (pglm_hmc_dense.hip.h): no product is ever stored, no workspace.
+long long pgl_hmc_dense_work_doubles(int M, int P) { (void)M; (void)P; return 0; }
+
+// one product launch: (trans, epilogue) is one of the four instantiations the chain and pgl_tri_matvec_dev use
+static int tri_launch(pgl_handle h, int trans, int epi, const double* d_W, int M, int P, const double* d_x, double* d_y,
+                      double* d_Xt, const double* d_step, double scale)
+{
+    if (M > 65535) return fail(PGL_ERR_ARG, "at most 65535 rows per call");
+    const dim3 grid(h->opt_tri_rows ? 1 : (P + PGL_TRI_TILE - 1) / PGL_TRI_TILE, M);
+#define PGL_TRI_LAUNCH(T, E) hipLaunchKernelGGL((k_tri_matvec<T, E>), grid, dim3(256), 0, h->stream, d_W, d_x, P, d_y, d_Xt, d_step, scale)
+    if (epi == PGL_TRI_KICK) PGL_TRI_LAUNCH(1, PGL_TRI_KICK);
+    else if (epi == PGL_TRI_DRIFT) PGL_TRI_LAUNCH(0, PGL_TRI_DRIFT);
+    else if (trans) PGL_TRI_LAUNCH(1, PGL_TRI_STORE);
+    else PGL_TRI_LAUNCH(0, PGL_TRI_STORE);
+#undef PGL_TRI_LAUNCH
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+int pgl_tri_matvec_dev(pgl_handle h, const double* d_W, int M, int P, int trans, const double* d_x, double* d_y)
+{
+    if (!h || !d_W || !d_x || !d_y || d_x == d_y || M <= 0 || P <= 0) return fail(PGL_ERR_ARG, "bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    return tri_launch(h, trans, PGL_TRI_STORE, d_W, M, P, d_x, d_y, nullptr, nullptr, 0.0);
+}
+
+int pgl_hmc_dense_begin_dev(pgl_handle h, double* d_state, int M, int P, const double* d_W, double* d_work, double* d_Xt)
+{
+    (void)d_work;
+    if (!h || !d_state || !d_W || !d_Xt || M <= 0 || P <= 0) return fail(PGL_ERR_ARG, "bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    const HmcView v = pgl_hmc_view(d_state, M, P);
+    hipLaunchKernelGGL(k_hmc_dense_draw, dim3(M), dim3(256), 0, h->stream, v);
+    HIPCHK(hipGetLastError());
+    const double* step = v.sc + (size_t)2 * M;
+    int rc = tri_launch(h, 1, PGL_TRI_KICK, d_W, M, P, v.g, v.p, nullptr, step, 0.5);
+    if (rc) return rc;
+    return tri_launch(h, 0, PGL_TRI_DRIFT, d_W, M, P, v.p, v.q, d_Xt, step, 1.0);
+}
+
+int pgl_hmc_dense_leap_dev(pgl_handle h, double* d_state, int M, int P, const double* d_W, double* d_work, double* d_ll,
+                           double* d_grad, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu,
+                           double sigma, double lam, int last, int n_warmup, double* d_Xt, double* d_sample_out)
+{
+    (void)d_work;
+    if (!h || !d_state || !d_W || !d_ll || !d_grad || !d_Xt || M <= 0 || P <= 0) return fail(PGL_ERR_ARG, "bad argument");
+    BfgsPrior q;
+    int rc = ncg_prior(h, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    const HmcView v = pgl_hmc_view(d_state, M, P);
+    hipLaunchKernelGGL(k_hmc_dense_target, dim3(M), dim3(256), 0, h->stream, v, d_ll, d_grad, q);
+    HIPCHK(hipGetLastError());
+    const double* step = v.sc + (size_t)2 * M;
+    rc = tri_launch(h, 1, PGL_TRI_KICK, d_W, M, P, d_grad, v.p, nullptr, step, last ? 0.5 : 1.0);
+    if (rc) return rc;
+    if (!last) return tri_launch(h, 0, PGL_TRI_DRIFT, d_W, M, P, v.p, v.q, d_Xt, step, 1.0);
+    hipLaunchKernelGGL(k_hmc_dense_end, dim3(M), dim3(256), 0, h->stream, v, d_ll, d_grad, n_warmup, d_sample_out);
     HIPCHK(hipGetLastError());
     return PGL_OK;
 }

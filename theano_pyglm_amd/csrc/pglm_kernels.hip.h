@@ -21,6 +21,7 @@
 // Hessian-vector products H.v = F^T.(c o (F.v)) reuse the scheme with the epilogue swapped for one multiply (k_hvp5).
 // The dense Hessian H = F^T.diag(c).F is a contraction over time of its own (k_hess, pglm_hess.hip.h).
 // Posterior sampling runs HMC chains of all neurons in lock step around the ll+grad launch (k_hmc_*, pglm_hmc.hip.h).
+// A dense mass matrix adds two batched triangular matrix-vector products per leapfrog step (k_tri_matvec, pglm_hmc_dense.hip.h).
 // The per-neuron evidence comes from annealed importance sampling on the same moves (k_ais_*, pglm_ais.hip.h).
 // Simulation produces spikes instead of reading them: one workgroup per replicate runs the time loop (k_simulate,
 // pglm_simulate.hip.h).
@@ -39,6 +40,7 @@
 #include "pglm_bfgs.hip.h"
 #include "pglm_ncg.hip.h"
 #include "pglm_hmc.hip.h"
+#include "pglm_hmc_dense.hip.h"
 #include "pglm_ais.hip.h"
 #include "pglm_rescale.hip.h"
 #include "pglm_simulate.hip.h"

@@ -42,7 +42,8 @@ def initialize_test_harness(model_name, data, data_dir=None):
     return popn, popn_true, x_true
 
 
-def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False, gof=False, ppc=0, hmc=0, ais=0):
+def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False, gof=False, ppc=0, hmc=0, ais=0,
+                   hmc_mass='laplace'):
     """test/synth_map.py:10-32."""
     popn, popn_true, x_true = initialize_test_harness(model_name, data, data_dir)
     x0 = popn.sample(rng)
@@ -62,25 +63,27 @@ def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, r
         from theano_pyglm_amd.inference import predictive
         print(predictive.format_table(predictive.predictive_counts(popn, x_inf, ppc)))
     if hmc:
-        print(hmc_bias_table(popn, x_inf, hmc))
+        print(hmc_bias_table(popn, x_inf, hmc, hmc_mass))
     if ais:
         print(ais_evidence_table(popn, x_inf, ais))
     return x_inf, ll_inf, wall
 
 
-def hmc_bias_table(popn, x, n_draws):
-    """n_draws kept HMC draws from x: one line per neuron, bias posterior mean +- sd (and the Laplace standard error)."""
+def hmc_bias_table(popn, x, n_draws, mass='laplace'):
+    """n_draws kept HMC draws from x with the mass matrix `mass` ('laplace' or 'laplace_dense'): one line per neuron, bias
+    posterior mean +- sd (and the Laplace standard error)."""
     from theano_pyglm_amd.inference import batched_hmc
     from theano_pyglm_amd.inference.laplace import laplace_glms
     t0 = time.time()
-    res = batched_hmc.sample_glms_hmc(popn, x, n_draws, mass='laplace')
+    res = batched_hmc.sample_glms_hmc(popn, x, n_draws, mass=mass)
     wall = time.time() - t0
     s = batched_hmc.summarize(res['samples'][:, :, 0])
     try:
         se = [r['stderr_vec'][0] if r['pd'] else float('nan') for r in laplace_glms(popn, x)]
     except ValueError:
         se = None
-    lines = ["HMC: %d draws per neuron in %.2f s (%d ll+grad launches)" % (n_draws, wall, res['n_evals']),
+    lines = ["HMC%s: %d draws per neuron in %.2f s (%d ll+grad launches)"
+             % ("" if mass == 'laplace' else " (mass=%s)" % mass, n_draws, wall, res['n_evals']),
              "neuron   bias mean +- sd        ESS  accept   step" + ("   Laplace se" if se is not None else "")]
     for n in range(popn.N):
         ln = "%6d  %9.4f +- %-8.4f %6.0f  %6.2f  %6.4f" % (n, s['mean'][n], s['sd'][n], s['ess'][n], res['accept_rate'][n],
@@ -123,6 +126,8 @@ def main():
                     help='after the fit: predictive spike counts of N replicates simulated from the fitted model on the device')
     ap.add_argument('--hmc', type=int, default=0, metavar='N',
                     help='after the fit: N posterior draws per neuron by lock-step HMC on the device; prints the bias mean +- sd')
+    ap.add_argument('--hmc-mass', choices=['laplace', 'laplace_dense'], default='laplace',
+                    help="mass matrix of --hmc: 1 / diag A ('laplace') or the full Laplace covariance ('laplace_dense')")
     ap.add_argument('--ais', type=int, default=0, metavar='K',
                     help='after the fit: log evidence of every neuron given the network by annealed importance sampling with '
                          'K particles on the device, beside the Laplace log evidence (Gaussian impulse priors only)')
@@ -130,7 +135,8 @@ def main():
     with open(args.dataFile, 'rb') as f:
         data = pickle.load(f)
     run_synth_test(args.model, data, args.resultsDir, os.path.dirname(args.dataFile),
-                   False if args.sequential else ('torch' if args.newton_cg else None), use_rop=args.newton_cg, gof=args.gof, ppc=args.ppc, hmc=args.hmc, ais=args.ais)
+                   False if args.sequential else ('torch' if args.newton_cg else None), use_rop=args.newton_cg, gof=args.gof, ppc=args.ppc, hmc=args.hmc, ais=args.ais,
+                   hmc_mass=args.hmc_mass)
 
 
 if __name__ == '__main__':

@@ -18,6 +18,11 @@ the kept chain is a valid Markov chain; the random numbers are stateless functio
 component), documented in include/pyglm_hip.h, so a chain over a range of neurons equals the matching rows of a chain over
 all of them.
 
+The mass matrix is diagonal (mass=None, 'laplace' or an (M, P) array) or dense: mass='laplace_dense' or an (M, P, P)
+array of inverse mass matrices Sigma, factored on the host as Sigma = W W^T (factor_inverse_mass) and uploaded once.  The
+dense chain (csrc/pglm_hmc_dense.h) runs in the whitened momentum r = W^T p: a leapfrog step is the same evaluation plus
+two batched triangular matrix-vector products (pgl_hmc_dense_*), the draws, decisions and step-size rule unchanged.
+
 Served: exactly the populations of batched_newton_cg.supported (the packings whose per-neuron vector is the device's
 theta row, under the priors the row kernels know).  Time-sharded populations are not (nothing is all-reduced).
 """
@@ -42,16 +47,82 @@ def _check(population):
                          "evaluations are not all-reduced")
 
 
-def _laplace_minv(population, x, n_lo, n_hi, floor):
-    """1 / max(diag A, floor) in the theta layout, A = minus the Hessian of the log posterior at x."""
+def _theta_positions(population, x, n_lo, P):
+    """Packed position of every theta column (the per-neuron packed vector and the theta row hold the same numbers)."""
     from theano_pyglm_amd.utils.packvec import packdict, unpackdict, get_vars
-    H = population.compute_hessian_packed(x, n_lo, n_hi)
     _, shapes = packdict(get_vars(population.glm_syms(), x['glms'][n_lo]))
-    P = H.shape[1]
-    pi = np.rint(population.glm.theta_row(unpackdict(np.arange(P, dtype=float), shapes))).astype(int)   # packed position of theta column
+    return np.rint(population.glm.theta_row(unpackdict(np.arange(P, dtype=float), shapes))).astype(int)
+
+
+def _minv_from_hessian(H, pi, floor):
     d = -np.diagonal(H, axis1=1, axis2=2)[:, pi]
     d = np.where(np.isfinite(d), d, floor)
     return 1.0 / np.maximum(d, floor)
+
+
+def _laplace_minv(population, x, n_lo, n_hi, floor):
+    """1 / max(diag A, floor) in the theta layout, A = minus the Hessian of the log posterior at x."""
+    H = population.compute_hessian_packed(x, n_lo, n_hi)
+    return _minv_from_hessian(H, _theta_positions(population, x, n_lo, H.shape[1]), floor)
+
+
+def factor_inverse_mass(Sigma, sym_tol=1e-8):
+    """Lower-triangular W with W W^T = Sigma for inverse mass matrices Sigma (P, P) or (M, P, P).  Sigma must be finite,
+    symmetric -- |S_ij - S_ji| <= sym_tol sqrt(S_ii S_jj): the rounding of a computed inverse passes, a matrix that was
+    never meant to be symmetric does not -- and positive definite, else ValueError.  The factorisation is equilibrated
+    like laplace_from_hessian's: W = D^1/2 chol(D^-1/2 Sigma D^-1/2), D = diag Sigma, so parameters on scales many orders
+    of magnitude apart cost it no digits."""
+    S = np.asarray(Sigma, dtype=float)
+    if S.ndim not in (2, 3) or S.shape[-1] != S.shape[-2] or S.shape[-1] == 0:
+        raise ValueError("inverse mass matrices: a (P, P) or (M, P, P) array, got shape %s" % (S.shape,))
+    if not np.all(np.isfinite(S)):
+        raise ValueError("inverse mass matrix with a NaN or infinite entry")
+    d = np.diagonal(S, axis1=-2, axis2=-1)
+    if not np.all(d > 0.0):
+        raise ValueError("inverse mass matrix is not positive definite (a diagonal entry <= 0)")
+    sd = np.sqrt(d)
+    St = np.swapaxes(S, -1, -2)
+    if np.any(np.abs(S - St) > sym_tol * sd[..., :, None] * sd[..., None, :]):
+        raise ValueError("inverse mass matrix is not symmetric")
+    C = 0.5 * (S + St) / (sd[..., :, None] * sd[..., None, :])
+    try:
+        L = np.linalg.cholesky(C)
+    except np.linalg.LinAlgError:
+        raise ValueError("inverse mass matrix is not positive definite")
+    return np.ascontiguousarray(sd[..., :, None] * L)
+
+
+def _laplace_rows(population, x, n_lo, n_hi):
+    """-> (H (M, P, P) packed Hessians of the log posterior at x, [(pd, cov)] per neuron: laplace_glms' 'pd' and 'cov',
+    the same algebra on the same Hessian).  The one place mass='laplace_dense' gets its covariances from."""
+    from theano_pyglm_amd.inference.laplace import laplace_from_hessian
+    H = population.compute_hessian_packed(x, n_lo, n_hi)
+    rows = []
+    for i in range(H.shape[0]):
+        res = laplace_from_hessian(-0.5 * (H[i] + H[i].T), 0.0)
+        rows.append((bool(res['pd']), res['cov']))
+    return H, rows
+
+
+def _laplace_dense_factor(population, x, n_lo, n_hi, floor):
+    """W (M, P, P) for mass='laplace_dense' in the theta layout and dense_rows (M,): Sigma = the Laplace covariance where
+    the Laplace result is positive definite (and factors), else W = diag(sqrt(minv)) with the 'laplace' rule's minv."""
+    H, rows = _laplace_rows(population, x, n_lo, n_hi)
+    M, P = H.shape[0], H.shape[1]
+    pi = _theta_positions(population, x, n_lo, P)
+    minv = _minv_from_hessian(H, pi, floor)
+    W = np.zeros((M, P, P))
+    dense = np.zeros(M, dtype=bool)
+    for i, (pd, cov) in enumerate(rows):
+        if pd:
+            try:
+                W[i] = factor_inverse_mass(np.asarray(cov)[np.ix_(pi, pi)])
+                dense[i] = True
+                continue
+            except ValueError:
+                pass
+        W[i][np.diag_indices(P)] = np.sqrt(minv[i])
+    return W, dense
 
 
 def sample_glms_hmc(population, x, n_samples, n_warmup=200, n_leapfrog=10, step_sz=0.1, thin=1, mass=None, seed=0,
@@ -60,11 +131,15 @@ def sample_glms_hmc(population, x, n_samples, n_warmup=200, n_leapfrog=10, step_
 
     n_warmup transitions adapt every row's step size and are dropped; then n_samples * thin transitions, every thin-th
     kept.  step_sz: the starting step size, a number or one per row.  mass: None (identity), 'laplace' (minv = 1 /
-    max(diag A, mass_floor), A = minus the Hessian of the log posterior at x: Population.compute_hessian_packed) or an
-    (M, P) array of inverse masses in the theta layout.
+    max(diag A, mass_floor), A = minus the Hessian of the log posterior at x: Population.compute_hessian_packed), an
+    (M, P) array of inverse masses in the theta layout, an (M, P, P) array of inverse mass MATRICES Sigma in the theta
+    layout (finite, symmetric, positive definite: factor_inverse_mass) or 'laplace_dense' (Sigma = the Laplace covariance
+    A^-1 of every neuron, laplace_glms' 'cov'; a neuron whose A is not positive definite runs on the 'laplace' rule).
     Returns {'samples': (n_samples, M, P) rows in the theta layout [bias, w_stim, w_ir], 'accept_rate': (M,) after
-    warm-up, 'step_sz': (M,) the frozen step sizes, 'n_evals': ll+grad launches}.  x is not changed.
-    population.last_fit_stats records the launch counts and the host synchronisations inside the chain."""
+    warm-up, 'step_sz': (M,) the frozen step sizes, 'n_evals': ll+grad launches} and, with 'laplace_dense', 'dense_rows':
+    (M,) bool, the rows that run on the full covariance.  x is not changed.
+    population.last_fit_stats records the launch counts, the host synchronisations inside the chain, 'mass' ('identity',
+    'diagonal' or 'dense') and 'mass_setup_s' (the Hessian and the host factorisation)."""
     _check(population)
     n_samples, n_warmup, n_leapfrog, thin = int(n_samples), int(n_warmup), int(n_leapfrog), int(thin)
     if n_samples <= 0 or n_warmup < 0 or n_leapfrog <= 0 or thin <= 0:
@@ -75,10 +150,24 @@ def sample_glms_hmc(population, x, n_samples, n_warmup=200, n_leapfrog=10, step_
     M = n_hi - n_lo
     if M <= 0:
         raise ValueError("empty neuron range")
+    import time
+    t0 = time.perf_counter()
+    factor = dense_rows = None
     if isinstance(mass, str):
-        if mass != 'laplace':
-            raise ValueError("mass: None, 'laplace' or an (M, P) array")
-        mass = _laplace_minv(population, x, n_lo, n_hi, float(mass_floor))
+        if mass == 'laplace':
+            mass = _laplace_minv(population, x, n_lo, n_hi, float(mass_floor))
+        elif mass == 'laplace_dense':
+            factor, dense_rows = _laplace_dense_factor(population, x, n_lo, n_hi, float(mass_floor))
+            mass = None
+        else:
+            raise ValueError("mass: None, 'laplace', 'laplace_dense', an (M, P) or an (M, P, P) array")
+    elif mass is not None and np.ndim(mass) == 3:
+        P = population.glm.P
+        if np.shape(mass) != (M, P, P):
+            raise ValueError("mass: an (M, P, P) = (%d, %d, %d) array of inverse mass matrices" % (M, P, P))
+        factor = factor_inverse_mass(mass)
+        mass = None
+    setup_s = time.perf_counter() - t0
     dev = torch.device('cuda', population.device)
     handles = []
     for data in population.data_sequences:
@@ -93,7 +182,7 @@ def sample_glms_hmc(population, x, n_samples, n_warmup=200, n_leapfrog=10, step_
     try:
         with torch.cuda.stream(stream):
             out = _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, n_leapfrog, step_sz, thin, mass,
-                         int(seed), n_lo, n_hi, M)
+                         int(seed), n_lo, n_hi, M, factor)
     finally:
         try:
             stream.synchronize()
@@ -101,11 +190,14 @@ def sample_glms_hmc(population, x, n_samples, n_warmup=200, n_leapfrog=10, step_
             pass
         for h in handles:
             h.set_stream(None)
+    if dense_rows is not None:
+        out['dense_rows'] = dense_rows
+    population.last_fit_stats['mass_setup_s'] = setup_s
     return out
 
 
 def _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, n_leapfrog, step_sz, thin, mass, seed, n_lo, n_hi,
-           M):
+           M, factor=None):
     pk = _Packing(population, torch, handles, (n_lo, n_hi))
     assert pk.identity                                        # (hvp_packing() is None: the row IS the theta row)
     h0 = handles[0]
@@ -128,6 +220,11 @@ def _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, n_le
     if not np.all(step > 0.0):
         raise ValueError("step_sz must be positive")
     minv_ptr = minv.data_ptr() if minv is not None else 0
+    Wd = work = None
+    if factor is not None:                                    # (M, P, P) lower-triangular factors: uploaded once
+        assert factor.shape == (M, P, P)
+        Wd = torch.tensor(factor, dtype=f64, device=dev)
+        work = torch.empty(h0.hmc_dense_work_doubles(M, P), dtype=f64, device=dev)
     Xt = torch.empty((M, P), dtype=f64, device=dev)
     bufs = [torch.empty(M * (1 + P), dtype=f64, device=dev) for _ in handles]     # [ll | grad] per data sequence
     samples = torch.empty((n_samples, M, P), dtype=f64, device=dev)
@@ -153,22 +250,32 @@ def _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, n_le
     syncs_before_chain = counts['syncs']
     evals_before_chain = counts['ll_grad']
     for t in range(n_total):
-        h0.hmc_begin_dev(st.data_ptr(), M, P, minv_ptr, Xt.data_ptr())
+        if Wd is not None:
+            h0.hmc_dense_begin_dev(st.data_ptr(), M, P, Wd.data_ptr(), work.data_ptr(), Xt.data_ptr())
+        else:
+            h0.hmc_begin_dev(st.data_ptr(), M, P, minv_ptr, Xt.data_ptr())
         counts['row'] += 1
         k = t - n_warmup
         keep = k >= 0 and (k + 1) % thin == 0
         for i in range(n_leapfrog):
             llt, gt = evaluate(Xt)
             last = i == n_leapfrog - 1
-            h0.hmc_leap_dev(st.data_ptr(), M, P, minv_ptr, llt.data_ptr(), gt.data_ptr(), prm, last, n_warmup, Xt.data_ptr(),
-                            samples[k // thin].data_ptr() if (last and keep) else 0)
+            out_ptr = samples[k // thin].data_ptr() if (last and keep) else 0
+            if Wd is not None:
+                h0.hmc_dense_leap_dev(st.data_ptr(), M, P, Wd.data_ptr(), work.data_ptr(), llt.data_ptr(), gt.data_ptr(), prm,
+                                      last, n_warmup, Xt.data_ptr(), out_ptr)
+            else:
+                h0.hmc_leap_dev(st.data_ptr(), M, P, minv_ptr, llt.data_ptr(), gt.data_ptr(), prm, last, n_warmup,
+                                Xt.data_ptr(), out_ptr)
             counts['row'] += 1
     syncs_in_chain = counts['syncs'] - syncs_before_chain
     wait()
     sch = sc.cpu().numpy()
     out = {'samples': samples.cpu().numpy(), 'accept_rate': sch[SC_NACC] / float(n_samples * thin), 'step_sz': sch[SC_STEP].copy(),
            'n_evals': counts['ll_grad']}
+    # ('row' counts the begin / leap CALLS of the C ABI; a dense call is three small launches, a diagonal one is one)
     population.last_fit_stats = {'sampler': 'lock-step HMC (hip row kernels)', 'transitions': n_total,
+                                 'mass': 'dense' if Wd is not None else ('diagonal' if minv is not None else 'identity'),
                                  'll_grad_launches': counts['ll_grad'], 'row_launches': counts['row'],
                                  'evaluations_per_transition': (counts['ll_grad'] - evals_before_chain) / float(n_total),
                                  'row_launches_per_transition': counts['row'] / float(n_total),

@@ -11,6 +11,14 @@ C2: N = 32, nT = 300 000; C3: N = 128, nT = 600 000.  Per configuration:
                              packed vectors, state dicts packed and unpacked per evaluation, called the way the
                              Hmc*Update classes call it (n_leapfrog + 1 evaluations per transition)
   bias_sd / laplace_se       posterior sd of every neuron's bias from the kept draws against the Laplace standard error
+  mass                       the diagonal ('laplace') and the dense ('laplace_dense') mass matrix from the same fit, same seed,
+                             same lengths, each the steady (second) call: ms_per_transition (the chain: the call minus the
+                             mass set-up), over_floor, setup_s (Hessian + host factorisation), accept rate, median frozen
+                             step, median ESS of the kept draws (of the biases, and of all parameters) and ESS per second of
+                             chain time; dense_over_diagonal_ms the ratio of the two chains
+  tri_matvec                 the dense chain's product launches alone (pgl_tri_matvec_dev on the uploaded factors): ms and
+                             achieved GB/s (the lower triangle's bytes) per product, on the (tile, row) grid the library uses
+                             and on one workgroup per row (the rejected variant, dev option 90)
 Records, sets no threshold.  Prints one JSON line."""
 import argparse, copy, json, os, sys, time
 import numpy as np
@@ -47,6 +55,57 @@ def host_route(popn, x, n_leapfrog, step_sz, n_transitions, seed=0):
         Q, acc, _ = hmc_lockstep(UG, step_sz, n_leapfrog, Q, rng=rng)
         n_acc += int(acc.sum())
     return (time.perf_counter() - t0) * 1e3 / n_transitions, n_acc / float(n_transitions * popn.N)
+
+
+def mass_figures(popn, x, mass, n_samples, n_warmup, n_leapfrog, floor_ms):
+    """One mass matrix: the steady (second) call of sample_glms_hmc and what its draws are worth."""
+    import torch
+    from theano_pyglm_amd.inference.batched_hmc import sample_glms_hmc, summarize
+    for rep in range(2):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = sample_glms_hmc(popn, x, n_samples, n_warmup=n_warmup, n_leapfrog=n_leapfrog, step_sz=0.1, mass=mass, seed=1)
+        wall = time.perf_counter() - t0
+    st = popn.last_fit_stats
+    chain_s = wall - st['mass_setup_s']
+    ess_bias = summarize(res['samples'][:, :, 0])['ess']
+    ess_all = summarize(res['samples'])['ess']
+    out = {'ms_per_transition': chain_s * 1e3 / st['transitions'], 'setup_s': st['mass_setup_s'],
+           'accept_rate': {'min': float(res['accept_rate'].min()), 'mean': float(res['accept_rate'].mean())},
+           'step_sz_median': float(np.median(res['step_sz'])),
+           'ess_median_bias': float(np.median(ess_bias)), 'ess_median_all': float(np.median(ess_all)),
+           'ess_min_all': float(np.min(ess_all))}
+    out['over_floor'] = out['ms_per_transition'] / floor_ms
+    out['ess_per_s_bias'] = out['ess_median_bias'] / chain_s
+    out['ess_per_s_all'] = out['ess_median_all'] / chain_s
+    if 'dense_rows' in res:
+        out['dense_rows'] = int(res['dense_rows'].sum())
+    return out
+
+
+def product_figures(popn, h, stream, N, P, reps=20):
+    """pgl_tri_matvec_dev alone on (N, P, P) factors: ms and GB/s of the lower triangle per product, both grids."""
+    import torch
+    dev = torch.device('cuda', popn.device)
+    W = torch.tril(torch.randn((N, P, P), dtype=torch.float64, device=dev))
+    xv = torch.randn((N, P), dtype=torch.float64, device=dev)
+    yv = torch.empty((N, P), dtype=torch.float64, device=dev)
+    nbytes = N * (P * (P + 1) // 2) * 8.0
+    out = {'bytes_per_product': nbytes}
+    torch.cuda.synchronize()
+    for label, rows in (('tile_grid', 0), ('row_grid', 1)):
+        h.set_option(90, rows)
+        for trans in (0, 1):
+            for k in range(2):
+                stream.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(reps):
+                    h.tri_matvec_dev(W.data_ptr(), N, P, trans, xv.data_ptr(), yv.data_ptr())
+                stream.synchronize()
+                ms = (time.perf_counter() - t0) * 1e3 / reps
+            out['%s_%s' % (label, 'Wt_x' if trans else 'W_x')] = {'ms': ms, 'GBps': nbytes / (ms * 1e-3) / 1e9}
+    h.set_option(90, 0)
+    return out
 
 
 def run(name, n_samples, n_warmup, n_leapfrog, host_transitions):
@@ -92,9 +151,14 @@ def run(name, n_samples, n_warmup, n_leapfrog, host_transitions):
                 h.ll_grad_dev(th.data_ptr(), We.data_ptr(), buf.data_ptr(), buf[N:].data_ptr(), 0, N)
             stream.synchronize()
             out['floor_ms_per_transition'] = (time.perf_counter() - t0) * 1e3 / reps
+        out['tri_matvec'] = product_figures(popn, h, stream, N, P)
     finally:
         h.set_stream(None)
     out['device_over_floor'] = out['device_ms_per_transition'] / out['floor_ms_per_transition']
+    out['mass'] = dict((m, mass_figures(popn, x, m, n_samples, n_warmup, n_leapfrog, out['floor_ms_per_transition']))
+                       for m in ('laplace', 'laplace_dense'))
+    out['mass']['dense_over_diagonal_ms'] = (out['mass']['laplace_dense']['ms_per_transition'] /
+                                             out['mass']['laplace']['ms_per_transition'])
     host_route(popn, x, n_leapfrog, 1e-3, 1)                   # warm
     ms, acc = host_route(popn, x, n_leapfrog, 1e-3, host_transitions)
     out['host_ms_per_transition'] = ms
