@@ -433,6 +433,55 @@ int pgl_ais_leap_dev(pgl_handle h, double* d_state, int K, int M, int P, const d
                      const double* d_grad, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma,
                      double lam, int last, int adapt, double* d_Xt, double* d_acc_out, double* d_step_out);
 
+/* Lock-step accelerated proximal gradient for the group-lasso MAP (inference/batched_prox.py) as row kernels on the
+ * handle's stream: the theta rows [bias, w_stim (Ds), w_ir (N groups of B)] of M neurons n_lo .. n_lo + M - 1 at once, one
+ * workgroup per row around ONE pgl_ll_grad_dev over all rows per call.  The objective of a row is F = f + h,
+ *     f = -ll - log N(bias; mu_b, sg_b) - log N(w_stim; 0, stim_sigma), the bias and stimulus terms of pgl_bfgs_objective_dev.
+ *         A non-finite f is +inf (a trial there fails); a NaN or infinite entry of its gradient becomes 0;
+ *     h = (lam_r / sigma) sum_g |w_g - mu|_2, minus the group-lasso log prior of pgl_bfgs_objective_dev kind 1, with lam_r
+ *         one number per row: d_lam (M), device.  lam_r = 0 and lam_r = +inf are served (+inf: every group ends at mu);
+ *     prox_{t h}: w_g <- mu + (v_g - mu) max(0, 1 - t lam_r / (sigma |v_g - mu|)) group by group (0 when the norm is 0),
+ *         bias and stimulus entries unchanged.  A shrunk group equals mu EXACTLY.
+ * The algorithm is FISTA with backtracking (Beck & Teboulle 2009), restated in csrc/pglm_prox.h, which is compiled for the
+ * host too.  From the extrapolated point y with (f_y, g_y) known, the trial z = prox_{t h}(y - t g_y) is evaluated; then
+ *     1. sufficient decrease: f_z finite and f_z <= f_y + <g_y, z - y> + |z - y|^2 / (2 t) + 1e-12 max(1, |f_y|);
+ *     2. failure: t <- t / 2, new trial; max_backtrack failures in one iteration end the row, status 2;
+ *     3. pass, F_z > F_x and y != x: restart -- z is dropped, y = x, tk = 1, t <- 2 t, new trial from x at once;
+ *     4. otherwise accept: xprev = x, x = z, g_x = g_z, iters += 1;
+ *     5. KKT residual r at x: the largest of |g| over bias and stimulus entries, |g_g + (lam_r / sigma) (w_g - mu) /
+ *        |w_g - mu||_inf over the non-zero groups, max(0, |g_g|_2 - lam_r / sigma) over the zero groups (w_g == mu);
+ *     6. r <= gtol ends the row with status 0, iters == maxiter with status 1;
+ *     7. tk' = (1 + sqrt(1 + 4 tk^2)) / 2, beta = (tk - 1) / tk'; beta = 0: y = x and the next trial goes out at once, else
+ *        y = x + beta (x - xprev) is evaluated first (a non-finite f_y restarts from x, t kept).
+ * What differs from the textbook: the function restart of step 3 (O'Donoghue & Candes 2015); the step doubles on a restart
+ * and never grows otherwise; the first step is BFGS's, t = min(1, 1.01 / |g|_2); and the rounding allowance of test 1,
+ * ten times the spread of ll between summation orders, without which the test fails on noise once |z - y|^2 / (2 t) is
+ * below the rounding of f.  An iteration is two evaluations, one after a start or a restart.
+ * Every sum over a row (<g_y, z - y>, |z - y|^2, the group norms, h, r) has a fixed order and uses no atomics: two runs give
+ * the same bits, and a group norm is summed by one thread, so B need not divide the wave size.
+ * All state of M rows of P parameters lives in ONE device block of pgl_prox_state_doubles(M, P) doubles, in this order:
+ *   (M,P) each: x, xprev, y, g_x (grad f at x), g_y (grad f at y);
+ *   (M) each:   f_x, F_x, f_y, t (the step), tk (the momentum parameter), iters (accepted steps), nfev (evaluations, the one
+ *               before init included), nbt (failed trials of the running iteration), restarts, phase (0: d_Xt holds y,
+ *               1: d_Xt holds the trial z, 2: ended), status, kkt (r at x), y_is_x, and the smallest margin of each kind of
+ *               decision taken so far, relative to the compared quantities: m_sd (test 1, over max(1, |f_y|)), m_restart
+ *               (test 3, over max(1, |F_x|)), m_zero (|1 - t lam_r / (sigma |v_g - mu|)| of a group), m_kkt (|r - gtol| / gtol).
+ *   init:  x in the state, (d_ll, d_grad) = ll (M) and its gradient (M, P) at x (overwritten with f, grad f): y = x, tk = 1,
+ *          the KKT test at x (maxiter <= 0 ends every row that fails it with status 1) and the first trial into d_Xt (M, P,
+ *          not part of the state), phase 1.
+ *   step:  (d_ll, d_grad) = the evaluation at d_Xt (overwritten with f, grad f): one call of the machine for every row
+ *          that has not ended; d_Xt = the points to evaluate next.  An ended row keeps x in its row of d_Xt -- it is
+ *          evaluated again, harmlessly -- and is never written again.
+ * flags_out: NULL, or M doubles of pinned host memory into which every row a kernel has advanced writes its phase: the
+ * driver reads it behind an event every few calls and never waits per iteration. */
+long long pgl_prox_state_doubles(int M, int P);
+int pgl_prox_init_dev(pgl_handle h, double* d_state, int M, int P, double* d_ll, double* d_grad, double mu_b, double sg_b,
+                      double stim_sigma, double mu, double sigma, const double* d_lam, double gtol, int maxiter, double* d_Xt,
+                      double* flags_out);
+int pgl_prox_step_dev(pgl_handle h, double* d_state, int M, int P, double* d_ll, double* d_grad, double mu_b, double sg_b,
+                      double stim_sigma, double mu, double sigma, const double* d_lam, double gtol, int maxiter, int max_backtrack,
+                      double* d_Xt, double* flags_out);
+
 /* convolve_with_basis(S, ibasis) (basis.py:201-236 via impulse.py:114-130):
  * fS_out (nT,N,B) row-major, float64. */
 int pgl_features(pgl_handle h, double* fS_out);

@@ -40,6 +40,7 @@ SYMBOLS = [
     'pgl_ncg_state_doubles', 'pgl_ncg_init_dev', 'pgl_ncg_cg_step_dev', 'pgl_ncg_trial_dev', 'pgl_ncg_search_step_dev',
     'pgl_hmc_state_doubles', 'pgl_hmc_init_dev', 'pgl_hmc_begin_dev', 'pgl_hmc_leap_dev',
     'pgl_hmc_dense_work_doubles', 'pgl_tri_matvec_dev', 'pgl_hmc_dense_begin_dev', 'pgl_hmc_dense_leap_dev',
+    'pgl_prox_state_doubles', 'pgl_prox_init_dev', 'pgl_prox_step_dev',
     'pgl_ais_state_doubles', 'pgl_ais_init_dev', 'pgl_ais_start_dev', 'pgl_ais_temper_dev', 'pgl_ais_begin_dev',
     'pgl_ais_leap_dev',
     'pgl_hess_dev', 'pgl_hess',
@@ -184,6 +185,11 @@ def load():
         lib.pgl_ais_temper_dev.argtypes = kmp + [C.c_int] + [C.c_double] * 6 + [C.c_double, vp]
         lib.pgl_ais_begin_dev.argtypes = kmp + [vp, vp]
         lib.pgl_ais_leap_dev.argtypes = kmp + [vp, vp, vp, C.c_int] + [C.c_double] * 6 + [C.c_int, C.c_int, vp, vp, vp]
+    if hasattr(lib, 'pgl_prox_init_dev'):                     # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
+        lib.pgl_prox_state_doubles.argtypes = [C.c_int, C.c_int]
+        prox = [vp, vp, C.c_int, C.c_int, vp, vp] + [C.c_double] * 5 + [vp, C.c_double, C.c_int]
+        lib.pgl_prox_init_dev.argtypes = prox + [vp, vp]
+        lib.pgl_prox_step_dev.argtypes = prox + [C.c_int, vp, vp]
     lib.pgl_features.argtypes = [vp, vp]
     lib.pgl_impulse_currents.argtypes = [vp, vp, vp]
     lib.pgl_state.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
@@ -217,7 +223,7 @@ def load():
             continue
         fn = getattr(lib, name)
         if name in ('pgl_bfgs_state_doubles', 'pgl_ncg_state_doubles', 'pgl_hmc_state_doubles', 'pgl_ais_state_doubles',
-                    'pgl_hmc_dense_work_doubles'):
+                    'pgl_hmc_dense_work_doubles', 'pgl_prox_state_doubles'):
             fn.restype = C.c_longlong
         elif name not in ('pgl_last_error',):
             fn.restype = C.c_int
@@ -651,6 +657,21 @@ class DeviceGlm(object):
                                              C.c_void_p(d_work) if d_work else None, C.c_void_p(d_ll), C.c_void_p(d_grad),
                                              int(prior[0]), *[float(z) for z in prior[1:]], 1 if last else 0, int(n_warmup),
                                              C.c_void_p(d_Xt), C.c_void_p(d_sample_out) if d_sample_out else None))
+
+    # -- lock-step proximal gradient row kernels for the group-lasso MAP (pgl_prox_*; inference/batched_prox.py).  prior:
+    # (mu_b, sg_b, stim_sigma, mu, sigma); d_lam: (M) device, one lam per row; flags_out: pinned host memory or 0
+    def prox_state_doubles(self, M, P):
+        return int(self.lib.pgl_prox_state_doubles(int(M), int(P)))
+
+    def prox_init_dev(self, d_state, M, P, d_ll, d_grad, prior, d_lam, gtol, maxiter, d_Xt, flags_out=0):
+        _chk(self.lib.pgl_prox_init_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_ll), C.c_void_p(d_grad),
+                                        *[float(z) for z in prior], C.c_void_p(d_lam), float(gtol), int(maxiter),
+                                        C.c_void_p(d_Xt), C.c_void_p(flags_out) if flags_out else None))
+
+    def prox_step_dev(self, d_state, M, P, d_ll, d_grad, prior, d_lam, gtol, maxiter, max_backtrack, d_Xt, flags_out=0):
+        _chk(self.lib.pgl_prox_step_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_ll), C.c_void_p(d_grad),
+                                        *[float(z) for z in prior], C.c_void_p(d_lam), float(gtol), int(maxiter),
+                                        int(max_backtrack), C.c_void_p(d_Xt), C.c_void_p(flags_out) if flags_out else None))
 
     # -- annealed importance sampling row kernels (pgl_ais_*; inference/batched_ais.py).  K particles x M neurons, rows
     # particle-major; prior: bfgs_objective_dev's tuple (Gaussian only); device pointers

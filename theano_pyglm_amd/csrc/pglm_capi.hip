@@ -233,7 +233,7 @@ static int sim_launch(const SimParams& sp, int n_rep, int threads, size_t lds, h
 extern "C" {
 
 const char* pgl_last_error(void) { return g_err.c_str(); }
-int pgl_version(void) { return 105; }
+int pgl_version(void) { return 106; }
 
 int pgl_device_count(void)
 {
@@ -2201,6 +2201,52 @@ int pgl_ais_leap_dev(pgl_handle h, double* d_state, int K, int M, int P, const d
     HIPCHK(hipSetDevice(h->device));
     hipLaunchKernelGGL(k_ais_leap, dim3(K * M), dim3(256), 0, h->stream, pgl_ais_view(d_state, K, M, P), d_minv, d_ll, d_grad, q,
                        last ? 1 : 0, adapt ? 1 : 0, d_Xt, d_acc_out, d_step_out);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+// ---- lock-step proximal gradient row kernels for the group-lasso MAP (inference/batched_prox.py) -------------------------
+long long pgl_prox_state_doubles(int M, int P) { return (long long)pgl_prox_doubles(M, P); }
+
+static int prox_args(pgl_handle h, double* d_state, int M, int P, double* d_ll, double* d_grad, double mu_b, double sg_b,
+                     double stim_sigma, double mu, double sigma, const double* d_lam, double gtol, int maxiter, int max_backtrack,
+                     double* d_Xt, double* flags_out, ProxArgs& a)
+{
+    if (!h || !d_state || !d_ll || !d_grad || !d_lam || !d_Xt || M <= 0 || P <= 0) return fail(PGL_ERR_ARG, "bad argument");
+    if (!(gtol > 0.0) || !(sigma > 0.0)) return fail(PGL_ERR_ARG, "gtol and sigma must be positive");
+    memset(&a, 0, sizeof(a));
+    int rc = ncg_prior(h, P, 1, mu_b, sg_b, stim_sigma, mu, sigma, 0.0, a.q);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    double* flags_dev = nullptr;
+    if (flags_out && flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
+    a.ll = d_ll; a.grad = d_grad; a.lam = d_lam; a.gtol = gtol; a.maxiter = maxiter; a.max_backtrack = max_backtrack;
+    a.Xt = d_Xt; a.flags = flags_dev;
+    return PGL_OK;
+}
+
+int pgl_prox_init_dev(pgl_handle h, double* d_state, int M, int P, double* d_ll, double* d_grad, double mu_b, double sg_b,
+                      double stim_sigma, double mu, double sigma, const double* d_lam, double gtol, int maxiter, double* d_Xt,
+                      double* flags_out)
+{
+    ProxArgs a;
+    int rc = prox_args(h, d_state, M, P, d_ll, d_grad, mu_b, sg_b, stim_sigma, mu, sigma, d_lam, gtol, maxiter, 1, d_Xt, flags_out, a);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_prox_init, dim3(M), dim3(256), 0, h->stream, pgl_prox_view(d_state, M, P), a);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+int pgl_prox_step_dev(pgl_handle h, double* d_state, int M, int P, double* d_ll, double* d_grad, double mu_b, double sg_b,
+                      double stim_sigma, double mu, double sigma, const double* d_lam, double gtol, int maxiter, int max_backtrack,
+                      double* d_Xt, double* flags_out)
+{
+    if (max_backtrack <= 0) return fail(PGL_ERR_ARG, "max_backtrack must be positive");
+    ProxArgs a;
+    int rc = prox_args(h, d_state, M, P, d_ll, d_grad, mu_b, sg_b, stim_sigma, mu, sigma, d_lam, gtol, maxiter, max_backtrack, d_Xt,
+                       flags_out, a);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_prox_step, dim3(M), dim3(256), 0, h->stream, pgl_prox_view(d_state, M, P), a);
     HIPCHK(hipGetLastError());
     return PGL_OK;
 }

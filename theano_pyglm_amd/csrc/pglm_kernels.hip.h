@@ -23,6 +23,8 @@
 // Posterior sampling runs HMC chains of all neurons in lock step around the ll+grad launch (k_hmc_*, pglm_hmc.hip.h).
 // A dense mass matrix adds two batched triangular matrix-vector products per leapfrog step (k_tri_matvec, pglm_hmc_dense.hip.h).
 // The per-neuron evidence comes from annealed importance sampling on the same moves (k_ais_*, pglm_ais.hip.h).
+// The group-lasso MAP runs accelerated proximal gradient fits of all neurons in lock step around the same launch (k_prox_*,
+// pglm_prox.hip.h).
 // Simulation produces spikes instead of reading them: one workgroup per replicate runs the time loop (k_simulate,
 // pglm_simulate.hip.h).
 #pragma once
@@ -42,5 +44,6 @@
 #include "pglm_hmc.hip.h"
 #include "pglm_hmc_dense.hip.h"
 #include "pglm_ais.hip.h"
+#include "pglm_prox.hip.h"
 #include "pglm_rescale.hip.h"
 #include "pglm_simulate.hip.h"

@@ -6,6 +6,8 @@ MAP fit on synthetic data -- counterpart of test/synth_map.py + test/synth_harne
 The sweep over the neurons runs as the GPU lock-step optimizer by default (inference/batched_bfgs.py);
 --sequential (batched=False) is the reference's loop of per-neuron scipy fits; --newton-cg runs the sweep as the GPU
 lock-step Newton-CG optimizer on device Hessian-vector products (inference/batched_newton_cg.py; the reference's use_rop).
+--prox runs the sweep as the GPU lock-step proximal-gradient fit of the group-lasso MAP (inference/batched_prox.py) and prints
+status, iterations and the number of non-zero presynaptic groups per neuron.
 --gof prints the time-rescaling KS table of the fitted model (inference/gof.py) after the fit.
 --ppc N prints the predictive spike-count table of N replicates simulated from the fitted model (inference/predictive.py).
 --hmc N draws N posterior samples of every neuron's parameters from the fit by lock-step HMC on the device
@@ -43,14 +45,16 @@ def initialize_test_harness(model_name, data, data_dir=None):
 
 
 def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False, gof=False, ppc=0, hmc=0, ais=0,
-                   hmc_mass='laplace'):
+                   hmc_mass='laplace', prox=False):
     """test/synth_map.py:10-32."""
     popn, popn_true, x_true = initialize_test_harness(model_name, data, data_dir)
     x0 = popn.sample(rng)
     print("LL0: %f" % popn.compute_log_p(x0))
     t0 = time.time()
-    x_inf = coord_descent(popn, x0=x0, maxiter=1, batched=batched, use_rop=use_rop)
+    x_inf = coord_descent(popn, x0=x0, maxiter=1, batched=batched, use_rop=use_rop, prox=prox)
     wall = time.time() - t0
+    if prox:
+        print(prox_table(popn, x_inf))
     ll_inf = popn.compute_log_p(x_inf)
     print("LL_inf: %f   (MAP wall-clock %.2f s)" % (ll_inf, wall))
     if results_dir is not None:
@@ -67,6 +71,20 @@ def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, r
     if ais:
         print(ais_evidence_table(popn, x_inf, ais))
     return x_inf, ll_inf, wall
+
+
+def prox_table(popn, x):
+    """One line per neuron from the last proximal-gradient sweep: status, iterations, evaluations and the number of
+    presynaptic groups of x that are not exactly at the prior's mu."""
+    import numpy as np
+    per = popn.last_fit_stats['per_neuron']
+    mu = float(popn.glm.imp_model.prior.mu)
+    lines = ["neuron  status  iters   nfev  non-zero groups (of %d)" % popn.N]
+    for n in range(popn.N):
+        w = np.asarray(x['glms'][n]['imp']['w_ir'], dtype=float).reshape(popn.N, -1)
+        lines.append("%6d  %6d  %5d  %5d  %6d" % (n, per['status'][n], per['iters'][n], per['nfev'][n],
+                                                int(np.sum(np.any(w != mu, axis=1)))))
+    return "\n".join(lines)
 
 
 def hmc_bias_table(popn, x, n_draws, mass='laplace'):
@@ -120,6 +138,9 @@ def main():
     ap.add_argument('--newton-cg', action='store_true',
                     help='lock-step Newton-CG on device Hessian-vector products instead of lock-step BFGS '
                          '(with --sequential: per-neuron scipy Newton-CG fits)')
+    ap.add_argument('--prox', action='store_true',
+                    help='group-lasso MAP by lock-step proximal gradient on the device (exact zeros); prints status, '
+                         'iterations and the non-zero groups per neuron')
     ap.add_argument('--gof', action='store_true',
                     help='after the fit: time-rescaling KS test of every neuron (rescaled inter-spike intervals against Exp(1))')
     ap.add_argument('--ppc', type=int, default=0, metavar='N',
@@ -136,7 +157,7 @@ def main():
         data = pickle.load(f)
     run_synth_test(args.model, data, args.resultsDir, os.path.dirname(args.dataFile),
                    False if args.sequential else ('torch' if args.newton_cg else None), use_rop=args.newton_cg, gof=args.gof, ppc=args.ppc, hmc=args.hmc, ais=args.ais,
-                   hmc_mass=args.hmc_mass)
+                   hmc_mass=args.hmc_mass, prox=args.prox)
 
 
 if __name__ == '__main__':

@@ -10,6 +10,11 @@ far and scored by the held-out log likelihood.  Training split, held-out split a
 each get their own device-resident handle, uploaded once; `set_hyperparameters` only changes
 host-side prior scalars, so nothing moves between candidates.
 
+--path replaces the grid of cold-ish BFGS sweeps by ONE warm-started regularisation path of the proximal-gradient solver
+(inference/batched_prox.py: lasso_path) on the training split, scored per neuron on the held-out split: every neuron gets
+the lam that predicts ITS held-out spikes best, the model is refitted on all data with those per-neuron lams, and -- when
+the true model is known -- the recovered support is printed against the true adjacency matrix.
+
 Note on the reference script: its `nlp` sums over `population.data_sequences`, which at that point
 holds the *full* data set only (the splits are preprocessed but never added, :26-31), so the
 reference trains every candidate on all data.  Here `data_sequences` is switched to the training
@@ -101,14 +106,71 @@ def run_xv(popn, data, models, train_frac=0.75, batched=None, rng=None, verbose=
     return best_x, best_ind, train_lps, xv_lls, total_lls
 
 
+def run_path(popn, data, train_frac=0.75, n_lams=10, lam_ratio=1e-2, rng=None, verbose=True):
+    """The --path sweep.  Returns (x refitted on all data with the per-neuron lams, lam (N,), the path's result dict)."""
+    from theano_pyglm_amd.inference import batched_prox
+    from theano_pyglm_amd.inference.smart_init import initialize_with_data
+    T_split = data['T'] * train_frac
+    train_data = popn.preprocess_data(segment_data(data, (0, T_split)))
+    xv_data = popn.preprocess_data(segment_data(data, (T_split, data['T'])))
+    full_sequences = popn.data_sequences
+    x0 = popn.sample(rng)
+    try:
+        popn.data_sequences = [train_data]
+        popn.set_data(train_data)
+        initialize_with_data(popn, train_data, x0)
+        path = batched_prox.lasso_path(popn, x0, n_lams=n_lams, lam_ratio=lam_ratio, heldout=xv_data)
+    finally:
+        popn.data_sequences = full_sequences
+        popn.set_data(data)
+        popn.release_data(train_data)
+        popn.release_data(xv_data)
+    lams = path['lams']
+    lam = lams[path['best']] if lams.ndim == 1 else lams[path['best'], np.arange(popn.N)]
+    if verbose:
+        for l in range(lams.shape[0]):
+            print("lam %10.4g:\tnon-zero groups %4d\tXV LL: %.1f" % (np.median(lams[l]), int(path['support'][l].sum()),
+                                                                   float(path['heldout_ll'][l].sum())))
+        print("per-neuron lam: %s" % np.array2string(lam, precision=4))
+    x = path['x_best']
+    res = batched_prox.fit_glms_prox(popn, x, lam=lam)
+    return x, lam, dict(path, refit=res)
+
+
+def support_table(support, A_true):
+    """Recovered support (N_pre, N_post) bool against the true adjacency matrix: true / false positives and negatives."""
+    A = np.asarray(A_true) != 0
+    S = np.asarray(support, dtype=bool)
+    tp, fp, fn, tn = np.sum(S & A), np.sum(S & ~A), np.sum(~S & A), np.sum(~S & ~A)
+    return "support against the true adjacency: %d true positives, %d false positives, %d false negatives, %d true negatives" \
+        % (tp, fp, fn, tn)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('-m', '--model', default='standard_glm')
     ap.add_argument('-d', '--dataFile', required=True)
     ap.add_argument('-r', '--resultsDir', default='.')
+    ap.add_argument('--path', action='store_true',
+                    help='one warm-started group-lasso path of the proximal-gradient solver with a lam per neuron, instead of '
+                         'the grid of BFGS sweeps')
     args = ap.parse_args()
     data = load_data(args.dataFile)
     popn, popn_true, x_true = initialize_test_harness(args.model, data, os.path.dirname(args.dataFile))
+    if args.path:
+        t0 = time.time()
+        best_x, lam, path = run_path(popn, data)
+        print("Path wall-clock %.2f s" % (time.time() - t0))
+        print("Best Total LL: %f" % popn.compute_ll(best_x))
+        if popn_true is not None:
+            print("True LL: %f" % popn_true.compute_ll(x_true))
+            # support[n_post, n_pre] of the fit; the adjacency matrix is A[n_pre, n_post]
+            A_true = x_true.get('net', {}).get('graph', {}).get('A')
+            if A_true is not None:
+                print(support_table(path['refit']['support'].T, np.reshape(A_true, (popn.N, popn.N))))
+        with open(os.path.join(args.resultsDir, 'results.pkl'), 'wb') as f:
+            pickle.dump(best_x, f, protocol=-1)
+        return
     base = make_model(args.model, N=data['N'], dt=0.001)
     stabilize_sparsity(base)
     t0 = time.time()

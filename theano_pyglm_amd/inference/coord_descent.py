@@ -279,13 +279,21 @@ def resolve_batched(population, batched):
     return batched
 
 
-def coord_descent(population, x0=None, maxiter=50, atol=1e-5, batched=None, verbose=False, use_rop=False):
+def coord_descent(population, x0=None, maxiter=50, atol=1e-5, batched=None, verbose=False, use_rop=False, prox=False):
     """coord_descent.py:206-266.  `batched`: see resolve_batched (None = automatic; batched=False is the
     reference's sweep of N sequential scipy BFGS fits, kept for comparison).  use_rop: the per-neuron fits of the
     sequential sweep run Newton-CG on device Hessian-vector products (parallel_coord_descent.py:62-63); with
     batched=None it selects that sweep.  use_rop with batched='torch' runs the sweep as ONE lock-step Newton-CG fit of all
-    neurons on the GPU (inference/batched_newton_cg.py); there is no numpy lock-step Newton: batched=True raises."""
+    neurons on the GPU (inference/batched_newton_cg.py); there is no numpy lock-step Newton: batched=True raises.
+    prox=True: the sweep is ONE lock-step proximal-gradient fit of the group-lasso MAP on the GPU (inference/batched_prox.py:
+    exact zeros in the impulse weights); it needs a group-lasso impulse prior and takes no other sweep option."""
     N = population.model['N']
+    if prox:
+        if use_rop or batched not in (None, 'torch'):
+            raise ValueError("prox=True runs the GPU lock-step proximal-gradient sweep: no use_rop, batched None or 'torch'")
+        from theano_pyglm_amd.inference import batched_prox
+        batched_prox._check(population)                       # unsupported prior / packing / time shard: before any device work
+        batched = 'torch'
     if use_rop and batched is None:
         batched = False
     if use_rop and batched and batched != 'torch':
@@ -313,7 +321,9 @@ def coord_descent(population, x0=None, maxiter=50, atol=1e-5, batched=None, verb
     it = 0
     while not converged and it < maxiter:
         it += 1
-        if batched == 'torch' and use_rop:
+        if prox:
+            batched_prox.fit_glms_prox(population, x, verbose=verbose)
+        elif batched == 'torch' and use_rop:
             batched_newton_cg.fit_glms_newton_cg_torch(population, x, verbose=verbose)
         elif batched == 'torch':
             from theano_pyglm_amd.inference.batched_bfgs import fit_glms_batched_torch
