@@ -216,6 +216,28 @@ int pgl_hess_dev(pgl_handle h, double* d_H, int ld);
 /* prepare + pgl_hess_dev with host pointers: theta ((n_hi-n_lo), P), Weff (N,N), H_out ((n_hi-n_lo), P, P). */
 int pgl_hess(pgl_handle h, int n_lo, int n_hi, const double* theta, const double* Weff, double* H_out);
 
+/* Batched dense factorisation for the Laplace posterior (inference/laplace.py; the reference builds the Hessian for its
+ * Newton fit and has no Laplace step).  With A_m = minus the Hessian of the log posterior of row m, symmetric, in the
+ * theta layout as pgl_hess_dev leaves it:
+ *     D = diag A,  C = D^-1/2 A D^-1/2 = Ls Ls^T                    (the equilibrated factorisation of laplace_from_hessian)
+ *     log det A = 2 sum_i log Ls_ii + sum_i log A_ii
+ * factor: in place on d_A (M, P, ld), ld >= P.  Only the lower triangle is read; it becomes Ls.  The strict upper triangle
+ *   and the columns P .. ld-1 are neither read nor written.  d_scale (M, P) = sqrt(A_ii), d_logdet (M), d_info (M) int32:
+ *   0, or k + 1 for the first column k whose diagonal entry or pivot is non-finite or <= 0 -- then the lower triangle, the
+ *   scales and the log det of that row are NaN (the other rows are not affected).  One workgroup per matrix, blocked
+ *   right-looking in blocks of 32 columns (k_chol_factor: diagonal block in LDS, panel rows solved against it 128 at a
+ *   time, trailing 64 x 64 tiles updated); LDS holds the 32 x 32 diagonal block and 128 rows of the panel (42 KB) whatever
+ *   P is, so any P runs.  P^3 / 3 flops per matrix; the length of the recording does not enter.
+ * inverse: the lower triangle of every d_L (M, P, ld) becomes its inverse, in place, by blocked forward substitution
+ *   (k_tri_inverse; |L X - I| <= c P u |L| |X| componentwise, as a column-by-column substitution gives).  Rows with
+ *   d_info[m] != 0 are skipped (they stay NaN after a failed factor); the same parts stay untouched.  Meant for the
+ *   well-scaled Ls: the caller puts the scales back, (D^1/2 Ls)^-1 = Ls^-1 D^-1/2.
+ * Both are f64 throughout, sum in an order that depends on P alone (a row's bits do not depend on the batch it is in, two
+ * runs give the same bits), use no atomics and are asynchronous on the handle's stream.  M <= 0, P <= 0, ld < P or a null
+ * pointer: PGL_ERR_ARG.  The handle supplies device and stream only: no data set is needed. */
+int pgl_chol_factor_dev(pgl_handle h, double* d_A, int M, int P, int ld, double* d_scale, double* d_logdet, int* d_info);
+int pgl_tri_inverse_dev(pgl_handle h, double* d_L, int M, int P, int ld, const int* d_info);
+
 /* The lock-step optimiser (inference/batched_bfgs.py) as row kernels on the handle's stream.  The reference calls
  * scipy.optimize.minimize(method="bfgs") neuron by neuron (coord_descent.py:161-204); these run the same algorithm --
  * BFGS from H = I, More'-Thuente strong-Wolfe line search with scipy's constants and first trial step

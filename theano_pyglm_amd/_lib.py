@@ -44,6 +44,7 @@ SYMBOLS = [
     'pgl_ais_state_doubles', 'pgl_ais_init_dev', 'pgl_ais_start_dev', 'pgl_ais_temper_dev', 'pgl_ais_begin_dev',
     'pgl_ais_leap_dev',
     'pgl_hess_dev', 'pgl_hess',
+    'pgl_chol_factor_dev', 'pgl_tri_inverse_dev',
     'pgl_rescale_count', 'pgl_rescale_dev', 'pgl_rescale',
     'pgl_simulate_streams', 'pgl_simulate_batch', 'pgl_simulate_batch_dev', 'pgl_simulate_batch_plan',
 ]
@@ -140,6 +141,9 @@ def load():
     if hasattr(lib, 'pgl_hess'):
         lib.pgl_hess_dev.argtypes = [vp, vp, C.c_int]
         lib.pgl_hess.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
+    if hasattr(lib, 'pgl_chol_factor_dev'):                   # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
+        lib.pgl_chol_factor_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+        lib.pgl_tri_inverse_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
     if hasattr(lib, 'pgl_rescale'):
         lib.pgl_rescale_count.argtypes = [vp, vp]
         lib.pgl_rescale_dev.argtypes = [vp, vp, vp, vp, vp, vp]
@@ -519,6 +523,40 @@ class DeviceGlm(object):
         out = np.empty((npost, self.P, self.P))
         _chk(self.lib.pgl_hess(self.h, int(n_lo), int(n_hi), _ptr(th), _ptr(We), _ptr(out)))
         return out
+
+    # -- batched dense factorisation for the Laplace posterior (pgl_chol_factor_dev / pgl_tri_inverse_dev) --------
+    @staticmethod
+    def _stack(A, name):
+        import torch
+        if not (isinstance(A, torch.Tensor) and A.is_cuda and A.dtype == torch.float64 and A.dim() == 3 and
+                A.is_contiguous() and A.shape[0] > 0 and 0 < A.shape[1] <= A.shape[2]):
+            raise ValueError("%s: a contiguous float64 device tensor (M, P, ld), ld >= P" % name)
+        return torch
+
+    def chol_factor(self, A):
+        """In place on the torch device tensor A (M, P, ld) f64: the lower triangle of every matrix becomes the factor Ls of
+        its equilibrated form (pgl_chol_factor_dev).  Returns (scale (M, P), logdet (M,), info (M,) int32) on A's device.
+        Asynchronous on the handle's stream: the caller orders it against the stream that produced A."""
+        torch = self._stack(A, 'chol_factor')
+        M, P, ld = A.shape
+        scale = torch.empty((M, P), dtype=torch.float64, device=A.device)
+        logdet = torch.empty(M, dtype=torch.float64, device=A.device)
+        info = torch.empty(M, dtype=torch.int32, device=A.device)
+        _chk(self.lib.pgl_chol_factor_dev(self.h, C.c_void_p(A.data_ptr()), int(M), int(P), int(ld),
+                                          C.c_void_p(scale.data_ptr()), C.c_void_p(logdet.data_ptr()),
+                                          C.c_void_p(info.data_ptr())))
+        return scale, logdet, info
+
+    def tri_inverse(self, L, info):
+        """In place on the torch device tensor L (M, P, ld) f64: the lower triangle of every matrix becomes its inverse
+        (pgl_tri_inverse_dev); rows with info[m] != 0 (int32 device tensor, chol_factor's) are skipped.  Asynchronous."""
+        torch = self._stack(L, 'tri_inverse')
+        if not (isinstance(info, torch.Tensor) and info.is_cuda and info.dtype == torch.int32 and info.is_contiguous() and
+                tuple(info.shape) == (L.shape[0],)):
+            raise ValueError("tri_inverse: info must be a contiguous int32 device tensor (M,)")
+        M, P, ld = L.shape
+        _chk(self.lib.pgl_tri_inverse_dev(self.h, C.c_void_p(L.data_ptr()), int(M), int(P), int(ld),
+                                          C.c_void_p(info.data_ptr())))
 
     # -- time-rescaling goodness of fit (pgl_rescale*) ------------------------------
     def rescale_count(self):

@@ -2086,6 +2086,25 @@ int pgl_tri_matvec_dev(pgl_handle h, const double* d_W, int M, int P, int trans,
     return tri_launch(h, trans, PGL_TRI_STORE, d_W, M, P, d_x, d_y, nullptr, nullptr, 0.0);
 }
 
+// ---- batched dense factorisation for the Laplace posterior (pglm_chol.hip.h) ------------------------------------------
+int pgl_chol_factor_dev(pgl_handle h, double* d_A, int M, int P, int ld, double* d_scale, double* d_logdet, int* d_info)
+{
+    if (!h || !d_A || !d_scale || !d_logdet || !d_info || M <= 0 || P <= 0 || ld < P) return fail(PGL_ERR_ARG, "bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_chol_factor, dim3(M), dim3(256), 0, h->stream, d_A, P, ld, d_scale, d_logdet, d_info);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+int pgl_tri_inverse_dev(pgl_handle h, double* d_L, int M, int P, int ld, const int* d_info)
+{
+    if (!h || !d_L || !d_info || M <= 0 || P <= 0 || ld < P) return fail(PGL_ERR_ARG, "bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_tri_inverse, dim3(M), dim3(256), 0, h->stream, d_L, P, ld, d_info);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
 int pgl_hmc_dense_begin_dev(pgl_handle h, double* d_state, int M, int P, const double* d_W, double* d_work, double* d_Xt)
 {
     (void)d_work;

@@ -22,6 +22,8 @@
 // The dense Hessian H = F^T.diag(c).F is a contraction over time of its own (k_hess, pglm_hess.hip.h).
 // Posterior sampling runs HMC chains of all neurons in lock step around the ll+grad launch (k_hmc_*, pglm_hmc.hip.h).
 // A dense mass matrix adds two batched triangular matrix-vector products per leapfrog step (k_tri_matvec, pglm_hmc_dense.hip.h).
+// The Laplace posterior factors and inverts the dense Hessians in place, one workgroup per matrix (k_chol_factor, k_tri_inverse,
+// pglm_chol.hip.h).
 // The per-neuron evidence comes from annealed importance sampling on the same moves (k_ais_*, pglm_ais.hip.h).
 // The group-lasso MAP runs accelerated proximal gradient fits of all neurons in lock step around the same launch (k_prox_*,
 // pglm_prox.hip.h).
@@ -43,6 +45,7 @@
 #include "pglm_ncg.hip.h"
 #include "pglm_hmc.hip.h"
 #include "pglm_hmc_dense.hip.h"
+#include "pglm_chol.hip.h"
 #include "pglm_ais.hip.h"
 #include "pglm_prox.hip.h"
 #include "pglm_rescale.hip.h"

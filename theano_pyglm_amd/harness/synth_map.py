@@ -45,7 +45,7 @@ def initialize_test_harness(model_name, data, data_dir=None):
 
 
 def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False, gof=False, ppc=0, hmc=0, ais=0,
-                   hmc_mass='laplace', prox=False):
+                   hmc_mass='laplace', prox=False, laplace_device=False):
     """test/synth_map.py:10-32."""
     popn, popn_true, x_true = initialize_test_harness(model_name, data, data_dir)
     x0 = popn.sample(rng)
@@ -67,9 +67,9 @@ def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, r
         from theano_pyglm_amd.inference import predictive
         print(predictive.format_table(predictive.predictive_counts(popn, x_inf, ppc)))
     if hmc:
-        print(hmc_bias_table(popn, x_inf, hmc, hmc_mass))
+        print(hmc_bias_table(popn, x_inf, hmc, hmc_mass, laplace_device))
     if ais:
-        print(ais_evidence_table(popn, x_inf, ais))
+        print(ais_evidence_table(popn, x_inf, ais, laplace_device))
     return x_inf, ll_inf, wall
 
 
@@ -87,17 +87,19 @@ def prox_table(popn, x):
     return "\n".join(lines)
 
 
-def hmc_bias_table(popn, x, n_draws, mass='laplace'):
+def hmc_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False):
     """n_draws kept HMC draws from x with the mass matrix `mass` ('laplace' or 'laplace_dense'): one line per neuron, bias
-    posterior mean +- sd (and the Laplace standard error)."""
+    posterior mean +- sd (and the Laplace standard error).  laplace_device: the Laplace factorisations (the dense mass
+    matrix and the standard errors) run on the device."""
     from theano_pyglm_amd.inference import batched_hmc
     from theano_pyglm_amd.inference.laplace import laplace_glms
     t0 = time.time()
-    res = batched_hmc.sample_glms_hmc(popn, x, n_draws, mass=mass)
+    res = batched_hmc.sample_glms_hmc(popn, x, n_draws, mass=mass,
+                                      factor_on_device=laplace_device and mass == 'laplace_dense')
     wall = time.time() - t0
     s = batched_hmc.summarize(res['samples'][:, :, 0])
     try:
-        se = [r['stderr_vec'][0] if r['pd'] else float('nan') for r in laplace_glms(popn, x)]
+        se = [r['stderr_vec'][0] if r['pd'] else float('nan') for r in laplace_glms(popn, x, device=laplace_device)]
     except ValueError:
         se = None
     lines = ["HMC%s: %d draws per neuron in %.2f s (%d ll+grad launches)"
@@ -110,7 +112,7 @@ def hmc_bias_table(popn, x, n_draws, mass='laplace'):
     return "\n".join(lines)
 
 
-def ais_evidence_table(popn, x, n_particles):
+def ais_evidence_table(popn, x, n_particles, laplace_device=False):
     """AIS with n_particles particles per neuron from x: one line per neuron, log_Z + log_prior_norm +- se, the ESS and the
     Laplace log evidence (both under the host priors, which drop their normalising constants)."""
     from theano_pyglm_amd.inference import batched_ais
@@ -118,7 +120,7 @@ def ais_evidence_table(popn, x, n_particles):
     t0 = time.time()
     res = batched_ais.ais_glms(popn, x, n_particles=n_particles, mass='laplace')
     wall = time.time() - t0
-    lap = [r['log_evidence'] for r in laplace_glms(popn, x)]
+    lap = [r['log_evidence'] for r in laplace_glms(popn, x, device=laplace_device)]
     lines = ["AIS: %d particles per neuron, %d temperatures in %.2f s (%d ll+grad launches)"
              % (n_particles, len(res['betas']), wall, res['n_evals']),
              "neuron   log evidence +- se           ESS      Laplace"]
@@ -152,12 +154,15 @@ def main():
     ap.add_argument('--ais', type=int, default=0, metavar='K',
                     help='after the fit: log evidence of every neuron given the network by annealed importance sampling with '
                          'K particles on the device, beside the Laplace log evidence (Gaussian impulse priors only)')
+    ap.add_argument('--laplace-device', action='store_true',
+                    help='the Laplace factorisations behind --hmc (standard errors, and the factor of --hmc-mass laplace_dense) '
+                         'and --ais run on the device (batched Cholesky and triangular inverse) instead of on the host')
     args = ap.parse_args()
     with open(args.dataFile, 'rb') as f:
         data = pickle.load(f)
     run_synth_test(args.model, data, args.resultsDir, os.path.dirname(args.dataFile),
                    False if args.sequential else ('torch' if args.newton_cg else None), use_rop=args.newton_cg, gof=args.gof, ppc=args.ppc, hmc=args.hmc, ais=args.ais,
-                   hmc_mass=args.hmc_mass, prox=args.prox)
+                   hmc_mass=args.hmc_mass, prox=args.prox, laplace_device=args.laplace_device)
 
 
 if __name__ == '__main__':

@@ -19,7 +19,8 @@ component), documented in include/pyglm_hip.h, so a chain over a range of neuron
 all of them.
 
 The mass matrix is diagonal (mass=None, 'laplace' or an (M, P) array) or dense: mass='laplace_dense' or an (M, P, P)
-array of inverse mass matrices Sigma, factored on the host as Sigma = W W^T (factor_inverse_mass) and uploaded once.  The
+array of inverse mass matrices Sigma, factored on the host as Sigma = W W^T (factor_inverse_mass) and uploaded once (or, for
+'laplace_dense' with factor_on_device=True, built on the device).  The
 dense chain (csrc/pglm_hmc_dense.h) runs in the whitened momentum r = W^T p: a leapfrog step is the same evaluation plus
 two batched triangular matrix-vector products (pgl_hmc_dense_*), the draws, decisions and step-size rule unchanged.
 
@@ -49,9 +50,10 @@ def _check(population):
 
 def _theta_positions(population, x, n_lo, P):
     """Packed position of every theta column (the per-neuron packed vector and the theta row hold the same numbers)."""
-    from theano_pyglm_amd.utils.packvec import packdict, unpackdict, get_vars
-    _, shapes = packdict(get_vars(population.glm_syms(), x['glms'][n_lo]))
-    return np.rint(population.glm.theta_row(unpackdict(np.arange(P, dtype=float), shapes))).astype(int)
+    from theano_pyglm_amd.inference.laplace import theta_positions
+    pi, _ = theta_positions(population, x, n_lo)
+    assert pi.size == P
+    return pi
 
 
 def _minv_from_hessian(H, pi, floor):
@@ -125,8 +127,25 @@ def _laplace_dense_factor(population, x, n_lo, n_hi, floor):
     return W, dense
 
 
+def _laplace_dense_factor_device(population, x, n_lo, n_hi, floor):
+    """_laplace_dense_factor with the factorisation on the device (laplace.laplace_on_device: one batched Cholesky and one
+    triangular inverse give W directly, no covariance and no second factorisation): W stays there, a torch tensor (M, P, P)
+    in the theta layout, and only dense_rows (M,) comes back.  Rows that are not positive definite get the 'laplace' rule."""
+    import torch
+    from theano_pyglm_amd.inference.laplace import laplace_on_device
+    res, A, _, _ = laplace_on_device(population, x, n_lo, n_hi)
+    W = res['W']
+    dense = res['pd'] & torch.isfinite(W).all(dim=2).all(dim=1)
+    d = torch.diagonal(A, dim1=1, dim2=2)
+    d = torch.where(torch.isfinite(d), d, torch.full_like(d, floor))
+    dense_h = dense.cpu().numpy()
+    for m in np.flatnonzero(~dense_h):                         # (rare: the stack is touched only where a row failed)
+        W[m] = torch.diag(torch.sqrt(1.0 / torch.clamp(d[m], min=floor)))
+    return W, dense_h
+
+
 def sample_glms_hmc(population, x, n_samples, n_warmup=200, n_leapfrog=10, step_sz=0.1, thin=1, mass=None, seed=0,
-                    n_lo=0, n_hi=None, mass_floor=1e-8):
+                    n_lo=0, n_hi=None, mass_floor=1e-8, factor_on_device=False):
     """Posterior samples of the parameter rows of neurons [n_lo, n_hi) given the rest of x, started at x.
 
     n_warmup transitions adapt every row's step size and are dropped; then n_samples * thin transitions, every thin-th
@@ -135,6 +154,9 @@ def sample_glms_hmc(population, x, n_samples, n_warmup=200, n_leapfrog=10, step_
     (M, P) array of inverse masses in the theta layout, an (M, P, P) array of inverse mass MATRICES Sigma in the theta
     layout (finite, symmetric, positive definite: factor_inverse_mass) or 'laplace_dense' (Sigma = the Laplace covariance
     A^-1 of every neuron, laplace_glms' 'cov'; a neuron whose A is not positive definite runs on the 'laplace' rule).
+    factor_on_device: with 'laplace_dense', the factor W of the Laplace covariance is built on the device
+    (pgl_chol_factor_dev, pgl_tri_inverse_dev) and handed to the chain without a host copy; the default keeps the host
+    factorisation, and with it the draws of earlier versions (the two W agree to rounding, not to the bit).
     Returns {'samples': (n_samples, M, P) rows in the theta layout [bias, w_stim, w_ir], 'accept_rate': (M,) after
     warm-up, 'step_sz': (M,) the frozen step sizes, 'n_evals': ll+grad launches} and, with 'laplace_dense', 'dense_rows':
     (M,) bool, the rows that run on the full covariance.  x is not changed.
@@ -157,7 +179,8 @@ def sample_glms_hmc(population, x, n_samples, n_warmup=200, n_leapfrog=10, step_
         if mass == 'laplace':
             mass = _laplace_minv(population, x, n_lo, n_hi, float(mass_floor))
         elif mass == 'laplace_dense':
-            factor, dense_rows = _laplace_dense_factor(population, x, n_lo, n_hi, float(mass_floor))
+            build = _laplace_dense_factor_device if factor_on_device else _laplace_dense_factor
+            factor, dense_rows = build(population, x, n_lo, n_hi, float(mass_floor))
             mass = None
         else:
             raise ValueError("mass: None, 'laplace', 'laplace_dense', an (M, P) or an (M, P, P) array")
@@ -222,8 +245,8 @@ def _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, n_le
     minv_ptr = minv.data_ptr() if minv is not None else 0
     Wd = work = None
     if factor is not None:                                    # (M, P, P) lower-triangular factors: uploaded once
-        assert factor.shape == (M, P, P)
-        Wd = torch.tensor(factor, dtype=f64, device=dev)
+        assert tuple(factor.shape) == (M, P, P)
+        Wd = factor if torch.is_tensor(factor) else torch.tensor(factor, dtype=f64, device=dev)
         work = torch.empty(h0.hmc_dense_work_doubles(M, P), dtype=f64, device=dev)
     Xt = torch.empty((M, P), dtype=f64, device=dev)
     bufs = [torch.empty(M * (1 + P), dtype=f64, device=dev) for _ in handles]     # [ll | grad] per data sequence
