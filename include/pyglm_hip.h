@@ -455,6 +455,36 @@ int pgl_ais_leap_dev(pgl_handle h, double* d_state, int K, int M, int P, const d
                      const double* d_grad, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma,
                      double lam, int last, int adapt, double* d_Xt, double* d_acc_out, double* d_step_out);
 
+/* Annealed importance sampling with a DENSE mass matrix (inference/batched_ais.py: mass = (M, P, P) or 'laplace_dense';
+ * restated in csrc/pglm_ais_dense.h over csrc/pglm_ais.h and csrc/pglm_hmc_dense.h).  The inverse mass matrix of NEURON i is
+ * Sigma_i = W_i W_i^T, d_W (M, P, P) row-major with W_i lower triangular, shared by the K particles of the neuron; only the
+ * entries j <= i are ever read (the strict upper triangle may hold anything).  The run above goes on in the whitened
+ * momentum r = W^T p: the state block is pgl_ais_state_doubles(R, P) with r in the place of p; pgl_ais_init_dev, _start_dev
+ * and _temper_dev are used unchanged, and the random numbers, the target, the weights, the decision and the step-size rule
+ * are those above:
+ *     transition t:  r_j = z_j (the SAME draws as the diagonal run);  H0 = U_beta + 1/2 sum_j r_j^2;  r -= step/2 W^T grad U_beta;
+ *         n_leapfrog times { q += step W r;  r -= step W^T grad U_beta(q) (step/2 the last time) };  H1, the decision.
+ * With W = diag(sqrt(minv)) it is the diagonal run in exact arithmetic.  d_W may change between two transitions (a mass
+ * per temperature): a mass that does not depend on the particle's state keeps every transition valid for its target.
+ *   pgl_tri_matvec_shared_dev:  d_x, d_y (K M, P), particle-major; row r: d_y[r] = W_{r mod M} d_x[r] (trans == 0) or
+ *           W_{r mod M}^T d_x[r] (trans != 0); d_y != d_x.  One launch on a grid of (tiles of 64 outputs, neurons): a
+ *           workgroup produces its tile for all K particles from one read of its part of W (8 particles per pass; more are
+ *           further passes inside the workgroup, any K).  f64, no atomics; every output is summed in the order of
+ *           pgl_tri_matvec_dev, which depends on P alone: row (k, i) equals the one-row pgl_tri_matvec_dev call with W_i bit
+ *           for bit, for any K and M, and two calls give the same bits.
+ *   begin:  the momentum draw and H0, then the half kick and the first drift as epilogues of the two products: three
+ *           launches.  d_Xt (R, P) = the points to evaluate next.
+ *   leap:   (d_ll, d_grad) = the evaluation at d_Xt (left as they are).  last == 0: grad U_beta, then the kick and the next
+ *           drift inside the products: three launches.  last != 0: grad U_beta, the half kick, then H1, accept or reject, the
+ *           step-size rule if adapt, t += 1, d_acc_out and d_step_out as pgl_ais_leap_dev: three launches.
+ * One leapfrog step is K pgl_ll_grad_dev calls and 3 small launches, whatever K is; nothing is read back.  prior_kind 1
+ * returns PGL_ERR_UNSUPPORTED. */
+int pgl_tri_matvec_shared_dev(pgl_handle h, const double* d_W, int M, int K, int P, int trans, const double* d_x, double* d_y);
+int pgl_ais_dense_begin_dev(pgl_handle h, double* d_state, int K, int M, int P, const double* d_W, double* d_Xt);
+int pgl_ais_dense_leap_dev(pgl_handle h, double* d_state, int K, int M, int P, const double* d_W, const double* d_ll,
+                           const double* d_grad, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu,
+                           double sigma, double lam, int last, int adapt, double* d_Xt, double* d_acc_out, double* d_step_out);
+
 /* Lock-step accelerated proximal gradient for the group-lasso MAP (inference/batched_prox.py) as row kernels on the
  * handle's stream: the theta rows [bias, w_stim (Ds), w_ir (N groups of B)] of M neurons n_lo .. n_lo + M - 1 at once, one
  * workgroup per row around ONE pgl_ll_grad_dev over all rows per call.  The objective of a row is F = f + h,

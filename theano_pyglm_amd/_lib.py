@@ -43,6 +43,7 @@ SYMBOLS = [
     'pgl_prox_state_doubles', 'pgl_prox_init_dev', 'pgl_prox_step_dev',
     'pgl_ais_state_doubles', 'pgl_ais_init_dev', 'pgl_ais_start_dev', 'pgl_ais_temper_dev', 'pgl_ais_begin_dev',
     'pgl_ais_leap_dev',
+    'pgl_tri_matvec_shared_dev', 'pgl_ais_dense_begin_dev', 'pgl_ais_dense_leap_dev',
     'pgl_hess_dev', 'pgl_hess',
     'pgl_chol_factor_dev', 'pgl_tri_inverse_dev',
     'pgl_rescale_count', 'pgl_rescale_dev', 'pgl_rescale',
@@ -189,6 +190,11 @@ def load():
         lib.pgl_ais_temper_dev.argtypes = kmp + [C.c_int] + [C.c_double] * 6 + [C.c_double, vp]
         lib.pgl_ais_begin_dev.argtypes = kmp + [vp, vp]
         lib.pgl_ais_leap_dev.argtypes = kmp + [vp, vp, vp, C.c_int] + [C.c_double] * 6 + [C.c_int, C.c_int, vp, vp, vp]
+    if hasattr(lib, 'pgl_ais_dense_leap_dev'):                # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
+        lib.pgl_tri_matvec_shared_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+        lib.pgl_ais_dense_begin_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+        lib.pgl_ais_dense_leap_dev.argtypes = ([vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int] + [C.c_double] * 6 +
+                                               [C.c_int, C.c_int, vp, vp, vp])
     if hasattr(lib, 'pgl_prox_init_dev'):                     # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
         lib.pgl_prox_state_doubles.argtypes = [C.c_int, C.c_int]
         prox = [vp, vp, C.c_int, C.c_int, vp, vp] + [C.c_double] * 5 + [vp, C.c_double, C.c_int]
@@ -739,6 +745,23 @@ class DeviceGlm(object):
         _chk(self.lib.pgl_ais_leap_dev(self.h, C.c_void_p(d_state), int(K), int(M), int(P), vp(d_minv), C.c_void_p(d_ll),
                                        C.c_void_p(d_grad), int(prior[0]), *[float(z) for z in prior[1:]], 1 if last else 0,
                                        1 if adapt else 0, C.c_void_p(d_Xt), vp(d_acc_out), vp(d_step_out)))
+
+    # -- the same run with a dense mass matrix (pgl_ais_dense_*): d_W (M, P, P) lower-triangular factors of the inverse mass
+    # matrices, one per NEURON, shared by its K particles; d_x, d_y (K M, P) particle-major
+    def tri_matvec_shared_dev(self, d_W, M, K, P, trans, d_x, d_y):
+        _chk(self.lib.pgl_tri_matvec_shared_dev(self.h, C.c_void_p(d_W), int(M), int(K), int(P), 1 if trans else 0,
+                                                C.c_void_p(d_x), C.c_void_p(d_y)))
+
+    def ais_dense_begin_dev(self, d_state, K, M, P, d_W, d_Xt):
+        _chk(self.lib.pgl_ais_dense_begin_dev(self.h, C.c_void_p(d_state), int(K), int(M), int(P), C.c_void_p(d_W),
+                                              C.c_void_p(d_Xt)))
+
+    def ais_dense_leap_dev(self, d_state, K, M, P, d_W, d_ll, d_grad, prior, last, adapt, d_Xt, d_acc_out=0, d_step_out=0):
+        vp = lambda a: C.c_void_p(a) if a else None
+        _chk(self.lib.pgl_ais_dense_leap_dev(self.h, C.c_void_p(d_state), int(K), int(M), int(P), C.c_void_p(d_W),
+                                             C.c_void_p(d_ll), C.c_void_p(d_grad), int(prior[0]),
+                                             *[float(z) for z in prior[1:]], 1 if last else 0, 1 if adapt else 0,
+                                             C.c_void_p(d_Xt), vp(d_acc_out), vp(d_step_out)))
 
     def sync(self):
         _chk(self.lib.pgl_sync(self.h))

@@ -2224,6 +2224,75 @@ int pgl_ais_leap_dev(pgl_handle h, double* d_state, int K, int M, int P, const d
     return PGL_OK;
 }
 
+// ---- annealed importance sampling with a dense mass matrix (inference/batched_ais.py: mass = (M, P, P) or 'laplace_dense') ---
+// one shared product launch: the particles of a neuron meet the neuron's W in one workgroup, KC at a time
+static int tri_shared_launch(pgl_handle h, int trans, int epi, const double* d_W, int K, int M, int P, const double* d_x,
+                             double* d_y, double* d_Xt, const double* d_step, double scale)
+{
+    if (M > 65535) return fail(PGL_ERR_ARG, "at most 65535 neurons per call");
+    const dim3 grid((P + PGL_TRI_TILE - 1) / PGL_TRI_TILE, M);
+#define PGL_TRI_LAUNCH(T, E, KC) hipLaunchKernelGGL((k_tri_matvec_shared<T, E, KC>), grid, dim3(256), 0, h->stream, d_W, d_x, K, M, P, d_y, d_Xt, d_step, scale)
+#define PGL_TRI_LAUNCH_KC(KC)                                                  \
+    do {                                                                       \
+        if (epi == PGL_TRI_KICK) PGL_TRI_LAUNCH(1, PGL_TRI_KICK, KC);          \
+        else if (epi == PGL_TRI_DRIFT) PGL_TRI_LAUNCH(0, PGL_TRI_DRIFT, KC);   \
+        else if (trans) PGL_TRI_LAUNCH(1, PGL_TRI_STORE, KC);                  \
+        else PGL_TRI_LAUNCH(0, PGL_TRI_STORE, KC);                             \
+    } while (0)
+    if (K == 1) PGL_TRI_LAUNCH_KC(1);
+    else if (K == 2) PGL_TRI_LAUNCH_KC(2);
+    else if (K <= 4) PGL_TRI_LAUNCH_KC(4);
+    else PGL_TRI_LAUNCH_KC(PGL_TRI_SHARED_KC);
+#undef PGL_TRI_LAUNCH_KC
+#undef PGL_TRI_LAUNCH
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+int pgl_tri_matvec_shared_dev(pgl_handle h, const double* d_W, int M, int K, int P, int trans, const double* d_x, double* d_y)
+{
+    if (!h || !d_W || !d_x || !d_y || d_x == d_y || M <= 0 || K <= 0 || P <= 0 || (long long)K * M > 0x7fffffffLL)
+        return fail(PGL_ERR_ARG, "bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    return tri_shared_launch(h, trans, PGL_TRI_STORE, d_W, K, M, P, d_x, d_y, nullptr, nullptr, 0.0);
+}
+
+int pgl_ais_dense_begin_dev(pgl_handle h, double* d_state, int K, int M, int P, const double* d_W, double* d_Xt)
+{
+    if (!h || !d_state || !d_W || !d_Xt || K <= 0 || M <= 0 || P <= 0 || (long long)K * M > 0x7fffffffLL)
+        return fail(PGL_ERR_ARG, "bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    const AisView v = pgl_ais_view(d_state, K, M, P);
+    hipLaunchKernelGGL(k_ais_dense_draw, dim3(K * M), dim3(256), 0, h->stream, v);
+    HIPCHK(hipGetLastError());
+    const double* step = v.sc + (size_t)2 * v.R;
+    int rc = tri_shared_launch(h, 1, PGL_TRI_KICK, d_W, K, M, P, v.g, v.p, nullptr, step, 0.5);
+    if (rc) return rc;
+    return tri_shared_launch(h, 0, PGL_TRI_DRIFT, d_W, K, M, P, v.p, v.q, d_Xt, step, 1.0);
+}
+
+int pgl_ais_dense_leap_dev(pgl_handle h, double* d_state, int K, int M, int P, const double* d_W, const double* d_ll,
+                           const double* d_grad, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu,
+                           double sigma, double lam, int last, int adapt, double* d_Xt, double* d_acc_out, double* d_step_out)
+{
+    if (!h || !d_state || !d_W || !d_ll || !d_grad || !d_Xt) return fail(PGL_ERR_ARG, "bad argument");
+    BfgsPrior q;
+    int rc = ais_prior(h, K, M, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    const AisView v = pgl_ais_view(d_state, K, M, P);
+    hipLaunchKernelGGL(k_ais_dense_target, dim3(K * M), dim3(256), 0, h->stream, v, d_grad, q);
+    HIPCHK(hipGetLastError());
+    const double* step = v.sc + (size_t)2 * v.R;
+    rc = tri_shared_launch(h, 1, PGL_TRI_KICK, d_W, K, M, P, v.gu, v.p, nullptr, step, last ? 0.5 : 1.0);
+    if (rc) return rc;
+    if (!last) return tri_shared_launch(h, 0, PGL_TRI_DRIFT, d_W, K, M, P, v.p, v.q, d_Xt, step, 1.0);
+    hipLaunchKernelGGL(k_ais_dense_end, dim3(K * M), dim3(256), 0, h->stream, v, d_ll, d_grad, q, adapt ? 1 : 0, d_acc_out,
+                       d_step_out);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
 // ---- lock-step proximal gradient row kernels for the group-lasso MAP (inference/batched_prox.py) -------------------------
 long long pgl_prox_state_doubles(int M, int P) { return (long long)pgl_prox_doubles(M, P); }
 

@@ -45,7 +45,7 @@ def initialize_test_harness(model_name, data, data_dir=None):
 
 
 def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False, gof=False, ppc=0, hmc=0, ais=0,
-                   hmc_mass='laplace', prox=False, laplace_device=False):
+                   hmc_mass='laplace', prox=False, laplace_device=False, ais_mass='laplace'):
     """test/synth_map.py:10-32."""
     popn, popn_true, x_true = initialize_test_harness(model_name, data, data_dir)
     x0 = popn.sample(rng)
@@ -69,7 +69,7 @@ def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, r
     if hmc:
         print(hmc_bias_table(popn, x_inf, hmc, hmc_mass, laplace_device))
     if ais:
-        print(ais_evidence_table(popn, x_inf, ais, laplace_device))
+        print(ais_evidence_table(popn, x_inf, ais, laplace_device, ais_mass))
     return x_inf, ll_inf, wall
 
 
@@ -112,17 +112,18 @@ def hmc_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False):
     return "\n".join(lines)
 
 
-def ais_evidence_table(popn, x, n_particles, laplace_device=False):
+def ais_evidence_table(popn, x, n_particles, laplace_device=False, mass='laplace'):
     """AIS with n_particles particles per neuron from x: one line per neuron, log_Z + log_prior_norm +- se, the ESS and the
-    Laplace log evidence (both under the host priors, which drop their normalising constants)."""
+    Laplace log evidence (both under the host priors, which drop their normalising constants).  mass: 'none' (identity),
+    'laplace' or 'laplace_dense' (the tempered dense mass)."""
     from theano_pyglm_amd.inference import batched_ais
     from theano_pyglm_amd.inference.laplace import laplace_glms
     t0 = time.time()
-    res = batched_ais.ais_glms(popn, x, n_particles=n_particles, mass='laplace')
+    res = batched_ais.ais_glms(popn, x, n_particles=n_particles, mass=None if mass == 'none' else mass)
     wall = time.time() - t0
     lap = [r['log_evidence'] for r in laplace_glms(popn, x, device=laplace_device)]
-    lines = ["AIS: %d particles per neuron, %d temperatures in %.2f s (%d ll+grad launches)"
-             % (n_particles, len(res['betas']), wall, res['n_evals']),
+    lines = ["AIS%s: %d particles per neuron, %d temperatures in %.2f s (%d ll+grad launches)"
+             % ("" if mass == 'laplace' else " (mass=%s)" % mass, n_particles, len(res['betas']), wall, res['n_evals']),
              "neuron   log evidence +- se           ESS      Laplace"]
     for n in range(popn.N):
         lines.append("%6d  %13.4f +- %-9.4f %6.1f  %11.4f" % (n, res['log_Z'][n] + res['log_prior_norm'][n], res['log_Z_se'][n],
@@ -154,6 +155,9 @@ def main():
     ap.add_argument('--ais', type=int, default=0, metavar='K',
                     help='after the fit: log evidence of every neuron given the network by annealed importance sampling with '
                          'K particles on the device, beside the Laplace log evidence (Gaussian impulse priors only)')
+    ap.add_argument('--ais-mass', choices=['none', 'laplace', 'laplace_dense'], default='laplace',
+                    help="mass matrix of --ais: identity ('none'), 1 / diag A ('laplace') or the tempered dense mass, the factor "
+                         "of (beta G + Lambda)^-1 at every temperature ('laplace_dense')")
     ap.add_argument('--laplace-device', action='store_true',
                     help='the Laplace factorisations behind --hmc (standard errors, and the factor of --hmc-mass laplace_dense) '
                          'and --ais run on the device (batched Cholesky and triangular inverse) instead of on the host')
@@ -162,7 +166,7 @@ def main():
         data = pickle.load(f)
     run_synth_test(args.model, data, args.resultsDir, os.path.dirname(args.dataFile),
                    False if args.sequential else ('torch' if args.newton_cg else None), use_rop=args.newton_cg, gof=args.gof, ppc=args.ppc, hmc=args.hmc, ais=args.ais,
-                   hmc_mass=args.hmc_mass, prox=args.prox, laplace_device=args.laplace_device)
+                   hmc_mass=args.hmc_mass, prox=args.prox, laplace_device=args.laplace_device, ais_mass=args.ais_mass)
 
 
 if __name__ == '__main__':

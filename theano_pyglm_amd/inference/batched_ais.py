@@ -20,6 +20,16 @@ particle's own history is not.  So one pilot particle (a random stream of its ow
 ladder with the adapting rule of pgl_hmc_decide and its step after each temperature's moves is recorded per (temperature,
 neuron); the K particles then run frozen on that table, which moves device to device.
 
+The mass matrix of the moves is diagonal (mass=None, 'laplace' or an (M, P) array) or dense: an (M, P, P) array of fixed
+inverse mass matrices, or 'laplace_dense', the TEMPERED dense mass.  The target changes along the ladder -- the prior at
+beta = 0, the posterior at beta = 1 -- and a mass fitted to the posterior is far too narrow for the first temperatures.  The
+priors are Gaussian, so their precision Lambda is a known diagonal; with G = minus the Hessian of ll at x the Gaussian
+approximation of the target at beta has precision A_beta = beta G + Lambda, and every temperature runs on the lower factor
+W of A_beta^-1 (tempered_factor: one batched Cholesky factorisation and one triangular inverse on the device per
+temperature).  The dense transition (csrc/pglm_ais_dense.h) runs in the whitened momentum r = W^T p; its two triangular
+products per leapfrog step read a neuron's W once for all of the neuron's particles (pgl_tri_matvec_shared_dev).  A mass
+that depends on beta but not on the particle's state keeps every transition valid for its target: the weights stay valid.
+
 Served: the populations of batched_newton_cg.supported with Gaussian impulse priors (the start is an exact draw from the
 normalised prior, which only the Gaussian form gives in closed form).  Not served: group lasso, the 'st' and Dirichlet
 packings, time-sharded populations.
@@ -27,7 +37,7 @@ packings, time-sharded populations.
 import numpy as np
 
 from theano_pyglm_amd.inference.batched_bfgs import _Packing
-from theano_pyglm_amd.inference.batched_hmc import _check, _laplace_minv, _STREAMS
+from theano_pyglm_amd.inference.batched_hmc import _check, _laplace_minv, _STREAMS, factor_inverse_mass
 from theano_pyglm_amd.inference.batched_newton_cg import supported  # noqa: F401  (the served populations: these, Gaussian)
 
 # the state block (include/pyglm_hip.h): NVEC (R, P) arrays, then the rows of the scalar block (PglAis, csrc/pglm_ais.h)
@@ -76,24 +86,79 @@ def log_prior_norm(prm, N, B, Dstim):
             0.5 * (1 + Dstim + N * B) * np.log(2.0 * np.pi))
 
 
+def prior_precision(prm, N, B, Dstim):
+    """The diagonal of Lambda, the precision of the Gaussian priors, over a row [bias, w_stim (Dstim), w_ir (N, B)]: (P,).
+    prm: _Packing.prior_params()."""
+    _, _, sg_b, stim_sigma, _, sigma, _ = prm
+    sd = np.concatenate(([sg_b], np.full(Dstim, stim_sigma), np.full(N * B, sigma))).astype(float)
+    return 1.0 / (sd * sd)
+
+
+def tempered_factor(G, lam, beta, floor, factor, inverse, xp, eye):
+    """The factor of the tempered mass on any backend.  G (M, P, P): minus the Hessians of ll in the theta layout, lam (P,)
+    the diagonal of Lambda, eye the (P, P) identity (xp arrays: numpy, or torch tensors on the device); factor, inverse:
+    laplace_from_factor's.  A = beta G + Lambda; W (M, P, P) lower triangular with W W^T = A^-1 by the route of
+    laplace.laplace_from_factor (the index reversal, ONE factorisation, ONE triangular inverse, the scales put back).  A row
+    whose A does not factor (info != 0) gets W = diag(1 / sqrt(max(diag A, floor))), a non-finite diagonal entry counting as
+    floor: the 'laplace' rule.  Nothing is read back: the choice is made where the arrays live.  At beta = 0 A is the
+    diagonal Lambda and W = Lambda^-1/2 exactly: nothing is factored.
+    Returns (W, info (M,): 0 where A factored); the strict upper triangle of W is 0."""
+    from theano_pyglm_amd.inference.laplace import laplace_from_factor
+    if beta == 0.0:
+        return xp.zeros_like(G) + (1.0 / xp.sqrt(lam))[None, :, None] * eye[None], xp.zeros_like(lam[:1]).repeat(G.shape[0])
+    A = beta * G + lam[None, :, None] * eye[None]
+    res = laplace_from_factor(A, factor, inverse, xp)
+    d = beta * xp.diagonal(G, 0, 1, 2) + lam[None]
+    d = xp.where(xp.isfinite(d), d, xp.full_like(d, floor))
+    fb = 1.0 / xp.sqrt(xp.where(d > floor, d, xp.full_like(d, floor)))
+    bad = res['info'] != 0
+    return xp.where(bad[:, None, None], fb[:, :, None] * eye[None], res['W']), res['info']
+
+
+def _ll_hessians(population, torch, dev, handles, x, n_lo, n_hi, P):
+    """G (M, P, P) = minus the sum over the data sequences of the Hessian of ll at x, rows [n_lo, n_hi), on the device in
+    the theta layout -- computed as laplace.laplace_on_device computes it (hvp_prepare + hess per sequence, summed where
+    pgl_hess_dev leaves them).  Queued on the current stream; nothing is read back."""
+    f64 = torch.float64
+    M = n_hi - n_lo
+    theta = torch.tensor(population.theta_matrix(x, n_lo, n_hi), dtype=f64, device=dev)
+    Weff = torch.tensor(population.W_eff(x), dtype=f64, device=dev)
+    G = torch.zeros((M, P, P), dtype=f64, device=dev)
+    buf = torch.empty((M, P, P), dtype=f64, device=dev)
+    for h in handles:
+        h.hvp_prepare(theta.data_ptr(), Weff.data_ptr(), n_lo, n_hi)
+        h.hess(buf.data_ptr(), P)
+        G.sub_(buf)
+    return G
+
+
 def ais_glms(population, x, n_particles=16, betas=None, n_temps=200, n_steps=1, n_leapfrog=10, step_sz=0.1, pilot=True,
              mass=None, seed=0, particle0=0, n_lo=0, n_hi=None, mass_floor=1e-8):
     """log Z_n = log of the integral of L_n(theta) prior(theta) over the parameter row (bias, w_stim, w_ir) of every neuron
     of [n_lo, n_hi), given the network of x, under the NORMALISED Gaussian priors.
 
     betas: the ladder (starts at 0, ends at 1, increases); None: reference_ladder(n_temps).  At every temperature but the
-    last, n_steps HMC transitions of n_leapfrog steps.  mass: as sample_glms_hmc -- None, 'laplace' (evaluated at x) or an
-    (M, P) array of inverse masses; all particles of a neuron share it.  pilot: find the (J-1, M) step table with one
+    last, n_steps HMC transitions of n_leapfrog steps.  mass: as sample_glms_hmc -- None, 'laplace' (evaluated at x), an
+    (M, P) array of inverse masses, an (M, P, P) array of inverse mass MATRICES Sigma in the theta layout (finite, symmetric,
+    positive definite: factor_inverse_mass; the same at every temperature) or 'laplace_dense', the tempered dense mass:
+    at temperature beta_j the lower factor W_j of (beta_j G + Lambda)^-1, G = minus the Hessian of ll at x, Lambda the
+    priors' precision (tempered_factor).  A row whose matrix does not factor at a temperature runs there on the 'laplace'
+    rule, diag(1 / sqrt(max(diag, mass_floor))).  All particles of a neuron share the mass; the pilot uses the same W_j.
+    The W_j are RECOMPUTED for the main run, not kept from the pilot's: kept they are (J-1) M P^2 8 bytes (20 GB at N = 128,
+    P = 641 with 49 temperatures), recomputed they cost one factorisation and one inverse per temperature (about 15 ms
+    there, beside about a second of evaluations), and the same inputs give the same bits both times.  pilot: find the (J-1, M) step table with one
     adapting pilot particle started at step_sz (a number); False: step_sz, a number or a (J-1, M) table, is the table.
     Particles are numbered particle0 .. particle0 + n_particles - 1: runs with different ranges and the same seed are
     independent particles of one larger run.  x supplies the network (and the point of the Hessian for mass='laplace'); it
     is not changed.
 
     Returns a dict: 'log_Z' (M,), 'log_Z_se' (M,), 'ess' (M,) (weights_summary), 'log_weights' (K, M), 'samples'
-    (K, M, P) the final points, 'accept_rate' (J-1, M), 'step_sz' (J-1, M), 'betas', 'log_prior_norm' (M,) and 'n_evals'
-    (ll+grad launches).  The host priors -- and with them laplace_glms -- drop the priors' normalising constants: the number
+    (K, M, P) the final points, 'accept_rate' (J-1, M), 'step_sz' (J-1, M), 'betas', 'log_prior_norm' (M,), 'n_evals'
+    (ll+grad launches), 'mass' (the form used: 'identity', 'diagonal', 'dense' or 'laplace_dense') and, with
+    'laplace_dense', 'dense_rows' (J-1, M) bool: the rows that ran on the full factor at each temperature.  The host priors -- and with them laplace_glms -- drop the priors' normalising constants: the number
     comparable with laplace_glms' 'log_evidence' is log_Z + log_prior_norm.
-    population.last_fit_stats records the launch counts and the host synchronisations inside the run (none)."""
+    population.last_fit_stats records the launch counts -- with a dense mass also 'factorisations' (tempered_factor calls)
+    and 'product_launches' (pgl_tri_matvec_shared launches) -- and the host synchronisations inside the run (none)."""
     _check(population)
     K, n_steps, n_leapfrog = int(n_particles), int(n_steps), int(n_leapfrog)
     if K <= 0 or n_steps <= 0 or n_leapfrog <= 0 or int(particle0) < 0:
@@ -108,10 +173,19 @@ def ais_glms(population, x, n_particles=16, betas=None, n_temps=200, n_steps=1, 
     if _Packing(population, None).prior_params()[0] != 0:
         raise ValueError("annealed importance sampling starts from an exact prior draw: Gaussian impulse priors only "
                          "(group lasso is not served)")
+    factor = None
     if isinstance(mass, str):
-        if mass != 'laplace':
-            raise ValueError("mass: None, 'laplace' or an (M, P) array")
-        mass = _laplace_minv(population, x, n_lo, n_hi, float(mass_floor))
+        if mass == 'laplace':
+            mass = _laplace_minv(population, x, n_lo, n_hi, float(mass_floor))
+        elif mass == 'laplace_dense':
+            factor, mass = 'tempered', None
+        else:
+            raise ValueError("mass: None, 'laplace', 'laplace_dense', an (M, P) or an (M, P, P) array")
+    elif mass is not None and np.ndim(mass) == 3:
+        P = population.glm.P
+        if np.shape(mass) != (M, P, P):
+            raise ValueError("mass: an (M, P, P) = (%d, %d, %d) array of inverse mass matrices" % (M, P, P))
+        factor, mass = factor_inverse_mass(mass), None
     dev = torch.device('cuda', population.device)
     handles = []
     for data in population.data_sequences:
@@ -126,7 +200,7 @@ def ais_glms(population, x, n_particles=16, betas=None, n_temps=200, n_steps=1, 
     try:
         with torch.cuda.stream(stream):
             out = _run(population, torch, dev, stream, handles, x, K, betas, n_steps, n_leapfrog, step_sz, bool(pilot), mass,
-                       int(seed), int(particle0), n_lo, n_hi, M)
+                       int(seed), int(particle0), n_lo, n_hi, M, factor, float(mass_floor))
     finally:
         try:
             stream.synchronize()
@@ -138,7 +212,7 @@ def ais_glms(population, x, n_particles=16, betas=None, n_temps=200, n_steps=1, 
 
 
 def _run(population, torch, dev, stream, handles, x, K, betas, n_steps, n_leapfrog, step_sz, pilot, mass, seed, particle0,
-         n_lo, n_hi, M):
+         n_lo, n_hi, M, factor=None, mass_floor=1e-8):
     pk = _Packing(population, torch, handles, (n_lo, n_hi))
     assert pk.identity                                        # (hvp_packing() is None: the row IS the theta row)
     h0 = handles[0]
@@ -163,11 +237,39 @@ def _run(population, torch, dev, stream, handles, x, K, betas, n_steps, n_leapfr
         table = torch.tensor(th, dtype=f64, device=dev)
     if not step0 > 0.0 or (table is not None and not bool(np.all(th > 0.0))):
         raise ValueError("step_sz must be positive")
-    counts = {'ll_grad': 0, 'row': 0, 'syncs': 0}
+    counts = {'ll_grad': 0, 'row': 0, 'syncs': 0, 'factor': 0, 'product': 0}
 
     def wait():
         counts['syncs'] += 1
         stream.synchronize()
+
+    # the dense forms: factor_at(j) -> W (M, P, P) on the device for the moves at betas[j] (None: the diagonal forms)
+    factor_at = dense_rows = None
+    if isinstance(factor, str):                               # 'laplace_dense': one factor per temperature, recomputed per run
+        G = _ll_hessians(population, torch, dev, handles, x, n_lo, n_hi, P)
+        lam = torch.tensor(prior_precision(prm, population.N, pk.B, pk.nbk), dtype=f64, device=dev)
+        eye = torch.eye(P, dtype=f64, device=dev)
+        dense_rows = torch.zeros((max(J - 1, 1), M), dtype=torch.bool, device=dev)
+
+        def chol(Ar):
+            Ar = Ar.contiguous()
+            return (Ar,) + h0.chol_factor(Ar)
+
+        def tri_inv(Ls, info):
+            h0.tri_inverse(Ls, info)
+            return Ls
+
+        def factor_at(j):
+            W, info = tempered_factor(G, lam, float(betas[j]), mass_floor, chol, tri_inv, torch, eye)
+            dense_rows[j - 1] = info == 0
+            counts['factor'] += 1
+            return W.contiguous()
+    elif factor is not None:                                  # (M, P, P) lower-triangular factors: uploaded once
+        assert tuple(factor.shape) == (M, P, P)
+        Wfix = torch.tensor(factor, dtype=f64, device=dev)
+
+        def factor_at(j):
+            return Wfix
 
     def ladder(Kr, part0, adapt, table):
         """One run of Kr particles over the whole ladder -> (state block, accept counts (J-1, R), steps (J-1, R) or None)."""
@@ -198,13 +300,25 @@ def _run(population, torch, dev, stream, handles, x, K, betas, n_steps, n_leapfr
             counts['row'] += 1
             if j == J:
                 break
+            Wj = factor_at(j) if factor_at is not None else None
             for _ in range(n_steps):
-                h0.ais_begin_dev(sp, Kr, M, P, minv_ptr, Xt.data_ptr())
+                if Wj is not None:
+                    h0.ais_dense_begin_dev(sp, Kr, M, P, Wj.data_ptr(), Xt.data_ptr())
+                else:
+                    h0.ais_begin_dev(sp, Kr, M, P, minv_ptr, Xt.data_ptr())
                 for i in range(n_leapfrog):
                     ll, g = evaluate()
-                    h0.ais_leap_dev(sp, Kr, M, P, minv_ptr, ll, g, prm, i == n_leapfrog - 1, adapt, Xt.data_ptr(),
-                                    acc[j - 1].data_ptr(), steps[j - 1].data_ptr() if adapt else 0)
+                    if Wj is not None:
+                        h0.ais_dense_leap_dev(sp, Kr, M, P, Wj.data_ptr(), ll, g, prm, i == n_leapfrog - 1, adapt,
+                                              Xt.data_ptr(), acc[j - 1].data_ptr(), steps[j - 1].data_ptr() if adapt else 0)
+                    else:
+                        h0.ais_leap_dev(sp, Kr, M, P, minv_ptr, ll, g, prm, i == n_leapfrog - 1, adapt, Xt.data_ptr(),
+                                        acc[j - 1].data_ptr(), steps[j - 1].data_ptr() if adapt else 0)
+                # ('row' counts the begin / leap CALLS of the C ABI; a dense call is three small launches, two of them
+                # products but for the last leap's one; a diagonal call is one launch)
                 counts['row'] += 1 + n_leapfrog
+                if Wj is not None:
+                    counts['product'] += 2 * n_leapfrog + 1
         return st, acc, steps
 
     if pilot and J > 1:
@@ -221,8 +335,13 @@ def _run(population, torch, dev, stream, handles, x, K, betas, n_steps, n_leapfr
            'samples': st[:R * P].view(K, M, P).cpu().numpy(),
            'accept_rate': acc[:J - 1].view(J - 1, K, M).sum(dim=1).cpu().numpy() / float(K * n_steps),
            'step_sz': table.cpu().numpy() if J > 1 else np.zeros((0, M)), 'betas': betas,
-           'log_prior_norm': np.full(M, log_prior_norm(prm, population.N, pk.B, Dstim)), 'n_evals': counts['ll_grad']}
+           'log_prior_norm': np.full(M, log_prior_norm(prm, population.N, pk.B, Dstim)), 'n_evals': counts['ll_grad'],
+           'mass': ('laplace_dense' if isinstance(factor, str) else 'dense') if factor is not None else
+                   ('diagonal' if minv is not None else 'identity')}
+    if dense_rows is not None:
+        out['dense_rows'] = dense_rows[:J - 1].cpu().numpy()
     population.last_fit_stats = {'sampler': 'annealed importance sampling (hip row kernels)', 'particles': K, 'pilot': int(pilot and J > 1),
                                  'temperatures': J, 'll_grad_launches': counts['ll_grad'], 'row_launches': counts['row'],
+                                 'mass': out['mass'], 'factorisations': counts['factor'], 'product_launches': counts['product'],
                                  'host_syncs_in_run': syncs_in_run, 'host_syncs': counts['syncs']}
     return out

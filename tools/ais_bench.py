@@ -3,7 +3,7 @@ Seeded inputs as tools/ncg_bench.py makes them (Poisson spikes at 20 Hz), standa
 the Gaussian N(0, 1) -- the template's group lasso is not served: AIS starts from an exact prior draw -- started at the
 lock-step BFGS MAP fit, Laplace mass.
 
-    python tools/ais_bench.py [--configs C2,C3] [--out profiles/ais_bench.json]
+    python tools/ais_bench.py [--configs C2,C3] [--mass laplace,laplace_dense] [--out profiles/ais_bench.json]
 
 C2: N = 32, nT = 300 000; C3: N = 128, nT = 600 000.  Per configuration:
   run_s            wall time of ais_glms (K particles and the pilot; the mass is computed before, outside the clock)
@@ -11,6 +11,10 @@ C2: N = 32, nT = 300 000; C3: N = 128, nT = 600 000.  Per configuration:
   run_over_floor   their ratio
   row_s            the row launches of the same run alone (every pgl_ais_* launch, no evaluation in between)
   neurons          per neuron: log_Z + log_prior_norm, its standard error, the ESS and the Laplace log evidence
+  mass             with --mass laplace,laplace_dense: the same fit, seed, ladder, K and n_leapfrog under both masses in this
+                   process -- per mass: wall time, launches, the ratio to the floor, accept rate and median step per
+                   temperature, median ESS and standard error, AIS minus Laplace; for the dense mass also the seconds of
+                   its factorisations and of its product launches alone, and dense_over_laplace, the ratio of the two runs
 Records, sets no threshold.  Prints one JSON line."""
 import argparse, json, os, sys, time
 import numpy as np
@@ -73,7 +77,72 @@ def row_launches_alone(popn, K, M, P, prm, betas, n_steps, n_leapfrog, with_pilo
         h.set_stream(None)
 
 
-def run(name, K, n_temps, n_steps, n_leapfrog):
+def summary(res, lap, N):
+    """What a run says about the evidence: per-temperature accept rate and median step, ESS, standard error, AIS - Laplace."""
+    fin = lambda v: float(v) if np.isfinite(v) else None
+    d = np.array([res['log_Z'][n] + res['log_prior_norm'][n] - lap[n]['log_evidence'] for n in range(N)])
+    ok = np.isfinite(d)
+    return {'accept_rate_per_temperature': [float(v) for v in res['accept_rate'].mean(axis=1)],
+            'step_median_per_temperature': [float(v) for v in np.median(res['step_sz'], axis=1)],
+            'accept_rate': {'min': float(res['accept_rate'].min()), 'mean': float(res['accept_rate'].mean())},
+            'ess_median': float(np.median(res['ess'])), 'ess_min': float(np.min(res['ess'])), 'ess_max': float(np.max(res['ess'])),
+            'se_median': fin(np.nanmedian(res['log_Z_se'])),
+            'ais_minus_laplace': {'rows': int(ok.sum()), 'min': fin(np.min(d[ok])) if ok.any() else None,
+                                  'median': fin(np.median(d[ok])) if ok.any() else None,
+                                  'max': fin(np.max(d[ok])) if ok.any() else None}}
+
+
+def dense_parts_alone(popn, x, K, N, P, betas, st):
+    """Seconds of the dense run's own work alone: its factorisations (tempered_factor, as many as the run made) and its
+    product launches (pgl_tri_matvec_shared_dev, half of them with the pilot's one particle, half with K)."""
+    import torch
+    from theano_pyglm_amd.inference import batched_ais as BA
+    from theano_pyglm_amd.inference.batched_bfgs import _Packing
+    h = popn._handle(popn.data_sequences[0])
+    dev = torch.device('cuda', popn.device)
+    f64 = torch.float64
+    stream = torch.cuda.Stream(dev)
+    h.set_stream(stream.cuda_stream)
+    try:
+        with torch.cuda.stream(stream):
+            pk = _Packing(popn, torch, [h], (0, N))
+            t0 = time.perf_counter()
+            G = BA._ll_hessians(popn, torch, dev, [h], x, 0, N, P)
+            stream.synchronize()
+            hess_s = time.perf_counter() - t0
+            lam = torch.tensor(BA.prior_precision(pk.prior_params(), N, pk.B, pk.nbk), dtype=f64, device=dev)
+            eye = torch.eye(P, dtype=f64, device=dev)
+
+            def chol(Ar):
+                Ar = Ar.contiguous()
+                return (Ar,) + h.chol_factor(Ar)
+
+            def tri_inv(Ls, info):
+                h.tri_inverse(Ls, info)
+                return Ls
+            W = None
+            for timed in (False, True):                         # (once to warm the allocator, then the clock)
+                stream.synchronize()
+                t0 = time.perf_counter()
+                for i in range(st['factorisations'] if timed else 1):
+                    W, _ = BA.tempered_factor(G, lam, float(betas[1 + i % (len(betas) - 2)]), 1e-8, chol, tri_inv, torch, eye)
+                stream.synchronize()
+                factor_s = time.perf_counter() - t0
+            xs = torch.randn((K * N, P), dtype=f64, device=dev)
+            ys = torch.empty((K * N, P), dtype=f64, device=dev)
+            half = st['product_launches'] // 2
+            stream.synchronize()
+            t0 = time.perf_counter()
+            for Kr in (1, K):
+                for i in range(half):
+                    h.tri_matvec_shared_dev(W.data_ptr(), N, Kr, P, i & 1, xs.data_ptr(), ys.data_ptr())
+            stream.synchronize()
+            return {'hessian_s': hess_s, 'factor_s': factor_s, 'product_s': time.perf_counter() - t0}
+    finally:
+        h.set_stream(None)
+
+
+def run(name, K, n_temps, n_steps, n_leapfrog, masses=('laplace',)):
     import torch
     from theano_pyglm_amd.inference.batched_ais import ais_glms, reference_ladder
     from theano_pyglm_amd.inference.batched_bfgs import fit_glms_batched_torch, _Packing
@@ -121,6 +190,24 @@ def run(name, K, n_temps, n_steps, n_leapfrog):
                       'max': float(res['step_sz'].max())}
     lap = laplace_glms(popn, x)
     fin = lambda v: float(v) if np.isfinite(v) else None
+    if 'laplace_dense' in masses:
+        cmp_ = {'laplace': dict(summary(res, lap, N), run_s=out['run_s'], run_over_floor=out['run_over_floor'],
+                                launches=out['launches'])}
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rd = ais_glms(popn, x, n_particles=K, betas=betas, n_steps=n_steps, n_leapfrog=n_leapfrog, step_sz=0.1,
+                      mass='laplace_dense', seed=1)
+        run_s = time.perf_counter() - t0                        # (the Hessians of ll are inside this clock)
+        sd = popn.last_fit_stats
+        assert sd['ll_grad_launches'] == st['ll_grad_launches']
+        dense = dict(summary(rd, lap, N), run_s=run_s, run_over_floor=run_s / out['floor_s'],
+                     launches={k: sd[k] for k in ('ll_grad_launches', 'row_launches', 'factorisations', 'product_launches',
+                                                  'host_syncs_in_run')},
+                     dense_rows_share=float(rd['dense_rows'].mean()))
+        dense.update(dense_parts_alone(popn, x, K, N, P, betas, sd))
+        cmp_['laplace_dense'] = dense
+        cmp_['dense_over_laplace'] = run_s / out['run_s']
+        out['mass'] = cmp_
     out['neurons'] = [{'n': n, 'ais_log_evidence': fin(res['log_Z'][n] + res['log_prior_norm'][n]), 'se': fin(res['log_Z_se'][n]),
                        'ess': fin(res['ess'][n]), 'laplace_log_evidence': fin(lap[n]['log_evidence'])} for n in range(N)]
     d = np.array([(r['ais_log_evidence'] - r['laplace_log_evidence']) if None not in (r['ais_log_evidence'], r['laplace_log_evidence'])
@@ -141,11 +228,16 @@ if __name__ == '__main__':
     ap.add_argument('--temps', type=int, default=50)
     ap.add_argument('--steps', type=int, default=1)
     ap.add_argument('--leapfrog', type=int, default=10)
+    ap.add_argument('--mass', default='laplace', help="laplace (the record as it was) or laplace,laplace_dense (adds the "
+                    "comparison under the key 'mass')")
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
+    masses = tuple(a.mass.split(','))
+    if 'laplace' not in masses or not set(masses) <= {'laplace', 'laplace_dense'}:
+        ap.error("--mass: laplace or laplace,laplace_dense")
     res = {'bench': 'ais'}
     for name in a.configs.split(','):
-        res[name] = run(name, a.particles, a.temps, a.steps, a.leapfrog)
+        res[name] = run(name, a.particles, a.temps, a.steps, a.leapfrog, masses)
     line = json.dumps(res, sort_keys=True)
     print(line)
     if a.out:
