@@ -405,6 +405,58 @@ int pgl_hmc_dense_leap_dev(pgl_handle h, double* d_state, int M, int P, const do
                            double* d_grad, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu,
                            double sigma, double lam, int last, int n_warmup, double* d_Xt, double* d_sample_out);
 
+/* The No-U-Turn sampler for the same posteriors (inference/batched_nuts.py; the transition is restated in
+ * csrc/pglm_nuts.h and, with its leaves in a list, in inference/nuts.py), as row kernels on the handle's stream: one
+ * workgroup per neuron row, ONE pgl_ll_grad_dev of all rows per leapfrog step, and rows that do not wait for each other.
+ * Multinomial NUTS (Hoffman & Gelman 2014; Betancourt 2017) in the whitened momentum r = W^T p, K = 1/2 sum r_j^2, the
+ * inverse mass matrix of row m being W_m W_m^T:  d_W (M, P, P) lower triangular (only j <= i is read), or d_W NULL and
+ * d_minv (M, P) (W = diag(sqrt(minv)), applied inside the row kernel), or both NULL (identity).
+ *   target      U, its gradient, the priors and the non-finite rules of pgl_hmc_leap_dev.
+ *   leapfrog    from an edge (q, r, h = W^T grad U(q)) in direction v:  r' = r - v eps/2 h;  q' = q + v eps W r';  one
+ *               evaluation;  h' = W^T grad U(q');  r'' = r' - v eps/2 h'.  Every edge keeps (q, r, h): no second product.
+ *   tree        doubling d = 0, 1, ... < max_depth (at most 10) draws a direction and builds 2^d leaves from that edge.
+ *               The U-turn test  rho . r_first > 0 and rho . r_last > 0  (rho: the sum of r over the block; Euclidean in
+ *               these coordinates) is applied to every aligned block of 2^k leaves of the new subtree, k >= 1, as soon as
+ *               its last leaf exists, and to the whole tree after a merge; nothing else is cross-checked.  A U-turn or a
+ *               divergence inside the new subtree discards the subtree and ends the transition; a U-turn of the merged
+ *               tree or d + 1 = max_depth ends it after the merge.  'depth' counts the doublings begun.
+ *   divergence  a leaf with non-finite H, or H - H0 > 1000: weight 0, and the transition is counted (t >= n_warmup).
+ *   proposal    log weights H0 - H.  Leaf i of a subtree replaces the subtree's candidate iff i = 0 or
+ *               log u < log w_i - log sum_{k<=i} w_k;  at a merge the subtree's candidate replaces the tree's iff
+ *               log u < log w_subtree - log w_tree.
+ *   storage     O(max_depth) vectors per row: an even leaf i checkpoints (r_i, the subtree's running rho before it) in
+ *               slot popcount(i); the odd leaf i reads slot popcount(i) - k for each of its k = 1 .. trailing one bits.
+ *               The candidate keeps (q, U, grad U, h): a new transition needs no evaluation.
+ *   statistic   the mean over all leaves built in the transition of min(1, exp(H0 - H)), 0 for a divergent leaf.
+ *   step size   per row, dual averaging (Hoffman & Gelman 2014, alg. 5) with delta = target_accept, gamma = 0.05, t0 = 10,
+ *               kappa = 0.75, mu = log(10 step0), clipped to [1e-4, 10]; at t = n_warmup frozen at exp(log eps bar).
+ *   random numbers  stateless: pgl_hmc's key (seed, neuron index, transition) and uniforms.  z_j: counters 2 j + 1,
+ *               2 j + 2 (the momentum of the HMC chain);  direction of doubling d: 2 P + 1 + d (forward iff u < 1/2);
+ *               merge uniform of doubling d: 2 P + 17 + d;  selection uniform of leaf i of doubling d:
+ *               2 P + 33 + (2^d - 1 + i).  A chain over [n_lo, n_hi) equals the matching rows of a chain over all neurons.
+ * d_state: pgl_nuts_state_doubles(M, P, max_depth) doubles = 17 + 2 max_depth (M, P) arrays -- the first is the rows'
+ * current point -- then 30 (M) arrays of scalars, field-major (PglNuts of csrc/pglm_nuts.h: 2 step, 3 t, 7 done,
+ * 21 leapfrog steps so far, 22 divergent transitions and 23 the sum of the statistic with t >= n_warmup, 24 - 28 depth,
+ * leaves, stop reason (1 block U-turn, 2 tree U-turn, 3 max_depth, 4 divergence), selected leaf and statistic of the last
+ * transition).  Every row runs n_warmup + n_keep thin transitions, counts its own t, writes its kept points into
+ * d_samples (n_keep, M, P) and (depth, leapfrog steps) of the kept transitions into d_stats (n_keep, 2, M) (either may
+ * be NULL), then sets done and idles with its d_Xt row left at its current point.
+ *   pgl_nuts_init_dev:  the rows' points are the first array of d_state; d_ll (M), d_grad (M, P) hold ll and its gradient
+ *           there (overwritten).  d_step0 (M): the starting steps.  Draws the first momentum; d_Xt = the first points to
+ *           evaluate.  1 launch (diagonal), 4 (dense).
+ *   pgl_nuts_step_dev:  after one evaluation of all rows at d_Xt: one leapfrog step of every row that is not done and
+ *           d_Xt = the next points.  1 launch (diagonal); dense: 2 small launches and 2 products (pgl_tri_matvec_dev's
+ *           kernel, the drift its epilogue). */
+long long pgl_nuts_state_doubles(int M, int P, int max_depth);
+int pgl_nuts_init_dev(pgl_handle h, double* d_state, int M, int P, int max_depth, int n_lo, double* d_ll, double* d_grad,
+                      int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam,
+                      const double* d_minv, const double* d_W, const double* d_step0, uint64_t seed, int n_warmup, int thin,
+                      int n_keep, double* d_Xt);
+int pgl_nuts_step_dev(pgl_handle h, double* d_state, int M, int P, int max_depth, double* d_ll, double* d_grad,
+                      int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam,
+                      const double* d_minv, const double* d_W, double target_accept, int n_warmup, int thin, int n_keep,
+                      double* d_Xt, double* d_samples, double* d_stats);
+
 /* Annealed importance sampling (Neal 2001; inference/batched_ais.py) of the evidence log Z_n of every neuron given the
  * network, as row kernels on the handle's stream, on top of the HMC moves above (restated nowhere: csrc/pglm_ais.h uses
  * csrc/pglm_hmc.h).  The run covers R = K M rows: K particles of the M neurons n_lo .. n_lo + M - 1, particle-major -- row

@@ -40,6 +40,7 @@ SYMBOLS = [
     'pgl_ncg_state_doubles', 'pgl_ncg_init_dev', 'pgl_ncg_cg_step_dev', 'pgl_ncg_trial_dev', 'pgl_ncg_search_step_dev',
     'pgl_hmc_state_doubles', 'pgl_hmc_init_dev', 'pgl_hmc_begin_dev', 'pgl_hmc_leap_dev',
     'pgl_hmc_dense_work_doubles', 'pgl_tri_matvec_dev', 'pgl_hmc_dense_begin_dev', 'pgl_hmc_dense_leap_dev',
+    'pgl_nuts_state_doubles', 'pgl_nuts_init_dev', 'pgl_nuts_step_dev',
     'pgl_prox_state_doubles', 'pgl_prox_init_dev', 'pgl_prox_step_dev',
     'pgl_ais_state_doubles', 'pgl_ais_init_dev', 'pgl_ais_start_dev', 'pgl_ais_temper_dev', 'pgl_ais_begin_dev',
     'pgl_ais_leap_dev',
@@ -182,6 +183,12 @@ def load():
         lib.pgl_hmc_dense_begin_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
         lib.pgl_hmc_dense_leap_dev.argtypes = ([vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int] + [C.c_double] * 6 +
                                                [C.c_int, C.c_int, vp, vp])
+    if hasattr(lib, 'pgl_nuts_step_dev'):                     # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
+        lib.pgl_nuts_state_doubles.argtypes = [C.c_int, C.c_int, C.c_int]
+        lib.pgl_nuts_init_dev.argtypes = ([vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int] + [C.c_double] * 6 +
+                                          [vp, vp, vp, C.c_uint64, C.c_int, C.c_int, C.c_int, vp])
+        lib.pgl_nuts_step_dev.argtypes = ([vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int] + [C.c_double] * 6 +
+                                          [vp, vp, C.c_double, C.c_int, C.c_int, C.c_int, vp, vp, vp])
     if hasattr(lib, 'pgl_ais_init_dev'):                      # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
         lib.pgl_ais_state_doubles.argtypes = [C.c_int, C.c_int]
         kmp = [vp, vp, C.c_int, C.c_int, C.c_int]
@@ -233,7 +240,7 @@ def load():
             continue
         fn = getattr(lib, name)
         if name in ('pgl_bfgs_state_doubles', 'pgl_ncg_state_doubles', 'pgl_hmc_state_doubles', 'pgl_ais_state_doubles',
-                    'pgl_hmc_dense_work_doubles', 'pgl_prox_state_doubles'):
+                    'pgl_hmc_dense_work_doubles', 'pgl_prox_state_doubles', 'pgl_nuts_state_doubles'):
             fn.restype = C.c_longlong
         elif name not in ('pgl_last_error',):
             fn.restype = C.c_int
@@ -682,6 +689,27 @@ class DeviceGlm(object):
                                        C.c_void_p(d_ll), C.c_void_p(d_grad), int(prior[0]), *[float(z) for z in prior[1:]],
                                        1 if last else 0, int(n_warmup), C.c_void_p(d_Xt),
                                        C.c_void_p(d_sample_out) if d_sample_out else None))
+
+    # -- NUTS row kernels (pgl_nuts_*; inference/batched_nuts.py).  d_minv (M, P) or d_W (M, P, P) or neither; device pointers
+    def nuts_state_doubles(self, M, P, max_depth):
+        return int(self.lib.pgl_nuts_state_doubles(int(M), int(P), int(max_depth)))
+
+    def nuts_init_dev(self, d_state, M, P, max_depth, n_lo, d_ll, d_grad, prior, d_minv, d_W, d_step0, seed, n_warmup, thin,
+                      n_keep, d_Xt):
+        _chk(self.lib.pgl_nuts_init_dev(self.h, C.c_void_p(d_state), int(M), int(P), int(max_depth), int(n_lo),
+                                        C.c_void_p(d_ll), C.c_void_p(d_grad), int(prior[0]), *[float(z) for z in prior[1:]],
+                                        C.c_void_p(d_minv) if d_minv else None, C.c_void_p(d_W) if d_W else None,
+                                        C.c_void_p(d_step0), int(seed) & 0xffffffffffffffff, int(n_warmup), int(thin),
+                                        int(n_keep), C.c_void_p(d_Xt)))
+
+    def nuts_step_dev(self, d_state, M, P, max_depth, d_ll, d_grad, prior, d_minv, d_W, target_accept, n_warmup, thin, n_keep,
+                      d_Xt, d_samples=0, d_stats=0):
+        _chk(self.lib.pgl_nuts_step_dev(self.h, C.c_void_p(d_state), int(M), int(P), int(max_depth), C.c_void_p(d_ll),
+                                        C.c_void_p(d_grad), int(prior[0]), *[float(z) for z in prior[1:]],
+                                        C.c_void_p(d_minv) if d_minv else None, C.c_void_p(d_W) if d_W else None,
+                                        float(target_accept), int(n_warmup), int(thin), int(n_keep), C.c_void_p(d_Xt),
+                                        C.c_void_p(d_samples) if d_samples else None,
+                                        C.c_void_p(d_stats) if d_stats else None))
 
     # -- the same chain with a dense mass matrix (pgl_hmc_dense_*): d_W (M, P, P) lower-triangular factors of the inverse
     # mass matrices; d_work: hmc_dense_work_doubles(M, P) doubles (0: none)

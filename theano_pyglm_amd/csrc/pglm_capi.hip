@@ -2141,6 +2141,79 @@ int pgl_hmc_dense_leap_dev(pgl_handle h, double* d_state, int M, int P, const do
     return PGL_OK;
 }
 
+// ---- NUTS row kernels (inference/batched_nuts.py) ------------------------------------------------------------------------
+long long pgl_nuts_state_doubles(int M, int P, int max_depth)
+{
+    if (M <= 0 || P <= 0 || max_depth < 1 || max_depth > PGL_NUTS_MAX_DEPTH) return 0;
+    return (long long)pgl_nuts_doubles(M, P, max_depth);
+}
+
+static int nuts_args(pgl_handle h, const double* d_state, int M, int P, int max_depth, const double* d_ll, const double* d_grad,
+                     int n_warmup, int thin, int n_keep, const double* d_Xt)
+{
+    if (!h || !d_state || !d_ll || !d_grad || !d_Xt || M <= 0 || P <= 0 || n_warmup < 0 || thin <= 0 || n_keep < 0 ||
+        (long long)n_warmup + (long long)n_keep * thin > 0x7fffffffLL)
+        return fail(PGL_ERR_ARG, "bad argument");
+    if (max_depth < 1 || max_depth > PGL_NUTS_MAX_DEPTH) return fail(PGL_ERR_ARG, "max_depth: 1 .. 10");
+    return PGL_OK;
+}
+
+int pgl_nuts_init_dev(pgl_handle h, double* d_state, int M, int P, int max_depth, int n_lo, double* d_ll, double* d_grad,
+                      int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam,
+                      const double* d_minv, const double* d_W, const double* d_step0, uint64_t seed, int n_warmup, int thin,
+                      int n_keep, double* d_Xt)
+{
+    int rc = nuts_args(h, d_state, M, P, max_depth, d_ll, d_grad, n_warmup, thin, n_keep, d_Xt);
+    if (rc) return rc;
+    if (!d_step0 || n_lo < 0 || n_lo + M > h->N) return fail(PGL_ERR_ARG, "bad argument");
+    BfgsPrior q;
+    rc = ncg_prior(h, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    const NutsView v = pgl_nuts_view(d_state, M, P, max_depth);
+    const size_t MP = (size_t)M * P;
+    if (d_W) {
+        hipLaunchKernelGGL(k_nuts_target, dim3(M), dim3(256), 0, h->stream, v, (int)PGL_NUTS_QC, d_ll, d_grad, q);
+        HIPCHK(hipGetLastError());
+        rc = tri_launch(h, 1, PGL_TRI_STORE, d_W, M, P, d_grad, v.vec + PGL_NUTS_HB * MP, nullptr, nullptr, 0.0);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_nuts_init, dim3(M), dim3(256), 0, h->stream, v, d_ll, d_grad, q, d_W ? 1 : 0, d_minv, n_lo, d_step0,
+                       (unsigned long long)seed, n_warmup + n_keep * thin, d_Xt);
+    HIPCHK(hipGetLastError());
+    if (!d_W) return PGL_OK;
+    return tri_launch(h, 0, PGL_TRI_DRIFT, d_W, M, P, v.vec + PGL_NUTS_RW * MP, v.vec + PGL_NUTS_QW * MP, d_Xt,
+                      v.sc + (size_t)PGL_NUTS_F_VE * M, 1.0);
+}
+
+int pgl_nuts_step_dev(pgl_handle h, double* d_state, int M, int P, int max_depth, double* d_ll, double* d_grad,
+                      int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam,
+                      const double* d_minv, const double* d_W, double target_accept, int n_warmup, int thin, int n_keep,
+                      double* d_Xt, double* d_samples, double* d_stats)
+{
+    int rc = nuts_args(h, d_state, M, P, max_depth, d_ll, d_grad, n_warmup, thin, n_keep, d_Xt);
+    if (rc) return rc;
+    if (!(target_accept > 0.0 && target_accept < 1.0)) return fail(PGL_ERR_ARG, "target_accept: in (0, 1)");
+    BfgsPrior q;
+    rc = ncg_prior(h, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    const NutsView v = pgl_nuts_view(d_state, M, P, max_depth);
+    const size_t MP = (size_t)M * P;
+    if (d_W) {
+        hipLaunchKernelGGL(k_nuts_target, dim3(M), dim3(256), 0, h->stream, v, (int)PGL_NUTS_QW, d_ll, d_grad, q);
+        HIPCHK(hipGetLastError());
+        rc = tri_launch(h, 1, PGL_TRI_STORE, d_W, M, P, d_grad, v.vec + PGL_NUTS_HB * MP, nullptr, nullptr, 0.0);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_nuts_step, dim3(M), dim3(256), 0, h->stream, v, d_ll, d_grad, q, d_W ? 1 : 0, d_minv, target_accept,
+                       n_warmup, thin, n_keep, d_Xt, d_samples, d_stats);
+    HIPCHK(hipGetLastError());
+    if (!d_W) return PGL_OK;
+    return tri_launch(h, 0, PGL_TRI_DRIFT, d_W, M, P, v.vec + PGL_NUTS_RW * MP, v.vec + PGL_NUTS_QW * MP, d_Xt,
+                      v.sc + (size_t)PGL_NUTS_F_VE * M, 1.0);
+}
+
 // ---- annealed importance sampling row kernels (inference/batched_ais.py) -----------------------------------------------
 long long pgl_ais_state_doubles(int R, int P) { return (long long)pgl_ais_doubles((size_t)(R > 0 ? R : 0), (size_t)(P > 0 ? P : 0)); }
 

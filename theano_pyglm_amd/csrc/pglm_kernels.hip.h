@@ -22,6 +22,7 @@
 // The dense Hessian H = F^T.diag(c).F is a contraction over time of its own (k_hess, pglm_hess.hip.h).
 // Posterior sampling runs HMC chains of all neurons in lock step around the ll+grad launch (k_hmc_*, pglm_hmc.hip.h).
 // A dense mass matrix adds two batched triangular matrix-vector products per leapfrog step (k_tri_matvec, pglm_hmc_dense.hip.h).
+// The No-U-Turn sampler runs on the same launch and products with rows that do not wait for each other (k_nuts_*, pglm_nuts.hip.h).
 // The Laplace posterior factors and inverts the dense Hessians in place, one workgroup per matrix (k_chol_factor, k_tri_inverse,
 // pglm_chol.hip.h).
 // The per-neuron evidence comes from annealed importance sampling on the same moves (k_ais_*, pglm_ais.hip.h).
@@ -46,6 +47,7 @@
 #include "pglm_ncg.hip.h"
 #include "pglm_hmc.hip.h"
 #include "pglm_hmc_dense.hip.h"
+#include "pglm_nuts.hip.h"
 #include "pglm_chol.hip.h"
 #include "pglm_ais.hip.h"
 #include "pglm_ais_dense.hip.h"

@@ -13,6 +13,8 @@ status, iterations and the number of non-zero presynaptic groups per neuron.
 --hmc N draws N posterior samples of every neuron's parameters from the fit by lock-step HMC on the device
 (inference/batched_hmc.py) and prints the bias posterior mean +- sd per neuron, beside the Laplace standard error when
 the model's packing has one.
+--nuts N does the same with the No-U-Turn sampler (inference/batched_nuts.py; --hmc-mass applies) and prints the same table
+plus the median tree depth and the divergent transitions per neuron.
 --ais K estimates every neuron's log evidence given the network from the fit by annealed importance sampling with K
 particles on the device (inference/batched_ais.py; Gaussian impulse priors only) and prints log_Z + log_prior_norm +- se, the
 ESS and the Laplace log evidence beside it.
@@ -45,7 +47,7 @@ def initialize_test_harness(model_name, data, data_dir=None):
 
 
 def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False, gof=False, ppc=0, hmc=0, ais=0,
-                   hmc_mass='laplace', prox=False, laplace_device=False, ais_mass='laplace'):
+                   hmc_mass='laplace', prox=False, laplace_device=False, ais_mass='laplace', nuts=0):
     """test/synth_map.py:10-32."""
     popn, popn_true, x_true = initialize_test_harness(model_name, data, data_dir)
     x0 = popn.sample(rng)
@@ -68,6 +70,8 @@ def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, r
         print(predictive.format_table(predictive.predictive_counts(popn, x_inf, ppc)))
     if hmc:
         print(hmc_bias_table(popn, x_inf, hmc, hmc_mass, laplace_device))
+    if nuts:
+        print(nuts_bias_table(popn, x_inf, nuts, hmc_mass, laplace_device))
     if ais:
         print(ais_evidence_table(popn, x_inf, ais, laplace_device, ais_mass))
     return x_inf, ll_inf, wall
@@ -112,6 +116,35 @@ def hmc_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False):
     return "\n".join(lines)
 
 
+def nuts_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, **kw):
+    """hmc_bias_table with the No-U-Turn sampler: the same columns ('accept' is the mean acceptance statistic after
+    warm-up) plus the median tree depth of the kept transitions and the divergent transitions after warm-up.  kw: further
+    arguments of sample_glms_nuts (n_warmup, max_depth, ...)."""
+    import numpy as np
+    from theano_pyglm_amd.inference import batched_nuts
+    from theano_pyglm_amd.inference.laplace import laplace_glms
+    t0 = time.time()
+    res = batched_nuts.sample_glms_nuts(popn, x, n_draws, mass=mass,
+                                        factor_on_device=laplace_device and mass == 'laplace_dense', **kw)
+    wall = time.time() - t0
+    s = batched_nuts.summarize(res['samples'][:, :, 0])
+    try:
+        se = [r['stderr_vec'][0] if r['pd'] else float('nan') for r in laplace_glms(popn, x, device=laplace_device)]
+    except ValueError:
+        se = None
+    depth = np.median(res['depth'], axis=0)
+    lines = ["NUTS%s: %d draws per neuron in %.2f s (%d ll+grad launches, %d idle row evaluations; median depth %g, "
+             "%d divergent transitions)" % ("" if mass == 'laplace' else " (mass=%s)" % mass, n_draws, wall, res['n_evals'],
+                                           res['idle_row_evaluations'], np.median(res['depth']), res['divergent'].sum()),
+             "neuron   bias mean +- sd        ESS  accept   step  depth  divergent" + ("   Laplace se" if se is not None else "")]
+    for n in range(popn.N):
+        ln = "%6d  %9.4f +- %-8.4f %6.0f  %6.2f  %6.4f  %5g  %9d" % (n, s['mean'][n], s['sd'][n], s['ess'][n],
+                                                                    res['accept_rate'][n], res['step_sz'][n], depth[n],
+                                                                    res['divergent'][n])
+        lines.append(ln + ("   %10.4f" % se[n] if se is not None else ""))
+    return "\n".join(lines)
+
+
 def ais_evidence_table(popn, x, n_particles, laplace_device=False, mass='laplace'):
     """AIS with n_particles particles per neuron from x: one line per neuron, log_Z + log_prior_norm +- se, the ESS and the
     Laplace log evidence (both under the host priors, which drop their normalising constants).  mass: 'none' (identity),
@@ -131,7 +164,7 @@ def ais_evidence_table(popn, x, n_particles, laplace_device=False, mass='laplace
     return "\n".join(lines)
 
 
-def main():
+def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('-m', '--model', default='standard_glm')
     ap.add_argument('-d', '--dataFile', required=True)
@@ -150,8 +183,11 @@ def main():
                     help='after the fit: predictive spike counts of N replicates simulated from the fitted model on the device')
     ap.add_argument('--hmc', type=int, default=0, metavar='N',
                     help='after the fit: N posterior draws per neuron by lock-step HMC on the device; prints the bias mean +- sd')
+    ap.add_argument('--nuts', type=int, default=0, metavar='N',
+                    help='after the fit: N posterior draws per neuron by the No-U-Turn sampler on the device; prints the table '
+                         'of --hmc plus the median tree depth and the divergent transitions')
     ap.add_argument('--hmc-mass', choices=['laplace', 'laplace_dense'], default='laplace',
-                    help="mass matrix of --hmc: 1 / diag A ('laplace') or the full Laplace covariance ('laplace_dense')")
+                    help="mass matrix of --hmc and --nuts: 1 / diag A ('laplace') or the full Laplace covariance ('laplace_dense')")
     ap.add_argument('--ais', type=int, default=0, metavar='K',
                     help='after the fit: log evidence of every neuron given the network by annealed importance sampling with '
                          'K particles on the device, beside the Laplace log evidence (Gaussian impulse priors only)')
@@ -161,12 +197,16 @@ def main():
     ap.add_argument('--laplace-device', action='store_true',
                     help='the Laplace factorisations behind --hmc (standard errors, and the factor of --hmc-mass laplace_dense) '
                          'and --ais run on the device (batched Cholesky and triangular inverse) instead of on the host')
-    args = ap.parse_args()
+    return ap
+
+
+def main(argv=None):
+    args = parser().parse_args(argv)
     with open(args.dataFile, 'rb') as f:
         data = pickle.load(f)
     run_synth_test(args.model, data, args.resultsDir, os.path.dirname(args.dataFile),
                    False if args.sequential else ('torch' if args.newton_cg else None), use_rop=args.newton_cg, gof=args.gof, ppc=args.ppc, hmc=args.hmc, ais=args.ais,
-                   hmc_mass=args.hmc_mass, prox=args.prox, laplace_device=args.laplace_device, ais_mass=args.ais_mass)
+                   hmc_mass=args.hmc_mass, prox=args.prox, laplace_device=args.laplace_device, ais_mass=args.ais_mass, nuts=args.nuts)
 
 
 if __name__ == '__main__':

@@ -1,0 +1,187 @@
+"""
+The No-U-Turn sampler for the per-neuron GLM posteriors with the chain state resident on the GPU.
+
+The setting is batched_hmc's: given the network the neurons' parameter rows have independent posteriors, and ONE
+pgl_ll_grad_dev evaluates all of them for the price of one.  What changes is the transition: multinomial NUTS (Hoffman &
+Gelman 2014; Betancourt 2017) as inference/nuts.py states it and csrc/pglm_nuts.h restates it in O(max_depth) storage --
+no trajectory length to guess -- with a step size per row from dual averaging towards target_accept during the warm-up,
+frozen afterwards.  It runs as HIP row kernels (pgl_nuts_*, one workgroup per neuron) on state that never leaves the
+device.  Trees differ in size from row to row and from transition to transition, so the rows do not wait for each other:
+every launch is one leapfrog step of every row that still has transitions to run, a row that ends a transition starts
+its next one in the same launch, counts its own t and writes its kept points itself; a row that has finished idles (its
+evaluation is wasted: 'idle_row_evaluations').  The host only enqueues evaluation + step launches and looks at the rows'
+done flags behind an event every POLL launches, one window late, so the queue never runs dry.
+
+The mass matrix is batched_hmc's: None, 'laplace', an (M, P) array, 'laplace_dense' or an (M, P, P) array
+(factor_inverse_mass; factor_on_device=True builds the Laplace factor on the device).  All of them are one code path: the
+chain runs in the whitened momentum r = W^T p, a diagonal W inside the row kernel, a dense one through two
+pgl_tri_matvec_dev products per leapfrog step.
+
+Served: the populations batched_hmc serves, with the same errors for the others.
+"""
+import numpy as np
+
+from theano_pyglm_amd.inference.batched_bfgs import _Packing
+from theano_pyglm_amd.inference.batched_hmc import (_STREAMS, _check, _laplace_dense_factor, _laplace_dense_factor_device,
+                                                    _laplace_minv, factor_inverse_mass, samples_to_states, summarize,
+                                                    supported)
+
+# rows of the scalar block of the state (PglNuts, csrc/pglm_nuts.h)
+SC_STEP, SC_T, SC_DONE, SC_NLEAP, SC_NDIV, SC_ACC = 2, 3, 7, 21, 22, 23
+NSCAL, NVEC = 30, 17
+POLL = 8                                                      # launches between two looks at the done flags
+
+
+def sample_glms_nuts(population, x, n_samples, n_warmup=200, max_depth=8, step_sz=0.1, target_accept=0.8, thin=1, mass=None,
+                     seed=0, n_lo=0, n_hi=None, factor_on_device=False, mass_floor=1e-8):
+    """Posterior samples of the parameter rows of neurons [n_lo, n_hi) given the rest of x, started at x.
+
+    n_warmup transitions adapt every row's step size (dual averaging towards target_accept) and are dropped; then
+    n_samples * thin transitions, every thin-th kept.  max_depth: at most that many doublings per transition (1 .. 10).
+    step_sz: the starting step, a number or one per row.  mass, factor_on_device, mass_floor: as sample_glms_hmc.
+    Returns sample_glms_hmc's dict -- 'samples' (n_samples, M, P), 'accept_rate' (M,) (here the mean acceptance statistic
+    after warm-up), 'step_sz' (M,) the frozen steps, 'n_evals', with 'laplace_dense' 'dense_rows' -- and 'depth',
+    'n_leapfrog' (n_samples, M) of the kept transitions, 'divergent' (M,) divergent transitions after warm-up, 'step'
+    (= 'step_sz'), 'launches' (evaluation + step launches: the largest number of leapfrog steps of any row, plus fewer
+    than 2 POLL because the done flags are read every POLL launches and one window late) and 'idle_row_evaluations' (the
+    sum over rows of launches - the row's leapfrog steps).  x is not changed."""
+    _check(population)
+    n_samples, n_warmup, max_depth, thin = int(n_samples), int(n_warmup), int(max_depth), int(thin)
+    if n_samples <= 0 or n_warmup < 0 or thin <= 0:
+        raise ValueError("n_samples and thin must be positive, n_warmup not negative")
+    if not 1 <= max_depth <= 10:
+        raise ValueError("max_depth: 1 .. 10")
+    if not 0.0 < float(target_accept) < 1.0:
+        raise ValueError("target_accept: in (0, 1)")
+    import time
+    import torch
+    n_hi = population.N if n_hi is None else n_hi
+    M = n_hi - n_lo
+    if M <= 0:
+        raise ValueError("empty neuron range")
+    t0 = time.perf_counter()
+    factor = dense_rows = None
+    if isinstance(mass, str):
+        if mass == 'laplace':
+            mass = _laplace_minv(population, x, n_lo, n_hi, float(mass_floor))
+        elif mass == 'laplace_dense':
+            build = _laplace_dense_factor_device if factor_on_device else _laplace_dense_factor
+            factor, dense_rows = build(population, x, n_lo, n_hi, float(mass_floor))
+            mass = None
+        else:
+            raise ValueError("mass: None, 'laplace', 'laplace_dense', an (M, P) or an (M, P, P) array")
+    elif mass is not None and np.ndim(mass) == 3:
+        if np.shape(mass) != (M,) + (population.glm.P,) * 2:
+            raise ValueError("mass: an (M, P, P) = (%d, %d, %d) array of inverse mass matrices" % ((M,) + (population.glm.P,) * 2))
+        factor = factor_inverse_mass(mass)
+        mass = None
+    setup_s = time.perf_counter() - t0
+    P = population.glm.P
+    if mass is not None:
+        mass = np.ascontiguousarray(mass, dtype=float)
+        if mass.shape != (M, P) or not np.all(np.isfinite(mass)) or not np.all(mass > 0.0):
+            raise ValueError("mass: an (M, P) = (%d, %d) array of positive inverse masses" % (M, P))
+    step_sz = np.ascontiguousarray(np.broadcast_to(np.asarray(step_sz, dtype=float), (M,)))
+    if not np.all(step_sz > 0.0):
+        raise ValueError("step_sz must be positive")
+    dev = torch.device('cuda', population.device)
+    handles = []
+    for data in population.data_sequences:
+        population.set_data(data)
+        handles.append(population._handle(data))
+    stream = _STREAMS.get(dev.index)
+    if stream is None:
+        stream = _STREAMS[dev.index] = torch.cuda.Stream(dev)
+    stream.wait_stream(torch.cuda.current_stream(dev))
+    for h in handles:
+        h.set_stream(stream.cuda_stream)
+    try:
+        with torch.cuda.stream(stream):
+            out = _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, max_depth, step_sz,
+                         float(target_accept), thin, mass, int(seed), n_lo, n_hi, M, factor)
+    finally:
+        try:
+            stream.synchronize()
+        except Exception:
+            pass
+        for h in handles:
+            h.set_stream(None)
+    if dense_rows is not None:
+        out['dense_rows'] = dense_rows
+    population.last_fit_stats['mass_setup_s'] = setup_s
+    return out
+
+
+def _chain(population, torch, dev, stream, handles, x, n_keep, n_warmup, D, step_sz, delta, thin, mass, seed, n_lo, n_hi, M,
+           factor):
+    pk = _Packing(population, torch, handles, (n_lo, n_hi))
+    assert pk.identity                                        # (hvp_packing() is None: the row IS the theta row)
+    h0 = handles[0]
+    P = pk.Pp
+    prm = pk.prior_params()
+    f64 = torch.float64
+    MP = M * P
+    st = torch.zeros(h0.nuts_state_doubles(M, P, D), dtype=f64, device=dev)
+    sc = st[(NVEC + 2 * D) * MP:].view(NSCAL, M)
+    st[0:MP].view(M, P).copy_(torch.tensor(pk.pack(x, n_lo, n_hi), dtype=f64, device=dev))
+    Weff = torch.tensor(population.W_eff(x), dtype=f64, device=dev)
+    minv = Wd = None
+    assert P == population.glm.P                              # (mass and step_sz were checked against it by the caller)
+    if mass is not None:
+        minv = torch.tensor(mass, dtype=f64, device=dev)
+    if factor is not None:                                    # (M, P, P) lower-triangular factors: uploaded once
+        assert tuple(factor.shape) == (M, P, P)
+        Wd = factor if torch.is_tensor(factor) else torch.tensor(factor, dtype=f64, device=dev)
+    step0 = torch.tensor(step_sz, dtype=f64, device=dev)
+    minv_ptr = minv.data_ptr() if minv is not None else 0
+    W_ptr = Wd.data_ptr() if Wd is not None else 0
+    Xt = torch.empty((M, P), dtype=f64, device=dev)
+    bufs = [torch.empty(M * (1 + P), dtype=f64, device=dev) for _ in handles]     # [ll | grad] per data sequence
+    samples = torch.zeros((n_keep, M, P), dtype=f64, device=dev)
+    stats = torch.zeros((n_keep, 2, M), dtype=f64, device=dev)
+    flags = [torch.zeros(M, dtype=f64).pin_memory() for _ in range(2)]
+    counts = {'ll_grad': 0, 'polls': 0}
+
+    def evaluate(Xe):
+        tot = None
+        for h, buf in zip(handles, bufs):
+            h.ll_grad_dev(Xe.data_ptr(), Weff.data_ptr(), buf.data_ptr(), buf[M:].data_ptr(), n_lo, n_hi)
+            tot = buf if tot is None else tot.add_(buf)
+        counts['ll_grad'] += 1
+        return tot[:M], tot[M:]
+
+    ll0, g0 = evaluate(st[0:MP].view(M, P))
+    h0.nuts_init_dev(st.data_ptr(), M, P, D, n_lo, ll0.data_ptr(), g0.data_ptr(), prm, minv_ptr, W_ptr, step0.data_ptr(), seed,
+                     n_warmup, thin, n_keep, Xt.data_ptr())
+    launches, events, all_done = 0, [], False
+    while not all_done:
+        llt, gt = evaluate(Xt)
+        h0.nuts_step_dev(st.data_ptr(), M, P, D, llt.data_ptr(), gt.data_ptr(), prm, minv_ptr, W_ptr, delta, n_warmup, thin,
+                         n_keep, Xt.data_ptr(), samples.data_ptr(), stats.data_ptr())
+        launches += 1
+        if launches % POLL == 0:
+            fl = flags[(launches // POLL) % 2]
+            fl.copy_(sc[SC_DONE], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(stream)
+            events.append((ev, fl))
+            if len(events) > 1:                               # the look lags one window behind: the queue never runs dry
+                ev, fl = events.pop(0)
+                ev.synchronize()
+                counts['polls'] += 1
+                all_done = bool(np.all(fl.numpy() != 0.0))
+    stream.synchronize()
+    sch = sc.cpu().numpy()
+    sth = stats.cpu().numpy()
+    nleap = sch[SC_NLEAP]
+    out = {'samples': samples.cpu().numpy(), 'accept_rate': sch[SC_ACC] / float(n_keep * thin), 'step_sz': sch[SC_STEP].copy(),
+           'n_evals': counts['ll_grad'], 'depth': sth[:, 0].astype(int), 'n_leapfrog': sth[:, 1].astype(int),
+           'divergent': sch[SC_NDIV].astype(int), 'step': sch[SC_STEP].copy(), 'launches': launches,
+           'idle_row_evaluations': int(np.sum(launches - nleap))}
+    assert np.all(sch[SC_DONE] != 0.0) and np.all(sch[SC_T] == n_warmup + n_keep * thin)
+    population.last_fit_stats = {'sampler': 'NUTS (hip row kernels)', 'transitions': n_warmup + n_keep * thin,
+                                 'mass': 'dense' if Wd is not None else ('diagonal' if minv is not None else 'identity'),
+                                 'll_grad_launches': counts['ll_grad'], 'step_launches': launches,
+                                 'leapfrog_steps': nleap.astype(int), 'flag_reads': counts['polls'],
+                                 'idle_share': float(np.sum(launches - nleap)) / float(launches * M)}
+    return out
