@@ -39,18 +39,19 @@ def oracle_target(probs, n_lo, n_hi):
     return target
 
 
-def mirror_run(probs, K, n_lo, n_hi, prm, betas, n_steps, L, table, seed, particle0=0):
+def mirror_run(probs, K, n_lo, n_hi, prm, betas, n_steps, L, table, seed, particle0=0, minv=None):
     p0 = probs[0]
     mir = AM.Mirror(oracle_target(probs, n_lo, n_hi), K, n_hi - n_lo, (p0.N, p0.B, p0.Dstim, prm[1:]), n_lo=n_lo,
-                    particle0=particle0, step0=0.1, seed=seed)
+                    particle0=particle0, step0=0.1, seed=seed, minv=minv)
     out = mir.run(betas, n_steps, L, adapt=False, step_table=table)
     out['draws'] = mir.draws
     out['ll_seen'] = np.array(mir.ll_seen)
     return out
 
 
-def device_run(probs, K, n_lo, n_hi, prm, betas, n_steps, L, table, seed, particle0=0):
-    """The same run through the C ABI; the decisions are read after every transition (a test's privilege).
+def device_run(probs, K, n_lo, n_hi, prm, betas, n_steps, L, table, seed, particle0=0, minv=None):
+    """The same run through the C ABI (minv (M, P): the neurons' inverse masses, None: 1); the decisions are read after every
+    transition (a test's privilege).
     -> dict as the mirror's, plus 'draws' and 'll_draws' (the evaluation at the draws)."""
     import torch
     p0 = probs[0]
@@ -70,6 +71,8 @@ def device_run(probs, K, n_lo, n_hi, prm, betas, n_steps, L, table, seed, partic
             sc = st[6 * R * P:].view(15, R)
             Weff = torch.tensor(p0.Weff, dtype=f64, device=dev)
             tab = torch.tensor(np.asarray(table, dtype=float).reshape(J - 1, M), dtype=f64, device=dev)
+            mt = None if minv is None else torch.tensor(np.asarray(minv, dtype=float).reshape(M, P), dtype=f64, device=dev)
+            md = 0 if mt is None else mt.data_ptr()
             Xt = torch.empty((R, P), dtype=f64, device=dev)
             bufs = [torch.empty(R * (1 + P), dtype=f64, device=dev) for _ in hs]
             accepts = torch.zeros((J - 1, R), dtype=f64, device=dev)
@@ -96,10 +99,10 @@ def device_run(probs, K, n_lo, n_hi, prm, betas, n_steps, L, table, seed, partic
                 if j == J:
                     break
                 for _ in range(n_steps):
-                    h0.ais_begin_dev(sp, K, M, P, 0, Xt.data_ptr())
+                    h0.ais_begin_dev(sp, K, M, P, md, Xt.data_ptr())
                     for i in range(L):
                         ll, g = evaluate()
-                        h0.ais_leap_dev(sp, K, M, P, 0, ll, g, prm, i == L - 1, False, Xt.data_ptr(), accepts[j - 1].data_ptr(),
+                        h0.ais_leap_dev(sp, K, M, P, md, ll, g, prm, i == L - 1, False, Xt.data_ptr(), accepts[j - 1].data_ptr(),
                                         steps[j - 1].data_ptr())
                     stream.synchronize()
                     accepted.append(sc[AM.SC['acc']].cpu().numpy() != 0.0)
@@ -112,13 +115,13 @@ def device_run(probs, K, n_lo, n_hi, prm, betas, n_steps, L, table, seed, partic
             h.close()
 
 
-def compare(probs, K, n_lo, n_hi, prm, betas, n_steps, L, table, seed, label=""):
-    m = mirror_run(probs, K, n_lo, n_hi, prm, betas, n_steps, L, table, seed)
+def compare(probs, K, n_lo, n_hi, prm, betas, n_steps, L, table, seed, label="", minv=None):
+    m = mirror_run(probs, K, n_lo, n_hi, prm, betas, n_steps, L, table, seed, minv=minv)
     print("%s mirror: accepted %d of %d, smallest margin %.3e" % (label, m['accepted'].sum(), m['accepted'].size, m['margins'].min()))
     assert np.all(np.isfinite(m['ll_seen'][0]))                 # ll is finite at every prior draw
     assert m['margins'].min() > MARGIN                          # the condition the case was seeded for
     assert m['accepted'].any() and not m['accepted'].all()      # both outcomes of the decision
-    d = device_run(probs, K, n_lo, n_hi, prm, betas, n_steps, L, table, seed)
+    d = device_run(probs, K, n_lo, n_hi, prm, betas, n_steps, L, table, seed, minv=minv)
     assert np.array_equal(d['accepted'], m['accepted'])
     assert np.array_equal(d['accepts'], m['accepts']) and np.array_equal(d['steps'], m['steps'])
     err = np.max(np.abs(d['samples'] - m['samples']) / np.max(np.abs(m['samples']), axis=2, keepdims=True))
@@ -157,6 +160,21 @@ def test_strided_row_loops():
     p = _problem(70, 512, 'explinear', 37, ibasis=H.std_ibasis()[:, :4])
     assert p.P == 281
     compare([p], 2, 0, 70, _prior('explinear'), [0.0, 0.5, 1.0], 1, 3, _table([0.05], 70), 3, label="N=70")    # mirror: 84 of 140, 1.5e-2
+
+
+@pytest.mark.gpu
+def test_per_neuron_masses_shared_by_the_particles():
+    """pgl_ais_begin_dev starts a transition with the chain's k_hmc_begin on the AIS state: K M = 6 rows, scalar stride 6,
+    and row r on row r mod M of minv.  K = 3, neurons 1 .. 2 of N = 5 (M = 2), P = 26 (no multiple of 64), an (M, P) minv
+    whose two rows differ (one constant, one random in [0.5, 4)): a wrong row of minv or a wrong stride moves the points by
+    orders of magnitude more than the bound and changes decisions.  Against the host mirror at the bounds of compare():
+    the decisions, accept counts and steps bit for bit, points and weights within 1e-9 -- the mirror is fed by the CPU
+    oracle, whose ll and gradient agree with the device's to rounding and not to the bit, so the points cannot."""
+    p = _problem(5, 2000, 'explinear', 31)
+    assert p.P == 26
+    minv = np.stack([np.full(p.P, 0.25), 0.5 + 3.5 * np.random.default_rng(47).random(p.P)])
+    compare([p], 3, 1, 3, _prior('explinear'), BETAS, 2, 3, _table([0.12, 0.06, 0.04], 2), 3, label="minv",
+            minv=minv)                                          # mirror: 26 of 36 accepted, smallest margin 4.3e-2
 
 
 @pytest.mark.gpu

@@ -79,6 +79,7 @@ def test_shared_product_against_numpy_and_the_one_row_product(handle, P):
         ref = np.einsum('mij,kmj->kmi', A, xl)
         mag = np.einsum('mij,kmj->kmi', np.abs(A), np.abs(xl)).astype(float)
         one = torch.full((Kmax, 3, P), np.nan, dtype=f64, device=dev)
+        torch.cuda.synchronize()                                # (the fill runs on torch's stream, the products on the handle's)
         for k in range(Kmax):
             for i in range(3):
                 handle.tri_matvec_dev(Wd[i].data_ptr(), 1, P, trans, xd[k, i].data_ptr(), one[k, i].data_ptr())

@@ -60,7 +60,8 @@ def _device_product(h, W, x, trans):
 @pytest.mark.parametrize('P', [1, 2, 63, 64, 65, 255, 256, 257, 281, 641])
 def test_tri_matvec_against_numpy(handle, P):
     """y = W x and W^T x for M = 1 and 3 with NaN above the diagonal: within 1e-13 sum|w||x| of an extended-precision
-    numpy product per output, the same bits twice, and the rows of the M = 3 call equal to the M = 1 calls bit for bit."""
+    numpy product per output, the same bits twice, the rows of the M = 3 call equal to the M = 1 calls bit for bit, and
+    the same bits from the row grid (development option 90: one workgroup per matrix walks all its tiles)."""
     assert TILE == 64                                          # (else P = TILE - 1, TILE, TILE + 1 belong to the list)
     rng = np.random.default_rng(100 + P)
     W = rng.standard_normal((3, P, P))
@@ -78,6 +79,11 @@ def test_tri_matvec_against_numpy(handle, P):
         print("P = %d trans = %d: largest error / sum|w||x| = %.3e" % (P, trans, err))
         assert err <= 1e-13
         assert np.array_equal(y3, _device_product(handle, Wn, x, trans))
+        handle.set_option(90, 1)
+        try:
+            assert np.array_equal(y3, _device_product(handle, Wn, x, trans))
+        finally:
+            handle.set_option(90, 0)
         for m in range(3):
             y1 = _device_product(handle, Wn[m:m + 1], x[m:m + 1], trans)
             assert np.array_equal(y1[0], y3[m])

@@ -29,8 +29,20 @@ __host__ __device__ inline AisView pgl_ais_view(double* st, int K, int M, int P)
     v.sc = st + PGL_AIS_NVEC * RP;
     return v;
 }
-#define PGL_AIS_FIELDS(F) F(h.U0, 0) F(h.H0, 1) F(h.step, 2) F(h.avg_accept, 3) F(h.n_accept, 4) F(h.t, 5) F(h.acc, 6) \
-    F(h.neuron, 7) F(h.seed_lo, 8) F(h.seed_hi, 9) F(ll0, 10) F(lp0, 11) F(beta, 12) F(logw, 13) F(particle, 14)
+// the scalar rows: PglHmc's, at PglHmc's indices, then PglAis's own
+#define PGL_AIS_FIELDS(F) PGL_HMC_FIELDS_IN(F, h.) F(ll0, 10) F(lp0, 11) F(beta, 12) F(logw, 13) F(particle, 14)
+static_assert(PGL_HMC_NSCAL == 10 && PGL_AIS_NSCAL == 15, "PglAis's own rows follow the PGL_HMC_NSCAL rows of PglHmc");
+// The rows of an AIS state as a chain of R rows, for the chain's kernels that start a transition (k_hmc_begin,
+// k_hmc_dense_draw): q, p, q0, g are the first four arrays of both blocks, and the scalar rows 0 .. PGL_HMC_NSCAL - 1 are
+// PglHmc's by PGL_AIS_FIELDS.  (Not pgl_hmc_view(st, R, P): the scalar blocks start behind NVEC arrays, and NVEC differs.)
+__host__ __device__ inline HmcView pgl_ais_hmc_view(const AisView& a)
+{
+    HmcView v;
+    v.M = a.R; v.P = a.P;
+    v.q = a.q; v.p = a.p; v.q0 = a.q0; v.g = a.g;
+    v.sc = a.sc;
+    return v;
+}
 __device__ __forceinline__ void pgl_ais_load(const AisView& v, int r, PglAis* s)
 {
 #define PGL_AIS_LD(name, k) s->name = v.sc[(size_t)k * v.R + r];
@@ -125,32 +137,31 @@ __global__ __launch_bounds__(256) void k_ais_temper(const AisView v, const BfgsP
     }
 }
 
-// start of a transition, as k_hmc_begin; minv (M, P) is shared by the particles of a neuron
-__global__ __launch_bounds__(256) void k_ais_begin(const AisView v, const double* __restrict__ minv, double* __restrict__ Xt)
+// end of a transition: H1 from ll1, lp1 (ll and the log prior at q) and ks, the decision (*dec, shared), the step-size rule
+// if adapt, t += 1; acc_out[row] += the decision and step_out[row] = the row's step after it (null: none); then accept
+// (ll, the log prior, grad ll = grad_row and grad U = gu of the new point are kept) or restore q0
+__device__ __forceinline__ void pgl_ais_finish_row(const AisView& v, const int r, const double ll1, const double lp1,
+                                                   const double ks, const double* grad_row, const int adapt, double* acc_out,
+                                                   double* step_out, int* dec, const int tid)
 {
-    __shared__ double red[12];
-    const int r = blockIdx.x, tid = threadIdx.x, P = v.P;
-    const size_t o = (size_t)r * P, om = (size_t)(r % v.M) * P;
-    PglAis s;
-    pgl_ais_load(v, r, &s);
-    const pgl_hmc_u64 key = pgl_hmc_row_key(&s.h);
-    double ks = 0.0;
-    for (int c = tid; c < P; c += 256) {
-        const double mi = minv ? minv[om + c] : 1.0;
-        const double q0 = v.q[o + c];
-        double p = pgl_hmc_momentum(pgl_hmc_normal(key, (pgl_hmc_u64)c), mi);
-        ks += pgl_hmc_kinetic_elem(p, mi);
-        p = pgl_hmc_kick(p, 0.5, s.h.step, v.g[o + c]);
-        const double qn = pgl_hmc_drift(q0, s.h.step, mi, p);
-        v.q0[o + c] = q0;
-        v.p[o + c] = p;
-        v.q[o + c] = qn;
-        Xt[o + c] = qn;
-    }
-    ks = pgl_blk_sum(ks, red);
+    const size_t o = (size_t)r * v.P;
     if (tid == 0) {
-        pgl_hmc_begin(&s.h, ks);
-        v.sc[(size_t)1 * v.R + r] = s.h.H0;
+        PglAis s;
+        pgl_ais_load(v, r, &s);
+        const double u = pgl_hmc_accept_uniform(pgl_hmc_row_key(&s.h));
+        *dec = pgl_ais_decide(&s, ll1, lp1, ks, u, adapt);
+        pgl_ais_store(v, r, &s);
+        if (acc_out) acc_out[r] += (double)*dec;
+        if (step_out) step_out[r] = s.h.step;
+    }
+    __syncthreads();
+    if (*dec != 0) {
+        for (int c = tid; c < v.P; c += 256) {
+            v.g[o + c] = v.gu[o + c];
+            v.gll[o + c] = grad_row[c];
+        }
+    } else {
+        for (int c = tid; c < v.P; c += 256) v.q[o + c] = v.q0[o + c];
     }
 }
 
@@ -182,30 +193,6 @@ __global__ __launch_bounds__(256) void k_ais_leap(const AisView v, const double*
         }
         return;
     }
-    double ks = 0.0;
-    for (int c = tid; c < P; c += 256) {
-        const double mi = minv ? minv[om + c] : 1.0;
-        const double p = pgl_hmc_kick(v.p[o + c], 0.5, step, v.gu[o + c]);
-        v.p[o + c] = p;
-        ks += pgl_hmc_kinetic_elem(p, mi);
-    }
-    ks = pgl_blk_sum(ks, red);
-    if (tid == 0) {
-        PglAis s;
-        pgl_ais_load(v, r, &s);
-        const double u = pgl_hmc_accept_uniform(pgl_hmc_row_key(&s.h));
-        dec = pgl_ais_decide(&s, ll[r], lp1, ks, u, adapt);
-        pgl_ais_store(v, r, &s);
-        if (acc_out) acc_out[r] += (double)dec;
-        if (step_out) step_out[r] = s.h.step;
-    }
-    __syncthreads();
-    if (dec != 0) {
-        for (int c = tid; c < P; c += 256) {
-            v.g[o + c] = v.gu[o + c];
-            v.gll[o + c] = grad[o + c];
-        }
-    } else {
-        for (int c = tid; c < P; c += 256) v.q[o + c] = v.q0[o + c];
-    }
+    const double ks = pgl_hmc_end_kinetic<0>(v.p + o, v.gu + o, minv ? minv + om : nullptr, step, P, red, tid);
+    pgl_ais_finish_row(v, r, ll[r], lp1, ks, grad + o, adapt, acc_out, step_out, &dec, tid);
 }

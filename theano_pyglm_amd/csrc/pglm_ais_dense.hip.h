@@ -9,6 +9,7 @@
 // 64 outputs, neuron) and produces that tile for all K particles from ONE read of its part of W_i -- the grid of
 // k_tri_matvec, (tile, row), with the particles folded into the workgroup.  The kick and the drift are the products'
 // epilogues: a leapfrog step is a row kernel and two product launches whatever K is.  Only j <= i of W is read.
+// A transition starts with the chain's own k_hmc_dense_draw on pgl_ais_hmc_view.
 // Every output is summed in the order of k_tri_matvec, which depends on P alone: row (k, i) of a K-particle call has the
 // bits of the one-row k_tri_matvec call with W_i, for any K and M -- subset = batch, repeat = same bits.
 // ---------------------------------------------------------------------------
@@ -99,30 +100,6 @@ __global__ __launch_bounds__(256) void k_tri_matvec_shared(const double* __restr
     }
 }
 
-// start of a transition: the momentum r = z (the draws of k_ais_begin), H0, q0 = q.  The half kick and the first drift
-// are the two product launches behind it.
-__global__ __launch_bounds__(256) void k_ais_dense_draw(const AisView v)
-{
-    __shared__ double red[12];
-    const int r = blockIdx.x, tid = threadIdx.x, P = v.P;
-    const size_t o = (size_t)r * P;
-    PglAis s;
-    pgl_ais_load(v, r, &s);
-    const pgl_hmc_u64 key = pgl_hmc_row_key(&s.h);
-    double ks = 0.0;
-    for (int c = tid; c < P; c += 256) {
-        const double z = pgl_hmc_normal(key, (pgl_hmc_u64)c);
-        ks += pgl_hmcd_kinetic_elem(z);
-        v.p[o + c] = z;
-        v.q0[o + c] = v.q[o + c];
-    }
-    ks = pgl_blk_sum(ks, red);
-    if (tid == 0) {
-        pgl_hmc_begin(&s.h, ks);
-        v.sc[(size_t)1 * v.R + r] = s.h.H0;
-    }
-}
-
 // after the evaluation of all rows at Xt = q: gu = grad U_beta along the trajectory from grad = grad ll (left as it is);
 // the kick's product reads gu next
 __global__ __launch_bounds__(256) void k_ais_dense_target(const AisView v, const double* __restrict__ grad, const BfgsPrior q)
@@ -134,37 +111,17 @@ __global__ __launch_bounds__(256) void k_ais_dense_target(const AisView v, const
 }
 
 // end of a transition, after the last half kick: H1 from ll[row], the log prior at q (summed again, as k_ais_dense_target
-// summed it: gu is rewritten with the same bits) and r; the decision, the step-size rule if adapt, t += 1; accept (ll, the
-// log prior, grad ll and grad U of the new point are kept) or restore; acc_out / step_out as k_ais_leap
+// summed it: gu is rewritten with the same bits) and r, then pgl_ais_finish_row as the last branch of k_ais_leap
 __global__ __launch_bounds__(256) void k_ais_dense_end(const AisView v, const double* __restrict__ ll,
                                                        const double* __restrict__ grad, const BfgsPrior q, const int adapt,
                                                        double* __restrict__ acc_out, double* __restrict__ step_out)
 {
     __shared__ double red[12];
     __shared__ int dec;
-    const int r = blockIdx.x, tid = threadIdx.x, P = v.P;
-    const size_t o = (size_t)r * P;
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const size_t o = (size_t)r * v.P;
     const double lp1 = pgl_ais_target_row(v.q + o, grad + o, v.gu + o, v.sc[(size_t)12 * v.R + r], q, red, tid);
     __syncthreads();                                                           // red is free, gu of the row is in memory
-    double ks = 0.0;
-    for (int c = tid; c < P; c += 256) ks += pgl_hmcd_kinetic_elem(v.p[o + c]);
-    ks = pgl_blk_sum(ks, red);
-    if (tid == 0) {
-        PglAis s;
-        pgl_ais_load(v, r, &s);
-        const double u = pgl_hmc_accept_uniform(pgl_hmc_row_key(&s.h));
-        dec = pgl_ais_decide(&s, ll[r], lp1, ks, u, adapt);
-        pgl_ais_store(v, r, &s);
-        if (acc_out) acc_out[r] += (double)dec;
-        if (step_out) step_out[r] = s.h.step;
-    }
-    __syncthreads();
-    if (dec != 0) {
-        for (int c = tid; c < P; c += 256) {
-            v.g[o + c] = v.gu[o + c];
-            v.gll[o + c] = grad[o + c];
-        }
-    } else {
-        for (int c = tid; c < P; c += 256) v.q[o + c] = v.q0[o + c];
-    }
+    const double ks = pgl_hmc_end_kinetic<1>(v.p + o, nullptr, nullptr, 0.0, v.P, red, tid);
+    pgl_ais_finish_row(v, r, ll[r], lp1, ks, grad + o, adapt, acc_out, step_out, &dec, tid);
 }

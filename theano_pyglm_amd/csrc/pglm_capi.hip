@@ -2039,7 +2039,7 @@ int pgl_hmc_begin_dev(pgl_handle h, double* d_state, int M, int P, const double*
 {
     if (!h || !d_state || !d_Xt || M <= 0 || P <= 0) return fail(PGL_ERR_ARG, "bad argument");
     HIPCHK(hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_hmc_begin, dim3(M), dim3(256), 0, h->stream, pgl_hmc_view(d_state, M, P), d_minv, d_Xt);
+    hipLaunchKernelGGL(k_hmc_begin, dim3(M), dim3(256), 0, h->stream, pgl_hmc_view(d_state, M, P), d_minv, M, d_Xt);
     HIPCHK(hipGetLastError());
     return PGL_OK;
 }
@@ -2063,17 +2063,24 @@ int pgl_hmc_leap_dev(pgl_handle h, double* d_state, int M, int P, const double* 
 // The kick and the drift are epilogues of the products (pglm_hmc_dense.hip.h): no product is ever stored, no workspace.
 long long pgl_hmc_dense_work_doubles(int M, int P) { (void)M; (void)P; return 0; }
 
-// one product launch: (trans, epilogue) is one of the four instantiations the chain and pgl_tri_matvec_dev use
+// The four (TRANS, EPI) instantiations of a product kernel that the chains and pgl_tri_matvec*_dev use: LAUNCH(TRANS, EPI, KC)
+// for the one that (trans, epi) names.
+#define PGL_TRI_DISPATCH(LAUNCH, KC)                                           \
+    do {                                                                       \
+        if (epi == PGL_TRI_KICK) LAUNCH(1, PGL_TRI_KICK, KC);                  \
+        else if (epi == PGL_TRI_DRIFT) LAUNCH(0, PGL_TRI_DRIFT, KC);           \
+        else if (trans) LAUNCH(1, PGL_TRI_STORE, KC);                          \
+        else LAUNCH(0, PGL_TRI_STORE, KC);                                     \
+    } while (0)
+
+// one product launch, one vector per matrix (the chain, NUTS, pgl_tri_matvec_dev)
 static int tri_launch(pgl_handle h, int trans, int epi, const double* d_W, int M, int P, const double* d_x, double* d_y,
                       double* d_Xt, const double* d_step, double scale)
 {
     if (M > 65535) return fail(PGL_ERR_ARG, "at most 65535 rows per call");
     const dim3 grid(h->opt_tri_rows ? 1 : (P + PGL_TRI_TILE - 1) / PGL_TRI_TILE, M);
-#define PGL_TRI_LAUNCH(T, E) hipLaunchKernelGGL((k_tri_matvec<T, E>), grid, dim3(256), 0, h->stream, d_W, d_x, P, d_y, d_Xt, d_step, scale)
-    if (epi == PGL_TRI_KICK) PGL_TRI_LAUNCH(1, PGL_TRI_KICK);
-    else if (epi == PGL_TRI_DRIFT) PGL_TRI_LAUNCH(0, PGL_TRI_DRIFT);
-    else if (trans) PGL_TRI_LAUNCH(1, PGL_TRI_STORE);
-    else PGL_TRI_LAUNCH(0, PGL_TRI_STORE);
+#define PGL_TRI_LAUNCH(T, E, KC) hipLaunchKernelGGL((k_tri_matvec<T, E>), grid, dim3(256), 0, h->stream, d_W, d_x, P, d_y, d_Xt, d_step, scale)
+    PGL_TRI_DISPATCH(PGL_TRI_LAUNCH, 1);
 #undef PGL_TRI_LAUNCH
     HIPCHK(hipGetLastError());
     return PGL_OK;
@@ -2277,7 +2284,8 @@ int pgl_ais_begin_dev(pgl_handle h, double* d_state, int K, int M, int P, const 
     if (!h || !d_state || !d_Xt || K <= 0 || M <= 0 || P <= 0 || (long long)K * M > 0x7fffffffLL)
         return fail(PGL_ERR_ARG, "bad argument");
     HIPCHK(hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_ais_begin, dim3(K * M), dim3(256), 0, h->stream, pgl_ais_view(d_state, K, M, P), d_minv, d_Xt);
+    hipLaunchKernelGGL(k_hmc_begin, dim3(K * M), dim3(256), 0, h->stream, pgl_ais_hmc_view(pgl_ais_view(d_state, K, M, P)), d_minv, M,
+                       d_Xt);
     HIPCHK(hipGetLastError());
     return PGL_OK;
 }
@@ -2305,18 +2313,10 @@ static int tri_shared_launch(pgl_handle h, int trans, int epi, const double* d_W
     if (M > 65535) return fail(PGL_ERR_ARG, "at most 65535 neurons per call");
     const dim3 grid((P + PGL_TRI_TILE - 1) / PGL_TRI_TILE, M);
 #define PGL_TRI_LAUNCH(T, E, KC) hipLaunchKernelGGL((k_tri_matvec_shared<T, E, KC>), grid, dim3(256), 0, h->stream, d_W, d_x, K, M, P, d_y, d_Xt, d_step, scale)
-#define PGL_TRI_LAUNCH_KC(KC)                                                  \
-    do {                                                                       \
-        if (epi == PGL_TRI_KICK) PGL_TRI_LAUNCH(1, PGL_TRI_KICK, KC);          \
-        else if (epi == PGL_TRI_DRIFT) PGL_TRI_LAUNCH(0, PGL_TRI_DRIFT, KC);   \
-        else if (trans) PGL_TRI_LAUNCH(1, PGL_TRI_STORE, KC);                  \
-        else PGL_TRI_LAUNCH(0, PGL_TRI_STORE, KC);                             \
-    } while (0)
-    if (K == 1) PGL_TRI_LAUNCH_KC(1);
-    else if (K == 2) PGL_TRI_LAUNCH_KC(2);
-    else if (K <= 4) PGL_TRI_LAUNCH_KC(4);
-    else PGL_TRI_LAUNCH_KC(PGL_TRI_SHARED_KC);
-#undef PGL_TRI_LAUNCH_KC
+    if (K == 1) PGL_TRI_DISPATCH(PGL_TRI_LAUNCH, 1);
+    else if (K == 2) PGL_TRI_DISPATCH(PGL_TRI_LAUNCH, 2);
+    else if (K <= 4) PGL_TRI_DISPATCH(PGL_TRI_LAUNCH, 4);
+    else PGL_TRI_DISPATCH(PGL_TRI_LAUNCH, PGL_TRI_SHARED_KC);
 #undef PGL_TRI_LAUNCH
     HIPCHK(hipGetLastError());
     return PGL_OK;
@@ -2336,7 +2336,7 @@ int pgl_ais_dense_begin_dev(pgl_handle h, double* d_state, int K, int M, int P, 
         return fail(PGL_ERR_ARG, "bad argument");
     HIPCHK(hipSetDevice(h->device));
     const AisView v = pgl_ais_view(d_state, K, M, P);
-    hipLaunchKernelGGL(k_ais_dense_draw, dim3(K * M), dim3(256), 0, h->stream, v);
+    hipLaunchKernelGGL(k_hmc_dense_draw, dim3(K * M), dim3(256), 0, h->stream, pgl_ais_hmc_view(v));
     HIPCHK(hipGetLastError());
     const double* step = v.sc + (size_t)2 * v.R;
     int rc = tri_shared_launch(h, 1, PGL_TRI_KICK, d_W, K, M, P, v.g, v.p, nullptr, step, 0.5);

@@ -10,7 +10,7 @@
 // its gradient and the NaN rules.  All state lives in ONE device block of doubles laid out by pgl_hmc_view.  Every row
 // takes the same number of steps: no lists, no flags, nothing for the host to read before the chain has ended.
 // ---------------------------------------------------------------------------
-#include "pglm_hmc.h"
+#include "pglm_hmc_dense.h"                     // (pglm_hmc.h, and the dense chain's per-element rules)
 
 struct HmcView {
     int M, P;
@@ -30,8 +30,10 @@ __host__ __device__ inline HmcView pgl_hmc_view(double* st, int M, int P)
     v.sc = st + PGL_HMC_NVEC * MP;
     return v;
 }
-#define PGL_HMC_FIELDS(F) F(U0, 0) F(H0, 1) F(step, 2) F(avg_accept, 3) F(n_accept, 4) F(t, 5) F(acc, 6) F(neuron, 7) \
-    F(seed_lo, 8) F(seed_hi, 9)
+// (IN: the fields as members of IN -- empty here, `h.` for the PglHmc at the head of PglAis, whose rows are these)
+#define PGL_HMC_FIELDS_IN(F, IN) F(IN U0, 0) F(IN H0, 1) F(IN step, 2) F(IN avg_accept, 3) F(IN n_accept, 4) F(IN t, 5) \
+    F(IN acc, 6) F(IN neuron, 7) F(IN seed_lo, 8) F(IN seed_hi, 9)
+#define PGL_HMC_FIELDS(F) PGL_HMC_FIELDS_IN(F, )
 __device__ __forceinline__ void pgl_hmc_load(const HmcView& v, int r, PglHmc* s)
 {
 #define PGL_HMC_LD(name, k) s->name = v.sc[(size_t)k * v.M + r];
@@ -88,18 +90,21 @@ __global__ __launch_bounds__(256) void k_hmc_init(const HmcView v, double* __res
     }
 }
 
-// start of a transition: momentum, H0, the half kick with grad U at q, the first drift; Xt[row] = the point to evaluate
-__global__ __launch_bounds__(256) void k_hmc_begin(const HmcView v, const double* __restrict__ minv, double* __restrict__ Xt)
+// start of a transition: momentum, H0, the half kick with grad U at q, the first drift; Xt[row] = the point to evaluate.
+// minv (minv_rows, P): row r runs on row r mod minv_rows (the chain: minv_rows = M; the K M rows of an annealed importance
+// sampling run, particle-major, share the M rows of their neurons)
+__global__ __launch_bounds__(256) void k_hmc_begin(const HmcView v, const double* __restrict__ minv, const int minv_rows,
+                                                   double* __restrict__ Xt)
 {
     __shared__ double red[12];
     const int r = blockIdx.x, tid = threadIdx.x, P = v.P;
-    const size_t o = (size_t)r * P;
+    const size_t o = (size_t)r * P, om = (size_t)(r % minv_rows) * P;
     PglHmc s;
     pgl_hmc_load(v, r, &s);
     const pgl_hmc_u64 key = pgl_hmc_row_key(&s);
     double ks = 0.0;
     for (int c = tid; c < P; c += 256) {
-        const double mi = minv ? minv[o + c] : 1.0;
+        const double mi = minv ? minv[om + c] : 1.0;
         const double q0 = v.q[o + c];
         double p = pgl_hmc_momentum(pgl_hmc_normal(key, (pgl_hmc_u64)c), mi);
         ks += pgl_hmc_kinetic_elem(p, mi);
@@ -114,6 +119,55 @@ __global__ __launch_bounds__(256) void k_hmc_begin(const HmcView v, const double
     if (tid == 0) {
         pgl_hmc_begin(&s, ks);
         v.sc[(size_t)1 * v.M + r] = s.H0;
+    }
+}
+
+// ---- the end of a transition, shared by the diagonal and the dense kernels of the chain and of annealed importance sampling ----
+// The kinetic sum of one row (p, gu, minv: the row's P entries) in every thread.  DENSE 0: the last half kick p -= step/2 gu
+// first (p is rewritten), then sum p^2 minv (minv null: 1).  DENSE 1: p holds the whitened momentum, kicked by the product
+// already: sum r^2.
+template <int DENSE>
+__device__ __forceinline__ double pgl_hmc_end_kinetic(double* p, const double* gu, const double* minv, const double step,
+                                                      const int P, double* red, const int tid)
+{
+    double ks = 0.0;
+    for (int c = tid; c < P; c += 256) {
+        if (DENSE) ks += pgl_hmcd_kinetic_elem(p[c]);
+        else {
+            const double mi = minv ? minv[c] : 1.0;
+            const double pc = pgl_hmc_kick(p[c], 0.5, step, gu[c]);
+            p[c] = pc;
+            ks += pgl_hmc_kinetic_elem(pc, mi);
+        }
+    }
+    return pgl_blk_sum(ks, red);
+}
+// H1 from U1 and ks, the decision (*dec, shared), the step-size rule while t < n_warmup, t += 1; then accept (grad_row, grad
+// U of the new point, is kept) or restore q0, and the row's point into sample_out[row] (null: none)
+__device__ __forceinline__ void pgl_hmc_finish_row(const HmcView& v, const int r, const double U1, const double ks,
+                                                   const double* grad_row, const int n_warmup, double* sample_out, int* dec,
+                                                   const int tid)
+{
+    const size_t o = (size_t)r * v.P;
+    if (tid == 0) {
+        PglHmc s;
+        pgl_hmc_load(v, r, &s);
+        const double u = pgl_hmc_accept_uniform(pgl_hmc_row_key(&s));
+        *dec = pgl_hmc_decide(&s, U1, ks, u, n_warmup);
+        pgl_hmc_store(v, r, &s);
+    }
+    __syncthreads();
+    const bool acc = *dec != 0;
+    for (int c = tid; c < v.P; c += 256) {
+        double qc;
+        if (acc) {
+            qc = v.q[o + c];
+            v.g[o + c] = grad_row[c];
+        } else {
+            qc = v.q0[o + c];
+            v.q[o + c] = qc;
+        }
+        if (sample_out) sample_out[o + c] = qc;
     }
 }
 
@@ -143,33 +197,7 @@ __global__ __launch_bounds__(256) void k_hmc_leap(const HmcView v, const double*
         if (tid == 0) ll[r] = U1;
         return;
     }
-    double ks = 0.0;
-    for (int c = tid; c < P; c += 256) {
-        const double mi = minv ? minv[o + c] : 1.0;
-        const double p = pgl_hmc_kick(v.p[o + c], 0.5, step, grad[o + c]);
-        v.p[o + c] = p;
-        ks += pgl_hmc_kinetic_elem(p, mi);
-    }
-    ks = pgl_blk_sum(ks, red);
-    if (tid == 0) {
-        PglHmc s;
-        pgl_hmc_load(v, r, &s);
-        const double u = pgl_hmc_accept_uniform(pgl_hmc_row_key(&s));
-        dec = pgl_hmc_decide(&s, U1, ks, u, n_warmup);
-        pgl_hmc_store(v, r, &s);
-        ll[r] = U1;
-    }
-    __syncthreads();
-    const bool acc = dec != 0;
-    for (int c = tid; c < P; c += 256) {
-        double qc;
-        if (acc) {
-            qc = v.q[o + c];
-            v.g[o + c] = grad[o + c];
-        } else {
-            qc = v.q0[o + c];
-            v.q[o + c] = qc;
-        }
-        if (sample_out) sample_out[o + c] = qc;
-    }
+    const double ks = pgl_hmc_end_kinetic<0>(v.p + o, grad + o, minv ? minv + o : nullptr, step, P, red, tid);
+    if (tid == 0) ll[r] = U1;
+    pgl_hmc_finish_row(v, r, U1, ks, grad + o, n_warmup, sample_out, &dec, tid);
 }

@@ -101,38 +101,16 @@ __global__ __launch_bounds__(256) void k_hmc_dense_target(const HmcView v, doubl
     if (tid == 0) ll[r] = U1;
 }
 
-// end of a transition, after the last half kick: H1 from U1 = ll[row] and r, the decision, the step-size rule while
-// t < n_warmup, t += 1, accept (grad U of the new point is kept) or restore, the row's point into sample_out[row] (null:
-// none) -- the last branch of k_hmc_leap
+// end of a transition, after the last half kick: H1 from U1 = ll[row] and r, then pgl_hmc_finish_row as the last branch of
+// k_hmc_leap
 __global__ __launch_bounds__(256) void k_hmc_dense_end(const HmcView v, const double* __restrict__ ll,
                                                        const double* __restrict__ grad, const int n_warmup,
                                                        double* __restrict__ sample_out)
 {
     __shared__ double red[12];
     __shared__ int dec;
-    const int r = blockIdx.x, tid = threadIdx.x, P = v.P;
-    const size_t o = (size_t)r * P;
-    double ks = 0.0;
-    for (int c = tid; c < P; c += 256) ks += pgl_hmcd_kinetic_elem(v.p[o + c]);
-    ks = pgl_blk_sum(ks, red);
-    if (tid == 0) {
-        PglHmc s;
-        pgl_hmc_load(v, r, &s);
-        const double u = pgl_hmc_accept_uniform(pgl_hmc_row_key(&s));
-        dec = pgl_hmc_decide(&s, ll[r], ks, u, n_warmup);
-        pgl_hmc_store(v, r, &s);
-    }
-    __syncthreads();
-    const bool acc = dec != 0;
-    for (int c = tid; c < P; c += 256) {
-        double qc;
-        if (acc) {
-            qc = v.q[o + c];
-            v.g[o + c] = grad[o + c];
-        } else {
-            qc = v.q0[o + c];
-            v.q[o + c] = qc;
-        }
-        if (sample_out) sample_out[o + c] = qc;
-    }
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const size_t o = (size_t)r * v.P;
+    const double ks = pgl_hmc_end_kinetic<1>(v.p + o, nullptr, nullptr, 0.0, v.P, red, tid);
+    pgl_hmc_finish_row(v, r, ll[r], ks, grad + o, n_warmup, sample_out, &dec, tid);
 }

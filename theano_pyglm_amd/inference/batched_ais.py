@@ -37,7 +37,9 @@ packings, time-sharded populations.
 import numpy as np
 
 from theano_pyglm_amd.inference.batched_bfgs import _Packing
-from theano_pyglm_amd.inference.batched_hmc import _check, _laplace_minv, _STREAMS, factor_inverse_mass
+from theano_pyglm_amd.inference.batched_hmc import _check, _laplace_minv, resolve_mass  # noqa: F401  (_laplace_minv: what
+#                                                                        mass='laplace' computes, for callers that freeze it)
+from theano_pyglm_amd.inference.lockstep import session
 from theano_pyglm_amd.inference.batched_newton_cg import supported  # noqa: F401  (the served populations: these, Gaussian)
 
 # the state block (include/pyglm_hip.h): NVEC (R, P) arrays, then the rows of the scalar block (PglAis, csrc/pglm_ais.h)
@@ -164,51 +166,17 @@ def ais_glms(population, x, n_particles=16, betas=None, n_temps=200, n_steps=1, 
     if K <= 0 or n_steps <= 0 or n_leapfrog <= 0 or int(particle0) < 0:
         raise ValueError("n_particles, n_steps and n_leapfrog must be positive, particle0 not negative")
     betas = reference_ladder(n_temps) if betas is None else check_ladder(betas)
-    import torch
-    N = population.N
-    n_hi = N if n_hi is None else n_hi
+    n_hi = population.N if n_hi is None else n_hi
     M = n_hi - n_lo
     if M <= 0:
         raise ValueError("empty neuron range")
     if _Packing(population, None).prior_params()[0] != 0:
         raise ValueError("annealed importance sampling starts from an exact prior draw: Gaussian impulse priors only "
                          "(group lasso is not served)")
-    factor = None
-    if isinstance(mass, str):
-        if mass == 'laplace':
-            mass = _laplace_minv(population, x, n_lo, n_hi, float(mass_floor))
-        elif mass == 'laplace_dense':
-            factor, mass = 'tempered', None
-        else:
-            raise ValueError("mass: None, 'laplace', 'laplace_dense', an (M, P) or an (M, P, P) array")
-    elif mass is not None and np.ndim(mass) == 3:
-        P = population.glm.P
-        if np.shape(mass) != (M, P, P):
-            raise ValueError("mass: an (M, P, P) = (%d, %d, %d) array of inverse mass matrices" % (M, P, P))
-        factor, mass = factor_inverse_mass(mass), None
-    dev = torch.device('cuda', population.device)
-    handles = []
-    for data in population.data_sequences:
-        population.set_data(data)
-        handles.append(population._handle(data))
-    stream = _STREAMS.get(dev.index)
-    if stream is None:
-        stream = _STREAMS[dev.index] = torch.cuda.Stream(dev)
-    stream.wait_stream(torch.cuda.current_stream(dev))
-    for h in handles:
-        h.set_stream(stream.cuda_stream)
-    try:
-        with torch.cuda.stream(stream):
-            out = _run(population, torch, dev, stream, handles, x, K, betas, n_steps, n_leapfrog, step_sz, bool(pilot), mass,
-                       int(seed), int(particle0), n_lo, n_hi, M, factor, float(mass_floor))
-    finally:
-        try:
-            stream.synchronize()
-        except Exception:
-            pass
-        for h in handles:
-            h.set_stream(None)
-    return out
+    minv, factor, _, _ = resolve_mass(population, x, mass, n_lo, n_hi, mass_floor, dense='tempered')
+    with session(population) as (torch, dev, stream, handles):
+        return _run(population, torch, dev, stream, handles, x, K, betas, n_steps, n_leapfrog, step_sz, bool(pilot), minv,
+                    int(seed), int(particle0), n_lo, n_hi, M, factor, float(mass_floor))
 
 
 def _run(population, torch, dev, stream, handles, x, K, betas, n_steps, n_leapfrog, step_sz, pilot, mass, seed, particle0,
@@ -221,12 +189,8 @@ def _run(population, torch, dev, stream, handles, x, K, betas, n_steps, n_leapfr
     f64 = torch.float64
     J = betas.size - 1
     Weff = torch.tensor(population.W_eff(x), dtype=f64, device=dev)
-    minv = None
-    if mass is not None:
-        mh = np.ascontiguousarray(mass, dtype=float)
-        if mh.shape != (M, P) or not np.all(np.isfinite(mh)) or not np.all(mh > 0.0):
-            raise ValueError("mass: an (M, P) = (%d, %d) array of positive inverse masses" % (M, P))
-        minv = torch.tensor(mh, dtype=f64, device=dev)
+    assert P == population.glm.P                              # (resolve_mass checked mass against it)
+    minv = torch.tensor(mass, dtype=f64, device=dev) if mass is not None else None
     minv_ptr = minv.data_ptr() if minv is not None else 0
     if pilot:
         step0 = float(step_sz)

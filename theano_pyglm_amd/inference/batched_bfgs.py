@@ -24,6 +24,7 @@ import numpy as np
 from theano_pyglm_amd.components.bkgd import NoStimulus, BasisStimulus, SpatiotemporalStimulus
 from theano_pyglm_amd.components.impulse import LinearBasisImpulses, DirichletImpulses
 from theano_pyglm_amd.components.priors import Gaussian, GroupLasso
+from theano_pyglm_amd.inference.lockstep import session
 
 
 def supported(population):
@@ -284,37 +285,15 @@ def fit_glms_batched_torch(population, x, maxiter=225, gtol=1e-5, n_lo=0, n_hi=N
                 stats['groups'] += 1
         population.last_fit_stats = stats
         return np.concatenate(nlps), its, evs
-    handles = []
-    for data in population.data_sequences:
-        population.set_data(data)
-        handles.append(population._handle(data))
-    # the optimiser's stream: one per device, kept between fits (a fresh stream costs its first wait ~6 ms: the hardware
-    # queue behind it is created on first use)
-    stream = _STREAMS.get(dev.index)
-    if stream is None:
-        stream = _STREAMS[dev.index] = torch.cuda.Stream(dev)
-    stream.wait_stream(torch.cuda.current_stream(dev))        # whatever the caller queued comes first
-    for h in handles:
-        h.set_stream(stream.cuda_stream)
-    try:
-        with torch.cuda.stream(stream):
-            out = _lockstep_bfgs(population, torch, dev, stream, handles, x, maxiter, gtol, n_lo, n_hi, M,
-                                 verbose, reduce, 0 if lag is None else max(0, int(lag)), init_scaling, max_trials, hessian)
-            stream.synchronize()
-    finally:
-        # also on the error path: kernels still queued on `stream` read the optimizer state and the handles' scratch;
-        # let them finish before the caching allocator reuses the tensors and the handles go back to their own streams
-        try:
-            stream.synchronize()
-        except Exception:
-            pass
-        for h in handles:
-            h.set_stream(None)
+    # everything runs on the lock-step drivers' stream, which the device handles are switched to (lockstep.session)
+    with session(population) as (torch, dev, stream, handles):
+        out = _lockstep_bfgs(population, torch, dev, stream, handles, x, maxiter, gtol, n_lo, n_hi, M,
+                             verbose, reduce, 0 if lag is None else max(0, int(lag)), init_scaling, max_trials, hessian)
+        stream.synchronize()
     return out
 
 
 _HOST_BUFFERS = {}
-_STREAMS = {}
 
 
 def _host_buffers(torch, M, nring):

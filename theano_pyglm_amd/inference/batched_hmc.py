@@ -31,12 +31,11 @@ import numpy as np
 
 from theano_pyglm_amd.inference.batched_bfgs import _Packing
 from theano_pyglm_amd.inference.batched_newton_cg import supported  # noqa: F401  (the served populations are the same)
+from theano_pyglm_amd.inference.lockstep import RangeEvaluator, session
 
 # rows of the scalar block of the state (PglHmc, csrc/pglm_hmc.h)
 SC_U0, SC_H0, SC_STEP, SC_AVG, SC_NACC, SC_T, SC_ACC = 0, 1, 2, 3, 4, 5, 6
 NSCAL = 10
-
-_STREAMS = {}
 
 
 def _check(population):
@@ -144,6 +143,40 @@ def _laplace_dense_factor_device(population, x, n_lo, n_hi, floor):
     return W, dense_h
 
 
+def resolve_mass(population, x, mass, n_lo, n_hi, mass_floor, factor_on_device=False, dense='laplace'):
+    """The mass= argument of the samplers for the rows [n_lo, n_hi) -> (minv, factor, dense_rows, setup_s): minv (M, P)
+    positive inverse masses on the host or None; factor (M, P, P) lower-triangular W with W W^T = the inverse mass matrix
+    (host array, or a device tensor with factor_on_device) or None; dense_rows (M,) bool with 'laplace_dense', else None;
+    setup_s: the seconds spent on Hessians and factorisations.  dense='tempered' (annealed importance sampling, which
+    builds one factor per temperature itself): 'laplace_dense' gives factor = 'tempered' and computes nothing."""
+    import time
+    t0 = time.perf_counter()
+    M, P = n_hi - n_lo, population.glm.P
+    minv = factor = dense_rows = None
+    if isinstance(mass, str):
+        if mass == 'laplace':
+            minv = _laplace_minv(population, x, n_lo, n_hi, float(mass_floor))
+        elif mass == 'laplace_dense' and dense == 'tempered':
+            factor = 'tempered'
+        elif mass == 'laplace_dense':
+            build = _laplace_dense_factor_device if factor_on_device else _laplace_dense_factor
+            factor, dense_rows = build(population, x, n_lo, n_hi, float(mass_floor))
+        else:
+            raise ValueError("mass: None, 'laplace', 'laplace_dense', an (M, P) or an (M, P, P) array")
+    elif mass is not None and np.ndim(mass) == 3:
+        if np.shape(mass) != (M, P, P):
+            raise ValueError("mass: an (M, P, P) = (%d, %d, %d) array of inverse mass matrices" % (M, P, P))
+        factor = factor_inverse_mass(mass)
+    else:
+        minv = mass
+    setup_s = time.perf_counter() - t0
+    if minv is not None:
+        minv = np.ascontiguousarray(minv, dtype=float)
+        if minv.shape != (M, P) or not np.all(np.isfinite(minv)) or not np.all(minv > 0.0):
+            raise ValueError("mass: an (M, P) = (%d, %d) array of positive inverse masses" % (M, P))
+    return minv, factor, dense_rows, setup_s
+
+
 def sample_glms_hmc(population, x, n_samples, n_warmup=200, n_leapfrog=10, step_sz=0.1, thin=1, mass=None, seed=0,
                     n_lo=0, n_hi=None, mass_floor=1e-8, factor_on_device=False):
     """Posterior samples of the parameter rows of neurons [n_lo, n_hi) given the rest of x, started at x.
@@ -166,53 +199,14 @@ def sample_glms_hmc(population, x, n_samples, n_warmup=200, n_leapfrog=10, step_
     n_samples, n_warmup, n_leapfrog, thin = int(n_samples), int(n_warmup), int(n_leapfrog), int(thin)
     if n_samples <= 0 or n_warmup < 0 or n_leapfrog <= 0 or thin <= 0:
         raise ValueError("n_samples, n_leapfrog and thin must be positive, n_warmup not negative")
-    import torch
-    N = population.N
-    n_hi = N if n_hi is None else n_hi
+    n_hi = population.N if n_hi is None else n_hi
     M = n_hi - n_lo
     if M <= 0:
         raise ValueError("empty neuron range")
-    import time
-    t0 = time.perf_counter()
-    factor = dense_rows = None
-    if isinstance(mass, str):
-        if mass == 'laplace':
-            mass = _laplace_minv(population, x, n_lo, n_hi, float(mass_floor))
-        elif mass == 'laplace_dense':
-            build = _laplace_dense_factor_device if factor_on_device else _laplace_dense_factor
-            factor, dense_rows = build(population, x, n_lo, n_hi, float(mass_floor))
-            mass = None
-        else:
-            raise ValueError("mass: None, 'laplace', 'laplace_dense', an (M, P) or an (M, P, P) array")
-    elif mass is not None and np.ndim(mass) == 3:
-        P = population.glm.P
-        if np.shape(mass) != (M, P, P):
-            raise ValueError("mass: an (M, P, P) = (%d, %d, %d) array of inverse mass matrices" % (M, P, P))
-        factor = factor_inverse_mass(mass)
-        mass = None
-    setup_s = time.perf_counter() - t0
-    dev = torch.device('cuda', population.device)
-    handles = []
-    for data in population.data_sequences:
-        population.set_data(data)
-        handles.append(population._handle(data))
-    stream = _STREAMS.get(dev.index)
-    if stream is None:
-        stream = _STREAMS[dev.index] = torch.cuda.Stream(dev)
-    stream.wait_stream(torch.cuda.current_stream(dev))
-    for h in handles:
-        h.set_stream(stream.cuda_stream)
-    try:
-        with torch.cuda.stream(stream):
-            out = _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, n_leapfrog, step_sz, thin, mass,
-                         int(seed), n_lo, n_hi, M, factor)
-    finally:
-        try:
-            stream.synchronize()
-        except Exception:
-            pass
-        for h in handles:
-            h.set_stream(None)
+    minv, factor, dense_rows, setup_s = resolve_mass(population, x, mass, n_lo, n_hi, mass_floor, factor_on_device)
+    with session(population) as (torch, dev, stream, handles):
+        out = _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, n_leapfrog, step_sz, thin, minv,
+                     int(seed), n_lo, n_hi, M, factor)
     if dense_rows is not None:
         out['dense_rows'] = dense_rows
     population.last_fit_stats['mass_setup_s'] = setup_s
@@ -233,37 +227,24 @@ def _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, n_le
     sc = st[4 * MP:].view(NSCAL, M)
     q.copy_(torch.tensor(pk.pack(x, n_lo, n_hi), dtype=f64, device=dev))
     Weff = torch.tensor(population.W_eff(x), dtype=f64, device=dev)
-    minv = None
-    if mass is not None:
-        mh = np.ascontiguousarray(mass, dtype=float)
-        if mh.shape != (M, P) or not np.all(np.isfinite(mh)) or not np.all(mh > 0.0):
-            raise ValueError("mass: an (M, P) = (%d, %d) array of positive inverse masses" % (M, P))
-        minv = torch.tensor(mh, dtype=f64, device=dev)
+    assert P == population.glm.P                              # (resolve_mass checked mass against it)
+    minv = torch.tensor(mass, dtype=f64, device=dev) if mass is not None else None
     step = np.ascontiguousarray(np.broadcast_to(np.asarray(step_sz, dtype=float), (M,)))
     if not np.all(step > 0.0):
         raise ValueError("step_sz must be positive")
     minv_ptr = minv.data_ptr() if minv is not None else 0
-    Wd = work = None
+    Wd = None
     if factor is not None:                                    # (M, P, P) lower-triangular factors: uploaded once
         assert tuple(factor.shape) == (M, P, P)
         Wd = factor if torch.is_tensor(factor) else torch.tensor(factor, dtype=f64, device=dev)
-        work = torch.empty(h0.hmc_dense_work_doubles(M, P), dtype=f64, device=dev)
     Xt = torch.empty((M, P), dtype=f64, device=dev)
-    bufs = [torch.empty(M * (1 + P), dtype=f64, device=dev) for _ in handles]     # [ll | grad] per data sequence
+    evaluate = RangeEvaluator(torch, dev, handles, Weff, M, P, n_lo, n_hi)
     samples = torch.empty((n_samples, M, P), dtype=f64, device=dev)
-    counts = {'ll_grad': 0, 'row': 0, 'syncs': 0}
+    counts = {'row': 0, 'syncs': 0}
 
     def wait():
         counts['syncs'] += 1
         stream.synchronize()
-
-    def evaluate(Xe):
-        tot = None
-        for h, buf in zip(handles, bufs):
-            h.ll_grad_dev(Xe.data_ptr(), Weff.data_ptr(), buf.data_ptr(), buf[M:].data_ptr(), n_lo, n_hi)
-            tot = buf if tot is None else tot.add_(buf)
-        counts['ll_grad'] += 1
-        return tot[:M], tot[M:]
 
     ll0, g0 = evaluate(q)
     h0.hmc_init_dev(st.data_ptr(), M, P, n_lo, ll0.data_ptr(), g0.data_ptr(), prm, float(step[0]), seed)
@@ -271,10 +252,10 @@ def _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, n_le
         sc[SC_STEP].copy_(torch.tensor(step, dtype=f64, device=dev))
     n_total = n_warmup + n_samples * thin
     syncs_before_chain = counts['syncs']
-    evals_before_chain = counts['ll_grad']
+    evals_before_chain = evaluate.count
     for t in range(n_total):
         if Wd is not None:
-            h0.hmc_dense_begin_dev(st.data_ptr(), M, P, Wd.data_ptr(), work.data_ptr(), Xt.data_ptr())
+            h0.hmc_dense_begin_dev(st.data_ptr(), M, P, Wd.data_ptr(), 0, Xt.data_ptr())
         else:
             h0.hmc_begin_dev(st.data_ptr(), M, P, minv_ptr, Xt.data_ptr())
         counts['row'] += 1
@@ -285,7 +266,7 @@ def _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, n_le
             last = i == n_leapfrog - 1
             out_ptr = samples[k // thin].data_ptr() if (last and keep) else 0
             if Wd is not None:
-                h0.hmc_dense_leap_dev(st.data_ptr(), M, P, Wd.data_ptr(), work.data_ptr(), llt.data_ptr(), gt.data_ptr(), prm,
+                h0.hmc_dense_leap_dev(st.data_ptr(), M, P, Wd.data_ptr(), 0, llt.data_ptr(), gt.data_ptr(), prm,
                                       last, n_warmup, Xt.data_ptr(), out_ptr)
             else:
                 h0.hmc_leap_dev(st.data_ptr(), M, P, minv_ptr, llt.data_ptr(), gt.data_ptr(), prm, last, n_warmup,
@@ -295,12 +276,12 @@ def _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, n_le
     wait()
     sch = sc.cpu().numpy()
     out = {'samples': samples.cpu().numpy(), 'accept_rate': sch[SC_NACC] / float(n_samples * thin), 'step_sz': sch[SC_STEP].copy(),
-           'n_evals': counts['ll_grad']}
+           'n_evals': evaluate.count}
     # ('row' counts the begin / leap CALLS of the C ABI; a dense call is three small launches, a diagonal one is one)
     population.last_fit_stats = {'sampler': 'lock-step HMC (hip row kernels)', 'transitions': n_total,
                                  'mass': 'dense' if Wd is not None else ('diagonal' if minv is not None else 'identity'),
-                                 'll_grad_launches': counts['ll_grad'], 'row_launches': counts['row'],
-                                 'evaluations_per_transition': (counts['ll_grad'] - evals_before_chain) / float(n_total),
+                                 'll_grad_launches': evaluate.count, 'row_launches': counts['row'],
+                                 'evaluations_per_transition': (evaluate.count - evals_before_chain) / float(n_total),
                                  'row_launches_per_transition': counts['row'] / float(n_total),
                                  'host_syncs_in_chain': syncs_in_chain, 'host_syncs': counts['syncs']}
     return out

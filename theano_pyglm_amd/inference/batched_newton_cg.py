@@ -25,6 +25,7 @@ a Gaussian or group-lasso prior).  Time-sharded populations are not (the driver 
 import numpy as np
 
 from theano_pyglm_amd.inference.batched_bfgs import _Packing
+from theano_pyglm_amd.inference.lockstep import RangeEvaluator, session
 
 PHASE_CG, PHASE_SEARCH, PHASE_DONE = 0.0, 1.0, 2.0
 # rows of the scalar block of the state (PglNcg, csrc/pglm_ncg.h)
@@ -45,7 +46,6 @@ def _check(population):
 
 
 _HOST_BUFFERS = {}
-_STREAMS = {}
 
 
 def _host_buffers(torch, device_index, M):
@@ -68,34 +68,13 @@ def fit_glms_newton_cg_torch(population, x, maxiter=225, n_lo=0, n_hi=None, verb
     info = {'X', 'status', 'nit', 'nhev', 'applies'} (a synchronising copy: for tests and traces).
     population.last_fit_stats records the launch counts."""
     _check(population)
-    import torch
-    N = population.N
-    n_hi = N if n_hi is None else n_hi
+    n_hi = population.N if n_hi is None else n_hi
     M = n_hi - n_lo
     if M <= 0:
         raise ValueError("empty neuron range")
-    dev = torch.device('cuda', population.device)
-    handles = []
-    for data in population.data_sequences:
-        population.set_data(data)
-        handles.append(population._handle(data))
-    stream = _STREAMS.get(dev.index)
-    if stream is None:
-        stream = _STREAMS[dev.index] = torch.cuda.Stream(dev)
-    stream.wait_stream(torch.cuda.current_stream(dev))
-    for h in handles:
-        h.set_stream(stream.cuda_stream)
-    try:
-        with torch.cuda.stream(stream):
-            out = _lockstep(population, torch, dev, stream, handles, x, int(maxiter), n_lo, n_hi, M, verbose, on_outer)
-            stream.synchronize()
-    finally:
-        try:
-            stream.synchronize()
-        except Exception:
-            pass
-        for h in handles:
-            h.set_stream(None)
+    with session(population) as (torch, dev, stream, handles):
+        out = _lockstep(population, torch, dev, stream, handles, x, int(maxiter), n_lo, n_hi, M, verbose, on_outer)
+        stream.synchronize()
     return out
 
 
@@ -114,7 +93,7 @@ def _lockstep(population, torch, dev, stream, handles, x, maxiter, n_lo, n_hi, M
     X.copy_(torch.tensor(pk.pack(x, n_lo, n_hi), dtype=f64, device=dev))
     Weff = torch.tensor(population.W_eff(x), dtype=f64, device=dev)
     V = torch.zeros((M, P), dtype=f64, device=dev)            # input of the next product, written by the row kernels
-    bufs = [torch.empty(M * (1 + P), dtype=f64, device=dev) for _ in handles]     # [ll | grad] per data sequence
+    whole = RangeEvaluator(torch, dev, handles, Weff, M, P, n_lo, n_hi)          # (its buffers serve the lists too)
     hvs = [torch.empty((M, P), dtype=f64, device=dev) for _ in handles]
     Xts = [torch.empty((M, P), dtype=f64, device=dev) for _ in range(2)]
     lists = torch.empty(3 * M, dtype=torch.int32, device=dev)
@@ -130,18 +109,15 @@ def _lockstep(population, torch, dev, stream, handles, x, maxiter, n_lo, n_hi, M
 
     def evaluate(Xt, idx32, L):
         tot = None
-        for h, full in zip(handles, bufs):
+        for h, full in zip(handles, whole.bufs):
             buf = full[:L * (1 + P)]
-            if idx32 is None:
-                h.ll_grad_dev(Xt.data_ptr(), Weff.data_ptr(), buf.data_ptr(), buf[L:].data_ptr(), n_lo, n_hi)
-            else:
-                h.ll_grad_list_dev(idx32.data_ptr(), L, Xt.data_ptr(), Weff.data_ptr(), buf.data_ptr(), buf[L:].data_ptr())
+            h.ll_grad_list_dev(idx32.data_ptr(), L, Xt.data_ptr(), Weff.data_ptr(), buf.data_ptr(), buf[L:].data_ptr())
             tot = buf if tot is None else tot.add_(buf)
         counts['ll_grad'] += 1
         counts['neuron_evaluations'] += L
         return tot[:L], tot[L:]
 
-    ll0, g0 = evaluate(X, None, M)
+    ll0, g0 = whole(X)
     h0.ncg_init_dev(st.data_ptr(), M, P, ll0.data_ptr(), g0.data_ptr(), prm, maxiter, V.data_ptr(), flags.data_ptr())
     wait()
     while np.any(fl != PHASE_DONE):
@@ -203,7 +179,8 @@ def _lockstep(population, torch, dev, stream, handles, x, maxiter, n_lo, n_hi, M
     status = sch[SC_STATUS].astype(int)
     population.last_fit_stats = {'optimizer': 'lock-step Newton-CG (hip row kernels)', 'outer_iterations': counts['outer'],
                                  'apply_launches': counts['apply'], 'prepare_launches': counts['prepare'],
-                                 'll_grad_launches': counts['ll_grad'], 'neuron_evaluations': counts['neuron_evaluations'],
+                                 'll_grad_launches': counts['ll_grad'] + whole.count,
+                                 'neuron_evaluations': counts['neuron_evaluations'] + M * whole.count,
                                  'cg_lengths': list(counts['cg_lengths']), 'apply_kernels': counts.get('apply_kernels'),
                                  'per_neuron': {'nit': [int(v) for v in nit], 'nhev': [int(v) for v in nhev],
                                                 'nfev': [int(v) for v in nfev], 'status': [int(v) for v in status]}}

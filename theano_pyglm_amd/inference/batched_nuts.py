@@ -22,9 +22,10 @@ Served: the populations batched_hmc serves, with the same errors for the others.
 import numpy as np
 
 from theano_pyglm_amd.inference.batched_bfgs import _Packing
-from theano_pyglm_amd.inference.batched_hmc import (_STREAMS, _check, _laplace_dense_factor, _laplace_dense_factor_device,
-                                                    _laplace_minv, factor_inverse_mass, samples_to_states, summarize,
-                                                    supported)
+from theano_pyglm_amd.inference.batched_hmc import _check, resolve_mass
+from theano_pyglm_amd.inference.batched_hmc import (_laplace_minv, factor_inverse_mass, samples_to_states,  # noqa: F401
+                                                    summarize, supported)                                   # (the same here)
+from theano_pyglm_amd.inference.lockstep import RangeEvaluator, session
 
 # rows of the scalar block of the state (PglNuts, csrc/pglm_nuts.h)
 SC_STEP, SC_T, SC_DONE, SC_NLEAP, SC_NDIV, SC_ACC = 2, 3, 7, 21, 22, 23
@@ -53,59 +54,17 @@ def sample_glms_nuts(population, x, n_samples, n_warmup=200, max_depth=8, step_s
         raise ValueError("max_depth: 1 .. 10")
     if not 0.0 < float(target_accept) < 1.0:
         raise ValueError("target_accept: in (0, 1)")
-    import time
-    import torch
     n_hi = population.N if n_hi is None else n_hi
     M = n_hi - n_lo
     if M <= 0:
         raise ValueError("empty neuron range")
-    t0 = time.perf_counter()
-    factor = dense_rows = None
-    if isinstance(mass, str):
-        if mass == 'laplace':
-            mass = _laplace_minv(population, x, n_lo, n_hi, float(mass_floor))
-        elif mass == 'laplace_dense':
-            build = _laplace_dense_factor_device if factor_on_device else _laplace_dense_factor
-            factor, dense_rows = build(population, x, n_lo, n_hi, float(mass_floor))
-            mass = None
-        else:
-            raise ValueError("mass: None, 'laplace', 'laplace_dense', an (M, P) or an (M, P, P) array")
-    elif mass is not None and np.ndim(mass) == 3:
-        if np.shape(mass) != (M,) + (population.glm.P,) * 2:
-            raise ValueError("mass: an (M, P, P) = (%d, %d, %d) array of inverse mass matrices" % ((M,) + (population.glm.P,) * 2))
-        factor = factor_inverse_mass(mass)
-        mass = None
-    setup_s = time.perf_counter() - t0
-    P = population.glm.P
-    if mass is not None:
-        mass = np.ascontiguousarray(mass, dtype=float)
-        if mass.shape != (M, P) or not np.all(np.isfinite(mass)) or not np.all(mass > 0.0):
-            raise ValueError("mass: an (M, P) = (%d, %d) array of positive inverse masses" % (M, P))
+    mass, factor, dense_rows, setup_s = resolve_mass(population, x, mass, n_lo, n_hi, mass_floor, factor_on_device)
     step_sz = np.ascontiguousarray(np.broadcast_to(np.asarray(step_sz, dtype=float), (M,)))
     if not np.all(step_sz > 0.0):
         raise ValueError("step_sz must be positive")
-    dev = torch.device('cuda', population.device)
-    handles = []
-    for data in population.data_sequences:
-        population.set_data(data)
-        handles.append(population._handle(data))
-    stream = _STREAMS.get(dev.index)
-    if stream is None:
-        stream = _STREAMS[dev.index] = torch.cuda.Stream(dev)
-    stream.wait_stream(torch.cuda.current_stream(dev))
-    for h in handles:
-        h.set_stream(stream.cuda_stream)
-    try:
-        with torch.cuda.stream(stream):
-            out = _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, max_depth, step_sz,
-                         float(target_accept), thin, mass, int(seed), n_lo, n_hi, M, factor)
-    finally:
-        try:
-            stream.synchronize()
-        except Exception:
-            pass
-        for h in handles:
-            h.set_stream(None)
+    with session(population) as (torch, dev, stream, handles):
+        out = _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, max_depth, step_sz,
+                     float(target_accept), thin, mass, int(seed), n_lo, n_hi, M, factor)
     if dense_rows is not None:
         out['dense_rows'] = dense_rows
     population.last_fit_stats['mass_setup_s'] = setup_s
@@ -136,19 +95,11 @@ def _chain(population, torch, dev, stream, handles, x, n_keep, n_warmup, D, step
     minv_ptr = minv.data_ptr() if minv is not None else 0
     W_ptr = Wd.data_ptr() if Wd is not None else 0
     Xt = torch.empty((M, P), dtype=f64, device=dev)
-    bufs = [torch.empty(M * (1 + P), dtype=f64, device=dev) for _ in handles]     # [ll | grad] per data sequence
+    evaluate = RangeEvaluator(torch, dev, handles, Weff, M, P, n_lo, n_hi)
     samples = torch.zeros((n_keep, M, P), dtype=f64, device=dev)
     stats = torch.zeros((n_keep, 2, M), dtype=f64, device=dev)
     flags = [torch.zeros(M, dtype=f64).pin_memory() for _ in range(2)]
-    counts = {'ll_grad': 0, 'polls': 0}
-
-    def evaluate(Xe):
-        tot = None
-        for h, buf in zip(handles, bufs):
-            h.ll_grad_dev(Xe.data_ptr(), Weff.data_ptr(), buf.data_ptr(), buf[M:].data_ptr(), n_lo, n_hi)
-            tot = buf if tot is None else tot.add_(buf)
-        counts['ll_grad'] += 1
-        return tot[:M], tot[M:]
+    counts = {'polls': 0}
 
     ll0, g0 = evaluate(st[0:MP].view(M, P))
     h0.nuts_init_dev(st.data_ptr(), M, P, D, n_lo, ll0.data_ptr(), g0.data_ptr(), prm, minv_ptr, W_ptr, step0.data_ptr(), seed,
@@ -175,13 +126,13 @@ def _chain(population, torch, dev, stream, handles, x, n_keep, n_warmup, D, step
     sth = stats.cpu().numpy()
     nleap = sch[SC_NLEAP]
     out = {'samples': samples.cpu().numpy(), 'accept_rate': sch[SC_ACC] / float(n_keep * thin), 'step_sz': sch[SC_STEP].copy(),
-           'n_evals': counts['ll_grad'], 'depth': sth[:, 0].astype(int), 'n_leapfrog': sth[:, 1].astype(int),
+           'n_evals': evaluate.count, 'depth': sth[:, 0].astype(int), 'n_leapfrog': sth[:, 1].astype(int),
            'divergent': sch[SC_NDIV].astype(int), 'step': sch[SC_STEP].copy(), 'launches': launches,
            'idle_row_evaluations': int(np.sum(launches - nleap))}
     assert np.all(sch[SC_DONE] != 0.0) and np.all(sch[SC_T] == n_warmup + n_keep * thin)
     population.last_fit_stats = {'sampler': 'NUTS (hip row kernels)', 'transitions': n_warmup + n_keep * thin,
                                  'mass': 'dense' if Wd is not None else ('diagonal' if minv is not None else 'identity'),
-                                 'll_grad_launches': counts['ll_grad'], 'step_launches': launches,
+                                 'll_grad_launches': evaluate.count, 'step_launches': launches,
                                  'leapfrog_steps': nleap.astype(int), 'flag_reads': counts['polls'],
                                  'idle_share': float(np.sum(launches - nleap)) / float(launches * M)}
     return out

@@ -24,6 +24,7 @@ import numpy as np
 
 from theano_pyglm_amd.components.priors import GroupLasso
 from theano_pyglm_amd.inference.batched_bfgs import _Packing
+from theano_pyglm_amd.inference.lockstep import RangeEvaluator, session
 
 PHASE_Y, PHASE_TRIAL, PHASE_DONE = 0.0, 1.0, 2.0
 # rows of the scalar block of the state (PglProx, csrc/pglm_prox.h)
@@ -34,7 +35,6 @@ NVEC = 5
 POLL = 4                                                       # launches between two looks at the flags
 
 _HOST_FLAGS = {}
-_STREAMS = {}
 
 
 def supported(population):
@@ -97,29 +97,8 @@ def _fit(population, x, lam, maxiter, gtol, max_backtrack, n_lo, n_hi, verbose, 
     if M <= 0:
         raise ValueError("empty neuron range")
     lam = _row_lams(population, lam, M)
-    import torch
-    dev = torch.device('cuda', population.device)
-    handles = []
-    for data in population.data_sequences:
-        population.set_data(data)
-        handles.append(population._handle(data))
-    stream = _STREAMS.get(dev.index)
-    if stream is None:
-        stream = _STREAMS[dev.index] = torch.cuda.Stream(dev)
-    stream.wait_stream(torch.cuda.current_stream(dev))
-    for h in handles:
-        h.set_stream(stream.cuda_stream)
-    try:
-        with torch.cuda.stream(stream):
-            return _lockstep(population, torch, dev, stream, handles, x, lam, maxiter, gtol, max_backtrack, n_lo, n_hi, M, verbose,
-                             write)
-    finally:
-        try:
-            stream.synchronize()
-        except Exception:
-            pass
-        for h in handles:
-            h.set_stream(None)
+    with session(population) as (torch, dev, stream, handles):
+        return _lockstep(population, torch, dev, stream, handles, x, lam, maxiter, gtol, max_backtrack, n_lo, n_hi, M, verbose, write)
 
 
 def _lockstep(population, torch, dev, stream, handles, x, lam, maxiter, gtol, max_backtrack, n_lo, n_hi, M, verbose, write):
@@ -139,19 +118,11 @@ def _lockstep(population, torch, dev, stream, handles, x, lam, maxiter, gtol, ma
     Weff = torch.tensor(population.W_eff(x), dtype=f64, device=dev)
     d_lam = torch.tensor(lam, dtype=f64, device=dev)
     Xt = torch.empty((M, P), dtype=f64, device=dev)
-    bufs = [torch.empty(M * (1 + P), dtype=f64, device=dev) for _ in handles]     # [ll | grad] per data sequence
+    evaluate = RangeEvaluator(torch, dev, handles, Weff, M, P, n_lo, n_hi)
     flags = _flags(torch, dev.index, M)
     flags.fill_(PHASE_TRIAL)
     fl = flags.numpy()
-    counts = {'ll_grad': 0, 'row': 0, 'polls': 0}
-
-    def evaluate(Xe):
-        tot = None
-        for h, buf in zip(handles, bufs):
-            h.ll_grad_dev(Xe.data_ptr(), Weff.data_ptr(), buf.data_ptr(), buf[M:].data_ptr(), n_lo, n_hi)
-            tot = buf if tot is None else tot.add_(buf)
-        counts['ll_grad'] += 1
-        return tot[:M], tot[M:]
+    counts = {'row': 0, 'polls': 0}
 
     ll0, g0 = evaluate(X)
     h0.prox_init_dev(st.data_ptr(), M, P, ll0.data_ptr(), g0.data_ptr(), prm, d_lam.data_ptr(), gtol, maxiter, Xt.data_ptr(),
@@ -202,7 +173,7 @@ def _lockstep(population, torch, dev, stream, handles, x, lam, maxiter, gtol, ma
     res = {'status': sch[SC['status']].astype(int), 'iters': sch[SC['iters']].astype(int), 'nfev': sch[SC['nfev']].astype(int),
            'kkt': sch[SC['kkt']].copy(), 'objective': sch[SC['F_x']].copy(),
            'support': np.any(Xh[:, o:].reshape(M, pk.N, pk.B) != prm[3], axis=2), 'lam': lam.copy()}
-    population.last_fit_stats = {'optimizer': 'lock-step proximal gradient (hip row kernels)', 'll_grad_launches': counts['ll_grad'],
+    population.last_fit_stats = {'optimizer': 'lock-step proximal gradient (hip row kernels)', 'll_grad_launches': evaluate.count,
                                  'row_launches': counts['row'], 'flag_polls': counts['polls'], 'loop_s': loop_s,
                                  'restarts': [int(v) for v in sch[SC['restarts']]],
                                  'per_neuron': {'iters': [int(v) for v in res['iters']], 'nfev': [int(v) for v in res['nfev']],
