@@ -457,6 +457,51 @@ int pgl_nuts_step_dev(pgl_handle h, double* d_state, int M, int P, int max_depth
                       const double* d_minv, const double* d_W, double target_accept, int n_warmup, int thin, int n_keep,
                       double* d_Xt, double* d_samples, double* d_stats);
 
+/* Several chains per neuron, and a diagonal mass matrix learned during the warm-up (inference/batched_hmc.py and
+ * batched_nuts.py: n_chains, mass='adapt'; the rules are csrc/pglm_adapt.h, the host side inference/mass_adapt.py).
+ *   chains      a run of C chains of the M neurons n_lo .. n_lo + M - 1 has R = C M rows, chain-major: row c M + m is chain
+ *               c of neuron n_lo + m, so block c of any (R, P) array is the (M, P) theta block one pgl_ll_grad_dev(n_lo,
+ *               n_lo + M) takes and returns.  Chain c runs on the seed  chain_seed(seed, c) = seed for c = 0, else
+ *               mix(mix(seed + G) ^ (G c))  (64-bit; mix = pgl_hmc's finaliser, G = 0x9e3779b97f4a7c15), with the key
+ *               (that seed, neuron index, transition): chain c equals the single-chain run with that seed, bit for bit.
+ *               The init calls below set this up; every other call of the chain takes M = R rows (d_minv (R, P), d_W
+ *               (R, P, P): one per row).
+ *   schedule    host side, from n = n_warmup (Stan's windowed adaptation):  n < 20: no window.  n >= 150: init = 75, term
+ *               = 50, base = 25;  else init = floor(0.15 n), term = floor(0.10 n), base = n - init - term.  Windows start
+ *               at init, have sizes base, 2 base, 4 base, ... and tile [init, n - term): a window is stretched to n - term
+ *               unless its doubled successor would end before n - term.  d_sched (ints, on the device, uploaded once):
+ *               [n_win, start of window 0, end of window 0, end of window 1, ...].
+ *   estimate    per row and parameter a Welford count n, mean, M2 over the row's point q after every transition t of the
+ *               running window (a rejected transition contributes the repeated point):  d = q - mean;  mean += d / n;
+ *               M2 += d (q - mean).  After the transition with t + 1 = the window's end:  var = M2 / (n - 1);
+ *               minv = n / (n + 5) var + 1e-3 * 5 / (n + 5)  (non-finite: 1);  the row of d_minv is rewritten, the
+ *               accumulators are zeroed, and the row's step-size adaptation restarts -- HMC: avg_accept = 0.9, step kept;
+ *               NUTS: mu = log(10 step), Hbar = 0, log eps bar = 0, and the iterate m of the dual averaging counts from the
+ *               window's end (the averaged step is still taken at t = n_warmup).  After the last window d_minv is never
+ *               written again.  A transition runs wholly under one minv: the switch falls between the end of transition
+ *               t and the momentum draw of t + 1.
+ * d_adapt: pgl_adapt_state_doubles(R, P) doubles, zeroed by the caller = mean (R, P), M2 (R, P), count (R), window index (R).
+ * d_minv (R, P): ones at the start (the chain before the first window's end is the identity-mass chain, bit for bit).
+ *   pgl_hmc_init_chains_dev, pgl_nuts_init_chains_dev:  pgl_hmc_init_dev / pgl_nuts_init_dev for C chains (C = 1: the same).
+ *   pgl_mass_adapt_dev:  HMC, one small launch after the last pgl_hmc_leap_dev of a transition and before the next
+ *           pgl_hmc_begin_dev (which reads d_minv); needed only for transitions init <= t < the last window's end.
+ *   pgl_nuts_adapt_step_dev:  pgl_nuts_step_dev for the diagonal chain, with the rules above applied inside the row kernel
+ *           at the row's own transition boundary (rows are asynchronous), before the next momentum and edge are formed;
+ *           h = sqrt(minv) o grad U of the current point is recomputed at a switch.  1 launch. */
+long long pgl_adapt_state_doubles(int R, int P);
+int pgl_hmc_init_chains_dev(pgl_handle h, double* d_state, int M, int C, int P, int n_lo, double* d_ll, double* d_grad,
+                            int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam,
+                            double step0, uint64_t seed);
+int pgl_nuts_init_chains_dev(pgl_handle h, double* d_state, int M, int C, int P, int max_depth, int n_lo, double* d_ll,
+                             double* d_grad, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu,
+                             double sigma, double lam, const double* d_minv, const double* d_W, const double* d_step0,
+                             uint64_t seed, int n_warmup, int thin, int n_keep, double* d_Xt);
+int pgl_mass_adapt_dev(pgl_handle h, double* d_state, int R, int P, double* d_adapt, const int* d_sched, double* d_minv);
+int pgl_nuts_adapt_step_dev(pgl_handle h, double* d_state, int M, int P, int max_depth, double* d_ll, double* d_grad,
+                            int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam,
+                            double* d_minv, double* d_adapt, const int* d_sched, double target_accept, int n_warmup, int thin,
+                            int n_keep, double* d_Xt, double* d_samples, double* d_stats);
+
 /* Annealed importance sampling (Neal 2001; inference/batched_ais.py) of the evidence log Z_n of every neuron given the
  * network, as row kernels on the handle's stream, on top of the HMC moves above (restated nowhere: csrc/pglm_ais.h uses
  * csrc/pglm_hmc.h).  The run covers R = K M rows: K particles of the M neurons n_lo .. n_lo + M - 1, particle-major -- row

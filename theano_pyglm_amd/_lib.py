@@ -41,6 +41,8 @@ SYMBOLS = [
     'pgl_hmc_state_doubles', 'pgl_hmc_init_dev', 'pgl_hmc_begin_dev', 'pgl_hmc_leap_dev',
     'pgl_hmc_dense_work_doubles', 'pgl_tri_matvec_dev', 'pgl_hmc_dense_begin_dev', 'pgl_hmc_dense_leap_dev',
     'pgl_nuts_state_doubles', 'pgl_nuts_init_dev', 'pgl_nuts_step_dev',
+    'pgl_adapt_state_doubles', 'pgl_mass_adapt_dev', 'pgl_nuts_adapt_step_dev', 'pgl_hmc_init_chains_dev',
+    'pgl_nuts_init_chains_dev',
     'pgl_prox_state_doubles', 'pgl_prox_init_dev', 'pgl_prox_step_dev',
     'pgl_ais_state_doubles', 'pgl_ais_init_dev', 'pgl_ais_start_dev', 'pgl_ais_temper_dev', 'pgl_ais_begin_dev',
     'pgl_ais_leap_dev',
@@ -189,6 +191,15 @@ def load():
                                           [vp, vp, vp, C.c_uint64, C.c_int, C.c_int, C.c_int, vp])
         lib.pgl_nuts_step_dev.argtypes = ([vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int] + [C.c_double] * 6 +
                                           [vp, vp, C.c_double, C.c_int, C.c_int, C.c_int, vp, vp, vp])
+    if hasattr(lib, 'pgl_mass_adapt_dev'):                    # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
+        lib.pgl_adapt_state_doubles.argtypes = [C.c_int, C.c_int]
+        lib.pgl_mass_adapt_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
+        lib.pgl_nuts_adapt_step_dev.argtypes = ([vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int] + [C.c_double] * 6 +
+                                                [vp, vp, vp, C.c_double, C.c_int, C.c_int, C.c_int, vp, vp, vp])
+        lib.pgl_hmc_init_chains_dev.argtypes = ([vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int] +
+                                                [C.c_double] * 6 + [C.c_double, C.c_uint64])
+        lib.pgl_nuts_init_chains_dev.argtypes = ([vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int] +
+                                                 [C.c_double] * 6 + [vp, vp, vp, C.c_uint64, C.c_int, C.c_int, C.c_int, vp])
     if hasattr(lib, 'pgl_ais_init_dev'):                      # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
         lib.pgl_ais_state_doubles.argtypes = [C.c_int, C.c_int]
         kmp = [vp, vp, C.c_int, C.c_int, C.c_int]
@@ -240,7 +251,7 @@ def load():
             continue
         fn = getattr(lib, name)
         if name in ('pgl_bfgs_state_doubles', 'pgl_ncg_state_doubles', 'pgl_hmc_state_doubles', 'pgl_ais_state_doubles',
-                    'pgl_hmc_dense_work_doubles', 'pgl_prox_state_doubles', 'pgl_nuts_state_doubles'):
+                    'pgl_hmc_dense_work_doubles', 'pgl_prox_state_doubles', 'pgl_nuts_state_doubles', 'pgl_adapt_state_doubles'):
             fn.restype = C.c_longlong
         elif name not in ('pgl_last_error',):
             fn.restype = C.c_int
@@ -710,6 +721,38 @@ class DeviceGlm(object):
                                         float(target_accept), int(n_warmup), int(thin), int(n_keep), C.c_void_p(d_Xt),
                                         C.c_void_p(d_samples) if d_samples else None,
                                         C.c_void_p(d_stats) if d_stats else None))
+
+    # -- several chains per neuron and the warm-up mass adaptation (csrc/pglm_adapt.h).  Rows: R = C M, chain c of neuron
+    # n_lo + m is row c M + m; d_adapt: adapt_state_doubles(R, P) zeroed doubles; d_sched: mass_adapt.schedule_ints on the device
+    def hmc_init_chains_dev(self, d_state, M, n_chains, P, n_lo, d_ll, d_grad, prior, step0, seed):
+        _chk(self.lib.pgl_hmc_init_chains_dev(self.h, C.c_void_p(d_state), int(M), int(n_chains), int(P), int(n_lo),
+                                              C.c_void_p(d_ll), C.c_void_p(d_grad), int(prior[0]),
+                                              *[float(z) for z in prior[1:]], float(step0), int(seed) & 0xffffffffffffffff))
+
+    def nuts_init_chains_dev(self, d_state, M, n_chains, P, max_depth, n_lo, d_ll, d_grad, prior, d_minv, d_W, d_step0, seed,
+                             n_warmup, thin, n_keep, d_Xt):
+        _chk(self.lib.pgl_nuts_init_chains_dev(self.h, C.c_void_p(d_state), int(M), int(n_chains), int(P), int(max_depth),
+                                               int(n_lo), C.c_void_p(d_ll), C.c_void_p(d_grad), int(prior[0]),
+                                               *[float(z) for z in prior[1:]], C.c_void_p(d_minv) if d_minv else None,
+                                               C.c_void_p(d_W) if d_W else None, C.c_void_p(d_step0),
+                                               int(seed) & 0xffffffffffffffff, int(n_warmup), int(thin), int(n_keep),
+                                               C.c_void_p(d_Xt)))
+
+    def adapt_state_doubles(self, R, P):
+        return int(self.lib.pgl_adapt_state_doubles(int(R), int(P)))
+
+    def mass_adapt_dev(self, d_state, R, P, d_adapt, d_sched, d_minv):
+        _chk(self.lib.pgl_mass_adapt_dev(self.h, C.c_void_p(d_state), int(R), int(P), C.c_void_p(d_adapt), C.c_void_p(d_sched),
+                                         C.c_void_p(d_minv)))
+
+    def nuts_adapt_step_dev(self, d_state, R, P, max_depth, d_ll, d_grad, prior, d_minv, d_adapt, d_sched, target_accept,
+                            n_warmup, thin, n_keep, d_Xt, d_samples=0, d_stats=0):
+        _chk(self.lib.pgl_nuts_adapt_step_dev(self.h, C.c_void_p(d_state), int(R), int(P), int(max_depth), C.c_void_p(d_ll),
+                                              C.c_void_p(d_grad), int(prior[0]), *[float(z) for z in prior[1:]],
+                                              C.c_void_p(d_minv), C.c_void_p(d_adapt), C.c_void_p(d_sched),
+                                              float(target_accept), int(n_warmup), int(thin), int(n_keep), C.c_void_p(d_Xt),
+                                              C.c_void_p(d_samples) if d_samples else None,
+                                              C.c_void_p(d_stats) if d_stats else None))
 
     # -- the same chain with a dense mass matrix (pgl_hmc_dense_*): d_W (M, P, P) lower-triangular factors of the inverse
     # mass matrices; d_work: hmc_dense_work_doubles(M, P) doubles (0: none)

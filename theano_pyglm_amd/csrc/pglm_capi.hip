@@ -2019,18 +2019,51 @@ int pgl_ncg_search_step_dev(pgl_handle h, double* d_state, int M, int P, const i
 // ---- lock-step HMC row kernels (inference/batched_hmc.py) --------------------------------------------------------------
 long long pgl_hmc_state_doubles(int M, int P) { return (long long)pgl_hmc_doubles(M, P); }
 
-int pgl_hmc_init_dev(pgl_handle h, double* d_state, int M, int P, int n_lo, double* d_ll, double* d_grad, int prior_kind,
-                     double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam, double step0,
-                     uint64_t seed)
+// R = C M rows: chain c of neuron n_lo + m is row c M + m and runs on pgl_chain_seed(seed, c)
+static int hmc_init(pgl_handle h, double* d_state, int M, int C, int P, int n_lo, double* d_ll, double* d_grad, int prior_kind,
+                    double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam, double step0,
+                    uint64_t seed)
 {
-    if (!h || !d_state || !d_ll || !d_grad || M <= 0 || P <= 0 || n_lo < 0 || n_lo + M > h->N || !(step0 > 0.0))
+    if (!h || !d_state || !d_ll || !d_grad || M <= 0 || C <= 0 || P <= 0 || n_lo < 0 || n_lo + M > h->N || !(step0 > 0.0) ||
+        (long long)M * C > 0x7fffffffLL)
         return fail(PGL_ERR_ARG, "bad argument");
     BfgsPrior q;
     int rc = ncg_prior(h, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
     if (rc) return rc;
     HIPCHK(hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_hmc_init, dim3(M), dim3(256), 0, h->stream, pgl_hmc_view(d_state, M, P), d_ll, d_grad, q, n_lo, step0,
-                       (unsigned long long)seed);
+    hipLaunchKernelGGL(k_hmc_init, dim3(M * C), dim3(256), 0, h->stream, pgl_hmc_view(d_state, M * C, P), d_ll, d_grad, q, n_lo,
+                       step0, (unsigned long long)seed, M);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+int pgl_hmc_init_dev(pgl_handle h, double* d_state, int M, int P, int n_lo, double* d_ll, double* d_grad, int prior_kind,
+                     double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam, double step0,
+                     uint64_t seed)
+{
+    return hmc_init(h, d_state, M, 1, P, n_lo, d_ll, d_grad, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, step0, seed);
+}
+
+int pgl_hmc_init_chains_dev(pgl_handle h, double* d_state, int M, int C, int P, int n_lo, double* d_ll, double* d_grad,
+                            int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam,
+                            double step0, uint64_t seed)
+{
+    return hmc_init(h, d_state, M, C, P, n_lo, d_ll, d_grad, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, step0, seed);
+}
+
+// ---- windowed diagonal mass adaptation (mass='adapt'; pglm_adapt.h) ---------------------------------------------------
+long long pgl_adapt_state_doubles(int R, int P)
+{
+    if (R <= 0 || P <= 0) return 0;
+    return (long long)pgl_adapt_doubles(R, P);
+}
+
+int pgl_mass_adapt_dev(pgl_handle h, double* d_state, int R, int P, double* d_adapt, const int* d_sched, double* d_minv)
+{
+    if (!h || !d_state || !d_adapt || !d_sched || !d_minv || R <= 0 || P <= 0) return fail(PGL_ERR_ARG, "bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_hmc_mass_adapt, dim3(R), dim3(256), 0, h->stream, pgl_hmc_view(d_state, R, P),
+                       pgl_adapt_view(d_adapt, R, P), d_sched, d_minv);
     HIPCHK(hipGetLastError());
     return PGL_OK;
 }
@@ -2165,14 +2198,16 @@ static int nuts_args(pgl_handle h, const double* d_state, int M, int P, int max_
     return PGL_OK;
 }
 
-int pgl_nuts_init_dev(pgl_handle h, double* d_state, int M, int P, int max_depth, int n_lo, double* d_ll, double* d_grad,
-                      int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam,
+static int nuts_init(pgl_handle h, double* d_state, int M0, int C, int P, int max_depth, int n_lo, double* d_ll, double* d_grad,
+                     int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam,
                       const double* d_minv, const double* d_W, const double* d_step0, uint64_t seed, int n_warmup, int thin,
                       int n_keep, double* d_Xt)
 {
+    if (M0 <= 0 || C <= 0 || (long long)M0 * C > 0x7fffffffLL) return fail(PGL_ERR_ARG, "bad argument");
+    const int M = M0 * C;                                                      // rows: chain c of neuron n_lo + m is row c M0 + m
     int rc = nuts_args(h, d_state, M, P, max_depth, d_ll, d_grad, n_warmup, thin, n_keep, d_Xt);
     if (rc) return rc;
-    if (!d_step0 || n_lo < 0 || n_lo + M > h->N) return fail(PGL_ERR_ARG, "bad argument");
+    if (!d_step0 || n_lo < 0 || n_lo + M0 > h->N) return fail(PGL_ERR_ARG, "bad argument");
     BfgsPrior q;
     rc = ncg_prior(h, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
     if (rc) return rc;
@@ -2186,11 +2221,30 @@ int pgl_nuts_init_dev(pgl_handle h, double* d_state, int M, int P, int max_depth
         if (rc) return rc;
     }
     hipLaunchKernelGGL(k_nuts_init, dim3(M), dim3(256), 0, h->stream, v, d_ll, d_grad, q, d_W ? 1 : 0, d_minv, n_lo, d_step0,
-                       (unsigned long long)seed, n_warmup + n_keep * thin, d_Xt);
+                       (unsigned long long)seed, n_warmup + n_keep * thin, d_Xt, M0);
     HIPCHK(hipGetLastError());
     if (!d_W) return PGL_OK;
     return tri_launch(h, 0, PGL_TRI_DRIFT, d_W, M, P, v.vec + PGL_NUTS_RW * MP, v.vec + PGL_NUTS_QW * MP, d_Xt,
                       v.sc + (size_t)PGL_NUTS_F_VE * M, 1.0);
+}
+
+int pgl_nuts_init_dev(pgl_handle h, double* d_state, int M, int P, int max_depth, int n_lo, double* d_ll, double* d_grad,
+                      int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam,
+                      const double* d_minv, const double* d_W, const double* d_step0, uint64_t seed, int n_warmup, int thin,
+                      int n_keep, double* d_Xt)
+{
+    return nuts_init(h, d_state, M, 1, P, max_depth, n_lo, d_ll, d_grad, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam,
+                     d_minv, d_W, d_step0, seed, n_warmup, thin, n_keep, d_Xt);
+}
+
+// d_minv, d_W: (C M, P) / (C M, P, P), one per row
+int pgl_nuts_init_chains_dev(pgl_handle h, double* d_state, int M, int C, int P, int max_depth, int n_lo, double* d_ll,
+                             double* d_grad, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu,
+                             double sigma, double lam, const double* d_minv, const double* d_W, const double* d_step0,
+                             uint64_t seed, int n_warmup, int thin, int n_keep, double* d_Xt)
+{
+    return nuts_init(h, d_state, M, C, P, max_depth, n_lo, d_ll, d_grad, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam,
+                     d_minv, d_W, d_step0, seed, n_warmup, thin, n_keep, d_Xt);
 }
 
 int pgl_nuts_step_dev(pgl_handle h, double* d_state, int M, int P, int max_depth, double* d_ll, double* d_grad,
@@ -2219,6 +2273,27 @@ int pgl_nuts_step_dev(pgl_handle h, double* d_state, int M, int P, int max_depth
     if (!d_W) return PGL_OK;
     return tri_launch(h, 0, PGL_TRI_DRIFT, d_W, M, P, v.vec + PGL_NUTS_RW * MP, v.vec + PGL_NUTS_QW * MP, d_Xt,
                       v.sc + (size_t)PGL_NUTS_F_VE * M, 1.0);
+}
+
+// pgl_nuts_step_dev for the diagonal chain under mass='adapt': d_minv (M, P) is read and, at a row's window ends, rewritten
+int pgl_nuts_adapt_step_dev(pgl_handle h, double* d_state, int M, int P, int max_depth, double* d_ll, double* d_grad,
+                            int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam,
+                            double* d_minv, double* d_adapt, const int* d_sched, double target_accept, int n_warmup, int thin,
+                            int n_keep, double* d_Xt, double* d_samples, double* d_stats)
+{
+    int rc = nuts_args(h, d_state, M, P, max_depth, d_ll, d_grad, n_warmup, thin, n_keep, d_Xt);
+    if (rc) return rc;
+    if (!d_minv || !d_adapt || !d_sched) return fail(PGL_ERR_ARG, "bad argument");
+    if (!(target_accept > 0.0 && target_accept < 1.0)) return fail(PGL_ERR_ARG, "target_accept: in (0, 1)");
+    BfgsPrior q;
+    rc = ncg_prior(h, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_nuts_adapt_step, dim3(M), dim3(256), 0, h->stream, pgl_nuts_view(d_state, M, P, max_depth), d_ll,
+                       d_grad, q, d_minv, target_accept, n_warmup, thin, n_keep, d_Xt, d_samples, d_stats,
+                       pgl_adapt_view(d_adapt, M, P), d_sched);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
 }
 
 // ---- annealed importance sampling row kernels (inference/batched_ais.py) -----------------------------------------------

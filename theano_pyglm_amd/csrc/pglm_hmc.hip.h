@@ -11,6 +11,7 @@
 // takes the same number of steps: no lists, no flags, nothing for the host to read before the chain has ended.
 // ---------------------------------------------------------------------------
 #include "pglm_hmc_dense.h"                     // (pglm_hmc.h, and the dense chain's per-element rules)
+#include "pglm_adapt.h"                         // (pgl_chain_seed)
 
 struct HmcView {
     int M, P;
@@ -71,10 +72,11 @@ __device__ __forceinline__ double pgl_hmc_target_row(const double* __restrict__ 
 }
 
 // start of a chain: q of every row is in the state, (ll, grad) hold ll and its gradient at q, row by row (overwritten
-// with U and grad U)
+// with U and grad U).  chain_rows: the rows of one chain -- row r is chain r / chain_rows of neuron n_lo + r % chain_rows
+// and runs on pgl_chain_seed(seed, chain) (one chain: chain_rows = M, the seed itself)
 __global__ __launch_bounds__(256) void k_hmc_init(const HmcView v, double* __restrict__ ll, double* __restrict__ grad,
                                                   const BfgsPrior q, const int n_lo, const double step0,
-                                                  const unsigned long long seed)
+                                                  const unsigned long long seed, const int chain_rows)
 {
     __shared__ double red[12];
     const int r = blockIdx.x, tid = threadIdx.x, P = v.P;
@@ -84,7 +86,7 @@ __global__ __launch_bounds__(256) void k_hmc_init(const HmcView v, double* __res
     for (int c = tid; c < P; c += 256) v.g[o + c] = grad[o + c];
     if (tid == 0) {
         PglHmc s;
-        pgl_hmc_init(&s, U, step0, n_lo + r, seed);
+        pgl_hmc_init(&s, U, step0, n_lo + r % chain_rows, pgl_chain_seed(seed, (pgl_hmc_u64)(r / chain_rows)));
         pgl_hmc_store(v, r, &s);
         ll[r] = U;
     }

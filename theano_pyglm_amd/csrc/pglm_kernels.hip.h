@@ -47,6 +47,7 @@
 #include "pglm_ncg.hip.h"
 #include "pglm_hmc.hip.h"
 #include "pglm_hmc_dense.hip.h"
+#include "pglm_adapt.hip.h"
 #include "pglm_nuts.hip.h"
 #include "pglm_chol.hip.h"
 #include "pglm_ais.hip.h"

@@ -152,15 +152,21 @@ PGL_NUTS_FN void pgl_nuts_init(PglNuts* s, int P, double U0, double step0, int n
     pgl_nuts_start(s, P, n_total);
 }
 
-// dual averaging after transition t with statistic alpha (t < n_warmup)
-PGL_NUTS_FN void pgl_nuts_adapt(PglNuts* s, double alpha, double delta, int n_warmup)
+// dual averaging after transition t with statistic alpha (t < n_warmup).  m0: the transitions completed when the dual
+// averaging was last restarted (pglm_adapt.h restarts it at the end of a mass window; 0: never), so the iterate is
+// m = t + 1 - m0; the averaged step is taken at t + 1 = n_warmup whatever m0.
+PGL_NUTS_FN void pgl_nuts_adapt_from(PglNuts* s, double alpha, double delta, int n_warmup, double m0)
 {
-    const double m = s->t + 1.0;
+    const double m = s->t + 1.0 - m0;
     s->hbar = (1.0 - 1.0 / (m + PGL_NUTS_T0)) * s->hbar + (delta - alpha) / (m + PGL_NUTS_T0);
     const double le = s->mu - sqrt(m) / PGL_NUTS_GAMMA * s->hbar;
     const double eta = exp(-PGL_NUTS_KAPPA * log(m));
     s->logeps_bar = eta * le + (1.0 - eta) * s->logeps_bar;
-    s->step = pgl_nuts_clip_step(exp(m == (double)n_warmup ? s->logeps_bar : le));
+    s->step = pgl_nuts_clip_step(exp(s->t + 1.0 == (double)n_warmup ? s->logeps_bar : le));
+}
+PGL_NUTS_FN void pgl_nuts_adapt(PglNuts* s, double alpha, double delta, int n_warmup)
+{
+    pgl_nuts_adapt_from(s, alpha, delta, n_warmup, 0.0);
 }
 
 // The leaf s->i of the running subtree is complete: U1 at it, ksum = sum r^2 of its momentum.  dots[2 (k - 1)], [2 (k - 1)
@@ -174,8 +180,10 @@ PGL_NUTS_FN void pgl_nuts_adapt(PglNuts* s, double alpha, double delta, int n_wa
 //              then a new transition starts (pgl_nuts_start) unless DONE.
 // mg (host tests; null on the device): mg[0] = min over selection decisions of |log u - log ratio|, mg[1] = min over
 // leaves of |H - H0 - 1000|; both only ever lowered.
-PGL_NUTS_FN int pgl_nuts_leaf(PglNuts* s, int P, int max_depth, double U1, double ksum, const double* dots, double dot_l,
-                              double dot_r, double delta, int n_warmup, int thin, int n_keep, int* keep_slot, double* mg)
+// da_m0: pgl_nuts_adapt_from's m0 (pgl_nuts_leaf: 0).
+PGL_NUTS_FN int pgl_nuts_leaf_from(PglNuts* s, int P, int max_depth, double U1, double ksum, const double* dots, double dot_l,
+                                   double dot_r, double delta, int n_warmup, int thin, int n_keep, int* keep_slot, double* mg,
+                                   double da_m0)
 {
     const pgl_hmc_u64 key = pgl_nuts_row_key(s);
     const int d = (int)s->depth - 1, size = 1 << d, i = (int)s->i, leafno = size - 1 + i;
@@ -235,7 +243,7 @@ PGL_NUTS_FN int pgl_nuts_leaf(PglNuts* s, int P, int max_depth, double U1, doubl
     const double alpha = s->sum_acc / s->n_leaf;
     s->last_depth = s->depth; s->last_nleaf = s->n_leaf; s->last_stop = (double)stop; s->last_sel = s->sel;
     s->last_acc = alpha;
-    if (s->t < (double)n_warmup) pgl_nuts_adapt(s, alpha, delta, n_warmup);
+    if (s->t < (double)n_warmup) pgl_nuts_adapt_from(s, alpha, delta, n_warmup, da_m0);
     else {
         s->acc_post += alpha;
         if (stop == PGL_NUTS_STOP_DIVERGENT) s->n_div += 1.0;
@@ -247,6 +255,11 @@ PGL_NUTS_FN int pgl_nuts_leaf(PglNuts* s, int P, int max_depth, double U1, doubl
     act |= PGL_NUTS_END | PGL_NUTS_NEWSUB;
     if (s->done != 0.0) act = (act & ~PGL_NUTS_NEWSUB) | PGL_NUTS_DONE;
     return act;
+}
+PGL_NUTS_FN int pgl_nuts_leaf(PglNuts* s, int P, int max_depth, double U1, double ksum, const double* dots, double dot_l,
+                              double dot_r, double delta, int n_warmup, int thin, int n_keep, int* keep_slot, double* mg)
+{
+    return pgl_nuts_leaf_from(s, P, max_depth, U1, ksum, dots, dot_l, dot_r, delta, n_warmup, thin, n_keep, keep_slot, mg, 0.0);
 }
 
 #endif

@@ -14,7 +14,7 @@
 // per leapfrog step;  dense (W (M, P, P)) -- k_nuts_target, the product W^T grad U (k_tri_matvec, stored), k_nuts_step,
 // and the product W r with the drift as its epilogue (k_tri_matvec<0, DRIFT> with the row's signed step).
 // ---------------------------------------------------------------------------
-#include "pglm_nuts.h"
+#include "pglm_adapt.h"                         // (pglm_nuts.h, and the mass adaptation's rules)
 #include <cstddef>
 
 struct NutsView {
@@ -127,11 +127,12 @@ __device__ __forceinline__ double pgl_nuts_advance_elem(const NutsView& v, const
 
 // start of a chain: the rows' points are in QC.  Diagonal mass: (ll, grad) hold ll and its gradient there (overwritten
 // with U and grad U); dense: U and grad U already (k_nuts_target) and HB = W^T grad U.  Draws the first momentum and
-// takes the first half kick (and, diagonal, the first drift: Xt[row] = the point to evaluate).
+// takes the first half kick (and, diagonal, the first drift: Xt[row] = the point to evaluate).  chain_rows: k_hmc_init's.
 __global__ __launch_bounds__(256) void k_nuts_init(const NutsView v, double* __restrict__ ll, double* __restrict__ grad,
                                                    const BfgsPrior q, const int dense, const double* __restrict__ minv,
                                                    const int n_lo, const double* __restrict__ step0,
-                                                   const unsigned long long seed, const int n_total, double* __restrict__ Xt)
+                                                   const unsigned long long seed, const int n_total, double* __restrict__ Xt,
+                                                   const int chain_rows)
 {
     __shared__ double red[12];
     __shared__ PglNuts sh;
@@ -148,7 +149,7 @@ __global__ __launch_bounds__(256) void k_nuts_init(const NutsView v, double* __r
         pgl_nuts_row(v, PGL_NUTS_HC, r)[c] = dense ? pgl_nuts_row(v, PGL_NUTS_HB, r)[c] : (minv ? sqrt(minv[o + c]) : 1.0) * g;
     }
     if (tid == 0) {
-        pgl_nuts_init(&sh, P, U, step0[r], n_lo + r, seed, n_total);
+        pgl_nuts_init(&sh, P, U, step0[r], n_lo + r % chain_rows, pgl_chain_seed(seed, (pgl_hmc_u64)(r / chain_rows)), n_total);
         ll[r] = U;
     }
     __syncthreads();
@@ -167,16 +168,23 @@ __global__ __launch_bounds__(256) void k_nuts_init(const NutsView v, double* __r
 // come in and are turned into U, grad U in place; dense: they are U and grad U (k_nuts_target) and HB = W^T grad U.
 // Completes the leaf, takes the decisions of pgl_nuts_leaf, moves the vectors, writes a kept point into
 // samples[slot, row] and (depth, leaves) into stats[slot, :, row], and prepares the next leaf.
-__global__ __launch_bounds__(256) void k_nuts_step(const NutsView v, double* __restrict__ ll, double* __restrict__ grad,
-                                                   const BfgsPrior q, const int dense, const double* __restrict__ minv,
-                                                   const double delta, const int n_warmup, const int thin, const int n_keep,
-                                                   double* __restrict__ Xt, double* __restrict__ samples,
-                                                   double* __restrict__ stats)
+// ADAPT (k_nuts_adapt_step; diagonal mass only): the row's mass adaptation of pglm_adapt.h at the row's own transition
+// boundary -- after the candidate of the ended transition is in QC and before the next momentum and edge are formed: the
+// Welford update of the window with QC, and at a window's end the new row of minv (this launch's leaf was still formed
+// with the old one), HC = sqrt(minv) o GC with it, and the restart of the dual averaging.
+template <int ADAPT>
+__device__ __forceinline__ void pgl_nuts_step_row(const NutsView v, double* __restrict__ ll, double* __restrict__ grad,
+                                                  const BfgsPrior q, const int dense, const double* minv,
+                                                  const double delta, const int n_warmup, const int thin, const int n_keep,
+                                                  double* __restrict__ Xt, double* __restrict__ samples,
+                                                  double* __restrict__ stats, const AdaptView a, const int* __restrict__ sched,
+                                                  double* minv_out)
 {
     __shared__ double red[12];
     __shared__ double sdots[2 * PGL_NUTS_MAX_DEPTH + 2];
     __shared__ PglNuts sh;
-    __shared__ int sact, sslot;
+    __shared__ int sact, sslot, sadapt;
+    __shared__ double sn;
     const int r = blockIdx.x, tid = threadIdx.x, P = v.P, M = v.M, D = v.D;
     const size_t o = (size_t)r * P;
     if (v.sc[(size_t)PGL_NUTS_F_DONE * M + r] != 0.0) return;                  // (the whole workgroup)
@@ -246,7 +254,21 @@ __global__ __launch_bounds__(256) void k_nuts_step(const NutsView v, double* __r
     if (tid == 0) {
         pgl_nuts_load(v, r, &sh);
         int slot = -1;
-        sact = pgl_nuts_leaf(&sh, P, D, U1, ks, sdots, dl, dr, delta, n_warmup, thin, n_keep, &slot, (double*)0);
+        if (ADAPT) {
+            PglAdapt ad;
+            ad.count = a.count[r]; ad.widx = a.widx[r];
+            sact = pgl_nuts_leaf_from(&sh, P, D, U1, ks, sdots, dl, dr, delta, n_warmup, thin, n_keep, &slot, (double*)0,
+                                      pgl_adapt_restart_t(&ad, sched));
+            int aa = 0;
+            double n = 0.0;
+            if (sact & PGL_NUTS_END) aa = pgl_adapt_row(&ad, sched, (int)sh.t - 1, &n);
+            if (aa) {
+                a.count[r] = ad.count; a.widx[r] = ad.widx;
+            }
+            if (aa & PGL_ADAPT_SWITCH) pgl_adapt_restart_nuts(&sh);
+            sadapt = aa; sn = n;
+        } else
+            sact = pgl_nuts_leaf(&sh, P, D, U1, ks, sdots, dl, dr, delta, n_warmup, thin, n_keep, &slot, (double*)0);
         sslot = slot;
         ll[r] = U1;
         if ((sact & PGL_NUTS_END) && slot >= 0 && stats) {
@@ -278,6 +300,17 @@ __global__ __launch_bounds__(256) void k_nuts_step(const NutsView v, double* __r
         }
         if ((act & PGL_NUTS_END) && slot >= 0 && samples)
             samples[((size_t)slot * M + r) * P + c] = pgl_nuts_row(v, PGL_NUTS_QC, r)[c];
+        if (ADAPT && sadapt) {
+            double mean = a.mean[o + c], m2 = a.m2[o + c];
+            pgl_adapt_welford(pgl_nuts_row(v, PGL_NUTS_QC, r)[c], sn, &mean, &m2);
+            if (sadapt & PGL_ADAPT_SWITCH) {
+                const double mi = pgl_adapt_minv(m2, sn);
+                minv_out[o + c] = mi;
+                pgl_nuts_row(v, PGL_NUTS_HC, r)[c] = sqrt(mi) * pgl_nuts_row(v, PGL_NUTS_GC, r)[c];
+                mean = 0.0; m2 = 0.0;
+            }
+            a.mean[o + c] = mean; a.m2[o + c] = m2;
+        }
         ks0 += pgl_nuts_advance_elem(v, r, c, act, sh.v, sh.ve, key, dense != 0, minv, Xt);
     }
     if (act & PGL_NUTS_END) {                                                  // (uniform over the workgroup)
@@ -285,4 +318,25 @@ __global__ __launch_bounds__(256) void k_nuts_step(const NutsView v, double* __r
         if (tid == 0 && !(act & PGL_NUTS_DONE)) pgl_nuts_energy0(&sh, ks0);
     }
     if (tid == 0) pgl_nuts_store(v, r, &sh);
+}
+
+__global__ __launch_bounds__(256) void k_nuts_step(const NutsView v, double* __restrict__ ll, double* __restrict__ grad,
+                                                   const BfgsPrior q, const int dense, const double* __restrict__ minv,
+                                                   const double delta, const int n_warmup, const int thin, const int n_keep,
+                                                   double* __restrict__ Xt, double* __restrict__ samples,
+                                                   double* __restrict__ stats)
+{
+    AdaptView a;
+    a.R = 0; a.P = 0; a.mean = a.m2 = a.count = a.widx = nullptr;
+    pgl_nuts_step_row<0>(v, ll, grad, q, dense, minv, delta, n_warmup, thin, n_keep, Xt, samples, stats, a, nullptr, nullptr);
+}
+// the diagonal chain under mass='adapt': minv (M, P) is read and, at a row's window ends, rewritten
+__global__ __launch_bounds__(256) void k_nuts_adapt_step(const NutsView v, double* __restrict__ ll, double* __restrict__ grad,
+                                                         const BfgsPrior q, double* minv, const double delta,
+                                                         const int n_warmup, const int thin, const int n_keep,
+                                                         double* __restrict__ Xt, double* __restrict__ samples,
+                                                         double* __restrict__ stats, const AdaptView a,
+                                                         const int* __restrict__ sched)
+{
+    pgl_nuts_step_row<1>(v, ll, grad, q, 0, minv, delta, n_warmup, thin, n_keep, Xt, samples, stats, a, sched, minv);
 }

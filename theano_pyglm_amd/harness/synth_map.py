@@ -186,8 +186,9 @@ def parser():
     ap.add_argument('--nuts', type=int, default=0, metavar='N',
                     help='after the fit: N posterior draws per neuron by the No-U-Turn sampler on the device; prints the table '
                          'of --hmc plus the median tree depth and the divergent transitions')
-    ap.add_argument('--hmc-mass', choices=['laplace', 'laplace_dense'], default='laplace',
-                    help="mass matrix of --hmc and --nuts: 1 / diag A ('laplace') or the full Laplace covariance ('laplace_dense')")
+    ap.add_argument('--hmc-mass', choices=['laplace', 'laplace_dense', 'adapt'], default='laplace',
+                    help="mass matrix of --hmc and --nuts: 1 / diag A ('laplace'), the full Laplace covariance ('laplace_dense') "
+                         "or a diagonal one learned during the warm-up ('adapt')")
     ap.add_argument('--ais', type=int, default=0, metavar='K',
                     help='after the fit: log evidence of every neuron given the network by annealed importance sampling with '
                          'K particles on the device, beside the Laplace log evidence (Gaussian impulse priors only)')

@@ -152,7 +152,8 @@ def ais_glms(population, x, n_particles=16, betas=None, n_temps=200, n_steps=1, 
     adapting pilot particle started at step_sz (a number); False: step_sz, a number or a (J-1, M) table, is the table.
     Particles are numbered particle0 .. particle0 + n_particles - 1: runs with different ranges and the same seed are
     independent particles of one larger run.  x supplies the network (and the point of the Hessian for mass='laplace'); it
-    is not changed.
+    is not changed.  mass='adapt' (the samplers' warm-up adaptation) raises ValueError: a mass that depends on the states
+    of the particles would invalidate the weights.
 
     Returns a dict: 'log_Z' (M,), 'log_Z_se' (M,), 'ess' (M,) (weights_summary), 'log_weights' (K, M), 'samples'
     (K, M, P) the final points, 'accept_rate' (J-1, M), 'step_sz' (J-1, M), 'betas', 'log_prior_norm' (M,), 'n_evals'
@@ -162,6 +163,9 @@ def ais_glms(population, x, n_particles=16, betas=None, n_temps=200, n_steps=1, 
     population.last_fit_stats records the launch counts -- with a dense mass also 'factorisations' (tempered_factor calls)
     and 'product_launches' (pgl_tri_matvec_shared launches) -- and the host synchronisations inside the run (none)."""
     _check(population)
+    if isinstance(mass, str) and mass == 'adapt':
+        raise ValueError("mass='adapt' is not available in annealed importance sampling: a mass that depends on the "
+                         "particles' states would invalidate the weights")
     K, n_steps, n_leapfrog = int(n_particles), int(n_steps), int(n_leapfrog)
     if K <= 0 or n_steps <= 0 or n_leapfrog <= 0 or int(particle0) < 0:
         raise ValueError("n_particles, n_steps and n_leapfrog must be positive, particle0 not negative")

@@ -148,13 +148,22 @@ def resolve_mass(population, x, mass, n_lo, n_hi, mass_floor, factor_on_device=F
     positive inverse masses on the host or None; factor (M, P, P) lower-triangular W with W W^T = the inverse mass matrix
     (host array, or a device tensor with factor_on_device) or None; dense_rows (M,) bool with 'laplace_dense', else None;
     setup_s: the seconds spent on Hessians and factorisations.  dense='tempered' (annealed importance sampling, which
-    builds one factor per temperature itself): 'laplace_dense' gives factor = 'tempered' and computes nothing."""
+    builds one factor per temperature itself): 'laplace_dense' gives factor = 'tempered' and computes nothing.
+    mass='adapt' (the chain learns a diagonal mass during its warm-up) gives minv = 'adapt' and setup_s = 0."""
     import time
     t0 = time.perf_counter()
     M, P = n_hi - n_lo, population.glm.P
     minv = factor = dense_rows = None
     if isinstance(mass, str):
-        if mass == 'laplace':
+        if mass == 'adapt':
+            # learned by the chain itself during its warm-up (csrc/pglm_adapt.h): nothing to compute here
+            if dense == 'tempered':
+                raise ValueError("mass='adapt' is not available in annealed importance sampling: a mass that depends on "
+                                 "the particles' states would invalidate the weights")
+            if factor_on_device:
+                raise ValueError("mass='adapt' builds no factor: factor_on_device does not apply")
+            return 'adapt', None, None, 0
+        elif mass == 'laplace':
             minv = _laplace_minv(population, x, n_lo, n_hi, float(mass_floor))
         elif mass == 'laplace_dense' and dense == 'tempered':
             factor = 'tempered'
@@ -162,7 +171,7 @@ def resolve_mass(population, x, mass, n_lo, n_hi, mass_floor, factor_on_device=F
             build = _laplace_dense_factor_device if factor_on_device else _laplace_dense_factor
             factor, dense_rows = build(population, x, n_lo, n_hi, float(mass_floor))
         else:
-            raise ValueError("mass: None, 'laplace', 'laplace_dense', an (M, P) or an (M, P, P) array")
+            raise ValueError("mass: None, 'laplace', 'laplace_dense', an (M, P) or an (M, P, P) array, or 'adapt'")
     elif mass is not None and np.ndim(mass) == 3:
         if np.shape(mass) != (M, P, P):
             raise ValueError("mass: an (M, P, P) = (%d, %d, %d) array of inverse mass matrices" % (M, P, P))
@@ -177,8 +186,45 @@ def resolve_mass(population, x, mass, n_lo, n_hi, mass_floor, factor_on_device=F
     return minv, factor, dense_rows, setup_s
 
 
+def chain_starts(pk, x, n_lo, n_hi, n_chains, seed, init_jitter):
+    """The starting points (n_chains M, P) of the chains, chain-major: x's rows, plus init_jitter * z with z the stateless
+    normals of mass_adapt.start_jitter under the chain's seed."""
+    from theano_pyglm_amd.inference.mass_adapt import chain_seed, start_jitter
+    X0 = np.asarray(pk.pack(x, n_lo, n_hi), dtype=float)
+    M, P = X0.shape
+    X = np.tile(X0, (n_chains, 1))
+    if init_jitter != 0.0:
+        for c in range(n_chains):
+            for m in range(M):
+                X[c * M + m] += init_jitter * start_jitter(chain_seed(seed, c), n_lo + m, P)
+    return X
+
+
+def _check_chains(n_chains, init_jitter):
+    n_chains, init_jitter = int(n_chains), float(init_jitter)
+    if n_chains <= 0:
+        raise ValueError("n_chains must be positive")
+    if not np.isfinite(init_jitter) or init_jitter < 0.0:
+        raise ValueError("init_jitter must be a finite number, not negative")
+    return n_chains, init_jitter
+
+
+def per_row(a, M, n_chains):
+    """An (M, ...) array a neuron's chains share -> (n_chains M, ...), chain-major."""
+    return a if n_chains == 1 else a.repeat(*([n_chains] + [1] * (a.dim() - 1)))
+
+
+def split_chains(a, M, n_chains, axis):
+    """The rows axis (n_chains M) of a result -> (n_chains, M) with the chain axis in front; n_chains = 1: unchanged."""
+    if n_chains == 1:
+        return a
+    a = np.asarray(a)
+    b = a.reshape(a.shape[:axis] + (n_chains, M) + a.shape[axis + 1:])
+    return np.ascontiguousarray(np.moveaxis(b, axis, 0))
+
+
 def sample_glms_hmc(population, x, n_samples, n_warmup=200, n_leapfrog=10, step_sz=0.1, thin=1, mass=None, seed=0,
-                    n_lo=0, n_hi=None, mass_floor=1e-8, factor_on_device=False):
+                    n_lo=0, n_hi=None, mass_floor=1e-8, factor_on_device=False, n_chains=1, init_jitter=0.0):
     """Posterior samples of the parameter rows of neurons [n_lo, n_hi) given the rest of x, started at x.
 
     n_warmup transitions adapt every row's step size and are dropped; then n_samples * thin transitions, every thin-th
@@ -187,18 +233,29 @@ def sample_glms_hmc(population, x, n_samples, n_warmup=200, n_leapfrog=10, step_
     (M, P) array of inverse masses in the theta layout, an (M, P, P) array of inverse mass MATRICES Sigma in the theta
     layout (finite, symmetric, positive definite: factor_inverse_mass) or 'laplace_dense' (Sigma = the Laplace covariance
     A^-1 of every neuron, laplace_glms' 'cov'; a neuron whose A is not positive definite runs on the 'laplace' rule).
+    mass='adapt': a diagonal mass learned by every row from its own warm-up draws in Stan's windows (mass_adapt.
+    adapt_windows; the estimate, on the device, is csrc/pglm_adapt.h) -- no Hessian, no mode, one more small row launch per
+    transition of the windows and no host synchronisation; with n_warmup < 20 there is no window and the chain is the
+    mass=None chain.
     factor_on_device: with 'laplace_dense', the factor W of the Laplace covariance is built on the device
     (pgl_chol_factor_dev, pgl_tri_inverse_dev) and handed to the chain without a host copy; the default keeps the host
     factorisation, and with it the draws of earlier versions (the two W agree to rounding, not to the bit).
+    n_chains = C > 1: C chains per neuron in the same launches (the state has C M rows; an evaluation is C pgl_ll_grad_dev,
+    one per chain).  Chain c runs on the seed mass_adapt.chain_seed(seed, c) and equals the single-chain run with that
+    seed; arrays given per neuron (step_sz, an (M, P) or (M, P, P) mass) are shared by a neuron's chains, 'adapt' learns
+    one mass per chain.  All chains start at x, plus init_jitter * z (mass_adapt.start_jitter) when init_jitter > 0.
     Returns {'samples': (n_samples, M, P) rows in the theta layout [bias, w_stim, w_ir], 'accept_rate': (M,) after
     warm-up, 'step_sz': (M,) the frozen step sizes, 'n_evals': ll+grad launches} and, with 'laplace_dense', 'dense_rows':
-    (M,) bool, the rows that run on the full covariance.  x is not changed.
+    (M,) bool, the rows that run on the full covariance; with 'adapt', 'minv' (M, P) the learned inverse masses and
+    'adapt_windows'.  With n_chains > 1 'samples', 'accept_rate', 'step_sz' and 'minv' gain a leading chain axis
+    (summarize(samples, chains=True) takes them).  x is not changed.
     population.last_fit_stats records the launch counts, the host synchronisations inside the chain, 'mass' ('identity',
-    'diagonal' or 'dense') and 'mass_setup_s' (the Hessian and the host factorisation)."""
+    'diagonal', 'adapted diagonal' or 'dense') and 'mass_setup_s' (the Hessian and the host factorisation; 0 for 'adapt')."""
     _check(population)
     n_samples, n_warmup, n_leapfrog, thin = int(n_samples), int(n_warmup), int(n_leapfrog), int(thin)
     if n_samples <= 0 or n_warmup < 0 or n_leapfrog <= 0 or thin <= 0:
         raise ValueError("n_samples, n_leapfrog and thin must be positive, n_warmup not negative")
+    n_chains, init_jitter = _check_chains(n_chains, init_jitter)
     n_hi = population.N if n_hi is None else n_hi
     M = n_hi - n_lo
     if M <= 0:
@@ -206,7 +263,7 @@ def sample_glms_hmc(population, x, n_samples, n_warmup=200, n_leapfrog=10, step_
     minv, factor, dense_rows, setup_s = resolve_mass(population, x, mass, n_lo, n_hi, mass_floor, factor_on_device)
     with session(population) as (torch, dev, stream, handles):
         out = _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, n_leapfrog, step_sz, thin, minv,
-                     int(seed), n_lo, n_hi, M, factor)
+                     int(seed), n_lo, n_hi, M, factor, n_chains, init_jitter)
     if dense_rows is not None:
         out['dense_rows'] = dense_rows
     population.last_fit_stats['mass_setup_s'] = setup_s
@@ -214,21 +271,32 @@ def sample_glms_hmc(population, x, n_samples, n_warmup=200, n_leapfrog=10, step_
 
 
 def _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, n_leapfrog, step_sz, thin, mass, seed, n_lo, n_hi,
-           M, factor=None):
+           M, factor=None, n_chains=1, init_jitter=0.0):
+    from theano_pyglm_amd.inference.mass_adapt import adapt_windows, schedule_ints
     pk = _Packing(population, torch, handles, (n_lo, n_hi))
     assert pk.identity                                        # (hvp_packing() is None: the row IS the theta row)
     h0 = handles[0]
     P = pk.Pp
     prm = pk.prior_params()
     f64 = torch.float64
-    MP = M * P
-    st = torch.zeros(h0.hmc_state_doubles(M, P), dtype=f64, device=dev)
-    q = st[0:MP].view(M, P)
-    sc = st[4 * MP:].view(NSCAL, M)
-    q.copy_(torch.tensor(pk.pack(x, n_lo, n_hi), dtype=f64, device=dev))
+    C, R = n_chains, n_chains * M                             # rows: chain c of neuron n_lo + m is row c M + m
+    RP = R * P
+    st = torch.zeros(h0.hmc_state_doubles(R, P), dtype=f64, device=dev)
+    q = st[0:RP].view(R, P)
+    sc = st[4 * RP:].view(NSCAL, R)
+    q.copy_(torch.tensor(chain_starts(pk, x, n_lo, n_hi, C, seed, init_jitter), dtype=f64, device=dev))
     Weff = torch.tensor(population.W_eff(x), dtype=f64, device=dev)
     assert P == population.glm.P                              # (resolve_mass checked mass against it)
-    minv = torch.tensor(mass, dtype=f64, device=dev) if mass is not None else None
+    adapt = isinstance(mass, str) and mass == 'adapt'
+    windows, ad, sched = [], None, None
+    if adapt:                                                 # ones: the identity chain until the first window ends
+        minv = torch.ones((R, P), dtype=f64, device=dev)
+        windows = adapt_windows(n_warmup)
+        if windows:
+            ad = torch.zeros(h0.adapt_state_doubles(R, P), dtype=f64, device=dev)
+            sched = torch.tensor(schedule_ints(windows), dtype=torch.int32, device=dev)
+    else:
+        minv = per_row(torch.tensor(mass, dtype=f64, device=dev), M, C) if mass is not None else None
     step = np.ascontiguousarray(np.broadcast_to(np.asarray(step_sz, dtype=float), (M,)))
     if not np.all(step > 0.0):
         raise ValueError("step_sz must be positive")
@@ -236,28 +304,31 @@ def _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, n_le
     Wd = None
     if factor is not None:                                    # (M, P, P) lower-triangular factors: uploaded once
         assert tuple(factor.shape) == (M, P, P)
-        Wd = factor if torch.is_tensor(factor) else torch.tensor(factor, dtype=f64, device=dev)
-    Xt = torch.empty((M, P), dtype=f64, device=dev)
-    evaluate = RangeEvaluator(torch, dev, handles, Weff, M, P, n_lo, n_hi)
-    samples = torch.empty((n_samples, M, P), dtype=f64, device=dev)
-    counts = {'row': 0, 'syncs': 0}
+        Wd = per_row(factor if torch.is_tensor(factor) else torch.tensor(factor, dtype=f64, device=dev), M, C)
+    Xt = torch.empty((R, P), dtype=f64, device=dev)
+    evaluate = RangeEvaluator(torch, dev, handles, Weff, M, P, n_lo, n_hi, C)
+    samples = torch.empty((n_samples, R, P), dtype=f64, device=dev)
+    counts = {'row': 0, 'adapt': 0, 'syncs': 0}
 
     def wait():
         counts['syncs'] += 1
         stream.synchronize()
 
     ll0, g0 = evaluate(q)
-    h0.hmc_init_dev(st.data_ptr(), M, P, n_lo, ll0.data_ptr(), g0.data_ptr(), prm, float(step[0]), seed)
+    if C == 1:
+        h0.hmc_init_dev(st.data_ptr(), M, P, n_lo, ll0.data_ptr(), g0.data_ptr(), prm, float(step[0]), seed)
+    else:
+        h0.hmc_init_chains_dev(st.data_ptr(), M, C, P, n_lo, ll0.data_ptr(), g0.data_ptr(), prm, float(step[0]), seed)
     if np.any(step != step[0]):
-        sc[SC_STEP].copy_(torch.tensor(step, dtype=f64, device=dev))
+        sc[SC_STEP].copy_(torch.tensor(np.tile(step, C), dtype=f64, device=dev))
     n_total = n_warmup + n_samples * thin
     syncs_before_chain = counts['syncs']
     evals_before_chain = evaluate.count
     for t in range(n_total):
         if Wd is not None:
-            h0.hmc_dense_begin_dev(st.data_ptr(), M, P, Wd.data_ptr(), 0, Xt.data_ptr())
+            h0.hmc_dense_begin_dev(st.data_ptr(), R, P, Wd.data_ptr(), 0, Xt.data_ptr())
         else:
-            h0.hmc_begin_dev(st.data_ptr(), M, P, minv_ptr, Xt.data_ptr())
+            h0.hmc_begin_dev(st.data_ptr(), R, P, minv_ptr, Xt.data_ptr())
         counts['row'] += 1
         k = t - n_warmup
         keep = k >= 0 and (k + 1) % thin == 0
@@ -266,24 +337,36 @@ def _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, n_le
             last = i == n_leapfrog - 1
             out_ptr = samples[k // thin].data_ptr() if (last and keep) else 0
             if Wd is not None:
-                h0.hmc_dense_leap_dev(st.data_ptr(), M, P, Wd.data_ptr(), 0, llt.data_ptr(), gt.data_ptr(), prm,
+                h0.hmc_dense_leap_dev(st.data_ptr(), R, P, Wd.data_ptr(), 0, llt.data_ptr(), gt.data_ptr(), prm,
                                       last, n_warmup, Xt.data_ptr(), out_ptr)
             else:
-                h0.hmc_leap_dev(st.data_ptr(), M, P, minv_ptr, llt.data_ptr(), gt.data_ptr(), prm, last, n_warmup,
+                h0.hmc_leap_dev(st.data_ptr(), R, P, minv_ptr, llt.data_ptr(), gt.data_ptr(), prm, last, n_warmup,
                                 Xt.data_ptr(), out_ptr)
             counts['row'] += 1
+        if windows and windows[0][0] <= t < windows[-1][1]:   # (the rows' window state is on the device; the host only
+            h0.mass_adapt_dev(st.data_ptr(), R, P, ad.data_ptr(), sched.data_ptr(), minv_ptr)   # knows when none is open)
+            counts['adapt'] += 1
     syncs_in_chain = counts['syncs'] - syncs_before_chain
     wait()
     sch = sc.cpu().numpy()
-    out = {'samples': samples.cpu().numpy(), 'accept_rate': sch[SC_NACC] / float(n_samples * thin), 'step_sz': sch[SC_STEP].copy(),
-           'n_evals': evaluate.count}
+    out = {'samples': split_chains(samples.cpu().numpy(), M, C, 1),
+           'accept_rate': split_chains(sch[SC_NACC] / float(n_samples * thin), M, C, 0),
+           'step_sz': split_chains(sch[SC_STEP].copy(), M, C, 0), 'n_evals': evaluate.count}
+    if adapt:
+        out['minv'] = split_chains(minv.cpu().numpy(), M, C, 0)
+        out['adapt_windows'] = windows
     # ('row' counts the begin / leap CALLS of the C ABI; a dense call is three small launches, a diagonal one is one)
     population.last_fit_stats = {'sampler': 'lock-step HMC (hip row kernels)', 'transitions': n_total,
-                                 'mass': 'dense' if Wd is not None else ('diagonal' if minv is not None else 'identity'),
+                                 'mass': 'dense' if Wd is not None else ('adapted diagonal' if adapt else
+                                                                         ('diagonal' if minv is not None else 'identity')),
                                  'll_grad_launches': evaluate.count, 'row_launches': counts['row'],
                                  'evaluations_per_transition': (evaluate.count - evals_before_chain) / float(n_total),
                                  'row_launches_per_transition': counts['row'] / float(n_total),
                                  'host_syncs_in_chain': syncs_in_chain, 'host_syncs': counts['syncs']}
+    if adapt:
+        population.last_fit_stats['adapt_launches'] = counts['adapt']
+    if C > 1:
+        population.last_fit_stats['n_chains'] = C
     return out
 
 
@@ -310,10 +393,20 @@ def effective_sample_size(x):
     return float(n / max(tau, 1.0 / n))
 
 
-def summarize(samples):
+def summarize(samples, chains=False):
     """Per-parameter summary of samples (n, ...): dict of arrays shaped like one draw -- 'mean', 'sd' (n - 1), 'q025',
-    'q975' and 'ess' (effective_sample_size)."""
+    'q975' and 'ess' (effective_sample_size).  chains=True: samples (n_chains, n, ...) as the samplers return them with
+    n_chains > 1 -- the moments and quantiles of the pooled draws, 'ess' the sum of the chains' effective sample sizes, and
+    'rhat' (mass_adapt.rhat: split-R-hat)."""
     s = np.asarray(samples, dtype=float)
+    if chains:
+        from theano_pyglm_amd.inference.mass_adapt import rhat
+        if s.ndim < 2:
+            raise ValueError("summarize(chains=True): samples (n_chains, n, ...)")
+        out = summarize(s.reshape((s.shape[0] * s.shape[1],) + s.shape[2:]))
+        out['ess'] = sum(summarize(c)['ess'] for c in s)
+        out['rhat'] = rhat(s)
+        return out
     n = s.shape[0]
     flat = s.reshape(n, -1)
     ess = np.array([effective_sample_size(flat[:, j]) for j in range(flat.shape[1])]).reshape(s.shape[1:])

@@ -42,17 +42,26 @@ def session(population):
 class RangeEvaluator(object):
     """ll and its gradient of the rows [n_lo, n_hi) at X (M, P): one pgl_ll_grad_dev per data sequence into that sequence's
     [ll | grad] buffer, summed into the first.  evaluator(X) -> (ll (M,), grad (M, P)), views of the first buffer, valid
-    until the next call; .count: the calls so far."""
+    until the next call; .count: the calls so far.
+    n_chains = C > 1: X is (C M, P), chain-major (row c M + m: chain c of neuron n_lo + m), the buffers hold C M rows and a
+    call is C pgl_ll_grad_dev per data sequence, one per chain block; .count still counts calls."""
 
-    def __init__(self, torch, dev, handles, Weff, M, P, n_lo, n_hi):
+    def __init__(self, torch, dev, handles, Weff, M, P, n_lo, n_hi, n_chains=1):
         self.handles, self.Weff, self.M, self.n_lo, self.n_hi = handles, Weff, M, n_lo, n_hi
-        self.bufs = [torch.empty(M * (1 + P), dtype=torch.float64, device=dev) for _ in handles]
+        self.P, self.C, self.R = P, int(n_chains), M * int(n_chains)
+        self.bufs = [torch.empty(self.R * (1 + P), dtype=torch.float64, device=dev) for _ in handles]
         self.count = 0
 
     def __call__(self, X):
-        M, tot = self.M, None
+        M, R, P, tot = self.M, self.R, self.P, None
         for h, buf in zip(self.handles, self.bufs):
-            h.ll_grad_dev(X.data_ptr(), self.Weff.data_ptr(), buf.data_ptr(), buf[M:].data_ptr(), self.n_lo, self.n_hi)
+            if self.C == 1:
+                h.ll_grad_dev(X.data_ptr(), self.Weff.data_ptr(), buf.data_ptr(), buf[M:].data_ptr(), self.n_lo, self.n_hi)
+            else:
+                xp, lp, gp = X.data_ptr(), buf.data_ptr(), buf[R:].data_ptr()
+                for c in range(self.C):
+                    h.ll_grad_dev(xp + 8 * c * M * P, self.Weff.data_ptr(), lp + 8 * c * M, gp + 8 * c * M * P, self.n_lo,
+                                  self.n_hi)
             tot = buf if tot is None else tot.add_(buf)
         self.count += 1
-        return tot[:M], tot[M:]
+        return tot[:R], tot[R:]
