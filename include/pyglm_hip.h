@@ -90,6 +90,10 @@ typedef struct pgl_context* pgl_handle;
  * fused / Gibbs kernels (!= 0 invalidates the results, except bit 0x1000: event-window pair currents although all columns
  * share the presynaptic neuron, and bits 8-11: forced sub-block count of k_gibbs_rate_cols). */
 
+/* What pgl_version() returns: it changes with every change of a signature or a struct below, and a binding refuses a
+ * library that reports another number (theano_pyglm_amd/_lib.py: ABI_VERSION). */
+#define PGL_ABI_VERSION 107
+
 const char* pgl_last_error(void);
 int pgl_version(void);
 /* number of visible HIP devices (0 when there is none; never fails) */
@@ -253,20 +257,26 @@ int pgl_tri_inverse_dev(pgl_handle h, double* d_L, int M, int P, int ld, const i
  *   trial:      Xt[j] = X[r] + alpha[r] p[r], r = d_rows[j] (NULL: j), j < L
  *   objective:  rows of d_Xt are theta rows [bias, w_stim, w_ir]; in place ll -> f = -(ll + log prior),
  *               grad -> g = -(grad + prior gradient) with fit_glm's NaN rules (coord_descent.py:170-182);
- *               priors: bias.py:33, bkgd.py:76 (stim_sigma), priors.py:139 (kind 0) / 202 (kind 1: group lasso)
- *               (rows in another packing: the caller supplies f and g itself)
+ *               the prior is a pgl_prior (rows in another packing: the caller supplies f and g itself)
  *   linesearch: one step of every listed row's search: next trial step, or the row takes the step (acc = 1), or the
  *               search is stuck: best sufficient-decrease point if any, else stall = 1 (scipy stops with
  *               "precision loss" there); at most max_trials steps per search (scipy: 100)
  *   hmul:       rows with acc = 1: H += U V^T (pending update) and t = H g in one pass over H
  *   update:     U, V, H_new g, next direction and first step, restart (once) / freeze of stalled rows, convergence;
  *               init_scaling != 0: H <- (s.y / y.y) I before the first update after a (re)start (not scipy's). */
+
+/* The prior of a theta row [bias, w_stim, w_ir], for every lock-step call below that takes one (read during the call, not
+ * kept):  bias ~ N(mu_b, sg_b) (bias.py:33), stimulus weights ~ N(0, stim_sigma) (bkgd.py:76), and the impulse weights
+ * kind 0: N(mu, sigma) (priors.py:139), kind 1: group lasso, -(lam / sigma) sum_g |w_g - mu|_2 over the N groups of B
+ * (priors.py:202).  Any other kind is PGL_ERR_ARG, except that pgl_bfgs_step_dev takes kind < 0 as "f and g arrive final".
+ * A NULL prior is PGL_ERR_ARG. */
+typedef struct pgl_prior { int kind; double mu_b, sg_b, stim_sigma, mu, sigma, lam; } pgl_prior;
+
 long long pgl_bfgs_state_doubles(int M, int P);
 int pgl_bfgs_init_dev(pgl_handle h, double* d_state, int M, int P, double gtol);
 int pgl_bfgs_trial_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, double* d_Xt);
 int pgl_bfgs_objective_dev(pgl_handle h, int L, int P, const double* d_Xt, double* d_ll_f, double* d_grad_g,
-                           int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma,
-                           double lam);
+                           const pgl_prior* prior);
 int pgl_bfgs_linesearch_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, const double* d_Xt,
                             const double* d_f, const double* d_g, int max_trials);
 int pgl_bfgs_hmul_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, double* d_H, int ld);
@@ -281,7 +291,7 @@ int pgl_bfgs_update_dev(pgl_handle h, double* d_state, int M, int P, double gtol
                         double* d_coef, int Kmax);
 /* Everything an evaluation of the L listed rows is followed by, as ONE call (and, while the update history is short, ONE
  * row kernel -- one workgroup per row -- instead of objective | linesearch | hmul | update | trial): priors and NaN rules on
- * (d_ll_f, d_grad_g) in place (prior_kind >= 0; < 0: they already hold f and g), the line-search step, t = H g for the rows
+ * (d_ll_f, d_grad_g) in place (prior->kind >= 0; < 0: they already hold f and g), the line-search step, t = H g for the rows
  * that took a step (update history d_hist / d_coef / d_ab as for pgl_bfgs_hmul_hist_dev, or dense d_H / ld as for
  * pgl_bfgs_hmul_dev -- exactly one of the two), the update, and the NEXT trial point of every listed row:
  *   d_Xt_next[d_pos_next[r]] = X[r] + alpha[r] p[r]   (d_pos_next (M) int32: position of row r in the next launch's list, < 0
@@ -290,10 +300,9 @@ int pgl_bfgs_update_dev(pgl_handle h, double* d_state, int M, int P, double gtol
  * driver polls it behind an event, no copy kernel.  hk_bound: upper bound on the updates in any row's history (launches so
  * far), selects the one-kernel or the split form (PGL_OPT_BFGS_MERGE).  coord_descent.py:161-204 is the unit replaced. */
 int pgl_bfgs_step_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, const double* d_Xt, double* d_ll_f,
-                      double* d_grad_g, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma,
-                      double lam, int max_trials, double gtol, int maxiter, int init_scaling, double* d_hist, double* d_coef,
-                      int Kmax, double* d_ab, int hk_bound, double* d_H, int ld, const int* d_pos_next, double* d_Xt_next,
-                      double* flags_out);
+                      double* d_grad_g, const pgl_prior* prior, int max_trials, double gtol, int maxiter, int init_scaling,
+                      double* d_hist, double* d_coef, int Kmax, double* d_ab, int hk_bound, double* d_H, int ld,
+                      const int* d_pos_next, double* d_Xt_next, double* flags_out);
 
 /* Lock-step Newton-CG (inference/batched_newton_cg.py) as row kernels on the handle's stream: the algorithm of
  * scipy.optimize.minimize(method='Newton-CG', jac=, hessp=) as fit_glm(use_rop=True) calls it per neuron
@@ -306,7 +315,7 @@ int pgl_bfgs_step_dev(pgl_handle h, double* d_state, int M, int P, const int* d_
  *               1 maxiter, 2 precision loss, 3 CG failure), phase (0 CG, 1 line search, 2 finished), slope, alpha, fb,
  *               alpha_acc, moved;  then the line-search state, (18, M).
  * Rows are theta rows [bias, w_stim, w_ir]; the objective is f = -(ll + log prior), H v = -(H_ll v + H_prior v) with the
- * priors of pgl_bfgs_objective_dev (same arguments) and fit_glm's NaN rules (objective NaN -> 1e16, a gradient or a
+ * pgl_prior and fit_glm's NaN rules (objective NaN -> 1e16, a gradient or a
  * product holding a NaN -> 0).  d_V (M, P) is the input of the next product, row by row (zero for every row whose CG does
  * not run, so that its product is harmless); flags_out (NULL or M doubles of PINNED host memory) receives the phase of
  * every row a kernel has advanced, written by the kernel itself.  A finished row is never written again.
@@ -320,22 +329,21 @@ int pgl_bfgs_step_dev(pgl_handle h, double* d_state, int M, int P, const int* d_
  *                position; < 0: not listed; d_Xt_next NULL: none, use trial); accepted -> convergence test
  *                (|alpha pk|_1 <= P * 1e-5: status 0) or the start of the next outer iteration as in init. */
 long long pgl_ncg_state_doubles(int M, int P);
-int pgl_ncg_init_dev(pgl_handle h, double* d_state, int M, int P, double* d_ll, double* d_grad, int prior_kind, double mu_b,
-                     double sg_b, double stim_sigma, double mu, double sigma, double lam, int maxiter, double* d_V,
-                     double* flags_out);
-int pgl_ncg_cg_step_dev(pgl_handle h, double* d_state, int M, int P, double* d_hv, int prior_kind, double mu_b, double sg_b,
-                        double stim_sigma, double mu, double sigma, double lam, double* d_V, double* flags_out);
+int pgl_ncg_init_dev(pgl_handle h, double* d_state, int M, int P, double* d_ll, double* d_grad, const pgl_prior* prior,
+                     int maxiter, double* d_V, double* flags_out);
+int pgl_ncg_cg_step_dev(pgl_handle h, double* d_state, int M, int P, double* d_hv, const pgl_prior* prior, double* d_V,
+                        double* flags_out);
 int pgl_ncg_trial_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, double* d_Xt);
 int pgl_ncg_search_step_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, const double* d_Xt,
-                            double* d_ll_f, double* d_grad_g, int prior_kind, double mu_b, double sg_b, double stim_sigma,
-                            double mu, double sigma, double lam, int maxiter, const int* d_pos_next, double* d_Xt_next,
-                            double* d_V, double* flags_out);
+                            double* d_ll_f, double* d_grad_g, const pgl_prior* prior, int maxiter, const int* d_pos_next,
+                            double* d_Xt_next, double* d_V, double* flags_out);
 
 /* Lock-step Hamiltonian Monte Carlo (inference/batched_hmc.py) as row kernels on the handle's stream: posterior samples of
- * the theta rows [bias, w_stim, w_ir] of M neurons n_lo .. n_lo + M - 1 at once, one workgroup per row around ONE
+ * the theta rows [bias, w_stim, w_ir] of M neurons n_lo .. n_lo + M - 1 at once (C chains each: see "chains" below; every
+ * call but init takes the C M rows as its M), one workgroup per row around ONE
  * pgl_ll_grad_dev over all rows per leapfrog step.  The algorithm is Neal (2011) fig. 2 as inference/hmc.py: hmc_lockstep
  * states it (restated in csrc/pglm_hmc.h) with a diagonal mass matrix:
- *     U = -(ll + log prior), the priors of pgl_bfgs_objective_dev (same arguments).  A non-finite ll + log prior gives
+ *     U = -(ll + log prior), the prior a pgl_prior.  A non-finite ll + log prior gives
  *         U = +inf; a NaN or infinite entry of its gradient becomes 0; a transition that ends at a non-finite energy is
  *         rejected (the rules of hmc_lockstep's callers, gibbs.py: _neg_lp_grad).
  *     K = 1/2 sum_j p_j^2 minv_j;  d_minv (M, P) is the diagonal of the inverse mass matrix, NULL = identity.
@@ -360,7 +368,7 @@ int pgl_ncg_search_step_dev(pgl_handle h, double* d_state, int M, int P, const i
  *   (M) each:   U0 (U at the last accepted point), H0, step, avg_accept (starts at 0.9), n_accept (accepted transitions
  *               among those with t >= n_warmup), t (completed transitions), acc (the last decision), neuron, seed_lo,
  *               seed_hi (the 32-bit halves of the seed).
- *   init:   q in the state, (d_ll, d_grad) = ll (M) and its gradient (M, P) at q (overwritten with U, grad U); t = 0.
+ *   init:   q in the state, (d_ll, d_grad) = ll (C M) and its gradient (C M, P) at q (overwritten with U, grad U); t = 0.
  *   begin:  draws the momentum, H0, the half kick and the first drift; d_Xt (M, P, not part of the state) = the points to
  *           evaluate next.
  *   leap:   (d_ll, d_grad) = the evaluation at d_Xt (overwritten).  last == 0: full kick, next drift into d_Xt.
@@ -369,13 +377,11 @@ int pgl_ncg_search_step_dev(pgl_handle h, double* d_state, int M, int P, const i
  *           NULL, the rows' current points q into d_sample_out (M, P).
  * One transition is n_leapfrog evaluations and n_leapfrog + 1 row launches; nothing has to be read back in between. */
 long long pgl_hmc_state_doubles(int M, int P);
-int pgl_hmc_init_dev(pgl_handle h, double* d_state, int M, int P, int n_lo, double* d_ll, double* d_grad, int prior_kind,
-                     double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam, double step0,
-                     uint64_t seed);
+int pgl_hmc_init_dev(pgl_handle h, double* d_state, int M, int C, int P, int n_lo, double* d_ll, double* d_grad,
+                     const pgl_prior* prior, double step0, uint64_t seed);
 int pgl_hmc_begin_dev(pgl_handle h, double* d_state, int M, int P, const double* d_minv, double* d_Xt);
 int pgl_hmc_leap_dev(pgl_handle h, double* d_state, int M, int P, const double* d_minv, double* d_ll, double* d_grad,
-                     int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam, int last,
-                     int n_warmup, double* d_Xt, double* d_sample_out);
+                     const pgl_prior* prior, int last, int n_warmup, double* d_Xt, double* d_sample_out);
 
 /* Lock-step HMC with a DENSE mass matrix (inference/batched_hmc.py: mass = (M, P, P) or 'laplace_dense'; restated in
  * csrc/pglm_hmc_dense.h).  The inverse mass matrix of row m is Sigma_m = W_m W_m^T, d_W (M, P, P) row-major with W_m lower
@@ -395,15 +401,12 @@ int pgl_hmc_leap_dev(pgl_handle h, double* d_state, int M, int P, const double* 
  *   leap:   (d_ll, d_grad) = the evaluation at d_Xt (overwritten with U, grad U).  last == 0: the kick and the next drift,
  *           again inside the products: three launches.  last != 0: the half kick, then H1, accept or reject, the step-size
  *           rule while t < n_warmup, t += 1 and d_sample_out as pgl_hmc_leap_dev: three launches.
- *   d_work: pgl_hmc_dense_work_doubles(M, P) doubles of scratch for the calls.  Because no product is ever stored, that
- *           is 0 and d_work may be NULL; the argument keeps the calls open to an unfused implementation.
+ * No product is ever stored, so the calls need no workspace.
  * One transition is n_leapfrog evaluations and 3 (n_leapfrog + 1) small launches; nothing has to be read back in between. */
-long long pgl_hmc_dense_work_doubles(int M, int P);
 int pgl_tri_matvec_dev(pgl_handle h, const double* d_W, int M, int P, int trans, const double* d_x, double* d_y);
-int pgl_hmc_dense_begin_dev(pgl_handle h, double* d_state, int M, int P, const double* d_W, double* d_work, double* d_Xt);
-int pgl_hmc_dense_leap_dev(pgl_handle h, double* d_state, int M, int P, const double* d_W, double* d_work, double* d_ll,
-                           double* d_grad, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu,
-                           double sigma, double lam, int last, int n_warmup, double* d_Xt, double* d_sample_out);
+int pgl_hmc_dense_begin_dev(pgl_handle h, double* d_state, int M, int P, const double* d_W, double* d_Xt);
+int pgl_hmc_dense_leap_dev(pgl_handle h, double* d_state, int M, int P, const double* d_W, double* d_ll, double* d_grad,
+                           const pgl_prior* prior, int last, int n_warmup, double* d_Xt, double* d_sample_out);
 
 /* The No-U-Turn sampler for the same posteriors (inference/batched_nuts.py; the transition is restated in
  * csrc/pglm_nuts.h and, with its leaves in a list, in inference/nuts.py), as row kernels on the handle's stream: one
@@ -441,21 +444,20 @@ int pgl_hmc_dense_leap_dev(pgl_handle h, double* d_state, int M, int P, const do
  * transition).  Every row runs n_warmup + n_keep thin transitions, counts its own t, writes its kept points into
  * d_samples (n_keep, M, P) and (depth, leapfrog steps) of the kept transitions into d_stats (n_keep, 2, M) (either may
  * be NULL), then sets done and idles with its d_Xt row left at its current point.
- *   pgl_nuts_init_dev:  the rows' points are the first array of d_state; d_ll (M), d_grad (M, P) hold ll and its gradient
+ *   pgl_nuts_init_dev:  C chains of M neurons ("chains" below; every array here then has C M rows, d_minv and d_W one per
+ *           row).  The rows' points are the first array of d_state; d_ll (M), d_grad (M, P) hold ll and its gradient
  *           there (overwritten).  d_step0 (M): the starting steps.  Draws the first momentum; d_Xt = the first points to
  *           evaluate.  1 launch (diagonal), 4 (dense).
  *   pgl_nuts_step_dev:  after one evaluation of all rows at d_Xt: one leapfrog step of every row that is not done and
  *           d_Xt = the next points.  1 launch (diagonal); dense: 2 small launches and 2 products (pgl_tri_matvec_dev's
  *           kernel, the drift its epilogue). */
 long long pgl_nuts_state_doubles(int M, int P, int max_depth);
-int pgl_nuts_init_dev(pgl_handle h, double* d_state, int M, int P, int max_depth, int n_lo, double* d_ll, double* d_grad,
-                      int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam,
-                      const double* d_minv, const double* d_W, const double* d_step0, uint64_t seed, int n_warmup, int thin,
-                      int n_keep, double* d_Xt);
+int pgl_nuts_init_dev(pgl_handle h, double* d_state, int M, int C, int P, int max_depth, int n_lo, double* d_ll,
+                      double* d_grad, const pgl_prior* prior, const double* d_minv, const double* d_W, const double* d_step0,
+                      uint64_t seed, int n_warmup, int thin, int n_keep, double* d_Xt);
 int pgl_nuts_step_dev(pgl_handle h, double* d_state, int M, int P, int max_depth, double* d_ll, double* d_grad,
-                      int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam,
-                      const double* d_minv, const double* d_W, double target_accept, int n_warmup, int thin, int n_keep,
-                      double* d_Xt, double* d_samples, double* d_stats);
+                      const pgl_prior* prior, const double* d_minv, const double* d_W, double target_accept, int n_warmup,
+                      int thin, int n_keep, double* d_Xt, double* d_samples, double* d_stats);
 
 /* Several chains per neuron, and a diagonal mass matrix learned during the warm-up (inference/batched_hmc.py and
  * batched_nuts.py: n_chains, mass='adapt'; the rules are csrc/pglm_adapt.h, the host side inference/mass_adapt.py).
@@ -464,8 +466,8 @@ int pgl_nuts_step_dev(pgl_handle h, double* d_state, int M, int P, int max_depth
  *               n_lo + M) takes and returns.  Chain c runs on the seed  chain_seed(seed, c) = seed for c = 0, else
  *               mix(mix(seed + G) ^ (G c))  (64-bit; mix = pgl_hmc's finaliser, G = 0x9e3779b97f4a7c15), with the key
  *               (that seed, neuron index, transition): chain c equals the single-chain run with that seed, bit for bit.
- *               The init calls below set this up; every other call of the chain takes M = R rows (d_minv (R, P), d_W
- *               (R, P, P): one per row).
+ *               pgl_hmc_init_dev and pgl_nuts_init_dev set this up from (M, C); every other call of the chain takes M = R
+ *               rows (d_minv (R, P), d_W (R, P, P): one per row).
  *   schedule    host side, from n = n_warmup (Stan's windowed adaptation):  n < 20: no window.  n >= 150: init = 75, term
  *               = 50, base = 25;  else init = floor(0.15 n), term = floor(0.10 n), base = n - init - term.  Windows start
  *               at init, have sizes base, 2 base, 4 base, ... and tile [init, n - term): a window is stretched to n - term
@@ -482,25 +484,16 @@ int pgl_nuts_step_dev(pgl_handle h, double* d_state, int M, int P, int max_depth
  *               t and the momentum draw of t + 1.
  * d_adapt: pgl_adapt_state_doubles(R, P) doubles, zeroed by the caller = mean (R, P), M2 (R, P), count (R), window index (R).
  * d_minv (R, P): ones at the start (the chain before the first window's end is the identity-mass chain, bit for bit).
- *   pgl_hmc_init_chains_dev, pgl_nuts_init_chains_dev:  pgl_hmc_init_dev / pgl_nuts_init_dev for C chains (C = 1: the same).
  *   pgl_mass_adapt_dev:  HMC, one small launch after the last pgl_hmc_leap_dev of a transition and before the next
  *           pgl_hmc_begin_dev (which reads d_minv); needed only for transitions init <= t < the last window's end.
  *   pgl_nuts_adapt_step_dev:  pgl_nuts_step_dev for the diagonal chain, with the rules above applied inside the row kernel
  *           at the row's own transition boundary (rows are asynchronous), before the next momentum and edge are formed;
  *           h = sqrt(minv) o grad U of the current point is recomputed at a switch.  1 launch. */
 long long pgl_adapt_state_doubles(int R, int P);
-int pgl_hmc_init_chains_dev(pgl_handle h, double* d_state, int M, int C, int P, int n_lo, double* d_ll, double* d_grad,
-                            int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam,
-                            double step0, uint64_t seed);
-int pgl_nuts_init_chains_dev(pgl_handle h, double* d_state, int M, int C, int P, int max_depth, int n_lo, double* d_ll,
-                             double* d_grad, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu,
-                             double sigma, double lam, const double* d_minv, const double* d_W, const double* d_step0,
-                             uint64_t seed, int n_warmup, int thin, int n_keep, double* d_Xt);
 int pgl_mass_adapt_dev(pgl_handle h, double* d_state, int R, int P, double* d_adapt, const int* d_sched, double* d_minv);
 int pgl_nuts_adapt_step_dev(pgl_handle h, double* d_state, int M, int P, int max_depth, double* d_ll, double* d_grad,
-                            int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam,
-                            double* d_minv, double* d_adapt, const int* d_sched, double target_accept, int n_warmup, int thin,
-                            int n_keep, double* d_Xt, double* d_samples, double* d_stats);
+                            const pgl_prior* prior, double* d_minv, double* d_adapt, const int* d_sched, double target_accept,
+                            int n_warmup, int thin, int n_keep, double* d_Xt, double* d_samples, double* d_stats);
 
 /* Annealed importance sampling (Neal 2001; inference/batched_ais.py) of the evidence log Z_n of every neuron given the
  * network, as row kernels on the handle's stream, on top of the HMC moves above (restated nowhere: csrc/pglm_ais.h uses
@@ -508,9 +501,8 @@ int pgl_nuts_adapt_step_dev(pgl_handle h, double* d_state, int M, int P, int max
  * r = k M + i is particle particle0 + k of neuron n_lo + i -- so block k of any (R, P) array is the (M, P) theta block one
  * pgl_ll_grad_dev(n_lo, n_lo + M) takes and returns.  Over a ladder 0 = beta_0 < ... < beta_J = 1 the target is
  *     U_beta = -(beta ll + log prior),  grad U_beta = -(beta grad ll + grad log prior),  with the NaN rules above.
- * Only the Gaussian priors are served (prior_kind 0: bias N(mu_b, sg_b), stimulus weights N(0, stim_sigma), impulse
- * weights N(mu, sigma), all standard deviations positive): the start is an exact draw from the normalised prior.
- * prior_kind 1 returns PGL_ERR_UNSUPPORTED.  Per row:
+ * Only the Gaussian priors are served (pgl_prior kind 0, all standard deviations positive): the start is an exact draw
+ * from the normalised prior.  kind 1 returns PGL_ERR_UNSUPPORTED.  Per row:
  *     1. q_j = m_j + s_j z_j;  evaluate;  log w = 0.
  *     2. for j = 1 .. J:  log w += (beta_j - beta_{j-1}) ll0, ll0 = ll at the current point -- the point that was sampled
  *        under beta_{j-1} (a non-finite ll0 makes log w = -inf for good);  then the target becomes U_{beta_j}.
@@ -540,17 +532,16 @@ int pgl_nuts_adapt_step_dev(pgl_handle h, double* d_state, int M, int P, int max
  *           t += 1; d_acc_out[r] += the decision and d_step_out[r] = the row's step after it (R entries each; NULL: none).
  * One leapfrog step is K pgl_ll_grad_dev calls (one per particle block) and one row launch; nothing is read back. */
 long long pgl_ais_state_doubles(int R, int P);
-int pgl_ais_init_dev(pgl_handle h, double* d_state, int K, int M, int P, int n_lo, int particle0, int prior_kind, double mu_b,
-                     double sg_b, double stim_sigma, double mu, double sigma, double lam, double step0, uint64_t seed,
-                     double* d_Xt);
+int pgl_ais_init_dev(pgl_handle h, double* d_state, int K, int M, int P, int n_lo, int particle0, const pgl_prior* prior,
+                     double step0, uint64_t seed, double* d_Xt);
 int pgl_ais_start_dev(pgl_handle h, double* d_state, int K, int M, int P, const double* d_ll, const double* d_grad,
-                      int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam);
-int pgl_ais_temper_dev(pgl_handle h, double* d_state, int K, int M, int P, int prior_kind, double mu_b, double sg_b,
-                       double stim_sigma, double mu, double sigma, double lam, double beta, const double* d_step_row);
+                      const pgl_prior* prior);
+int pgl_ais_temper_dev(pgl_handle h, double* d_state, int K, int M, int P, const pgl_prior* prior, double beta,
+                       const double* d_step_row);
 int pgl_ais_begin_dev(pgl_handle h, double* d_state, int K, int M, int P, const double* d_minv, double* d_Xt);
 int pgl_ais_leap_dev(pgl_handle h, double* d_state, int K, int M, int P, const double* d_minv, const double* d_ll,
-                     const double* d_grad, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma,
-                     double lam, int last, int adapt, double* d_Xt, double* d_acc_out, double* d_step_out);
+                     const double* d_grad, const pgl_prior* prior, int last, int adapt, double* d_Xt, double* d_acc_out,
+                     double* d_step_out);
 
 /* Annealed importance sampling with a DENSE mass matrix (inference/batched_ais.py: mass = (M, P, P) or 'laplace_dense';
  * restated in csrc/pglm_ais_dense.h over csrc/pglm_ais.h and csrc/pglm_hmc_dense.h).  The inverse mass matrix of NEURON i is
@@ -574,13 +565,13 @@ int pgl_ais_leap_dev(pgl_handle h, double* d_state, int K, int M, int P, const d
  *   leap:   (d_ll, d_grad) = the evaluation at d_Xt (left as they are).  last == 0: grad U_beta, then the kick and the next
  *           drift inside the products: three launches.  last != 0: grad U_beta, the half kick, then H1, accept or reject, the
  *           step-size rule if adapt, t += 1, d_acc_out and d_step_out as pgl_ais_leap_dev: three launches.
- * One leapfrog step is K pgl_ll_grad_dev calls and 3 small launches, whatever K is; nothing is read back.  prior_kind 1
- * returns PGL_ERR_UNSUPPORTED. */
+ * One leapfrog step is K pgl_ll_grad_dev calls and 3 small launches, whatever K is; nothing is read back.  A prior of
+ * kind 1 returns PGL_ERR_UNSUPPORTED. */
 int pgl_tri_matvec_shared_dev(pgl_handle h, const double* d_W, int M, int K, int P, int trans, const double* d_x, double* d_y);
 int pgl_ais_dense_begin_dev(pgl_handle h, double* d_state, int K, int M, int P, const double* d_W, double* d_Xt);
 int pgl_ais_dense_leap_dev(pgl_handle h, double* d_state, int K, int M, int P, const double* d_W, const double* d_ll,
-                           const double* d_grad, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu,
-                           double sigma, double lam, int last, int adapt, double* d_Xt, double* d_acc_out, double* d_step_out);
+                           const double* d_grad, const pgl_prior* prior, int last, int adapt, double* d_Xt, double* d_acc_out,
+                           double* d_step_out);
 
 /* Lock-step accelerated proximal gradient for the group-lasso MAP (inference/batched_prox.py) as row kernels on the
  * handle's stream: the theta rows [bias, w_stim (Ds), w_ir (N groups of B)] of M neurons n_lo .. n_lo + M - 1 at once, one
@@ -622,14 +613,13 @@ int pgl_ais_dense_leap_dev(pgl_handle h, double* d_state, int K, int M, int P, c
  *          that has not ended; d_Xt = the points to evaluate next.  An ended row keeps x in its row of d_Xt -- it is
  *          evaluated again, harmlessly -- and is never written again.
  * flags_out: NULL, or M doubles of pinned host memory into which every row a kernel has advanced writes its phase: the
- * driver reads it behind an event every few calls and never waits per iteration. */
+ * driver reads it behind an event every few calls and never waits per iteration.
+ * prior: kind must be 1 (else PGL_ERR_ARG); its lam is ignored, d_lam rules. */
 long long pgl_prox_state_doubles(int M, int P);
-int pgl_prox_init_dev(pgl_handle h, double* d_state, int M, int P, double* d_ll, double* d_grad, double mu_b, double sg_b,
-                      double stim_sigma, double mu, double sigma, const double* d_lam, double gtol, int maxiter, double* d_Xt,
-                      double* flags_out);
-int pgl_prox_step_dev(pgl_handle h, double* d_state, int M, int P, double* d_ll, double* d_grad, double mu_b, double sg_b,
-                      double stim_sigma, double mu, double sigma, const double* d_lam, double gtol, int maxiter, int max_backtrack,
-                      double* d_Xt, double* flags_out);
+int pgl_prox_init_dev(pgl_handle h, double* d_state, int M, int P, double* d_ll, double* d_grad, const pgl_prior* prior,
+                      const double* d_lam, double gtol, int maxiter, double* d_Xt, double* flags_out);
+int pgl_prox_step_dev(pgl_handle h, double* d_state, int M, int P, double* d_ll, double* d_grad, const pgl_prior* prior,
+                      const double* d_lam, double gtol, int maxiter, int max_backtrack, double* d_Xt, double* flags_out);
 
 /* convolve_with_basis(S, ibasis) (basis.py:201-236 via impulse.py:114-130):
  * fS_out (nT,N,B) row-major, float64. */

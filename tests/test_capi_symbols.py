@@ -30,6 +30,41 @@ def test_header_symbols_exported():
     assert _lib.load().pgl_version() >= 100
 
 
+def test_prior_struct_layout_and_converter():
+    """_lib.Prior is pgl_prior of the header (the library holds sizeof to 56 with a static_assert), field for field, and
+    as_prior keeps the order of the 7-tuple."""
+    from theano_pyglm_amd import _lib
+    assert ctypes.sizeof(_lib.Prior) == 56
+    assert [f[0] for f in _lib.Prior._fields_] == ['kind', 'mu_b', 'sg_b', 'stim_sigma', 'mu', 'sigma', 'lam']
+    assert [getattr(_lib.Prior, f).offset for f, _ in _lib.Prior._fields_] == [0, 8, 16, 24, 32, 40, 48]
+    src = open(os.path.join(ROOT, 'include', 'pyglm_hip.h')).read()
+    assert 'typedef struct pgl_prior { int kind; double mu_b, sg_b, stim_sigma, mu, sigma, lam; } pgl_prior;' in src
+    t = (1, 0.7, 1.3, 0.45, -0.2, 2.1, 0.35)
+    p = _lib.as_prior(t)
+    assert tuple(getattr(p, f) for f, _ in _lib.Prior._fields_) == t
+    assert _lib.as_prior(p) is p
+    with pytest.raises(ValueError):
+        _lib.as_prior(t[1:6])
+
+
+def test_load_refuses_another_abi_version(monkeypatch):
+    import __graft_entry__ as ge
+    ge.build_hip()
+    from theano_pyglm_amd import _lib
+    built = _lib.load().pgl_version()
+    assert built == _lib.ABI_VERSION == int(re.search(r'#define PGL_ABI_VERSION (\d+)',
+                                                      open(os.path.join(ROOT, 'include', 'pyglm_hip.h')).read()).group(1))
+    monkeypatch.setattr(_lib, 'ABI_VERSION', built + 1)
+    monkeypatch.setattr(_lib, '_lib', None)
+    with pytest.raises(_lib.PglError) as e:
+        _lib.load()
+    assert str(built) in str(e.value) and str(built + 1) in str(e.value) and _lib.LIB_PATH in str(e.value)
+    assert 'rebuild' in str(e.value)
+    assert _lib._lib is None                                  # nothing half-loaded is cached
+    monkeypatch.undo()
+    assert _lib.load().pgl_version() == _lib.ABI_VERSION
+
+
 def test_no_cpu_fallback():
     from theano_pyglm_amd import _lib
     if _lib.device_count() > 0:

@@ -134,7 +134,6 @@ def dense_device_chain(probs, X0, n_lo, n_hi, prm, n_trans, L, step, seed, W, n_
             sc = st[4 * M * P:].view(10, M)
             Weff = torch.tensor(p0.Weff, dtype=f64, device=dev)
             Wd = torch.tensor(_nan_above(W), dtype=f64, device=dev)
-            work = torch.empty(h0.hmc_dense_work_doubles(M, P), dtype=f64, device=dev)
             Xt = torch.empty((M, P), dtype=f64, device=dev)
             bufs = [torch.empty(M * (1 + P), dtype=f64, device=dev) for _ in hs]
             samples = torch.zeros((n_trans, M, P), dtype=f64, device=dev)
@@ -150,11 +149,10 @@ def dense_device_chain(probs, X0, n_lo, n_hi, prm, n_trans, L, step, seed, W, n_
             h0.hmc_init_dev(st.data_ptr(), M, P, n_lo, ll.data_ptr(), g.data_ptr(), prm, step, seed)
             acc = []
             for t in range(n_trans):
-                h0.hmc_dense_begin_dev(st.data_ptr(), M, P, Wd.data_ptr(), work.data_ptr(), Xt.data_ptr())
+                h0.hmc_dense_begin_dev(st.data_ptr(), M, P, Wd.data_ptr(), Xt.data_ptr())
                 for i in range(L):
                     ll, g = evaluate(Xt)
-                    h0.hmc_dense_leap_dev(st.data_ptr(), M, P, Wd.data_ptr(), work.data_ptr(), ll.data_ptr(), g.data_ptr(), prm,
-                                          i == L - 1, n_warmup, Xt.data_ptr(), samples[t].data_ptr() if i == L - 1 else 0)
+                    h0.hmc_dense_leap_dev(st.data_ptr(), M, P, Wd.data_ptr(), ll.data_ptr(), g.data_ptr(), prm, i == L - 1, n_warmup, Xt.data_ptr(), samples[t].data_ptr() if i == L - 1 else 0)
                 stream.synchronize()
                 acc.append(sc[HM.SC['acc']].cpu().numpy() != 0.0)
             stream.synchronize()

@@ -39,10 +39,9 @@ SYMBOLS = [
     'pgl_hvp_prepare_dev', 'pgl_hvp_prepare_list_dev', 'pgl_hvp_apply_dev', 'pgl_hvp',
     'pgl_ncg_state_doubles', 'pgl_ncg_init_dev', 'pgl_ncg_cg_step_dev', 'pgl_ncg_trial_dev', 'pgl_ncg_search_step_dev',
     'pgl_hmc_state_doubles', 'pgl_hmc_init_dev', 'pgl_hmc_begin_dev', 'pgl_hmc_leap_dev',
-    'pgl_hmc_dense_work_doubles', 'pgl_tri_matvec_dev', 'pgl_hmc_dense_begin_dev', 'pgl_hmc_dense_leap_dev',
+    'pgl_tri_matvec_dev', 'pgl_hmc_dense_begin_dev', 'pgl_hmc_dense_leap_dev',
     'pgl_nuts_state_doubles', 'pgl_nuts_init_dev', 'pgl_nuts_step_dev',
-    'pgl_adapt_state_doubles', 'pgl_mass_adapt_dev', 'pgl_nuts_adapt_step_dev', 'pgl_hmc_init_chains_dev',
-    'pgl_nuts_init_chains_dev',
+    'pgl_adapt_state_doubles', 'pgl_mass_adapt_dev', 'pgl_nuts_adapt_step_dev',
     'pgl_prox_state_doubles', 'pgl_prox_init_dev', 'pgl_prox_step_dev',
     'pgl_ais_state_doubles', 'pgl_ais_init_dev', 'pgl_ais_start_dev', 'pgl_ais_temper_dev', 'pgl_ais_begin_dev',
     'pgl_ais_leap_dev',
@@ -54,8 +53,34 @@ SYMBOLS = [
 ]
 
 
+ABI_VERSION = 107                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
+
+
 class PglError(RuntimeError):
     pass
+
+
+class Prior(C.Structure):
+    """pgl_prior of include/pyglm_hip.h."""
+    _fields_ = [('kind', C.c_int), ('mu_b', C.c_double), ('sg_b', C.c_double), ('stim_sigma', C.c_double),
+                ('mu', C.c_double), ('sigma', C.c_double), ('lam', C.c_double)]
+
+
+def as_prior(p):
+    """A Prior from a Prior or from the tuple (kind, mu_b, sg_b, stim_sigma, mu, sigma, lam) of _Packing.prior_params()."""
+    if isinstance(p, Prior):
+        return p
+    if len(p) != 7:
+        raise ValueError("prior: (kind, mu_b, sg_b, stim_sigma, mu, sigma, lam)")
+    return Prior(int(p[0]), *[float(z) for z in p[1:]])
+
+
+def _prox_prior(p):
+    """as_prior for the prox calls, which also take the five numbers (mu_b, sg_b, stim_sigma, mu, sigma) of the smooth part
+    as the host mirror states them (tests/prox_mirror.py): the kind is 1 and lam is the calls' d_lam."""
+    if not isinstance(p, Prior) and len(p) == 5:
+        p = (1,) + tuple(p) + (0.0,)
+    return as_prior(p)
 
 
 def plan_kernels(N, B=5, R=200, Dstim=0, nT=300000, stim=0, n_lo=0, count=None, path=0, opt_kernel=0, opt_f32=0):
@@ -108,11 +133,16 @@ def load():
                        % LIB_PATH)
     _preload_torch_hip()
     lib = C.CDLL(LIB_PATH)
+    lib.pgl_version.restype = C.c_int
+    lib.pgl_version.argtypes = []
+    if lib.pgl_version() != ABI_VERSION:                      # before any signature below is trusted
+        raise PglError("HIP library %s has ABI version %d, this binding needs %d: rebuild it "
+                       "(`python -c 'import __graft_entry__ as g; g.build()'`)" % (LIB_PATH, lib.pgl_version(), ABI_VERSION))
     dp = C.POINTER(C.c_double)
     vp = C.c_void_p
+    pr = C.POINTER(Prior)
     lib.pgl_last_error.restype = C.c_char_p
     lib.pgl_last_error.argtypes = []
-    lib.pgl_version.restype = C.c_int
     lib.pgl_device_count.restype = C.c_int
     lib.pgl_create.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
                                C.POINTER(vp)]
@@ -131,93 +161,68 @@ def load():
     lib.pgl_timing_summary.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.pgl_set_stream.argtypes = [vp, vp]
     lib.pgl_sta.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_double, C.c_int, vp, C.c_int, vp]
-    if hasattr(lib, 'pgl_leading_singular_pairs'):
-        lib.pgl_leading_singular_pairs.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    lib.pgl_leading_singular_pairs.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     lib.pgl_ll_grad.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.pgl_ll_grad_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.pgl_ll_grad_list_dev.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
     lib.pgl_sync.argtypes = [vp]
-    if hasattr(lib, 'pgl_hvp'):                               # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
-        lib.pgl_hvp_prepare_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp]
-        lib.pgl_hvp_prepare_list_dev.argtypes = [vp, vp, C.c_int, vp, vp]
-        lib.pgl_hvp_apply_dev.argtypes = [vp, vp, vp]
-        lib.pgl_hvp.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp]
-    if hasattr(lib, 'pgl_hess'):
-        lib.pgl_hess_dev.argtypes = [vp, vp, C.c_int]
-        lib.pgl_hess.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
-    if hasattr(lib, 'pgl_chol_factor_dev'):                   # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
-        lib.pgl_chol_factor_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
-        lib.pgl_tri_inverse_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
-    if hasattr(lib, 'pgl_rescale'):
-        lib.pgl_rescale_count.argtypes = [vp, vp]
-        lib.pgl_rescale_dev.argtypes = [vp, vp, vp, vp, vp, vp]
-        lib.pgl_rescale.argtypes = [vp, vp, vp, vp, vp]
-    if hasattr(lib, 'pgl_bfgs_hmul_dev'):                     # (older dev A/B builds named by PYGLM_HIP_LIB lack it)
-        lib.pgl_bfgs_state_doubles.argtypes = [C.c_int, C.c_int]
-        lib.pgl_bfgs_init_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double]
-        lib.pgl_bfgs_trial_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp]
-        lib.pgl_bfgs_objective_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int] + [C.c_double] * 6
-        lib.pgl_bfgs_linesearch_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int]
-        lib.pgl_bfgs_hmul_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int]
-        lib.pgl_bfgs_update_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, vp, vp, C.c_int]
-        lib.pgl_bfgs_hmul_hist_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp]
-    if hasattr(lib, 'pgl_bfgs_step_dev'):
-        lib.pgl_bfgs_step_dev.argtypes = ([vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int] + [C.c_double] * 6 +
-                                          [C.c_int, C.c_double, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int,
-                                           vp, vp, vp])
-    if hasattr(lib, 'pgl_ncg_init_dev'):                      # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
-        lib.pgl_ncg_state_doubles.argtypes = [C.c_int, C.c_int]
-        lib.pgl_ncg_init_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int] + [C.c_double] * 6 + [C.c_int, vp, vp]
-        lib.pgl_ncg_cg_step_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int] + [C.c_double] * 6 + [vp, vp]
-        lib.pgl_ncg_trial_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp]
-        lib.pgl_ncg_search_step_dev.argtypes = ([vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int] +
-                                                [C.c_double] * 6 + [C.c_int, vp, vp, vp, vp])
-    if hasattr(lib, 'pgl_hmc_init_dev'):                      # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
-        lib.pgl_hmc_state_doubles.argtypes = [C.c_int, C.c_int]
-        lib.pgl_hmc_init_dev.argtypes = ([vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int] + [C.c_double] * 6 +
-                                         [C.c_double, C.c_uint64])
-        lib.pgl_hmc_begin_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
-        lib.pgl_hmc_leap_dev.argtypes = ([vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int] + [C.c_double] * 6 +
-                                         [C.c_int, C.c_int, vp, vp])
-    if hasattr(lib, 'pgl_hmc_dense_leap_dev'):                # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
-        lib.pgl_hmc_dense_work_doubles.argtypes = [C.c_int, C.c_int]
-        lib.pgl_tri_matvec_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
-        lib.pgl_hmc_dense_begin_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
-        lib.pgl_hmc_dense_leap_dev.argtypes = ([vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int] + [C.c_double] * 6 +
-                                               [C.c_int, C.c_int, vp, vp])
-    if hasattr(lib, 'pgl_nuts_step_dev'):                     # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
-        lib.pgl_nuts_state_doubles.argtypes = [C.c_int, C.c_int, C.c_int]
-        lib.pgl_nuts_init_dev.argtypes = ([vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int] + [C.c_double] * 6 +
-                                          [vp, vp, vp, C.c_uint64, C.c_int, C.c_int, C.c_int, vp])
-        lib.pgl_nuts_step_dev.argtypes = ([vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int] + [C.c_double] * 6 +
-                                          [vp, vp, C.c_double, C.c_int, C.c_int, C.c_int, vp, vp, vp])
-    if hasattr(lib, 'pgl_mass_adapt_dev'):                    # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
-        lib.pgl_adapt_state_doubles.argtypes = [C.c_int, C.c_int]
-        lib.pgl_mass_adapt_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
-        lib.pgl_nuts_adapt_step_dev.argtypes = ([vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int] + [C.c_double] * 6 +
-                                                [vp, vp, vp, C.c_double, C.c_int, C.c_int, C.c_int, vp, vp, vp])
-        lib.pgl_hmc_init_chains_dev.argtypes = ([vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int] +
-                                                [C.c_double] * 6 + [C.c_double, C.c_uint64])
-        lib.pgl_nuts_init_chains_dev.argtypes = ([vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int] +
-                                                 [C.c_double] * 6 + [vp, vp, vp, C.c_uint64, C.c_int, C.c_int, C.c_int, vp])
-    if hasattr(lib, 'pgl_ais_init_dev'):                      # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
-        lib.pgl_ais_state_doubles.argtypes = [C.c_int, C.c_int]
-        kmp = [vp, vp, C.c_int, C.c_int, C.c_int]
-        lib.pgl_ais_init_dev.argtypes = kmp + [C.c_int, C.c_int, C.c_int] + [C.c_double] * 6 + [C.c_double, C.c_uint64, vp]
-        lib.pgl_ais_start_dev.argtypes = kmp + [vp, vp, C.c_int] + [C.c_double] * 6
-        lib.pgl_ais_temper_dev.argtypes = kmp + [C.c_int] + [C.c_double] * 6 + [C.c_double, vp]
-        lib.pgl_ais_begin_dev.argtypes = kmp + [vp, vp]
-        lib.pgl_ais_leap_dev.argtypes = kmp + [vp, vp, vp, C.c_int] + [C.c_double] * 6 + [C.c_int, C.c_int, vp, vp, vp]
-    if hasattr(lib, 'pgl_ais_dense_leap_dev'):                # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
-        lib.pgl_tri_matvec_shared_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
-        lib.pgl_ais_dense_begin_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
-        lib.pgl_ais_dense_leap_dev.argtypes = ([vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int] + [C.c_double] * 6 +
-                                               [C.c_int, C.c_int, vp, vp, vp])
-    if hasattr(lib, 'pgl_prox_init_dev'):                     # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
-        lib.pgl_prox_state_doubles.argtypes = [C.c_int, C.c_int]
-        prox = [vp, vp, C.c_int, C.c_int, vp, vp] + [C.c_double] * 5 + [vp, C.c_double, C.c_int]
-        lib.pgl_prox_init_dev.argtypes = prox + [vp, vp]
-        lib.pgl_prox_step_dev.argtypes = prox + [C.c_int, vp, vp]
+    lib.pgl_hvp_prepare_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp]
+    lib.pgl_hvp_prepare_list_dev.argtypes = [vp, vp, C.c_int, vp, vp]
+    lib.pgl_hvp_apply_dev.argtypes = [vp, vp, vp]
+    lib.pgl_hvp.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    lib.pgl_hess_dev.argtypes = [vp, vp, C.c_int]
+    lib.pgl_hess.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
+    lib.pgl_chol_factor_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    lib.pgl_tri_inverse_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
+    lib.pgl_rescale_count.argtypes = [vp, vp]
+    lib.pgl_rescale_dev.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.pgl_rescale.argtypes = [vp, vp, vp, vp, vp]
+    # the lock-step methods; pr: const pgl_prior*
+    lib.pgl_bfgs_state_doubles.argtypes = [C.c_int, C.c_int]
+    lib.pgl_bfgs_init_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double]
+    lib.pgl_bfgs_trial_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp]
+    lib.pgl_bfgs_objective_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, pr]
+    lib.pgl_bfgs_linesearch_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int]
+    lib.pgl_bfgs_hmul_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int]
+    lib.pgl_bfgs_update_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, vp, vp, C.c_int]
+    lib.pgl_bfgs_hmul_hist_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp]
+    lib.pgl_bfgs_step_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, pr, C.c_int, C.c_double, C.c_int,
+                                      C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp]
+    lib.pgl_ncg_state_doubles.argtypes = [C.c_int, C.c_int]
+    lib.pgl_ncg_init_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, pr, C.c_int, vp, vp]
+    lib.pgl_ncg_cg_step_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, pr, vp, vp]
+    lib.pgl_ncg_trial_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp]
+    lib.pgl_ncg_search_step_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, pr, C.c_int, vp, vp, vp, vp]
+    lib.pgl_hmc_state_doubles.argtypes = [C.c_int, C.c_int]
+    lib.pgl_hmc_init_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, pr, C.c_double, C.c_uint64]
+    lib.pgl_hmc_begin_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
+    lib.pgl_hmc_leap_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, pr, C.c_int, C.c_int, vp, vp]
+    lib.pgl_tri_matvec_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.pgl_hmc_dense_begin_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
+    lib.pgl_hmc_dense_leap_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, pr, C.c_int, C.c_int, vp, vp]
+    lib.pgl_nuts_state_doubles.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.pgl_nuts_init_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, pr, vp, vp, vp, C.c_uint64,
+                                      C.c_int, C.c_int, C.c_int, vp]
+    lib.pgl_nuts_step_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, pr, vp, vp, C.c_double, C.c_int, C.c_int,
+                                      C.c_int, vp, vp, vp]
+    lib.pgl_adapt_state_doubles.argtypes = [C.c_int, C.c_int]
+    lib.pgl_mass_adapt_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
+    lib.pgl_nuts_adapt_step_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, pr, vp, vp, vp, C.c_double, C.c_int,
+                                            C.c_int, C.c_int, vp, vp, vp]
+    lib.pgl_ais_state_doubles.argtypes = [C.c_int, C.c_int]
+    kmp = [vp, vp, C.c_int, C.c_int, C.c_int]
+    lib.pgl_ais_init_dev.argtypes = kmp + [C.c_int, C.c_int, pr, C.c_double, C.c_uint64, vp]
+    lib.pgl_ais_start_dev.argtypes = kmp + [vp, vp, pr]
+    lib.pgl_ais_temper_dev.argtypes = kmp + [pr, C.c_double, vp]
+    lib.pgl_ais_begin_dev.argtypes = kmp + [vp, vp]
+    lib.pgl_ais_leap_dev.argtypes = kmp + [vp, vp, vp, pr, C.c_int, C.c_int, vp, vp, vp]
+    lib.pgl_tri_matvec_shared_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.pgl_ais_dense_begin_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.pgl_ais_dense_leap_dev.argtypes = kmp + [vp, vp, vp, pr, C.c_int, C.c_int, vp, vp, vp]
+    lib.pgl_prox_state_doubles.argtypes = [C.c_int, C.c_int]
+    prox = [vp, vp, C.c_int, C.c_int, vp, vp, pr, vp, C.c_double, C.c_int]
+    lib.pgl_prox_init_dev.argtypes = prox + [vp, vp]
+    lib.pgl_prox_step_dev.argtypes = prox + [C.c_int, vp, vp]
     lib.pgl_features.argtypes = [vp, vp]
     lib.pgl_impulse_currents.argtypes = [vp, vp, vp]
     lib.pgl_state.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
@@ -231,27 +236,22 @@ def load():
     lib.pgl_gibbs_currents.argtypes = [vp, C.c_int, vp]
     lib.pgl_last_timing.argtypes = [vp, dp, dp]
     lib.pgl_info.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int]
-    if hasattr(lib, 'pgl_plan_kernels'):
-        lib.pgl_plan_kernels.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int,
-                                         C.c_int, C.c_int, C.c_char_p, C.c_int]
-    if hasattr(lib, 'pgl_last_kernels'):
-        lib.pgl_last_kernels.argtypes = [vp, C.c_char_p, C.c_int]
+    lib.pgl_plan_kernels.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_int, C.c_int, C.c_char_p, C.c_int]
+    lib.pgl_last_kernels.argtypes = [vp, C.c_char_p, C.c_int]
     lib.pgl_simulate.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_double, vp, vp, vp,
                                  C.c_int64, C.c_uint64, vp, vp]
-    if hasattr(lib, 'pgl_simulate_batch'):                    # (older dev A/B builds named by PYGLM_HIP_LIB lack them)
-        lib.pgl_simulate_streams.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_double, vp, vp, C.c_int, C.c_uint64,
-                                             vp, vp, vp]
-        sim = [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_double, vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_int,
-               vp, vp, vp, vp]
-        lib.pgl_simulate_batch.argtypes = sim
-        lib.pgl_simulate_batch_dev.argtypes = sim + [vp, vp]
-        lib.pgl_simulate_batch_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
+    lib.pgl_simulate_streams.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_double, vp, vp, C.c_int, C.c_uint64,
+                                         vp, vp, vp]
+    sim = [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_double, vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_int,
+           vp, vp, vp, vp]
+    lib.pgl_simulate_batch.argtypes = sim
+    lib.pgl_simulate_batch_dev.argtypes = sim + [vp, vp]
+    lib.pgl_simulate_batch_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
     for name in SYMBOLS:
-        if 'PYGLM_HIP_LIB' in os.environ and not hasattr(lib, name):
-            continue
         fn = getattr(lib, name)
         if name in ('pgl_bfgs_state_doubles', 'pgl_ncg_state_doubles', 'pgl_hmc_state_doubles', 'pgl_ais_state_doubles',
-                    'pgl_hmc_dense_work_doubles', 'pgl_prox_state_doubles', 'pgl_nuts_state_doubles', 'pgl_adapt_state_doubles'):
+                    'pgl_prox_state_doubles', 'pgl_nuts_state_doubles', 'pgl_adapt_state_doubles'):
             fn.restype = C.c_longlong
         elif name not in ('pgl_last_error',):
             fn.restype = C.c_int
@@ -616,10 +616,10 @@ class DeviceGlm(object):
         _chk(self.lib.pgl_bfgs_trial_dev(self.h, C.c_void_p(d_state), int(M), int(P),
                                          C.c_void_p(d_rows) if d_rows else None, int(L), C.c_void_p(d_Xt)))
 
-    def bfgs_objective_dev(self, L, P, d_Xt, d_ll_f, d_grad_g, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam):
+    # prior, here and below: a Prior or the tuple of _Packing.prior_params() (as_prior)
+    def bfgs_objective_dev(self, L, P, d_Xt, d_ll_f, d_grad_g, prior):
         _chk(self.lib.pgl_bfgs_objective_dev(self.h, int(L), int(P), C.c_void_p(d_Xt), C.c_void_p(d_ll_f),
-                                             C.c_void_p(d_grad_g), int(prior_kind), float(mu_b), float(sg_b),
-                                             float(stim_sigma), float(mu), float(sigma), float(lam)))
+                                             C.c_void_p(d_grad_g), C.byref(as_prior(prior))))
 
     def bfgs_init_dev(self, d_state, M, P, gtol):
         _chk(self.lib.pgl_bfgs_init_dev(self.h, C.c_void_p(d_state), int(M), int(P), float(gtol)))
@@ -646,28 +646,27 @@ class DeviceGlm(object):
     def bfgs_step_dev(self, d_state, M, P, d_rows, L, d_Xt, d_f, d_g, prior=None, max_trials=100, gtol=1e-5, maxiter=225,
                       init_scaling=False, d_hist=0, d_coef=0, Kmax=0, d_ab=0, hk_bound=0, d_H=0, ld=0, d_pos_next=0,
                       d_Xt_next=0, flags_out=0):
-        """One whole optimiser iteration behind an evaluation (pgl_bfgs_step_dev).  prior: the tuple of
-        bfgs_objective_dev's prior arguments, or None when d_f / d_g already hold the objective and its gradient."""
+        """One whole optimiser iteration behind an evaluation (pgl_bfgs_step_dev).  prior: as for bfgs_objective_dev, or
+        None when d_f / d_g already hold the objective and its gradient."""
         vp = lambda a: C.c_void_p(a) if a else None
         pr = (-1, 0.0, 1.0, 1.0, 0.0, 1.0, 0.0) if prior is None else prior
         _chk(self.lib.pgl_bfgs_step_dev(self.h, C.c_void_p(d_state), int(M), int(P), vp(d_rows), int(L), C.c_void_p(d_Xt),
-                                        C.c_void_p(d_f), C.c_void_p(d_g), int(pr[0]), *[float(z) for z in pr[1:]],
-                                        int(max_trials), float(gtol), int(maxiter), 1 if init_scaling else 0, vp(d_hist),
+                                        C.c_void_p(d_f), C.c_void_p(d_g), C.byref(as_prior(pr)), int(max_trials), float(gtol), int(maxiter), 1 if init_scaling else 0, vp(d_hist),
                                         vp(d_coef), int(Kmax), vp(d_ab), int(hk_bound), vp(d_H), int(ld), vp(d_pos_next),
                                         vp(d_Xt_next), vp(flags_out)))
 
-    # -- lock-step Newton-CG row kernels (pgl_ncg_*; inference/batched_newton_cg.py).  prior: bfgs_objective_dev's tuple
+    # -- lock-step Newton-CG row kernels (pgl_ncg_*; inference/batched_newton_cg.py)
     def ncg_state_doubles(self, M, P):
         return int(self.lib.pgl_ncg_state_doubles(int(M), int(P)))
 
     def ncg_init_dev(self, d_state, M, P, d_ll, d_grad, prior, maxiter, d_V, flags_out=0):
         _chk(self.lib.pgl_ncg_init_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_ll), C.c_void_p(d_grad),
-                                       int(prior[0]), *[float(z) for z in prior[1:]], int(maxiter), C.c_void_p(d_V),
+                                       C.byref(as_prior(prior)), int(maxiter), C.c_void_p(d_V),
                                        C.c_void_p(flags_out) if flags_out else None))
 
     def ncg_cg_step_dev(self, d_state, M, P, d_hv, prior, d_V, flags_out=0):
-        _chk(self.lib.pgl_ncg_cg_step_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_hv), int(prior[0]),
-                                          *[float(z) for z in prior[1:]], C.c_void_p(d_V),
+        _chk(self.lib.pgl_ncg_cg_step_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_hv),
+                                          C.byref(as_prior(prior)), C.c_void_p(d_V),
                                           C.c_void_p(flags_out) if flags_out else None))
 
     def ncg_trial_dev(self, d_state, M, P, d_rows, L, d_Xt):
@@ -678,17 +677,17 @@ class DeviceGlm(object):
                             flags_out=0):
         vp = lambda a: C.c_void_p(a) if a else None
         _chk(self.lib.pgl_ncg_search_step_dev(self.h, C.c_void_p(d_state), int(M), int(P), vp(d_rows), int(L),
-                                              C.c_void_p(d_Xt), C.c_void_p(d_f), C.c_void_p(d_g), int(prior[0]),
-                                              *[float(z) for z in prior[1:]], int(maxiter), vp(d_pos_next), vp(d_Xt_next),
-                                              C.c_void_p(d_V), vp(flags_out)))
+                                              C.c_void_p(d_Xt), C.c_void_p(d_f), C.c_void_p(d_g), C.byref(as_prior(prior)),
+                                              int(maxiter), vp(d_pos_next), vp(d_Xt_next), C.c_void_p(d_V), vp(flags_out)))
 
-    # -- lock-step HMC row kernels (pgl_hmc_*; inference/batched_hmc.py).  prior: bfgs_objective_dev's tuple; device pointers
+    # -- lock-step HMC row kernels (pgl_hmc_*; inference/batched_hmc.py); device pointers.  n_chains = C: the run has R = C M
+    # rows, chain c of neuron n_lo + m is row c M + m, and every call after init takes R as its M
     def hmc_state_doubles(self, M, P):
         return int(self.lib.pgl_hmc_state_doubles(int(M), int(P)))
 
-    def hmc_init_dev(self, d_state, M, P, n_lo, d_ll, d_grad, prior, step0, seed):
-        _chk(self.lib.pgl_hmc_init_dev(self.h, C.c_void_p(d_state), int(M), int(P), int(n_lo), C.c_void_p(d_ll),
-                                       C.c_void_p(d_grad), int(prior[0]), *[float(z) for z in prior[1:]], float(step0),
+    def hmc_init_dev(self, d_state, M, P, n_lo, d_ll, d_grad, prior, step0, seed, n_chains=1):
+        _chk(self.lib.pgl_hmc_init_dev(self.h, C.c_void_p(d_state), int(M), int(n_chains), int(P), int(n_lo),
+                                       C.c_void_p(d_ll), C.c_void_p(d_grad), C.byref(as_prior(prior)), float(step0),
                                        int(seed) & 0xffffffffffffffff))
 
     def hmc_begin_dev(self, d_state, M, P, d_minv, d_Xt):
@@ -697,18 +696,19 @@ class DeviceGlm(object):
 
     def hmc_leap_dev(self, d_state, M, P, d_minv, d_ll, d_grad, prior, last, n_warmup, d_Xt, d_sample_out=0):
         _chk(self.lib.pgl_hmc_leap_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_minv) if d_minv else None,
-                                       C.c_void_p(d_ll), C.c_void_p(d_grad), int(prior[0]), *[float(z) for z in prior[1:]],
+                                       C.c_void_p(d_ll), C.c_void_p(d_grad), C.byref(as_prior(prior)),
                                        1 if last else 0, int(n_warmup), C.c_void_p(d_Xt),
                                        C.c_void_p(d_sample_out) if d_sample_out else None))
 
-    # -- NUTS row kernels (pgl_nuts_*; inference/batched_nuts.py).  d_minv (M, P) or d_W (M, P, P) or neither; device pointers
+    # -- NUTS row kernels (pgl_nuts_*; inference/batched_nuts.py).  d_minv (M, P) or d_W (M, P, P) or neither; device pointers;
+    # n_chains as for hmc_init_dev (d_minv, d_W: one per row)
     def nuts_state_doubles(self, M, P, max_depth):
         return int(self.lib.pgl_nuts_state_doubles(int(M), int(P), int(max_depth)))
 
     def nuts_init_dev(self, d_state, M, P, max_depth, n_lo, d_ll, d_grad, prior, d_minv, d_W, d_step0, seed, n_warmup, thin,
-                      n_keep, d_Xt):
-        _chk(self.lib.pgl_nuts_init_dev(self.h, C.c_void_p(d_state), int(M), int(P), int(max_depth), int(n_lo),
-                                        C.c_void_p(d_ll), C.c_void_p(d_grad), int(prior[0]), *[float(z) for z in prior[1:]],
+                      n_keep, d_Xt, n_chains=1):
+        _chk(self.lib.pgl_nuts_init_dev(self.h, C.c_void_p(d_state), int(M), int(n_chains), int(P), int(max_depth), int(n_lo),
+                                        C.c_void_p(d_ll), C.c_void_p(d_grad), C.byref(as_prior(prior)),
                                         C.c_void_p(d_minv) if d_minv else None, C.c_void_p(d_W) if d_W else None,
                                         C.c_void_p(d_step0), int(seed) & 0xffffffffffffffff, int(n_warmup), int(thin),
                                         int(n_keep), C.c_void_p(d_Xt)))
@@ -716,28 +716,14 @@ class DeviceGlm(object):
     def nuts_step_dev(self, d_state, M, P, max_depth, d_ll, d_grad, prior, d_minv, d_W, target_accept, n_warmup, thin, n_keep,
                       d_Xt, d_samples=0, d_stats=0):
         _chk(self.lib.pgl_nuts_step_dev(self.h, C.c_void_p(d_state), int(M), int(P), int(max_depth), C.c_void_p(d_ll),
-                                        C.c_void_p(d_grad), int(prior[0]), *[float(z) for z in prior[1:]],
+                                        C.c_void_p(d_grad), C.byref(as_prior(prior)),
                                         C.c_void_p(d_minv) if d_minv else None, C.c_void_p(d_W) if d_W else None,
                                         float(target_accept), int(n_warmup), int(thin), int(n_keep), C.c_void_p(d_Xt),
                                         C.c_void_p(d_samples) if d_samples else None,
                                         C.c_void_p(d_stats) if d_stats else None))
 
-    # -- several chains per neuron and the warm-up mass adaptation (csrc/pglm_adapt.h).  Rows: R = C M, chain c of neuron
-    # n_lo + m is row c M + m; d_adapt: adapt_state_doubles(R, P) zeroed doubles; d_sched: mass_adapt.schedule_ints on the device
-    def hmc_init_chains_dev(self, d_state, M, n_chains, P, n_lo, d_ll, d_grad, prior, step0, seed):
-        _chk(self.lib.pgl_hmc_init_chains_dev(self.h, C.c_void_p(d_state), int(M), int(n_chains), int(P), int(n_lo),
-                                              C.c_void_p(d_ll), C.c_void_p(d_grad), int(prior[0]),
-                                              *[float(z) for z in prior[1:]], float(step0), int(seed) & 0xffffffffffffffff))
-
-    def nuts_init_chains_dev(self, d_state, M, n_chains, P, max_depth, n_lo, d_ll, d_grad, prior, d_minv, d_W, d_step0, seed,
-                             n_warmup, thin, n_keep, d_Xt):
-        _chk(self.lib.pgl_nuts_init_chains_dev(self.h, C.c_void_p(d_state), int(M), int(n_chains), int(P), int(max_depth),
-                                               int(n_lo), C.c_void_p(d_ll), C.c_void_p(d_grad), int(prior[0]),
-                                               *[float(z) for z in prior[1:]], C.c_void_p(d_minv) if d_minv else None,
-                                               C.c_void_p(d_W) if d_W else None, C.c_void_p(d_step0),
-                                               int(seed) & 0xffffffffffffffff, int(n_warmup), int(thin), int(n_keep),
-                                               C.c_void_p(d_Xt)))
-
+    # -- the warm-up mass adaptation (csrc/pglm_adapt.h) over the R rows of a run; d_adapt: adapt_state_doubles(R, P) zeroed
+    # doubles; d_sched: mass_adapt.schedule_ints on the device
     def adapt_state_doubles(self, R, P):
         return int(self.lib.pgl_adapt_state_doubles(int(R), int(P)))
 
@@ -748,64 +734,58 @@ class DeviceGlm(object):
     def nuts_adapt_step_dev(self, d_state, R, P, max_depth, d_ll, d_grad, prior, d_minv, d_adapt, d_sched, target_accept,
                             n_warmup, thin, n_keep, d_Xt, d_samples=0, d_stats=0):
         _chk(self.lib.pgl_nuts_adapt_step_dev(self.h, C.c_void_p(d_state), int(R), int(P), int(max_depth), C.c_void_p(d_ll),
-                                              C.c_void_p(d_grad), int(prior[0]), *[float(z) for z in prior[1:]],
+                                              C.c_void_p(d_grad), C.byref(as_prior(prior)),
                                               C.c_void_p(d_minv), C.c_void_p(d_adapt), C.c_void_p(d_sched),
                                               float(target_accept), int(n_warmup), int(thin), int(n_keep), C.c_void_p(d_Xt),
                                               C.c_void_p(d_samples) if d_samples else None,
                                               C.c_void_p(d_stats) if d_stats else None))
 
     # -- the same chain with a dense mass matrix (pgl_hmc_dense_*): d_W (M, P, P) lower-triangular factors of the inverse
-    # mass matrices; d_work: hmc_dense_work_doubles(M, P) doubles (0: none)
-    def hmc_dense_work_doubles(self, M, P):
-        return int(self.lib.pgl_hmc_dense_work_doubles(int(M), int(P)))
-
+    # mass matrices
     def tri_matvec_dev(self, d_W, M, P, trans, d_x, d_y):
         _chk(self.lib.pgl_tri_matvec_dev(self.h, C.c_void_p(d_W), int(M), int(P), 1 if trans else 0, C.c_void_p(d_x),
                                          C.c_void_p(d_y)))
 
-    def hmc_dense_begin_dev(self, d_state, M, P, d_W, d_work, d_Xt):
-        _chk(self.lib.pgl_hmc_dense_begin_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_W),
-                                              C.c_void_p(d_work) if d_work else None, C.c_void_p(d_Xt)))
+    def hmc_dense_begin_dev(self, d_state, M, P, d_W, d_Xt):
+        _chk(self.lib.pgl_hmc_dense_begin_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_W), C.c_void_p(d_Xt)))
 
-    def hmc_dense_leap_dev(self, d_state, M, P, d_W, d_work, d_ll, d_grad, prior, last, n_warmup, d_Xt, d_sample_out=0):
-        _chk(self.lib.pgl_hmc_dense_leap_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_W),
-                                             C.c_void_p(d_work) if d_work else None, C.c_void_p(d_ll), C.c_void_p(d_grad),
-                                             int(prior[0]), *[float(z) for z in prior[1:]], 1 if last else 0, int(n_warmup),
+    def hmc_dense_leap_dev(self, d_state, M, P, d_W, d_ll, d_grad, prior, last, n_warmup, d_Xt, d_sample_out=0):
+        _chk(self.lib.pgl_hmc_dense_leap_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_W), C.c_void_p(d_ll),
+                                             C.c_void_p(d_grad), C.byref(as_prior(prior)), 1 if last else 0, int(n_warmup),
                                              C.c_void_p(d_Xt), C.c_void_p(d_sample_out) if d_sample_out else None))
 
     # -- lock-step proximal gradient row kernels for the group-lasso MAP (pgl_prox_*; inference/batched_prox.py).  prior:
-    # (mu_b, sg_b, stim_sigma, mu, sigma); d_lam: (M) device, one lam per row; flags_out: pinned host memory or 0
+    # kind 1, its lam unused (_prox_prior); d_lam: (M) device, one lam per row; flags_out: pinned host memory or 0
     def prox_state_doubles(self, M, P):
         return int(self.lib.pgl_prox_state_doubles(int(M), int(P)))
 
     def prox_init_dev(self, d_state, M, P, d_ll, d_grad, prior, d_lam, gtol, maxiter, d_Xt, flags_out=0):
         _chk(self.lib.pgl_prox_init_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_ll), C.c_void_p(d_grad),
-                                        *[float(z) for z in prior], C.c_void_p(d_lam), float(gtol), int(maxiter),
+                                        C.byref(_prox_prior(prior)), C.c_void_p(d_lam), float(gtol), int(maxiter),
                                         C.c_void_p(d_Xt), C.c_void_p(flags_out) if flags_out else None))
 
     def prox_step_dev(self, d_state, M, P, d_ll, d_grad, prior, d_lam, gtol, maxiter, max_backtrack, d_Xt, flags_out=0):
         _chk(self.lib.pgl_prox_step_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_ll), C.c_void_p(d_grad),
-                                        *[float(z) for z in prior], C.c_void_p(d_lam), float(gtol), int(maxiter),
+                                        C.byref(_prox_prior(prior)), C.c_void_p(d_lam), float(gtol), int(maxiter),
                                         int(max_backtrack), C.c_void_p(d_Xt), C.c_void_p(flags_out) if flags_out else None))
 
     # -- annealed importance sampling row kernels (pgl_ais_*; inference/batched_ais.py).  K particles x M neurons, rows
-    # particle-major; prior: bfgs_objective_dev's tuple (Gaussian only); device pointers
+    # particle-major; prior: Gaussian only; device pointers
     def ais_state_doubles(self, R, P):
         return int(self.lib.pgl_ais_state_doubles(int(R), int(P)))
 
     def ais_init_dev(self, d_state, K, M, P, n_lo, particle0, prior, step0, seed, d_Xt):
         _chk(self.lib.pgl_ais_init_dev(self.h, C.c_void_p(d_state), int(K), int(M), int(P), int(n_lo), int(particle0),
-                                       int(prior[0]), *[float(z) for z in prior[1:]], float(step0),
-                                       int(seed) & 0xffffffffffffffff, C.c_void_p(d_Xt)))
+                                       C.byref(as_prior(prior)), float(step0), int(seed) & 0xffffffffffffffff,
+                                       C.c_void_p(d_Xt)))
 
     def ais_start_dev(self, d_state, K, M, P, d_ll, d_grad, prior):
         _chk(self.lib.pgl_ais_start_dev(self.h, C.c_void_p(d_state), int(K), int(M), int(P), C.c_void_p(d_ll),
-                                        C.c_void_p(d_grad), int(prior[0]), *[float(z) for z in prior[1:]]))
+                                        C.c_void_p(d_grad), C.byref(as_prior(prior))))
 
     def ais_temper_dev(self, d_state, K, M, P, prior, beta, d_step_row=0):
-        _chk(self.lib.pgl_ais_temper_dev(self.h, C.c_void_p(d_state), int(K), int(M), int(P), int(prior[0]),
-                                         *[float(z) for z in prior[1:]], float(beta),
-                                         C.c_void_p(d_step_row) if d_step_row else None))
+        _chk(self.lib.pgl_ais_temper_dev(self.h, C.c_void_p(d_state), int(K), int(M), int(P), C.byref(as_prior(prior)),
+                                         float(beta), C.c_void_p(d_step_row) if d_step_row else None))
 
     def ais_begin_dev(self, d_state, K, M, P, d_minv, d_Xt):
         _chk(self.lib.pgl_ais_begin_dev(self.h, C.c_void_p(d_state), int(K), int(M), int(P),
@@ -814,8 +794,8 @@ class DeviceGlm(object):
     def ais_leap_dev(self, d_state, K, M, P, d_minv, d_ll, d_grad, prior, last, adapt, d_Xt, d_acc_out=0, d_step_out=0):
         vp = lambda a: C.c_void_p(a) if a else None
         _chk(self.lib.pgl_ais_leap_dev(self.h, C.c_void_p(d_state), int(K), int(M), int(P), vp(d_minv), C.c_void_p(d_ll),
-                                       C.c_void_p(d_grad), int(prior[0]), *[float(z) for z in prior[1:]], 1 if last else 0,
-                                       1 if adapt else 0, C.c_void_p(d_Xt), vp(d_acc_out), vp(d_step_out)))
+                                       C.c_void_p(d_grad), C.byref(as_prior(prior)), 1 if last else 0, 1 if adapt else 0,
+                                       C.c_void_p(d_Xt), vp(d_acc_out), vp(d_step_out)))
 
     # -- the same run with a dense mass matrix (pgl_ais_dense_*): d_W (M, P, P) lower-triangular factors of the inverse mass
     # matrices, one per NEURON, shared by its K particles; d_x, d_y (K M, P) particle-major
@@ -830,9 +810,9 @@ class DeviceGlm(object):
     def ais_dense_leap_dev(self, d_state, K, M, P, d_W, d_ll, d_grad, prior, last, adapt, d_Xt, d_acc_out=0, d_step_out=0):
         vp = lambda a: C.c_void_p(a) if a else None
         _chk(self.lib.pgl_ais_dense_leap_dev(self.h, C.c_void_p(d_state), int(K), int(M), int(P), C.c_void_p(d_W),
-                                             C.c_void_p(d_ll), C.c_void_p(d_grad), int(prior[0]),
-                                             *[float(z) for z in prior[1:]], 1 if last else 0, 1 if adapt else 0,
-                                             C.c_void_p(d_Xt), vp(d_acc_out), vp(d_step_out)))
+                                             C.c_void_p(d_ll), C.c_void_p(d_grad), C.byref(as_prior(prior)),
+                                             1 if last else 0, 1 if adapt else 0, C.c_void_p(d_Xt), vp(d_acc_out),
+                                             vp(d_step_out)))
 
     def sync(self):
         _chk(self.lib.pgl_sync(self.h))

@@ -230,10 +230,19 @@ static int sim_launch(const SimParams& sp, int n_rep, int threads, size_t lds, h
     return PGL_OK;
 }
 
+// one workgroup of 256 threads per row on the handle's stream: the launch shape of every row kernel of the lock-step methods
+template <typename... Params, typename... Args>
+static int launch_rows(pgl_handle h, void (*kernel)(Params...), int rows, Args&&... args)
+{
+    hipLaunchKernelGGL(kernel, dim3(rows), dim3(256), 0, h->stream, static_cast<Params>(args)...);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
 extern "C" {
 
 const char* pgl_last_error(void) { return g_err.c_str(); }
-int pgl_version(void) { return 106; }
+int pgl_version(void) { return PGL_ABI_VERSION; }
 
 int pgl_device_count(void)
 {
@@ -1756,736 +1765,8 @@ int pgl_hess(pgl_handle h, int n_lo, int n_hi, const double* theta, const double
     return PGL_OK;
 }
 
-// ---- lock-step BFGS bookkeeping kernels (inference/batched_bfgs.py) ----------------------------------------------
-long long pgl_bfgs_state_doubles(int M, int P) { return (long long)pgl_bfgs_doubles(M, P); }
-
-int pgl_bfgs_trial_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, double* d_Xt)
-{
-    if (!h || !d_state || !d_Xt || M <= 0 || P <= 0 || L <= 0 || L > M) return fail(PGL_ERR_ARG, "bad argument");
-    HIPCHK(hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_bfgs_trial, dim3(L), dim3(256), 0, h->stream, pgl_bfgs_view(d_state, M, P), d_rows, d_Xt);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-int pgl_bfgs_objective_dev(pgl_handle h, int L, int P, const double* d_Xt, double* d_ll_f, double* d_grad_g,
-                           int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma,
-                           double lam)
-{
-    if (!h || !d_Xt || !d_ll_f || !d_grad_g || L <= 0) return fail(PGL_ERR_ARG, "bad argument");
-    // (separable stimulus: the stimulus block of a row is [w_t, w_x], both under N(0, stim_sigma) -- bkgd.py:223-224 with mu = 0)
-    if (P != 1 + h->Dstim + h->Kimp) return fail(PGL_ERR_ARG, "rows must be theta rows [bias, w_stim, w_ir]");
-    if (prior_kind != 0 && prior_kind != 1) return fail(PGL_ERR_ARG, "prior kind: 0 Gaussian, 1 group lasso");
-    HIPCHK(hipSetDevice(h->device));
-    BfgsPrior q;
-    q.N = h->N; q.B = h->B; q.Dstim = h->Dstim; q.kind = prior_kind;
-    q.mu_b = mu_b; q.sg_b = sg_b; q.stim_sigma = stim_sigma; q.mu = mu; q.sigma = sigma; q.lam = lam;
-    hipLaunchKernelGGL(k_bfgs_objective, dim3(L), dim3(256), 0, h->stream, P, d_Xt, d_ll_f, d_grad_g, q);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-int pgl_bfgs_init_dev(pgl_handle h, double* d_state, int M, int P, double gtol)
-{
-    if (!h || !d_state || M <= 0 || P <= 0) return fail(PGL_ERR_ARG, "bad argument");
-    HIPCHK(hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_bfgs_init, dim3(M), dim3(256), 0, h->stream, pgl_bfgs_view(d_state, M, P), gtol);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-static BfgsStepArgs bfgs_step_args(int phases)
-{
-    BfgsStepArgs a;
-    memset(&a, 0, sizeof(a));
-    a.phases = phases;
-    a.max_trials = 100;
-    return a;
-}
-
-int pgl_bfgs_linesearch_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, const double* d_Xt,
-                            const double* d_f, const double* d_g, int max_trials)
-{
-    if (!h || !d_state || !d_Xt || !d_f || !d_g || M <= 0 || P <= 0 || L <= 0 || L > M || max_trials <= 0)
-        return fail(PGL_ERR_ARG, "bad argument");
-    HIPCHK(hipSetDevice(h->device));
-    BfgsStepArgs a = bfgs_step_args(PGL_STEP_LS);            // f, g arrive final: no prior phase
-    a.rows = d_rows; a.Xt = d_Xt; a.ft = const_cast<double*>(d_f); a.gt = const_cast<double*>(d_g);
-    a.max_trials = max_trials;
-    hipLaunchKernelGGL(k_bfgs_step<256>, dim3(L), dim3(256), 0, h->stream, pgl_bfgs_view(d_state, M, P), a);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-int pgl_bfgs_hmul_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, double* d_H, int ld)
-{
-    if (!h || !d_state || !d_H || M <= 0 || P <= 0 || L <= 0 || L > M) return fail(PGL_ERR_ARG, "bad argument");
-    if (ld < P || (ld & 1) || (reinterpret_cast<uintptr_t>(d_H) & 15))
-        return fail(PGL_ERR_ARG, "H: leading dimension even and >= P, base 16-byte aligned");
-    HIPCHK(hipSetDevice(h->device));
-    const unsigned bx = (unsigned)((P + 4 * PGL_HM_ROWS - 1) / (4 * PGL_HM_ROWS));
-    hipLaunchKernelGGL(k_bfgs_hmul, dim3(bx, (unsigned)L), dim3(256), 0, h->stream, pgl_bfgs_view(d_state, M, P), d_rows,
-                       d_H, ld);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-int pgl_bfgs_hmul_hist_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, const double* d_hist,
-                           const double* d_coef, int Kmax, double* d_ab)
-{
-    if (!h || !d_state || !d_hist || !d_coef || !d_ab || M <= 0 || P <= 0 || L <= 0 || L > M || Kmax <= 0)
-        return fail(PGL_ERR_ARG, "bad argument");
-    HIPCHK(hipSetDevice(h->device));
-    const BfgsView v = pgl_bfgs_view(d_state, M, P);
-    hipLaunchKernelGGL(k_bfgs_hdots, dim3((unsigned)((Kmax + 3) / 4), (unsigned)L), dim3(256), 0, h->stream, v, d_rows, d_hist,
-                       d_coef, Kmax, d_ab);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_bfgs_hcomb, dim3((unsigned)((P + 63) / 64), (unsigned)L), dim3(512), 0, h->stream, v, d_rows, d_hist, Kmax,
-                       (const double*)d_ab);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-int pgl_bfgs_update_dev(pgl_handle h, double* d_state, int M, int P, double gtol, int maxiter, int init_scaling, double* d_hist,
-                        double* d_coef, int Kmax)
-{
-    if (!h || !d_state || M <= 0 || P <= 0) return fail(PGL_ERR_ARG, "bad argument");
-    if ((d_hist != nullptr) != (d_coef != nullptr) || (d_hist && Kmax < maxiter))
-        return fail(PGL_ERR_ARG, "history buffers: both or none, room for maxiter updates");
-    HIPCHK(hipSetDevice(h->device));
-    BfgsStepArgs a = bfgs_step_args(PGL_STEP_UPDATE);        // every row of the shard, no trial points
-    a.gtol = gtol; a.maxiter = maxiter; a.init_scaling = init_scaling; a.Wh = d_hist; a.cs = d_coef; a.Kmax = Kmax;
-    hipLaunchKernelGGL(k_bfgs_step<256>, dim3(M), dim3(256), 0, h->stream, pgl_bfgs_view(d_state, M, P), a);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-// the address the device uses for a buffer of pinned host memory that a row kernel writes its flags into (looked up once)
-static int flags_device_pointer(pgl_handle h, double* flags_out, double** flags_dev)
-{
-    for (int i = 0; i < 4; ++i)
-        if (h->flags_host[i] == flags_out) {
-            *flags_dev = h->flags_dev[i];
-            return PGL_OK;
-        }
-    void* dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, flags_out, 0) != hipSuccess || !dp) {
-        (void)hipGetLastError();
-        return fail(PGL_ERR_ARG, "flags_out must be pinned (page-locked, device-mapped) host memory");
-    }
-    *flags_dev = (double*)dp;
-    h->flags_host[h->flags_next] = flags_out;
-    h->flags_dev[h->flags_next] = *flags_dev;
-    h->flags_next = (h->flags_next + 1) & 3;
-    return PGL_OK;
-}
-
-// One whole iteration behind an evaluation (see k_bfgs_step): in ONE launch while the update history of a row is short
-// (hk_bound * P numbers, PGL_OPT_BFGS_MERGE), else as line search | k_bfgs_hdots | k_bfgs_hcomb | update (dense inverse
-// Hessians: line search | k_bfgs_hmul | update).
-int pgl_bfgs_step_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, const double* d_Xt, double* d_ll_f,
-                      double* d_grad_g, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma,
-                      double lam, int max_trials, double gtol, int maxiter, int init_scaling, double* d_hist, double* d_coef,
-                      int Kmax, double* d_ab, int hk_bound, double* d_H, int ld, const int* d_pos_next, double* d_Xt_next,
-                      double* flags_out)
-{
-    if (!h || !d_state || !d_Xt || !d_ll_f || !d_grad_g || M <= 0 || P <= 0 || L <= 0 || L > M || max_trials <= 0)
-        return fail(PGL_ERR_ARG, "bad argument");
-    if (prior_kind > 1) return fail(PGL_ERR_ARG, "prior kind: 0 Gaussian, 1 group lasso, < 0: f and g arrive final");
-    if (prior_kind >= 0 && P != 1 + h->Dstim + h->Kimp) return fail(PGL_ERR_ARG, "rows must be theta rows [bias, w_stim, w_ir]");
-    if ((d_hist != nullptr) != (d_coef != nullptr) || (d_hist && (Kmax < maxiter || !d_ab)))
-        return fail(PGL_ERR_ARG, "history buffers: all or none, room for maxiter updates");
-    if ((d_hist != nullptr) == (d_H != nullptr)) return fail(PGL_ERR_ARG, "either the update history or dense inverse Hessians");
-    if (d_H && (ld < P || (ld & 1) || (reinterpret_cast<uintptr_t>(d_H) & 15)))
-        return fail(PGL_ERR_ARG, "H: leading dimension even and >= P, base 16-byte aligned");
-    HIPCHK(hipSetDevice(h->device));
-    double* flags_dev = nullptr;
-    if (flags_out && flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
-    const BfgsView v = pgl_bfgs_view(d_state, M, P);
-    BfgsStepArgs a = bfgs_step_args(0);
-    a.rows = d_rows; a.Xt = d_Xt; a.ft = d_ll_f; a.gt = d_grad_g;
-    a.have_prior = prior_kind >= 0 ? 1 : 0;
-    a.q.N = h->N; a.q.B = h->B; a.q.Dstim = h->Dstim; a.q.kind = prior_kind;
-    a.q.mu_b = mu_b; a.q.sg_b = sg_b; a.q.stim_sigma = stim_sigma; a.q.mu = mu; a.q.sigma = sigma; a.q.lam = lam;
-    a.max_trials = max_trials; a.gtol = gtol; a.maxiter = maxiter; a.init_scaling = init_scaling;
-    a.Wh = d_hist; a.cs = d_coef; a.Kmax = Kmax; a.ab = d_ab;
-    a.pos_next = d_pos_next; a.Xt_next = d_Xt_next; a.flags_out = flags_dev;
-    const bool merged = d_hist && (long long)std::max(hk_bound, 0) * P <= (long long)h->opt_bfgs_merge;
-    if (merged) {
-        a.phases = PGL_STEP_LS | PGL_STEP_HIST | PGL_STEP_UPDATE;
-        hipLaunchKernelGGL(k_bfgs_step<1024>, dim3(L), dim3(1024), 0, h->stream, v, a);
-        HIPCHK(hipGetLastError());
-        return PGL_OK;
-    }
-    a.phases = PGL_STEP_LS;
-    hipLaunchKernelGGL(k_bfgs_step<256>, dim3(L), dim3(256), 0, h->stream, v, a);
-    HIPCHK(hipGetLastError());
-    if (d_hist) {
-        const int Kb = std::min(Kmax, std::max(hk_bound, 1));       // no row holds more than hk_bound updates
-        hipLaunchKernelGGL(k_bfgs_hdots, dim3((unsigned)((Kb + 3) / 4), (unsigned)L), dim3(256), 0, h->stream, v, d_rows,
-                           (const double*)d_hist, (const double*)d_coef, Kmax, d_ab);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_bfgs_hcomb, dim3((unsigned)((P + 63) / 64), (unsigned)L), dim3(512), 0, h->stream, v, d_rows,
-                           (const double*)d_hist, Kmax, (const double*)d_ab);
-        HIPCHK(hipGetLastError());
-    } else {
-        const unsigned bx = (unsigned)((P + 4 * PGL_HM_ROWS - 1) / (4 * PGL_HM_ROWS));
-        hipLaunchKernelGGL(k_bfgs_hmul, dim3(bx, (unsigned)L), dim3(256), 0, h->stream, v, d_rows, d_H, ld);
-        HIPCHK(hipGetLastError());
-    }
-    a.phases = PGL_STEP_UPDATE;
-    hipLaunchKernelGGL(k_bfgs_step<256>, dim3(L), dim3(256), 0, h->stream, v, a);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-// ---- lock-step Newton-CG row kernels (inference/batched_newton_cg.py) --------------------------------------------------
-long long pgl_ncg_state_doubles(int M, int P) { return (long long)pgl_ncg_doubles(M, P); }
-
-static int ncg_prior(pgl_handle h, int P, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma,
-                     double lam, BfgsPrior& q)
-{
-    if (P != 1 + h->Dstim + h->Kimp) return fail(PGL_ERR_ARG, "rows must be theta rows [bias, w_stim, w_ir]");
-    if (prior_kind != 0 && prior_kind != 1) return fail(PGL_ERR_ARG, "prior kind: 0 Gaussian, 1 group lasso");
-    if (h->B > PGL_MAXB) return fail(PGL_ERR_UNSUPPORTED, "impulse basis too wide for the row kernels");
-    q.N = h->N; q.B = h->B; q.Dstim = h->Dstim; q.kind = prior_kind;
-    q.mu_b = mu_b; q.sg_b = sg_b; q.stim_sigma = stim_sigma; q.mu = mu; q.sigma = sigma; q.lam = lam;
-    return PGL_OK;
-}
-
-int pgl_ncg_init_dev(pgl_handle h, double* d_state, int M, int P, double* d_ll, double* d_grad, int prior_kind, double mu_b,
-                     double sg_b, double stim_sigma, double mu, double sigma, double lam, int maxiter, double* d_V,
-                     double* flags_out)
-{
-    if (!h || !d_state || !d_ll || !d_grad || !d_V || M <= 0 || P <= 0) return fail(PGL_ERR_ARG, "bad argument");
-    BfgsPrior q;
-    int rc = ncg_prior(h, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    double* flags_dev = nullptr;
-    if (flags_out && flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
-    hipLaunchKernelGGL(k_ncg_init, dim3(M), dim3(256), 0, h->stream, pgl_ncg_view(d_state, M, P), d_ll, d_grad, q, maxiter, d_V,
-                       flags_dev);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-int pgl_ncg_cg_step_dev(pgl_handle h, double* d_state, int M, int P, double* d_hv, int prior_kind, double mu_b, double sg_b,
-                        double stim_sigma, double mu, double sigma, double lam, double* d_V, double* flags_out)
-{
-    if (!h || !d_state || !d_hv || !d_V || M <= 0 || P <= 0) return fail(PGL_ERR_ARG, "bad argument");
-    BfgsPrior q;
-    int rc = ncg_prior(h, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    double* flags_dev = nullptr;
-    if (flags_out && flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
-    hipLaunchKernelGGL(k_ncg_cg_step, dim3(M), dim3(256), 0, h->stream, pgl_ncg_view(d_state, M, P), d_hv, q, d_V, flags_dev);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-int pgl_ncg_trial_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, double* d_Xt)
-{
-    if (!h || !d_state || !d_Xt || M <= 0 || P <= 0 || L <= 0 || L > M) return fail(PGL_ERR_ARG, "bad argument");
-    HIPCHK(hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_ncg_trial, dim3(L), dim3(256), 0, h->stream, pgl_ncg_view(d_state, M, P), d_rows, d_Xt);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-int pgl_ncg_search_step_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, const double* d_Xt,
-                            double* d_ll_f, double* d_grad_g, int prior_kind, double mu_b, double sg_b, double stim_sigma,
-                            double mu, double sigma, double lam, int maxiter, const int* d_pos_next, double* d_Xt_next,
-                            double* d_V, double* flags_out)
-{
-    if (!h || !d_state || !d_Xt || !d_ll_f || !d_grad_g || !d_V || M <= 0 || P <= 0 || L <= 0 || L > M)
-        return fail(PGL_ERR_ARG, "bad argument");
-    if (d_Xt_next == d_Xt) return fail(PGL_ERR_ARG, "the next trial points need a buffer of their own");
-    NcgSearchArgs a;
-    memset(&a, 0, sizeof(a));
-    int rc = ncg_prior(h, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, a.q);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    double* flags_dev = nullptr;
-    if (flags_out && flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
-    a.rows = d_rows; a.Xt = d_Xt; a.ft = d_ll_f; a.gt = d_grad_g; a.maxiter = maxiter;
-    a.pos_next = d_pos_next; a.Xt_next = d_Xt_next; a.V = d_V; a.flags = flags_dev;
-    hipLaunchKernelGGL(k_ncg_search_step, dim3(L), dim3(256), 0, h->stream, pgl_ncg_view(d_state, M, P), a);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-// ---- lock-step HMC row kernels (inference/batched_hmc.py) --------------------------------------------------------------
-long long pgl_hmc_state_doubles(int M, int P) { return (long long)pgl_hmc_doubles(M, P); }
-
-// R = C M rows: chain c of neuron n_lo + m is row c M + m and runs on pgl_chain_seed(seed, c)
-static int hmc_init(pgl_handle h, double* d_state, int M, int C, int P, int n_lo, double* d_ll, double* d_grad, int prior_kind,
-                    double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam, double step0,
-                    uint64_t seed)
-{
-    if (!h || !d_state || !d_ll || !d_grad || M <= 0 || C <= 0 || P <= 0 || n_lo < 0 || n_lo + M > h->N || !(step0 > 0.0) ||
-        (long long)M * C > 0x7fffffffLL)
-        return fail(PGL_ERR_ARG, "bad argument");
-    BfgsPrior q;
-    int rc = ncg_prior(h, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_hmc_init, dim3(M * C), dim3(256), 0, h->stream, pgl_hmc_view(d_state, M * C, P), d_ll, d_grad, q, n_lo,
-                       step0, (unsigned long long)seed, M);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-int pgl_hmc_init_dev(pgl_handle h, double* d_state, int M, int P, int n_lo, double* d_ll, double* d_grad, int prior_kind,
-                     double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam, double step0,
-                     uint64_t seed)
-{
-    return hmc_init(h, d_state, M, 1, P, n_lo, d_ll, d_grad, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, step0, seed);
-}
-
-int pgl_hmc_init_chains_dev(pgl_handle h, double* d_state, int M, int C, int P, int n_lo, double* d_ll, double* d_grad,
-                            int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam,
-                            double step0, uint64_t seed)
-{
-    return hmc_init(h, d_state, M, C, P, n_lo, d_ll, d_grad, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, step0, seed);
-}
-
-// ---- windowed diagonal mass adaptation (mass='adapt'; pglm_adapt.h) ---------------------------------------------------
-long long pgl_adapt_state_doubles(int R, int P)
-{
-    if (R <= 0 || P <= 0) return 0;
-    return (long long)pgl_adapt_doubles(R, P);
-}
-
-int pgl_mass_adapt_dev(pgl_handle h, double* d_state, int R, int P, double* d_adapt, const int* d_sched, double* d_minv)
-{
-    if (!h || !d_state || !d_adapt || !d_sched || !d_minv || R <= 0 || P <= 0) return fail(PGL_ERR_ARG, "bad argument");
-    HIPCHK(hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_hmc_mass_adapt, dim3(R), dim3(256), 0, h->stream, pgl_hmc_view(d_state, R, P),
-                       pgl_adapt_view(d_adapt, R, P), d_sched, d_minv);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-int pgl_hmc_begin_dev(pgl_handle h, double* d_state, int M, int P, const double* d_minv, double* d_Xt)
-{
-    if (!h || !d_state || !d_Xt || M <= 0 || P <= 0) return fail(PGL_ERR_ARG, "bad argument");
-    HIPCHK(hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_hmc_begin, dim3(M), dim3(256), 0, h->stream, pgl_hmc_view(d_state, M, P), d_minv, M, d_Xt);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-int pgl_hmc_leap_dev(pgl_handle h, double* d_state, int M, int P, const double* d_minv, double* d_ll, double* d_grad,
-                     int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam, int last,
-                     int n_warmup, double* d_Xt, double* d_sample_out)
-{
-    if (!h || !d_state || !d_ll || !d_grad || !d_Xt || M <= 0 || P <= 0) return fail(PGL_ERR_ARG, "bad argument");
-    BfgsPrior q;
-    int rc = ncg_prior(h, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_hmc_leap, dim3(M), dim3(256), 0, h->stream, pgl_hmc_view(d_state, M, P), d_minv, d_ll, d_grad, q,
-                       last ? 1 : 0, n_warmup, d_Xt, d_sample_out);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-// ---- lock-step HMC with a dense mass matrix (inference/batched_hmc.py: mass = (M, P, P) or 'laplace_dense') -------------
-// The kick and the drift are epilogues of the products (pglm_hmc_dense.hip.h): no product is ever stored, no workspace.
-long long pgl_hmc_dense_work_doubles(int M, int P) { (void)M; (void)P; return 0; }
-
-// The four (TRANS, EPI) instantiations of a product kernel that the chains and pgl_tri_matvec*_dev use: LAUNCH(TRANS, EPI, KC)
-// for the one that (trans, epi) names.
-#define PGL_TRI_DISPATCH(LAUNCH, KC)                                           \
-    do {                                                                       \
-        if (epi == PGL_TRI_KICK) LAUNCH(1, PGL_TRI_KICK, KC);                  \
-        else if (epi == PGL_TRI_DRIFT) LAUNCH(0, PGL_TRI_DRIFT, KC);           \
-        else if (trans) LAUNCH(1, PGL_TRI_STORE, KC);                          \
-        else LAUNCH(0, PGL_TRI_STORE, KC);                                     \
-    } while (0)
-
-// one product launch, one vector per matrix (the chain, NUTS, pgl_tri_matvec_dev)
-static int tri_launch(pgl_handle h, int trans, int epi, const double* d_W, int M, int P, const double* d_x, double* d_y,
-                      double* d_Xt, const double* d_step, double scale)
-{
-    if (M > 65535) return fail(PGL_ERR_ARG, "at most 65535 rows per call");
-    const dim3 grid(h->opt_tri_rows ? 1 : (P + PGL_TRI_TILE - 1) / PGL_TRI_TILE, M);
-#define PGL_TRI_LAUNCH(T, E, KC) hipLaunchKernelGGL((k_tri_matvec<T, E>), grid, dim3(256), 0, h->stream, d_W, d_x, P, d_y, d_Xt, d_step, scale)
-    PGL_TRI_DISPATCH(PGL_TRI_LAUNCH, 1);
-#undef PGL_TRI_LAUNCH
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-int pgl_tri_matvec_dev(pgl_handle h, const double* d_W, int M, int P, int trans, const double* d_x, double* d_y)
-{
-    if (!h || !d_W || !d_x || !d_y || d_x == d_y || M <= 0 || P <= 0) return fail(PGL_ERR_ARG, "bad argument");
-    HIPCHK(hipSetDevice(h->device));
-    return tri_launch(h, trans, PGL_TRI_STORE, d_W, M, P, d_x, d_y, nullptr, nullptr, 0.0);
-}
-
-// ---- batched dense factorisation for the Laplace posterior (pglm_chol.hip.h) ------------------------------------------
-int pgl_chol_factor_dev(pgl_handle h, double* d_A, int M, int P, int ld, double* d_scale, double* d_logdet, int* d_info)
-{
-    if (!h || !d_A || !d_scale || !d_logdet || !d_info || M <= 0 || P <= 0 || ld < P) return fail(PGL_ERR_ARG, "bad argument");
-    HIPCHK(hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_chol_factor, dim3(M), dim3(256), 0, h->stream, d_A, P, ld, d_scale, d_logdet, d_info);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-int pgl_tri_inverse_dev(pgl_handle h, double* d_L, int M, int P, int ld, const int* d_info)
-{
-    if (!h || !d_L || !d_info || M <= 0 || P <= 0 || ld < P) return fail(PGL_ERR_ARG, "bad argument");
-    HIPCHK(hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_tri_inverse, dim3(M), dim3(256), 0, h->stream, d_L, P, ld, d_info);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-int pgl_hmc_dense_begin_dev(pgl_handle h, double* d_state, int M, int P, const double* d_W, double* d_work, double* d_Xt)
-{
-    (void)d_work;
-    if (!h || !d_state || !d_W || !d_Xt || M <= 0 || P <= 0) return fail(PGL_ERR_ARG, "bad argument");
-    HIPCHK(hipSetDevice(h->device));
-    const HmcView v = pgl_hmc_view(d_state, M, P);
-    hipLaunchKernelGGL(k_hmc_dense_draw, dim3(M), dim3(256), 0, h->stream, v);
-    HIPCHK(hipGetLastError());
-    const double* step = v.sc + (size_t)2 * M;
-    int rc = tri_launch(h, 1, PGL_TRI_KICK, d_W, M, P, v.g, v.p, nullptr, step, 0.5);
-    if (rc) return rc;
-    return tri_launch(h, 0, PGL_TRI_DRIFT, d_W, M, P, v.p, v.q, d_Xt, step, 1.0);
-}
-
-int pgl_hmc_dense_leap_dev(pgl_handle h, double* d_state, int M, int P, const double* d_W, double* d_work, double* d_ll,
-                           double* d_grad, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu,
-                           double sigma, double lam, int last, int n_warmup, double* d_Xt, double* d_sample_out)
-{
-    (void)d_work;
-    if (!h || !d_state || !d_W || !d_ll || !d_grad || !d_Xt || M <= 0 || P <= 0) return fail(PGL_ERR_ARG, "bad argument");
-    BfgsPrior q;
-    int rc = ncg_prior(h, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    const HmcView v = pgl_hmc_view(d_state, M, P);
-    hipLaunchKernelGGL(k_hmc_dense_target, dim3(M), dim3(256), 0, h->stream, v, d_ll, d_grad, q);
-    HIPCHK(hipGetLastError());
-    const double* step = v.sc + (size_t)2 * M;
-    rc = tri_launch(h, 1, PGL_TRI_KICK, d_W, M, P, d_grad, v.p, nullptr, step, last ? 0.5 : 1.0);
-    if (rc) return rc;
-    if (!last) return tri_launch(h, 0, PGL_TRI_DRIFT, d_W, M, P, v.p, v.q, d_Xt, step, 1.0);
-    hipLaunchKernelGGL(k_hmc_dense_end, dim3(M), dim3(256), 0, h->stream, v, d_ll, d_grad, n_warmup, d_sample_out);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-// ---- NUTS row kernels (inference/batched_nuts.py) ------------------------------------------------------------------------
-long long pgl_nuts_state_doubles(int M, int P, int max_depth)
-{
-    if (M <= 0 || P <= 0 || max_depth < 1 || max_depth > PGL_NUTS_MAX_DEPTH) return 0;
-    return (long long)pgl_nuts_doubles(M, P, max_depth);
-}
-
-static int nuts_args(pgl_handle h, const double* d_state, int M, int P, int max_depth, const double* d_ll, const double* d_grad,
-                     int n_warmup, int thin, int n_keep, const double* d_Xt)
-{
-    if (!h || !d_state || !d_ll || !d_grad || !d_Xt || M <= 0 || P <= 0 || n_warmup < 0 || thin <= 0 || n_keep < 0 ||
-        (long long)n_warmup + (long long)n_keep * thin > 0x7fffffffLL)
-        return fail(PGL_ERR_ARG, "bad argument");
-    if (max_depth < 1 || max_depth > PGL_NUTS_MAX_DEPTH) return fail(PGL_ERR_ARG, "max_depth: 1 .. 10");
-    return PGL_OK;
-}
-
-static int nuts_init(pgl_handle h, double* d_state, int M0, int C, int P, int max_depth, int n_lo, double* d_ll, double* d_grad,
-                     int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam,
-                      const double* d_minv, const double* d_W, const double* d_step0, uint64_t seed, int n_warmup, int thin,
-                      int n_keep, double* d_Xt)
-{
-    if (M0 <= 0 || C <= 0 || (long long)M0 * C > 0x7fffffffLL) return fail(PGL_ERR_ARG, "bad argument");
-    const int M = M0 * C;                                                      // rows: chain c of neuron n_lo + m is row c M0 + m
-    int rc = nuts_args(h, d_state, M, P, max_depth, d_ll, d_grad, n_warmup, thin, n_keep, d_Xt);
-    if (rc) return rc;
-    if (!d_step0 || n_lo < 0 || n_lo + M0 > h->N) return fail(PGL_ERR_ARG, "bad argument");
-    BfgsPrior q;
-    rc = ncg_prior(h, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    const NutsView v = pgl_nuts_view(d_state, M, P, max_depth);
-    const size_t MP = (size_t)M * P;
-    if (d_W) {
-        hipLaunchKernelGGL(k_nuts_target, dim3(M), dim3(256), 0, h->stream, v, (int)PGL_NUTS_QC, d_ll, d_grad, q);
-        HIPCHK(hipGetLastError());
-        rc = tri_launch(h, 1, PGL_TRI_STORE, d_W, M, P, d_grad, v.vec + PGL_NUTS_HB * MP, nullptr, nullptr, 0.0);
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(k_nuts_init, dim3(M), dim3(256), 0, h->stream, v, d_ll, d_grad, q, d_W ? 1 : 0, d_minv, n_lo, d_step0,
-                       (unsigned long long)seed, n_warmup + n_keep * thin, d_Xt, M0);
-    HIPCHK(hipGetLastError());
-    if (!d_W) return PGL_OK;
-    return tri_launch(h, 0, PGL_TRI_DRIFT, d_W, M, P, v.vec + PGL_NUTS_RW * MP, v.vec + PGL_NUTS_QW * MP, d_Xt,
-                      v.sc + (size_t)PGL_NUTS_F_VE * M, 1.0);
-}
-
-int pgl_nuts_init_dev(pgl_handle h, double* d_state, int M, int P, int max_depth, int n_lo, double* d_ll, double* d_grad,
-                      int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam,
-                      const double* d_minv, const double* d_W, const double* d_step0, uint64_t seed, int n_warmup, int thin,
-                      int n_keep, double* d_Xt)
-{
-    return nuts_init(h, d_state, M, 1, P, max_depth, n_lo, d_ll, d_grad, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam,
-                     d_minv, d_W, d_step0, seed, n_warmup, thin, n_keep, d_Xt);
-}
-
-// d_minv, d_W: (C M, P) / (C M, P, P), one per row
-int pgl_nuts_init_chains_dev(pgl_handle h, double* d_state, int M, int C, int P, int max_depth, int n_lo, double* d_ll,
-                             double* d_grad, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu,
-                             double sigma, double lam, const double* d_minv, const double* d_W, const double* d_step0,
-                             uint64_t seed, int n_warmup, int thin, int n_keep, double* d_Xt)
-{
-    return nuts_init(h, d_state, M, C, P, max_depth, n_lo, d_ll, d_grad, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam,
-                     d_minv, d_W, d_step0, seed, n_warmup, thin, n_keep, d_Xt);
-}
-
-int pgl_nuts_step_dev(pgl_handle h, double* d_state, int M, int P, int max_depth, double* d_ll, double* d_grad,
-                      int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam,
-                      const double* d_minv, const double* d_W, double target_accept, int n_warmup, int thin, int n_keep,
-                      double* d_Xt, double* d_samples, double* d_stats)
-{
-    int rc = nuts_args(h, d_state, M, P, max_depth, d_ll, d_grad, n_warmup, thin, n_keep, d_Xt);
-    if (rc) return rc;
-    if (!(target_accept > 0.0 && target_accept < 1.0)) return fail(PGL_ERR_ARG, "target_accept: in (0, 1)");
-    BfgsPrior q;
-    rc = ncg_prior(h, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    const NutsView v = pgl_nuts_view(d_state, M, P, max_depth);
-    const size_t MP = (size_t)M * P;
-    if (d_W) {
-        hipLaunchKernelGGL(k_nuts_target, dim3(M), dim3(256), 0, h->stream, v, (int)PGL_NUTS_QW, d_ll, d_grad, q);
-        HIPCHK(hipGetLastError());
-        rc = tri_launch(h, 1, PGL_TRI_STORE, d_W, M, P, d_grad, v.vec + PGL_NUTS_HB * MP, nullptr, nullptr, 0.0);
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(k_nuts_step, dim3(M), dim3(256), 0, h->stream, v, d_ll, d_grad, q, d_W ? 1 : 0, d_minv, target_accept,
-                       n_warmup, thin, n_keep, d_Xt, d_samples, d_stats);
-    HIPCHK(hipGetLastError());
-    if (!d_W) return PGL_OK;
-    return tri_launch(h, 0, PGL_TRI_DRIFT, d_W, M, P, v.vec + PGL_NUTS_RW * MP, v.vec + PGL_NUTS_QW * MP, d_Xt,
-                      v.sc + (size_t)PGL_NUTS_F_VE * M, 1.0);
-}
-
-// pgl_nuts_step_dev for the diagonal chain under mass='adapt': d_minv (M, P) is read and, at a row's window ends, rewritten
-int pgl_nuts_adapt_step_dev(pgl_handle h, double* d_state, int M, int P, int max_depth, double* d_ll, double* d_grad,
-                            int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam,
-                            double* d_minv, double* d_adapt, const int* d_sched, double target_accept, int n_warmup, int thin,
-                            int n_keep, double* d_Xt, double* d_samples, double* d_stats)
-{
-    int rc = nuts_args(h, d_state, M, P, max_depth, d_ll, d_grad, n_warmup, thin, n_keep, d_Xt);
-    if (rc) return rc;
-    if (!d_minv || !d_adapt || !d_sched) return fail(PGL_ERR_ARG, "bad argument");
-    if (!(target_accept > 0.0 && target_accept < 1.0)) return fail(PGL_ERR_ARG, "target_accept: in (0, 1)");
-    BfgsPrior q;
-    rc = ncg_prior(h, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_nuts_adapt_step, dim3(M), dim3(256), 0, h->stream, pgl_nuts_view(d_state, M, P, max_depth), d_ll,
-                       d_grad, q, d_minv, target_accept, n_warmup, thin, n_keep, d_Xt, d_samples, d_stats,
-                       pgl_adapt_view(d_adapt, M, P), d_sched);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-// ---- annealed importance sampling row kernels (inference/batched_ais.py) -----------------------------------------------
-long long pgl_ais_state_doubles(int R, int P) { return (long long)pgl_ais_doubles((size_t)(R > 0 ? R : 0), (size_t)(P > 0 ? P : 0)); }
-
-static int ais_prior(pgl_handle h, int K, int M, int P, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu,
-                     double sigma, double lam, BfgsPrior& q)
-{
-    if (K <= 0 || M <= 0 || P <= 0 || (long long)K * M > 0x7fffffffLL) return fail(PGL_ERR_ARG, "bad argument");
-    if (prior_kind == 1)
-        return fail(PGL_ERR_UNSUPPORTED, "annealed importance sampling starts from an exact prior draw: Gaussian priors only");
-    int rc = ncg_prior(h, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
-    if (rc) return rc;
-    if (!(sg_b > 0.0) || !(sigma > 0.0) || (h->Dstim > 0 && !(stim_sigma > 0.0)))
-        return fail(PGL_ERR_ARG, "the prior standard deviations must be positive");
-    return PGL_OK;
-}
-
-int pgl_ais_init_dev(pgl_handle h, double* d_state, int K, int M, int P, int n_lo, int particle0, int prior_kind, double mu_b,
-                     double sg_b, double stim_sigma, double mu, double sigma, double lam, double step0, uint64_t seed,
-                     double* d_Xt)
-{
-    if (!h || !d_state || !d_Xt || n_lo < 0 || M <= 0 || n_lo + M > h->N || particle0 < -1 || !(step0 > 0.0))
-        return fail(PGL_ERR_ARG, "bad argument");
-    BfgsPrior q;
-    int rc = ais_prior(h, K, M, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_ais_init, dim3(K * M), dim3(256), 0, h->stream, pgl_ais_view(d_state, K, M, P), d_Xt, q, n_lo,
-                       particle0, step0, (unsigned long long)seed);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-int pgl_ais_start_dev(pgl_handle h, double* d_state, int K, int M, int P, const double* d_ll, const double* d_grad,
-                      int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma, double lam)
-{
-    if (!h || !d_state || !d_ll || !d_grad) return fail(PGL_ERR_ARG, "bad argument");
-    BfgsPrior q;
-    int rc = ais_prior(h, K, M, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_ais_start, dim3(K * M), dim3(256), 0, h->stream, pgl_ais_view(d_state, K, M, P), d_ll, d_grad, q);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-int pgl_ais_temper_dev(pgl_handle h, double* d_state, int K, int M, int P, int prior_kind, double mu_b, double sg_b,
-                       double stim_sigma, double mu, double sigma, double lam, double beta, const double* d_step_row)
-{
-    if (!h || !d_state || !(beta >= 0.0 && beta <= 1.0)) return fail(PGL_ERR_ARG, "bad argument");
-    BfgsPrior q;
-    int rc = ais_prior(h, K, M, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_ais_temper, dim3(K * M), dim3(256), 0, h->stream, pgl_ais_view(d_state, K, M, P), q, beta, d_step_row);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-int pgl_ais_begin_dev(pgl_handle h, double* d_state, int K, int M, int P, const double* d_minv, double* d_Xt)
-{
-    if (!h || !d_state || !d_Xt || K <= 0 || M <= 0 || P <= 0 || (long long)K * M > 0x7fffffffLL)
-        return fail(PGL_ERR_ARG, "bad argument");
-    HIPCHK(hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_hmc_begin, dim3(K * M), dim3(256), 0, h->stream, pgl_ais_hmc_view(pgl_ais_view(d_state, K, M, P)), d_minv, M,
-                       d_Xt);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-int pgl_ais_leap_dev(pgl_handle h, double* d_state, int K, int M, int P, const double* d_minv, const double* d_ll,
-                     const double* d_grad, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu, double sigma,
-                     double lam, int last, int adapt, double* d_Xt, double* d_acc_out, double* d_step_out)
-{
-    if (!h || !d_state || !d_ll || !d_grad || !d_Xt) return fail(PGL_ERR_ARG, "bad argument");
-    BfgsPrior q;
-    int rc = ais_prior(h, K, M, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_ais_leap, dim3(K * M), dim3(256), 0, h->stream, pgl_ais_view(d_state, K, M, P), d_minv, d_ll, d_grad, q,
-                       last ? 1 : 0, adapt ? 1 : 0, d_Xt, d_acc_out, d_step_out);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-// ---- annealed importance sampling with a dense mass matrix (inference/batched_ais.py: mass = (M, P, P) or 'laplace_dense') ---
-// one shared product launch: the particles of a neuron meet the neuron's W in one workgroup, KC at a time
-static int tri_shared_launch(pgl_handle h, int trans, int epi, const double* d_W, int K, int M, int P, const double* d_x,
-                             double* d_y, double* d_Xt, const double* d_step, double scale)
-{
-    if (M > 65535) return fail(PGL_ERR_ARG, "at most 65535 neurons per call");
-    const dim3 grid((P + PGL_TRI_TILE - 1) / PGL_TRI_TILE, M);
-#define PGL_TRI_LAUNCH(T, E, KC) hipLaunchKernelGGL((k_tri_matvec_shared<T, E, KC>), grid, dim3(256), 0, h->stream, d_W, d_x, K, M, P, d_y, d_Xt, d_step, scale)
-    if (K == 1) PGL_TRI_DISPATCH(PGL_TRI_LAUNCH, 1);
-    else if (K == 2) PGL_TRI_DISPATCH(PGL_TRI_LAUNCH, 2);
-    else if (K <= 4) PGL_TRI_DISPATCH(PGL_TRI_LAUNCH, 4);
-    else PGL_TRI_DISPATCH(PGL_TRI_LAUNCH, PGL_TRI_SHARED_KC);
-#undef PGL_TRI_LAUNCH
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-int pgl_tri_matvec_shared_dev(pgl_handle h, const double* d_W, int M, int K, int P, int trans, const double* d_x, double* d_y)
-{
-    if (!h || !d_W || !d_x || !d_y || d_x == d_y || M <= 0 || K <= 0 || P <= 0 || (long long)K * M > 0x7fffffffLL)
-        return fail(PGL_ERR_ARG, "bad argument");
-    HIPCHK(hipSetDevice(h->device));
-    return tri_shared_launch(h, trans, PGL_TRI_STORE, d_W, K, M, P, d_x, d_y, nullptr, nullptr, 0.0);
-}
-
-int pgl_ais_dense_begin_dev(pgl_handle h, double* d_state, int K, int M, int P, const double* d_W, double* d_Xt)
-{
-    if (!h || !d_state || !d_W || !d_Xt || K <= 0 || M <= 0 || P <= 0 || (long long)K * M > 0x7fffffffLL)
-        return fail(PGL_ERR_ARG, "bad argument");
-    HIPCHK(hipSetDevice(h->device));
-    const AisView v = pgl_ais_view(d_state, K, M, P);
-    hipLaunchKernelGGL(k_hmc_dense_draw, dim3(K * M), dim3(256), 0, h->stream, pgl_ais_hmc_view(v));
-    HIPCHK(hipGetLastError());
-    const double* step = v.sc + (size_t)2 * v.R;
-    int rc = tri_shared_launch(h, 1, PGL_TRI_KICK, d_W, K, M, P, v.g, v.p, nullptr, step, 0.5);
-    if (rc) return rc;
-    return tri_shared_launch(h, 0, PGL_TRI_DRIFT, d_W, K, M, P, v.p, v.q, d_Xt, step, 1.0);
-}
-
-int pgl_ais_dense_leap_dev(pgl_handle h, double* d_state, int K, int M, int P, const double* d_W, const double* d_ll,
-                           const double* d_grad, int prior_kind, double mu_b, double sg_b, double stim_sigma, double mu,
-                           double sigma, double lam, int last, int adapt, double* d_Xt, double* d_acc_out, double* d_step_out)
-{
-    if (!h || !d_state || !d_W || !d_ll || !d_grad || !d_Xt) return fail(PGL_ERR_ARG, "bad argument");
-    BfgsPrior q;
-    int rc = ais_prior(h, K, M, P, prior_kind, mu_b, sg_b, stim_sigma, mu, sigma, lam, q);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    const AisView v = pgl_ais_view(d_state, K, M, P);
-    hipLaunchKernelGGL(k_ais_dense_target, dim3(K * M), dim3(256), 0, h->stream, v, d_grad, q);
-    HIPCHK(hipGetLastError());
-    const double* step = v.sc + (size_t)2 * v.R;
-    rc = tri_shared_launch(h, 1, PGL_TRI_KICK, d_W, K, M, P, v.gu, v.p, nullptr, step, last ? 0.5 : 1.0);
-    if (rc) return rc;
-    if (!last) return tri_shared_launch(h, 0, PGL_TRI_DRIFT, d_W, K, M, P, v.p, v.q, d_Xt, step, 1.0);
-    hipLaunchKernelGGL(k_ais_dense_end, dim3(K * M), dim3(256), 0, h->stream, v, d_ll, d_grad, q, adapt ? 1 : 0, d_acc_out,
-                       d_step_out);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-// ---- lock-step proximal gradient row kernels for the group-lasso MAP (inference/batched_prox.py) -------------------------
-long long pgl_prox_state_doubles(int M, int P) { return (long long)pgl_prox_doubles(M, P); }
-
-static int prox_args(pgl_handle h, double* d_state, int M, int P, double* d_ll, double* d_grad, double mu_b, double sg_b,
-                     double stim_sigma, double mu, double sigma, const double* d_lam, double gtol, int maxiter, int max_backtrack,
-                     double* d_Xt, double* flags_out, ProxArgs& a)
-{
-    if (!h || !d_state || !d_ll || !d_grad || !d_lam || !d_Xt || M <= 0 || P <= 0) return fail(PGL_ERR_ARG, "bad argument");
-    if (!(gtol > 0.0) || !(sigma > 0.0)) return fail(PGL_ERR_ARG, "gtol and sigma must be positive");
-    memset(&a, 0, sizeof(a));
-    int rc = ncg_prior(h, P, 1, mu_b, sg_b, stim_sigma, mu, sigma, 0.0, a.q);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    double* flags_dev = nullptr;
-    if (flags_out && flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
-    a.ll = d_ll; a.grad = d_grad; a.lam = d_lam; a.gtol = gtol; a.maxiter = maxiter; a.max_backtrack = max_backtrack;
-    a.Xt = d_Xt; a.flags = flags_dev;
-    return PGL_OK;
-}
-
-int pgl_prox_init_dev(pgl_handle h, double* d_state, int M, int P, double* d_ll, double* d_grad, double mu_b, double sg_b,
-                      double stim_sigma, double mu, double sigma, const double* d_lam, double gtol, int maxiter, double* d_Xt,
-                      double* flags_out)
-{
-    ProxArgs a;
-    int rc = prox_args(h, d_state, M, P, d_ll, d_grad, mu_b, sg_b, stim_sigma, mu, sigma, d_lam, gtol, maxiter, 1, d_Xt, flags_out, a);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_prox_init, dim3(M), dim3(256), 0, h->stream, pgl_prox_view(d_state, M, P), a);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
-int pgl_prox_step_dev(pgl_handle h, double* d_state, int M, int P, double* d_ll, double* d_grad, double mu_b, double sg_b,
-                      double stim_sigma, double mu, double sigma, const double* d_lam, double gtol, int maxiter, int max_backtrack,
-                      double* d_Xt, double* flags_out)
-{
-    if (max_backtrack <= 0) return fail(PGL_ERR_ARG, "max_backtrack must be positive");
-    ProxArgs a;
-    int rc = prox_args(h, d_state, M, P, d_ll, d_grad, mu_b, sg_b, stim_sigma, mu, sigma, d_lam, gtol, maxiter, max_backtrack, d_Xt,
-                       flags_out, a);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_prox_step, dim3(M), dim3(256), 0, h->stream, pgl_prox_view(d_state, M, P), a);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
+// the lock-step entry points, BFGS bookkeeping through proximal gradient (inside extern "C")
+#include "pglm_capi_rows.h"
 
 int pgl_sync(pgl_handle h)
 {

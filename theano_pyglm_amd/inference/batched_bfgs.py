@@ -76,7 +76,7 @@ class _Packing(object):
         self.stim_sigma = float(bk.sigma) if self.bk == 'st_sep' else 0.01
 
     def prior_params(self):
-        """(kind, mu_b, sg_b, stim_sigma, mu, sigma, lam) for pgl_bfgs_objective_dev."""
+        """(kind, mu_b, sg_b, stim_sigma, mu, sigma, lam): the fields of pgl_prior (_lib.as_prior)."""
         glm = self.glm
         pr = glm.imp_model.prior
         kind = 1 if isinstance(pr, GroupLasso) else 0
@@ -394,7 +394,7 @@ def _lockstep_bfgs(population, torch, dev, stream, handles, x, maxiter, gtol, n_
 
     f0, g0, pr0 = evaluate(X, None, None, M)
     if pr0 is not None:
-        h0.bfgs_objective_dev(M, P, X.data_ptr(), f0.data_ptr(), g0.data_ptr(), *pr0)
+        h0.bfgs_objective_dev(M, P, X.data_ptr(), f0.data_ptr(), g0.data_ptr(), pr0)
     f.copy_(f0)
     g.copy_(g0)
     h0.bfgs_init_dev(st.data_ptr(), M, P, gtol)

@@ -315,10 +315,7 @@ def _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, n_le
         stream.synchronize()
 
     ll0, g0 = evaluate(q)
-    if C == 1:
-        h0.hmc_init_dev(st.data_ptr(), M, P, n_lo, ll0.data_ptr(), g0.data_ptr(), prm, float(step[0]), seed)
-    else:
-        h0.hmc_init_chains_dev(st.data_ptr(), M, C, P, n_lo, ll0.data_ptr(), g0.data_ptr(), prm, float(step[0]), seed)
+    h0.hmc_init_dev(st.data_ptr(), M, P, n_lo, ll0.data_ptr(), g0.data_ptr(), prm, float(step[0]), seed, n_chains=C)
     if np.any(step != step[0]):
         sc[SC_STEP].copy_(torch.tensor(np.tile(step, C), dtype=f64, device=dev))
     n_total = n_warmup + n_samples * thin
@@ -326,7 +323,7 @@ def _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, n_le
     evals_before_chain = evaluate.count
     for t in range(n_total):
         if Wd is not None:
-            h0.hmc_dense_begin_dev(st.data_ptr(), R, P, Wd.data_ptr(), 0, Xt.data_ptr())
+            h0.hmc_dense_begin_dev(st.data_ptr(), R, P, Wd.data_ptr(), Xt.data_ptr())
         else:
             h0.hmc_begin_dev(st.data_ptr(), R, P, minv_ptr, Xt.data_ptr())
         counts['row'] += 1
@@ -337,8 +334,8 @@ def _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, n_le
             last = i == n_leapfrog - 1
             out_ptr = samples[k // thin].data_ptr() if (last and keep) else 0
             if Wd is not None:
-                h0.hmc_dense_leap_dev(st.data_ptr(), R, P, Wd.data_ptr(), 0, llt.data_ptr(), gt.data_ptr(), prm,
-                                      last, n_warmup, Xt.data_ptr(), out_ptr)
+                h0.hmc_dense_leap_dev(st.data_ptr(), R, P, Wd.data_ptr(), llt.data_ptr(), gt.data_ptr(), prm, last,
+                                      n_warmup, Xt.data_ptr(), out_ptr)
             else:
                 h0.hmc_leap_dev(st.data_ptr(), R, P, minv_ptr, llt.data_ptr(), gt.data_ptr(), prm, last, n_warmup,
                                 Xt.data_ptr(), out_ptr)

@@ -116,12 +116,8 @@ def _chain(population, torch, dev, stream, handles, x, n_keep, n_warmup, D, step
     counts = {'polls': 0}
 
     ll0, g0 = evaluate(st[0:RP].view(R, P))
-    if C == 1:
-        h0.nuts_init_dev(st.data_ptr(), M, P, D, n_lo, ll0.data_ptr(), g0.data_ptr(), prm, minv_ptr, W_ptr, step0.data_ptr(),
-                         seed, n_warmup, thin, n_keep, Xt.data_ptr())
-    else:
-        h0.nuts_init_chains_dev(st.data_ptr(), M, C, P, D, n_lo, ll0.data_ptr(), g0.data_ptr(), prm, minv_ptr, W_ptr,
-                                step0.data_ptr(), seed, n_warmup, thin, n_keep, Xt.data_ptr())
+    h0.nuts_init_dev(st.data_ptr(), M, P, D, n_lo, ll0.data_ptr(), g0.data_ptr(), prm, minv_ptr, W_ptr, step0.data_ptr(),
+                     seed, n_warmup, thin, n_keep, Xt.data_ptr(), n_chains=C)
     launches, events, all_done = 0, [], False
     while not all_done:
         llt, gt = evaluate(Xt)

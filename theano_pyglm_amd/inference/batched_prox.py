@@ -107,7 +107,7 @@ def _lockstep(population, torch, dev, stream, handles, x, lam, maxiter, gtol, ma
         raise ValueError("lock-step proximal gradient: the per-neuron vector of this population is not the device's theta row")
     h0 = handles[0]
     P = pk.Pp
-    prm = pk.prior_params()[1:6]                              # (mu_b, sg_b, stim_sigma, mu, sigma)
+    prm = pk.prior_params()
     f64 = torch.float64
     MP = M * P
     st = torch.zeros(h0.prox_state_doubles(M, P), dtype=f64, device=dev)
@@ -172,7 +172,7 @@ def _lockstep(population, torch, dev, stream, handles, x, lam, maxiter, gtol, ma
     o = 1 + pk.nbk
     res = {'status': sch[SC['status']].astype(int), 'iters': sch[SC['iters']].astype(int), 'nfev': sch[SC['nfev']].astype(int),
            'kkt': sch[SC['kkt']].copy(), 'objective': sch[SC['F_x']].copy(),
-           'support': np.any(Xh[:, o:].reshape(M, pk.N, pk.B) != prm[3], axis=2), 'lam': lam.copy()}
+           'support': np.any(Xh[:, o:].reshape(M, pk.N, pk.B) != prm[4], axis=2), 'lam': lam.copy()}
     population.last_fit_stats = {'optimizer': 'lock-step proximal gradient (hip row kernels)', 'll_grad_launches': evaluate.count,
                                  'row_launches': counts['row'], 'flag_polls': counts['polls'], 'loop_s': loop_s,
                                  'restarts': [int(v) for v in sch[SC['restarts']]],

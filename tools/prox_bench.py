@@ -86,7 +86,7 @@ def run(name, n_lams, reps):
     lam = torch.full((N,), out['lam'], dtype=f64, device=dev)
     Xt = torch.empty((N, P), dtype=f64, device=dev)
     pk = BP._Packing(popn, torch, [h], (0, N))
-    prm = pk.prior_params()[1:6]
+    prm = pk.prior_params()
     stream = torch.cuda.Stream(dev)
     h.set_stream(stream.cuda_stream)
     try:
