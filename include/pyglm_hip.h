@@ -92,7 +92,7 @@ typedef struct pgl_context* pgl_handle;
 
 /* What pgl_version() returns: it changes with every change of a signature or a struct below, and a binding refuses a
  * library that reports another number (theano_pyglm_amd/_lib.py: ABI_VERSION). */
-#define PGL_ABI_VERSION 107
+#define PGL_ABI_VERSION 108
 
 const char* pgl_last_error(void);
 int pgl_version(void);
@@ -572,6 +572,61 @@ int pgl_ais_dense_begin_dev(pgl_handle h, double* d_state, int K, int M, int P, 
 int pgl_ais_dense_leap_dev(pgl_handle h, double* d_state, int K, int M, int P, const double* d_W, const double* d_ll,
                            const double* d_grad, const pgl_prior* prior, int last, int adapt, double* d_Xt, double* d_acc_out,
                            double* d_step_out);
+
+/* Adaptive sequential Monte Carlo (Del Moral, Doucet & Jasra 2006; ladder rule of Jasra et al. 2011 / Zhou, Johansen &
+ * Aston 2016; inference/batched_smc.py) of the evidence log Z_n on the tempered path above, restated in csrc/pglm_smc.h over
+ * csrc/pglm_ais.h.  The rows are the AIS rows (d_state: the pgl_ais_state_doubles(K M, P) block, r = k M + i, particles
+ * 0 .. K - 1); every NEURON owns its temperature, its evidence, ONE step size shared by its K particles, and a done flag.
+ * The estimate of Z is consistent, not unbiased as Neal's AIS is.  A stage of a neuron that is not done, with W_k the
+ * normalised weights exp(logw_k) / sum (a particle with a non-finite ll0 or logw = -inf is dead: W_k = 0 for good):
+ *   0. step rule (stages after the first): a = acceptances of the moves since the last stage / (K n_steps),
+ *      step = clip(step exp(a - 0.9), 1e-3, 1).
+ *   1. next temperature: CESS(d) = K (sum W_k v_k)^2 / sum W_k v_k^2, v_k = exp(d (ll0_k - max ll0)).  CESS(1 - beta) >=
+ *      cess K: d = 1 - beta.  Else 60 halvings of [0, 1 - beta] towards CESS = cess K, d = the lower end.  d = max(d,
+ *      delta_min); d >= 1 - beta: d = 1 - beta and beta = 1 exactly.
+ *   2. log_Z += d max ll0 + log sum W_k v_k;  W_k = W_k v_k / sum W v, logw_k = log W_k.  No live particle: log_Z = -inf,
+ *      the neuron is done and its rows stay as they are.
+ *   3. resampling when ESS = 1 / sum W_k^2 < ess_min K: systematic with ONE uniform
+ *          u = U_0 of key(mix(seed ^ 0x5eed5eed5eed5eed), n, stage)      n: NEURON index, stage: the stage's number from 0,
+ *      key, mix and U_0 as above, u in (0, 1); with c_j = W_0 + ... + W_j summed in index order, anc[k] = the first j with
+ *      c_j >= (u + k) / K (past the end by rounding: the last live particle); then logw = 0 for every slot.  Slot k takes q,
+ *      gll, ll0, lp0 of slot anc[k], out of place through scratch; its seed, particle index, t and step stay with the
+ *      slot, so copies of one particle diverge at their next momentum draw.
+ *   4. beta, U0 and g of every row of the neuron from the kept parts at the new beta (no evaluation), step of the row =
+ *      the neuron's.  beta = 1: done, no move follows.  Else n_steps transitions under the new target.
+ * A done neuron never changes again: stage returns at once for it, and in the moves a row of a done neuron draws nothing,
+ * moves nothing, advances no t, adds no acceptance and writes its current q to d_Xt.  Active rows have the bits of the
+ * pgl_ais_* kernels on the same state.
+ * d_smc: ONE device block of pgl_smc_state_doubles(K, M, P, S) doubles, S = the stage records kept per neuron, in this order:
+ *   (M) each:      beta, log_Z, step, stage (completed stages), done, n_resampled, acc (acceptances the last stage summed),
+ *                  live (the last stage call changed the neuron's rows), rs (it resampled), ess (before that resampling);
+ *   (S, M) each:   records of stage s: beta after it, ESS before resampling, CESS, resampled (0 / 1), accept rate of the moves
+ *                  that followed (NaN where none did), the step they ran on; NaN beyond a neuron's last stage;
+ *   (R) each:      anc (ancestor particle of every row in the last stage), w (normalised weights after the last stage's update,
+ *                  before its resampling), acc (acceptances of every row since the last stage);
+ *   (1):           n_active, the neurons not done after the last stage call -- the one number a driver reads per stage;
+ *   scratch:       (R, P), (R, P), (2, R): q, gll and ll0, lp0 on their way between slots.
+ *   init:   pgl_ais_init_dev with particle0 = 0, and the start of d_smc (every step = step0).  Then pgl_ais_start_dev.
+ *   stage:  steps 0 to 4 for every neuron, three launches: one workgroup per neuron (any K >= 1), then two of one workgroup
+ *           per row (gather into scratch, scatter and retemper).  f64, no atomics, fixed summation order.
+ *   gather: the last two launches of stage on their own, by what d_smc holds: a neuron with live != 0 is retempered to its
+ *           beta and step, and where rs != 0 slot k first takes the kept parts of slot anc[k]; n_active is counted.
+ *   begin / leap, dense_begin / dense_leap: pgl_ais_begin_dev / _leap_dev / pgl_ais_dense_begin_dev / _dense_leap_dev with
+ *           adapt = 0, the guard above, and the decisions added into d_smc's acc. */
+long long pgl_smc_state_doubles(int K, int M, int P, int S);
+int pgl_smc_init_dev(pgl_handle h, double* d_state, double* d_smc, int K, int M, int P, int S, int n_lo, const pgl_prior* prior,
+                     double step0, uint64_t seed, double* d_Xt);
+int pgl_smc_stage_dev(pgl_handle h, double* d_state, double* d_smc, int K, int M, int P, int S, const pgl_prior* prior,
+                      int n_steps, double cess, double ess_min, double delta_min, uint64_t seed);
+int pgl_smc_gather_dev(pgl_handle h, double* d_state, double* d_smc, int K, int M, int P, int S, const pgl_prior* prior);
+int pgl_smc_begin_dev(pgl_handle h, double* d_state, double* d_smc, int K, int M, int P, int S, const double* d_minv,
+                      double* d_Xt);
+int pgl_smc_leap_dev(pgl_handle h, double* d_state, double* d_smc, int K, int M, int P, int S, const double* d_minv,
+                     const double* d_ll, const double* d_grad, const pgl_prior* prior, int last, double* d_Xt);
+int pgl_smc_dense_begin_dev(pgl_handle h, double* d_state, double* d_smc, int K, int M, int P, int S, const double* d_W,
+                            double* d_Xt);
+int pgl_smc_dense_leap_dev(pgl_handle h, double* d_state, double* d_smc, int K, int M, int P, int S, const double* d_W,
+                           const double* d_ll, const double* d_grad, const pgl_prior* prior, int last, double* d_Xt);
 
 /* Lock-step accelerated proximal gradient for the group-lasso MAP (inference/batched_prox.py) as row kernels on the
  * handle's stream: the theta rows [bias, w_stim (Ds), w_ir (N groups of B)] of M neurons n_lo .. n_lo + M - 1 at once, one

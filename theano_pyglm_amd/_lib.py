@@ -46,6 +46,8 @@ SYMBOLS = [
     'pgl_ais_state_doubles', 'pgl_ais_init_dev', 'pgl_ais_start_dev', 'pgl_ais_temper_dev', 'pgl_ais_begin_dev',
     'pgl_ais_leap_dev',
     'pgl_tri_matvec_shared_dev', 'pgl_ais_dense_begin_dev', 'pgl_ais_dense_leap_dev',
+    'pgl_smc_state_doubles', 'pgl_smc_init_dev', 'pgl_smc_stage_dev', 'pgl_smc_gather_dev', 'pgl_smc_begin_dev', 'pgl_smc_leap_dev',
+    'pgl_smc_dense_begin_dev', 'pgl_smc_dense_leap_dev',
     'pgl_hess_dev', 'pgl_hess',
     'pgl_chol_factor_dev', 'pgl_tri_inverse_dev',
     'pgl_rescale_count', 'pgl_rescale_dev', 'pgl_rescale',
@@ -53,7 +55,7 @@ SYMBOLS = [
 ]
 
 
-ABI_VERSION = 107                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
+ABI_VERSION = 108                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
 
 
 class PglError(RuntimeError):
@@ -219,6 +221,15 @@ def load():
     lib.pgl_tri_matvec_shared_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     lib.pgl_ais_dense_begin_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     lib.pgl_ais_dense_leap_dev.argtypes = kmp + [vp, vp, vp, pr, C.c_int, C.c_int, vp, vp, vp]
+    lib.pgl_smc_state_doubles.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    smc = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.pgl_smc_init_dev.argtypes = smc + [C.c_int, pr, C.c_double, C.c_uint64, vp]
+    lib.pgl_smc_stage_dev.argtypes = smc + [pr, C.c_int, C.c_double, C.c_double, C.c_double, C.c_uint64]
+    lib.pgl_smc_gather_dev.argtypes = smc + [pr]
+    lib.pgl_smc_begin_dev.argtypes = smc + [vp, vp]
+    lib.pgl_smc_leap_dev.argtypes = smc + [vp, vp, vp, pr, C.c_int, vp]
+    lib.pgl_smc_dense_begin_dev.argtypes = smc + [vp, vp]
+    lib.pgl_smc_dense_leap_dev.argtypes = smc + [vp, vp, vp, pr, C.c_int, vp]
     lib.pgl_prox_state_doubles.argtypes = [C.c_int, C.c_int]
     prox = [vp, vp, C.c_int, C.c_int, vp, vp, pr, vp, C.c_double, C.c_int]
     lib.pgl_prox_init_dev.argtypes = prox + [vp, vp]
@@ -251,7 +262,7 @@ def load():
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name in ('pgl_bfgs_state_doubles', 'pgl_ncg_state_doubles', 'pgl_hmc_state_doubles', 'pgl_ais_state_doubles',
-                    'pgl_prox_state_doubles', 'pgl_nuts_state_doubles', 'pgl_adapt_state_doubles'):
+                    'pgl_prox_state_doubles', 'pgl_nuts_state_doubles', 'pgl_adapt_state_doubles', 'pgl_smc_state_doubles'):
             fn.restype = C.c_longlong
         elif name not in ('pgl_last_error',):
             fn.restype = C.c_int
@@ -813,6 +824,42 @@ class DeviceGlm(object):
                                              C.c_void_p(d_ll), C.c_void_p(d_grad), C.byref(as_prior(prior)),
                                              1 if last else 0, 1 if adapt else 0, C.c_void_p(d_Xt), vp(d_acc_out),
                                              vp(d_step_out)))
+
+    # -- adaptive sequential Monte Carlo on the AIS rows (pgl_smc_*; inference/batched_smc.py): d_state the AIS block of
+    # K M rows, d_smc the per-neuron block of smc_state_doubles(K, M, P, S) doubles, S the number of stage records
+    def smc_state_doubles(self, K, M, P, S):
+        return int(self.lib.pgl_smc_state_doubles(int(K), int(M), int(P), int(S)))
+
+    def _smc(self, d_state, d_smc, K, M, P, S):
+        return (self.h, C.c_void_p(d_state), C.c_void_p(d_smc), int(K), int(M), int(P), int(S))
+
+    def smc_init_dev(self, d_state, d_smc, K, M, P, S, n_lo, prior, step0, seed, d_Xt):
+        _chk(self.lib.pgl_smc_init_dev(*self._smc(d_state, d_smc, K, M, P, S), int(n_lo), C.byref(as_prior(prior)),
+                                       float(step0), int(seed) & 0xffffffffffffffff, C.c_void_p(d_Xt)))
+
+    def smc_stage_dev(self, d_state, d_smc, K, M, P, S, prior, n_steps, cess, ess_min, delta_min, seed):
+        _chk(self.lib.pgl_smc_stage_dev(*self._smc(d_state, d_smc, K, M, P, S), C.byref(as_prior(prior)), int(n_steps),
+                                        float(cess), float(ess_min), float(delta_min), int(seed) & 0xffffffffffffffff))
+
+    def smc_gather_dev(self, d_state, d_smc, K, M, P, S, prior):
+        _chk(self.lib.pgl_smc_gather_dev(*self._smc(d_state, d_smc, K, M, P, S), C.byref(as_prior(prior))))
+
+    def smc_begin_dev(self, d_state, d_smc, K, M, P, S, d_minv, d_Xt):
+        _chk(self.lib.pgl_smc_begin_dev(*self._smc(d_state, d_smc, K, M, P, S), C.c_void_p(d_minv) if d_minv else None,
+                                        C.c_void_p(d_Xt)))
+
+    def smc_leap_dev(self, d_state, d_smc, K, M, P, S, d_minv, d_ll, d_grad, prior, last, d_Xt):
+        _chk(self.lib.pgl_smc_leap_dev(*self._smc(d_state, d_smc, K, M, P, S), C.c_void_p(d_minv) if d_minv else None,
+                                       C.c_void_p(d_ll), C.c_void_p(d_grad), C.byref(as_prior(prior)), 1 if last else 0,
+                                       C.c_void_p(d_Xt)))
+
+    def smc_dense_begin_dev(self, d_state, d_smc, K, M, P, S, d_W, d_Xt):
+        _chk(self.lib.pgl_smc_dense_begin_dev(*self._smc(d_state, d_smc, K, M, P, S), C.c_void_p(d_W), C.c_void_p(d_Xt)))
+
+    def smc_dense_leap_dev(self, d_state, d_smc, K, M, P, S, d_W, d_ll, d_grad, prior, last, d_Xt):
+        _chk(self.lib.pgl_smc_dense_leap_dev(*self._smc(d_state, d_smc, K, M, P, S), C.c_void_p(d_W), C.c_void_p(d_ll),
+                                             C.c_void_p(d_grad), C.byref(as_prior(prior)), 1 if last else 0,
+                                             C.c_void_p(d_Xt)))
 
     def sync(self):
         _chk(self.lib.pgl_sync(self.h))

@@ -169,15 +169,22 @@ __device__ __forceinline__ void pgl_ais_finish_row(const AisView& v, const int r
 // last == 0: full kick, next drift, Xt[row] = the next point.  last != 0: half kick, H1, the decision (on accept ll, the
 // log prior, grad ll and grad U of the new point are kept), the step-size rule if adapt, t += 1; acc_out[row] += the
 // decision and step_out[row] = the row's step after it (null: none).
-__global__ __launch_bounds__(256) void k_ais_leap(const AisView v, const double* __restrict__ minv, const double* __restrict__ ll,
-                                                  const double* __restrict__ grad, const BfgsPrior q, const int last,
-                                                  const int adapt, double* __restrict__ Xt, double* __restrict__ acc_out,
-                                                  double* __restrict__ step_out)
+// GUARD (k_smc_leap, pglm_smc.hip.h): done (M), one flag per neuron; a row of a done neuron moves nothing, advances no t and
+// (last == 0) writes its current q to Xt.
+template <int GUARD>
+__device__ __forceinline__ void pgl_ais_leap_row(const AisView& v, const double* __restrict__ minv, const double* __restrict__ ll,
+                                                 const double* __restrict__ grad, const BfgsPrior& q, const int last,
+                                                 const int adapt, double* __restrict__ Xt, double* __restrict__ acc_out,
+                                                 double* __restrict__ step_out, const double* __restrict__ done, double* red,
+                                                 int* dec)
 {
-    __shared__ double red[12];
-    __shared__ int dec;
     const int r = blockIdx.x, tid = threadIdx.x, P = v.P;
     const size_t o = (size_t)r * P, om = (size_t)(r % v.M) * P;
+    if (GUARD && done[r % v.M] != 0.0) {
+        if (!last)
+            for (int c = tid; c < P; c += 256) Xt[o + c] = v.q[o + c];
+        return;
+    }
     const double beta = v.sc[(size_t)12 * v.R + r];
     const double lp1 = pgl_ais_target_row(v.q + o, grad + o, v.gu + o, beta, q, red, tid);
     __syncthreads();                                                           // grad U of the row is in memory
@@ -194,5 +201,14 @@ __global__ __launch_bounds__(256) void k_ais_leap(const AisView v, const double*
         return;
     }
     const double ks = pgl_hmc_end_kinetic<0>(v.p + o, v.gu + o, minv ? minv + om : nullptr, step, P, red, tid);
-    pgl_ais_finish_row(v, r, ll[r], lp1, ks, grad + o, adapt, acc_out, step_out, &dec, tid);
+    pgl_ais_finish_row(v, r, ll[r], lp1, ks, grad + o, adapt, acc_out, step_out, dec, tid);
+}
+__global__ __launch_bounds__(256) void k_ais_leap(const AisView v, const double* __restrict__ minv, const double* __restrict__ ll,
+                                                  const double* __restrict__ grad, const BfgsPrior q, const int last,
+                                                  const int adapt, double* __restrict__ Xt, double* __restrict__ acc_out,
+                                                  double* __restrict__ step_out)
+{
+    __shared__ double red[12];
+    __shared__ int dec;
+    pgl_ais_leap_row<0>(v, minv, ll, grad, q, last, adapt, Xt, acc_out, step_out, nullptr, red, &dec);
 }

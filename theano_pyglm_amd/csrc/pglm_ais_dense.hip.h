@@ -24,15 +24,30 @@
 // sets per workgroup in LDS; K > KC is a loop over chunks of KC particles inside the workgroup (W then comes from cache
 // once per further chunk).  A chunk's missing particles (K not a multiple of KC) recompute the chunk's first and store
 // nothing.  step (K M): one per row.  EPI as k_tri_matvec.
-template <int TRANS, int EPI, int KC>
-__global__ __launch_bounds__(256) void k_tri_matvec_shared(const double* __restrict__ W, const double* __restrict__ x, const int K,
+// GUARD (k_smc_tri_matvec_shared, pglm_smc.hip.h): done (M), one flag per neuron; the workgroups of a done neuron compute
+// nothing -- KICK leaves y as it is, DRIFT leaves y as it is and copies it to Xt.
+template <int TRANS, int EPI, int KC, int GUARD>
+__device__ __forceinline__ void pgl_tri_matvec_shared_body(const double* __restrict__ W, const double* __restrict__ x, const int K,
                                                            const int M, const int P, double* __restrict__ y,
                                                            double* __restrict__ Xt, const double* __restrict__ step,
-                                                           const double scale)
+                                                           const double scale, const double* __restrict__ done,
+                                                           double (*part)[TRANS ? 4 : 1][PGL_TRI_TILE])
 {
     constexpr int NW = TRANS ? 4 : 1;
-    __shared__ double part[KC][NW][PGL_TRI_TILE];
     const int m = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (GUARD && done[m] != 0.0) {
+        if (EPI == PGL_TRI_DRIFT) {
+            const int ntile = (P + PGL_TRI_TILE - 1) / PGL_TRI_TILE;
+            for (int tile = blockIdx.x; tile < ntile; tile += gridDim.x)
+                for (int e = tid; e < K * PGL_TRI_TILE; e += 256) {
+                    const int c = tile * PGL_TRI_TILE + e % PGL_TRI_TILE;
+                    if (c >= P) continue;
+                    const size_t o = ((size_t)(e / PGL_TRI_TILE) * M + m) * P;
+                    Xt[o + c] = y[o + c];
+                }
+        }
+        return;
+    }
     const double* Wr = W + (size_t)m * P * P;
     const int ntile = (P + PGL_TRI_TILE - 1) / PGL_TRI_TILE;
     for (int tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
@@ -99,29 +114,52 @@ __global__ __launch_bounds__(256) void k_tri_matvec_shared(const double* __restr
         }
     }
 }
+template <int TRANS, int EPI, int KC>
+__global__ __launch_bounds__(256) void k_tri_matvec_shared(const double* __restrict__ W, const double* __restrict__ x, const int K,
+                                                           const int M, const int P, double* __restrict__ y,
+                                                           double* __restrict__ Xt, const double* __restrict__ step,
+                                                           const double scale)
+{
+    __shared__ double part[KC][TRANS ? 4 : 1][PGL_TRI_TILE];
+    pgl_tri_matvec_shared_body<TRANS, EPI, KC, 0>(W, x, K, M, P, y, Xt, step, scale, nullptr, part);
+}
 
 // after the evaluation of all rows at Xt = q: gu = grad U_beta along the trajectory from grad = grad ll (left as it is);
 // the kick's product reads gu next
-__global__ __launch_bounds__(256) void k_ais_dense_target(const AisView v, const double* __restrict__ grad, const BfgsPrior q)
+// (the row bodies of this kernel and the next are shared with their guarded forms, k_smc_dense_target / _end of
+// pglm_smc.hip.h, which pass the rows of a done neuron by)
+__device__ __forceinline__ void pgl_ais_dense_target_row(const AisView& v, const double* __restrict__ grad, const BfgsPrior& q,
+                                                         double* red)
 {
-    __shared__ double red[12];
     const int r = blockIdx.x, tid = threadIdx.x;
     const size_t o = (size_t)r * v.P;
     pgl_ais_target_row(v.q + o, grad + o, v.gu + o, v.sc[(size_t)12 * v.R + r], q, red, tid);
 }
+__global__ __launch_bounds__(256) void k_ais_dense_target(const AisView v, const double* __restrict__ grad, const BfgsPrior q)
+{
+    __shared__ double red[12];
+    pgl_ais_dense_target_row(v, grad, q, red);
+}
 
 // end of a transition, after the last half kick: H1 from ll[row], the log prior at q (summed again, as k_ais_dense_target
 // summed it: gu is rewritten with the same bits) and r, then pgl_ais_finish_row as the last branch of k_ais_leap
+__device__ __forceinline__ void pgl_ais_dense_end_row(const AisView& v, const double* __restrict__ ll,
+                                                      const double* __restrict__ grad, const BfgsPrior& q, const int adapt,
+                                                      double* __restrict__ acc_out, double* __restrict__ step_out, double* red,
+                                                      int* dec)
+{
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const size_t o = (size_t)r * v.P;
+    const double lp1 = pgl_ais_target_row(v.q + o, grad + o, v.gu + o, v.sc[(size_t)12 * v.R + r], q, red, tid);
+    __syncthreads();                                                           // red is free, gu of the row is in memory
+    const double ks = pgl_hmc_end_kinetic<1>(v.p + o, nullptr, nullptr, 0.0, v.P, red, tid);
+    pgl_ais_finish_row(v, r, ll[r], lp1, ks, grad + o, adapt, acc_out, step_out, dec, tid);
+}
 __global__ __launch_bounds__(256) void k_ais_dense_end(const AisView v, const double* __restrict__ ll,
                                                        const double* __restrict__ grad, const BfgsPrior q, const int adapt,
                                                        double* __restrict__ acc_out, double* __restrict__ step_out)
 {
     __shared__ double red[12];
     __shared__ int dec;
-    const int r = blockIdx.x, tid = threadIdx.x;
-    const size_t o = (size_t)r * v.P;
-    const double lp1 = pgl_ais_target_row(v.q + o, grad + o, v.gu + o, v.sc[(size_t)12 * v.R + r], q, red, tid);
-    __syncthreads();                                                           // red is free, gu of the row is in memory
-    const double ks = pgl_hmc_end_kinetic<1>(v.p + o, nullptr, nullptr, 0.0, v.P, red, tid);
-    pgl_ais_finish_row(v, r, ll[r], lp1, ks, grad + o, adapt, acc_out, step_out, &dec, tid);
+    pgl_ais_dense_end_row(v, ll, grad, q, adapt, acc_out, step_out, red, &dec);
 }

@@ -527,12 +527,19 @@ int pgl_ais_leap_dev(pgl_handle h, double* d_state, int K, int M, int P, const d
 
 // ---- annealed importance sampling with a dense mass matrix (inference/batched_ais.py: mass = (M, P, P) or 'laplace_dense') ---
 // one shared product launch: the particles of a neuron meet the neuron's W in one workgroup, KC at a time
+// (d_done: the guarded form of the sequential Monte Carlo moves, one flag per neuron; null: the plain kernel.  Two
+// instantiations per (TRANS, EPI, KC), chosen here, rather than one kernel with a nullable flag pointer: the plain kernel keeps
+// the registers and the bits it had before the guard existed, at the price of a second copy in the code object.)
 static int tri_shared_launch(pgl_handle h, int trans, int epi, const double* d_W, int K, int M, int P, const double* d_x,
-                             double* d_y, double* d_Xt, const double* d_step, double scale)
+                             double* d_y, double* d_Xt, const double* d_step, double scale, const double* d_done = nullptr)
 {
     if (M > 65535) return fail(PGL_ERR_ARG, "at most 65535 neurons per call");
     const dim3 grid((P + PGL_TRI_TILE - 1) / PGL_TRI_TILE, M);
-#define PGL_TRI_LAUNCH(T, E, KC) hipLaunchKernelGGL((k_tri_matvec_shared<T, E, KC>), grid, dim3(256), 0, h->stream, d_W, d_x, K, M, P, d_y, d_Xt, d_step, scale)
+#define PGL_TRI_LAUNCH(T, E, KC)                                                                                               \
+    do {                                                                                                                       \
+        if (d_done) hipLaunchKernelGGL((k_smc_tri_matvec_shared<T, E, KC>), grid, dim3(256), 0, h->stream, d_W, d_x, K, M, P, d_y, d_Xt, d_step, scale, d_done); \
+        else hipLaunchKernelGGL((k_tri_matvec_shared<T, E, KC>), grid, dim3(256), 0, h->stream, d_W, d_x, K, M, P, d_y, d_Xt, d_step, scale); \
+    } while (0)
     if (K == 1) PGL_TRI_DISPATCH(PGL_TRI_LAUNCH, 1);
     else if (K == 2) PGL_TRI_DISPATCH(PGL_TRI_LAUNCH, 2);
     else if (K <= 4) PGL_TRI_DISPATCH(PGL_TRI_LAUNCH, 4);
@@ -581,6 +588,129 @@ int pgl_ais_dense_leap_dev(pgl_handle h, double* d_state, int K, int M, int P, c
     if (rc) return rc;
     if (!last) return tri_shared_launch(h, 0, PGL_TRI_DRIFT, d_W, K, M, P, v.p, v.q, d_Xt, step, 1.0);
     return launch_rows(h, k_ais_dense_end, K * M, v, d_ll, d_grad, q, adapt ? 1 : 0, d_acc_out, d_step_out);
+}
+
+// ---- adaptive sequential Monte Carlo of the evidence (inference/batched_smc.py) ----------------------------------------
+long long pgl_smc_state_doubles(int K, int M, int P, int S)
+{
+    if (K <= 0 || M <= 0 || P <= 0 || S <= 0) return 0;
+    return (long long)pgl_smc_doubles((size_t)K, (size_t)M, (size_t)P, (size_t)S);
+}
+
+static int smc_args(pgl_handle h, const double* d_state, const double* d_smc, int S)
+{
+    if (!h || !d_state || !d_smc || S <= 0) return fail(PGL_ERR_ARG, "bad argument");
+    return PGL_OK;
+}
+
+int pgl_smc_init_dev(pgl_handle h, double* d_state, double* d_smc, int K, int M, int P, int S, int n_lo, const pgl_prior* prior,
+                     double step0, uint64_t seed, double* d_Xt)
+{
+    int rc = smc_args(h, d_state, d_smc, S);
+    if (rc) return rc;
+    rc = pgl_ais_init_dev(h, d_state, K, M, P, n_lo, 0, prior, step0, seed, d_Xt);
+    if (rc) return rc;
+    return launch_rows(h, k_smc_init, M, pgl_smc_view(d_smc, K, M, P, S), step0);
+}
+
+// the second half of a stage on its own: gather and retemper by the block's anc, live, rs, beta and step as they stand
+int pgl_smc_gather_dev(pgl_handle h, double* d_state, double* d_smc, int K, int M, int P, int S, const pgl_prior* prior)
+{
+    int rc = smc_args(h, d_state, d_smc, S);
+    if (rc) return rc;
+    BfgsPrior q;
+    rc = ais_prior(h, K, M, P, prior, q);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    const AisView v = pgl_ais_view(d_state, K, M, P);
+    const SmcView m = pgl_smc_view(d_smc, K, M, P, S);
+    rc = launch_rows(h, k_smc_gather, K * M, v, m);
+    if (rc) return rc;
+    return launch_rows(h, k_smc_retemper, K * M, v, m, q);
+}
+
+int pgl_smc_stage_dev(pgl_handle h, double* d_state, double* d_smc, int K, int M, int P, int S, const pgl_prior* prior,
+                      int n_steps, double cess, double ess_min, double delta_min, uint64_t seed)
+{
+    int rc = smc_args(h, d_state, d_smc, S);
+    if (rc) return rc;
+    if (n_steps <= 0 || !(cess > 0.0 && cess < 1.0) || !(ess_min >= 0.0 && ess_min <= 1.0) || !(delta_min > 0.0 && delta_min <= 1.0))
+        return fail(PGL_ERR_ARG, "n_steps positive, cess in (0, 1), ess_min in [0, 1], delta_min in (0, 1]");
+    BfgsPrior q;
+    rc = ais_prior(h, K, M, P, prior, q);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    const AisView v = pgl_ais_view(d_state, K, M, P);
+    const SmcView m = pgl_smc_view(d_smc, K, M, P, S);
+    rc = launch_rows(h, k_smc_stage, M, v, m, n_steps, cess, ess_min, delta_min, (unsigned long long)seed);
+    if (rc) return rc;
+    return pgl_smc_gather_dev(h, d_state, d_smc, K, M, P, S, prior);
+}
+
+int pgl_smc_begin_dev(pgl_handle h, double* d_state, double* d_smc, int K, int M, int P, int S, const double* d_minv,
+                      double* d_Xt)
+{
+    int rc = smc_args(h, d_state, d_smc, S);
+    if (rc) return rc;
+    if (!d_Xt || K <= 0 || M <= 0 || P <= 0 || (long long)K * M > 0x7fffffffLL) return fail(PGL_ERR_ARG, "bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    const SmcView m = pgl_smc_view(d_smc, K, M, P, S);
+    return launch_rows(h, k_smc_begin, K * M, pgl_ais_hmc_view(pgl_ais_view(d_state, K, M, P)), d_minv, M, d_Xt,
+                       m.sc + (size_t)PGL_SMC_F_DONE * M);
+}
+
+int pgl_smc_leap_dev(pgl_handle h, double* d_state, double* d_smc, int K, int M, int P, int S, const double* d_minv,
+                     const double* d_ll, const double* d_grad, const pgl_prior* prior, int last, double* d_Xt)
+{
+    int rc = smc_args(h, d_state, d_smc, S);
+    if (rc) return rc;
+    if (!d_ll || !d_grad || !d_Xt) return fail(PGL_ERR_ARG, "bad argument");
+    BfgsPrior q;
+    rc = ais_prior(h, K, M, P, prior, q);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    const SmcView m = pgl_smc_view(d_smc, K, M, P, S);
+    return launch_rows(h, k_smc_leap, K * M, pgl_ais_view(d_state, K, M, P), d_minv, d_ll, d_grad, q, last ? 1 : 0, d_Xt, m.acc,
+                       m.sc + (size_t)PGL_SMC_F_DONE * M);
+}
+
+int pgl_smc_dense_begin_dev(pgl_handle h, double* d_state, double* d_smc, int K, int M, int P, int S, const double* d_W,
+                            double* d_Xt)
+{
+    int rc = smc_args(h, d_state, d_smc, S);
+    if (rc) return rc;
+    if (!d_W || !d_Xt || K <= 0 || M <= 0 || P <= 0 || (long long)K * M > 0x7fffffffLL) return fail(PGL_ERR_ARG, "bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    const AisView v = pgl_ais_view(d_state, K, M, P);
+    const double* done = pgl_smc_view(d_smc, K, M, P, S).sc + (size_t)PGL_SMC_F_DONE * M;
+    rc = launch_rows(h, k_smc_dense_draw, K * M, pgl_ais_hmc_view(v), done, M);
+    if (rc) return rc;
+    const double* step = v.sc + (size_t)2 * v.R;
+    rc = tri_shared_launch(h, 1, PGL_TRI_KICK, d_W, K, M, P, v.g, v.p, nullptr, step, 0.5, done);
+    if (rc) return rc;
+    return tri_shared_launch(h, 0, PGL_TRI_DRIFT, d_W, K, M, P, v.p, v.q, d_Xt, step, 1.0, done);
+}
+
+int pgl_smc_dense_leap_dev(pgl_handle h, double* d_state, double* d_smc, int K, int M, int P, int S, const double* d_W,
+                           const double* d_ll, const double* d_grad, const pgl_prior* prior, int last, double* d_Xt)
+{
+    int rc = smc_args(h, d_state, d_smc, S);
+    if (rc) return rc;
+    if (!d_W || !d_ll || !d_grad || !d_Xt) return fail(PGL_ERR_ARG, "bad argument");
+    BfgsPrior q;
+    rc = ais_prior(h, K, M, P, prior, q);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    const AisView v = pgl_ais_view(d_state, K, M, P);
+    const SmcView m = pgl_smc_view(d_smc, K, M, P, S);
+    const double* done = m.sc + (size_t)PGL_SMC_F_DONE * M;
+    rc = launch_rows(h, k_smc_dense_target, K * M, v, d_grad, q, done);
+    if (rc) return rc;
+    const double* step = v.sc + (size_t)2 * v.R;
+    rc = tri_shared_launch(h, 1, PGL_TRI_KICK, d_W, K, M, P, v.gu, v.p, nullptr, step, last ? 0.5 : 1.0, done);
+    if (rc) return rc;
+    if (!last) return tri_shared_launch(h, 0, PGL_TRI_DRIFT, d_W, K, M, P, v.p, v.q, d_Xt, step, 1.0, done);
+    return launch_rows(h, k_smc_dense_end, K * M, v, d_ll, d_grad, q, m.acc, done);
 }
 
 // ---- lock-step proximal gradient row kernels for the group-lasso MAP (inference/batched_prox.py) -------------------------

@@ -94,13 +94,19 @@ __global__ __launch_bounds__(256) void k_hmc_init(const HmcView v, double* __res
 
 // start of a transition: momentum, H0, the half kick with grad U at q, the first drift; Xt[row] = the point to evaluate.
 // minv (minv_rows, P): row r runs on row r mod minv_rows (the chain: minv_rows = M; the K M rows of an annealed importance
-// sampling run, particle-major, share the M rows of their neurons)
-__global__ __launch_bounds__(256) void k_hmc_begin(const HmcView v, const double* __restrict__ minv, const int minv_rows,
-                                                   double* __restrict__ Xt)
+// sampling run, particle-major, share the M rows of their neurons).
+// GUARD (k_smc_begin, pglm_smc.hip.h): done (minv_rows), one flag per neuron; a row of a done neuron draws nothing, moves
+// nothing and writes its current q to Xt.
+template <int GUARD>
+__device__ __forceinline__ void pgl_hmc_begin_row(const HmcView& v, const double* __restrict__ minv, const int minv_rows,
+                                                  double* __restrict__ Xt, const double* __restrict__ done, double* red)
 {
-    __shared__ double red[12];
     const int r = blockIdx.x, tid = threadIdx.x, P = v.P;
     const size_t o = (size_t)r * P, om = (size_t)(r % minv_rows) * P;
+    if (GUARD && done[r % minv_rows] != 0.0) {
+        for (int c = tid; c < P; c += 256) Xt[o + c] = v.q[o + c];
+        return;
+    }
     PglHmc s;
     pgl_hmc_load(v, r, &s);
     const pgl_hmc_u64 key = pgl_hmc_row_key(&s);
@@ -122,6 +128,12 @@ __global__ __launch_bounds__(256) void k_hmc_begin(const HmcView v, const double
         pgl_hmc_begin(&s, ks);
         v.sc[(size_t)1 * v.M + r] = s.H0;
     }
+}
+__global__ __launch_bounds__(256) void k_hmc_begin(const HmcView v, const double* __restrict__ minv, const int minv_rows,
+                                                   double* __restrict__ Xt)
+{
+    __shared__ double red[12];
+    pgl_hmc_begin_row<0>(v, minv, minv_rows, Xt, nullptr, red);
 }
 
 // ---- the end of a transition, shared by the diagonal and the dense kernels of the chain and of annealed importance sampling ----

@@ -68,11 +68,15 @@ __global__ __launch_bounds__(256) void k_tri_matvec(const double* __restrict__ W
 
 // start of a transition: the momentum r = z (the draws of k_hmc_begin), H0, q0 = q.  The half kick and the first drift
 // are the two product launches behind it.
-__global__ __launch_bounds__(256) void k_hmc_dense_draw(const HmcView v)
+// GUARD (k_smc_dense_draw, pglm_smc.hip.h): done (n_done), one flag per neuron, row r belongs to neuron r mod n_done; a row
+// of a done neuron is passed by.
+template <int GUARD>
+__device__ __forceinline__ void pgl_hmc_dense_draw_row(const HmcView& v, const double* __restrict__ done, const int n_done,
+                                                       double* red)
 {
-    __shared__ double red[12];
     const int r = blockIdx.x, tid = threadIdx.x, P = v.P;
     const size_t o = (size_t)r * P;
+    if (GUARD && done[r % n_done] != 0.0) return;
     PglHmc s;
     pgl_hmc_load(v, r, &s);
     const pgl_hmc_u64 key = pgl_hmc_row_key(&s);
@@ -88,6 +92,11 @@ __global__ __launch_bounds__(256) void k_hmc_dense_draw(const HmcView v)
         pgl_hmc_begin(&s, ks);
         v.sc[(size_t)1 * v.M + r] = s.H0;
     }
+}
+__global__ __launch_bounds__(256) void k_hmc_dense_draw(const HmcView v)
+{
+    __shared__ double red[12];
+    pgl_hmc_dense_draw_row<0>(v, nullptr, 1, red);
 }
 
 // after ONE evaluation of all rows at Xt = q: (ll, grad) -> U, grad U in place (the kick's product reads grad U next)

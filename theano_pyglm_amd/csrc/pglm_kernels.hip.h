@@ -27,6 +27,8 @@
 // pglm_chol.hip.h).
 // The per-neuron evidence comes from annealed importance sampling on the same moves (k_ais_*, pglm_ais.hip.h).
 // Its dense mass shares one read of a neuron's factor among the neuron's particles (k_tri_matvec_shared, pglm_ais_dense.hip.h).
+// Adaptive sequential Monte Carlo walks the same tempered path with per-neuron ladders and resampling on the device (k_smc_*,
+// pglm_smc.hip.h).
 // The group-lasso MAP runs accelerated proximal gradient fits of all neurons in lock step around the same launch (k_prox_*,
 // pglm_prox.hip.h).
 // Simulation produces spikes instead of reading them: one workgroup per replicate runs the time loop (k_simulate,
@@ -52,6 +54,7 @@
 #include "pglm_chol.hip.h"
 #include "pglm_ais.hip.h"
 #include "pglm_ais_dense.hip.h"
+#include "pglm_smc.hip.h"
 #include "pglm_prox.hip.h"
 #include "pglm_rescale.hip.h"
 #include "pglm_simulate.hip.h"

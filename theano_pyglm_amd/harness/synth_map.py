@@ -18,6 +18,8 @@ plus the median tree depth and the divergent transitions per neuron.
 --ais K estimates every neuron's log evidence given the network from the fit by annealed importance sampling with K
 particles on the device (inference/batched_ais.py; Gaussian impulse priors only) and prints log_Z + log_prior_norm +- se, the
 ESS and the Laplace log evidence beside it.
+--smc K does the same by adaptive sequential Monte Carlo (inference/batched_smc.py; --ais-mass applies): the table of --ais
+without a standard error (one run gives none), plus the stages and the resamplings of every neuron.
 """
 import argparse
 import os
@@ -47,7 +49,7 @@ def initialize_test_harness(model_name, data, data_dir=None):
 
 
 def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False, gof=False, ppc=0, hmc=0, ais=0,
-                   hmc_mass='laplace', prox=False, laplace_device=False, ais_mass='laplace', nuts=0):
+                   hmc_mass='laplace', prox=False, laplace_device=False, ais_mass='laplace', nuts=0, smc=0):
     """test/synth_map.py:10-32."""
     popn, popn_true, x_true = initialize_test_harness(model_name, data, data_dir)
     x0 = popn.sample(rng)
@@ -74,6 +76,8 @@ def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, r
         print(nuts_bias_table(popn, x_inf, nuts, hmc_mass, laplace_device))
     if ais:
         print(ais_evidence_table(popn, x_inf, ais, laplace_device, ais_mass))
+    if smc:
+        print(smc_evidence_table(popn, x_inf, smc, laplace_device, ais_mass))
     return x_inf, ll_inf, wall
 
 
@@ -164,6 +168,26 @@ def ais_evidence_table(popn, x, n_particles, laplace_device=False, mass='laplace
     return "\n".join(lines)
 
 
+def smc_evidence_table(popn, x, n_particles, laplace_device=False, mass='laplace'):
+    """Adaptive SMC with n_particles particles per neuron from x: one line per neuron, log_Z + log_prior_norm, the ESS of the
+    final weights, the Laplace log evidence, the stages and the resamplings.  No standard error: one run gives none."""
+    from theano_pyglm_amd.inference import batched_smc
+    from theano_pyglm_amd.inference.laplace import laplace_glms
+    t0 = time.time()
+    res = batched_smc.smc_glms(popn, x, n_particles=n_particles, mass=None if mass == 'none' else mass)
+    wall = time.time() - t0
+    lap = [r['log_evidence'] for r in laplace_glms(popn, x, device=laplace_device)]
+    lines = ["SMC%s: %d particles per neuron, up to %d stages in %.2f s (%d ll+grad launches, %.0f %% of row evaluations idle)"
+             % ("" if mass == 'laplace' else " (mass=%s)" % mass, n_particles, res['betas'].shape[0], wall, res['n_evals'],
+                100.0 * res['idle_row_evaluations']),
+             "neuron   log evidence      ESS      Laplace  stages  resampled"]
+    for n in range(popn.N):
+        lines.append("%6d  %13.4f  %6.1f  %11.4f  %6d  %9d%s"
+                     % (n, res['log_Z'][n] + res['log_prior_norm'][n], res['ess'][res['n_stages'][n] - 1, n], lap[n],
+                        res['n_stages'][n], res['n_resampled'][n], "" if res['finished'][n] else "  (unfinished)"))
+    return "\n".join(lines)
+
+
 def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('-m', '--model', default='standard_glm')
@@ -192,6 +216,9 @@ def parser():
     ap.add_argument('--ais', type=int, default=0, metavar='K',
                     help='after the fit: log evidence of every neuron given the network by annealed importance sampling with '
                          'K particles on the device, beside the Laplace log evidence (Gaussian impulse priors only)')
+    ap.add_argument('--smc', type=int, default=0, metavar='K',
+                    help='after the fit: log evidence of every neuron by adaptive sequential Monte Carlo with K particles on the '
+                         'device (per-neuron ladders, resampling; --ais-mass applies), with stages and resamplings per neuron')
     ap.add_argument('--ais-mass', choices=['none', 'laplace', 'laplace_dense'], default='laplace',
                     help="mass matrix of --ais: identity ('none'), 1 / diag A ('laplace') or the tempered dense mass, the factor "
                          "of (beta G + Lambda)^-1 at every temperature ('laplace_dense')")
@@ -207,7 +234,7 @@ def main(argv=None):
         data = pickle.load(f)
     run_synth_test(args.model, data, args.resultsDir, os.path.dirname(args.dataFile),
                    False if args.sequential else ('torch' if args.newton_cg else None), use_rop=args.newton_cg, gof=args.gof, ppc=args.ppc, hmc=args.hmc, ais=args.ais,
-                   hmc_mass=args.hmc_mass, prox=args.prox, laplace_device=args.laplace_device, ais_mass=args.ais_mass, nuts=args.nuts)
+                   hmc_mass=args.hmc_mass, prox=args.prox, laplace_device=args.laplace_device, ais_mass=args.ais_mass, nuts=args.nuts, smc=args.smc)
 
 
 if __name__ == '__main__':

@@ -134,6 +134,38 @@ def _ll_hessians(population, torch, dev, handles, x, n_lo, n_hi, P):
     return G
 
 
+def tempered_factor_rows(G, lam, betas, floor, factor, inverse, xp, eye):
+    """tempered_factor with one temperature per ROW: betas (M,) on G's backend (a device vector is never read back).
+    A_i = betas_i G_i + Lambda, W_i W_i^T = A_i^-1 by the same route, the same fall-back for a row that does not factor.  A
+    row at beta = 0 goes through the factorisation of the diagonal Lambda like any other (W = Lambda^-1/2 within 2 ulp).
+    Returns (W, info (M,))."""
+    from theano_pyglm_amd.inference.laplace import laplace_from_factor
+    b = betas[:, None, None]
+    A = b * G + lam[None, :, None] * eye[None]
+    res = laplace_from_factor(A, factor, inverse, xp)
+    d = betas[:, None] * xp.diagonal(G, 0, 1, 2) + lam[None]
+    d = xp.where(xp.isfinite(d), d, xp.full_like(d, floor))
+    fb = 1.0 / xp.sqrt(xp.where(d > floor, d, xp.full_like(d, floor)))
+    bad = res['info'] != 0
+    return xp.where(bad[:, None, None], fb[:, :, None] * eye[None], res['W']), res['info']
+
+
+def evaluate_particles(handles, bufs, Xt, Weff, K, M, P, n_lo, n_hi, counts):
+    """ll and its gradient of all K M rows of Xt (particle-major): one pgl_ll_grad_dev per particle block -- the (M, P) block
+    of rows k M .. -- and data sequence into that sequence's [ll (R) | grad (R, P)] buffer, summed into the first.
+    counts['ll_grad'] += K.  -> (pointer to ll, pointer to grad).  The loop annealed importance sampling and sequential
+    Monte Carlo share."""
+    R = K * M
+    for h, buf in zip(handles, bufs):
+        for k in range(K):
+            h.ll_grad_dev(Xt[k * M].data_ptr(), Weff.data_ptr(), buf[k * M:].data_ptr(),
+                          buf[R + k * M * P:].data_ptr(), n_lo, n_hi)
+        if buf is not bufs[0]:
+            bufs[0].add_(buf)
+    counts['ll_grad'] += K
+    return bufs[0].data_ptr(), bufs[0][R:].data_ptr()
+
+
 def ais_glms(population, x, n_particles=16, betas=None, n_temps=200, n_steps=1, n_leapfrog=10, step_sz=0.1, pilot=True,
              mass=None, seed=0, particle0=0, n_lo=0, n_hi=None, mass_floor=1e-8):
     """log Z_n = log of the integral of L_n(theta) prior(theta) over the parameter row (bias, w_stim, w_ir) of every neuron
@@ -250,14 +282,7 @@ def _run(population, torch, dev, stream, handles, x, K, betas, n_steps, n_leapfr
         sp = st.data_ptr()
 
         def evaluate():
-            for h, buf in zip(handles, bufs):
-                for k in range(Kr):                           # one launch per particle block: the (M, P) block of rows k M ..
-                    h.ll_grad_dev(Xt[k * M].data_ptr(), Weff.data_ptr(), buf[k * M:].data_ptr(),
-                                  buf[R + k * M * P:].data_ptr(), n_lo, n_hi)
-                if buf is not bufs[0]:
-                    bufs[0].add_(buf)
-            counts['ll_grad'] += Kr
-            return bufs[0].data_ptr(), bufs[0][R:].data_ptr()
+            return evaluate_particles(handles, bufs, Xt, Weff, Kr, M, P, n_lo, n_hi, counts)
 
         h0.ais_init_dev(sp, Kr, M, P, n_lo, part0, prm, step0, seed, Xt.data_ptr())
         ll, g = evaluate()
