@@ -241,6 +241,18 @@ int pgl_hess(pgl_handle h, int n_lo, int n_hi, const double* theta, const double
  * pointer: PGL_ERR_ARG.  The handle supplies device and stream only: no data set is needed. */
 int pgl_chol_factor_dev(pgl_handle h, double* d_A, int M, int P, int ld, double* d_scale, double* d_logdet, int* d_info);
 int pgl_tri_inverse_dev(pgl_handle h, double* d_L, int M, int P, int ld, const int* d_info);
+/* solve against the factor: for every row m with d_info[m] == 0
+ *     x = D^-1/2 Ls^-T Ls^-1 D^-1/2 b = A^-1 b
+ *   with d_Ls (M, P, ld) and d_scale (M, P) exactly as pgl_chol_factor_dev left them (only the lower triangle is read);
+ *   d_b and d_x are (M, P) and may be the same memory.  A row with d_info[m] != 0 gets NaN in x, and nothing else of it is
+ *   read or written.  One workgroup per matrix (k_chol_solve): blocked forward then backward substitution in blocks of 32,
+ *   the diagonal block in LDS and solved in the registers of one wave, the off-diagonal part as a blocked matrix-vector
+ *   product along the rows of Ls; 2 P^2 flops per matrix, where the inverse costs P^3 / 3 and two products.  The result
+ *   satisfies the componentwise bound of a substitution, |Ls y - D^-1/2 b| <= c P u |Ls| |y| and its transpose.
+ *   f64 throughout, no atomics, sums in an order that depends on P alone, asynchronous on the handle's stream; argument
+ *   errors as for the factor. */
+int pgl_chol_solve_dev(pgl_handle h, const double* d_Ls, int M, int P, int ld, const double* d_scale, const int* d_info,
+                       const double* d_b, double* d_x);
 
 /* The lock-step optimiser (inference/batched_bfgs.py) as row kernels on the handle's stream.  The reference calls
  * scipy.optimize.minimize(method="bfgs") neuron by neuron (coord_descent.py:161-204); these run the same algorithm --
@@ -337,6 +349,49 @@ int pgl_ncg_trial_dev(pgl_handle h, double* d_state, int M, int P, const int* d_
 int pgl_ncg_search_step_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, const double* d_Xt,
                             double* d_ll_f, double* d_grad_g, const pgl_prior* prior, int maxiter, const int* d_pos_next,
                             double* d_Xt_next, double* d_V, double* flags_out);
+
+/* Lock-step dense Newton (inference/batched_newton.py) as row kernels on the handle's stream: the reference's default
+ * second-order route (parallel_coord_descent.py:62 use_hessian=True; map.py:38-45) as a line-search Newton method with
+ * Hessian modification (restated in csrc/pglm_newton.h), for all M neurons of a range at once.  Per outer iteration, for
+ * the rows still running: pgl_hvp_prepare_list_dev + pgl_hess_dev (summed over the data sequences), assemble,
+ * pgl_chol_factor_dev, pgl_chol_solve_dev, direction; then one pgl_ll_grad_list_dev of the rows still searching per
+ * line-search trial.  All optimiser state of M rows of P parameters lives in ONE device block of
+ * pgl_newton_state_doubles(M, P) doubles (flags and counters stored as doubles), in this order:
+ *   (M,P) each: X, g, p (the direction), Xb, gb (best trial of the running search);
+ *   (M) each:   f, fprev, slope, alpha, shift, nit, nfev, nhess, nfact, status (-1 running, 0 converged, 1 maxiter, 2 the
+ *               search found no acceptable point, 3 no descent direction), phase (0 needs a Hessian, 1 line search,
+ *               2 finished, 3 refactor: its shift was raised);  then the line-search state, (18, M).
+ * Rows are theta rows [bias, w_stim, w_ir]; the objective is f = -(ll + log prior) with the pgl_prior and fit_glm's NaN
+ * rules (objective NaN -> 1e16, a gradient holding a NaN -> 0), as pgl_ncg_* applies them.  d_rows (L) int32 lists rows of
+ * the state (NULL: row j at position j); everything "by list position" is (L, ..).  flags_out (NULL or M doubles of PINNED
+ * host memory) receives the phase of every row a kernel has advanced.  A finished row is never written again.
+ *   init:        X in the state, (d_ll, d_grad) = ll and gradient at X by row (overwritten with f, g); maxiter <= 0 ends
+ *                every row with status 1, else a row with max|g| <= gtol ends with status 0, else phase 0.
+ *   assemble:    d_H (L, P, ld) holds the sum over the data sequences of the Hessians of ll of the listed rows
+ *                (pgl_hess_dev); its lower triangle becomes A = -H - H_prior(X) + shift diag(-H - H_prior) in place (the
+ *                strict upper triangle is neither read nor written).  H_prior: kind 0 a constant diagonal; kind 1 the
+ *                B x B block of every group, -(lam / sigma) (I / |d| - d d^T / |d|^3), d = w_g - mu: non-finite at a zero
+ *                group, which then fails the factor.  d_rhs (L, P) or NULL: -g of the listed rows, the solve's input.
+ *                The state is read only (X, g, shift).
+ *   direction:   d_info (L) and d_p (L, P) = -(A + shift diag A)^-1 g from factor and solve.  A row whose factor failed or
+ *                whose slope g.p is not negative (or not finite) raises its shift, 0 -> 1e-6 -> x 100 -> .. -> 1e2, and
+ *                goes to phase 3: assemble from the SAME Hessian, factor, solve, direction again -- the Hessian is not
+ *                recomputed, the caller keeps an unshifted copy.  After the last shift the row takes p = -g.  Otherwise
+ *                p = d_p, and the row's More'-Thuente search starts with first step 1 (phase 1).
+ *   trial:       Xt[j] = X[r] + alpha[r] p[r] for a row in phase 1, X[r] for any other (the points of a Hessian list).
+ *   search_step: as pgl_ncg_search_step_dev; a row that takes a point converges when max|g| <= gtol (status 0), stops
+ *                with status 1 when nit == maxiter, else goes back to phase 0 with shift 0; a stuck search: status 2. */
+long long pgl_newton_state_doubles(int M, int P);
+int pgl_newton_init_dev(pgl_handle h, double* d_state, int M, int P, double* d_ll, double* d_grad, const pgl_prior* prior,
+                        double gtol, int maxiter, double* flags_out);
+int pgl_newton_assemble_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, double* d_H, int ld,
+                            const pgl_prior* prior, double* d_rhs);
+int pgl_newton_direction_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, const int* d_info,
+                             const double* d_p, double* flags_out);
+int pgl_newton_trial_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, double* d_Xt);
+int pgl_newton_search_step_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, const double* d_Xt,
+                               double* d_ll_f, double* d_grad_g, const pgl_prior* prior, double gtol, int maxiter,
+                               const int* d_pos_next, double* d_Xt_next, double* flags_out);
 
 /* Lock-step Hamiltonian Monte Carlo (inference/batched_hmc.py) as row kernels on the handle's stream: posterior samples of
  * the theta rows [bias, w_stim, w_ir] of M neurons n_lo .. n_lo + M - 1 at once (C chains each: see "chains" below; every

@@ -49,7 +49,9 @@ SYMBOLS = [
     'pgl_smc_state_doubles', 'pgl_smc_init_dev', 'pgl_smc_stage_dev', 'pgl_smc_gather_dev', 'pgl_smc_begin_dev', 'pgl_smc_leap_dev',
     'pgl_smc_dense_begin_dev', 'pgl_smc_dense_leap_dev',
     'pgl_hess_dev', 'pgl_hess',
-    'pgl_chol_factor_dev', 'pgl_tri_inverse_dev',
+    'pgl_chol_factor_dev', 'pgl_tri_inverse_dev', 'pgl_chol_solve_dev',
+    'pgl_newton_state_doubles', 'pgl_newton_init_dev', 'pgl_newton_assemble_dev', 'pgl_newton_direction_dev',
+    'pgl_newton_trial_dev', 'pgl_newton_search_step_dev',
     'pgl_rescale_count', 'pgl_rescale_dev', 'pgl_rescale',
     'pgl_simulate_streams', 'pgl_simulate_batch', 'pgl_simulate_batch_dev', 'pgl_simulate_batch_plan',
 ]
@@ -176,6 +178,7 @@ def load():
     lib.pgl_hess.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
     lib.pgl_chol_factor_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     lib.pgl_tri_inverse_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
+    lib.pgl_chol_solve_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.pgl_rescale_count.argtypes = [vp, vp]
     lib.pgl_rescale_dev.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.pgl_rescale.argtypes = [vp, vp, vp, vp, vp]
@@ -195,6 +198,13 @@ def load():
     lib.pgl_ncg_cg_step_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, pr, vp, vp]
     lib.pgl_ncg_trial_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp]
     lib.pgl_ncg_search_step_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, pr, C.c_int, vp, vp, vp, vp]
+    lib.pgl_newton_state_doubles.argtypes = [C.c_int, C.c_int]
+    lib.pgl_newton_init_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, pr, C.c_double, C.c_int, vp]
+    lib.pgl_newton_assemble_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, pr, vp]
+    lib.pgl_newton_direction_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]
+    lib.pgl_newton_trial_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp]
+    lib.pgl_newton_search_step_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, pr, C.c_double, C.c_int, vp,
+                                               vp, vp]
     lib.pgl_hmc_state_doubles.argtypes = [C.c_int, C.c_int]
     lib.pgl_hmc_init_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, pr, C.c_double, C.c_uint64]
     lib.pgl_hmc_begin_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
@@ -261,8 +271,8 @@ def load():
     lib.pgl_simulate_batch_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
     for name in SYMBOLS:
         fn = getattr(lib, name)
-        if name in ('pgl_bfgs_state_doubles', 'pgl_ncg_state_doubles', 'pgl_hmc_state_doubles', 'pgl_ais_state_doubles',
-                    'pgl_prox_state_doubles', 'pgl_nuts_state_doubles', 'pgl_adapt_state_doubles', 'pgl_smc_state_doubles'):
+        if name in ('pgl_bfgs_state_doubles', 'pgl_ncg_state_doubles', 'pgl_newton_state_doubles', 'pgl_hmc_state_doubles',
+                    'pgl_ais_state_doubles', 'pgl_prox_state_doubles', 'pgl_nuts_state_doubles', 'pgl_adapt_state_doubles', 'pgl_smc_state_doubles'):
             fn.restype = C.c_longlong
         elif name not in ('pgl_last_error',):
             fn.restype = C.c_int
@@ -593,6 +603,23 @@ class DeviceGlm(object):
         _chk(self.lib.pgl_tri_inverse_dev(self.h, C.c_void_p(L.data_ptr()), int(M), int(P), int(ld),
                                           C.c_void_p(info.data_ptr())))
 
+    def chol_solve(self, Ls, scale, info, b, out=None):
+        """x = A^-1 b for every matrix of the factor Ls (M, P, ld) with chol_factor's scale (M, P) and info (M,)
+        (pgl_chol_solve_dev); b (M, P) f64 on the device.  out: (M, P), may be b itself; default a new tensor.  Rows with
+        info[m] != 0 are NaN.  Asynchronous on the handle's stream; returns out."""
+        torch = self._stack(Ls, 'chol_solve')
+        M, P, ld = Ls.shape
+        out = torch.empty((M, P), dtype=torch.float64, device=Ls.device) if out is None else out
+        for t, dt, shp, what in ((scale, torch.float64, (M, P), 'scale'), (info, torch.int32, (M,), 'info'),
+                                 (b, torch.float64, (M, P), 'b'), (out, torch.float64, (M, P), 'out')):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous() and
+                    tuple(t.shape) == shp):
+                raise ValueError("chol_solve: %s must be a contiguous %s device tensor %s" % (what, dt, shp))
+        _chk(self.lib.pgl_chol_solve_dev(self.h, C.c_void_p(Ls.data_ptr()), int(M), int(P), int(ld),
+                                         C.c_void_p(scale.data_ptr()), C.c_void_p(info.data_ptr()),
+                                         C.c_void_p(b.data_ptr()), C.c_void_p(out.data_ptr())))
+        return out
+
     # -- time-rescaling goodness of fit (pgl_rescale*) ------------------------------
     def rescale_count(self):
         """(N + 1) int64 offsets of every neuron's rescaled intervals in the concatenated output, for the current time
@@ -690,6 +717,37 @@ class DeviceGlm(object):
         _chk(self.lib.pgl_ncg_search_step_dev(self.h, C.c_void_p(d_state), int(M), int(P), vp(d_rows), int(L),
                                               C.c_void_p(d_Xt), C.c_void_p(d_f), C.c_void_p(d_g), C.byref(as_prior(prior)),
                                               int(maxiter), vp(d_pos_next), vp(d_Xt_next), C.c_void_p(d_V), vp(flags_out)))
+
+    # -- lock-step dense Newton row kernels (pgl_newton_*; inference/batched_newton.py); device pointers
+    def newton_state_doubles(self, M, P):
+        return int(self.lib.pgl_newton_state_doubles(int(M), int(P)))
+
+    def newton_init_dev(self, d_state, M, P, d_ll, d_grad, prior, gtol, maxiter, flags_out=0):
+        _chk(self.lib.pgl_newton_init_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_ll), C.c_void_p(d_grad),
+                                          C.byref(as_prior(prior)), float(gtol), int(maxiter),
+                                          C.c_void_p(flags_out) if flags_out else None))
+
+    def newton_assemble_dev(self, d_state, M, P, d_rows, L, d_H, ld, prior, d_rhs=0):
+        vp = lambda a: C.c_void_p(a) if a else None
+        _chk(self.lib.pgl_newton_assemble_dev(self.h, C.c_void_p(d_state), int(M), int(P), vp(d_rows), int(L), C.c_void_p(d_H),
+                                              int(ld), C.byref(as_prior(prior)), vp(d_rhs)))
+
+    def newton_direction_dev(self, d_state, M, P, d_rows, L, d_info, d_p, flags_out=0):
+        vp = lambda a: C.c_void_p(a) if a else None
+        _chk(self.lib.pgl_newton_direction_dev(self.h, C.c_void_p(d_state), int(M), int(P), vp(d_rows), int(L),
+                                               C.c_void_p(d_info), C.c_void_p(d_p), vp(flags_out)))
+
+    def newton_trial_dev(self, d_state, M, P, d_rows, L, d_Xt):
+        _chk(self.lib.pgl_newton_trial_dev(self.h, C.c_void_p(d_state), int(M), int(P),
+                                           C.c_void_p(d_rows) if d_rows else None, int(L), C.c_void_p(d_Xt)))
+
+    def newton_search_step_dev(self, d_state, M, P, d_rows, L, d_Xt, d_f, d_g, prior, gtol, maxiter, d_pos_next, d_Xt_next,
+                               flags_out=0):
+        vp = lambda a: C.c_void_p(a) if a else None
+        _chk(self.lib.pgl_newton_search_step_dev(self.h, C.c_void_p(d_state), int(M), int(P), vp(d_rows), int(L),
+                                                 C.c_void_p(d_Xt), C.c_void_p(d_f), C.c_void_p(d_g),
+                                                 C.byref(as_prior(prior)), float(gtol), int(maxiter), vp(d_pos_next),
+                                                 vp(d_Xt_next), vp(flags_out)))
 
     # -- lock-step HMC row kernels (pgl_hmc_*; inference/batched_hmc.py); device pointers.  n_chains = C: the run has R = C M
     # rows, chain c of neuron n_lo + m is row c M + m, and every call after init takes R as its M

@@ -335,6 +335,77 @@ int pgl_tri_inverse_dev(pgl_handle h, double* d_L, int M, int P, int ld, const i
     return launch_rows(h, k_tri_inverse, M, d_L, P, ld, d_info);
 }
 
+int pgl_chol_solve_dev(pgl_handle h, const double* d_Ls, int M, int P, int ld, const double* d_scale, const int* d_info,
+                       const double* d_b, double* d_x)
+{
+    if (!h || !d_Ls || !d_scale || !d_info || !d_b || !d_x || M <= 0 || P <= 0 || ld < P) return fail(PGL_ERR_ARG, "bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    return launch_rows(h, k_chol_solve, M, d_Ls, P, ld, d_scale, d_info, d_b, d_x);
+}
+
+// ---- lock-step dense Newton row kernels (inference/batched_newton.py) --------------------------------------------------
+long long pgl_newton_state_doubles(int M, int P) { return (long long)pgl_newton_doubles(M, P); }
+
+int pgl_newton_init_dev(pgl_handle h, double* d_state, int M, int P, double* d_ll, double* d_grad, const pgl_prior* prior,
+                        double gtol, int maxiter, double* flags_out)
+{
+    if (!h || !d_state || !d_ll || !d_grad || M <= 0 || P <= 0) return fail(PGL_ERR_ARG, "bad argument");
+    BfgsPrior q;
+    int rc = fill_prior(h, P, prior, q);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    double* flags_dev = nullptr;
+    if (flags_out && flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
+    return launch_rows(h, k_newton_init, M, pgl_newton_view(d_state, M, P), d_ll, d_grad, q, gtol, maxiter, flags_dev);
+}
+
+int pgl_newton_assemble_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, double* d_H, int ld,
+                            const pgl_prior* prior, double* d_rhs)
+{
+    if (!h || !d_state || !d_H || M <= 0 || P <= 0 || L <= 0 || L > M || ld < P) return fail(PGL_ERR_ARG, "bad argument");
+    BfgsPrior q;
+    int rc = fill_prior(h, P, prior, q);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    return launch_rows(h, k_newton_assemble, L, pgl_newton_view(d_state, M, P), d_rows, d_H, ld, q, d_rhs);
+}
+
+int pgl_newton_direction_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, const int* d_info,
+                             const double* d_p, double* flags_out)
+{
+    if (!h || !d_state || !d_info || !d_p || M <= 0 || P <= 0 || L <= 0 || L > M) return fail(PGL_ERR_ARG, "bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    double* flags_dev = nullptr;
+    if (flags_out && flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
+    return launch_rows(h, k_newton_direction, L, pgl_newton_view(d_state, M, P), d_rows, d_info, d_p, flags_dev);
+}
+
+int pgl_newton_trial_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, double* d_Xt)
+{
+    if (!h || !d_state || !d_Xt || M <= 0 || P <= 0 || L <= 0 || L > M) return fail(PGL_ERR_ARG, "bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    return launch_rows(h, k_newton_trial, L, pgl_newton_view(d_state, M, P), d_rows, d_Xt);
+}
+
+int pgl_newton_search_step_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, const double* d_Xt,
+                               double* d_ll_f, double* d_grad_g, const pgl_prior* prior, double gtol, int maxiter,
+                               const int* d_pos_next, double* d_Xt_next, double* flags_out)
+{
+    if (!h || !d_state || !d_Xt || !d_ll_f || !d_grad_g || M <= 0 || P <= 0 || L <= 0 || L > M)
+        return fail(PGL_ERR_ARG, "bad argument");
+    if (d_Xt_next == d_Xt) return fail(PGL_ERR_ARG, "the next trial points need a buffer of their own");
+    NewtonSearchArgs a;
+    memset(&a, 0, sizeof(a));
+    int rc = fill_prior(h, P, prior, a.q);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    double* flags_dev = nullptr;
+    if (flags_out && flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
+    a.rows = d_rows; a.Xt = d_Xt; a.ft = d_ll_f; a.gt = d_grad_g; a.gtol = gtol; a.maxiter = maxiter;
+    a.pos_next = d_pos_next; a.Xt_next = d_Xt_next; a.flags = flags_dev;
+    return launch_rows(h, k_newton_search_step, L, pgl_newton_view(d_state, M, P), a);
+}
+
 int pgl_hmc_dense_begin_dev(pgl_handle h, double* d_state, int M, int P, const double* d_W, double* d_Xt)
 {
     if (!h || !d_state || !d_W || !d_Xt || M <= 0 || P <= 0) return fail(PGL_ERR_ARG, "bad argument");

@@ -186,6 +186,96 @@ __global__ __launch_bounds__(256) void k_chol_factor(double* __restrict__ A, con
     }
 }
 
+// solve against the factor, x = D^-1/2 Ls^-T Ls^-1 D^-1/2 b (the Newton direction of pglm_newton.hip.h: 2 P^2 flops where
+// the inverse costs P^3 / 3 and two products).  One workgroup per matrix, blocks of 32 like the factor, the vector in the
+// caller's x row throughout (b and x may be the same memory: every element is read by the thread that writes it).  Both
+// substitutions are left-looking, so that every pass over Ls runs along its rows:
+//   forward,  block K top down:   r_K = y_K - sum_{c < k0} Ls[K, c] y_c   one wave per row, lanes along the columns, a wave64
+//             butterfly per row; then Ls[K, K] y_K = r_K in the first wave, the block's vector in registers (lane i holds
+//             y_i, a shuffle hands the finished y_j down), the diagonal block in LDS;
+//   backward, block K bottom up:  r_K = x_K - sum_{i >= k0 + 32} Ls[i, K]^T x_i   thread (c, s) sums the rows i = s mod 8 of
+//             column k0 + c, the eight partials meet in LDS in a fixed tree; then Ls[K, K]^T x_K = r_K as above.
+// Every sum runs in an order that P alone decides.  A row with info != 0 gets NaN and nothing of it is read.
+__global__ __launch_bounds__(256) void k_chol_solve(const double* __restrict__ L, const int P, const int ld,
+                                                    const double* __restrict__ scale, const int* __restrict__ info,
+                                                    const double* b, double* x)
+{
+    __shared__ double D[PGL_CH_NB][PGL_CH_PAD];
+    __shared__ double part[8][PGL_CH_NB];
+    __shared__ double xs[PGL_CH_NB];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const double* Lm = L + (size_t)blockIdx.x * P * ld;
+    const double* sc = scale + (size_t)blockIdx.x * P;
+    const double* bv = b + (size_t)blockIdx.x * P;
+    double* xv = x + (size_t)blockIdx.x * P;
+    if (info[blockIdx.x] != 0) {                                 // (the whole workgroup, before any barrier)
+        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        for (int i = tid; i < P; i += 256) xv[i] = nan;
+        return;
+    }
+    for (int i = tid; i < P; i += 256) xv[i] = bv[i] / sc[i];
+    __syncthreads();
+    // forward: Ls y = D^-1/2 b
+    for (int k0 = 0; k0 < P; k0 += PGL_CH_NB) {
+        const int nb = min(PGL_CH_NB, P - k0);
+        for (int e = tid; e < PGL_CH_NB * PGL_CH_NB; e += 256) {
+            const int i = e >> 5, c = e & 31;
+            D[i][c] = (i < nb && c <= i) ? Lm[(size_t)(k0 + i) * ld + k0 + c] : (i == c ? 1.0 : 0.0);
+        }
+        for (int i = wave; i < nb; i += 4) {
+            const double* row = Lm + (size_t)(k0 + i) * ld;
+            double s = 0.0;
+            for (int c = lane; c < k0; c += 64) s = fma(row[c], xv[c], s);
+            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+            if (lane == 0) xs[i] = xv[k0 + i] - s;
+        }
+        __syncthreads();
+        if (wave == 0) {
+            const int li = lane & 31;
+            double yi = lane < nb ? xs[li] : 0.0;
+            const double dii = D[li][li];
+            for (int j = 0; j < nb; ++j) {
+                const double yj = __shfl(yi / dii, j, 64);
+                if (lane == j) yi = yj;
+                else if (lane > j && lane < nb) yi = fma(-D[li][j], yj, yi);
+            }
+            if (lane < nb) xv[k0 + lane] = yi;
+        }
+        __syncthreads();
+    }
+    // backward: Ls^T z = y
+    for (int k0 = ((P - 1) / PGL_CH_NB) * PGL_CH_NB; k0 >= 0; k0 -= PGL_CH_NB) {
+        const int nb = min(PGL_CH_NB, P - k0);
+        for (int e = tid; e < PGL_CH_NB * PGL_CH_NB; e += 256) {
+            const int i = e >> 5, c = e & 31;
+            D[i][c] = (i < nb && c <= i) ? Lm[(size_t)(k0 + i) * ld + k0 + c] : (i == c ? 1.0 : 0.0);
+        }
+        {
+            // (rows below the block exist only when the block is a full one: k0 + c < P)
+            const int c = tid & 31, s = tid >> 5;
+            double a = 0.0;
+            for (int i = k0 + PGL_CH_NB + s; i < P; i += 8) a = fma(Lm[(size_t)i * ld + k0 + c], xv[i], a);
+            part[s][c] = a;
+        }
+        __syncthreads();
+        if (wave == 0) {
+            const int li = lane & 31;
+            const double sum = ((part[0][li] + part[1][li]) + (part[2][li] + part[3][li])) +
+                               ((part[4][li] + part[5][li]) + (part[6][li] + part[7][li]));
+            double zi = lane < nb ? xv[k0 + li] - sum : 0.0;
+            const double dii = D[li][li];
+            for (int j = nb - 1; j >= 0; --j) {
+                const double zj = __shfl(zi / dii, j, 64);
+                if (lane == j) zi = zj;
+                else if (lane < j) zi = fma(-D[j][li], zj, zi);
+            }
+            if (lane < nb) xv[k0 + lane] = zi;
+        }
+        __syncthreads();
+    }
+    for (int i = tid; i < P; i += 256) xv[i] = xv[i] / sc[i];
+}
+
 __global__ __launch_bounds__(256) void k_tri_inverse(double* __restrict__ L, const int P, const int ld,
                                                      const int* __restrict__ info)
 {

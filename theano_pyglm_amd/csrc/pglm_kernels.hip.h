@@ -25,6 +25,7 @@
 // The No-U-Turn sampler runs on the same launch and products with rows that do not wait for each other (k_nuts_*, pglm_nuts.hip.h).
 // The Laplace posterior factors and inverts the dense Hessians in place, one workgroup per matrix (k_chol_factor, k_tri_inverse,
 // pglm_chol.hip.h).
+// The dense Newton fit solves against that factor (k_chol_solve) between its row kernels (k_newton_*, pglm_newton.hip.h).
 // The per-neuron evidence comes from annealed importance sampling on the same moves (k_ais_*, pglm_ais.hip.h).
 // Its dense mass shares one read of a neuron's factor among the neuron's particles (k_tri_matvec_shared, pglm_ais_dense.hip.h).
 // Adaptive sequential Monte Carlo walks the same tempered path with per-neuron ladders and resampling on the device (k_smc_*,
@@ -47,6 +48,7 @@
 #include "pglm_stim.hip.h"
 #include "pglm_bfgs.hip.h"
 #include "pglm_ncg.hip.h"
+#include "pglm_newton.hip.h"
 #include "pglm_hmc.hip.h"
 #include "pglm_hmc_dense.hip.h"
 #include "pglm_adapt.hip.h"

@@ -6,6 +6,7 @@ MAP fit on synthetic data -- counterpart of test/synth_map.py + test/synth_harne
 The sweep over the neurons runs as the GPU lock-step optimizer by default (inference/batched_bfgs.py);
 --sequential (batched=False) is the reference's loop of per-neuron scipy fits; --newton-cg runs the sweep as the GPU
 lock-step Newton-CG optimizer on device Hessian-vector products (inference/batched_newton_cg.py; the reference's use_rop).
+--newton runs the sweep as the GPU lock-step dense-Hessian Newton fit (inference/batched_newton.py; the reference's use_hessian).
 --prox runs the sweep as the GPU lock-step proximal-gradient fit of the group-lasso MAP (inference/batched_prox.py) and prints
 status, iterations and the number of non-zero presynaptic groups per neuron.
 --gof prints the time-rescaling KS table of the fitted model (inference/gof.py) after the fit.
@@ -49,13 +50,13 @@ def initialize_test_harness(model_name, data, data_dir=None):
 
 
 def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False, gof=False, ppc=0, hmc=0, ais=0,
-                   hmc_mass='laplace', prox=False, laplace_device=False, ais_mass='laplace', nuts=0, smc=0):
+                   hmc_mass='laplace', prox=False, laplace_device=False, ais_mass='laplace', nuts=0, smc=0, newton=False):
     """test/synth_map.py:10-32."""
     popn, popn_true, x_true = initialize_test_harness(model_name, data, data_dir)
     x0 = popn.sample(rng)
     print("LL0: %f" % popn.compute_log_p(x0))
     t0 = time.time()
-    x_inf = coord_descent(popn, x0=x0, maxiter=1, batched=batched, use_rop=use_rop, prox=prox)
+    x_inf = coord_descent(popn, x0=x0, maxiter=1, batched=batched, use_rop=use_rop, prox=prox, newton=newton)
     wall = time.time() - t0
     if prox:
         print(prox_table(popn, x_inf))
@@ -198,6 +199,9 @@ def parser():
     ap.add_argument('--newton-cg', action='store_true',
                     help='lock-step Newton-CG on device Hessian-vector products instead of lock-step BFGS '
                          '(with --sequential: per-neuron scipy Newton-CG fits)')
+    ap.add_argument('--newton', action='store_true',
+                    help='lock-step dense-Hessian Newton on the device (Hessian contraction, batched Cholesky factor and '
+                         'solve per outer iteration) instead of lock-step BFGS')
     ap.add_argument('--prox', action='store_true',
                     help='group-lasso MAP by lock-step proximal gradient on the device (exact zeros); prints status, '
                          'iterations and the non-zero groups per neuron')
@@ -234,7 +238,8 @@ def main(argv=None):
         data = pickle.load(f)
     run_synth_test(args.model, data, args.resultsDir, os.path.dirname(args.dataFile),
                    False if args.sequential else ('torch' if args.newton_cg else None), use_rop=args.newton_cg, gof=args.gof, ppc=args.ppc, hmc=args.hmc, ais=args.ais,
-                   hmc_mass=args.hmc_mass, prox=args.prox, laplace_device=args.laplace_device, ais_mass=args.ais_mass, nuts=args.nuts, smc=args.smc)
+                   hmc_mass=args.hmc_mass, prox=args.prox, laplace_device=args.laplace_device, ais_mass=args.ais_mass, nuts=args.nuts, smc=args.smc,
+                   newton=args.newton)
 
 
 if __name__ == '__main__':

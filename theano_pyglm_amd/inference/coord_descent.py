@@ -139,10 +139,12 @@ def fit_network(x, net_inf_prms):
 def fit_glm(xn, n, glm_inf_prms, verbose=False, maxiter=225, use_hessian=False, use_rop=False, hessp=None):
     """coord_descent.py:161-204; with use_rop the Newton-CG fit of parallel_coord_descent.py:119-121 / map.py:38-45 on
     hessp = prep_second_order_glm_inference(population).  Rop takes precedence over the dense Hessian
-    (parallel_coord_descent.py:75-76); use_hessian alone raises: the dense P x P Hessian is not built."""
+    (parallel_coord_descent.py:75-76); use_hessian alone raises: the per-neuron fit has no dense-Hessian route -- the dense
+    Newton fit is the lock-step sweep of all neurons, coord_descent(newton=True) / inference/batched_newton.py."""
     if use_hessian and not use_rop:
-        raise NotImplementedError("use_hessian: the dense P x P Hessian is not built; use_rop=True runs Newton-CG on "
-                                  "Hessian-vector products")
+        raise NotImplementedError("use_hessian: the per-neuron fit has no dense P x P Hessian route; the dense Newton fit is "
+                                  "the lock-step sweep coord_descent(newton=True) (inference/batched_newton.py), and "
+                                  "use_rop=True runs Newton-CG on Hessian-vector products")
     if use_rop and hessp is None:
         raise ValueError("use_rop=True needs hessp = prep_second_order_glm_inference(population)")
     glm_syms, glm_nll, g_glm_nll = glm_inf_prms
@@ -279,15 +281,24 @@ def resolve_batched(population, batched):
     return batched
 
 
-def coord_descent(population, x0=None, maxiter=50, atol=1e-5, batched=None, verbose=False, use_rop=False, prox=False):
+def coord_descent(population, x0=None, maxiter=50, atol=1e-5, batched=None, verbose=False, use_rop=False, prox=False,
+                  newton=False):
     """coord_descent.py:206-266.  `batched`: see resolve_batched (None = automatic; batched=False is the
     reference's sweep of N sequential scipy BFGS fits, kept for comparison).  use_rop: the per-neuron fits of the
     sequential sweep run Newton-CG on device Hessian-vector products (parallel_coord_descent.py:62-63); with
     batched=None it selects that sweep.  use_rop with batched='torch' runs the sweep as ONE lock-step Newton-CG fit of all
     neurons on the GPU (inference/batched_newton_cg.py); there is no numpy lock-step Newton: batched=True raises.
     prox=True: the sweep is ONE lock-step proximal-gradient fit of the group-lasso MAP on the GPU (inference/batched_prox.py:
-    exact zeros in the impulse weights); it needs a group-lasso impulse prior and takes no other sweep option."""
+    exact zeros in the impulse weights); it needs a group-lasso impulse prior and takes no other sweep option.
+    newton=True: the sweep is ONE lock-step dense-Hessian Newton fit of all neurons on the GPU (inference/batched_newton.py:
+    the reference's use_hessian route); exclusive with use_rop and prox, batched None or 'torch'."""
     N = population.model['N']
+    if newton:
+        if use_rop or prox or batched not in (None, 'torch'):
+            raise ValueError("newton=True runs the GPU lock-step dense Newton sweep: no use_rop, no prox, batched None or 'torch'")
+        from theano_pyglm_amd.inference import batched_newton
+        batched_newton._check(population)                     # unsupported packing / time shard: before any device work
+        batched = 'torch'
     if prox:
         if use_rop or batched not in (None, 'torch'):
             raise ValueError("prox=True runs the GPU lock-step proximal-gradient sweep: no use_rop, batched None or 'torch'")
@@ -323,6 +334,8 @@ def coord_descent(population, x0=None, maxiter=50, atol=1e-5, batched=None, verb
         it += 1
         if prox:
             batched_prox.fit_glms_prox(population, x, verbose=verbose)
+        elif newton:
+            batched_newton.fit_glms_newton_torch(population, x, verbose=verbose)
         elif batched == 'torch' and use_rop:
             batched_newton_cg.fit_glms_newton_cg_torch(population, x, verbose=verbose)
         elif batched == 'torch':
