@@ -81,7 +81,8 @@ typedef struct pgl_context* pgl_handle;
 #define PGL_OPT_RECORD_KERNELS 96 /* dev / test: 1 = every ll(+grad) evaluation and pgl_gibbs_prepare_all records the fused kernel
                                    * instantiations it launches, in launch order (pgl_last_kernels), and so do pgl_hvp_prepare_* /
                                    * pgl_hvp_apply_dev (k_hvp5 and the k_fused* launches around it), pgl_hess_dev (k_hess) and
-                                   * pgl_rescale_dev (the forward launches, then k_rescale_*); 0 (default) = off */
+                                   * pgl_rescale_dev (the forward launches, then k_rescale_*) and pgl_pointwise_dev (the forward launches,
+                                   * then k_pw_chunk and k_pw_block); 0 (default) = off */
 
 /* Development switches (not part of the drop-in surface; results stay valid unless stated): 95 = 2 keeps the narrow post
  * blocks of a wide population off the one-image-buffer form of k_fused6 and the block-ring kernel k_fused8 (they run on
@@ -92,7 +93,7 @@ typedef struct pgl_context* pgl_handle;
 
 /* What pgl_version() returns: it changes with every change of a signature or a struct below, and a binding refuses a
  * library that reports another number (theano_pyglm_amd/_lib.py: ABI_VERSION). */
-#define PGL_ABI_VERSION 108
+#define PGL_ABI_VERSION 109
 
 const char* pgl_last_error(void);
 int pgl_version(void);
@@ -812,6 +813,38 @@ int pgl_rescale_dev(pgl_handle h, const double* d_theta, const double* d_Weff, d
                     double* d_stats);
 int pgl_rescale(pgl_handle h, const double* theta, const double* Weff, double* tau_out, double* stats_out);
 
+/* Pointwise log-likelihood of a parameter draw, resolved in time, and its accumulation over posterior draws for WAIC
+ * (Watanabe 2010; Vehtari, Gelman & Gabry 2017) and held-out predictive densities.  The reference computes the held-out
+ * density with a callback per Gibbs sample (test/parallel_mcmc.py:59-90) and has no pointwise criterion.  For neuron n over
+ * the handle's time range [t_lo, t_hi) (pgl_set_time_range is honoured):
+ *     term_t = -dt * lam_t + S[t,n] * log lam_t,  lam_t = nlin(theta_n[0] + x[t,n]), x the bias-free total current of
+ *             pgl_gibbs_prepare_all; all f64 (the rate function of pgl_rescale); log lam = the current itself for the exp
+ *             nonlinearity; a bin with S = 0 contributes -dt * lam only (never 0 * log 0).  Spike counts come from the
+ *             event lists.
+ *     chunk   256 consecutive bins, counted from t_lo; the last one may be short;
+ *     block   block_chunks >= 1 consecutive chunks, counted from the first; the last one may be short:
+ *             n_blocks = ceil(nchunks / block_chunks); a block_chunks >= nchunks gives one block, the ll of the range;
+ *     ll_blk[b][n] = sum of term_t over the bins of block b.  Given the spike history the likelihood factorises over bins,
+ *             so the block sums are conditionally independent pointwise terms.
+ *     accumulator over draws, per (block, neuron) four doubles in planes (4, n_blocks, N) -- m, e, mean, M2 -- by the rule of
+ *             theano_pyglm_amd/csrc/pglm_pointwise.h:  draw 0 sets m = l, e = 1, mean = l, M2 = 0 (the caller need not
+ *             clear the state); draw s >= 1:  l > m: e = e exp(m - l) + 1, m = l;  else e += exp(l - m);  d = l - mean;
+ *             mean += d / (s + 1);  M2 += d (l - mean).  After S draws log mean_s exp(l_s) = log(e / S) + m and the sample
+ *             variance is M2 / (S - 1).  A non-finite l makes the four values of that (block, neuron) NaN for good and
+ *             touches nothing else.
+ * pointwise_count: n_blocks_out (host) for the current time range.
+ * pointwise_dev:   device pointers, asynchronous on the handle's stream.  d_theta (N, P), d_Weff (N, N): the forward pass of
+ *     pgl_gibbs_prepare_all runs on them (and leaves its state, as that call does); d_ll_blk (n_blocks, N) out, or NULL;
+ *     d_acc (4, n_blocks, N) in/out, or NULL; at least one of the two; draw = the index s of this draw for d_acc.  Two
+ *     launches behind the forward ones (k_pw_chunk: one read of the currents, no (nT, N) array; k_pw_block), every sum in a
+ *     fixed order and no atomics: two calls give the same bits.
+ * pointwise:       host pointers, ll_blk_out (n_blocks, N).
+ * Stimulus forms and errors as pgl_rescale_dev; block_chunks < 1, draw < 0 or both outputs NULL: PGL_ERR_ARG. */
+int pgl_pointwise_count(pgl_handle h, int block_chunks, int64_t* n_blocks_out);
+int pgl_pointwise_dev(pgl_handle h, const double* d_theta, const double* d_Weff, int block_chunks, double* d_ll_blk,
+                      double* d_acc, int64_t draw);
+int pgl_pointwise(pgl_handle h, const double* theta, const double* Weff, int block_chunks, double* ll_blk_out);
+
 /* Spike-triggered average, pyglm/utils/sta.py:6-85 (used by smart_init.py:28-98 and 100-158):
  *   A[i,l,d] = sum_t S[t,n_i] * istim[t-l,d] / sum_t S[t,n_i],  l = 0..L-1, terms with t-l < 0 dropped,
  * istim = np.interp of stim (Tstim,D) to the bin grid, divided by dt_stim/dt (sta.py:27-41).
@@ -919,7 +952,8 @@ int pgl_set_stream(pgl_handle h, void* stream);
  * pgl_hvp_apply_dev after such a prepare (k_hvp5<.., 0> + pass 2 of k_fused5, or the forward-only and backward-only K-split
  * launches of every column slice), 5 the k_hess launches of pgl_hess_dev after such a prepare (one per batch of rows),
  * 6 the launches of pgl_rescale_dev (those of path 2, then k_rescale_chunk<nlin>, k_rescale_scan, k_rescale_finish; the dry
- * run's context has nlin = PGL_NLIN_EXP).
+ * run's context has nlin = PGL_NLIN_EXP), 7 the launches of pgl_pointwise_dev (those of path 2, then k_pw_chunk<nlin>,
+ * k_pw_block).
  * Paths 3 / 4 / 5 with stim >= 1 return PGL_ERR_UNSUPPORTED, as the calls themselves.
  * The reference has no counterpart (Theano picks its own C implementations); tests hold every reachable instantiation to
  * zero bytes of scratch. */
@@ -927,7 +961,7 @@ int pgl_plan_kernels(int N, int B, int R, int Dstim, long long nT, int stim, int
                      int opt_f32, char* out, int cap);
 
 /* The fused kernel instantiations the handle's last pgl_ll_grad / pgl_ll_grad_dev / pgl_ll_grad_list_dev /
- * pgl_gibbs_prepare_all / pgl_hvp_prepare_* / pgl_hvp_apply_dev / pgl_hess_dev / pgl_rescale_dev call launched, one per line in `out`, in launch order and in the format of pgl_plan_kernels
+ * pgl_gibbs_prepare_all / pgl_hvp_prepare_* / pgl_hvp_apply_dev / pgl_hess_dev / pgl_rescale_dev / pgl_pointwise_dev call launched, one per line in `out`, in launch order and in the format of pgl_plan_kernels
  * (which enqueues the same launch sequence on a device-less context).  Needs PGL_OPT_RECORD_KERNELS = 1 on the handle
  * (PGL_ERR_STATE otherwise).  Dev / test entry point: tests compare it with the dry run. */
 int pgl_last_kernels(pgl_handle h, char* out, int cap);

@@ -53,11 +53,12 @@ SYMBOLS = [
     'pgl_newton_state_doubles', 'pgl_newton_init_dev', 'pgl_newton_assemble_dev', 'pgl_newton_direction_dev',
     'pgl_newton_trial_dev', 'pgl_newton_search_step_dev',
     'pgl_rescale_count', 'pgl_rescale_dev', 'pgl_rescale',
+    'pgl_pointwise_count', 'pgl_pointwise_dev', 'pgl_pointwise',
     'pgl_simulate_streams', 'pgl_simulate_batch', 'pgl_simulate_batch_dev', 'pgl_simulate_batch_plan',
 ]
 
 
-ABI_VERSION = 108                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
+ABI_VERSION = 109                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
 
 
 class PglError(RuntimeError):
@@ -182,6 +183,9 @@ def load():
     lib.pgl_rescale_count.argtypes = [vp, vp]
     lib.pgl_rescale_dev.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.pgl_rescale.argtypes = [vp, vp, vp, vp, vp]
+    lib.pgl_pointwise_count.argtypes = [vp, C.c_int, vp]
+    lib.pgl_pointwise_dev.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int64]
+    lib.pgl_pointwise.argtypes = [vp, vp, vp, C.c_int, vp]
     # the lock-step methods; pr: const pgl_prior*
     lib.pgl_bfgs_state_doubles.argtypes = [C.c_int, C.c_int]
     lib.pgl_bfgs_init_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double]
@@ -645,6 +649,30 @@ class DeviceGlm(object):
         stats = np.empty((self.N, 4))
         _chk(self.lib.pgl_rescale(self.h, _ptr(th), _ptr(We), _ptr(tau), _ptr(stats)))
         return tau[:int(off[-1])], off, stats
+
+    # -- pointwise log-likelihood of a draw, and its accumulation over draws (pgl_pointwise*) -------------
+    def pointwise_count(self, block_chunks=1):
+        """Number of time blocks of block_chunks chunks (RESCALE_CHUNK bins each, counted from t_lo) in the current time
+        range."""
+        n = C.c_int64()
+        _chk(self.lib.pgl_pointwise_count(self.h, int(block_chunks), C.byref(n)))
+        return int(n.value)
+
+    def pointwise_dev(self, d_theta, d_Weff, block_chunks, d_ll_blk=0, d_acc=0, draw=0):
+        """Device-pointer form (integers; asynchronous): d_theta (N, P), d_Weff (N, N), d_ll_blk (n_blocks, N) out or 0,
+        d_acc (4, n_blocks, N) in/out or 0 with the index `draw` of this draw; see pgl_pointwise_dev."""
+        _chk(self.lib.pgl_pointwise_dev(self.h, C.c_void_p(d_theta), C.c_void_p(d_Weff), int(block_chunks),
+                                        C.c_void_p(d_ll_blk) if d_ll_blk else None, C.c_void_p(d_acc) if d_acc else None,
+                                        int(draw)))
+
+    def pointwise(self, theta, Weff, block_chunks=1):
+        """Block sums of the log-likelihood terms of every neuron over the current time range with host arrays: theta
+        (N, P), Weff (N, N) -> (n_blocks, N)."""
+        th = _f64(theta, (self.N, self.P))
+        We = _f64(Weff, (self.N, self.N))
+        out = np.empty((self.pointwise_count(block_chunks), self.N))
+        _chk(self.lib.pgl_pointwise(self.h, _ptr(th), _ptr(We), int(block_chunks), _ptr(out)))
+        return out
 
     # -- lock-step optimiser bookkeeping (device pointers as integers; asynchronous on the handle's stream) --
     def bfgs_state_doubles(self, M, P):

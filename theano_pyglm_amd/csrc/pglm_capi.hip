@@ -124,6 +124,7 @@ struct pgl_context {
     // time rescaling (pgl_rescale_dev): in-chunk sums at the events, chunk totals and their prefix; pgl_rescale: the device
     // copies of its offsets and results
     DevBuf rs_pre, rs_tot, rs_cum, rs_off, rs_tau, rs_stats;
+    DevBuf pw_part, pw_out;              // pointwise ll (pgl_pointwise_dev): chunk sums; pgl_pointwise: the device copy of ll_blk_out
     std::vector<double> hvp_host;        // pgl_hvp: theta and Weff of its last prepare (a CG solve repeats them: no new prepare)
 };
 
@@ -306,7 +307,8 @@ int pgl_destroy(pgl_handle h)
                       &h->gargs, &h->gpart, &h->gout, &h->ghs, &h->gfs, &h->zf, &h->zfT, &h->sbt, &h->Yf, &h->Qb, &h->Qf,
                       &h->spart, &h->sepC, &h->sepA, &h->sepAT, &h->sepD, &h->YfT, &h->Hb, &h->wpart, &h->QvT, &h->staA,
                       &h->Cbuf, &h->hvp_idx, &h->hvp_Weff, &h->hvp_ll, &h->hvp_v, &h->hvp_out,
-                      &h->hess_part, &h->hess_out, &h->rs_pre, &h->rs_tot, &h->rs_cum, &h->rs_off, &h->rs_tau, &h->rs_stats};
+                      &h->hess_part, &h->hess_out, &h->rs_pre, &h->rs_tot, &h->rs_cum, &h->rs_off, &h->rs_tau, &h->rs_stats,
+                      &h->pw_part, &h->pw_out};
     for (DevBuf* b : bufs) release(*b);
     for (int s = 0; s < pgl_context::NEV; ++s)
         for (int i = 0; i < 4; ++i)
@@ -1851,6 +1853,7 @@ int pgl_set_stream(pgl_handle h, void* stream)
 
 static int enqueue_gibbs_forward(pgl_handle h);
 static int enqueue_rescale(pgl_handle h, double* d_tau, const long long* d_off, double* d_stats);
+static int enqueue_pointwise(pgl_handle h, int block_chunks, double* d_ll_blk, double* d_acc, long long draw);
 
 int pgl_last_kernels(pgl_handle h, char* out, int cap)
 {
@@ -1870,7 +1873,8 @@ int pgl_last_kernels(pgl_handle h, char* out, int cap)
 // exists, 3 at the frame rate through the slab.  path: 0 ll+grad, 1 ll only, 2 the forward launches of pgl_gibbs_prepare_all,
 // 3 the launches of pgl_hvp_prepare_*, 4 those of pgl_hvp_apply_dev after such a prepare (k_hvp5 and the fused kernels around
 // it; stim >= 1: PGL_ERR_UNSUPPORTED, as the real call), 5 the k_hess launches of pgl_hess_dev after such a prepare,
-// 6 the launches of pgl_rescale_dev (the forward launches of path 2, then the k_rescale_* kernels).
+// 6 the launches of pgl_rescale_dev (the forward launches of path 2, then the k_rescale_* kernels), 7 those of
+// pgl_pointwise_dev (the forward launches of path 2, then k_pw_chunk and k_pw_block).
 int pgl_plan_kernels(int N, int B, int R, int Dstim, long long nT, int stim, int n_lo, int count, int path, int opt_kernel,
                      int opt_f32, char* out, int cap)
 {
@@ -1902,10 +1906,11 @@ int pgl_plan_kernels(int N, int B, int R, int Dstim, long long nT, int stim, int
         }
     } else {
         g_dry = &names;
-        rc = (path == 2 || path == 6) ? enqueue_gibbs_forward(&c)
+        rc = (path == 2 || path == 6 || path == 7) ? enqueue_gibbs_forward(&c)
                          : enqueue_ll_grad(&c, n_lo, n_lo + count, nullptr, nullptr, &dummy, path == 0 ? &dummy : nullptr);
     }
     if (rc == PGL_OK && path == 6) rc = enqueue_rescale(&c, &dummy, nullptr, &dummy);
+    if (rc == PGL_OK && path == 7) rc = enqueue_pointwise(&c, 1, &dummy, nullptr, 0);
     g_dry = nullptr;
     // (under g_dry nothing but a dispatch (pglm_launch.h) without an instantiation for the plan fails with PGL_ERR_HIP)
     if (rc == PGL_ERR_HIP) return fail(PGL_ERR_UNSUPPORTED, "no kernel instantiation for this plan");
@@ -2840,6 +2845,108 @@ int pgl_rescale(pgl_handle h, const double* theta, const double* Weff, double* t
     if (rc) return rc;
     if (ntau) HIPCHK(hipMemcpyAsync(tau_out, h->rs_tau.p, ntau * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(stats_out, h->rs_stats.p, (size_t)N * 4 * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return PGL_OK;
+}
+
+// ---- pointwise log-likelihood: block sums of the ll terms of a draw (pglm_pointwise.hip.h) ------------------------------
+static long long pointwise_chunks(const pgl_context* h) { return (h->t_hi - h->t_lo + PGL_RS_CHUNK - 1) / PGL_RS_CHUNK; }
+
+int pgl_pointwise_count(pgl_handle h, int block_chunks, int64_t* n_blocks_out)
+{
+    if (!h) return fail(PGL_ERR_ARG, "null handle");
+    if (!n_blocks_out) return fail(PGL_ERR_ARG, "null argument");
+    if (block_chunks < 1) return fail(PGL_ERR_ARG, "block_chunks must be at least 1");
+    *n_blocks_out = (pointwise_chunks(h) + block_chunks - 1) / block_chunks;
+    return PGL_OK;
+}
+
+// the k_pw_* launches behind a forward pass (GX of the handle's time range is on the stream).  The dry run of the dispatch
+// runs this too: the RULE above enqueue_ll_grad holds here.
+static int enqueue_pointwise(pgl_handle h, int block_chunks, double* d_ll_blk, double* d_acc, long long draw)
+{
+    struct Append {                                            // PGL_OPT_RECORD_KERNELS: behind the forward launches
+        explicit Append(pgl_context* h) { if (h->opt_record && !g_dry) g_rec = &h->last_kernels; }
+        ~Append() { g_rec = nullptr; }
+    } record(h);
+    const auto named = [](const std::string& name) {          // true: dry run, launch nothing
+        if (g_dry) g_dry->push_back(name);
+        else if (g_rec) g_rec->push_back(name);
+        return g_dry != nullptr;
+    };
+    const long long nchunks = pointwise_chunks(h);
+    const long long n_blocks = (nchunks + block_chunks - 1) / block_chunks;
+    const int xs = g_dry ? 16 * ((h->N + 15) / 16) : h->gx_xs;
+    ENSURE(h->pw_part, (size_t)nchunks * xs * 8);
+    PointwiseParams p;
+    p.GX = (const double*)h->GX.p; p.theta = (const double*)h->gtheta.p;
+    p.spk = (const int2*)h->spk.p; p.wlo = (const int*)h->wlo.p; p.whi = (const int*)h->whi.p;
+    p.part = (double*)h->pw_part.p; p.ll_blk = d_ll_blk; p.acc = d_acc;
+    p.t_lo = h->t_lo; p.t_hi = h->t_hi; p.draw = draw;
+    p.N = h->N; p.xs = xs; p.P = 1 + h->Dstim + h->Kimp; p.nnz = (int)h->nnz; p.nchunks = (int)nchunks;
+    p.block_chunks = (int)std::min<long long>(block_chunks, nchunks); p.n_blocks = (int)n_blocks;
+    p.dt = h->dt;
+    if (!named(h->nlin == PGL_NLIN_EXPLINEAR ? "k_pw_chunk<1>" : "k_pw_chunk<0>")) {
+        const unsigned blocks = (unsigned)((nchunks * xs + 255) / 256);
+        if (h->nlin == PGL_NLIN_EXPLINEAR) hipLaunchKernelGGL(k_pw_chunk<1>, dim3(blocks), dim3(256), 0, h->stream, p);
+        else hipLaunchKernelGGL(k_pw_chunk<0>, dim3(blocks), dim3(256), 0, h->stream, p);
+        HIPCHK(hipGetLastError());
+    }
+    if (!named("k_pw_block")) {
+        const unsigned blocks = (unsigned)((n_blocks * xs + 255) / 256);
+        hipLaunchKernelGGL(k_pw_block, dim3(blocks), dim3(256), 0, h->stream, p);
+        HIPCHK(hipGetLastError());
+    }
+    return PGL_OK;
+}
+
+int pgl_pointwise_dev(pgl_handle h, const double* d_theta, const double* d_Weff, int block_chunks, double* d_ll_blk,
+                      double* d_acc, int64_t draw)
+{
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if (!d_theta || !d_Weff) return fail(PGL_ERR_ARG, "null argument");
+    if (!d_ll_blk && !d_acc) return fail(PGL_ERR_ARG, "pointwise ll: neither d_ll_blk nor d_acc is given");
+    if (block_chunks < 1) return fail(PGL_ERR_ARG, "block_chunks must be at least 1");
+    if (draw < 0) return fail(PGL_ERR_ARG, "draw must not be negative");
+    if (pointwise_chunks(h) > 0x7fffffff / 2048)
+        return fail(PGL_ERR_UNSUPPORTED, "time range too long for the pointwise kernels");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t P = 1 + (size_t)h->Dstim + h->Kimp;
+    const int N = h->N;
+    ENSURE(h->gtheta, (size_t)N * P * 8);
+    ENSURE(h->Weff, (size_t)N * N * 8);
+    if (d_theta != h->gtheta.p)
+        HIPCHK(hipMemcpyAsync(h->gtheta.p, d_theta, (size_t)N * P * 8, hipMemcpyDeviceToDevice, h->stream));
+    if (d_Weff != h->Weff.p)
+        HIPCHK(hipMemcpyAsync(h->Weff.p, d_Weff, (size_t)N * N * 8, hipMemcpyDeviceToDevice, h->stream));
+    rc = enqueue_gibbs_forward(h);
+    if (rc) return rc;
+    return enqueue_pointwise(h, block_chunks, d_ll_blk, d_acc, (long long)draw);
+}
+
+int pgl_pointwise(pgl_handle h, const double* theta, const double* Weff, int block_chunks, double* ll_blk_out)
+{
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if (!theta || !Weff || !ll_blk_out) return fail(PGL_ERR_ARG, "null argument");
+    int64_t n_blocks = 0;
+    rc = pgl_pointwise_count(h, block_chunks, &n_blocks);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t P = 1 + (size_t)h->Dstim + h->Kimp;
+    const int N = h->N;
+    const size_t bytes = (size_t)n_blocks * N * 8;
+    ENSURE(h->gtheta, (size_t)N * P * 8);
+    ENSURE(h->Weff, (size_t)N * N * 8);
+    ENSURE(h->pw_out, bytes);
+    HIPCHK(hipMemcpyAsync(h->gtheta.p, theta, (size_t)N * P * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->Weff.p, Weff, (size_t)N * N * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));          // (pageable sources: see pgl_gibbs_prepare_all)
+    rc = pgl_pointwise_dev(h, (const double*)h->gtheta.p, (const double*)h->Weff.p, block_chunks, (double*)h->pw_out.p,
+                           nullptr, 0);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(ll_blk_out, h->pw_out.p, bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return PGL_OK;
 }

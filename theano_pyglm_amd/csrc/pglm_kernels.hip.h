@@ -34,6 +34,8 @@
 // pglm_prox.hip.h).
 // Simulation produces spikes instead of reading them: one workgroup per replicate runs the time loop (k_simulate,
 // pglm_simulate.hip.h).
+// Model comparison needs the log-likelihood of a draw resolved in time: block sums behind the forward-only pass, folded over
+// the draws on the device (k_pw_chunk, k_pw_block, pglm_pointwise.hip.h).
 #pragma once
 //
 // The kernels live in one header per family; this file is the translation unit's table of contents.
@@ -59,4 +61,5 @@
 #include "pglm_smc.hip.h"
 #include "pglm_prox.hip.h"
 #include "pglm_rescale.hip.h"
+#include "pglm_pointwise.hip.h"
 #include "pglm_simulate.hip.h"

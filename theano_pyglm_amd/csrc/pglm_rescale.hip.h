@@ -34,8 +34,10 @@ struct RescaleParams {
     double dt;
 };
 
-// first event of neuron n in a bin >= t, 0 <= t <= nT (index into spk; the neuron's list ends at `end`)
-__device__ __forceinline__ int pgl_rs_first_event(const RescaleParams& p, const int n, const long long t, int& end)
+// first event of neuron n in a bin >= t, 0 <= t <= nT (index into spk; the neuron's list ends at `end`); Prm: RescaleParams,
+// or the PointwiseParams of pglm_pointwise.hip.h (spk, wlo, whi, N, nnz)
+template <class Prm>
+__device__ __forceinline__ int pgl_rs_first_event(const Prm& p, const int n, const long long t, int& end)
 {
     end = (n + 1 < p.N) ? p.wlo[n + 1] : p.nnz;
     const long long tile = t >> 4;

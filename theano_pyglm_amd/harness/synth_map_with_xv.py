@@ -15,6 +15,11 @@ host-side prior scalars, so nothing moves between candidates.
 the lam that predicts ITS held-out spikes best, the model is refitted on all data with those per-neuron lams, and -- when
 the true model is known -- the recovered support is printed against the true adjacency matrix.
 
+--heldout-lpd [N] adds, for the winner of either sweep, the held-out log predictive density of the same 25 % split: the
+model is refitted on the training split, N (default 100) posterior draws per neuron come from the No-U-Turn sampler there, and
+log (1/N) sum_s p(held-out | theta_s) per neuron is computed on the device (inference/model_compare.py: heldout_lpd) -- what
+the reference's test/parallel_mcmc.py prints per Gibbs sample.
+
 Note on the reference script: its `nlp` sums over `population.data_sequences`, which at that point
 holds the *full* data set only (the splits are preprocessed but never added, :26-31), so the
 reference trains every candidate on all data.  Here `data_sequences` is switched to the training
@@ -137,6 +142,30 @@ def run_path(popn, data, train_frac=0.75, n_lams=10, lam_ratio=1e-2, rng=None, v
     return x, lam, dict(path, refit=res)
 
 
+def run_heldout_lpd(popn, data, x, n_draws=100, train_frac=0.75, batched=None, mass='laplace', seed=0):
+    """Held-out log predictive density of the model's current hyper-parameters on the last (1 - train_frac) of the data: MAP
+    fit on the training split from x, n_draws NUTS draws per neuron there, heldout_lpd on the held-out split.  Returns the
+    dict of model_compare.heldout_lpd; x is not changed."""
+    from theano_pyglm_amd.inference import batched_nuts, model_compare
+    T_split = data['T'] * train_frac
+    train_data = popn.preprocess_data(segment_data(data, (0, T_split)))
+    xv_data = popn.preprocess_data(segment_data(data, (T_split, data['T'])))
+    full_sequences = popn.data_sequences
+    try:
+        popn.data_sequences = [train_data]
+        popn.set_data(train_data)
+        x_train = coord_descent(popn, x0=copy.deepcopy(x), maxiter=1, batched=batched)
+        samples = batched_nuts.sample_glms_nuts(popn, x_train, n_draws, mass=mass, seed=seed)['samples']
+        popn.data_sequences = [xv_data]
+        popn.set_data(xv_data)
+        return model_compare.heldout_lpd(popn, x_train, samples)
+    finally:
+        popn.data_sequences = full_sequences
+        popn.set_data(data)
+        popn.release_data(train_data)
+        popn.release_data(xv_data)
+
+
 def support_table(support, A_true):
     """Recovered support (N_pre, N_post) bool against the true adjacency matrix: true / false positives and negatives."""
     A = np.asarray(A_true) != 0
@@ -144,6 +173,14 @@ def support_table(support, A_true):
     tp, fp, fn, tn = np.sum(S & A), np.sum(S & ~A), np.sum(~S & A), np.sum(~S & ~A)
     return "support against the true adjacency: %d true positives, %d false positives, %d false negatives, %d true negatives" \
         % (tp, fp, fn, tn)
+
+
+def heldout_table(popn, data, x, n_draws):
+    from theano_pyglm_amd.inference import model_compare
+    t0 = time.time()
+    res = run_heldout_lpd(popn, data, x, n_draws)
+    return model_compare.format_table(res) + "\n(refit on the training split, %d draws and their held-out density in %.2f s)" \
+        % (n_draws, time.time() - t0)
 
 
 def main():
@@ -154,6 +191,9 @@ def main():
     ap.add_argument('--path', action='store_true',
                     help='one warm-started group-lasso path of the proximal-gradient solver with a lam per neuron, instead of '
                          'the grid of BFGS sweeps')
+    ap.add_argument('--heldout-lpd', type=int, nargs='?', const=100, default=0, metavar='N',
+                    help='after the sweep: held-out log predictive density of the winner on the 25 %% split, from N (default '
+                         '100) NUTS draws per neuron on the training split')
     args = ap.parse_args()
     data = load_data(args.dataFile)
     popn, popn_true, x_true = initialize_test_harness(args.model, data, os.path.dirname(args.dataFile))
@@ -168,6 +208,8 @@ def main():
             A_true = x_true.get('net', {}).get('graph', {}).get('A')
             if A_true is not None:
                 print(support_table(path['refit']['support'].T, np.reshape(A_true, (popn.N, popn.N))))
+        if args.heldout_lpd:
+            print(heldout_table(popn, data, best_x, args.heldout_lpd))
         with open(os.path.join(args.resultsDir, 'results.pkl'), 'wb') as f:
             pickle.dump(best_x, f, protocol=-1)
         return
@@ -179,6 +221,8 @@ def main():
     print("Best Total LL: %f" % popn.compute_ll(best_x))
     if popn_true is not None:
         print("True LL: %f" % popn_true.compute_ll(x_true))
+    if args.heldout_lpd:
+        print(heldout_table(popn, data, best_x, args.heldout_lpd))
     with open(os.path.join(args.resultsDir, 'results.pkl'), 'wb') as f:
         pickle.dump(best_x, f, protocol=-1)
 

@@ -395,6 +395,24 @@ class Population(object):
             stats += st
         return [np.concatenate(p) if p else np.zeros(0) for p in parts], stats
 
+    # -- model comparison ------------------------------------------------------------------
+    def compute_pointwise_ll(self, vars, block_chunks=1):
+        """The log-likelihood of every neuron under `vars` resolved in time: sums of -dt lam_t + S[t,n] log lam_t over blocks
+        of block_chunks * 256 consecutive bins (the last block of a sequence may be short), one forward pass and one
+        segmented sum on the device per data sequence (pgl_pointwise).  Returns (n_blocks_total, N), the data sequences one
+        after the other; a column sums to that neuron's ll.  Given the spike history the blocks are conditionally
+        independent terms: the pointwise values of inference/model_compare.py."""
+        if self._time_shard is not None:
+            raise ValueError("the pointwise log-likelihood of a time-sharded population is not implemented")
+        self._check_vars(vars)
+        theta = self.theta_matrix(vars)
+        Weff = self.W_eff(vars)
+        parts = []
+        for data in self.data_sequences:
+            self.set_data(data)
+            parts.append(self._handle(self._current).pointwise(theta, Weff, block_chunks))
+        return np.concatenate(parts, axis=0) if parts else np.zeros((0, self.N))
+
     # -- state ---------------------------------------------------------------------------
     def eval_state(self, vars):
         """population.py:88-120: rates, currents and component state of every neuron."""
