@@ -93,7 +93,7 @@ typedef struct pgl_context* pgl_handle;
 
 /* What pgl_version() returns: it changes with every change of a signature or a struct below, and a binding refuses a
  * library that reports another number (theano_pyglm_amd/_lib.py: ABI_VERSION). */
-#define PGL_ABI_VERSION 109
+#define PGL_ABI_VERSION 110
 
 const char* pgl_last_error(void);
 int pgl_version(void);
@@ -844,6 +844,37 @@ int pgl_pointwise_count(pgl_handle h, int block_chunks, int64_t* n_blocks_out);
 int pgl_pointwise_dev(pgl_handle h, const double* d_theta, const double* d_Weff, int block_chunks, double* d_ll_blk,
                       double* d_acc, int64_t draw);
 int pgl_pointwise(pgl_handle h, const double* theta, const double* Weff, int block_chunks, double* ll_blk_out);
+
+/* PSIS-LOO: Pareto-smoothed importance-sampling leave-one-out (Vehtari, Gelman & Gabry 2017; Vehtari, Simpson, Gelman, Yao &
+ * Gabry 2024) of the columns of a matrix ll (S, C), element [s, c] at s * ld + c: column c holds the pointwise term of one
+ * (block, neuron) under the S posterior draws -- the matrix pgl_pointwise_dev writes draw after draw.  The reference has no
+ * pointwise criterion.  The rule of one column l_0 .. l_{S-1} (theano_pyglm_amd/csrc/pglm_psis.h):
+ *   ratios    r_s = -l_s, x_s = r_s - max r;
+ *   order     on the raw doubles l_s, before any arithmetic: descending l, ties by the draw index (smaller first);
+ *   tail      M = ceil(min(S / 5, 3 sqrt(S))); the cutoff element has rank S - M - 1 (0-based), x_cut = max(its x,
+ *             log(DBL_MIN)); the tail = the n <= M elements whose raw l is strictly smaller than the cutoff element's;
+ *   n < 5     khat = +inf and nothing is smoothed;
+ *   fit       generalized Pareto law on the excesses e_i = exp(x_tail,i) - exp(x_cut), ascending, by Zhang & Stephens (2009)
+ *             as loo / ArviZ state it: m = 30 + floor(sqrt(n)) candidates b_i = 1 / e_n + (1 - sqrt(m / (i - 0.5))) /
+ *             (3 e_q), q = floor(n / 4 + 0.5);  k_i = mean log1p(-b_i e);  L_i = n (log(-b_i / k_i) - k_i - 1);
+ *             w_i = 1 / sum_j exp(L_j - L_i), those below 10 DBL_EPSILON dropped, the rest renormalised;  b = sum w_i b_i;
+ *             k = mean log1p(-b e);  sigma = -k / b;  khat = (n k + 5) / (n + 10);
+ *   smooth    (khat finite) the tail element of rank i of n:  x = log(exp(x_cut) + sigma expm1(-khat log1p(-p_i)) / khat),
+ *             p_i = (i - 0.5) / n; the limit -sigma log1p(-p_i) for |khat| < DBL_EPSILON;
+ *   weights   every x truncated at 0;  lw_s = x_s - logsumexp(x)  (shifted by max x);
+ *   out       planes (PGL_PSIS_NOUT = 4, C):  elpd = log sum_s exp(lw_s + l_s) (shifted by its maximum), khat,
+ *             n_eff = 1 / sum_s exp(2 lw_s), the tail length n.
+ *   A column that holds a NaN or an infinite l gives four NaNs (and NaN weights) and touches no other column.
+ * Every sum has a fixed order (pglm_psis.hip.h) and nothing is atomic: two calls give the same bits, and a column gives the
+ * same bits alone and among others.  One workgroup per column, the column in LDS: S <= PGL_PSIS_MAX_DRAWS (4096).
+ * psis_loo_dev: device pointers, asynchronous on the handle's stream; needs no data on the handle.  d_out (4, C); d_lw the log
+ *     weights (S, C) at the same ld, or NULL.  d_lw must not overlap d_ll.
+ * psis_loo:     host pointers, ll (S, C) and lw (S, C) or NULL contiguous, out (4, C).
+ * S < 2, C < 1, ld < C or a NULL pointer: PGL_ERR_ARG;  S > PGL_PSIS_MAX_DRAWS: PGL_ERR_UNSUPPORTED. */
+#define PGL_PSIS_NOUT 4
+#define PGL_PSIS_MAX_DRAWS 4096
+int pgl_psis_loo_dev(pgl_handle h, const double* d_ll, int64_t S, int64_t C, int64_t ld, double* d_out, double* d_lw);
+int pgl_psis_loo(pgl_handle h, const double* ll, int64_t S, int64_t C, double* out, double* lw);
 
 /* Spike-triggered average, pyglm/utils/sta.py:6-85 (used by smart_init.py:28-98 and 100-158):
  *   A[i,l,d] = sum_t S[t,n_i] * istim[t-l,d] / sum_t S[t,n_i],  l = 0..L-1, terms with t-l < 0 dropped,

@@ -54,11 +54,15 @@ SYMBOLS = [
     'pgl_newton_trial_dev', 'pgl_newton_search_step_dev',
     'pgl_rescale_count', 'pgl_rescale_dev', 'pgl_rescale',
     'pgl_pointwise_count', 'pgl_pointwise_dev', 'pgl_pointwise',
+    'pgl_psis_loo_dev', 'pgl_psis_loo',
     'pgl_simulate_streams', 'pgl_simulate_batch', 'pgl_simulate_batch_dev', 'pgl_simulate_batch_plan',
 ]
 
 
-ABI_VERSION = 109                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
+ABI_VERSION = 110                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
+
+PSIS_NOUT = 4                       # PGL_PSIS_NOUT: planes of psis_loo's result -- elpd, khat, n_eff, tail length
+PSIS_MAX_DRAWS = 4096               # PGL_PSIS_MAX_DRAWS: the draws a workgroup's LDS holds; more: PGL_ERR_UNSUPPORTED
 
 
 class PglError(RuntimeError):
@@ -186,6 +190,8 @@ def load():
     lib.pgl_pointwise_count.argtypes = [vp, C.c_int, vp]
     lib.pgl_pointwise_dev.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int64]
     lib.pgl_pointwise.argtypes = [vp, vp, vp, C.c_int, vp]
+    lib.pgl_psis_loo_dev.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp]
+    lib.pgl_psis_loo.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp]
     # the lock-step methods; pr: const pgl_prior*
     lib.pgl_bfgs_state_doubles.argtypes = [C.c_int, C.c_int]
     lib.pgl_bfgs_init_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double]
@@ -673,6 +679,50 @@ class DeviceGlm(object):
         out = np.empty((self.pointwise_count(block_chunks), self.N))
         _chk(self.lib.pgl_pointwise(self.h, _ptr(th), _ptr(We), int(block_chunks), _ptr(out)))
         return out
+
+    # -- PSIS-LOO of the columns of a pointwise matrix over draws (pgl_psis_loo*) -----------------------
+    def psis_loo(self, ll, out=None, weights=False):
+        """PSIS-LOO of every column of the torch device tensor ll (S, ...) f64, the draws on axis 0 (pgl_psis_loo_dev).  The
+        trailing axes are flattened to columns; they must be contiguous among themselves, and the stride of axis 0 is the
+        leading dimension, so a last-axis slice full[:, a:b] of a matrix is served where it is.  Returns out (4, ...) on ll's
+        device -- elpd, khat, n_eff, tail length per column; `out`: a contiguous tensor of that shape to write into.
+        weights=True also returns the log weights, a tensor of ll's shape and strides; weights=<tensor of ll's shape and
+        strides> writes them there (it must not overlap ll).  Asynchronous on the handle's stream."""
+        import torch
+        if not (isinstance(ll, torch.Tensor) and ll.is_cuda and ll.dtype == torch.float64 and ll.dim() >= 2 and ll.numel() > 0):
+            raise ValueError("psis_loo: a float64 device tensor (S, ...)")
+        S, shape = int(ll.shape[0]), tuple(ll.shape[1:])
+        ncol = int(np.prod(shape))
+        ld = int(ll.stride(0))
+        if not ll[0].is_contiguous() or ld < ncol:
+            raise ValueError("psis_loo: the trailing axes must be contiguous and the draw stride at least their size")
+        if out is None:
+            out = torch.empty((PSIS_NOUT,) + shape, dtype=torch.float64, device=ll.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and
+                  tuple(out.shape) == (PSIS_NOUT,) + shape):
+            raise ValueError("psis_loo: out must be a contiguous float64 device tensor %s" % ((PSIS_NOUT,) + shape,))
+        lw = None
+        if weights is True:
+            lw = torch.empty_strided(tuple(ll.shape), tuple(ll.stride()), dtype=torch.float64, device=ll.device)
+        elif weights is not False and weights is not None:
+            lw = weights
+            if not (isinstance(lw, torch.Tensor) and lw.is_cuda and lw.dtype == torch.float64 and lw.shape == ll.shape and
+                    lw.stride() == ll.stride()):
+                raise ValueError("psis_loo: weights must be a float64 device tensor of ll's shape and strides")
+        _chk(self.lib.pgl_psis_loo_dev(self.h, C.c_void_p(ll.data_ptr()), S, ncol, ld, C.c_void_p(out.data_ptr()),
+                                       C.c_void_p(lw.data_ptr()) if lw is not None else None))
+        return out if lw is None else (out, lw)
+
+    def psis_loo_host(self, ll, weights=False):
+        """The same with a host array ll (S, ...): -> out (4, ...), or (out, lw) with weights=True (pgl_psis_loo)."""
+        a = np.ascontiguousarray(ll, dtype=np.float64)
+        if a.ndim < 2 or a.size == 0:
+            raise ValueError("psis_loo_host: an array (S, ...)")
+        S, shape = a.shape[0], a.shape[1:]
+        out = np.empty((PSIS_NOUT,) + shape)
+        lw = np.empty(a.shape) if weights else None
+        _chk(self.lib.pgl_psis_loo(self.h, _ptr(a), int(S), int(np.prod(shape)), _ptr(out), _ptr(lw) if weights else None))
+        return (out, lw) if weights else out
 
     # -- lock-step optimiser bookkeeping (device pointers as integers; asynchronous on the handle's stream) --
     def bfgs_state_doubles(self, M, P):

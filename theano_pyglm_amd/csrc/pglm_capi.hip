@@ -124,6 +124,7 @@ struct pgl_context {
     // time rescaling (pgl_rescale_dev): in-chunk sums at the events, chunk totals and their prefix; pgl_rescale: the device
     // copies of its offsets and results
     DevBuf rs_pre, rs_tot, rs_cum, rs_off, rs_tau, rs_stats;
+    DevBuf psis_in, psis_out, psis_lw;   // pgl_psis_loo: the device copies of its host arrays
     DevBuf pw_part, pw_out;              // pointwise ll (pgl_pointwise_dev): chunk sums; pgl_pointwise: the device copy of ll_blk_out
     std::vector<double> hvp_host;        // pgl_hvp: theta and Weff of its last prepare (a CG solve repeats them: no new prepare)
 };
@@ -308,7 +309,7 @@ int pgl_destroy(pgl_handle h)
                       &h->spart, &h->sepC, &h->sepA, &h->sepAT, &h->sepD, &h->YfT, &h->Hb, &h->wpart, &h->QvT, &h->staA,
                       &h->Cbuf, &h->hvp_idx, &h->hvp_Weff, &h->hvp_ll, &h->hvp_v, &h->hvp_out,
                       &h->hess_part, &h->hess_out, &h->rs_pre, &h->rs_tot, &h->rs_cum, &h->rs_off, &h->rs_tau, &h->rs_stats,
-                      &h->pw_part, &h->pw_out};
+                      &h->pw_part, &h->pw_out, &h->psis_in, &h->psis_out, &h->psis_lw};
     for (DevBuf* b : bufs) release(*b);
     for (int s = 0; s < pgl_context::NEV; ++s)
         for (int i = 0; i < 4; ++i)
@@ -2947,6 +2948,40 @@ int pgl_pointwise(pgl_handle h, const double* theta, const double* Weff, int blo
                            nullptr, 0);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(ll_blk_out, h->pw_out.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return PGL_OK;
+}
+
+// ---- PSIS-LOO of the columns of a pointwise matrix (pglm_psis.hip.h) ---------------------------------------------------
+int pgl_psis_loo_dev(pgl_handle h, const double* d_ll, int64_t S, int64_t C, int64_t ld, double* d_out, double* d_lw)
+{
+    if (!h || !d_ll || !d_out || S < 2 || C < 1 || ld < C) return fail(PGL_ERR_ARG, "bad argument");
+    if (C > 0x7fffffff) return fail(PGL_ERR_ARG, "at most 2^31 - 1 columns per call");
+    if (S > PGL_PSIS_MAX_DRAWS)
+        return fail(PGL_ERR_UNSUPPORTED, "PSIS-LOO: more than PGL_PSIS_MAX_DRAWS = " + std::to_string(PGL_PSIS_MAX_DRAWS) +
+                                         " draws do not fit a workgroup's LDS");
+    HIPCHK(hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_psis_column, dim3((unsigned)C), dim3(PGL_PSIS_THREADS), psis_lds_bytes(S), h->stream, d_ll,
+                       (long long)S, (long long)C, (long long)ld, d_out, d_lw);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+int pgl_psis_loo(pgl_handle h, const double* ll, int64_t S, int64_t C, double* out, double* lw)
+{
+    if (!h || !ll || !out || S < 2 || C < 1) return fail(PGL_ERR_ARG, "bad argument");
+    if (S > PGL_PSIS_MAX_DRAWS) return pgl_psis_loo_dev(h, ll, S, C, C, out, lw);       // (its error, before any copy)
+    HIPCHK(hipSetDevice(h->device));
+    const size_t bytes = (size_t)S * C * 8, obytes = (size_t)PGL_PSIS_NOUT * C * 8;
+    ENSURE(h->psis_in, bytes);
+    ENSURE(h->psis_out, obytes);
+    if (lw) ENSURE(h->psis_lw, bytes);
+    HIPCHK(hipMemcpyAsync(h->psis_in.p, ll, bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));          // (pageable source)
+    int rc = pgl_psis_loo_dev(h, (const double*)h->psis_in.p, S, C, C, (double*)h->psis_out.p, lw ? (double*)h->psis_lw.p : nullptr);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(out, h->psis_out.p, obytes, hipMemcpyDeviceToHost, h->stream));
+    if (lw) HIPCHK(hipMemcpyAsync(lw, h->psis_lw.p, bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return PGL_OK;
 }

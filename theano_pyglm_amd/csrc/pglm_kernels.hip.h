@@ -36,6 +36,8 @@
 // pglm_simulate.hip.h).
 // Model comparison needs the log-likelihood of a draw resolved in time: block sums behind the forward-only pass, folded over
 // the draws on the device (k_pw_chunk, k_pw_block, pglm_pointwise.hip.h).
+// PSIS-LOO takes the matrix of those terms over the draws one column per workgroup: ranks, generalized-Pareto fit, smoothed
+// weights (k_psis_column, pglm_psis.hip.h).
 #pragma once
 //
 // The kernels live in one header per family; this file is the translation unit's table of contents.
@@ -62,4 +64,5 @@
 #include "pglm_prox.hip.h"
 #include "pglm_rescale.hip.h"
 #include "pglm_pointwise.hip.h"
+#include "pglm_psis.hip.h"
 #include "pglm_simulate.hip.h"

@@ -23,6 +23,8 @@ ESS and the Laplace log evidence beside it.
 without a standard error (one run gives none), plus the stages and the resamplings of every neuron.
 --waic (with --hmc N or --nuts N) prints the WAIC table of those draws after them (inference/model_compare.py: the pointwise
 log-likelihood of every draw in blocks of 10240 bins, accumulated on the device).
+--loo (with --hmc N or --nuts N) prints the PSIS-LOO table of those draws: elpd_loo, p_loo, looic, se and the khat diagnostic
+(model_compare.loo_glms: Pareto smoothing of the (draws, blocks, neurons) matrix on the device).
 """
 import argparse
 import os
@@ -52,7 +54,7 @@ def initialize_test_harness(model_name, data, data_dir=None):
 
 
 def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False, gof=False, ppc=0, hmc=0, ais=0,
-                   hmc_mass='laplace', prox=False, laplace_device=False, ais_mass='laplace', nuts=0, smc=0, newton=False, waic=False):
+                   hmc_mass='laplace', prox=False, laplace_device=False, ais_mass='laplace', nuts=0, smc=0, newton=False, waic=False, loo=False):
     """test/synth_map.py:10-32."""
     popn, popn_true, x_true = initialize_test_harness(model_name, data, data_dir)
     x0 = popn.sample(rng)
@@ -74,9 +76,9 @@ def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, r
         from theano_pyglm_amd.inference import predictive
         print(predictive.format_table(predictive.predictive_counts(popn, x_inf, ppc)))
     if hmc:
-        print(hmc_bias_table(popn, x_inf, hmc, hmc_mass, laplace_device, waic=waic))
+        print(hmc_bias_table(popn, x_inf, hmc, hmc_mass, laplace_device, waic=waic, loo=loo))
     if nuts:
-        print(nuts_bias_table(popn, x_inf, nuts, hmc_mass, laplace_device, waic=waic))
+        print(nuts_bias_table(popn, x_inf, nuts, hmc_mass, laplace_device, waic=waic, loo=loo))
     if ais:
         print(ais_evidence_table(popn, x_inf, ais, laplace_device, ais_mass))
     if smc:
@@ -98,10 +100,10 @@ def prox_table(popn, x):
     return "\n".join(lines)
 
 
-def hmc_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=False):
+def hmc_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=False, loo=False):
     """n_draws kept HMC draws from x with the mass matrix `mass` ('laplace' or 'laplace_dense'): one line per neuron, bias
     posterior mean +- sd (and the Laplace standard error).  laplace_device: the Laplace factorisations (the dense mass
-    matrix and the standard errors) run on the device.  waic: the WAIC table of the draws follows (waic_table)."""
+    matrix and the standard errors) run on the device.  waic / loo: the WAIC / PSIS-LOO table of the draws follows (waic_table, loo_table)."""
     from theano_pyglm_amd.inference import batched_hmc
     from theano_pyglm_amd.inference.laplace import laplace_glms
     t0 = time.time()
@@ -122,13 +124,15 @@ def hmc_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=
         lines.append(ln + ("   %10.4f" % se[n] if se is not None else ""))
     if waic:
         lines.append(waic_table(popn, x, res['samples']))
+    if loo:
+        lines.append(loo_table(popn, x, res['samples']))
     return "\n".join(lines)
 
 
-def nuts_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=False, **kw):
+def nuts_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=False, loo=False, **kw):
     """hmc_bias_table with the No-U-Turn sampler: the same columns ('accept' is the mean acceptance statistic after
     warm-up) plus the median tree depth of the kept transitions and the divergent transitions after warm-up.  kw: further
-    arguments of sample_glms_nuts (n_warmup, max_depth, ...).  waic: the WAIC table of the draws follows (waic_table)."""
+    arguments of sample_glms_nuts (n_warmup, max_depth, ...).  waic / loo: the WAIC / PSIS-LOO table of the draws follows (waic_table, loo_table)."""
     import numpy as np
     from theano_pyglm_amd.inference import batched_nuts
     from theano_pyglm_amd.inference.laplace import laplace_glms
@@ -153,6 +157,8 @@ def nuts_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic
         lines.append(ln + ("   %10.4f" % se[n] if se is not None else ""))
     if waic:
         lines.append(waic_table(popn, x, res['samples']))
+    if loo:
+        lines.append(loo_table(popn, x, res['samples']))
     return "\n".join(lines)
 
 
@@ -163,6 +169,15 @@ def waic_table(popn, x, samples, block_chunks=40):
     t0 = time.time()
     res = model_compare.waic_glms(popn, x, samples, block_chunks=block_chunks)
     return model_compare.format_table(res) + "\n(pointwise log-likelihood of %d draws in %.2f s)" % (res['n_draws'], time.time() - t0)
+
+
+def loo_table(popn, x, samples, block_chunks=40):
+    """The PSIS-LOO table of posterior draws (samples (S, N, P) of all neurons) on the population's data, in blocks of 256
+    block_chunks bins: the matrix of pointwise terms stays on the device (model_compare.loo_glms)."""
+    from theano_pyglm_amd.inference import model_compare
+    t0 = time.time()
+    res = model_compare.loo_glms(popn, x, samples, block_chunks=block_chunks)
+    return model_compare.format_table(res) + "\n(pointwise log-likelihood and PSIS of %d draws in %.2f s)" % (res['n_draws'], time.time() - t0)
 
 
 def ais_evidence_table(popn, x, n_particles, laplace_device=False, mass='laplace'):
@@ -247,6 +262,9 @@ def parser():
     ap.add_argument('--waic', action='store_true',
                     help='with --hmc N or --nuts N: the WAIC of every neuron from those draws (pointwise log-likelihood in blocks '
                          'of 10240 bins, accumulated over the draws on the device)')
+    ap.add_argument('--loo', action='store_true',
+                    help='with --hmc N or --nuts N: PSIS-LOO of every neuron from those draws, with the khat diagnostic per '
+                         'block (the matrix of pointwise terms stays on the device; beside or instead of --waic)')
     return ap
 
 
@@ -257,7 +275,7 @@ def main(argv=None):
     run_synth_test(args.model, data, args.resultsDir, os.path.dirname(args.dataFile),
                    False if args.sequential else ('torch' if args.newton_cg else None), use_rop=args.newton_cg, gof=args.gof, ppc=args.ppc, hmc=args.hmc, ais=args.ais,
                    hmc_mass=args.hmc_mass, prox=args.prox, laplace_device=args.laplace_device, ais_mass=args.ais_mass, nuts=args.nuts, smc=args.smc,
-                   newton=args.newton, waic=args.waic)
+                   newton=args.newton, waic=args.waic, loo=args.loo)
 
 
 if __name__ == '__main__':
