@@ -93,7 +93,7 @@ typedef struct pgl_context* pgl_handle;
 
 /* What pgl_version() returns: it changes with every change of a signature or a struct below, and a binding refuses a
  * library that reports another number (theano_pyglm_amd/_lib.py: ABI_VERSION). */
-#define PGL_ABI_VERSION 110
+#define PGL_ABI_VERSION 111
 
 const char* pgl_last_error(void);
 int pgl_version(void);
@@ -891,6 +891,32 @@ int pgl_sta(pgl_handle h, const double* stim, int64_t Tstim, int D, double dt_st
  * A_out == NULL has left on the device (same n, L, D; consumed by this call) -- the initialisation of a wide stimulus never
  * moves its 157 MB of averages over PCIe. */
 int pgl_leading_singular_pairs(pgl_handle h, const double* A, int n, int L, int D, double* U, double* sigma, double* V);
+/* Degenerate matrices of a batch: a matrix of zeros returns sigma = 0 and zeros for both vectors (the start vector e_0 of
+ * the zero Gram matrix does not survive the alternating steps: A e_0 = 0 stays unnormalised); a matrix that holds a NaN
+ * returns NaN for sigma and in every component of both vectors.  Either touches no other matrix of the batch: every
+ * matrix gets the bits it gets alone. */
+
+/* One thin GEMM of the stimulus path on device operands, through the launchers the library itself uses (a test entry: it
+ * lets each kernel be observed on its own, at its own tails):
+ *   C[b][m scm + n scn] = sum_{k < K} A[b][m sam + k sak] * B[b][n sbn + k sbk],  m < M, n < N, b < batch,
+ * strides in doubles, operand b at d_X + b sXb.  Nothing outside those M N batch elements of C is written.  Asynchronous on
+ * the handle's stream; needs no data on the handle.  kernel picks the instantiation:
+ *   PGL_GEMM_NT         k_gemm_nt: 64 x 64 tiles through LDS.  sak = sbk = scn = 1 (lda = sam, ldb = sbn, ldc = scm), batch = 1.
+ *   PGL_GEMM_MFMA_1/_4  k_gemm_mfma<1> / <4>: any strides (0 broadcasts), any batch.
+ *   PGL_GEMM_KC_4_1_8   k_gemm_kc<4, 1, 8>: both operands k-contiguous (sak = sbk = 1), d_A and d_B 16-byte aligned, sam and
+ *                       sbn even, K even, batch = 1.
+ *   PGL_GEMM_KC_1_0_16  k_gemm_kc<1, 0, 16>: A k-contiguous (sak = 1), 16-byte aligned, sam even; B n-contiguous (sbn = 1,
+ *                       ldb = sbk); K even, batch = 1.
+ * A precondition that does not hold, a NULL pointer, a negative stride, M, N, K or batch < 1: PGL_ERR_ARG, and nothing is
+ * launched. */
+#define PGL_GEMM_NT 0
+#define PGL_GEMM_MFMA_1 1
+#define PGL_GEMM_MFMA_4 2
+#define PGL_GEMM_KC_4_1_8 3
+#define PGL_GEMM_KC_1_0_16 4
+int pgl_gemm_dev(pgl_handle h, int kernel, const double* d_A, int64_t sam, int64_t sak, int64_t sAb, const double* d_B,
+                 int64_t sbn, int64_t sbk, int64_t sBb, double* d_C, int64_t scm, int64_t scn, int64_t sCb, int M, int N, int K,
+                 int batch);
 
 /* Population.simulate (population.py:233-389), native host implementation (no GPU needed):
  * integrate-and-fire thinning of the conditional intensity.  Per bin t: lam = nlin(X[t,:]),

@@ -26,6 +26,7 @@ def test_header_symbols_exported():
     for n in names:
         assert hasattr(lib, n), "libpyglm_hip.so does not export %s" % n
     assert sorted(_lib.SYMBOLS) == names
+    assert 'pgl_gemm_dev' in names and _lib.ABI_VERSION >= 111      # (the thin-GEMM test entry came with ABI 111)
     _lib.load()
     assert _lib.load().pgl_version() >= 100
 

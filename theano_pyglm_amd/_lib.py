@@ -35,7 +35,7 @@ SYMBOLS = [
     'pgl_timing_summary', 'pgl_set_stream',
     'pgl_set_stimulus_separable', 'pgl_ll_grad_list_dev', 'pgl_gibbs_prepare_all', 'pgl_gibbs_ll_cols', 'pgl_gibbs_update_cols', 'pgl_gibbs_currents',
     'pgl_bfgs_state_doubles', 'pgl_bfgs_init_dev', 'pgl_bfgs_trial_dev', 'pgl_bfgs_objective_dev',
-    'pgl_bfgs_linesearch_dev', 'pgl_bfgs_hmul_dev', 'pgl_bfgs_hmul_hist_dev', 'pgl_bfgs_update_dev', 'pgl_bfgs_step_dev', 'pgl_plan_kernels', 'pgl_last_kernels', 'pgl_leading_singular_pairs',
+    'pgl_bfgs_linesearch_dev', 'pgl_bfgs_hmul_dev', 'pgl_bfgs_hmul_hist_dev', 'pgl_bfgs_update_dev', 'pgl_bfgs_step_dev', 'pgl_plan_kernels', 'pgl_last_kernels', 'pgl_leading_singular_pairs', 'pgl_gemm_dev',
     'pgl_hvp_prepare_dev', 'pgl_hvp_prepare_list_dev', 'pgl_hvp_apply_dev', 'pgl_hvp',
     'pgl_ncg_state_doubles', 'pgl_ncg_init_dev', 'pgl_ncg_cg_step_dev', 'pgl_ncg_trial_dev', 'pgl_ncg_search_step_dev',
     'pgl_hmc_state_doubles', 'pgl_hmc_init_dev', 'pgl_hmc_begin_dev', 'pgl_hmc_leap_dev',
@@ -59,7 +59,9 @@ SYMBOLS = [
 ]
 
 
-ABI_VERSION = 110                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
+ABI_VERSION = 111                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
+
+GEMM_NT, GEMM_MFMA_1, GEMM_MFMA_4, GEMM_KC_4_1_8, GEMM_KC_1_0_16 = range(5)   # PGL_GEMM_*: the kernel of pgl_gemm_dev
 
 PSIS_NOUT = 4                       # PGL_PSIS_NOUT: planes of psis_loo's result -- elpd, khat, n_eff, tail length
 PSIS_MAX_DRAWS = 4096               # PGL_PSIS_MAX_DRAWS: the draws a workgroup's LDS holds; more: PGL_ERR_UNSUPPORTED
@@ -171,6 +173,8 @@ def load():
     lib.pgl_set_stream.argtypes = [vp, vp]
     lib.pgl_sta.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_double, C.c_int, vp, C.c_int, vp]
     lib.pgl_leading_singular_pairs.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    lib.pgl_gemm_dev.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, C.c_int64,
+                                 vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.pgl_ll_grad.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.pgl_ll_grad_dev.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.pgl_ll_grad_list_dev.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
@@ -509,6 +513,15 @@ class DeviceGlm(object):
         U, sig, V = np.empty((n, L)), np.empty(n), np.empty((n, D))
         _chk(self.lib.pgl_leading_singular_pairs(self.h, _ptr(A), n, L, D, _ptr(U), _ptr(sig), _ptr(V)))
         return U, sig, V
+
+    def gemm_dev(self, kernel, A, sa, B, sb, Cm, sc, M, N, K, batch=1):
+        """One thin GEMM on device operands (pgl_gemm_dev): C[b][m scm + n scn] = sum_k A[b][m sam + k sak] B[b][n sbn + k sbk].
+        kernel: GEMM_NT, GEMM_MFMA_1, GEMM_MFMA_4, GEMM_KC_4_1_8 or GEMM_KC_1_0_16.  A, B, Cm: device addresses (int) of the
+        first element; sa = (sam, sak, sAb), sb = (sbn, sbk, sBb), sc = (scm, scn, sCb), in doubles.  Asynchronous on the
+        handle's stream; PglError where the kernel's preconditions do not hold (nothing is launched then)."""
+        _chk(self.lib.pgl_gemm_dev(self.h, int(kernel), C.c_void_p(A), int(sa[0]), int(sa[1]), int(sa[2]),
+                                   C.c_void_p(B), int(sb[0]), int(sb[1]), int(sb[2]),
+                                   C.c_void_p(Cm), int(sc[0]), int(sc[1]), int(sc[2]), int(M), int(N), int(K), int(batch)))
 
     # -- hot path -------------------------------------------------------------
     def ll_grad(self, theta, Weff, n_lo=0, n_hi=None, want_grad=True):

@@ -220,6 +220,40 @@ static void launch_sepf(int which, const SepfParams& sp, hipStream_t s)
     }
 }
 
+// ---- the thin GEMMs (pglm_stim.hip.h): one launcher per kernel template, the only places that state a grid shape.  The
+// callers below and pgl_gemm_dev (the test entry) all launch through them.
+static int launch_gemm_nt(pgl_handle h, const double* A, int lda, const double* B, int ldb, double* C, int ldc,
+                          int M, int N, int K)
+{
+    dim3 grid((unsigned)((N + 63) / 64), (unsigned)((M + 63) / 64));
+    hipLaunchKernelGGL(k_gemm_nt, grid, dim3(256), 0, h->stream, A, lda, B, ldb, C, ldc, M, N, K);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+// k_gemm_mfma<NT>: any strides, a batch along blockIdx.z
+template <int NT>
+static int launch_gemm_mfma_nt(pgl_handle h, const double* A, long long sam, long long sak, long long sAb, const double* B,
+                               long long sbn, long long sbk, long long sBb, double* C, long long scm, long long scn,
+                               long long sCb, int M, int N, int K, int batch)
+{
+    hipLaunchKernelGGL(k_gemm_mfma<NT>, dim3((M + 15) / 16, (N + 16 * NT - 1) / (16 * NT), batch), dim3(512), 0, h->stream, A,
+                       sam, sak, B, sbn, sbk, C, scm, scn, M, N, K, sAb, sBb, sCb);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+// k_gemm_kc<NT, BK, NB>: A k-contiguous, 16-byte aligned with lda even, K even; B likewise (BK = 1) or n-contiguous (BK = 0)
+template <int NT, int BK, int NB>
+static int launch_gemm_kc(pgl_handle h, const double* A, long long lda, const double* B, long long ldb, double* C,
+                          long long scm, long long scn, int M, int N, int K)
+{
+    hipLaunchKernelGGL((k_gemm_kc<NT, BK, NB>), dim3((unsigned)((M + 15) / 16), (unsigned)((N + 16 * NT - 1) / (16 * NT))),
+                       dim3(512), 0, h->stream, A, lda, B, ldb, C, scm, scn, M, N, K);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
 // one workgroup per replicate (k_simulate, pglm_simulate.hip.h)
 template <int NLIN, bool RING_LDS>
 static int sim_launch(const SimParams& sp, int n_rep, int threads, size_t lds, hipStream_t s)
@@ -584,15 +618,6 @@ int pgl_set_stimulus(pgl_handle h, const double* stim, int64_t Tstim, int D, dou
     return PGL_OK;
 }
 
-static int launch_gemm_nt(pgl_handle h, const double* A, int lda, const double* B, int ldb, double* C, int ldc,
-                          int M, int N, int K)
-{
-    dim3 grid((unsigned)((N + 63) / 64), (unsigned)((M + 63) / 64));
-    hipLaunchKernelGGL(k_gemm_nt, grid, dim3(256), 0, h->stream, A, lda, B, ldb, C, ldc, M, N, K);
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
-}
-
 // Frame-rate coefficient table of the separable stimulus (k_sepf_fwd): for bin t = q F + o, base = max(F - M, 0),
 //   C[t][j][bt] = sum_{tau = 1 .. min(Rt, t)} basis_t[tau-1][bt] * (weight of frame base + j in np.interp at bin t - tau)
 // for t < q (M + 1); later bins repeat the rows q M + o.  np.interp between frames f = s / q and f + 1 at bin s
@@ -784,15 +809,9 @@ static int launch_gemm_mfma(pgl_handle h, const double* A, long long sam, long l
     // operands whose m / n index is the contiguous one load whole 128-byte lines per 16-lane group; a k-contiguous
     // operand costs a line per lane (pick A for it: one tile per wave against NT of B)
     const int mb = (M + 15) / 16;
-    if ((long long)mb * ((N + 63) / 64) >= 128) {       // 16 x 64 per wave; else 16 x 16 (more workgroups)
-        hipLaunchKernelGGL(k_gemm_mfma<4>, dim3(mb, (N + 63) / 64), dim3(512), 0, h->stream, A, sam, sak, B, sbn, sbk,
-                           C, scm, scn, M, N, K);
-    } else {
-        hipLaunchKernelGGL(k_gemm_mfma<1>, dim3(mb, (N + 15) / 16), dim3(512), 0, h->stream, A, sam, sak, B, sbn, sbk,
-                           C, scm, scn, M, N, K);
-    }
-    HIPCHK(hipGetLastError());
-    return PGL_OK;
+    if ((long long)mb * ((N + 63) / 64) >= 128)         // 16 x 64 per wave; else 16 x 16 (more workgroups)
+        return launch_gemm_mfma_nt<4>(h, A, sam, sak, 0, B, sbn, sbk, 0, C, scm, scn, 0, M, N, K, 1);
+    return launch_gemm_mfma_nt<1>(h, A, sam, sak, 0, B, sbn, sbk, 0, C, scm, scn, 0, M, N, K, 1);
 }
 
 static int launch_sepf_any(pgl_handle h, int which, const SepfParams& sp)
@@ -814,10 +833,8 @@ static int sepf_forward(pgl_handle h, const Plan& pl, const double* d_theta, Sep
     int rc = PGL_OK;
     const double* wx = d_theta + 1 + h->sepBt;
     if (gemm_aligned(h->zf.p, h->sepBx) && gemm_aligned(wx, P)) {      // m = f, n = n, k = x (even): both operands k-contiguous
-        hipLaunchKernelGGL((k_gemm_kc<4, 1, 8>), dim3((unsigned)((h->sepT + 15) / 16), (unsigned)((pl.npost + 63) / 64)), dim3(512),
-                           0, h->stream, (const double*)h->zf.p, (long long)h->sepBx, wx, (long long)P, (double*)h->YfT.p,
-                           (long long)ldy, 1LL, (int)h->sepT, pl.npost, h->sepBx);
-        HIPCHK(hipGetLastError());
+        rc = launch_gemm_kc<4, 1, 8>(h, (const double*)h->zf.p, (long long)h->sepBx, wx, (long long)P, (double*)h->YfT.p,
+                                     (long long)ldy, 1LL, (int)h->sepT, pl.npost, h->sepBx);
     } else {                                                           // m = n, n = f, k = x
         rc = launch_gemm_mfma(h, wx, P, 1, (const double*)h->zfT.p, 1, h->sepT, (double*)h->YfT.p, 1, ldy, pl.npost,
                               (int)h->sepT, h->sepBx);
@@ -860,11 +877,9 @@ static int sepf_backward(pgl_handle h, SepfParams& sp, double* d_grad, bool fuse
     if (rc) return rc;
     // d ll / d w_x[n][x] = sum_f (stim . basis_x)[f][x] QvT[f][n]
     if (gemm_aligned(h->zfT.p, h->sepT)) {                             // m = x (rows of zfT: f contiguous), n = n, k = f
-        hipLaunchKernelGGL((k_gemm_kc<1, 0, 16>), dim3((unsigned)((h->sepBx + 15) / 16), (unsigned)((sp.npost + 15) / 16)), dim3(512),
-                           0, h->stream, (const double*)h->zfT.p, (long long)h->sepT, (const double*)h->QvT.p, (long long)sp.ldy,
-                           d_grad + 1 + h->sepBt, 1LL, (long long)sp.P, h->sepBx, sp.npost, (int)h->sepT);
-        HIPCHK(hipGetLastError());
-        return PGL_OK;
+        return launch_gemm_kc<1, 0, 16>(h, (const double*)h->zfT.p, (long long)h->sepT, (const double*)h->QvT.p,
+                                        (long long)sp.ldy, d_grad + 1 + h->sepBt, 1LL, (long long)sp.P, h->sepBx, sp.npost,
+                                        (int)h->sepT);
     }
     return launch_gemm_mfma(h, (const double*)h->zf.p, 1, h->sepBx, (const double*)h->QvT.p, 1, sp.ldy,
                             d_grad + 1 + h->sepBt, 1, sp.P, h->sepBx, sp.npost, (int)h->sepT);
@@ -936,10 +951,9 @@ int pgl_sta(pgl_handle h, const double* stim, int64_t Tstim, int D, double dt_st
         }
         if (e == hipSuccess) {                                    // A (nSel L, D) = Wt (nSel L, Tstim) . stim (Tstim, D)
             const int Mrows = nSel * L;
-            hipLaunchKernelGGL((k_gemm_kc<1, 0, 16>), dim3((unsigned)((Mrows + 15) / 16), (unsigned)((D + 15) / 16)), dim3(512), 0,
-                               h->stream, (const double*)dW.p, (long long)Tstim, (const double*)dstim.p, (long long)D,
-                               (double*)dA.p, (long long)D, 1LL, Mrows, D, (int)Tstim);
-            e = hipGetLastError();
+            if (launch_gemm_kc<1, 0, 16>(h, (const double*)dW.p, (long long)Tstim, (const double*)dstim.p, (long long)D,
+                                         (double*)dA.p, (long long)D, 1LL, Mrows, D, (int)Tstim))
+                e = hipErrorLaunchFailure;
         }
         if (e == hipSuccess && A_out)
             e = hipMemcpyAsync(A_out, dA.p, (size_t)nSel * LD * 8, hipMemcpyDeviceToHost, h->stream);
@@ -2664,15 +2678,11 @@ int pgl_leading_singular_pairs(pgl_handle h, const double* A, int n, int L, int 
         return done(PGL_ERR_HIP);
     const double* a = (const double*)dA.p;
     const long long sa = (long long)L * D, sg = (long long)m * m;
+    int launch_rc = PGL_OK;
     auto gemm = [&](const double* Am, long long sam, long long sak, long long sAb, const double* Bm, long long sbn, long long sbk,
                     long long sBb, double* C, long long scm, long long scn, long long sCb, int M, int N, int K) {
-        if (N >= 64) {
-            hipLaunchKernelGGL(k_gemm_mfma<4>, dim3((M + 15) / 16, (N + 63) / 64, n), dim3(512), 0, h->stream, Am, sam, sak, Bm, sbn,
-                               sbk, C, scm, scn, M, N, K, sAb, sBb, sCb);
-        } else {
-            hipLaunchKernelGGL(k_gemm_mfma<1>, dim3((M + 15) / 16, (N + 15) / 16, n), dim3(512), 0, h->stream, Am, sam, sak, Bm, sbn,
-                               sbk, C, scm, scn, M, N, K, sAb, sBb, sCb);
-        }
+        if (N >= 64) launch_rc |= launch_gemm_mfma_nt<4>(h, Am, sam, sak, sAb, Bm, sbn, sbk, sBb, C, scm, scn, sCb, M, N, K, n);
+        else launch_rc |= launch_gemm_mfma_nt<1>(h, Am, sam, sak, sAb, Bm, sbn, sbk, sBb, C, scm, scn, sCb, M, N, K, n);
     };
     // G = A A^T (wide) or A^T A (tall); element (i, j) of the small side
     if (wide) gemm(a, D, 1, sa, a, D, 1, sa, (double*)dG0.p, m, 1, sg, m, m, D);
@@ -2705,7 +2715,7 @@ int pgl_leading_singular_pairs(pgl_handle h, const double* A, int n, int L, int 
     }
     to_big();                                              // |A^T x| (wide) or |A x| (tall) = sigma_0
     hipLaunchKernelGGL(k_lsp_normalize, dim3(n), dim3(1024), 0, h->stream, y, big, (double*)dn.p);
-    if (hipGetLastError() != hipSuccess) return done(fail(PGL_ERR_HIP, "leading singular pairs: launch failed"));
+    if (launch_rc || hipGetLastError() != hipSuccess) return done(fail(PGL_ERR_HIP, "leading singular pairs: launch failed"));
     double* Uo = wide ? x : y;
     double* Vo = wide ? y : x;
     bool ok = hipMemcpyAsync(U, Uo, (size_t)n * L * 8, hipMemcpyDeviceToHost, h->stream) == hipSuccess &&
@@ -2727,6 +2737,43 @@ int pgl_leading_singular_pairs(pgl_handle h, const double* A, int n, int L, int 
         }
     }
     return done(PGL_OK);
+}
+
+// One thin GEMM on device operands through the launchers production uses (tests observe each instantiation on its own).
+int pgl_gemm_dev(pgl_handle h, int kernel, const double* d_A, int64_t sam, int64_t sak, int64_t sAb, const double* d_B,
+                 int64_t sbn, int64_t sbk, int64_t sBb, double* d_C, int64_t scm, int64_t scn, int64_t sCb, int M, int N, int K,
+                 int batch)
+{
+    if (!h || !d_A || !d_B || !d_C) return fail(PGL_ERR_ARG, "pgl_gemm_dev: null argument");
+    if (M <= 0 || N <= 0 || K <= 0 || batch <= 0 || batch > 65535) return fail(PGL_ERR_ARG, "pgl_gemm_dev: bad shape");
+    if (sam < 0 || sak < 0 || sbn < 0 || sbk < 0 || scm < 0 || scn < 0 || sAb < 0 || sBb < 0 || sCb < 0)
+        return fail(PGL_ERR_ARG, "pgl_gemm_dev: negative stride");
+    const bool kc = kernel == PGL_GEMM_KC_4_1_8 || kernel == PGL_GEMM_KC_1_0_16;
+    if ((kc || kernel == PGL_GEMM_NT) && batch != 1) return fail(PGL_ERR_ARG, "pgl_gemm_dev: this kernel takes no batch");
+    HIPCHK(hipSetDevice(h->device));
+    switch (kernel) {
+    case PGL_GEMM_NT:
+        if (sak != 1 || sbk != 1 || scn != 1) return fail(PGL_ERR_ARG, "pgl_gemm_dev: k_gemm_nt needs unit k and n strides");
+        if (sam > 0x7fffffffLL || sbn > 0x7fffffffLL || scm > 0x7fffffffLL)
+            return fail(PGL_ERR_ARG, "pgl_gemm_dev: k_gemm_nt takes int leading dimensions");
+        return launch_gemm_nt(h, d_A, (int)sam, d_B, (int)sbn, d_C, (int)scm, M, N, K);
+    case PGL_GEMM_MFMA_1:
+        return launch_gemm_mfma_nt<1>(h, d_A, sam, sak, sAb, d_B, sbn, sbk, sBb, d_C, scm, scn, sCb, M, N, K, batch);
+    case PGL_GEMM_MFMA_4:
+        return launch_gemm_mfma_nt<4>(h, d_A, sam, sak, sAb, d_B, sbn, sbk, sBb, d_C, scm, scn, sCb, M, N, K, batch);
+    case PGL_GEMM_KC_4_1_8:                               // both operands k-contiguous, 16-byte loads
+        if ((K & 1) || sak != 1 || sbk != 1) return fail(PGL_ERR_ARG, "pgl_gemm_dev: k_gemm_kc needs K even and unit k strides");
+        if (!gemm_aligned(d_A, sam) || !gemm_aligned(d_B, sbn))
+            return fail(PGL_ERR_ARG, "pgl_gemm_dev: k_gemm_kc needs 16-byte aligned operands with even leading dimensions");
+        return launch_gemm_kc<4, 1, 8>(h, d_A, sam, d_B, sbn, d_C, scm, scn, M, N, K);
+    case PGL_GEMM_KC_1_0_16:                              // A k-contiguous (16-byte loads), B n-contiguous (8-byte loads)
+        if ((K & 1) || sak != 1 || sbn != 1) return fail(PGL_ERR_ARG, "pgl_gemm_dev: k_gemm_kc needs K even and unit strides");
+        if (!gemm_aligned(d_A, sam))
+            return fail(PGL_ERR_ARG, "pgl_gemm_dev: k_gemm_kc needs a 16-byte aligned A with an even leading dimension");
+        return launch_gemm_kc<1, 0, 16>(h, d_A, sam, d_B, sbk, d_C, scm, scn, M, N, K);
+    default:
+        return fail(PGL_ERR_ARG, "pgl_gemm_dev: unknown kernel");
+    }
 }
 
 // ---- time rescaling: integrated rate between consecutive events (pglm_rescale.hip.h) ---------------------------------
