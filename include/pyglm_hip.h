@@ -93,7 +93,7 @@ typedef struct pgl_context* pgl_handle;
 
 /* What pgl_version() returns: it changes with every change of a signature or a struct below, and a binding refuses a
  * library that reports another number (theano_pyglm_amd/_lib.py: ABI_VERSION). */
-#define PGL_ABI_VERSION 111
+#define PGL_ABI_VERSION 112
 
 const char* pgl_last_error(void);
 int pgl_version(void);
@@ -875,6 +875,34 @@ int pgl_pointwise(pgl_handle h, const double* theta, const double* Weff, int blo
 #define PGL_PSIS_MAX_DRAWS 4096
 int pgl_psis_loo_dev(pgl_handle h, const double* d_ll, int64_t S, int64_t C, int64_t ld, double* d_out, double* d_lw);
 int pgl_psis_loo(pgl_handle h, const double* ll, int64_t S, int64_t C, double* out, double* lw);
+
+/* Convergence diagnostics of posterior draws (Vehtari, Gelman, Simpson, Carpenter & Buerkner 2021): rank-normalised and folded
+ * split-R-hat, bulk and tail effective sample size, the Monte-Carlo standard error of the mean, and the pooled moments and
+ * quantiles, of every column of the tensor x (n, C, K) the lock-step samplers keep: draw i of chain c of column k (parameter p
+ * of neuron m, k = m * P + p) at (i * C + c) * ld + k.  The reference has no convergence diagnostic.  The rule of one column
+ * (theano_pyglm_amd/csrc/pglm_diag.h), S = C n pooled draws, every chain split into halves of h = n / 2 draws (the middle draw
+ * of an odd n is in no half):
+ *   ranks     on the raw doubles, ties averaged; order statistics from the ranks; quantiles by numpy.percentile's linear rule;
+ *   scores    z = Phi^-1((rank - 3/8) / (S + 1/4)), Phi^-1 by Wichura's AS 241 (PPND16); folded: the scores of |x - median|;
+ *   R-hat     sqrt(var+ / W) over the 2 C split chains (eqs. 1-4);
+ *   ESS       biased autocovariances per split chain, rho_t = 1 - (W - mean acov[t]) / var+, Geyer's initial positive and
+ *             monotone sequences on pairs, the final odd term, tau >= 1 / log10(N): ESS = N / tau, N = 2 C h.
+ * out: PGL_DIAG_NOUT rows of K doubles, in this order:
+ *    0 mean   1 sd (n - 1)   2 median   3 q025   4 q975   5 rhat_plain (the split-R-hat of x itself)
+ *    6 rhat (the larger of the split-R-hats of z and of the folded scores)   7 ess_bulk (of z)
+ *    8 ess_tail (the smaller of the ESS of I(x <= q05) and I(x <= q95))   9 ess_mean (of x)   10 mcse_mean = sd / sqrt(ess_mean)
+ *   11 .. 14 the truncation lags of the ESS of z, I(x <= q05), I(x <= q95) and x.
+ * A column that holds a NaN or an infinity gives PGL_DIAG_NOUT NaNs; a constant column gives its value as mean, median and
+ * quantiles, sd = 0, every ESS and lag 0, and NaN R-hats and mcse_mean.  No column touches another.
+ * Every sum has a fixed order (pglm_diag.hip.h) and nothing is atomic: two calls give the same bits, and a column gives the
+ * same bits alone and among others.  One workgroup per column, the pooled column in LDS: C n <= PGL_DIAG_MAX_DRAWS (4096).
+ * chain_diag_dev: device pointers, asynchronous on the handle's stream; needs no data on the handle.  d_out (PGL_DIAG_NOUT, K).
+ * chain_diag:     host pointers, x (n, C, K) and out (PGL_DIAG_NOUT, K) contiguous.
+ * n < 8, C < 1, K < 1, ld < K or a NULL pointer: PGL_ERR_ARG;  C n > PGL_DIAG_MAX_DRAWS: PGL_ERR_UNSUPPORTED, nothing launched. */
+#define PGL_DIAG_NOUT 15
+#define PGL_DIAG_MAX_DRAWS 4096
+int pgl_chain_diag_dev(pgl_handle h, const double* d_x, int64_t n, int64_t C, int64_t K, int64_t ld, double* d_out);
+int pgl_chain_diag(pgl_handle h, const double* x, int64_t n, int64_t C, int64_t K, double* out);
 
 /* Spike-triggered average, pyglm/utils/sta.py:6-85 (used by smart_init.py:28-98 and 100-158):
  *   A[i,l,d] = sum_t S[t,n_i] * istim[t-l,d] / sum_t S[t,n_i],  l = 0..L-1, terms with t-l < 0 dropped,

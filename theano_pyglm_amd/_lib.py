@@ -55,16 +55,21 @@ SYMBOLS = [
     'pgl_rescale_count', 'pgl_rescale_dev', 'pgl_rescale',
     'pgl_pointwise_count', 'pgl_pointwise_dev', 'pgl_pointwise',
     'pgl_psis_loo_dev', 'pgl_psis_loo',
+    'pgl_chain_diag_dev', 'pgl_chain_diag',
     'pgl_simulate_streams', 'pgl_simulate_batch', 'pgl_simulate_batch_dev', 'pgl_simulate_batch_plan',
 ]
 
 
-ABI_VERSION = 111                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
+ABI_VERSION = 112                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
 
 GEMM_NT, GEMM_MFMA_1, GEMM_MFMA_4, GEMM_KC_4_1_8, GEMM_KC_1_0_16 = range(5)   # PGL_GEMM_*: the kernel of pgl_gemm_dev
 
 PSIS_NOUT = 4                       # PGL_PSIS_NOUT: planes of psis_loo's result -- elpd, khat, n_eff, tail length
 PSIS_MAX_DRAWS = 4096               # PGL_PSIS_MAX_DRAWS: the draws a workgroup's LDS holds; more: PGL_ERR_UNSUPPORTED
+DIAG_MAX_DRAWS = 4096               # PGL_DIAG_MAX_DRAWS: the pooled draws (chains x draws) chain_diag's workgroup holds
+DIAG_ROWS = ('mean', 'sd', 'median', 'q025', 'q975', 'rhat_plain', 'rhat', 'ess_bulk', 'ess_tail', 'ess_mean', 'mcse_mean',
+             'lag_bulk', 'lag_q05', 'lag_q95', 'lag_mean')          # the rows of chain_diag's result, in PGL_DIAG_* order
+DIAG_NOUT = len(DIAG_ROWS)          # PGL_DIAG_NOUT
 
 
 class PglError(RuntimeError):
@@ -196,6 +201,8 @@ def load():
     lib.pgl_pointwise.argtypes = [vp, vp, vp, C.c_int, vp]
     lib.pgl_psis_loo_dev.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp]
     lib.pgl_psis_loo.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp]
+    lib.pgl_chain_diag_dev.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp]
+    lib.pgl_chain_diag.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp]
     # the lock-step methods; pr: const pgl_prior*
     lib.pgl_bfgs_state_doubles.argtypes = [C.c_int, C.c_int]
     lib.pgl_bfgs_init_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double]
@@ -736,6 +743,45 @@ class DeviceGlm(object):
         lw = np.empty(a.shape) if weights else None
         _chk(self.lib.pgl_psis_loo(self.h, _ptr(a), int(S), int(np.prod(shape)), _ptr(out), _ptr(lw) if weights else None))
         return (out, lw) if weights else out
+
+    # -- convergence diagnostics of the columns of a samplers' tensor (pgl_chain_diag*) ------------------
+    def chain_diag(self, x, n_chains=1, out=None):
+        """Rank-normalised split-R-hat, bulk / tail / mean ESS, MCSE and the pooled moments and quantiles of every column
+        of the torch device tensor x (n, n_chains * M, ...) f64 as the lock-step samplers keep it: draw i of chain c of
+        neuron m in row c * M + m (pgl_chain_diag_dev; the rule: csrc/pglm_diag.h).  The trailing axes must be contiguous
+        among themselves; the stride of axis 0 may exceed their size.  Returns out (DIAG_NOUT, M, ...) on x's device, rows
+        in DIAG_ROWS order; `out`: a contiguous tensor of that shape to write into.  Asynchronous on the handle's stream."""
+        import torch
+        nc = int(n_chains)
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float64 and x.dim() >= 2 and x.numel() > 0):
+            raise ValueError("chain_diag: a float64 device tensor (n, n_chains * M, ...)")
+        if nc < 1 or x.shape[1] % nc:
+            raise ValueError("chain_diag: axis 1 must hold n_chains blocks of rows")
+        n, shape = int(x.shape[0]), (int(x.shape[1]) // nc,) + tuple(x.shape[2:])
+        K = int(np.prod(shape))
+        if not x[0].is_contiguous() or int(x.stride(0)) < nc * K or int(x.stride(0)) % nc:
+            raise ValueError("chain_diag: the trailing axes must be contiguous and the draw stride a multiple of n_chains")
+        if nc > 1 and int(x.stride(0)) != nc * K:
+            raise ValueError("chain_diag: with n_chains > 1 the draws must be contiguous")
+        ld = int(x.stride(0)) // nc
+        if out is None:
+            out = torch.empty((DIAG_NOUT,) + shape, dtype=torch.float64, device=x.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and
+                  tuple(out.shape) == (DIAG_NOUT,) + shape):
+            raise ValueError("chain_diag: out must be a contiguous float64 device tensor %s" % ((DIAG_NOUT,) + shape,))
+        _chk(self.lib.pgl_chain_diag_dev(self.h, C.c_void_p(x.data_ptr()), n, nc, K, ld, C.c_void_p(out.data_ptr())))
+        return out
+
+    def chain_diag_host(self, x, n_chains=1):
+        """The same with a host array x (n, n_chains * M, ...): -> out (DIAG_NOUT, M, ...) (pgl_chain_diag)."""
+        a = np.ascontiguousarray(x, dtype=np.float64)
+        nc = int(n_chains)
+        if a.ndim < 2 or a.size == 0 or nc < 1 or a.shape[1] % nc:
+            raise ValueError("chain_diag_host: an array (n, n_chains * M, ...)")
+        shape = (a.shape[1] // nc,) + a.shape[2:]
+        out = np.empty((DIAG_NOUT,) + shape)
+        _chk(self.lib.pgl_chain_diag(self.h, _ptr(a), int(a.shape[0]), nc, int(np.prod(shape)), _ptr(out)))
+        return out
 
     # -- lock-step optimiser bookkeeping (device pointers as integers; asynchronous on the handle's stream) --
     def bfgs_state_doubles(self, M, P):

@@ -125,6 +125,7 @@ struct pgl_context {
     // copies of its offsets and results
     DevBuf rs_pre, rs_tot, rs_cum, rs_off, rs_tau, rs_stats;
     DevBuf psis_in, psis_out, psis_lw;   // pgl_psis_loo: the device copies of its host arrays
+    DevBuf diag_in, diag_out;            // pgl_chain_diag: the same
     DevBuf pw_part, pw_out;              // pointwise ll (pgl_pointwise_dev): chunk sums; pgl_pointwise: the device copy of ll_blk_out
     std::vector<double> hvp_host;        // pgl_hvp: theta and Weff of its last prepare (a CG solve repeats them: no new prepare)
 };
@@ -343,7 +344,7 @@ int pgl_destroy(pgl_handle h)
                       &h->spart, &h->sepC, &h->sepA, &h->sepAT, &h->sepD, &h->YfT, &h->Hb, &h->wpart, &h->QvT, &h->staA,
                       &h->Cbuf, &h->hvp_idx, &h->hvp_Weff, &h->hvp_ll, &h->hvp_v, &h->hvp_out,
                       &h->hess_part, &h->hess_out, &h->rs_pre, &h->rs_tot, &h->rs_cum, &h->rs_off, &h->rs_tau, &h->rs_stats,
-                      &h->pw_part, &h->pw_out, &h->psis_in, &h->psis_out, &h->psis_lw};
+                      &h->pw_part, &h->pw_out, &h->psis_in, &h->psis_out, &h->psis_lw, &h->diag_in, &h->diag_out};
     for (DevBuf* b : bufs) release(*b);
     for (int s = 0; s < pgl_context::NEV; ++s)
         for (int i = 0; i < 4; ++i)
@@ -3029,6 +3030,43 @@ int pgl_psis_loo(pgl_handle h, const double* ll, int64_t S, int64_t C, double* o
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(out, h->psis_out.p, obytes, hipMemcpyDeviceToHost, h->stream));
     if (lw) HIPCHK(hipMemcpyAsync(lw, h->psis_lw.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return PGL_OK;
+}
+
+// ---- convergence diagnostics of the columns of a samplers' tensor (pglm_diag.hip.h) ----------------------------------------
+int pgl_chain_diag_dev(pgl_handle h, const double* d_x, int64_t n, int64_t C, int64_t K, int64_t ld, double* d_out)
+{
+    if (!h || !d_x || !d_out || n < PGL_DIAG_MIN_N || C < 1 || K < 1 || ld < K) return fail(PGL_ERR_ARG, "bad argument");
+    if (K > 0x7fffffff) return fail(PGL_ERR_ARG, "at most 2^31 - 1 columns per call");
+    if (n > PGL_DIAG_MAX_DRAWS || C > PGL_DIAG_MAX_DRAWS || n * C > PGL_DIAG_MAX_DRAWS)
+        return fail(PGL_ERR_UNSUPPORTED, "chain diagnostics: more than PGL_DIAG_MAX_DRAWS = " + std::to_string(PGL_DIAG_MAX_DRAWS) +
+                                         " pooled draws do not fit a workgroup's LDS");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t lds = diag_lds_bytes(n, C);
+    if (lds + PGL_DIAG_STATIC_LDS > 65536)
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_diag_column), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)lds));
+    hipLaunchKernelGGL(k_diag_column, dim3((unsigned)K), dim3(PGL_DIAG_THREADS), lds, h->stream, d_x, (int)n, (int)C,
+                       (long long)K, (long long)ld, d_out);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+int pgl_chain_diag(pgl_handle h, const double* x, int64_t n, int64_t C, int64_t K, double* out)
+{
+    if (!h || !x || !out || n < PGL_DIAG_MIN_N || C < 1 || K < 1) return fail(PGL_ERR_ARG, "bad argument");
+    if (n > PGL_DIAG_MAX_DRAWS || C > PGL_DIAG_MAX_DRAWS || n * C > PGL_DIAG_MAX_DRAWS)
+        return pgl_chain_diag_dev(h, x, n, C, K, K, out);                                // (its error, before any copy)
+    HIPCHK(hipSetDevice(h->device));
+    const size_t bytes = (size_t)n * C * K * 8, obytes = (size_t)PGL_DIAG_NOUT * K * 8;
+    ENSURE(h->diag_in, bytes);
+    ENSURE(h->diag_out, obytes);
+    HIPCHK(hipMemcpyAsync(h->diag_in.p, x, bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));          // (pageable source)
+    int rc = pgl_chain_diag_dev(h, (const double*)h->diag_in.p, n, C, K, K, (double*)h->diag_out.p);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(out, h->diag_out.p, obytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return PGL_OK;
 }

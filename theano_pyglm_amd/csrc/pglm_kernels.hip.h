@@ -38,6 +38,8 @@
 // the draws on the device (k_pw_chunk, k_pw_block, pglm_pointwise.hip.h).
 // PSIS-LOO takes the matrix of those terms over the draws one column per workgroup: ranks, generalized-Pareto fit, smoothed
 // weights (k_psis_column, pglm_psis.hip.h).
+// The samplers' draws are judged the same way, one column of (chains x draws) per workgroup: ranks by counting, normal scores,
+// split-R-hat, autocovariances in batches of lags and Geyer's sequence (k_diag_column, pglm_diag.hip.h).
 #pragma once
 //
 // The kernels live in one header per family; this file is the translation unit's table of contents.
@@ -65,4 +67,5 @@
 #include "pglm_rescale.hip.h"
 #include "pglm_pointwise.hip.h"
 #include "pglm_psis.hip.h"
+#include "pglm_diag.hip.h"
 #include "pglm_simulate.hip.h"

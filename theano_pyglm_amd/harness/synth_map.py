@@ -25,6 +25,9 @@ without a standard error (one run gives none), plus the stages and the resamplin
 log-likelihood of every draw in blocks of 10240 bins, accumulated on the device).
 --loo (with --hmc N or --nuts N) prints the PSIS-LOO table of those draws: elpd_loo, p_loo, looic, se and the khat diagnostic
 (model_compare.loo_glms: Pareto smoothing of the (draws, blocks, neurons) matrix on the device).
+--diag (with --hmc N or --nuts N, N >= 8) prints the convergence diagnostics of those draws per neuron: the worst rank-normalised
+R-hat, the smallest bulk and tail ESS, and the number of parameters with rhat > 1.01 or ess_bulk < 100 per chain
+(inference/diagnostics.py: k_diag_column on the draws where the sampler keeps them).
 """
 import argparse
 import os
@@ -54,7 +57,7 @@ def initialize_test_harness(model_name, data, data_dir=None):
 
 
 def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False, gof=False, ppc=0, hmc=0, ais=0,
-                   hmc_mass='laplace', prox=False, laplace_device=False, ais_mass='laplace', nuts=0, smc=0, newton=False, waic=False, loo=False):
+                   hmc_mass='laplace', prox=False, laplace_device=False, ais_mass='laplace', nuts=0, smc=0, newton=False, waic=False, loo=False, diag=False):
     """test/synth_map.py:10-32."""
     popn, popn_true, x_true = initialize_test_harness(model_name, data, data_dir)
     x0 = popn.sample(rng)
@@ -76,9 +79,9 @@ def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, r
         from theano_pyglm_amd.inference import predictive
         print(predictive.format_table(predictive.predictive_counts(popn, x_inf, ppc)))
     if hmc:
-        print(hmc_bias_table(popn, x_inf, hmc, hmc_mass, laplace_device, waic=waic, loo=loo))
+        print(hmc_bias_table(popn, x_inf, hmc, hmc_mass, laplace_device, waic=waic, loo=loo, diag=diag))
     if nuts:
-        print(nuts_bias_table(popn, x_inf, nuts, hmc_mass, laplace_device, waic=waic, loo=loo))
+        print(nuts_bias_table(popn, x_inf, nuts, hmc_mass, laplace_device, waic=waic, loo=loo, diag=diag))
     if ais:
         print(ais_evidence_table(popn, x_inf, ais, laplace_device, ais_mass))
     if smc:
@@ -100,15 +103,16 @@ def prox_table(popn, x):
     return "\n".join(lines)
 
 
-def hmc_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=False, loo=False):
+def hmc_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=False, loo=False, diag=False):
     """n_draws kept HMC draws from x with the mass matrix `mass` ('laplace' or 'laplace_dense'): one line per neuron, bias
     posterior mean +- sd (and the Laplace standard error).  laplace_device: the Laplace factorisations (the dense mass
-    matrix and the standard errors) run on the device.  waic / loo: the WAIC / PSIS-LOO table of the draws follows (waic_table, loo_table)."""
+    matrix and the standard errors) run on the device.  waic / loo: the WAIC / PSIS-LOO table of the draws follows (waic_table, loo_table); diag: the convergence table
+    (diagnostics.worst_table of the sampler's 'summary')."""
     from theano_pyglm_amd.inference import batched_hmc
     from theano_pyglm_amd.inference.laplace import laplace_glms
     t0 = time.time()
     res = batched_hmc.sample_glms_hmc(popn, x, n_draws, mass=mass,
-                                      factor_on_device=laplace_device and mass == 'laplace_dense')
+                                      factor_on_device=laplace_device and mass == 'laplace_dense', diagnostics=diag)
     wall = time.time() - t0
     s = batched_hmc.summarize(res['samples'][:, :, 0])
     try:
@@ -126,19 +130,23 @@ def hmc_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=
         lines.append(waic_table(popn, x, res['samples']))
     if loo:
         lines.append(loo_table(popn, x, res['samples']))
+    if diag:
+        from theano_pyglm_amd.inference.diagnostics import worst_table
+        lines.append(worst_table(res['summary'], res['samples'].shape[0] if res['samples'].ndim == 4 else 1))
     return "\n".join(lines)
 
 
-def nuts_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=False, loo=False, **kw):
+def nuts_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=False, loo=False, diag=False, **kw):
     """hmc_bias_table with the No-U-Turn sampler: the same columns ('accept' is the mean acceptance statistic after
     warm-up) plus the median tree depth of the kept transitions and the divergent transitions after warm-up.  kw: further
-    arguments of sample_glms_nuts (n_warmup, max_depth, ...).  waic / loo: the WAIC / PSIS-LOO table of the draws follows (waic_table, loo_table)."""
+    arguments of sample_glms_nuts (n_warmup, max_depth, ...).  waic / loo: the WAIC / PSIS-LOO table of the draws follows (waic_table, loo_table); diag: the convergence table
+    (diagnostics.worst_table of the sampler's 'summary')."""
     import numpy as np
     from theano_pyglm_amd.inference import batched_nuts
     from theano_pyglm_amd.inference.laplace import laplace_glms
     t0 = time.time()
     res = batched_nuts.sample_glms_nuts(popn, x, n_draws, mass=mass,
-                                        factor_on_device=laplace_device and mass == 'laplace_dense', **kw)
+                                        factor_on_device=laplace_device and mass == 'laplace_dense', diagnostics=diag, **kw)
     wall = time.time() - t0
     s = batched_nuts.summarize(res['samples'][:, :, 0])
     try:
@@ -159,6 +167,9 @@ def nuts_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic
         lines.append(waic_table(popn, x, res['samples']))
     if loo:
         lines.append(loo_table(popn, x, res['samples']))
+    if diag:
+        from theano_pyglm_amd.inference.diagnostics import worst_table
+        lines.append(worst_table(res['summary'], res['samples'].shape[0] if res['samples'].ndim == 4 else 1))
     return "\n".join(lines)
 
 
@@ -262,6 +273,9 @@ def parser():
     ap.add_argument('--waic', action='store_true',
                     help='with --hmc N or --nuts N: the WAIC of every neuron from those draws (pointwise log-likelihood in blocks '
                          'of 10240 bins, accumulated over the draws on the device)')
+    ap.add_argument('--diag', action='store_true',
+                    help='with --hmc N or --nuts N: rank-normalised R-hat and bulk / tail ESS of those draws per neuron, computed '
+                         'on the device (inference/diagnostics.py)')
     ap.add_argument('--loo', action='store_true',
                     help='with --hmc N or --nuts N: PSIS-LOO of every neuron from those draws, with the khat diagnostic per '
                          'block (the matrix of pointwise terms stays on the device; beside or instead of --waic)')
@@ -275,7 +289,7 @@ def main(argv=None):
     run_synth_test(args.model, data, args.resultsDir, os.path.dirname(args.dataFile),
                    False if args.sequential else ('torch' if args.newton_cg else None), use_rop=args.newton_cg, gof=args.gof, ppc=args.ppc, hmc=args.hmc, ais=args.ais,
                    hmc_mass=args.hmc_mass, prox=args.prox, laplace_device=args.laplace_device, ais_mass=args.ais_mass, nuts=args.nuts, smc=args.smc,
-                   newton=args.newton, waic=args.waic, loo=args.loo)
+                   newton=args.newton, waic=args.waic, loo=args.loo, diag=args.diag)
 
 
 if __name__ == '__main__':
