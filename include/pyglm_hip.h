@@ -845,6 +845,51 @@ int pgl_pointwise_dev(pgl_handle h, const double* d_theta, const double* d_Weff,
                       double* d_acc, int64_t draw);
 int pgl_pointwise(pgl_handle h, const double* theta, const double* Weff, int block_chunks, double* ll_blk_out);
 
+/* Expected and observed spike counts over time windows, and their accumulation over posterior draws: the firing rate of every
+ * neuron with its posterior band, and windowed predictive residuals.  The reference draws the rate with a +-2 sd band over the
+ * samples from the averaged eval_state dicts (pyglm/plotting/plot_results.py: plot_firing_rate(s_glm, s_glm_std);
+ * population.py:88-120: one neuron and three (nT) host arrays per call, per draw).  For neuron n over the handle's time range
+ * [t_lo, t_hi) (pgl_set_time_range is honoured):
+ *     window  win >= 1 consecutive bins, counted from t_lo; the last one may be short: n_win = ceil((t_hi - t_lo) / win).  win
+ *             is unrelated to the 256-bin chunk grid of pgl_rescale / pgl_pointwise: 1, 10, 50, 256, 300 and any win >= the
+ *             range (one window) are all valid.
+ *     Lam[w][n] = dt * sum_{t in window w} lam_t,  lam_t = nlin(theta_n[0] + x[t,n]), x the bias-free total current of
+ *             pgl_gibbs_prepare_all; all f64, the rate function of pgl_rescale and pgl_pointwise except that every element
+ *             picks the series of its own argument (theirs is picked by a vote of the wavefront, which would let a window's
+ *             last bit depend on its neighbours).  The order of the sum is fixed (theano_pyglm_amd/csrc/pglm_ratewin.h) and does
+ *             not depend on the launch geometry: the window is cut into pieces of at most 256 bins counted from the window's
+ *             own first bin, a piece is summed in ascending time, the pieces are added in ascending order, dt multiplies
+ *             last.  No atomics: two calls give the same bits, and a window gives the same bits whatever the other windows
+ *             and neurons are.
+ *     obs[w][n] = the sum of the spike counts of the event lists over the window's bins (a bin with several spikes counts
+ *             them all), as a double.
+ *     accumulator over draws, per (window, neuron) five doubles in planes (PGL_RW_NACC = 5, n_win, N) -- mean, M2, min, max,
+ *             pit -- by the rule of pglm_ratewin.h:  draw 0 sets mean = min = max = Lam, M2 = 0, pit = u (the caller need not
+ *             clear the state); draw s >= 1:  d = Lam - mean;  mean += d / (s + 1);  M2 = fma(d, Lam - mean, M2);  min, max;
+ *             pit += (u - pit) / (s + 1), where u = F(y - 1) + 0.5 f(y) is the mid-p value of y = obs under a Poisson law of
+ *             mean Lam: term_0 = exp(-Lam), term_k = term_{k-1} * Lam / k, summed ascending.  u is NaN if Lam > 700 or
+ *             y > PGL_RW_MAX_COUNT (1024): the pit plane of that entry then stays NaN, the other four planes are not
+ *             affected.  A non-finite Lam makes all five planes of that (window, neuron) NaN for good and touches nothing else.
+ *     pit is the posterior mean of the one-step-ahead predictive probability of the observed window count GIVEN THE OBSERVED
+ *             HISTORY: the currents come from the recorded spikes.  It is exact for win = 1; for longer windows it is an
+ *             approximation, because spikes inside the window feed back into the rate of its later bins.
+ * rate_windows_count: n_win_out (host) for the current time range.
+ * rate_windows_dev:   device pointers, asynchronous on the handle's stream.  d_theta (N, P), d_Weff (N, N): the forward pass of
+ *     pgl_gibbs_prepare_all runs on them (and leaves its state, as that call does); d_lam (n_win, N) out, or NULL; d_obs
+ *     (n_win, N) out, or NULL; d_acc (5, n_win, N) in/out, or NULL; at least one of the three; draw = the index s of this
+ *     draw for d_acc.  Two launches behind the forward ones (k_rw_piece: one read of the currents, no (nT, N) array;
+ *     k_rw_window).
+ * rate_windows:       host pointers, lam_out and obs_out (n_win, N).
+ * Stimulus forms as pgl_rescale_dev.  win < 1, draw < 0, all three outputs NULL or a NULL d_theta / d_Weff: PGL_ERR_ARG; n_win
+ * or the number of pieces times the neurons (padded to 16) beyond 2^31 - 1: PGL_ERR_UNSUPPORTED, nothing launched (a property
+ * of the shape: answered before the state of the handle); before pgl_set_spikes_* / pgl_set_basis: PGL_ERR_STATE. */
+#define PGL_RW_NACC 5
+#define PGL_RW_MAX_COUNT 1024
+int pgl_rate_windows_count(pgl_handle h, int64_t win, int64_t* n_win_out);
+int pgl_rate_windows_dev(pgl_handle h, const double* d_theta, const double* d_Weff, int64_t win, double* d_lam, double* d_obs,
+                         double* d_acc, int64_t draw);
+int pgl_rate_windows(pgl_handle h, const double* theta, const double* Weff, int64_t win, double* lam_out, double* obs_out);
+
 /* PSIS-LOO: Pareto-smoothed importance-sampling leave-one-out (Vehtari, Gelman & Gabry 2017; Vehtari, Simpson, Gelman, Yao &
  * Gabry 2024) of the columns of a matrix ll (S, C), element [s, c] at s * ld + c: column c holds the pointwise term of one
  * (block, neuron) under the S posterior draws -- the matrix pgl_pointwise_dev writes draw after draw.  The reference has no
@@ -1038,7 +1083,7 @@ int pgl_set_stream(pgl_handle h, void* stream);
  * launches of every column slice), 5 the k_hess launches of pgl_hess_dev after such a prepare (one per batch of rows),
  * 6 the launches of pgl_rescale_dev (those of path 2, then k_rescale_chunk<nlin>, k_rescale_scan, k_rescale_finish; the dry
  * run's context has nlin = PGL_NLIN_EXP), 7 the launches of pgl_pointwise_dev (those of path 2, then k_pw_chunk<nlin>,
- * k_pw_block).
+ * k_pw_block), 8 the launches of pgl_rate_windows_dev at win = 50 (those of path 2, then k_rw_piece<nlin>, k_rw_window).
  * Paths 3 / 4 / 5 with stim >= 1 return PGL_ERR_UNSUPPORTED, as the calls themselves.
  * The reference has no counterpart (Theano picks its own C implementations); tests hold every reachable instantiation to
  * zero bytes of scratch. */

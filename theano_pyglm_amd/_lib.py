@@ -54,6 +54,7 @@ SYMBOLS = [
     'pgl_newton_trial_dev', 'pgl_newton_search_step_dev',
     'pgl_rescale_count', 'pgl_rescale_dev', 'pgl_rescale',
     'pgl_pointwise_count', 'pgl_pointwise_dev', 'pgl_pointwise',
+    'pgl_rate_windows_count', 'pgl_rate_windows_dev', 'pgl_rate_windows',
     'pgl_psis_loo_dev', 'pgl_psis_loo',
     'pgl_chain_diag_dev', 'pgl_chain_diag',
     'pgl_simulate_streams', 'pgl_simulate_batch', 'pgl_simulate_batch_dev', 'pgl_simulate_batch_plan',
@@ -64,6 +65,9 @@ ABI_VERSION = 112                   # PGL_ABI_VERSION of include/pyglm_hip.h: lo
 
 GEMM_NT, GEMM_MFMA_1, GEMM_MFMA_4, GEMM_KC_4_1_8, GEMM_KC_1_0_16 = range(5)   # PGL_GEMM_*: the kernel of pgl_gemm_dev
 
+RW_NACC = 5                         # PGL_RW_NACC: planes of the rate-window accumulator -- mean, M2, min, max, pit
+RW_MAX_COUNT = 1024                 # PGL_RW_MAX_COUNT: the largest observed window count with a pit (more: NaN)
+RW_MAX_LAM = 700.0                  # the largest expected window count with a pit (more: NaN)
 PSIS_NOUT = 4                       # PGL_PSIS_NOUT: planes of psis_loo's result -- elpd, khat, n_eff, tail length
 PSIS_MAX_DRAWS = 4096               # PGL_PSIS_MAX_DRAWS: the draws a workgroup's LDS holds; more: PGL_ERR_UNSUPPORTED
 DIAG_MAX_DRAWS = 4096               # PGL_DIAG_MAX_DRAWS: the pooled draws (chains x draws) chain_diag's workgroup holds
@@ -199,6 +203,9 @@ def load():
     lib.pgl_pointwise_count.argtypes = [vp, C.c_int, vp]
     lib.pgl_pointwise_dev.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int64]
     lib.pgl_pointwise.argtypes = [vp, vp, vp, C.c_int, vp]
+    lib.pgl_rate_windows_count.argtypes = [vp, C.c_int64, vp]
+    lib.pgl_rate_windows_dev.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int64]
+    lib.pgl_rate_windows.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
     lib.pgl_psis_loo_dev.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp]
     lib.pgl_psis_loo.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp]
     lib.pgl_chain_diag_dev.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp]
@@ -699,6 +706,31 @@ class DeviceGlm(object):
         out = np.empty((self.pointwise_count(block_chunks), self.N))
         _chk(self.lib.pgl_pointwise(self.h, _ptr(th), _ptr(We), int(block_chunks), _ptr(out)))
         return out
+
+    # -- expected and observed counts over time windows, and their accumulation over draws (pgl_rate_windows*) ----
+    def rate_windows_count(self, win):
+        """Number of windows of `win` bins (counted from t_lo, the last one may be short) in the current time range."""
+        n = C.c_int64()
+        _chk(self.lib.pgl_rate_windows_count(self.h, int(win), C.byref(n)))
+        return int(n.value)
+
+    def rate_windows_dev(self, d_theta, d_Weff, win, d_lam=0, d_obs=0, d_acc=0, draw=0):
+        """Device-pointer form (integers; asynchronous): d_theta (N, P), d_Weff (N, N), d_lam and d_obs (n_win, N) out or 0,
+        d_acc (RW_NACC, n_win, N) in/out or 0 with the index `draw` of this draw; see pgl_rate_windows_dev."""
+        _chk(self.lib.pgl_rate_windows_dev(self.h, C.c_void_p(d_theta) if d_theta else None, C.c_void_p(d_Weff) if d_Weff else None,
+                                           int(win), C.c_void_p(d_lam) if d_lam else None, C.c_void_p(d_obs) if d_obs else None,
+                                           C.c_void_p(d_acc) if d_acc else None, int(draw)))
+
+    def rate_windows(self, theta, Weff, win):
+        """Expected and observed spike counts of every neuron over windows of `win` bins of the current time range with host
+        arrays: theta (N, P), Weff (N, N) -> (Lam, obs), each (n_win, N)."""
+        th = _f64(theta, (self.N, self.P))
+        We = _f64(Weff, (self.N, self.N))
+        n_win = self.rate_windows_count(win)
+        lam = np.empty((n_win, self.N))
+        obs = np.empty((n_win, self.N))
+        _chk(self.lib.pgl_rate_windows(self.h, _ptr(th), _ptr(We), int(win), _ptr(lam), _ptr(obs)))
+        return lam, obs
 
     # -- PSIS-LOO of the columns of a pointwise matrix over draws (pgl_psis_loo*) -----------------------
     def psis_loo(self, ll, out=None, weights=False):

@@ -127,6 +127,7 @@ struct pgl_context {
     DevBuf psis_in, psis_out, psis_lw;   // pgl_psis_loo: the device copies of its host arrays
     DevBuf diag_in, diag_out;            // pgl_chain_diag: the same
     DevBuf pw_part, pw_out;              // pointwise ll (pgl_pointwise_dev): chunk sums; pgl_pointwise: the device copy of ll_blk_out
+    DevBuf rw_part, rw_cnt, rw_out;      // rate windows (pgl_rate_windows_dev): piece sums of rate and spike counts; pgl_rate_windows: the device copy of its two results
     std::vector<double> hvp_host;        // pgl_hvp: theta and Weff of its last prepare (a CG solve repeats them: no new prepare)
 };
 
@@ -344,7 +345,7 @@ int pgl_destroy(pgl_handle h)
                       &h->spart, &h->sepC, &h->sepA, &h->sepAT, &h->sepD, &h->YfT, &h->Hb, &h->wpart, &h->QvT, &h->staA,
                       &h->Cbuf, &h->hvp_idx, &h->hvp_Weff, &h->hvp_ll, &h->hvp_v, &h->hvp_out,
                       &h->hess_part, &h->hess_out, &h->rs_pre, &h->rs_tot, &h->rs_cum, &h->rs_off, &h->rs_tau, &h->rs_stats,
-                      &h->pw_part, &h->pw_out, &h->psis_in, &h->psis_out, &h->psis_lw, &h->diag_in, &h->diag_out};
+                      &h->pw_part, &h->pw_out, &h->rw_part, &h->rw_cnt, &h->rw_out, &h->psis_in, &h->psis_out, &h->psis_lw, &h->diag_in, &h->diag_out};
     for (DevBuf* b : bufs) release(*b);
     for (int s = 0; s < pgl_context::NEV; ++s)
         for (int i = 0; i < 4; ++i)
@@ -1870,6 +1871,7 @@ int pgl_set_stream(pgl_handle h, void* stream)
 static int enqueue_gibbs_forward(pgl_handle h);
 static int enqueue_rescale(pgl_handle h, double* d_tau, const long long* d_off, double* d_stats);
 static int enqueue_pointwise(pgl_handle h, int block_chunks, double* d_ll_blk, double* d_acc, long long draw);
+static int enqueue_rate_windows(pgl_handle h, long long win, double* d_lam, double* d_obs, double* d_acc, long long draw);
 
 int pgl_last_kernels(pgl_handle h, char* out, int cap)
 {
@@ -1890,7 +1892,8 @@ int pgl_last_kernels(pgl_handle h, char* out, int cap)
 // 3 the launches of pgl_hvp_prepare_*, 4 those of pgl_hvp_apply_dev after such a prepare (k_hvp5 and the fused kernels around
 // it; stim >= 1: PGL_ERR_UNSUPPORTED, as the real call), 5 the k_hess launches of pgl_hess_dev after such a prepare,
 // 6 the launches of pgl_rescale_dev (the forward launches of path 2, then the k_rescale_* kernels), 7 those of
-// pgl_pointwise_dev (the forward launches of path 2, then k_pw_chunk and k_pw_block).
+// pgl_pointwise_dev (the forward launches of path 2, then k_pw_chunk and k_pw_block), 8 those of pgl_rate_windows_dev (the
+// forward launches of path 2, then k_rw_piece and k_rw_window).
 int pgl_plan_kernels(int N, int B, int R, int Dstim, long long nT, int stim, int n_lo, int count, int path, int opt_kernel,
                      int opt_f32, char* out, int cap)
 {
@@ -1922,11 +1925,12 @@ int pgl_plan_kernels(int N, int B, int R, int Dstim, long long nT, int stim, int
         }
     } else {
         g_dry = &names;
-        rc = (path == 2 || path == 6 || path == 7) ? enqueue_gibbs_forward(&c)
+        rc = (path == 2 || path == 6 || path == 7 || path == 8) ? enqueue_gibbs_forward(&c)
                          : enqueue_ll_grad(&c, n_lo, n_lo + count, nullptr, nullptr, &dummy, path == 0 ? &dummy : nullptr);
     }
     if (rc == PGL_OK && path == 6) rc = enqueue_rescale(&c, &dummy, nullptr, &dummy);
     if (rc == PGL_OK && path == 7) rc = enqueue_pointwise(&c, 1, &dummy, nullptr, 0);
+    if (rc == PGL_OK && path == 8) rc = enqueue_rate_windows(&c, 50, &dummy, nullptr, nullptr, 0);
     g_dry = nullptr;
     // (under g_dry nothing but a dispatch (pglm_launch.h) without an instantiation for the plan fails with PGL_ERR_HIP)
     if (rc == PGL_ERR_HIP) return fail(PGL_ERR_UNSUPPORTED, "no kernel instantiation for this plan");
@@ -2996,6 +3000,129 @@ int pgl_pointwise(pgl_handle h, const double* theta, const double* Weff, int blo
                            nullptr, 0);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(ll_blk_out, h->pw_out.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return PGL_OK;
+}
+
+// ---- rate windows: expected and observed counts over time windows, folded over draws (pglm_ratewin.hip.h) ----------------
+// (n_win, pieces) of the handle's time range at this window length
+static void rate_windows_shape(const pgl_context* h, long long win, long long& n_win, long long& npieces)
+{
+    const long long n = h->t_hi - h->t_lo;
+    n_win = pgl_rw_windows(n, win);
+    npieces = (n_win - 1) * pgl_rw_pieces(win) + pgl_rw_pieces(n - (n_win - 1) * win);
+}
+
+int pgl_rate_windows_count(pgl_handle h, int64_t win, int64_t* n_win_out)
+{
+    if (!h) return fail(PGL_ERR_ARG, "null handle");
+    if (!n_win_out) return fail(PGL_ERR_ARG, "null argument");
+    if (win < 1) return fail(PGL_ERR_ARG, "win must be at least 1");
+    *n_win_out = pgl_rw_windows(h->t_hi - h->t_lo, win);
+    return PGL_OK;
+}
+
+// the k_rw_* launches behind a forward pass (GX of the handle's time range is on the stream).  The dry run of the dispatch
+// runs this too: the RULE above enqueue_ll_grad holds here.
+static int enqueue_rate_windows(pgl_handle h, long long win, double* d_lam, double* d_obs, double* d_acc, long long draw)
+{
+    struct Append {                                            // PGL_OPT_RECORD_KERNELS: behind the forward launches
+        explicit Append(pgl_context* h) { if (h->opt_record && !g_dry) g_rec = &h->last_kernels; }
+        ~Append() { g_rec = nullptr; }
+    } record(h);
+    const auto named = [](const std::string& name) {          // true: dry run, launch nothing
+        if (g_dry) g_dry->push_back(name);
+        else if (g_rec) g_rec->push_back(name);
+        return g_dry != nullptr;
+    };
+    win = std::min<long long>(win, h->t_hi - h->t_lo);        // (one window: its length is the range)
+    long long n_win, npieces;
+    rate_windows_shape(h, win, n_win, npieces);
+    const int xs = g_dry ? 16 * ((h->N + 15) / 16) : h->gx_xs;
+    ENSURE(h->rw_part, (size_t)npieces * xs * 8);
+    ENSURE(h->rw_cnt, (size_t)npieces * xs * 4);
+    RateWinParams p;
+    p.GX = (const double*)h->GX.p; p.theta = (const double*)h->gtheta.p;
+    p.spk = (const int2*)h->spk.p; p.wlo = (const int*)h->wlo.p; p.whi = (const int*)h->whi.p;
+    p.part = (double*)h->rw_part.p; p.cnt = (int*)h->rw_cnt.p; p.lam = d_lam; p.obs = d_obs; p.acc = d_acc;
+    p.t_lo = h->t_lo; p.t_hi = h->t_hi; p.win = win; p.draw = draw;
+    p.n_win = n_win; p.npieces = npieces;
+    p.ppw = (int)pgl_rw_pieces(win);
+    p.group = (p.ppw == 1) ? (int)std::max<long long>(PGL_RW_PIECE / win, 1) : 1;
+    p.nunits = (npieces + p.group - 1) / p.group;
+    p.N = h->N; p.xs = xs; p.P = 1 + h->Dstim + h->Kimp; p.nnz = (int)h->nnz;
+    p.dt = h->dt;
+    if (!named(h->nlin == PGL_NLIN_EXPLINEAR ? "k_rw_piece<1>" : "k_rw_piece<0>")) {
+        const unsigned blocks = (unsigned)((p.nunits * xs + 255) / 256);
+        if (h->nlin == PGL_NLIN_EXPLINEAR) hipLaunchKernelGGL(k_rw_piece<1>, dim3(blocks), dim3(256), 0, h->stream, p);
+        else hipLaunchKernelGGL(k_rw_piece<0>, dim3(blocks), dim3(256), 0, h->stream, p);
+        HIPCHK(hipGetLastError());
+    }
+    if (!named("k_rw_window")) {
+        const unsigned blocks = (unsigned)((n_win * xs + 255) / 256);
+        hipLaunchKernelGGL(k_rw_window, dim3(blocks), dim3(256), 0, h->stream, p);
+        HIPCHK(hipGetLastError());
+    }
+    return PGL_OK;
+}
+
+int pgl_rate_windows_dev(pgl_handle h, const double* d_theta, const double* d_Weff, int64_t win, double* d_lam, double* d_obs,
+                         double* d_acc, int64_t draw)
+{
+    if (!h) return fail(PGL_ERR_ARG, "null handle");
+    if (!d_theta || !d_Weff) return fail(PGL_ERR_ARG, "null argument");
+    if (!d_lam && !d_obs && !d_acc) return fail(PGL_ERR_ARG, "rate windows: none of d_lam, d_obs and d_acc is given");
+    if (win < 1) return fail(PGL_ERR_ARG, "win must be at least 1");
+    if (draw < 0) return fail(PGL_ERR_ARG, "draw must not be negative");
+    {
+        // a property of the shape alone, so it is answered before the state of the handle: windows and pieces times the row
+        // stride of the currents are indexed in 32 bits by the launch grids
+        long long n_win, npieces;
+        rate_windows_shape(h, std::min<long long>(win, h->t_hi - h->t_lo), n_win, npieces);
+        const long long xs = 16 * (((long long)h->N + 15) / 16);
+        if (n_win * xs > 0x7fffffffLL || npieces * xs > 0x7fffffffLL)
+            return fail(PGL_ERR_UNSUPPORTED, "too many windows x neurons for the rate-window kernels: use a longer window or a shorter time range");
+    }
+    int rc = check_ready(h);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t P = 1 + (size_t)h->Dstim + h->Kimp;
+    const int N = h->N;
+    ENSURE(h->gtheta, (size_t)N * P * 8);
+    ENSURE(h->Weff, (size_t)N * N * 8);
+    if (d_theta != h->gtheta.p)
+        HIPCHK(hipMemcpyAsync(h->gtheta.p, d_theta, (size_t)N * P * 8, hipMemcpyDeviceToDevice, h->stream));
+    if (d_Weff != h->Weff.p)
+        HIPCHK(hipMemcpyAsync(h->Weff.p, d_Weff, (size_t)N * N * 8, hipMemcpyDeviceToDevice, h->stream));
+    rc = enqueue_gibbs_forward(h);
+    if (rc) return rc;
+    return enqueue_rate_windows(h, (long long)win, d_lam, d_obs, d_acc, (long long)draw);
+}
+
+int pgl_rate_windows(pgl_handle h, const double* theta, const double* Weff, int64_t win, double* lam_out, double* obs_out)
+{
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if (!theta || !Weff || !lam_out || !obs_out) return fail(PGL_ERR_ARG, "null argument");
+    int64_t n_win = 0;
+    rc = pgl_rate_windows_count(h, win, &n_win);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t P = 1 + (size_t)h->Dstim + h->Kimp;
+    const int N = h->N;
+    const size_t bytes = (size_t)n_win * N * 8;
+    ENSURE(h->gtheta, (size_t)N * P * 8);
+    ENSURE(h->Weff, (size_t)N * N * 8);
+    ENSURE(h->rw_out, 2 * bytes);
+    HIPCHK(hipMemcpyAsync(h->gtheta.p, theta, (size_t)N * P * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->Weff.p, Weff, (size_t)N * N * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));          // (pageable sources: see pgl_gibbs_prepare_all)
+    double* d_lam = (double*)h->rw_out.p;
+    rc = pgl_rate_windows_dev(h, (const double*)h->gtheta.p, (const double*)h->Weff.p, win, d_lam, d_lam + (size_t)n_win * N,
+                              nullptr, 0);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(lam_out, d_lam, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(obs_out, d_lam + (size_t)n_win * N, bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return PGL_OK;
 }

@@ -36,6 +36,8 @@
 // pglm_simulate.hip.h).
 // Model comparison needs the log-likelihood of a draw resolved in time: block sums behind the forward-only pass, folded over
 // the draws on the device (k_pw_chunk, k_pw_block, pglm_pointwise.hip.h).
+// Firing-rate bands and windowed predictive residuals need the expected and observed counts over user-chosen time windows,
+// folded over the draws the same way (k_rw_piece, k_rw_window, pglm_ratewin.hip.h).
 // PSIS-LOO takes the matrix of those terms over the draws one column per workgroup: ranks, generalized-Pareto fit, smoothed
 // weights (k_psis_column, pglm_psis.hip.h).
 // The samplers' draws are judged the same way, one column of (chains x draws) per workgroup: ranks by counting, normal scores,
@@ -66,6 +68,7 @@
 #include "pglm_prox.hip.h"
 #include "pglm_rescale.hip.h"
 #include "pglm_pointwise.hip.h"
+#include "pglm_ratewin.hip.h"
 #include "pglm_psis.hip.h"
 #include "pglm_diag.hip.h"
 #include "pglm_simulate.hip.h"

@@ -25,6 +25,9 @@ without a standard error (one run gives none), plus the stages and the resamplin
 log-likelihood of every draw in blocks of 10240 bins, accumulated on the device).
 --loo (with --hmc N or --nuts N) prints the PSIS-LOO table of those draws: elpd_loo, p_loo, looic, se and the khat diagnostic
 (model_compare.loo_glms: Pareto smoothing of the (draws, blocks, neurons) matrix on the device).
+--rates WIN (with --hmc N or --nuts N) prints the windowed predictive residuals of those draws per neuron: the largest |pearson|
+and its window, the KS distance of the pit values from the uniform law, and the share of windows whose observed count lies
+outside the draws' [min, max] (inference/predictive.py: rate_bands over windows of WIN bins, folded over the draws on the device).
 --diag (with --hmc N or --nuts N, N >= 8) prints the convergence diagnostics of those draws per neuron: the worst rank-normalised
 R-hat, the smallest bulk and tail ESS, and the number of parameters with rhat > 1.01 or ess_bulk < 100 per chain
 (inference/diagnostics.py: k_diag_column on the draws where the sampler keeps them).
@@ -57,7 +60,7 @@ def initialize_test_harness(model_name, data, data_dir=None):
 
 
 def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False, gof=False, ppc=0, hmc=0, ais=0,
-                   hmc_mass='laplace', prox=False, laplace_device=False, ais_mass='laplace', nuts=0, smc=0, newton=False, waic=False, loo=False, diag=False):
+                   hmc_mass='laplace', prox=False, laplace_device=False, ais_mass='laplace', nuts=0, smc=0, newton=False, waic=False, loo=False, diag=False, rates=0):
     """test/synth_map.py:10-32."""
     popn, popn_true, x_true = initialize_test_harness(model_name, data, data_dir)
     x0 = popn.sample(rng)
@@ -79,9 +82,9 @@ def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, r
         from theano_pyglm_amd.inference import predictive
         print(predictive.format_table(predictive.predictive_counts(popn, x_inf, ppc)))
     if hmc:
-        print(hmc_bias_table(popn, x_inf, hmc, hmc_mass, laplace_device, waic=waic, loo=loo, diag=diag))
+        print(hmc_bias_table(popn, x_inf, hmc, hmc_mass, laplace_device, waic=waic, loo=loo, diag=diag, rates=rates))
     if nuts:
-        print(nuts_bias_table(popn, x_inf, nuts, hmc_mass, laplace_device, waic=waic, loo=loo, diag=diag))
+        print(nuts_bias_table(popn, x_inf, nuts, hmc_mass, laplace_device, waic=waic, loo=loo, diag=diag, rates=rates))
     if ais:
         print(ais_evidence_table(popn, x_inf, ais, laplace_device, ais_mass))
     if smc:
@@ -103,7 +106,7 @@ def prox_table(popn, x):
     return "\n".join(lines)
 
 
-def hmc_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=False, loo=False, diag=False):
+def hmc_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=False, loo=False, diag=False, rates=0):
     """n_draws kept HMC draws from x with the mass matrix `mass` ('laplace' or 'laplace_dense'): one line per neuron, bias
     posterior mean +- sd (and the Laplace standard error).  laplace_device: the Laplace factorisations (the dense mass
     matrix and the standard errors) run on the device.  waic / loo: the WAIC / PSIS-LOO table of the draws follows (waic_table, loo_table); diag: the convergence table
@@ -130,13 +133,15 @@ def hmc_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=
         lines.append(waic_table(popn, x, res['samples']))
     if loo:
         lines.append(loo_table(popn, x, res['samples']))
+    if rates:
+        lines.append(rates_table(popn, x, res['samples'], rates))
     if diag:
         from theano_pyglm_amd.inference.diagnostics import worst_table
         lines.append(worst_table(res['summary'], res['samples'].shape[0] if res['samples'].ndim == 4 else 1))
     return "\n".join(lines)
 
 
-def nuts_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=False, loo=False, diag=False, **kw):
+def nuts_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=False, loo=False, diag=False, rates=0, **kw):
     """hmc_bias_table with the No-U-Turn sampler: the same columns ('accept' is the mean acceptance statistic after
     warm-up) plus the median tree depth of the kept transitions and the divergent transitions after warm-up.  kw: further
     arguments of sample_glms_nuts (n_warmup, max_depth, ...).  waic / loo: the WAIC / PSIS-LOO table of the draws follows (waic_table, loo_table); diag: the convergence table
@@ -167,10 +172,21 @@ def nuts_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic
         lines.append(waic_table(popn, x, res['samples']))
     if loo:
         lines.append(loo_table(popn, x, res['samples']))
+    if rates:
+        lines.append(rates_table(popn, x, res['samples'], rates))
     if diag:
         from theano_pyglm_amd.inference.diagnostics import worst_table
         lines.append(worst_table(res['summary'], res['samples'].shape[0] if res['samples'].ndim == 4 else 1))
     return "\n".join(lines)
+
+
+def rates_table(popn, x, samples, win):
+    """The windowed predictive residuals of posterior draws (samples (S, N, P) of all neurons) over windows of `win` bins:
+    predictive.format_rate_table of predictive.rate_bands."""
+    from theano_pyglm_amd.inference import predictive
+    t0 = time.time()
+    res = predictive.rate_bands(popn, x, samples, win=win)
+    return predictive.format_rate_table(res) + "\n(rate bands of %d draws in %.2f s)" % (res['n_draws'], time.time() - t0)
 
 
 def waic_table(popn, x, samples, block_chunks=40):
@@ -273,6 +289,9 @@ def parser():
     ap.add_argument('--waic', action='store_true',
                     help='with --hmc N or --nuts N: the WAIC of every neuron from those draws (pointwise log-likelihood in blocks '
                          'of 10240 bins, accumulated over the draws on the device)')
+    ap.add_argument('--rates', type=int, default=0, metavar='WIN',
+                    help='with --hmc N or --nuts N: windowed predictive residuals of those draws per neuron over windows of WIN '
+                         'bins (largest |pearson|, KS distance of the pit values, share of windows outside the band)')
     ap.add_argument('--diag', action='store_true',
                     help='with --hmc N or --nuts N: rank-normalised R-hat and bulk / tail ESS of those draws per neuron, computed '
                          'on the device (inference/diagnostics.py)')
@@ -289,7 +308,7 @@ def main(argv=None):
     run_synth_test(args.model, data, args.resultsDir, os.path.dirname(args.dataFile),
                    False if args.sequential else ('torch' if args.newton_cg else None), use_rop=args.newton_cg, gof=args.gof, ppc=args.ppc, hmc=args.hmc, ais=args.ais,
                    hmc_mass=args.hmc_mass, prox=args.prox, laplace_device=args.laplace_device, ais_mass=args.ais_mass, nuts=args.nuts, smc=args.smc,
-                   newton=args.newton, waic=args.waic, loo=args.loo, diag=args.diag)
+                   newton=args.newton, waic=args.waic, loo=args.loo, diag=args.diag, rates=args.rates)
 
 
 if __name__ == '__main__':

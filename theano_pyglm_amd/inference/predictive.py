@@ -5,6 +5,16 @@ every neuron's observed count with the replicates.
 
 A count far in a tail of its predictive distribution says the model does not reproduce that neuron's rate; it says nothing
 about timing (inference/gof.py tests that).  The reference has no counterpart.
+
+Resolved in time: rate_bands folds the expected count of every time window over posterior draws on the device (one forward
+pass plus pgl_rate_windows_dev per draw and data sequence; only the accumulator and the observed counts come back, once) --
+the firing rate with its posterior band that the reference's plot_firing_rate(s_glm, s_glm_std) draws from per-draw
+eval_state dicts, plus windowed residuals:
+    pearson = (obs - mean) / sqrt(mean + var)     the law of total variance of a Poisson count whose mean is random;
+    pit     the posterior mean of the Poisson mid-p value of the observed count, GIVEN THE OBSERVED HISTORY (the currents
+            are computed from the recorded spikes): exact for win = 1, an approximation for longer windows because spikes
+            inside a window feed back into its rate.  NaN where a draw's expected count exceeds 700 or the observed count
+            exceeds RW_MAX_COUNT = 1024.
 """
 import numpy as np
 
@@ -63,6 +73,101 @@ def predictive_counts(population, x, n_rep, seed=0):
     res = summarize_counts(observed, counts)
     res.update({'counts': counts, 'exceptions': exc, 'n_rep': int(n_rep)})
     return res
+
+
+def ks_uniform(u):
+    """KS distance of the values u from the uniform law on [0, 1] (NaN for an empty sample)"""
+    u = np.sort(np.asarray(u, dtype=float))
+    n = u.size
+    if n == 0:
+        return float('nan')
+    return float(max(np.max(np.arange(1, n + 1) / n - u), np.max(u - np.arange(n) / n)))
+
+
+def rate_bands(population, x, samples, win=50, n_lo=0, keep=False):
+    """Posterior bands of the expected spike count of neurons n_lo .. n_lo + M over windows of `win` bins, and the windowed
+    predictive residuals of the recorded counts, from the draws `samples`.
+
+    samples: (S, M, P) rows in the theta layout, as waic_glms takes them (a leading chain axis is flattened; a torch device
+    tensor is used where it is).  The other neurons and the network stay at x.  Per draw the rows overwrite a device copy of
+    theta_matrix(x) and every data sequence gets one pgl_rate_windows_dev call; nothing synchronises with the host inside
+    the loop.  Windows are counted from the start of each data sequence (the last one of a sequence may be short).
+    Returns a dict of (n_win, M) arrays -- obs, mean, sd (n - 1 form; NaN for one draw), min, max, pit, pearson -- with t0
+    (n_win) the windows' start times in seconds within their sequence, width (n_win) their lengths in seconds, and per
+    neuron pit_ks (the KS distance of the finite pit values from the uniform law) and n_pit_nan; n_draws, win,
+    windows_per_sequence, n_lo.  keep=True adds 'draws' (S, n_win, M), every draw's expected counts (for quantile bands),
+    kept on the device until the end.  mean / width[:, None] is the firing rate in Hz."""
+    from theano_pyglm_amd.inference.lockstep import session
+    from theano_pyglm_amd.inference.model_compare import _draws
+    if getattr(population, '_time_shard', None) is not None:
+        raise ValueError("the rate bands of a time-sharded population are not implemented")
+    win = int(win)
+    if win < 1:
+        raise ValueError("win must be at least 1")
+    N, P = population.N, population.glm.P
+    s, is_tensor = _draws(samples, P)
+    S, M = int(s.shape[0]), int(s.shape[1])
+    if n_lo < 0 or n_lo + M > N:
+        raise ValueError("neurons %d .. %d of %d" % (n_lo, n_lo + M, N))
+    population._check_vars(x)
+    theta0 = np.ascontiguousarray(population.theta_matrix(x))
+    dt = population.glm.dt
+    with session(population) as (torch, dev, stream, handles):
+        f64 = torch.float64
+        theta = torch.tensor(theta0, dtype=f64, device=dev)
+        Weff = torch.tensor(np.ascontiguousarray(population.W_eff(x)), dtype=f64, device=dev)
+        d_s = s.to(device=dev, dtype=f64).contiguous() if is_tensor else torch.tensor(s, dtype=f64, device=dev)
+        nw = [h.rate_windows_count(win) for h in handles]
+        off = np.concatenate(([0], np.cumsum(nw))).astype(int)
+        accs = [torch.empty((_lib.RW_NACC, n, N), dtype=f64, device=dev) for n in nw]
+        obss = [torch.empty((n, N), dtype=f64, device=dev) for n in nw]
+        lam = torch.empty((S, int(off[-1]), N), dtype=f64, device=dev) if keep else None
+        rows = theta[n_lo:n_lo + M]
+        for i in range(S):
+            rows.copy_(d_s[i])
+            for k, h in enumerate(handles):
+                h.rate_windows_dev(theta.data_ptr(), Weff.data_ptr(), win, lam[i, off[k]:].data_ptr() if keep else 0,
+                                   obss[k].data_ptr() if i == 0 else 0, accs[k].data_ptr(), i)
+        stream.synchronize()
+        acc = np.concatenate([a.cpu().numpy() for a in accs], axis=1)[:, :, n_lo:n_lo + M]
+        obs = np.concatenate([o.cpu().numpy() for o in obss], axis=0)[:, n_lo:n_lo + M]
+        kept = np.ascontiguousarray(lam.cpu().numpy()[:, :, n_lo:n_lo + M]) if keep else None
+    mean, m2, mn, mx, pit = acc
+    with np.errstate(invalid='ignore', divide='ignore'):
+        var = m2 / (S - 1.0) if S > 1 else np.full(m2.shape, np.nan)
+        pearson = (obs - mean) / np.sqrt(mean + (var if S > 1 else 0.0))
+    t0 = np.concatenate([np.arange(n) * (win * dt) for n in nw]) if nw else np.zeros(0)
+    # (a sequence's last window may be short: its length is what is left of the sequence)
+    width = np.full(t0.shape, win * dt)
+    for k, data in enumerate(population.data_sequences):
+        nT = int(np.asarray(data['S']).shape[0])
+        if nw[k] > 0:
+            width[off[k + 1] - 1] = (nT - (nw[k] - 1) * win) * dt
+    fin = np.isfinite(pit)
+    out = {'t0': t0, 'width': width, 'obs': np.ascontiguousarray(obs), 'mean': np.ascontiguousarray(mean),
+           'sd': np.sqrt(var), 'min': np.ascontiguousarray(mn), 'max': np.ascontiguousarray(mx),
+           'pit': np.ascontiguousarray(pit), 'pearson': pearson,
+           'pit_ks': np.array([ks_uniform(pit[fin[:, m], m]) for m in range(M)]),
+           'n_pit_nan': np.sum(~fin, axis=0).astype(np.int64), 'n_draws': S, 'win': win, 'windows_per_sequence': nw,
+           'n_lo': int(n_lo)}
+    if keep:
+        out['draws'] = kept
+    return out
+
+
+def format_rate_table(res):
+    """Per neuron: the largest |pearson| and its window, pit_ks, and the share of windows whose observed count lies outside
+    the draws' [min, max]."""
+    lines = ["windowed predictive residuals (%d draws, %d windows of %d bins)" % (res['n_draws'], len(res['t0']), res['win']),
+             "%6s %12s %10s %10s %10s %12s" % ('neuron', 'max|pearson|', 'window', 'pit KS', 'pit NaN', 'outside band')]
+    pe = np.where(np.isfinite(res['pearson']), np.abs(res['pearson']), -1.0)
+    outside = np.mean((res['obs'] < res['min']) | (res['obs'] > res['max']), axis=0)
+    for m in range(res['obs'].shape[1]):
+        w = int(np.argmax(pe[:, m]))
+        lines.append("%6d %12.3f %10d %10.4f %10d %11.1f%%" % (res['n_lo'] + m, pe[w, m], w, res['pit_ks'][m],
+                                                               res['n_pit_nan'][m], 100.0 * outside[m]))
+    lines.append("pit: conditional on the recorded history; exact for one-bin windows, approximate for longer ones")
+    return "\n".join(lines)
 
 
 def format_table(res):

@@ -413,6 +413,28 @@ class Population(object):
             parts.append(self._handle(self._current).pointwise(theta, Weff, block_chunks))
         return np.concatenate(parts, axis=0) if parts else np.zeros((0, self.N))
 
+    # -- firing rates in time ----------------------------------------------------------------
+    def compute_expected_counts(self, vars, win):
+        """Expected and observed spike counts of every neuron under `vars` over windows of `win` consecutive bins (counted
+        from the start of each data sequence; the last window of a sequence may be short): Lam = dt * sum of the rate over
+        the window, obs = the recorded spikes in it.  One forward pass and one windowed sum on the device per data sequence
+        (pgl_rate_windows); no rate array comes back to the host.  Returns (Lam, obs), each (n_win_total, N), the data
+        sequences one after the other.  Lam / (win dt) is the firing rate plot_firing_rate draws from eval_state."""
+        if self._time_shard is not None:
+            raise ValueError("the expected counts of a time-sharded population are not implemented")
+        self._check_vars(vars)
+        theta = self.theta_matrix(vars)
+        Weff = self.W_eff(vars)
+        lams, obss = [], []
+        for data in self.data_sequences:
+            self.set_data(data)
+            lam, obs = self._handle(self._current).rate_windows(theta, Weff, win)
+            lams.append(lam)
+            obss.append(obs)
+        if not lams:
+            return np.zeros((0, self.N)), np.zeros((0, self.N))
+        return np.concatenate(lams, axis=0), np.concatenate(obss, axis=0)
+
     # -- state ---------------------------------------------------------------------------
     def eval_state(self, vars):
         """population.py:88-120: rates, currents and component state of every neuron."""
