@@ -29,7 +29,7 @@ def test_rescale_symbols_and_version():
     from theano_pyglm_amd.population import Population
     assert hasattr(Population, 'compute_rescaled_intervals')
     # the chunk length the GPU tests place their edge events by
-    with open(os.path.join(ROOT, 'theano_pyglm_amd', 'csrc', 'pglm_rescale.hip.h')) as f:
+    with open(os.path.join(ROOT, 'theano_pyglm_amd', 'csrc', 'pglm_binwalk.hip.h')) as f:
         m = re.search(r'#define PGL_RS_CHUNK (\d+)', f.read())
     assert int(m.group(1)) == _lib.RESCALE_CHUNK and _lib.RESCALE_CHUNK % 16 == 0
 

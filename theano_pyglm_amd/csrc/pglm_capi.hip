@@ -1160,7 +1160,8 @@ struct KernelRecord {
 // RULE: pgl_plan_kernels runs enqueue_ll_grad, enqueue_hvp_prepare / _apply and enqueue_gibbs_forward with g_dry set on a
 // context that has no device, no stream and null buffers -- also inside processes that do have a GPU.  Every device operation
 // on these paths must therefore be skipped under g_dry, and the guards live in the steps the evaluations are made of, not in
-// the evaluations: launch_kernel (pglm_launch.h) records and returns, ensure() allocates nothing, the steps below and
+// the evaluations: launch_kernel (pglm_launch.h) and launch_behind (the k_rescale_* / k_pw_* / k_rw_* launches behind a
+// forward pass) record and return, ensure() allocates nothing, the steps below and
 // launch_prep, ensure_feature_images, launch_finalize_grad, sep_* / sepf_* return at their top or test g_dry at their one
 // device call.  What is left in the enqueue_* functions themselves: the timing events (never recorded by the dry run, whose
 // context has opt_timing = 0), the sepD sizing of the fused stimulus backward and the k_hvp_curv launch, each under its own
@@ -2136,21 +2137,28 @@ int pgl_gibbs_update(pgl_handle h, int n_pre, double delta)
 }
 
 // ---- batched column Gibbs: all post-synaptic columns on the device at once ----------------------
+// host theta (N, P) / Weff (N, N) of one draw -> h->gtheta / h->Weff, the device is current
+static int upload_draw(pgl_handle h, const double* theta, const double* Weff)
+{
+    const size_t tb = (size_t)h->N * (1 + (size_t)h->Dstim + h->Kimp) * 8, wb = (size_t)h->N * h->N * 8;
+    ENSURE(h->gtheta, tb);
+    ENSURE(h->Weff, wb);
+    HIPCHK(hipMemcpyAsync(h->gtheta.p, theta, tb, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->Weff.p, Weff, wb, hipMemcpyHostToDevice, h->stream));
+    // the caller's (pageable) theta / Weff may be temporaries that die when this call returns: the uploads
+    // must have left host memory by then, whatever the runtime does with pageable sources
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return PGL_OK;
+}
+
 int pgl_gibbs_prepare_all(pgl_handle h, const double* theta, const double* Weff)
 {
     int rc = check_ready(h);
     if (rc) return rc;
     if (!theta || !Weff) return fail(PGL_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(h->device));
-    const size_t P = 1 + (size_t)h->Dstim + h->Kimp;
-    const int N = h->N;
-    ENSURE(h->gtheta, (size_t)N * P * 8);
-    ENSURE(h->Weff, (size_t)N * N * 8);
-    HIPCHK(hipMemcpyAsync(h->gtheta.p, theta, (size_t)N * P * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->Weff.p, Weff, (size_t)N * N * 8, hipMemcpyHostToDevice, h->stream));
-    // the caller's (pageable) theta / Weff may be temporaries that die when this call returns: the uploads
-    // must have left host memory by then, whatever the runtime does with pageable sources
-    HIPCHK(hipStreamSynchronize(h->stream));
+    rc = upload_draw(h, theta, Weff);
+    if (rc) return rc;
     return enqueue_gibbs_forward(h);
 }
 
@@ -2807,47 +2815,81 @@ int pgl_rescale_count(pgl_handle h, int64_t* off_out)
     return PGL_OK;
 }
 
-// the k_rescale_* launches behind a forward pass (GX of the handle's time range is on the stream).  The dry run of the
-// dispatch runs this too: the RULE above enqueue_ll_grad holds here.
-static int enqueue_rescale(pgl_handle h, double* d_tau, const long long* d_off, double* d_stats)
+// ---- what the three consumers of GX below share: staging of a draw, launch geometry, launches behind a forward pass -----
+// theta / Weff of a draw on the device -> h->gtheta / h->Weff (no copy where they are the handle's own buffers already), then
+// the forward-only pass: GX of the handle's time range is on the stream
+static int forward_from_dev(pgl_handle h, const double* d_theta, const double* d_Weff)
 {
-    struct Append {                                            // PGL_OPT_RECORD_KERNELS: behind the forward launches
+    HIPCHK(hipSetDevice(h->device));
+    const size_t tb = (size_t)h->N * (1 + (size_t)h->Dstim + h->Kimp) * 8, wb = (size_t)h->N * h->N * 8;
+    ENSURE(h->gtheta, tb);
+    ENSURE(h->Weff, wb);
+    if (d_theta != h->gtheta.p) HIPCHK(hipMemcpyAsync(h->gtheta.p, d_theta, tb, hipMemcpyDeviceToDevice, h->stream));
+    if (d_Weff != h->Weff.p) HIPCHK(hipMemcpyAsync(h->Weff.p, d_Weff, wb, hipMemcpyDeviceToDevice, h->stream));
+    return enqueue_gibbs_forward(h);
+}
+
+// chunks of PGL_RS_CHUNK bins of the handle's time range
+static long long rs_chunks(const pgl_context* h) { return (h->t_hi - h->t_lo + PGL_RS_CHUNK - 1) / PGL_RS_CHUNK; }
+
+// what the walking kernels read (pglm_binwalk.hip.h); the dry run's context has no forward pass behind it: its row stride is
+// the padded N
+static BinSource bin_source(const pgl_context* h)
+{
+    BinSource s;
+    s.GX = (const double*)h->GX.p; s.theta = (const double*)h->gtheta.p;
+    s.spk = (const int2*)h->spk.p; s.wlo = (const int*)h->wlo.p; s.whi = (const int*)h->whi.p;
+    s.t_lo = h->t_lo; s.t_hi = h->t_hi;
+    s.N = h->N; s.xs = g_dry ? 16 * ((h->N + 15) / 16) : h->gx_xs; s.P = 1 + h->Dstim + h->Kimp; s.nnz = (int)h->nnz;
+    s.dt = h->dt;
+    return s;
+}
+
+extern "C++" {                                   // (templates over the params struct)
+// One launch behind a forward pass, `threads` a workgroup.  The dry run records the name and launches nothing -- the g_dry
+// guard the RULE above enqueue_ll_grad asks for; PGL_OPT_RECORD_KERNELS appends it behind the forward launches.
+template <typename Prm>
+static int launch_behind(pgl_handle h, const std::string& name, void (*kern)(Prm), unsigned blocks, unsigned threads,
+                         const Prm& p)
+{
+    struct Append {
         explicit Append(pgl_context* h) { if (h->opt_record && !g_dry) g_rec = &h->last_kernels; }
         ~Append() { g_rec = nullptr; }
     } record(h);
-    const auto named = [](const std::string& name) {          // true: dry run, launch nothing
-        if (g_dry) g_dry->push_back(name);
-        else if (g_rec) g_rec->push_back(name);
-        return g_dry != nullptr;
-    };
-    const long long nchunks = (h->t_hi - h->t_lo + PGL_RS_CHUNK - 1) / PGL_RS_CHUNK;
-    const int xs = g_dry ? 16 * ((h->N + 15) / 16) : h->gx_xs;
-    ENSURE(h->rs_pre, (size_t)std::max<int64_t>(h->nnz, 1) * 8);
-    ENSURE(h->rs_tot, (size_t)nchunks * xs * 8);
-    ENSURE(h->rs_cum, (size_t)(nchunks + 1) * xs * 8);
+    if (g_dry || g_rec) (g_dry ? g_dry : g_rec)->push_back(name);
+    if (g_dry) return PGL_OK;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), 0, h->stream, p);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+// the same for a kernel over units x columns of GX (256 threads a workgroup); walk1 / walk0: the explinear / exp
+// instantiations of a walking kernel `fam`
+static unsigned gx_blocks(long long units, const BinSource& s) { return (unsigned)((units * s.xs + 255) / 256); }
+template <typename Prm>
+static int launch_walk(pgl_handle h, const char* fam, void (*walk1)(Prm), void (*walk0)(Prm), long long units, const Prm& p)
+{
+    const bool el = h->nlin == PGL_NLIN_EXPLINEAR;
+    return launch_behind(h, std::string(fam) + (el ? "<1>" : "<0>"), el ? walk1 : walk0, gx_blocks(units, p.src), 256, p);
+}
+}  // extern "C++"
+
+// the k_rescale_* launches behind a forward pass.  The dry run of the dispatch runs this too: see launch_behind.
+static int enqueue_rescale(pgl_handle h, double* d_tau, const long long* d_off, double* d_stats)
+{
     RescaleParams p;
-    p.GX = (const double*)h->GX.p; p.theta = (const double*)h->gtheta.p;
-    p.spk = (const int2*)h->spk.p; p.wlo = (const int*)h->wlo.p; p.whi = (const int*)h->whi.p;
+    p.src = bin_source(h);
+    p.nchunks = (int)rs_chunks(h);
+    ENSURE(h->rs_pre, (size_t)std::max<int64_t>(h->nnz, 1) * 8);
+    ENSURE(h->rs_tot, (size_t)p.nchunks * p.src.xs * 8);
+    ENSURE(h->rs_cum, (size_t)(p.nchunks + 1) * p.src.xs * 8);
     p.pre = (double*)h->rs_pre.p; p.tot = (double*)h->rs_tot.p; p.cum = (double*)h->rs_cum.p;
     p.off = d_off; p.tau = d_tau; p.stats = d_stats;
-    p.t_lo = h->t_lo; p.t_hi = h->t_hi;
-    p.N = h->N; p.xs = xs; p.P = 1 + h->Dstim + h->Kimp; p.nnz = (int)h->nnz; p.nchunks = (int)nchunks;
-    p.dt = h->dt;
-    const unsigned blocks = (unsigned)((nchunks * xs + 255) / 256);
-    if (!named(h->nlin == PGL_NLIN_EXPLINEAR ? "k_rescale_chunk<1>" : "k_rescale_chunk<0>")) {
-        if (h->nlin == PGL_NLIN_EXPLINEAR) hipLaunchKernelGGL(k_rescale_chunk<1>, dim3(blocks), dim3(256), 0, h->stream, p);
-        else hipLaunchKernelGGL(k_rescale_chunk<0>, dim3(blocks), dim3(256), 0, h->stream, p);
-        HIPCHK(hipGetLastError());
-    }
-    if (!named("k_rescale_scan")) {
-        hipLaunchKernelGGL(k_rescale_scan, dim3((h->N + 15) / 16), dim3(16 * PGL_RS_SEGS), 0, h->stream, p);
-        HIPCHK(hipGetLastError());
-    }
-    if (!named("k_rescale_finish")) {
-        hipLaunchKernelGGL(k_rescale_finish, dim3(h->N), dim3(256), 0, h->stream, p);
-        HIPCHK(hipGetLastError());
-    }
-    return PGL_OK;
+    int rc = launch_walk(h, "k_rescale_chunk", k_rescale_chunk<1>, k_rescale_chunk<0>, p.nchunks, p);
+    if (rc) return rc;
+    rc = launch_behind(h, "k_rescale_scan", k_rescale_scan, (h->N + 15) / 16, 16 * PGL_RS_SEGS, p);
+    if (rc) return rc;
+    return launch_behind(h, "k_rescale_finish", k_rescale_finish, h->N, 256, p);
 }
 
 int pgl_rescale_dev(pgl_handle h, const double* d_theta, const double* d_Weff, double* d_tau, const int64_t* d_off,
@@ -2856,18 +2898,8 @@ int pgl_rescale_dev(pgl_handle h, const double* d_theta, const double* d_Weff, d
     int rc = check_ready(h);
     if (rc) return rc;
     if (!d_theta || !d_Weff || !d_tau || !d_off || !d_stats) return fail(PGL_ERR_ARG, "null argument");
-    if ((h->t_hi - h->t_lo + PGL_RS_CHUNK - 1) / PGL_RS_CHUNK > 0x7fffffff / 2048)
-        return fail(PGL_ERR_UNSUPPORTED, "time range too long for the rescaling kernels");
-    HIPCHK(hipSetDevice(h->device));
-    const size_t P = 1 + (size_t)h->Dstim + h->Kimp;
-    const int N = h->N;
-    ENSURE(h->gtheta, (size_t)N * P * 8);
-    ENSURE(h->Weff, (size_t)N * N * 8);
-    if (d_theta != h->gtheta.p)
-        HIPCHK(hipMemcpyAsync(h->gtheta.p, d_theta, (size_t)N * P * 8, hipMemcpyDeviceToDevice, h->stream));
-    if (d_Weff != h->Weff.p)
-        HIPCHK(hipMemcpyAsync(h->Weff.p, d_Weff, (size_t)N * N * 8, hipMemcpyDeviceToDevice, h->stream));
-    rc = enqueue_gibbs_forward(h);
+    if (rs_chunks(h) > 0x7fffffff / 2048) return fail(PGL_ERR_UNSUPPORTED, "time range too long for the rescaling kernels");
+    rc = forward_from_dev(h, d_theta, d_Weff);
     if (rc) return rc;
     return enqueue_rescale(h, d_tau, (const long long*)d_off, d_stats);
 }
@@ -2878,21 +2910,17 @@ int pgl_rescale(pgl_handle h, const double* theta, const double* Weff, double* t
     if (rc) return rc;
     if (!theta || !Weff || !tau_out || !stats_out) return fail(PGL_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(h->device));
-    const size_t P = 1 + (size_t)h->Dstim + h->Kimp;
     const int N = h->N;
     std::vector<int64_t> off((size_t)N + 1);
     rc = pgl_rescale_count(h, off.data());
     if (rc) return rc;
     const size_t ntau = (size_t)off[(size_t)N];
-    ENSURE(h->gtheta, (size_t)N * P * 8);
-    ENSURE(h->Weff, (size_t)N * N * 8);
     ENSURE(h->rs_off, ((size_t)N + 1) * 8);
     ENSURE(h->rs_tau, std::max<size_t>(ntau, 1) * 8);
     ENSURE(h->rs_stats, (size_t)N * 4 * 8);
-    HIPCHK(hipMemcpyAsync(h->gtheta.p, theta, (size_t)N * P * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->Weff.p, Weff, (size_t)N * N * 8, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->rs_off.p, off.data(), ((size_t)N + 1) * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));          // (pageable sources: see pgl_gibbs_prepare_all)
+    rc = upload_draw(h, theta, Weff);                 // (its synchronise covers the offsets too)
+    if (rc) return rc;
     rc = pgl_rescale_dev(h, (const double*)h->gtheta.p, (const double*)h->Weff.p, (double*)h->rs_tau.p,
                          (const int64_t*)h->rs_off.p, (double*)h->rs_stats.p);
     if (rc) return rc;
@@ -2903,54 +2931,30 @@ int pgl_rescale(pgl_handle h, const double* theta, const double* Weff, double* t
 }
 
 // ---- pointwise log-likelihood: block sums of the ll terms of a draw (pglm_pointwise.hip.h) ------------------------------
-static long long pointwise_chunks(const pgl_context* h) { return (h->t_hi - h->t_lo + PGL_RS_CHUNK - 1) / PGL_RS_CHUNK; }
-
 int pgl_pointwise_count(pgl_handle h, int block_chunks, int64_t* n_blocks_out)
 {
     if (!h) return fail(PGL_ERR_ARG, "null handle");
     if (!n_blocks_out) return fail(PGL_ERR_ARG, "null argument");
     if (block_chunks < 1) return fail(PGL_ERR_ARG, "block_chunks must be at least 1");
-    *n_blocks_out = (pointwise_chunks(h) + block_chunks - 1) / block_chunks;
+    *n_blocks_out = (rs_chunks(h) + block_chunks - 1) / block_chunks;
     return PGL_OK;
 }
 
-// the k_pw_* launches behind a forward pass (GX of the handle's time range is on the stream).  The dry run of the dispatch
-// runs this too: the RULE above enqueue_ll_grad holds here.
+// the k_pw_* launches behind a forward pass.  The dry run of the dispatch runs this too: see launch_behind.
 static int enqueue_pointwise(pgl_handle h, int block_chunks, double* d_ll_blk, double* d_acc, long long draw)
 {
-    struct Append {                                            // PGL_OPT_RECORD_KERNELS: behind the forward launches
-        explicit Append(pgl_context* h) { if (h->opt_record && !g_dry) g_rec = &h->last_kernels; }
-        ~Append() { g_rec = nullptr; }
-    } record(h);
-    const auto named = [](const std::string& name) {          // true: dry run, launch nothing
-        if (g_dry) g_dry->push_back(name);
-        else if (g_rec) g_rec->push_back(name);
-        return g_dry != nullptr;
-    };
-    const long long nchunks = pointwise_chunks(h);
-    const long long n_blocks = (nchunks + block_chunks - 1) / block_chunks;
-    const int xs = g_dry ? 16 * ((h->N + 15) / 16) : h->gx_xs;
-    ENSURE(h->pw_part, (size_t)nchunks * xs * 8);
+    const long long nchunks = rs_chunks(h);
     PointwiseParams p;
-    p.GX = (const double*)h->GX.p; p.theta = (const double*)h->gtheta.p;
-    p.spk = (const int2*)h->spk.p; p.wlo = (const int*)h->wlo.p; p.whi = (const int*)h->whi.p;
+    p.src = bin_source(h);
+    ENSURE(h->pw_part, (size_t)nchunks * p.src.xs * 8);
     p.part = (double*)h->pw_part.p; p.ll_blk = d_ll_blk; p.acc = d_acc;
-    p.t_lo = h->t_lo; p.t_hi = h->t_hi; p.draw = draw;
-    p.N = h->N; p.xs = xs; p.P = 1 + h->Dstim + h->Kimp; p.nnz = (int)h->nnz; p.nchunks = (int)nchunks;
-    p.block_chunks = (int)std::min<long long>(block_chunks, nchunks); p.n_blocks = (int)n_blocks;
-    p.dt = h->dt;
-    if (!named(h->nlin == PGL_NLIN_EXPLINEAR ? "k_pw_chunk<1>" : "k_pw_chunk<0>")) {
-        const unsigned blocks = (unsigned)((nchunks * xs + 255) / 256);
-        if (h->nlin == PGL_NLIN_EXPLINEAR) hipLaunchKernelGGL(k_pw_chunk<1>, dim3(blocks), dim3(256), 0, h->stream, p);
-        else hipLaunchKernelGGL(k_pw_chunk<0>, dim3(blocks), dim3(256), 0, h->stream, p);
-        HIPCHK(hipGetLastError());
-    }
-    if (!named("k_pw_block")) {
-        const unsigned blocks = (unsigned)((n_blocks * xs + 255) / 256);
-        hipLaunchKernelGGL(k_pw_block, dim3(blocks), dim3(256), 0, h->stream, p);
-        HIPCHK(hipGetLastError());
-    }
-    return PGL_OK;
+    p.draw = draw;
+    p.nchunks = (int)nchunks;
+    p.block_chunks = (int)std::min<long long>(block_chunks, nchunks);
+    p.n_blocks = (int)((nchunks + block_chunks - 1) / block_chunks);
+    const int rc = launch_walk(h, "k_pw_chunk", k_pw_chunk<1>, k_pw_chunk<0>, nchunks, p);
+    if (rc) return rc;
+    return launch_behind(h, "k_pw_block", k_pw_block, gx_blocks(p.n_blocks, p.src), 256, p);
 }
 
 int pgl_pointwise_dev(pgl_handle h, const double* d_theta, const double* d_Weff, int block_chunks, double* d_ll_blk,
@@ -2962,18 +2966,8 @@ int pgl_pointwise_dev(pgl_handle h, const double* d_theta, const double* d_Weff,
     if (!d_ll_blk && !d_acc) return fail(PGL_ERR_ARG, "pointwise ll: neither d_ll_blk nor d_acc is given");
     if (block_chunks < 1) return fail(PGL_ERR_ARG, "block_chunks must be at least 1");
     if (draw < 0) return fail(PGL_ERR_ARG, "draw must not be negative");
-    if (pointwise_chunks(h) > 0x7fffffff / 2048)
-        return fail(PGL_ERR_UNSUPPORTED, "time range too long for the pointwise kernels");
-    HIPCHK(hipSetDevice(h->device));
-    const size_t P = 1 + (size_t)h->Dstim + h->Kimp;
-    const int N = h->N;
-    ENSURE(h->gtheta, (size_t)N * P * 8);
-    ENSURE(h->Weff, (size_t)N * N * 8);
-    if (d_theta != h->gtheta.p)
-        HIPCHK(hipMemcpyAsync(h->gtheta.p, d_theta, (size_t)N * P * 8, hipMemcpyDeviceToDevice, h->stream));
-    if (d_Weff != h->Weff.p)
-        HIPCHK(hipMemcpyAsync(h->Weff.p, d_Weff, (size_t)N * N * 8, hipMemcpyDeviceToDevice, h->stream));
-    rc = enqueue_gibbs_forward(h);
+    if (rs_chunks(h) > 0x7fffffff / 2048) return fail(PGL_ERR_UNSUPPORTED, "time range too long for the pointwise kernels");
+    rc = forward_from_dev(h, d_theta, d_Weff);
     if (rc) return rc;
     return enqueue_pointwise(h, block_chunks, d_ll_blk, d_acc, (long long)draw);
 }
@@ -2987,15 +2981,10 @@ int pgl_pointwise(pgl_handle h, const double* theta, const double* Weff, int blo
     rc = pgl_pointwise_count(h, block_chunks, &n_blocks);
     if (rc) return rc;
     HIPCHK(hipSetDevice(h->device));
-    const size_t P = 1 + (size_t)h->Dstim + h->Kimp;
-    const int N = h->N;
-    const size_t bytes = (size_t)n_blocks * N * 8;
-    ENSURE(h->gtheta, (size_t)N * P * 8);
-    ENSURE(h->Weff, (size_t)N * N * 8);
+    const size_t bytes = (size_t)n_blocks * h->N * 8;
     ENSURE(h->pw_out, bytes);
-    HIPCHK(hipMemcpyAsync(h->gtheta.p, theta, (size_t)N * P * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->Weff.p, Weff, (size_t)N * N * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));          // (pageable sources: see pgl_gibbs_prepare_all)
+    rc = upload_draw(h, theta, Weff);
+    if (rc) return rc;
     rc = pgl_pointwise_dev(h, (const double*)h->gtheta.p, (const double*)h->Weff.p, block_chunks, (double*)h->pw_out.p,
                            nullptr, 0);
     if (rc) return rc;
@@ -3022,48 +3011,23 @@ int pgl_rate_windows_count(pgl_handle h, int64_t win, int64_t* n_win_out)
     return PGL_OK;
 }
 
-// the k_rw_* launches behind a forward pass (GX of the handle's time range is on the stream).  The dry run of the dispatch
-// runs this too: the RULE above enqueue_ll_grad holds here.
+// the k_rw_* launches behind a forward pass.  The dry run of the dispatch runs this too: see launch_behind.
 static int enqueue_rate_windows(pgl_handle h, long long win, double* d_lam, double* d_obs, double* d_acc, long long draw)
 {
-    struct Append {                                            // PGL_OPT_RECORD_KERNELS: behind the forward launches
-        explicit Append(pgl_context* h) { if (h->opt_record && !g_dry) g_rec = &h->last_kernels; }
-        ~Append() { g_rec = nullptr; }
-    } record(h);
-    const auto named = [](const std::string& name) {          // true: dry run, launch nothing
-        if (g_dry) g_dry->push_back(name);
-        else if (g_rec) g_rec->push_back(name);
-        return g_dry != nullptr;
-    };
-    win = std::min<long long>(win, h->t_hi - h->t_lo);        // (one window: its length is the range)
-    long long n_win, npieces;
-    rate_windows_shape(h, win, n_win, npieces);
-    const int xs = g_dry ? 16 * ((h->N + 15) / 16) : h->gx_xs;
-    ENSURE(h->rw_part, (size_t)npieces * xs * 8);
-    ENSURE(h->rw_cnt, (size_t)npieces * xs * 4);
     RateWinParams p;
-    p.GX = (const double*)h->GX.p; p.theta = (const double*)h->gtheta.p;
-    p.spk = (const int2*)h->spk.p; p.wlo = (const int*)h->wlo.p; p.whi = (const int*)h->whi.p;
+    p.src = bin_source(h);
+    p.win = std::min<long long>(win, h->t_hi - h->t_lo);      // (one window: its length is the range)
+    rate_windows_shape(h, p.win, p.n_win, p.npieces);
+    ENSURE(h->rw_part, (size_t)p.npieces * p.src.xs * 8);
+    ENSURE(h->rw_cnt, (size_t)p.npieces * p.src.xs * 4);
     p.part = (double*)h->rw_part.p; p.cnt = (int*)h->rw_cnt.p; p.lam = d_lam; p.obs = d_obs; p.acc = d_acc;
-    p.t_lo = h->t_lo; p.t_hi = h->t_hi; p.win = win; p.draw = draw;
-    p.n_win = n_win; p.npieces = npieces;
-    p.ppw = (int)pgl_rw_pieces(win);
-    p.group = (p.ppw == 1) ? (int)std::max<long long>(PGL_RW_PIECE / win, 1) : 1;
-    p.nunits = (npieces + p.group - 1) / p.group;
-    p.N = h->N; p.xs = xs; p.P = 1 + h->Dstim + h->Kimp; p.nnz = (int)h->nnz;
-    p.dt = h->dt;
-    if (!named(h->nlin == PGL_NLIN_EXPLINEAR ? "k_rw_piece<1>" : "k_rw_piece<0>")) {
-        const unsigned blocks = (unsigned)((p.nunits * xs + 255) / 256);
-        if (h->nlin == PGL_NLIN_EXPLINEAR) hipLaunchKernelGGL(k_rw_piece<1>, dim3(blocks), dim3(256), 0, h->stream, p);
-        else hipLaunchKernelGGL(k_rw_piece<0>, dim3(blocks), dim3(256), 0, h->stream, p);
-        HIPCHK(hipGetLastError());
-    }
-    if (!named("k_rw_window")) {
-        const unsigned blocks = (unsigned)((n_win * xs + 255) / 256);
-        hipLaunchKernelGGL(k_rw_window, dim3(blocks), dim3(256), 0, h->stream, p);
-        HIPCHK(hipGetLastError());
-    }
-    return PGL_OK;
+    p.draw = draw;
+    p.ppw = (int)pgl_rw_pieces(p.win);
+    p.group = (p.ppw == 1) ? (int)std::max<long long>(PGL_RW_PIECE / p.win, 1) : 1;
+    p.nunits = (p.npieces + p.group - 1) / p.group;
+    const int rc = launch_walk(h, "k_rw_piece", k_rw_piece<1>, k_rw_piece<0>, p.nunits, p);
+    if (rc) return rc;
+    return launch_behind(h, "k_rw_window", k_rw_window, gx_blocks(p.n_win, p.src), 256, p);
 }
 
 int pgl_rate_windows_dev(pgl_handle h, const double* d_theta, const double* d_Weff, int64_t win, double* d_lam, double* d_obs,
@@ -3085,16 +3049,7 @@ int pgl_rate_windows_dev(pgl_handle h, const double* d_theta, const double* d_We
     }
     int rc = check_ready(h);
     if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    const size_t P = 1 + (size_t)h->Dstim + h->Kimp;
-    const int N = h->N;
-    ENSURE(h->gtheta, (size_t)N * P * 8);
-    ENSURE(h->Weff, (size_t)N * N * 8);
-    if (d_theta != h->gtheta.p)
-        HIPCHK(hipMemcpyAsync(h->gtheta.p, d_theta, (size_t)N * P * 8, hipMemcpyDeviceToDevice, h->stream));
-    if (d_Weff != h->Weff.p)
-        HIPCHK(hipMemcpyAsync(h->Weff.p, d_Weff, (size_t)N * N * 8, hipMemcpyDeviceToDevice, h->stream));
-    rc = enqueue_gibbs_forward(h);
+    rc = forward_from_dev(h, d_theta, d_Weff);
     if (rc) return rc;
     return enqueue_rate_windows(h, (long long)win, d_lam, d_obs, d_acc, (long long)draw);
 }
@@ -3108,15 +3063,11 @@ int pgl_rate_windows(pgl_handle h, const double* theta, const double* Weff, int6
     rc = pgl_rate_windows_count(h, win, &n_win);
     if (rc) return rc;
     HIPCHK(hipSetDevice(h->device));
-    const size_t P = 1 + (size_t)h->Dstim + h->Kimp;
     const int N = h->N;
     const size_t bytes = (size_t)n_win * N * 8;
-    ENSURE(h->gtheta, (size_t)N * P * 8);
-    ENSURE(h->Weff, (size_t)N * N * 8);
     ENSURE(h->rw_out, 2 * bytes);
-    HIPCHK(hipMemcpyAsync(h->gtheta.p, theta, (size_t)N * P * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->Weff.p, Weff, (size_t)N * N * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));          // (pageable sources: see pgl_gibbs_prepare_all)
+    rc = upload_draw(h, theta, Weff);
+    if (rc) return rc;
     double* d_lam = (double*)h->rw_out.p;
     rc = pgl_rate_windows_dev(h, (const double*)h->gtheta.p, (const double*)h->Weff.p, win, d_lam, d_lam + (size_t)n_win * N,
                               nullptr, 0);

@@ -34,6 +34,8 @@
 // pglm_prox.hip.h).
 // Simulation produces spikes instead of reading them: one workgroup per replicate runs the time loop (k_simulate,
 // pglm_simulate.hip.h).
+// Rescaled intervals, the pointwise ll and the rate windows below sweep the forward-only pass's currents once, a thread per
+// (time unit, neuron) next to the neuron's event list: one source struct and one walk (pgl_bin_walk, pglm_binwalk.hip.h).
 // Model comparison needs the log-likelihood of a draw resolved in time: block sums behind the forward-only pass, folded over
 // the draws on the device (k_pw_chunk, k_pw_block, pglm_pointwise.hip.h).
 // Firing-rate bands and windowed predictive residuals need the expected and observed counts over user-chosen time windows,
@@ -66,6 +68,7 @@
 #include "pglm_ais_dense.hip.h"
 #include "pglm_smc.hip.h"
 #include "pglm_prox.hip.h"
+#include "pglm_binwalk.hip.h"
 #include "pglm_rescale.hip.h"
 #include "pglm_pointwise.hip.h"
 #include "pglm_ratewin.hip.h"

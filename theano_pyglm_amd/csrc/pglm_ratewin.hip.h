@@ -5,11 +5,11 @@
 // have nothing to do with the 256-bin chunk grid of the rescaling kernels; the order of every sum is the one pglm_ratewin.h
 // fixes (pieces of at most PGL_RW_PIECE = 256 bins counted from the window's own first bin, each summed in time order, added
 // in piece order), so the bits of a window do not depend on how the work is cut.  ONE read of GX, no (nT, N) array, two launches:
-//   k_rw_piece    units x columns of GX, consecutive lanes on consecutive neurons (k_pw_chunk's geometry: the 16 lanes of a
-//                 post tile read one 128-byte line of a row, PGL_RS_UNROLL rows in flight).  win > 256: a unit is one piece of a
-//                 window, so a long window is spread over ceil(win / 256) threads per neuron.  win <= 256: a window is one
-//                 piece and a unit is floor(256 / win) consecutive windows, so a thread still owns about 256 bins; it restarts
-//                 its sums at every window start.  Per piece: the sum of the rate and the sum of the spike counts -> part, cnt;
+//   k_rw_piece    units x columns of GX, a thread per (unit, neuron) on the walk of pglm_binwalk.hip.h.  win > 256: a unit is
+//                 one piece of a window, so a long window is spread over ceil(win / 256) threads per neuron.  win <= 256: a
+//                 window is one piece and a unit is floor(256 / win) consecutive windows, so a thread still owns about 256
+//                 bins; it restarts its sums at every window start.  Per piece: the sum of the rate and the sum of the spike
+//                 counts -> part, cnt;
 //   k_rw_window   one thread per (window, neuron): the window's piece sums added in piece order -> Lam, obs, and, with an
 //                 accumulator, the fold of pglm_ratewin.h (Welford mean and M2, min, max, running mean of the Poisson mid-p
 //                 value of the observed count).  With win >= the range this launch has N threads and reads nT / 256 doubles each.
@@ -24,22 +24,16 @@
 #include "pglm_ratewin.h"
 
 struct RateWinParams {
-    const double* GX;         // (nT, xs) bias-free total current
-    const double* theta;      // (N, P): column 0 is the bias
-    const int2* spk;          // event lists (bin, count), neuron after neuron, time-sorted
-    const int* wlo;           // window tables of the event lists (pgl_rs_first_event)
-    const int* whi;
+    BinSource src;            // currents, biases, event lists, time range (pglm_binwalk.hip.h)
     double* part;             // (npieces, xs) piece sums of the rate
     int* cnt;                 // (npieces, xs) piece sums of the spike counts
     double* lam;              // (n_win, N) expected counts, or null
     double* obs;              // (n_win, N) observed counts, or null
     double* acc;              // (PGL_RW_NACC, n_win, N) accumulator over draws, or null
-    long long t_lo, t_hi, win, draw;
+    long long win, draw;
     long long n_win, npieces, nunits;
-    int N, xs, P, nnz;
     int ppw;                  // pieces of a whole window: ceil(win / 256)
     int group;                // pieces (= windows) per unit where ppw = 1, else 1
-    double dt;
 };
 
 __device__ __forceinline__ double pgl_rw_lambda(const double x, const int nlin, const double* __restrict__ C)
@@ -66,81 +60,66 @@ __device__ __forceinline__ double pgl_rw_lambda(const double x, const int nlin, 
 template <int NLIN>
 __global__ __launch_bounds__(256) void k_rw_piece(const RateWinParams p)
 {
+    const BinSource& s = p.src;
     const long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    const int j = (int)(g % p.xs);
-    const long long u = g / p.xs;
-    if (u >= p.nunits || j >= p.N) return;
+    const int j = (int)(g % s.xs);
+    const long long u = g / s.xs;
+    if (u >= p.nunits || j >= s.N) return;
     const long long q0 = u * p.group;                            // the unit's first piece
     long long t0;
     int span, step;                                              // bins of the unit, bins of each of its pieces
     if (p.ppw == 1) {
-        t0 = p.t_lo + q0 * p.win;
-        const long long room = p.t_hi - t0, all = (long long)p.group * p.win;
+        t0 = s.t_lo + q0 * p.win;
+        const long long room = s.t_hi - t0, all = (long long)p.group * p.win;
         span = (int)((room < all) ? room : all);
         step = (int)p.win;
     } else {
-        const long long w0 = p.t_lo + (q0 / p.ppw) * p.win;      // the window's first bin
+        const long long w0 = s.t_lo + (q0 / p.ppw) * p.win;      // the window's first bin
         t0 = w0 + (q0 % p.ppw) * PGL_RW_PIECE;
-        const long long wend = (w0 + p.win < p.t_hi) ? w0 + p.win : p.t_hi;
+        const long long wend = (w0 + p.win < s.t_hi) ? w0 + p.win : s.t_hi;
         span = (int)((wend - t0 < PGL_RW_PIECE) ? wend - t0 : PGL_RW_PIECE);
         step = span;
     }
-    const double bias = p.theta[(size_t)j * p.P];
-    int eend;
-    int ei = pgl_rs_first_event(p, j, t0, eend);
-    long long tn = (ei < eend) ? p.spk[ei].x : -1;
-    const double* __restrict__ gx = p.GX + (size_t)t0 * p.xs + j;
-    size_t o = (size_t)q0 * p.xs + j;
+    size_t o = (size_t)q0 * s.xs + j;
     double acc = 0.0;
     int cnt = 0, left = step;
-    for (int k = 0; k < span; k += PGL_RS_UNROLL) {
-        double x[PGL_RS_UNROLL];
-#pragma unroll
-        for (int v = 0; v < PGL_RS_UNROLL; ++v) x[v] = (k + v < span) ? gx[(size_t)(k + v) * p.xs] : 0.0;
-#pragma unroll
-        for (int v = 0; v < PGL_RS_UNROLL; ++v) {
-            // (every lane evaluates every row, rows past the unit's end at x = 0 and dropped, as k_pw_chunk does)
-            const double lam = pgl_rw_lambda(bias + x[v], NLIN, PGL_C);
-            if (k + v < span) {
-                acc += lam;
-                if (t0 + k + v == tn) {
-                    cnt += p.spk[ei].y;
-                    ++ei;
-                    tn = (ei < eend) ? p.spk[ei].x : -1;
-                }
-                if (--left == 0 || k + v + 1 == span) {          // the piece ends here
-                    p.part[o] = acc;
-                    p.cnt[o] = cnt;
-                    o += p.xs;
-                    acc = 0.0;
-                    cnt = 0;
-                    left = step;
-                }
+    pgl_bin_walk(
+        s, j, t0, span, [](const double xv) { return pgl_rw_lambda(xv, NLIN, PGL_C); },
+        [&](const int k, const bool live, double, const double lam, bool, const int count, int) {
+            if (!live) return;
+            acc += lam;
+            cnt += count;
+            if (--left == 0 || k + 1 == span) {                  // the piece ends here
+                p.part[o] = acc;
+                p.cnt[o] = cnt;
+                o += s.xs;
+                acc = 0.0;
+                cnt = 0;
+                left = step;
             }
-        }
-    }
+        });
 }
 
 __global__ __launch_bounds__(256) void k_rw_window(const RateWinParams p)
 {
     const long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    const int j = (int)(g % p.xs);
-    const long long w = g / p.xs;
-    if (w >= p.n_win || j >= p.N) return;
+    const int j = (int)(g % p.src.xs);
+    const long long w = g / p.src.xs;
+    if (w >= p.n_win || j >= p.src.N) return;
     const long long q0 = w * p.ppw;
     const long long q1 = (q0 + p.ppw < p.npieces) ? q0 + p.ppw : p.npieces;
     double s = 0.0;
     int c = 0;
     for (long long q = q0; q < q1; ++q) {
-        s += p.part[(size_t)q * p.xs + j];
-        c += p.cnt[(size_t)q * p.xs + j];
+        s += p.part[(size_t)q * p.src.xs + j];
+        c += p.cnt[(size_t)q * p.src.xs + j];
     }
-    const double lam = p.dt * s, y = (double)c;
-    const size_t o = (size_t)w * p.N + j;
+    const double lam = p.src.dt * s, y = (double)c;
+    const size_t o = (size_t)w * p.src.N + j;
     if (p.lam) p.lam[o] = lam;
     if (p.obs) p.obs[o] = y;
     if (p.acc) {
-        const size_t pl = (size_t)p.n_win * p.N;
+        const size_t pl = (size_t)p.n_win * p.src.N;
         double mean = p.acc[o], m2 = p.acc[pl + o], mn = p.acc[2 * pl + o], mx = p.acc[3 * pl + o], pit = p.acc[4 * pl + o];
         pgl_rw_fold(lam, y, p.draw, &mean, &m2, &mn, &mx, &pit);
         p.acc[o] = mean; p.acc[pl + o] = m2; p.acc[2 * pl + o] = mn; p.acc[3 * pl + o] = mx; p.acc[4 * pl + o] = pit;

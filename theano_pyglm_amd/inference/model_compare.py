@@ -40,6 +40,8 @@ Per neuron, from S draws and the blocks b (Watanabe 2010; Vehtari, Gelman & Gabr
 The held-out log predictive density log (1/S) sum_s p(test | theta_s) is what the reference's test/parallel_mcmc.py prints
 per Gibbs sample (pred_ll_cbk); here it is one block per data sequence on the same path.
 """
+import contextlib
+
 import numpy as np
 
 from theano_pyglm_amd import _lib
@@ -59,6 +61,38 @@ def _draws(samples, P):
     return s, is_tensor
 
 
+@contextlib.contextmanager
+def _draw_loop(population, x, samples, n_lo, what):
+    """with _draw_loop(...) as (torch, dev, stream, handles, S, M, run): the session of a quantity folded over posterior draws
+    (lock-step's session: the handles of every data sequence on the drivers' stream).  samples: (S, M, P) rows of neurons
+    n_lo .. n_lo + M, see _draws; `what` names the quantity where a time-sharded population is turned down.  run(call) is
+    the loop: per draw i the rows overwrite a device copy of theta_matrix(x) and every handle k gets
+    call(i, k, handle, theta_ptr, Weff_ptr); nothing in it synchronises with the host."""
+    from theano_pyglm_amd.inference.lockstep import session
+    if getattr(population, '_time_shard', None) is not None:
+        raise ValueError("%s of a time-sharded population %s not implemented" % what)
+    N, P = population.N, population.glm.P
+    s, is_tensor = _draws(samples, P)
+    S, M = int(s.shape[0]), int(s.shape[1])
+    if n_lo < 0 or n_lo + M > N:
+        raise ValueError("neurons %d .. %d of %d" % (n_lo, n_lo + M, N))
+    population._check_vars(x)
+    theta0 = np.ascontiguousarray(population.theta_matrix(x))
+    with session(population) as (torch, dev, stream, handles):
+        f64 = torch.float64
+        theta = torch.tensor(theta0, dtype=f64, device=dev)
+        Weff = torch.tensor(np.ascontiguousarray(population.W_eff(x)), dtype=f64, device=dev)
+        d_s = s.to(device=dev, dtype=f64).contiguous() if is_tensor else torch.tensor(s, dtype=f64, device=dev)
+        rows = theta[n_lo:n_lo + M]
+
+        def run(call):
+            for i in range(S):
+                rows.copy_(d_s[i])
+                for k, h in enumerate(handles):
+                    call(i, k, h, theta.data_ptr(), Weff.data_ptr())
+        yield torch, dev, stream, handles, S, M, run
+
+
 def pointwise_ll_draws(population, x, samples, block_chunks=40, n_lo=0, pointwise=False):
     return _pointwise_ll_draws(population, x, samples, block_chunks, n_lo, pointwise, False)
 
@@ -74,35 +108,20 @@ def _pointwise_ll_draws(population, x, samples, block_chunks, n_lo, pointwise, p
     'route' come back instead of 'll'; above PSIS_MAX_DRAWS the matrix comes back for the numpy statement.)
     Returns a dict: 'acc' (4, n_blocks, M) -- m, e, mean, M2 of every (block, neuron), the data sequences one after the
     other --, 'n_draws', 'block_chunks', 'blocks_per_sequence', and with pointwise=True 'll' (S, n_blocks, M)."""
-    from theano_pyglm_amd.inference.lockstep import session
-    if getattr(population, '_time_shard', None) is not None:
-        raise ValueError("the pointwise log-likelihood of a time-sharded population is not implemented")
     block_chunks = int(block_chunks)
     if block_chunks < 1:
         raise ValueError("block_chunks must be at least 1")
-    N, P = population.N, population.glm.P
-    s, is_tensor = _draws(samples, P)
-    S, M = int(s.shape[0]), int(s.shape[1])
-    if n_lo < 0 or n_lo + M > N:
-        raise ValueError("neurons %d .. %d of %d" % (n_lo, n_lo + M, N))
-    population._check_vars(x)
-    theta0 = np.ascontiguousarray(population.theta_matrix(x))
-    with session(population) as (torch, dev, stream, handles):
+    N = population.N
+    what = ("the pointwise log-likelihood", "is")
+    with _draw_loop(population, x, samples, n_lo, what) as (torch, dev, stream, handles, S, M, run):
         f64 = torch.float64
-        theta = torch.tensor(theta0, dtype=f64, device=dev)
-        Weff = torch.tensor(np.ascontiguousarray(population.W_eff(x)), dtype=f64, device=dev)
-        d_s = s.to(device=dev, dtype=f64).contiguous() if is_tensor else torch.tensor(s, dtype=f64, device=dev)
         nb = [h.pointwise_count(block_chunks) for h in handles]
         off = np.concatenate(([0], np.cumsum(nb))).astype(int)
         accs = [torch.empty((4, n, N), dtype=f64, device=dev) for n in nb]
         ll = torch.empty((S, int(off[-1]), N), dtype=f64, device=dev) if pointwise or psis else None
         pointwise = ll is not None
-        rows = theta[n_lo:n_lo + M]
-        for i in range(S):
-            rows.copy_(d_s[i])
-            for k, h in enumerate(handles):
-                h.pointwise_dev(theta.data_ptr(), Weff.data_ptr(), block_chunks, ll[i, off[k]:].data_ptr() if pointwise else 0,
-                                accs[k].data_ptr(), i)
+        run(lambda i, k, h, theta, Weff: h.pointwise_dev(theta, Weff, block_chunks, ll[i, off[k]:].data_ptr() if pointwise else 0,
+                                                         accs[k].data_ptr(), i))
         if psis and 2 <= S <= _lib.PSIS_MAX_DRAWS:           # the matrix stays where it is: (4, n_blocks, M) comes back
             cols = ll if M == N else ll[:, :, n_lo:n_lo + M].contiguous()
             d_psis = handles[0].psis_loo(cols)

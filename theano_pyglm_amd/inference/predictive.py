@@ -97,37 +97,20 @@ def rate_bands(population, x, samples, win=50, n_lo=0, keep=False):
     neuron pit_ks (the KS distance of the finite pit values from the uniform law) and n_pit_nan; n_draws, win,
     windows_per_sequence, n_lo.  keep=True adds 'draws' (S, n_win, M), every draw's expected counts (for quantile bands),
     kept on the device until the end.  mean / width[:, None] is the firing rate in Hz."""
-    from theano_pyglm_amd.inference.lockstep import session
-    from theano_pyglm_amd.inference.model_compare import _draws
-    if getattr(population, '_time_shard', None) is not None:
-        raise ValueError("the rate bands of a time-sharded population are not implemented")
+    from theano_pyglm_amd.inference.model_compare import _draw_loop
     win = int(win)
     if win < 1:
         raise ValueError("win must be at least 1")
-    N, P = population.N, population.glm.P
-    s, is_tensor = _draws(samples, P)
-    S, M = int(s.shape[0]), int(s.shape[1])
-    if n_lo < 0 or n_lo + M > N:
-        raise ValueError("neurons %d .. %d of %d" % (n_lo, n_lo + M, N))
-    population._check_vars(x)
-    theta0 = np.ascontiguousarray(population.theta_matrix(x))
-    dt = population.glm.dt
-    with session(population) as (torch, dev, stream, handles):
+    N, dt = population.N, population.glm.dt
+    with _draw_loop(population, x, samples, n_lo, ("the rate bands", "are")) as (torch, dev, stream, handles, S, M, run):
         f64 = torch.float64
-        theta = torch.tensor(theta0, dtype=f64, device=dev)
-        Weff = torch.tensor(np.ascontiguousarray(population.W_eff(x)), dtype=f64, device=dev)
-        d_s = s.to(device=dev, dtype=f64).contiguous() if is_tensor else torch.tensor(s, dtype=f64, device=dev)
         nw = [h.rate_windows_count(win) for h in handles]
         off = np.concatenate(([0], np.cumsum(nw))).astype(int)
         accs = [torch.empty((_lib.RW_NACC, n, N), dtype=f64, device=dev) for n in nw]
         obss = [torch.empty((n, N), dtype=f64, device=dev) for n in nw]
         lam = torch.empty((S, int(off[-1]), N), dtype=f64, device=dev) if keep else None
-        rows = theta[n_lo:n_lo + M]
-        for i in range(S):
-            rows.copy_(d_s[i])
-            for k, h in enumerate(handles):
-                h.rate_windows_dev(theta.data_ptr(), Weff.data_ptr(), win, lam[i, off[k]:].data_ptr() if keep else 0,
-                                   obss[k].data_ptr() if i == 0 else 0, accs[k].data_ptr(), i)
+        run(lambda i, k, h, theta, Weff: h.rate_windows_dev(theta, Weff, win, lam[i, off[k]:].data_ptr() if keep else 0,
+                                                            obss[k].data_ptr() if i == 0 else 0, accs[k].data_ptr(), i))
         stream.synchronize()
         acc = np.concatenate([a.cpu().numpy() for a in accs], axis=1)[:, :, n_lo:n_lo + M]
         obs = np.concatenate([o.cpu().numpy() for o in obss], axis=0)[:, n_lo:n_lo + M]

@@ -372,6 +372,20 @@ class Population(object):
         parameter vector -- minus coord_descent.grad_nlp (coord_descent.py:61-80)."""
         return self.compute_lp_grad_packed(vars, n, n + 1)[1][0]
 
+    def _per_sequence(self, vars, what, call):
+        """[call(handle, theta, Weff) of every data sequence] at the whole population's theta_matrix and W_eff under `vars`;
+        `what` names the quantity where a time-sharded population is turned down."""
+        if self._time_shard is not None:
+            raise ValueError("%s of a time-sharded population %s not implemented" % what)
+        self._check_vars(vars)
+        theta = self.theta_matrix(vars)
+        Weff = self.W_eff(vars)
+        out = []
+        for data in self.data_sequences:
+            self.set_data(data)
+            out.append(call(self._handle(self._current), theta, Weff))
+        return out
+
     # -- goodness of fit -------------------------------------------------------------------
     def compute_rescaled_intervals(self, vars):
         """Time rescaling (Brown et al. 2002) of every neuron's spike train under `vars`: the integrated rate between
@@ -380,16 +394,10 @@ class Population(object):
         neuron n, the data sequences one after the other (the interval before the first event of a sequence is censored);
         stats (N, 4) summed over the sequences: expected count, event bins, event bins holding more than one spike, 0.
         A bin with several spikes is one event; the discrete-time correction of Haslinger et al. (2010) is not applied."""
-        if self._time_shard is not None:
-            raise ValueError("rescaled intervals of a time-sharded population are not implemented")
-        self._check_vars(vars)
-        theta = self.theta_matrix(vars)
-        Weff = self.W_eff(vars)
         parts = [[] for _ in range(self.N)]
         stats = np.zeros((self.N, 4))
-        for data in self.data_sequences:
-            self.set_data(data)
-            tau, off, st = self._handle(self._current).rescale(theta, Weff)
+        what = ("rescaled intervals", "are")
+        for tau, off, st in self._per_sequence(vars, what, lambda h, theta, Weff: h.rescale(theta, Weff)):
             for n in range(self.N):
                 parts[n].append(tau[off[n]:off[n + 1]])
             stats += st
@@ -402,15 +410,8 @@ class Population(object):
         segmented sum on the device per data sequence (pgl_pointwise).  Returns (n_blocks_total, N), the data sequences one
         after the other; a column sums to that neuron's ll.  Given the spike history the blocks are conditionally
         independent terms: the pointwise values of inference/model_compare.py."""
-        if self._time_shard is not None:
-            raise ValueError("the pointwise log-likelihood of a time-sharded population is not implemented")
-        self._check_vars(vars)
-        theta = self.theta_matrix(vars)
-        Weff = self.W_eff(vars)
-        parts = []
-        for data in self.data_sequences:
-            self.set_data(data)
-            parts.append(self._handle(self._current).pointwise(theta, Weff, block_chunks))
+        parts = self._per_sequence(vars, ("the pointwise log-likelihood", "is"),
+                                   lambda h, theta, Weff: h.pointwise(theta, Weff, block_chunks))
         return np.concatenate(parts, axis=0) if parts else np.zeros((0, self.N))
 
     # -- firing rates in time ----------------------------------------------------------------
@@ -420,20 +421,11 @@ class Population(object):
         the window, obs = the recorded spikes in it.  One forward pass and one windowed sum on the device per data sequence
         (pgl_rate_windows); no rate array comes back to the host.  Returns (Lam, obs), each (n_win_total, N), the data
         sequences one after the other.  Lam / (win dt) is the firing rate plot_firing_rate draws from eval_state."""
-        if self._time_shard is not None:
-            raise ValueError("the expected counts of a time-sharded population are not implemented")
-        self._check_vars(vars)
-        theta = self.theta_matrix(vars)
-        Weff = self.W_eff(vars)
-        lams, obss = [], []
-        for data in self.data_sequences:
-            self.set_data(data)
-            lam, obs = self._handle(self._current).rate_windows(theta, Weff, win)
-            lams.append(lam)
-            obss.append(obs)
-        if not lams:
+        pairs = self._per_sequence(vars, ("the expected counts", "are"),
+                                   lambda h, theta, Weff: h.rate_windows(theta, Weff, win))
+        if not pairs:
             return np.zeros((0, self.N)), np.zeros((0, self.N))
-        return np.concatenate(lams, axis=0), np.concatenate(obss, axis=0)
+        return np.concatenate([lam for lam, _ in pairs], axis=0), np.concatenate([obs for _, obs in pairs], axis=0)
 
     # -- state ---------------------------------------------------------------------------
     def eval_state(self, vars):
