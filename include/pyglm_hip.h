@@ -82,9 +82,14 @@ typedef struct pgl_context* pgl_handle;
                                    * instantiations it launches, in launch order (pgl_last_kernels), and so do pgl_hvp_prepare_* /
                                    * pgl_hvp_apply_dev (k_hvp5 and the k_fused* launches around it), pgl_hess_dev (k_hess) and
                                    * pgl_rescale_dev (the forward launches, then k_rescale_*) and pgl_pointwise_dev (the forward launches,
-                                   * then k_pw_chunk and k_pw_block); 0 (default) = off */
+                                   * then k_pw_chunk and k_pw_block); pgl_gibbs_ll_cols and pgl_gibbs_update_cols APPEND the names of
+                                   * their launches (k_gibbs_cols_setup, k_gibbs_pre_features, k_gibbs_rate_cols, k_gibbs_reduce_cols2 /
+                                   * k_gibbs_ll_cols, k_gibbs_reduce_cols / k_gibbs_update_cols) to the record, which setting the option
+                                   * clears; 0 (default) = off */
 
-/* Development switches (not part of the drop-in surface; results stay valid unless stated): 95 = 2 keeps the narrow post
+/* Development switches (not part of the drop-in surface; results stay valid unless stated): 99 = debug word: bits 16..20 force
+ * the sub-block loop of k_gibbs_rate_cols (1 .. 16; bits 8..11 are the older 4-bit field of the same, bit 12 switches the
+ * shared-presynaptic path off), the low bits are timing ablations with invalid results; 95 = 2 keeps the narrow post
  * blocks of a wide population off the one-image-buffer form of k_fused6 and the block-ring kernel k_fused8 (they run on
  * k_fused2); 97 = waves per block of
  * the partial reduction; 98 = post tiles per workgroup of the K-split kernels; 99 = kernel-internal ablation bits of the
@@ -93,7 +98,7 @@ typedef struct pgl_context* pgl_handle;
 
 /* What pgl_version() returns: it changes with every change of a signature or a struct below, and a binding refuses a
  * library that reports another number (theano_pyglm_amd/_lib.py: ABI_VERSION). */
-#define PGL_ABI_VERSION 112
+#define PGL_ABI_VERSION 113
 
 const char* pgl_last_error(void);
 int pgl_version(void);
@@ -1095,6 +1100,12 @@ int pgl_plan_kernels(int N, int B, int R, int Dstim, long long nT, int stim, int
  * (which enqueues the same launch sequence on a device-less context).  Needs PGL_OPT_RECORD_KERNELS = 1 on the handle
  * (PGL_ERR_STATE otherwise).  Dev / test entry point: tests compare it with the dry run. */
 int pgl_last_kernels(pgl_handle h, char* out, int cap);
+
+/* The launch geometry the host chose for the handle's last pgl_gibbs_ll_cols call made with PGL_OPT_RECORD_KERNELS = 1
+ * (PGL_ERR_STATE without one): out[0..9] = {path (0 regime-split, 1 all-f64), CP, nsplit, column groups, nloop, time blocks,
+ * spike blocks, same_pre, gtb, rows} (the fields a path does not have: nsplit = nloop = 1, the others 0); n >= 10.
+ * Dev / test entry point: tests/test_gpu_gibbs_sweep.py holds it to the Python statement of the arithmetic. */
+int pgl_gibbs_last_geometry(pgl_handle h, int* out, int n);
 
 /* Launch geometry and algorithmic work of the fused kernel for [n_lo,n_hi):
  * info[0]=blocks, [1]=threads/block, [2]=time chunks, [3]=k-tiles(16 rows),

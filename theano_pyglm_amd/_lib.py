@@ -35,7 +35,7 @@ SYMBOLS = [
     'pgl_timing_summary', 'pgl_set_stream',
     'pgl_set_stimulus_separable', 'pgl_ll_grad_list_dev', 'pgl_gibbs_prepare_all', 'pgl_gibbs_ll_cols', 'pgl_gibbs_update_cols', 'pgl_gibbs_currents',
     'pgl_bfgs_state_doubles', 'pgl_bfgs_init_dev', 'pgl_bfgs_trial_dev', 'pgl_bfgs_objective_dev',
-    'pgl_bfgs_linesearch_dev', 'pgl_bfgs_hmul_dev', 'pgl_bfgs_hmul_hist_dev', 'pgl_bfgs_update_dev', 'pgl_bfgs_step_dev', 'pgl_plan_kernels', 'pgl_last_kernels', 'pgl_leading_singular_pairs', 'pgl_gemm_dev',
+    'pgl_bfgs_linesearch_dev', 'pgl_bfgs_hmul_dev', 'pgl_bfgs_hmul_hist_dev', 'pgl_bfgs_update_dev', 'pgl_bfgs_step_dev', 'pgl_plan_kernels', 'pgl_last_kernels', 'pgl_gibbs_last_geometry', 'pgl_leading_singular_pairs', 'pgl_gemm_dev',
     'pgl_hvp_prepare_dev', 'pgl_hvp_prepare_list_dev', 'pgl_hvp_apply_dev', 'pgl_hvp',
     'pgl_ncg_state_doubles', 'pgl_ncg_init_dev', 'pgl_ncg_cg_step_dev', 'pgl_ncg_trial_dev', 'pgl_ncg_search_step_dev',
     'pgl_hmc_state_doubles', 'pgl_hmc_init_dev', 'pgl_hmc_begin_dev', 'pgl_hmc_leap_dev',
@@ -61,7 +61,7 @@ SYMBOLS = [
 ]
 
 
-ABI_VERSION = 112                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
+ABI_VERSION = 113                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
 
 GEMM_NT, GEMM_MFMA_1, GEMM_MFMA_4, GEMM_KC_4_1_8, GEMM_KC_1_0_16 = range(5)   # PGL_GEMM_*: the kernel of pgl_gemm_dev
 
@@ -288,6 +288,7 @@ def load():
     lib.pgl_plan_kernels.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_int, C.c_int, C.c_char_p, C.c_int]
     lib.pgl_last_kernels.argtypes = [vp, C.c_char_p, C.c_int]
+    lib.pgl_gibbs_last_geometry.argtypes = [vp, vp, C.c_int]
     lib.pgl_simulate.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_double, vp, vp, vp,
                                  C.c_int64, C.c_uint64, vp, vp]
     lib.pgl_simulate_streams.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_double, vp, vp, C.c_int, C.c_uint64,
@@ -1098,10 +1099,18 @@ class DeviceGlm(object):
 
     def last_kernels(self):
         """The fused kernel instantiations the last ll_grad / gibbs_prepare_all / hvp_* / hess call launched, in launch order, as
-        plan_kernels names them (pgl_last_kernels); needs set_option(OPT_RECORD_KERNELS, 1)."""
+        plan_kernels names them (pgl_last_kernels); needs set_option(OPT_RECORD_KERNELS, 1).  gibbs_ll_cols / gibbs_update_cols
+        append the k_gibbs_* kernels they launch; set_option(OPT_RECORD_KERNELS, 1) clears the record."""
         buf = C.create_string_buffer(16384)
         _chk(self.lib.pgl_last_kernels(self.h, buf, 16384))
         return [ln for ln in buf.value.decode().splitlines() if ln]
+
+    def gibbs_last_geometry(self):
+        """Launch geometry of the last recorded gibbs_ll_cols call (pgl_gibbs_last_geometry), as a dict."""
+        v = np.zeros(10, dtype=np.int32)
+        _chk(self.lib.pgl_gibbs_last_geometry(self.h, _ptr(v), 10))
+        keys = ['path', 'CP', 'nsplit', 'ygroups', 'nloop', 'nblk', 'sblk', 'same_pre', 'gtb', 'rows']
+        return dict(zip(keys, (int(x) for x in v)))
 
     def timing_summary(self, reset=True):
         """(n_launches, mean fused-kernel ms, mean whole-call ms) since the last reset."""

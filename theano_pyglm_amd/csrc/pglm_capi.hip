@@ -102,6 +102,7 @@ struct pgl_context {
     size_t pin_args_cap = 0;
     int opt_f32 = 0, opt_nchunks = 0, opt_dbg = 0, opt_kernel = 0, opt_ptw = 0, opt_gibbs = 0, opt_finw = 0, opt_sb6 = 0, opt_epi64 = 0, opt_timing = 1, opt_slice_cols = 0, opt_hlp = 0, opt_pbmajor = 0, opt_tri_rows = 0;
     int opt_img32 = 0;                   // PGL_OPT_FEATURE_F32 = 2: f32 resident blocks for the narrow-shard kernel (k_fused8<.., 1>)
+    int gibbs_geo[10] = {-1, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // launch geometry of the last recorded pgl_gibbs_ll_cols (pgl_gibbs_last_geometry)
     int opt_record = 0;                  // PGL_OPT_RECORD_KERNELS: last_kernels holds the fused launches of the last evaluation
     std::vector<std::string> last_kernels;
     long long call_no = 0;               // evaluations enqueued since the last pgl_set_option(PGL_OPT_TIMING)
@@ -1151,6 +1152,12 @@ struct KernelRecord {
     }
     ~KernelRecord() { g_rec = nullptr; }
 };
+// the batched Gibbs entry points (pgl_gibbs_ll_cols / pgl_gibbs_update_cols) APPEND the names of their launches, in launch
+// order: several calls can follow one another between two reads of pgl_last_kernels (setting the option clears the record)
+static inline void record_gibbs(pgl_context* h, const char* name)
+{
+    if (h->opt_record) h->last_kernels.push_back(name);
+}
 
 // Enqueue one evaluation on the handle's stream.  All pointers are device pointers.
 //  * one slice (N <= 128 and N*B + Dstim <= 640): prep + fused kernel + finalize;
@@ -2306,7 +2313,10 @@ int pgl_gibbs_ll_cols(pgl_handle h, int ncols, const int* n_post, const int* n_p
             const long long slots = (long long)gibbs_rate_wg_per_cu(lds) * h->numCU;
             gp.nloop = (int)std::max(1LL, std::min(8LL, nsub * ygroups / (6 * slots)));
         }
-        if ((h->opt_dbg >> 8) & 0xf) gp.nloop = std::min(PGL_GNL, (h->opt_dbg >> 8) & 0xf);      // tests: force the sub-block loop
+        // tests: force the sub-block loop -- bits 16..20 of the debug option (1 .. PGL_GNL), else its older 4-bit field in
+        // bits 8..11 (1 .. 15; bit 12 is the same_pre switch above, so 16 << 8 forces nothing)
+        if (const int forced = ((h->opt_dbg >> 16) & 0x1f) ? (h->opt_dbg >> 16) & 0x1f : (h->opt_dbg >> 8) & 0xf)
+            gp.nloop = std::min(PGL_GNL, forced);
         const int nblk = (int)((nsub + gp.nloop - 1) / gp.nloop);
         const int sblk = std::max(1, (max_ev + 255) / 256);
         ENSURE(h->gpart, (size_t)(nblk + sblk) * ncols * PGL_KMAX * 8);
@@ -2321,9 +2331,15 @@ int pgl_gibbs_ll_cols(pgl_handle h, int ncols, const int* n_post, const int* n_p
             ENSURE(h->gfs, (size_t)h->B * gp.fs_stride * 8);
             gp.fs = (const double*)h->gfs.p;
         }
+        if (h->opt_record) {
+            const int geo[10] = {0, gp.CP, gp.nsplit, ygroups, gp.nloop, nblk, sblk, same_pre ? 1 : 0, 0, 0};
+            std::copy(geo, geo + 10, h->gibbs_geo);
+        }
+        record_gibbs(h, "k_gibbs_cols_setup");
         hipLaunchKernelGGL(k_gibbs_cols_setup, dim3((ncols * h->Rk + 255) / 256), dim3(256), 0, h->stream, gp);
         HIPCHK(hipGetLastError());
         if (same_pre) {
+            record_gibbs(h, "k_gibbs_pre_features");
             hipLaunchKernelGGL(k_gibbs_pre_features, dim3((unsigned)((nrows + 255) / 256)), dim3(256), (size_t)h->B * h->Rk * 8,
                                h->stream, gp, n_pre[0], (double*)h->gfs.p);
             HIPCHK(hipGetLastError());
@@ -2332,8 +2348,10 @@ int pgl_gibbs_ll_cols(pgl_handle h, int ncols, const int* n_post, const int* n_p
         // of their own) dispatched last: they fill the slots the rate workgroups free at the end.  (On a side stream beside
         // the rate kernel -- two event hops -- they cost more than in line: 1.365 against 1.295 ms, round 3.)
         gp.nblkR = nblk; gp.nygR = ygroups; gp.nblkS = sblk;
+        record_gibbs(h, "k_gibbs_rate_cols");
         hipLaunchKernelGGL(rate_kernel, dim3((unsigned)(nblk * ygroups + sblk * ncols)), dim3(256), lds, h->stream, gp);
         HIPCHK(hipGetLastError());
+        record_gibbs(h, "k_gibbs_reduce_cols2");
         hipLaunchKernelGGL(k_gibbs_reduce_cols2, dim3(ncols, K), dim3(64), 0, h->stream, (const double*)gp.part, nblk,
                            (const double*)gp.partS, sblk, ncols, K, h->dt, (double*)h->pin_args);
         HIPCHK(hipGetLastError());
@@ -2365,14 +2383,29 @@ int pgl_gibbs_ll_cols(pgl_handle h, int ncols, const int* n_post, const int* n_p
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_gibbs_ll_cols),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return fail(PGL_ERR_HIP, hipGetErrorString(e));
+    if (h->opt_record) {
+        const int geo[10] = {1, gp.CP, 1, ygroups, 1, nblk, 0, 0, gtb, gp.rows};
+        std::copy(geo, geo + 10, h->gibbs_geo);
+    }
+    record_gibbs(h, "k_gibbs_ll_cols");
     hipLaunchKernelGGL(k_gibbs_ll_cols, dim3(nblk, ygroups), dim3(256), lds, h->stream, gp);
     HIPCHK(hipGetLastError());
+    record_gibbs(h, "k_gibbs_reduce_cols");
     hipLaunchKernelGGL(k_gibbs_reduce_cols, dim3(ncols), dim3(64), 0, h->stream, (const double*)h->gpart.p,
                        nblk, ncols, K, (double*)h->gout.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(h->pin_args, h->gout.p, (size_t)ncols * K * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     std::memcpy(ll_out, h->pin_args, (size_t)ncols * K * 8);
+    return PGL_OK;
+}
+
+int pgl_gibbs_last_geometry(pgl_handle h, int* out, int n)
+{
+    if (!h || !out || n < 10) return fail(PGL_ERR_ARG, "bad argument");
+    if (!h->opt_record) return fail(PGL_ERR_STATE, "kernel recording is off (PGL_OPT_RECORD_KERNELS)");
+    if (h->gibbs_geo[0] < 0) return fail(PGL_ERR_STATE, "no pgl_gibbs_ll_cols call has been recorded");
+    std::copy(h->gibbs_geo, h->gibbs_geo + 10, out);
     return PGL_OK;
 }
 
@@ -2392,6 +2425,7 @@ int pgl_gibbs_update_cols(pgl_handle h, int ncols, const int* n_post, const int*
     gp.rows = 1024;
     const int nblk = (int)((nrows + gp.rows - 1) / gp.rows);
     const size_t lds = (size_t)h->B * h->Rk * 8;
+    record_gibbs(h, "k_gibbs_update_cols");
     hipLaunchKernelGGL(k_gibbs_update_cols, dim3(nblk, ygroups), dim3(256), lds, h->stream, gp, (double*)h->GX.p);
     HIPCHK(hipGetLastError());
     // the column arguments were staged in the handle's pinned block: the next call refills it, so the
