@@ -42,6 +42,7 @@ E_POS, E_NEG, X_FAST = 6e-12, 4e-5, 12.0
 X_NAN, X_FLUSH = -745.2, -744.3        # no case may put an x inside (X_NAN, X_FLUSH): the all-f64 kernel flushes there
 UPD = 1e-13
 GRB, GNL, GECAP_R, GECAP, KMAX = 256, 16, 20, 24, 16     # PGL_GRB, PGL_GNL, PGL_GECAP_R, PGL_GECAP, PGL_KMAX
+GQ, SPT_N = 256, 196                                     # PGL_GQ, PGL_SPT_N
 NUM_CU, WG_PER_CU = 256, 4             # MI355X; occupancy of k_gibbs_rate_cols at <= 40 KB of LDS
 DEFECTS = ('f32_from_8', 'drop_ragged', 'drop_last_lag', 'drop_21st', 'swap_1_8', 'spikes_from_256', 'no_aw')
 
@@ -243,20 +244,20 @@ def dbg_nloop(opt_dbg):
 
 
 def geometry(ncols, K, n_pre, nrows, max_ev, nlin, opt_gibbs=0, forced_nloop=0, R=179, slots=WG_PER_CU * NUM_CU, opt_dbg=None,
-             num_cu=NUM_CU):
+             num_cu=NUM_CU, B=5):
     """What pgl_gibbs_ll_cols launches for ncols columns, K weights, the presynaptic list n_pre, nrows = t_hi - t_lo bins and
     max_ev = the largest number of post-synaptic events of a listed column inside the range.  forced_nloop: the decoded
     forced loop; opt_dbg: the raw debug option instead (decoded as the host does, its bit 0x1000 switches same_pre off).
 
-    Written from theano_pyglm_amd/csrc/pglm_capi.hip, pgl_gibbs_ll_cols (lines 2274-2400): the regime-split branch at 2282-2330
-    (gp.CP, gp.nsplit, ygroups, nsub, same_pre with the 0x1000 switch at 2294, gp.nloop at 2314 and its forced value at
-    2316-2319, nblk, sblk at 2321, then the four launches), the all-f64 branch at 2363-2380 (stage_cols' gp.CP = min(ncols,
-    256 / K) at 2261, gtb, rows, nblk) and TS at pglm_gibbs.hip.h:133 -- keep the two in step.
-    One simplification: `slots` stands for gibbs_rate_wg_per_cu(lds) * numCU, which the host takes from an occupancy query
-    at the launch's LDS size (a function of CP, same_pre and R); here it is the constant 4 * 256 of an MI355X at <= 40 KB.
-    It only enters the unforced nloop = nsub * ygroups / (6 * slots), which is below 1 for every launch under 6 144
-    sub-block units (the table's largest has 24), so the statement is exact for every case whatever the occupancy; the sweep
-    compares every field with what the device reports (pgl_gibbs_last_geometry)."""
+    An independent statement of the rule of theano_pyglm_amd/csrc/pglm_gibbs_plan.h: pgl_gibbs_dbg (the debug word),
+    pgl_gibbs_path, pgl_gibbs_plan_shape (CP, nsplit, ygroups, nsub, same_pre, hs_region, fs_stride, sblk, the LDS bytes; all of
+    the all-f64 path: CP = min(ncols, 256 / K), gtb, rows, nblk), pgl_gibbs_plan_loop (nloop, nblk, grid from `slots`) and TS of
+    k_gibbs_ll_cols.  tests/test_gibbs_plan_host.py compiles the header with gcc and compares every field with this function on
+    the CPU; the sweep compares what the device reports (pgl_gibbs_last_geometry).  The LDS bytes are stated here from the
+    kernels' own carve-up of the block (pgl_gibbs_rate_body, k_gibbs_ll_cols in pglm_gibbs.hip.h), region by region.
+    `slots` stands for gibbs_rate_wg_per_cu(lds) * numCU, which the host takes from an occupancy query at the launch's LDS size;
+    the default is the 4 * 256 of an MI355X at <= 40 KB.  It only enters the unforced nloop = nsub * ygroups / (6 * slots),
+    which is below 1 for every launch under 6 144 sub-block units (the case table's largest has 24)."""
     same_pre_on = True
     if opt_dbg is not None:
         forced_nloop = dbg_nloop(opt_dbg)
@@ -275,8 +276,13 @@ def geometry(ncols, K, n_pre, nrows, max_ev, nlin, opt_gibbs=0, forced_nloop=0, 
         sblk = max(1, -(-max_ev // 256))
         kernels = ['k_gibbs_cols_setup'] + (['k_gibbs_pre_features'] if same_pre else []) + ['k_gibbs_rate_cols',
                                                                                                'k_gibbs_reduce_cols2']
+        # first region: HS [CP][R], or with the shared train FS [B][GRB + 2] and BT [CP][8] if that is larger
+        hs_region = max(CP * R, B * (GRB + 2) + CP * 8) if same_pre else CP * R
+        doubles = hs_region + CP * (GRB + 2) + CP * KMAX + 4 * GQ + SPT_N + CP        # X0, Wl, Qx, TB, WM
+        lds = 8 * doubles + 8 * CP * GECAP_R + 4 * CP * GNL + 2 * CP * GNL + 16      # evS (int2), WL (int), WN (short), slack
         return dict(path='regime', kernels=kernels, CP=CP, nsplit=nsplit, ygroups=yg, nsub=nsub, nloop=nloop, nblk=nblk, sblk=sblk,
-                    same_pre=same_pre, grid=nblk * yg + sblk * ncols)
+                    same_pre=same_pre, grid=nblk * yg + sblk * ncols, hs_region=hs_region,
+                    fs_stride=-(-nrows // 64) * 64 if same_pre else 0, lds=lds)
     CP = max(1, min(ncols, 256 // max(1, K)))
     yg = -(-ncols // CP)
     gtb = 32
@@ -286,8 +292,15 @@ def geometry(ncols, K, n_pre, nrows, max_ev, nlin, opt_gibbs=0, forced_nloop=0, 
     rows = max(gtb, min(rows, 384))
     rows = -(-rows // gtb) * gtb
     TS = max(1, 256 // (CP * K))
+    lds = 8 * (B * R + 3 * gtb * CP) + 8 * CP * GECAP + 4 * CP                       # phiS, X0 / IC / SS, evS (int2), ecnt (int)
     return dict(path='f64', kernels=['k_gibbs_ll_cols', 'k_gibbs_reduce_cols'], CP=CP, ygroups=yg, gtb=gtb, rows=rows, TS=TS,
-                nblk=-(-nrows // rows), same_pre=False)
+                nblk=-(-nrows // rows), same_pre=False, lds=lds)
+
+
+def update_geometry(ncols, nrows, R=179, B=5):
+    """What pgl_gibbs_update_cols launches (pgl_gibbs_plan_update): a thread is a column, blocks of 1024 bins, the basis in LDS"""
+    CP = min(ncols, 256)
+    return dict(CP=CP, ygroups=-(-ncols // CP), rows=1024, nblk=-(-nrows // 1024), lds=8 * B * R)
 
 
 def events(p, n, t_lo=None, t_hi=None):

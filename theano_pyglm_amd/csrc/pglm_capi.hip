@@ -2075,6 +2075,17 @@ int pgl_gibbs_prepare(pgl_handle h, int n_post, const double* theta_n, const dou
     return PGL_OK;
 }
 
+// events of neuron n inside the handle's time range [t_lo, t_hi): indices into spk, from the host copy of the event lists
+static void event_range(const pgl_context* h, int n, int& lo, int& hi)
+{
+    const int2* evb = h->h_ev.data();
+    const auto before = [](const int2& e, int64_t t) { return (int64_t)e.x < t; };
+    const int2* b = evb + h->h_ptr[n];
+    const int2* e = evb + h->h_ptr[n + 1];
+    lo = (int)(std::lower_bound(b, e, h->t_lo, before) - evb);
+    hi = (int)(std::lower_bound(b, e, h->t_hi, before) - evb);
+}
+
 static int run_ll_current(pgl_handle h, const double* d_base, const double* d_stim,
                           const double* d_col, int n_post, double bias, double aw_cur,
                           const double* w, int K, double* ll_out)
@@ -2082,10 +2093,8 @@ static int run_ll_current(pgl_handle h, const double* d_base, const double* d_st
     // blocks of the streaming part; the spike-bin part writes one more partial row
     // the sums run over the evaluated time range [t_lo, t_hi) (pgl_set_time_range)
     const int nblocks = (int)std::min<int64_t>(1024, (h->t_hi - h->t_lo + 255) / 256);
-    const int2* evb = h->h_ev.data();
-    const auto before = [](const int2& e, int64_t t) { return (int64_t)e.x < t; };
-    const int e_lo = (int)(std::lower_bound(evb + h->h_ptr[n_post], evb + h->h_ptr[n_post + 1], h->t_lo, before) - evb);
-    const int e_hi = (int)(std::lower_bound(evb + h->h_ptr[n_post], evb + h->h_ptr[n_post + 1], h->t_hi, before) - evb);
+    int e_lo, e_hi;
+    event_range(h, n_post, e_lo, e_hi);
     const int sblocks = std::max(1, std::min(256, (e_hi - e_lo + 255) / 256));
     ENSURE(h->part, (size_t)(nblocks + sblocks) * PGL_KMAX * 8);
     ENSURE(h->outK, PGL_KMAX * 8);
@@ -2203,10 +2212,7 @@ static int enqueue_gibbs_forward(pgl_handle h)
     return PGL_OK;
 }
 
-// stage the column arguments in one pinned block, one H2D copy: [cols | pre | aw | w]
-static int stage_cols(pgl_handle h, int ncols, const int* n_post, const int* n_pre, const double* aw,
-                      const double* w, int nw, GibbsColsParams& gp, size_t extra_out_bytes,
-                      bool with_events = false, int* max_events = nullptr)
+static int check_cols(const pgl_context* h, int ncols, const int* n_post, const int* n_pre, const double* w)
 {
     if (h->gx_xs == 0) return fail(PGL_ERR_STATE, "pgl_gibbs_prepare_all has not been called");
     if (h->gx_t_lo != h->t_lo || h->gx_t_hi != h->t_hi)
@@ -2215,11 +2221,26 @@ static int stage_cols(pgl_handle h, int ncols, const int* n_post, const int* n_p
     for (int c = 0; c < ncols; ++c)
         if (n_post[c] < 0 || n_post[c] >= h->N || n_pre[c] < 0 || n_pre[c] >= h->N)
             return fail(PGL_ERR_ARG, "neuron index out of range");
+    return PGL_OK;
+}
+
+// device copies of the column arguments (stage_cols)
+struct ColsArgs {
+    const int *cols, *pre, *elo, *ehi;   // elo / ehi: the events of every n_post inside the time range (null unless asked for)
+    const double *aw, *w;
+    int max_ev;                          // largest ehi - elo
+};
+
+// stage the column arguments in one pinned block, one H2D copy: [cols | pre | aw | w | elo | ehi]; the block holds at least
+// out_bytes, for the results of the call
+static int stage_cols(pgl_handle h, int ncols, const int* n_post, const int* n_pre, const double* aw, const double* w, int nw,
+                      bool with_events, size_t out_bytes, ColsArgs& a)
+{
     const size_t o_pre = (size_t)ncols * 4, o_aw = ((o_pre + (size_t)ncols * 4 + 7) / 8) * 8;
     const size_t o_w = o_aw + (size_t)ncols * 8, o_elo = o_w + (size_t)ncols * nw * 8;
     const size_t o_ehi = o_elo + (size_t)ncols * 4;
     const size_t bytes = with_events ? ((o_ehi + (size_t)ncols * 4 + 7) / 8) * 8 : o_elo;
-    const size_t need = std::max(bytes, extra_out_bytes);
+    const size_t need = std::max(bytes, out_bytes);
     if (need > h->pin_args_cap) {
         if (h->pin_args) (void)hipHostFree(h->pin_args);
         h->pin_args = nullptr;
@@ -2232,45 +2253,113 @@ static int stage_cols(pgl_handle h, int ncols, const int* n_post, const int* n_p
     std::memcpy(h->pin_args + o_pre, n_pre, (size_t)ncols * 4);
     for (int c = 0; c < ncols; ++c) reinterpret_cast<double*>(h->pin_args + o_aw)[c] = aw ? aw[c] : 0.0;
     std::memcpy(h->pin_args + o_w, w, (size_t)ncols * nw * 8);
+    a.max_ev = 0;
     if (with_events) {
-        // events of every listed post-synaptic neuron inside the evaluated time range
-        const int2* evb = h->h_ev.data();
-        const auto before = [](const int2& e, int64_t t) { return (int64_t)e.x < t; };
-        int mx = 0;
+        int* lo = reinterpret_cast<int*>(h->pin_args + o_elo);
+        int* hi = reinterpret_cast<int*>(h->pin_args + o_ehi);
         for (int c = 0; c < ncols; ++c) {
-            const int2* b = evb + h->h_ptr[n_post[c]];
-            const int2* e = evb + h->h_ptr[n_post[c] + 1];
-            const int lo = (int)(std::lower_bound(b, e, h->t_lo, before) - evb);
-            const int hi = (int)(std::lower_bound(b, e, h->t_hi, before) - evb);
-            reinterpret_cast<int*>(h->pin_args + o_elo)[c] = lo;
-            reinterpret_cast<int*>(h->pin_args + o_ehi)[c] = hi;
-            mx = std::max(mx, hi - lo);
+            event_range(h, n_post[c], lo[c], hi[c]);
+            a.max_ev = std::max(a.max_ev, hi[c] - lo[c]);
         }
-        if (max_events) *max_events = mx;
     }
     HIPCHK(hipMemcpyAsync(h->gargs.p, h->pin_args, bytes, hipMemcpyHostToDevice, h->stream));
     const unsigned char* d = (const unsigned char*)h->gargs.p;
+    a.cols = (const int*)d; a.pre = (const int*)(d + o_pre); a.aw = (const double*)(d + o_aw); a.w = (const double*)(d + o_w);
+    a.elo = with_events ? (const int*)(d + o_elo) : nullptr;
+    a.ehi = with_events ? (const int*)(d + o_ehi) : nullptr;
+    return PGL_OK;
+}
+
+// what the k_gibbs_* kernels read of the handle, the staged arguments and the plan; the launchers add their own buffers
+static GibbsColsParams cols_params(const pgl_context* h, const ColsArgs& a, int ncols, int nw, const PglGibbsPlan& pl)
+{
+    GibbsColsParams gp{};
     gp.GX = (const double*)h->GX.p; gp.xs = h->gx_xs; gp.S = (const uint8_t*)h->S.p;
     gp.N = h->N; gp.B = h->B; gp.R = h->Rk; gp.P = 1 + h->Dstim + h->Kimp; gp.woff = 1 + h->Dstim;
     gp.spk = (const int2*)h->spk.p; gp.wlo = (const int*)h->wlo.p; gp.whi = (const int*)h->whi.p;
     gp.phi = (const double*)h->phi.p; gp.theta = (const double*)h->gtheta.p;
-    gp.cols = (const int*)d; gp.pre = (const int*)(d + o_pre); gp.aw = (const double*)(d + o_aw);
-    gp.w = (const double*)(d + o_w);
+    gp.cols = a.cols; gp.pre = a.pre; gp.aw = a.aw; gp.w = a.w; gp.elo = a.elo; gp.ehi = a.ehi;
     gp.ncols = ncols; gp.K = nw; gp.nlin = h->nlin; gp.dt = h->dt;
     gp.t_lo = h->t_lo; gp.t_hi = h->t_hi;
-    gp.CP = std::max(1, std::min(ncols, 256 / std::max(1, nw)));   // columns per workgroup (ll) / per sweep (update)
-    gp.part = nullptr;
-    gp.nsplit = 1;
-    gp.elo = with_events ? (const int*)(d + o_elo) : nullptr;
-    gp.ehi = with_events ? (const int*)(d + o_ehi) : nullptr;
-    gp.partS = nullptr;
-    gp.nloop = 1;
-    gp.hs = nullptr;
-    gp.fs = nullptr; gp.fs_stride = 0; gp.hs_region = 0;
-    gp.dbg = 0;
+    gp.CP = pl.CP; gp.rows = pl.rows; gp.gtb = pl.gtb;
+    gp.nsplit = pl.nsplit; gp.nloop = pl.nloop; gp.hs_region = pl.hs_region; gp.fs_stride = pl.fs_stride;
+    gp.nblkR = pl.nblk; gp.nygR = pl.ygroups; gp.nblkS = pl.sblk;
+    gp.dbg = pl.dbg;
+    return gp;
+}
+
+static void record_geometry(pgl_context* h, const PglGibbsPlan& pl)
+{
+    if (h->opt_record) pgl_gibbs_plan_report(&pl, h->gibbs_geo);
+}
+
+// regime-split path: the impulse responses of the pairs, the shared presynaptic features where every column has the same
+// n_pre, then rate and spike workgroups in ONE launch, the spike workgroups (short chains of dependent loads: 87 us as a launch
+// of their own) dispatched last: they fill the slots the rate workgroups free at the end.  (On a side stream beside the rate
+// kernel -- two event hops -- they cost more than in line: 1.365 against 1.295 ms.)
+static int launch_ll_cols_regime(pgl_handle h, const ColsArgs& a, int ncols, int K, int n_pre0, PglGibbsPlan& pl, double* ll_out)
+{
+    hipError_t e = ensure_dyn_lds(k_gibbs_rate_cols, pl.lds);
+    if (e != hipSuccess) return fail(PGL_ERR_HIP, hipGetErrorString(e));
+    pgl_gibbs_plan_loop(&pl, ncols, h->opt_dbg, (long long)gibbs_rate_wg_per_cu(pl.lds) * h->numCU);
+    ENSURE(h->gpart, (size_t)(pl.nblk + pl.sblk) * ncols * PGL_KMAX * 8);
+    ENSURE(h->ghs, (size_t)ncols * h->Rk * 8);
+    if (pl.same_pre) ENSURE(h->gfs, (size_t)h->B * pl.fs_stride * 8);
+    GibbsColsParams gp = cols_params(h, a, ncols, K, pl);
+    gp.part = (double*)h->gpart.p;
+    gp.partS = gp.part + (size_t)pl.nblk * ncols * PGL_KMAX;
+    gp.hs = (double*)h->ghs.p;
+    if (pl.same_pre) gp.fs = (const double*)h->gfs.p;
+    record_geometry(h, pl);
+    const long long nrows = h->t_hi - h->t_lo;
+    record_gibbs(h, "k_gibbs_cols_setup");
+    hipLaunchKernelGGL(k_gibbs_cols_setup, dim3((ncols * h->Rk + 255) / 256), dim3(256), 0, h->stream, gp);
+    HIPCHK(hipGetLastError());
+    if (pl.same_pre) {
+        record_gibbs(h, "k_gibbs_pre_features");
+        hipLaunchKernelGGL(k_gibbs_pre_features, dim3((unsigned)((nrows + 255) / 256)), dim3(256), (size_t)h->B * h->Rk * 8,
+                           h->stream, gp, n_pre0, (double*)h->gfs.p);
+        HIPCHK(hipGetLastError());
+    }
+    record_gibbs(h, "k_gibbs_rate_cols");
+    hipLaunchKernelGGL(k_gibbs_rate_cols, dim3(pl.grid), dim3(256), pl.lds, h->stream, gp);
+    HIPCHK(hipGetLastError());
+    record_gibbs(h, "k_gibbs_reduce_cols2");
+    hipLaunchKernelGGL(k_gibbs_reduce_cols2, dim3(ncols, K), dim3(64), 0, h->stream, (const double*)gp.part, pl.nblk,
+                       (const double*)gp.partS, pl.sblk, ncols, K, h->dt, (double*)h->pin_args);
+    HIPCHK(hipGetLastError());
+    // the results land in the pinned host block directly (its argument bytes were consumed by the upload
+    // that precedes the kernels on the stream): no device-to-host copy call
+    HIPCHK(hipStreamSynchronize(h->stream));
+    std::memcpy(ll_out, h->pin_args, (size_t)ncols * K * 8);
     return PGL_OK;
 }
 
+// all-f64 path: one kernel over (time blocks, column groups), a reduction into gout, one copy into the pinned block
+static int launch_ll_cols_f64(pgl_handle h, const ColsArgs& a, int ncols, int K, const PglGibbsPlan& pl, double* ll_out)
+{
+    ENSURE(h->gpart, (size_t)pl.nblk * ncols * PGL_KMAX * 8);
+    ENSURE(h->gout, (size_t)ncols * K * 8);
+    GibbsColsParams gp = cols_params(h, a, ncols, K, pl);
+    gp.part = (double*)h->gpart.p;
+    hipError_t e = ensure_dyn_lds(k_gibbs_ll_cols, pl.lds);
+    if (e != hipSuccess) return fail(PGL_ERR_HIP, hipGetErrorString(e));
+    record_geometry(h, pl);
+    record_gibbs(h, "k_gibbs_ll_cols");
+    hipLaunchKernelGGL(k_gibbs_ll_cols, dim3(pl.nblk, pl.ygroups), dim3(256), pl.lds, h->stream, gp);
+    HIPCHK(hipGetLastError());
+    record_gibbs(h, "k_gibbs_reduce_cols");
+    hipLaunchKernelGGL(k_gibbs_reduce_cols, dim3(ncols), dim3(64), 0, h->stream, (const double*)h->gpart.p,
+                       pl.nblk, ncols, K, (double*)h->gout.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h->pin_args, h->gout.p, (size_t)ncols * K * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    std::memcpy(ll_out, h->pin_args, (size_t)ncols * K * 8);
+    return PGL_OK;
+}
+
+// check, stage, plan (pglm_gibbs_plan.h), launch.  Staging comes before the plan because it finds the event ranges of the
+// listed columns, whose largest the plan needs; which path runs (and so whether the ranges are wanted) is known before both.
 int pgl_gibbs_ll_cols(pgl_handle h, int ncols, const int* n_post, const int* n_pre,
                       const double* aw_cur, const double* w, int K, double* ll_out)
 {
@@ -2278,126 +2367,19 @@ int pgl_gibbs_ll_cols(pgl_handle h, int ncols, const int* n_post, const int* n_p
     if (rc) return rc;
     if (K <= 0 || K > PGL_KMAX || !ll_out) return fail(PGL_ERR_ARG, "K must be in 1..16");
     HIPCHK(hipSetDevice(h->device));
-    GibbsColsParams gp;
-    if (h->nlin == PGL_NLIN_EXPLINEAR && h->opt_gibbs != 1 && h->Rk + PGL_GRB + 32 < 65535) {   // (16-bit event counts per window)
-        // regime-split path: rate terms by k_gibbs_rate_cols (single precision for the log1p term where
-        // |x| >= 12, compacted f64 elsewhere), spike terms from the event lists
-        int max_ev = 0;
-        rc = stage_cols(h, ncols, n_post, n_pre, aw_cur, w, K, gp, (size_t)ncols * K * 8, true, &max_ev);
-        if (rc) return rc;
-        gp.CP = std::min(ncols, 8);
-        gp.nsplit = (gp.CP >= 3) ? 1 : (gp.CP == 2) ? 2 : ((PGL_GRB / 64) % 4 == 0 ? 4 : 3);   // (PGL_GRB / 64) % nsplit == 0
-        const int ygroups = (ncols + gp.CP - 1) / gp.CP;
-        const long long nrows = h->t_hi - h->t_lo;
-        const long long nsub = (nrows + PGL_GRB - 1) / PGL_GRB;
-        // every column with the same presynaptic neuron (a sweep step): its filtered spike train once per launch
-        bool same_pre = ncols >= 2 && !(h->opt_dbg & 0x1000);
-        for (int c = 1; c < ncols && same_pre; ++c) same_pre = n_pre[c] == n_pre[0];
-        gp.hs_region = gp.CP * h->Rk;
-        if (same_pre) gp.hs_region = std::max(gp.hs_region, h->B * (PGL_GRB + 2) + gp.CP * 8);
-        const size_t lds = ((size_t)gp.hs_region + (size_t)gp.CP * (PGL_GRB + 2) + (size_t)gp.CP * PGL_KMAX +
-                            (size_t)4 * PGL_GQ + (size_t)PGL_SPT_N + (size_t)gp.CP) * 8 +     // (band queue, softplus-tail table, max |w|)
-                           (size_t)gp.CP * PGL_GECAP_R * 8 + (size_t)gp.CP * PGL_GNL * 6 + 16;
-        auto rate_kernel = k_gibbs_rate_cols;
-        {
-            hipError_t e = ensure_dyn_lds(rate_kernel, lds);
-            if (e != hipSuccess) return fail(PGL_ERR_HIP, hipGetErrorString(e));
-        }
-        // sub-blocks per workgroup: short loops.  The columns differ in how many of their elements fall into the f64
-        // band, so workgroups differ in run time and the dispatcher's dynamic placement has to even that out: at C4
-        // (37 504 sub-block units on 1 024 slots -- occupancy query: four workgroups per CU at <= 40 KB of LDS and 128
-        // VGPRs) loops of 3..10 sub-blocks run within 1 % of each other (1.14 ms per launch), 13 = three well-filled
-        // rounds 1.19, 16 1.25, 37 = ONE round filled to 99 % 1.23 ms (tools/r4/gibbs_nloop_scan.py).  So: at least six
-        // rounds of workgroups, loops of at most eight sub-blocks (the per-workgroup setup is amortised from ~4).
-        {
-            const long long slots = (long long)gibbs_rate_wg_per_cu(lds) * h->numCU;
-            gp.nloop = (int)std::max(1LL, std::min(8LL, nsub * ygroups / (6 * slots)));
-        }
-        // tests: force the sub-block loop -- bits 16..20 of the debug option (1 .. PGL_GNL), else its older 4-bit field in
-        // bits 8..11 (1 .. 15; bit 12 is the same_pre switch above, so 16 << 8 forces nothing)
-        if (const int forced = ((h->opt_dbg >> 16) & 0x1f) ? (h->opt_dbg >> 16) & 0x1f : (h->opt_dbg >> 8) & 0xf)
-            gp.nloop = std::min(PGL_GNL, forced);
-        const int nblk = (int)((nsub + gp.nloop - 1) / gp.nloop);
-        const int sblk = std::max(1, (max_ev + 255) / 256);
-        ENSURE(h->gpart, (size_t)(nblk + sblk) * ncols * PGL_KMAX * 8);
-        ENSURE(h->gout, (size_t)ncols * K * 8);
-        ENSURE(h->ghs, (size_t)ncols * h->Rk * 8);
-        gp.part = (double*)h->gpart.p;
-        gp.partS = gp.part + (size_t)nblk * ncols * PGL_KMAX;
-        gp.hs = (double*)h->ghs.p;
-        gp.dbg = h->opt_dbg & 0xff;
-        if (same_pre) {
-            gp.fs_stride = (nrows + 63) / 64 * 64;
-            ENSURE(h->gfs, (size_t)h->B * gp.fs_stride * 8);
-            gp.fs = (const double*)h->gfs.p;
-        }
-        if (h->opt_record) {
-            const int geo[10] = {0, gp.CP, gp.nsplit, ygroups, gp.nloop, nblk, sblk, same_pre ? 1 : 0, 0, 0};
-            std::copy(geo, geo + 10, h->gibbs_geo);
-        }
-        record_gibbs(h, "k_gibbs_cols_setup");
-        hipLaunchKernelGGL(k_gibbs_cols_setup, dim3((ncols * h->Rk + 255) / 256), dim3(256), 0, h->stream, gp);
-        HIPCHK(hipGetLastError());
-        if (same_pre) {
-            record_gibbs(h, "k_gibbs_pre_features");
-            hipLaunchKernelGGL(k_gibbs_pre_features, dim3((unsigned)((nrows + 255) / 256)), dim3(256), (size_t)h->B * h->Rk * 8,
-                               h->stream, gp, n_pre[0], (double*)h->gfs.p);
-            HIPCHK(hipGetLastError());
-        }
-        // rate and spike workgroups in ONE launch, the spike workgroups (short chains of dependent loads: 87 us as a launch
-        // of their own) dispatched last: they fill the slots the rate workgroups free at the end.  (On a side stream beside
-        // the rate kernel -- two event hops -- they cost more than in line: 1.365 against 1.295 ms, round 3.)
-        gp.nblkR = nblk; gp.nygR = ygroups; gp.nblkS = sblk;
-        record_gibbs(h, "k_gibbs_rate_cols");
-        hipLaunchKernelGGL(rate_kernel, dim3((unsigned)(nblk * ygroups + sblk * ncols)), dim3(256), lds, h->stream, gp);
-        HIPCHK(hipGetLastError());
-        record_gibbs(h, "k_gibbs_reduce_cols2");
-        hipLaunchKernelGGL(k_gibbs_reduce_cols2, dim3(ncols, K), dim3(64), 0, h->stream, (const double*)gp.part, nblk,
-                           (const double*)gp.partS, sblk, ncols, K, h->dt, (double*)h->pin_args);
-        HIPCHK(hipGetLastError());
-        // the results land in the pinned host block directly (its argument bytes were consumed by the upload
-        // that precedes the kernels on the stream): no device-to-host copy call
-        HIPCHK(hipStreamSynchronize(h->stream));
-        std::memcpy(ll_out, h->pin_args, (size_t)ncols * K * 8);
-        return PGL_OK;
-    }
-    rc = stage_cols(h, ncols, n_post, n_pre, aw_cur, w, K, gp, (size_t)ncols * K * 8);
+    rc = check_cols(h, ncols, n_post, n_pre, w);
     if (rc) return rc;
-    // enough blocks for a few per CU, at most 384 bins each (the block's presynaptic events -- window of
-    // rows + R bins, ~11 at 20 Hz -- are staged in LDS, PGL_GECAP per column), whole sub-blocks
-    const int ygroups = (ncols + gp.CP - 1) / gp.CP;
-    const long long nrows = h->t_hi - h->t_lo;
-    int gtb = 32;
-    while (gtb * gp.CP < 256) gtb += 32;                 // narrow launches: longer sub-blocks keep 256 threads busy
-    gp.gtb = gtb;
-    long long rows = (nrows * ygroups + 4 * h->numCU - 1) / (4LL * h->numCU);
-    rows = std::max<long long>(gtb, std::min<long long>(rows, 384));
-    rows = (rows + gtb - 1) / gtb * gtb;
-    gp.rows = (int)rows;
-    const int nblk = (int)((nrows + rows - 1) / rows);
-    ENSURE(h->gpart, (size_t)nblk * ncols * PGL_KMAX * 8);
-    ENSURE(h->gout, (size_t)ncols * K * 8);
-    gp.part = (double*)h->gpart.p;
-    const size_t lds = ((size_t)h->B * h->Rk + (size_t)3 * gtb * gp.CP) * 8 + (size_t)gp.CP * PGL_GECAP * 8 +
-                       (size_t)gp.CP * 4;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_gibbs_ll_cols),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail(PGL_ERR_HIP, hipGetErrorString(e));
-    if (h->opt_record) {
-        const int geo[10] = {1, gp.CP, 1, ygroups, 1, nblk, 0, 0, gtb, gp.rows};
-        std::copy(geo, geo + 10, h->gibbs_geo);
-    }
-    record_gibbs(h, "k_gibbs_ll_cols");
-    hipLaunchKernelGGL(k_gibbs_ll_cols, dim3(nblk, ygroups), dim3(256), lds, h->stream, gp);
-    HIPCHK(hipGetLastError());
-    record_gibbs(h, "k_gibbs_reduce_cols");
-    hipLaunchKernelGGL(k_gibbs_reduce_cols, dim3(ncols), dim3(64), 0, h->stream, (const double*)h->gpart.p,
-                       nblk, ncols, K, (double*)h->gout.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h->pin_args, h->gout.p, (size_t)ncols * K * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    std::memcpy(ll_out, h->pin_args, (size_t)ncols * K * 8);
-    return PGL_OK;
+    const int explinear = h->nlin == PGL_NLIN_EXPLINEAR;
+    const bool regime = pgl_gibbs_path(explinear, h->opt_gibbs, h->Rk) == PGL_GIBBS_REGIME;
+    ColsArgs a;
+    rc = stage_cols(h, ncols, n_post, n_pre, aw_cur, w, K, regime, (size_t)ncols * K * 8, a);
+    if (rc) return rc;
+    // every column with the same presynaptic neuron (a sweep step): its filtered spike train once per launch
+    const bool pre_equal = std::all_of(n_pre, n_pre + ncols, [&](int j) { return j == n_pre[0]; });
+    PglGibbsPlan pl;
+    pgl_gibbs_plan_shape(&pl, ncols, K, pre_equal, h->t_hi - h->t_lo, a.max_ev, explinear, h->opt_gibbs, h->opt_dbg, h->B, h->Rk,
+                         h->numCU);
+    return regime ? launch_ll_cols_regime(h, a, ncols, K, n_pre[0], pl, ll_out) : launch_ll_cols_f64(h, a, ncols, K, pl, ll_out);
 }
 
 int pgl_gibbs_last_geometry(pgl_handle h, int* out, int n)
@@ -2417,16 +2399,16 @@ int pgl_gibbs_update_cols(pgl_handle h, int ncols, const int* n_post, const int*
     for (int a = 0; a < ncols; ++a)                       // two deltas for one post neuron would race
         for (int b = a + 1; b < ncols; ++b)
             if (n_post && n_post[a] == n_post[b]) return fail(PGL_ERR_ARG, "duplicate post-synaptic column");
-    GibbsColsParams gp;
-    rc = stage_cols(h, ncols, n_post, n_pre, nullptr, delta, 1, gp, 0);
+    rc = check_cols(h, ncols, n_post, n_pre, delta);
     if (rc) return rc;
-    const int ygroups = (ncols + gp.CP - 1) / gp.CP;
-    const long long nrows = h->t_hi - h->t_lo;
-    gp.rows = 1024;
-    const int nblk = (int)((nrows + gp.rows - 1) / gp.rows);
-    const size_t lds = (size_t)h->B * h->Rk * 8;
+    ColsArgs a;
+    rc = stage_cols(h, ncols, n_post, n_pre, nullptr, delta, 1, false, 0, a);
+    if (rc) return rc;
+    PglGibbsPlan pl;
+    pgl_gibbs_plan_update(&pl, ncols, h->t_hi - h->t_lo, h->B, h->Rk);
+    const GibbsColsParams gp = cols_params(h, a, ncols, 1, pl);
     record_gibbs(h, "k_gibbs_update_cols");
-    hipLaunchKernelGGL(k_gibbs_update_cols, dim3(nblk, ygroups), dim3(256), lds, h->stream, gp, (double*)h->GX.p);
+    hipLaunchKernelGGL(k_gibbs_update_cols, dim3(pl.nblk, pl.ygroups), dim3(256), pl.lds, h->stream, gp, (double*)h->GX.p);
     HIPCHK(hipGetLastError());
     // the column arguments were staged in the handle's pinned block: the next call refills it, so the
     // asynchronous upload must have happened before this one returns
@@ -2824,17 +2806,6 @@ int pgl_gemm_dev(pgl_handle h, int kernel, const double* d_A, int64_t sam, int64
 }
 
 // ---- time rescaling: integrated rate between consecutive events (pglm_rescale.hip.h) ---------------------------------
-// events of neuron n inside the handle's time range, from the host copy of the event lists
-static void rescale_event_range(const pgl_context* h, int n, int& lo, int& hi)
-{
-    const int2* evb = h->h_ev.data();
-    const auto before = [](const int2& e, int64_t t) { return (int64_t)e.x < t; };
-    const int2* b = evb + h->h_ptr[n];
-    const int2* e = evb + h->h_ptr[n + 1];
-    lo = (int)(std::lower_bound(b, e, h->t_lo, before) - evb);
-    hi = (int)(std::lower_bound(b, e, h->t_hi, before) - evb);
-}
-
 int pgl_rescale_count(pgl_handle h, int64_t* off_out)
 {
     if (!h) return fail(PGL_ERR_ARG, "null handle");
@@ -2843,7 +2814,7 @@ int pgl_rescale_count(pgl_handle h, int64_t* off_out)
     off_out[0] = 0;
     for (int n = 0; n < h->N; ++n) {
         int lo, hi;
-        rescale_event_range(h, n, lo, hi);
+        event_range(h, n, lo, hi);
         off_out[n + 1] = off_out[n] + std::max(hi - lo - 1, 0);
     }
     return PGL_OK;

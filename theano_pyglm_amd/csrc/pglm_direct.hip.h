@@ -107,7 +107,7 @@ __global__ void k_axpy(double* __restrict__ y, const double* __restrict__ x, dou
 // The first sum streams all nT bins (k_ll_current: one exp per element and weight, log1p by
 // its series in the |x| > 9.25 tail); the second only visits the post-synaptic neuron's own
 // spike events (k_ll_current_spikes, ~2 % of the bins), so no log is evaluated for silent bins.
-#define PGL_KMAX 16
+#include "pglm_gibbs_plan.h"   // PGL_KMAX, with the rest of what the Gibbs launch geometry depends on
 __device__ __forceinline__ double pgl_lambda_only(const double x, const int nlin,
                                                   const double* __restrict__ C)
 {

@@ -1,6 +1,7 @@
 // batched collapsed-Gibbs columns: k_gibbs_*
 // Part of pglm_kernels.hip.h (included from there, in order; one translation unit).
 #pragma once
+#include "pglm_gibbs_plan.h"   // PGL_GRB, PGL_GQ, PGL_GNL, PGL_GECAP, PGL_GECAP_R, PGL_SPT_N, PGL_KMAX: what the launch geometry depends on
 // ---------------------------------------------------------------------------
 // Collapsed-Gibbs inner ll for MANY post-synaptic columns per launch (gibbs.py:977-1066).  The
 // columns (A[:,n], W[:,n]) are conditionally independent given the rest -- the reference maps them
@@ -73,8 +74,6 @@ struct GibbsColsParams {
     int dbg;                             // dev: 1 no event loop, 2 no phase B, 4 no event staging, 8 no GX loads, 16 no band passes,
                                          // 32 no exp, 64 no merge tree (results invalid when != 0)
 };
-
-#define PGL_GECAP 24          // staged presynaptic events per column and block (k_gibbs_ll_cols)
 
 // Thread = one (column, candidate weight) pair: one accumulator per thread, a short loop body (the code
 // of the first version -- 16 x 4 inlined softplus chains per pass -- did not fit the instruction cache
@@ -214,7 +213,7 @@ __global__ __launch_bounds__(256) void k_gibbs_ll_cols(const GibbsColsParams p)
 //     error (<= 1e-6 relative to itself: the f32 rounding of |x| <= 700 in the exponent) is <= 6e-12 of a bin
 //     whose rate is >= 12, or of a rate term < 6.2e-6 next to the spike terms.  ~10 instructions per
 //     evaluation instead of ~55 of the f64 exp + log1p.
-//   * |x| < 12 ("band", 13 % of the evaluations at C4, uniformly distributed in |x|: tools/gibbs_x_hist.py),
+//   * |x| < 12 ("band", 13 % of the evaluations at C4, uniformly distributed in |x| by a histogram of the currents),
 //     |x| >= 700 (lam underflows: reference NaN semantics), inf and NaN: the f64 path, on COMPACTED lanes -- band
 //     elements are queued per wave in LDS with their weight index and evaluated 64 at a time.
 //   * S*log(lam) only exists at the spike bins of n_post (2 % of the bins): k_gibbs_spike_cols walks the
@@ -225,23 +224,16 @@ __global__ __launch_bounds__(256) void k_gibbs_ll_cols(const GibbsColsParams p)
 // scans (fixed order, no atomics).  ~41 KB of LDS per workgroup: three workgroups per CU.
 //   part[blk][c][k] = sum_t lam_k(t)   (k_gibbs_reduce_cols2 applies -dt and adds the spike terms)
 // ---------------------------------------------------------------------------
-#ifndef PGL_GRB
-#define PGL_GRB 256
-#endif
-//                               bins per sub-block: six segments of 64 per wave and weight -- at C4 13 % of the evaluations are band
-                              // elements, ~50 per (item, weight): one f64 pass at ~80 % lane utilisation (four segments: 33 = 52 %)
+// PGL_GRB bins per sub-block: six segments of 64 per wave and weight -- at C4 13 % of the evaluations are band
+// elements, ~50 per (item, weight): one f64 pass at ~80 % lane utilisation (four segments: 33 = 52 %)
 #ifndef PGL_GFAST
 #define PGL_GFAST 12.0f             // (the test reads the single-precision |x|) from |x| >= 12 the log1p(exp(-|x|)) < 6.2e-6 term of the softplus
                                    // comes from the single-precision hardware exp (<= 6e-12 absolute per bin).  Measured round 3:
                                    // switching at |x| >= 8 (three series terms) moves 35 % of the compacted f64
-                                   // elements to the fast path -- |x| is uniform below 12 at C4, tools/gibbs_x_hist.py -- but buys
+                                   // elements to the fast path -- |x| is uniform below 12 at C4 -- but buys
                                    // only 3 % (1.41 vs 1.45 ms) for a 30x larger error (1.7e-10 per bin: the 1e-11 parity test
                                    // against the all-f64 kernel fails), so the threshold stays at 12
 #endif
-#ifndef PGL_GQ
-#define PGL_GQ PGL_GRB
-#endif
-//                               band-queue entries per wave (the band elements of one weight: <= PGL_GRB)
 // Occupancy of k_gibbs_rate_cols (tools/ubench/occ_gibbs_ubench.hip, hipOccupancyMaxActiveBlocksPerMultiprocessor): four
 // workgroups per CU up to 40 KB of LDS and 128 VGPRs, three up to 53 KB -- and three are 15-20 % slower.  The kernel sits
 // at 40 944 of 40 960 bytes at the C4 shape on purpose (which is why the staged-event cap is 20 and the event counts of
@@ -449,14 +441,6 @@ __global__ __launch_bounds__(256) void k_gibbs_cols_setup(const GibbsColsParams 
     for (int b = 0; b < p.B; ++b) hh = fma(p.phi[b * p.R + d], bt[b], hh);
     p.hs[i] = hh;
 }
-
-#define PGL_GNL 16            // at most this many sub-blocks per workgroup
-#define PGL_GECAP_R 20         // staged presynaptic events per column and sub-block (~9 at 20 Hz; more: read from HBM)
-#ifdef PGL_SPT_GLOBAL
-#define PGL_SPT_N 2
-#else
-#define PGL_SPT_N 196         // doubles of the softplus-tail table in LDS (97 x 2, padded)
-#endif
 
 // Pairwise merges of lane-partial vectors (the reduction tree of k_gibbs_rate_cols).  merge32(a, b): lanes 0..31
 // = a[l] + a[l + 32], lanes 32..63 = b[l - 32] + b[l] (v_permlane32_swap: the upper half of the first register
