@@ -98,7 +98,7 @@ typedef struct pgl_context* pgl_handle;
 
 /* What pgl_version() returns: it changes with every change of a signature or a struct below, and a binding refuses a
  * library that reports another number (theano_pyglm_amd/_lib.py: ABI_VERSION). */
-#define PGL_ABI_VERSION 113
+#define PGL_ABI_VERSION 114
 
 const char* pgl_last_error(void);
 int pgl_version(void);
@@ -799,7 +799,7 @@ int pgl_gibbs_currents(pgl_handle h, int n_post, double* x_out);
  *     lam_t = nlin(theta_n[0] + x[t,n]), x the bias-free total current of pgl_gibbs_prepare_all, all f64 (no
  *             single-precision shortcut: the rate functions of the PGL_OPT_EPI_F64 = 1 epilogue);
  *     event bins t_1 < ... < t_K: the bins of the range with S[t,n] >= 1 -- a bin with several spikes is ONE event
- *             (the discrete-time correction of Haslinger, Pipa & Brown 2010 is not applied);
+ *             (pgl_rescale applies no discrete-time correction; pgl_rescale_corr below does);
  *     tau_k = dt * sum_{s = t_{k-1}+1 .. t_k} lam_s, k = 2 .. K: the interval before the first event of the range is
  *             left-censored and dropped, so a neuron with K events gives max(K - 1, 0) intervals;
  *     Lambda_n = dt * sum_{t in range} lam_t, the expected count.
@@ -817,6 +817,63 @@ int pgl_rescale_count(pgl_handle h, int64_t* off_out);
 int pgl_rescale_dev(pgl_handle h, const double* d_theta, const double* d_Weff, double* d_tau, const int64_t* d_off,
                     double* d_stats);
 int pgl_rescale(pgl_handle h, const double* theta, const double* Weff, double* tau_out, double* stats_out);
+
+/* The same intervals with the discrete-time correction of Haslinger, Pipa & Brown (2010).  The model is Poisson per bin,
+ * P(event in bin s) = 1 - exp(-q_s) with q_s = dt lam_s, so Haslinger's q = -log(1 - p) is the term the sum above holds
+ * already, and only the event bin's own term changes -- the event lies somewhere inside its bin, not at its end:
+ *     open_k = dt * sum_{s = t_{k-1}+1 .. t_k - 1} lam_s      the bins strictly between the two events (none: 0)
+ *     q_k    = dt * lam_{t_k}
+ *     e_k    = -log1p(u_k * expm1(-q_k))                       in (0, q_k]
+ *     tau'_k = open_k + e_k
+ * with the stateless uniform (G and mix as in pgl_simulate_streams below, the draw where that has the replicate)
+ *     z = mix(mix(mix(mix(seed + G) + G * (draw + 1)) + G * (n + 1)) + G * (j + 1))
+ *     u = ((double)(z >> 11) + 0.5) * 2^-53                                                  in (0, 1]
+ * n: NEURON index, j: the index of the event t_k in the neuron's whole event list of the data sequence -- not in the time
+ * range, so the interval between two given events has the same u whatever pgl_set_time_range says.  The corrected
+ * intervals, and every statistic of them, are therefore a RANDOM function of seed (and draw): average over seeds, or
+ * report the seed.  At lam dt << 1, e_k -> u q_k and the correction vanishes with the bias it removes; at lam dt = 0.2 ..
+ * 0.5 the uncorrected KS distance of a true model is about 0.2 and fails every test (README.md, "Goodness of fit").
+ * open_k is summed in the pieces tau_k is made of, on chunks of 256 bins that lie on the ABSOLUTE bin grid (multiples of
+ * 256 from bin 0 of the data sequence; the first and last chunk of a range may be partial): the sum behind the earlier
+ * event to the end of its chunk, the chunks strictly between the two events total by total in chunk order, the sum from
+ * the start of the later event's chunk up to its bin (one sum between the two events where they share a chunk).  Every
+ * in-chunk sum starts anew behind an event, so open_k is never a difference -- not tau_k - q_k, not two running sums --
+ * and consecutive event bins give open_k = 0 exactly.  The rate of these pieces and of q_k is pgl_rescale's arithmetic with
+ * the log1p series of the explinear rate chosen from the element's own current: pgl_rescale chooses it by a vote of the 64
+ * lanes of a wavefront (other neurons, other chunks -- and which chunks share a wavefront changes with t_lo), which can move
+ * the last bit of a rate.  Two calls give the same bits, and ANY sub-range gives, bit for bit, the intervals of the whole
+ * range that lie wholly inside it, for both nonlinearities.  d_stats equals pgl_rescale_dev's bit for bit (column 3
+ * stays 0): a range whose t_lo is a multiple of 256 shares that call's chunks (one read of the currents: k_rcorr_chunk,
+ * k_rescale_scan, k_rcorr_finish); a range that starts inside a chunk takes the expected count from that call's own
+ * chunk and scan launches first (k_rescale_chunk, k_rescale_scan, k_rcorr_chunk, k_rcorr_finish: a second read, for such
+ * ranges only).
+ * Arguments and errors as pgl_rescale_dev / pgl_rescale; draw < 0: PGL_ERR_ARG.  (Rule and host mirror: csrc/pglm_gof.h.) */
+int pgl_rescale_corr_dev(pgl_handle h, const double* d_theta, const double* d_Weff, uint64_t seed, int64_t draw, double* d_tau,
+                         const int64_t* d_off, double* d_stats);
+int pgl_rescale_corr(pgl_handle h, const double* theta, const double* Weff, uint64_t seed, int64_t draw, double* tau_out,
+                     double* stats_out);
+
+/* Kolmogorov-Smirnov distance of segmented samples of rescaled intervals from Exp(1).  Segment m is
+ * tau[off[m] .. off[m+1]) (off: M + 1 non-decreasing int64 from 0; lengths from 0 up), n its length:
+ *     z_i = -expm1(-tau_i);  with z sorted ascending  D+ = max_p ((double)(p + 1) / (double)n - z_(p)),
+ *     D- = max_p (z_(p) - (double)p / (double)n), p from 0;  D = max(D+, D-);
+ *     n < 2: the three distances are NaN;  any tau_i that is NaN or negative: NaN as well (n is still reported, the
+ *     segment's part of zsorted is then unspecified);  tau = +inf is legal (z = 1).  Offsets that decrease give a segment
+ *     of negative length: NaN distances and that length in n, nothing read or written for it (the device entry does not
+ *     read the offsets; pgl_ks_uniform checks them on the host).
+ * ks (M, 4) = D, D+, D-, n per segment.  zsorted (the length of tau; may be NULL): every segment's z, sorted.  The sort is a
+ * fixed compare-exchange network (one workgroup per segment, k_ks_segment): its running time does not depend on the
+ * values (recorded as k_ks_segment under PGL_OPT_RECORD_KERNELS, appended to the record), the maxima and the sorted values do not depend on how ties fall, a segment gives the same bits alone or among
+ * others, and given the same z the result equals numpy's max((arange(1, n + 1) / n - z).max(), (z - arange(0, n) / n).max())
+ * bit for bit.
+ * ks_uniform_dev: device pointers, asynchronous on the handle's stream when d_zsorted is given; with d_zsorted = NULL the
+ *     call waits once for the stream to read off[M] and sorts in a buffer of the handle.  The handle supplies device and
+ *     stream only: no data set is needed.
+ * ks_uniform:     the same with host pointers.
+ * M < 1 or a NULL tau / off / ks: PGL_ERR_ARG. */
+#define PGL_KS_NOUT 4
+int pgl_ks_uniform_dev(pgl_handle h, const double* d_tau, const int64_t* d_off, int64_t M, double* d_ks, double* d_zsorted);
+int pgl_ks_uniform(pgl_handle h, const double* tau, const int64_t* off, int64_t M, double* ks_out, double* zsorted_out);
 
 /* Pointwise log-likelihood of a parameter draw, resolved in time, and its accumulation over posterior draws for WAIC
  * (Watanabe 2010; Vehtari, Gelman & Gabry 2017) and held-out predictive densities.  The reference computes the held-out
@@ -1088,7 +1145,8 @@ int pgl_set_stream(pgl_handle h, void* stream);
  * launches of every column slice), 5 the k_hess launches of pgl_hess_dev after such a prepare (one per batch of rows),
  * 6 the launches of pgl_rescale_dev (those of path 2, then k_rescale_chunk<nlin>, k_rescale_scan, k_rescale_finish; the dry
  * run's context has nlin = PGL_NLIN_EXP), 7 the launches of pgl_pointwise_dev (those of path 2, then k_pw_chunk<nlin>,
- * k_pw_block), 8 the launches of pgl_rate_windows_dev at win = 50 (those of path 2, then k_rw_piece<nlin>, k_rw_window).
+ * k_pw_block), 8 the launches of pgl_rate_windows_dev at win = 50 (those of path 2, then k_rw_piece<nlin>, k_rw_window),
+ * 9 the launches of pgl_rescale_corr_dev (those of path 2, then k_rcorr_chunk<nlin>, k_rescale_scan, k_rcorr_finish).
  * Paths 3 / 4 / 5 with stim >= 1 return PGL_ERR_UNSUPPORTED, as the calls themselves.
  * The reference has no counterpart (Theano picks its own C implementations); tests hold every reachable instantiation to
  * zero bytes of scratch. */

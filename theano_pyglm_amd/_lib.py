@@ -53,6 +53,7 @@ SYMBOLS = [
     'pgl_newton_state_doubles', 'pgl_newton_init_dev', 'pgl_newton_assemble_dev', 'pgl_newton_direction_dev',
     'pgl_newton_trial_dev', 'pgl_newton_search_step_dev',
     'pgl_rescale_count', 'pgl_rescale_dev', 'pgl_rescale',
+    'pgl_rescale_corr_dev', 'pgl_rescale_corr', 'pgl_ks_uniform_dev', 'pgl_ks_uniform',
     'pgl_pointwise_count', 'pgl_pointwise_dev', 'pgl_pointwise',
     'pgl_rate_windows_count', 'pgl_rate_windows_dev', 'pgl_rate_windows',
     'pgl_psis_loo_dev', 'pgl_psis_loo',
@@ -61,13 +62,15 @@ SYMBOLS = [
 ]
 
 
-ABI_VERSION = 113                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
+ABI_VERSION = 114                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
 
 GEMM_NT, GEMM_MFMA_1, GEMM_MFMA_4, GEMM_KC_4_1_8, GEMM_KC_1_0_16 = range(5)   # PGL_GEMM_*: the kernel of pgl_gemm_dev
 
 RW_NACC = 5                         # PGL_RW_NACC: planes of the rate-window accumulator -- mean, M2, min, max, pit
 RW_MAX_COUNT = 1024                 # PGL_RW_MAX_COUNT: the largest observed window count with a pit (more: NaN)
 RW_MAX_LAM = 700.0                  # the largest expected window count with a pit (more: NaN)
+KS_NOUT = 4                         # PGL_KS_NOUT: columns of ks_uniform's result -- D, D+, D-, n
+KS_TILE = 4096                      # PGL_KS_TILE: the doubles of a tile of the KS sort (csrc/pglm_gof.h)
 PSIS_NOUT = 4                       # PGL_PSIS_NOUT: planes of psis_loo's result -- elpd, khat, n_eff, tail length
 PSIS_MAX_DRAWS = 4096               # PGL_PSIS_MAX_DRAWS: the draws a workgroup's LDS holds; more: PGL_ERR_UNSUPPORTED
 DIAG_MAX_DRAWS = 4096               # PGL_DIAG_MAX_DRAWS: the pooled draws (chains x draws) chain_diag's workgroup holds
@@ -200,6 +203,10 @@ def load():
     lib.pgl_rescale_count.argtypes = [vp, vp]
     lib.pgl_rescale_dev.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.pgl_rescale.argtypes = [vp, vp, vp, vp, vp]
+    lib.pgl_rescale_corr_dev.argtypes = [vp, vp, vp, C.c_uint64, C.c_int64, vp, vp, vp]
+    lib.pgl_rescale_corr.argtypes = [vp, vp, vp, C.c_uint64, C.c_int64, vp, vp]
+    lib.pgl_ks_uniform_dev.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
+    lib.pgl_ks_uniform.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
     lib.pgl_pointwise_count.argtypes = [vp, C.c_int, vp]
     lib.pgl_pointwise_dev.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int64]
     lib.pgl_pointwise.argtypes = [vp, vp, vp, C.c_int, vp]
@@ -683,6 +690,76 @@ class DeviceGlm(object):
         stats = np.empty((self.N, 4))
         _chk(self.lib.pgl_rescale(self.h, _ptr(th), _ptr(We), _ptr(tau), _ptr(stats)))
         return tau[:int(off[-1])], off, stats
+
+    # -- discrete-time corrected intervals and the KS distance on the device (pgl_rescale_corr*, pgl_ks_uniform*) ----
+    def rescale_corr_dev(self, d_theta, d_Weff, d_tau, d_off, d_stats, seed=0, draw=0):
+        """rescale_dev with the discrete-time correction of the event bin's term at the uniforms of (seed, draw); see
+        pgl_rescale_corr_dev.  The pointers are integers or torch device tensors."""
+        a = [C.c_void_p(x.data_ptr() if hasattr(x, 'data_ptr') else x) for x in (d_theta, d_Weff, d_tau, d_off, d_stats)]
+        _chk(self.lib.pgl_rescale_corr_dev(self.h, a[0], a[1], C.c_uint64(int(seed) & (2 ** 64 - 1)), int(draw), a[2], a[3], a[4]))
+
+    def rescale_corr(self, theta, Weff, seed=0, draw=0):
+        """rescale with the discrete-time correction: (tau', off, stats); tau' is a random function of seed and draw, the same
+        bits for the same pair (pgl_rescale_corr)."""
+        th = _f64(theta, (self.N, self.P))
+        We = _f64(Weff, (self.N, self.N))
+        off = self.rescale_count()
+        tau = np.empty(max(int(off[-1]), 1))
+        stats = np.empty((self.N, 4))
+        _chk(self.lib.pgl_rescale_corr(self.h, _ptr(th), _ptr(We), C.c_uint64(int(seed) & (2 ** 64 - 1)), int(draw), _ptr(tau),
+                                       _ptr(stats)))
+        return tau[:int(off[-1])], off, stats
+
+    def ks_uniform(self, tau, off, out=None, zsorted=None):
+        """KS distance from Exp(1) of the segments tau[off[m]:off[m + 1]] of the torch device tensors tau (f64) and off
+        (M + 1, int64): -> out (M, 4) = D, D+, D-, n on tau's device, written into `out` (a row of a draws matrix, say)
+        where given.  zsorted: True returns (out, z) with every segment's z = -expm1(-tau) sorted, a tensor of tau's length
+        is written into, None lets the handle sort in a buffer of its own -- the call then waits once for the stream
+        (pgl_ks_uniform_dev)."""
+        import torch
+        if not (isinstance(tau, torch.Tensor) and tau.is_cuda and tau.dtype == torch.float64 and tau.dim() == 1 and
+                tau.is_contiguous()):
+            raise ValueError("ks_uniform: tau must be a contiguous float64 device vector")
+        if not (isinstance(off, torch.Tensor) and off.is_cuda and off.dtype == torch.int64 and off.dim() == 1 and
+                off.is_contiguous() and off.numel() >= 2):
+            raise ValueError("ks_uniform: off must be a contiguous int64 device vector (M + 1)")
+        M = int(off.numel()) - 1
+        n_tau = int(tau.numel())
+        src = tau if n_tau else torch.zeros(1, dtype=torch.float64, device=tau.device)     # (an empty tensor has no address)
+        if out is None:
+            out = torch.empty((M, KS_NOUT), dtype=torch.float64, device=tau.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and
+                  tuple(out.shape) == (M, KS_NOUT)):
+            raise ValueError("ks_uniform: out must be a contiguous float64 device tensor (%d, %d)" % (M, KS_NOUT))
+        z = None
+        if zsorted is True:
+            z = torch.empty(max(int(tau.numel()), 1), dtype=torch.float64, device=tau.device)
+        elif zsorted is not None and zsorted is not False:
+            z = zsorted
+            if not (isinstance(z, torch.Tensor) and z.is_cuda and z.dtype == torch.float64 and z.is_contiguous() and
+                    z.numel() >= max(n_tau, 1)):
+                raise ValueError("ks_uniform: zsorted must be a contiguous float64 device vector of tau's length")
+        _chk(self.lib.pgl_ks_uniform_dev(self.h, C.c_void_p(src.data_ptr()), C.c_void_p(off.data_ptr()), M,
+                                         C.c_void_p(out.data_ptr()), C.c_void_p(z.data_ptr()) if z is not None else None))
+        return (out, z[:n_tau]) if zsorted is True else out
+
+    def ks_uniform_dev(self, d_tau, d_off, M, d_ks, d_zsorted=0):
+        """Device-pointer form (integers): see pgl_ks_uniform_dev."""
+        _chk(self.lib.pgl_ks_uniform_dev(self.h, C.c_void_p(d_tau), C.c_void_p(d_off), int(M), C.c_void_p(d_ks),
+                                         C.c_void_p(d_zsorted) if d_zsorted else None))
+
+    def ks_uniform_host(self, tau, off, zsorted=False):
+        """The same with host arrays: -> ks (M, 4), or (ks, z) with zsorted=True (pgl_ks_uniform)."""
+        t = np.ascontiguousarray(tau, dtype=np.float64).ravel()
+        o = np.ascontiguousarray(off, dtype=np.int64).ravel()
+        if o.size < 2 or o[0] != 0 or int(o[-1]) != t.size:
+            raise ValueError("ks_uniform_host: off (M + 1) from 0 to len(tau)")
+        M = o.size - 1
+        ks = np.empty((M, KS_NOUT))
+        z = np.empty(max(t.size, 1)) if zsorted else None
+        tt = t if t.size else np.zeros(1)
+        _chk(self.lib.pgl_ks_uniform(self.h, _ptr(tt), _ptr(o), int(M), _ptr(ks), _ptr(z) if zsorted else None))
+        return (ks, z[:t.size]) if zsorted else ks
 
     # -- pointwise log-likelihood of a draw, and its accumulation over draws (pgl_pointwise*) -------------
     def pointwise_count(self, block_chunks=1):

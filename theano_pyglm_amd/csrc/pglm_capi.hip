@@ -125,6 +125,9 @@ struct pgl_context {
     // time rescaling (pgl_rescale_dev): in-chunk sums at the events, chunk totals and their prefix; pgl_rescale: the device
     // copies of its offsets and results
     DevBuf rs_pre, rs_tot, rs_cum, rs_off, rs_tau, rs_stats;
+    // the corrected intervals (pgl_rescale_corr_dev): the rate of every event's bin; pgl_ks_uniform_dev: the sorted values where
+    // the caller wants none; pgl_ks_uniform: the device copies of its arrays
+    DevBuf rs_qev, rs_tail, ks_work, ks_tau, ks_off, ks_out;
     DevBuf psis_in, psis_out, psis_lw;   // pgl_psis_loo: the device copies of its host arrays
     DevBuf diag_in, diag_out;            // pgl_chain_diag: the same
     DevBuf pw_part, pw_out;              // pointwise ll (pgl_pointwise_dev): chunk sums; pgl_pointwise: the device copy of ll_blk_out
@@ -346,6 +349,7 @@ int pgl_destroy(pgl_handle h)
                       &h->spart, &h->sepC, &h->sepA, &h->sepAT, &h->sepD, &h->YfT, &h->Hb, &h->wpart, &h->QvT, &h->staA,
                       &h->Cbuf, &h->hvp_idx, &h->hvp_Weff, &h->hvp_ll, &h->hvp_v, &h->hvp_out,
                       &h->hess_part, &h->hess_out, &h->rs_pre, &h->rs_tot, &h->rs_cum, &h->rs_off, &h->rs_tau, &h->rs_stats,
+                      &h->rs_qev, &h->rs_tail, &h->ks_work, &h->ks_tau, &h->ks_off, &h->ks_out,
                       &h->pw_part, &h->pw_out, &h->rw_part, &h->rw_cnt, &h->rw_out, &h->psis_in, &h->psis_out, &h->psis_lw, &h->diag_in, &h->diag_out};
     for (DevBuf* b : bufs) release(*b);
     for (int s = 0; s < pgl_context::NEV; ++s)
@@ -1877,7 +1881,8 @@ int pgl_set_stream(pgl_handle h, void* stream)
 }
 
 static int enqueue_gibbs_forward(pgl_handle h);
-static int enqueue_rescale(pgl_handle h, double* d_tau, const long long* d_off, double* d_stats);
+static int enqueue_rescale(pgl_handle h, double* d_tau, const long long* d_off, double* d_stats, bool corr = false,
+                           unsigned long long seed = 0, long long draw = 0);
 static int enqueue_pointwise(pgl_handle h, int block_chunks, double* d_ll_blk, double* d_acc, long long draw);
 static int enqueue_rate_windows(pgl_handle h, long long win, double* d_lam, double* d_obs, double* d_acc, long long draw);
 
@@ -1901,7 +1906,8 @@ int pgl_last_kernels(pgl_handle h, char* out, int cap)
 // it; stim >= 1: PGL_ERR_UNSUPPORTED, as the real call), 5 the k_hess launches of pgl_hess_dev after such a prepare,
 // 6 the launches of pgl_rescale_dev (the forward launches of path 2, then the k_rescale_* kernels), 7 those of
 // pgl_pointwise_dev (the forward launches of path 2, then k_pw_chunk and k_pw_block), 8 those of pgl_rate_windows_dev (the
-// forward launches of path 2, then k_rw_piece and k_rw_window).
+// forward launches of path 2, then k_rw_piece and k_rw_window), 9 those of pgl_rescale_corr_dev (the forward launches of path 2,
+// then k_rcorr_chunk, k_rescale_scan and k_rcorr_finish).
 int pgl_plan_kernels(int N, int B, int R, int Dstim, long long nT, int stim, int n_lo, int count, int path, int opt_kernel,
                      int opt_f32, char* out, int cap)
 {
@@ -1933,12 +1939,13 @@ int pgl_plan_kernels(int N, int B, int R, int Dstim, long long nT, int stim, int
         }
     } else {
         g_dry = &names;
-        rc = (path == 2 || path == 6 || path == 7 || path == 8) ? enqueue_gibbs_forward(&c)
+        rc = (path == 2 || path == 6 || path == 7 || path == 8 || path == 9) ? enqueue_gibbs_forward(&c)
                          : enqueue_ll_grad(&c, n_lo, n_lo + count, nullptr, nullptr, &dummy, path == 0 ? &dummy : nullptr);
     }
     if (rc == PGL_OK && path == 6) rc = enqueue_rescale(&c, &dummy, nullptr, &dummy);
     if (rc == PGL_OK && path == 7) rc = enqueue_pointwise(&c, 1, &dummy, nullptr, 0);
     if (rc == PGL_OK && path == 8) rc = enqueue_rate_windows(&c, 50, &dummy, nullptr, nullptr, 0);
+    if (rc == PGL_OK && path == 9) rc = enqueue_rescale(&c, &dummy, nullptr, &dummy, true);
     g_dry = nullptr;
     // (under g_dry nothing but a dispatch (pglm_launch.h) without an instantiation for the plan fails with PGL_ERR_HIP)
     if (rc == PGL_ERR_HIP) return fail(PGL_ERR_UNSUPPORTED, "no kernel instantiation for this plan");
@@ -2880,40 +2887,142 @@ static int launch_walk(pgl_handle h, const char* fam, void (*walk1)(Prm), void (
 }  // extern "C++"
 
 // the k_rescale_* launches behind a forward pass.  The dry run of the dispatch runs this too: see launch_behind.
-static int enqueue_rescale(pgl_handle h, double* d_tau, const long long* d_off, double* d_stats)
+// corr: the discrete-time corrected intervals (k_rcorr_chunk / k_rcorr_finish around the same scan).
+static int enqueue_rescale(pgl_handle h, double* d_tau, const long long* d_off, double* d_stats, bool corr, unsigned long long seed,
+                           long long draw)
 {
     RescaleParams p;
     p.src = bin_source(h);
     p.nchunks = (int)rs_chunks(h);
+    p.qev = nullptr; p.tail = nullptr; p.lam_row = nullptr; p.seed = seed; p.draw = draw;
+    // the corrected variant walks the absolute chunk grid: one chunk more where t_lo lies inside a chunk
+    p.c0 = h->t_lo / PGL_RS_CHUNK;
+    p.nchunks_abs = (int)((h->t_hi + PGL_RS_CHUNK - 1) / PGL_RS_CHUNK - p.c0);
+    const bool on_grid = h->t_lo % PGL_RS_CHUNK == 0;
     ENSURE(h->rs_pre, (size_t)std::max<int64_t>(h->nnz, 1) * 8);
-    ENSURE(h->rs_tot, (size_t)p.nchunks * p.src.xs * 8);
+    if (corr) {
+        ENSURE(h->rs_qev, (size_t)std::max<int64_t>(h->nnz, 1) * 8);
+        ENSURE(h->rs_tail, (size_t)p.nchunks_abs * p.src.xs * 8);
+        p.qev = (double*)h->rs_qev.p;
+        p.tail = (double*)h->rs_tail.p;
+    }
+    ENSURE(h->rs_tot, (size_t)std::max(p.nchunks, p.nchunks_abs) * p.src.xs * 8);
     ENSURE(h->rs_cum, (size_t)(p.nchunks + 1) * p.src.xs * 8);
     p.pre = (double*)h->rs_pre.p; p.tot = (double*)h->rs_tot.p; p.cum = (double*)h->rs_cum.p;
     p.off = d_off; p.tau = d_tau; p.stats = d_stats;
-    int rc = launch_walk(h, "k_rescale_chunk", k_rescale_chunk<1>, k_rescale_chunk<0>, p.nchunks, p);
+    p.lam_row = p.cum + (size_t)p.nchunks * p.src.xs;
+    int rc;
+    if (corr && !on_grid) {
+        // a range that starts inside a chunk: the expected count of stats is pgl_rescale_dev's own sum over the chunks from
+        // t_lo (a second read of the currents, for such ranges only), then the corrected intervals on the absolute grid
+        rc = launch_walk(h, "k_rescale_chunk", k_rescale_chunk<1>, k_rescale_chunk<0>, p.nchunks, p);
+        if (rc) return rc;
+        rc = launch_behind(h, "k_rescale_scan", k_rescale_scan, (h->N + 15) / 16, 16 * PGL_RS_SEGS, p);
+        if (rc) return rc;
+        rc = launch_walk(h, "k_rcorr_chunk", k_rcorr_chunk<1>, k_rcorr_chunk<0>, p.nchunks_abs, p);
+        if (rc) return rc;
+        return launch_behind(h, "k_rcorr_finish", k_rcorr_finish, h->N, 256, p);
+    }
+    rc = corr ? launch_walk(h, "k_rcorr_chunk", k_rcorr_chunk<1>, k_rcorr_chunk<0>, p.nchunks_abs, p)
+              : launch_walk(h, "k_rescale_chunk", k_rescale_chunk<1>, k_rescale_chunk<0>, p.nchunks, p);
     if (rc) return rc;
     rc = launch_behind(h, "k_rescale_scan", k_rescale_scan, (h->N + 15) / 16, 16 * PGL_RS_SEGS, p);
     if (rc) return rc;
-    return launch_behind(h, "k_rescale_finish", k_rescale_finish, h->N, 256, p);
+    return corr ? launch_behind(h, "k_rcorr_finish", k_rcorr_finish, h->N, 256, p)
+                : launch_behind(h, "k_rescale_finish", k_rescale_finish, h->N, 256, p);
+}
+
+static int rescale_host(pgl_handle h, const double* theta, const double* Weff, double* tau_out, double* stats_out, bool corr,
+                        uint64_t seed, int64_t draw);
+
+static int rescale_dev(pgl_handle h, const double* d_theta, const double* d_Weff, double* d_tau, const int64_t* d_off,
+                       double* d_stats, bool corr, uint64_t seed, int64_t draw)
+{
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if (!d_theta || !d_Weff || !d_tau || !d_off || !d_stats) return fail(PGL_ERR_ARG, "null argument");
+    if (draw < 0) return fail(PGL_ERR_ARG, "draw must not be negative");
+    if (rs_chunks(h) > 0x7fffffff / 2048) return fail(PGL_ERR_UNSUPPORTED, "time range too long for the rescaling kernels");
+    rc = forward_from_dev(h, d_theta, d_Weff);
+    if (rc) return rc;
+    return enqueue_rescale(h, d_tau, (const long long*)d_off, d_stats, corr, seed, draw);
 }
 
 int pgl_rescale_dev(pgl_handle h, const double* d_theta, const double* d_Weff, double* d_tau, const int64_t* d_off,
                     double* d_stats)
 {
-    int rc = check_ready(h);
+    return rescale_dev(h, d_theta, d_Weff, d_tau, d_off, d_stats, false, 0, 0);
+}
+
+// ---- the discrete-time corrected intervals and the KS distance of segmented samples (pglm_gof.h, pglm_gof.hip.h) ---------
+int pgl_rescale_corr_dev(pgl_handle h, const double* d_theta, const double* d_Weff, uint64_t seed, int64_t draw, double* d_tau,
+                         const int64_t* d_off, double* d_stats)
+{
+    return rescale_dev(h, d_theta, d_Weff, d_tau, d_off, d_stats, true, seed, draw);
+}
+
+int pgl_rescale_corr(pgl_handle h, const double* theta, const double* Weff, uint64_t seed, int64_t draw, double* tau_out,
+                     double* stats_out)
+{
+    return rescale_host(h, theta, Weff, tau_out, stats_out, true, seed, draw);
+}
+
+int pgl_ks_uniform_dev(pgl_handle h, const double* d_tau, const int64_t* d_off, int64_t M, double* d_ks, double* d_zsorted)
+{
+    if (!h) return fail(PGL_ERR_ARG, "null handle");
+    if (!d_tau || !d_off || !d_ks) return fail(PGL_ERR_ARG, "null argument");
+    if (M < 1 || M > 0x7fffffff) return fail(PGL_ERR_ARG, "pgl_ks_uniform_dev: M must lie in 1 .. 2^31 - 1");
+    HIPCHK(hipSetDevice(h->device));
+    if (!d_zsorted) {
+        // the network sorts in place: room for every z.  The one place where the call waits for the device
+        int64_t total = 0;
+        HIPCHK(hipMemcpyAsync(&total, d_off + M, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (total < 0) return fail(PGL_ERR_ARG, "pgl_ks_uniform_dev: negative offsets");
+        ENSURE(h->ks_work, (size_t)std::max<int64_t>(total, 1) * 8);
+        d_zsorted = (double*)h->ks_work.p;
+    }
+    KsParams p;
+    p.tau = d_tau; p.off = (const long long*)d_off; p.zs = d_zsorted; p.ks = d_ks;
+    return launch_behind(h, "k_ks_segment", k_ks_segment, (unsigned)M, PGL_KS_THREADS, p);
+}
+
+int pgl_ks_uniform(pgl_handle h, const double* tau, const int64_t* off, int64_t M, double* ks_out, double* zsorted_out)
+{
+    if (!h) return fail(PGL_ERR_ARG, "null handle");
+    if (!tau || !off || !ks_out) return fail(PGL_ERR_ARG, "null argument");
+    if (M < 1 || M > 0x7fffffff) return fail(PGL_ERR_ARG, "pgl_ks_uniform: M must lie in 1 .. 2^31 - 1");
+    for (int64_t m = 0; m < M; ++m)
+        if (off[m + 1] < off[m] || off[0] < 0) return fail(PGL_ERR_ARG, "pgl_ks_uniform: offsets must not decrease");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t total = (size_t)off[M], tb = std::max<size_t>(total, 1) * 8;
+    ENSURE(h->ks_tau, tb);
+    ENSURE(h->ks_work, tb);
+    ENSURE(h->ks_off, ((size_t)M + 1) * 8);
+    ENSURE(h->ks_out, (size_t)M * PGL_KS_NOUT * 8);
+    if (total) HIPCHK(hipMemcpyAsync(h->ks_tau.p, tau, total * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->ks_off.p, off, ((size_t)M + 1) * 8, hipMemcpyHostToDevice, h->stream));
+    int rc = pgl_ks_uniform_dev(h, (const double*)h->ks_tau.p, (const int64_t*)h->ks_off.p, M, (double*)h->ks_out.p,
+                                (double*)h->ks_work.p);
     if (rc) return rc;
-    if (!d_theta || !d_Weff || !d_tau || !d_off || !d_stats) return fail(PGL_ERR_ARG, "null argument");
-    if (rs_chunks(h) > 0x7fffffff / 2048) return fail(PGL_ERR_UNSUPPORTED, "time range too long for the rescaling kernels");
-    rc = forward_from_dev(h, d_theta, d_Weff);
-    if (rc) return rc;
-    return enqueue_rescale(h, d_tau, (const long long*)d_off, d_stats);
+    HIPCHK(hipMemcpyAsync(ks_out, h->ks_out.p, (size_t)M * PGL_KS_NOUT * 8, hipMemcpyDeviceToHost, h->stream));
+    if (zsorted_out && total) HIPCHK(hipMemcpyAsync(zsorted_out, h->ks_work.p, total * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return PGL_OK;
 }
 
 int pgl_rescale(pgl_handle h, const double* theta, const double* Weff, double* tau_out, double* stats_out)
 {
+    return rescale_host(h, theta, Weff, tau_out, stats_out, false, 0, 0);
+}
+
+static int rescale_host(pgl_handle h, const double* theta, const double* Weff, double* tau_out, double* stats_out, bool corr,
+                        uint64_t seed, int64_t draw)
+{
     int rc = check_ready(h);
     if (rc) return rc;
     if (!theta || !Weff || !tau_out || !stats_out) return fail(PGL_ERR_ARG, "null argument");
+    if (draw < 0) return fail(PGL_ERR_ARG, "draw must not be negative");
     HIPCHK(hipSetDevice(h->device));
     const int N = h->N;
     std::vector<int64_t> off((size_t)N + 1);
@@ -2926,8 +3035,8 @@ int pgl_rescale(pgl_handle h, const double* theta, const double* Weff, double* t
     HIPCHK(hipMemcpyAsync(h->rs_off.p, off.data(), ((size_t)N + 1) * 8, hipMemcpyHostToDevice, h->stream));
     rc = upload_draw(h, theta, Weff);                 // (its synchronise covers the offsets too)
     if (rc) return rc;
-    rc = pgl_rescale_dev(h, (const double*)h->gtheta.p, (const double*)h->Weff.p, (double*)h->rs_tau.p,
-                         (const int64_t*)h->rs_off.p, (double*)h->rs_stats.p);
+    rc = rescale_dev(h, (const double*)h->gtheta.p, (const double*)h->Weff.p, (double*)h->rs_tau.p,
+                     (const int64_t*)h->rs_off.p, (double*)h->rs_stats.p, corr, seed, draw);
     if (rc) return rc;
     if (ntau) HIPCHK(hipMemcpyAsync(tau_out, h->rs_tau.p, ntau * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(stats_out, h->rs_stats.p, (size_t)N * 4 * 8, hipMemcpyDeviceToHost, h->stream));

@@ -9,7 +9,9 @@ lock-step Newton-CG optimizer on device Hessian-vector products (inference/batch
 --newton runs the sweep as the GPU lock-step dense-Hessian Newton fit (inference/batched_newton.py; the reference's use_hessian).
 --prox runs the sweep as the GPU lock-step proximal-gradient fit of the group-lasso MAP (inference/batched_prox.py) and prints
 status, iterations and the number of non-zero presynaptic groups per neuron.
---gof prints the time-rescaling KS table of the fitted model (inference/gof.py) after the fit.
+--gof prints the time-rescaling KS table of the fitted model (inference/gof.py) after the fit; --gof-correct applies the
+discrete-time correction to it (a random function of its seed, 0).  With --hmc N or --nuts N, --gof-draws prints the KS
+distance over the posterior draws per neuron (corrected; sorted and tested on the device).
 --ppc N prints the predictive spike-count table of N replicates simulated from the fitted model (inference/predictive.py).
 --hmc N draws N posterior samples of every neuron's parameters from the fit by lock-step HMC on the device
 (inference/batched_hmc.py) and prints the bias posterior mean +- sd per neuron, beside the Laplace standard error when
@@ -60,7 +62,8 @@ def initialize_test_harness(model_name, data, data_dir=None):
 
 
 def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False, gof=False, ppc=0, hmc=0, ais=0,
-                   hmc_mass='laplace', prox=False, laplace_device=False, ais_mass='laplace', nuts=0, smc=0, newton=False, waic=False, loo=False, diag=False, rates=0):
+                   hmc_mass='laplace', prox=False, laplace_device=False, ais_mass='laplace', nuts=0, smc=0, newton=False, waic=False, loo=False, diag=False, rates=0,
+                   gof_correct=False, gof_draws=False):
     """test/synth_map.py:10-32."""
     popn, popn_true, x_true = initialize_test_harness(model_name, data, data_dir)
     x0 = popn.sample(rng)
@@ -77,14 +80,14 @@ def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, r
             pickle.dump(x_inf, f, protocol=-1)
     if gof:
         from theano_pyglm_amd.inference.gof import ks_time_rescaling, format_table
-        print(format_table(ks_time_rescaling(popn, x_inf)))
+        print(format_table(ks_time_rescaling(popn, x_inf, correct=True) if gof_correct else ks_time_rescaling(popn, x_inf)))
     if ppc:
         from theano_pyglm_amd.inference import predictive
         print(predictive.format_table(predictive.predictive_counts(popn, x_inf, ppc)))
     if hmc:
-        print(hmc_bias_table(popn, x_inf, hmc, hmc_mass, laplace_device, waic=waic, loo=loo, diag=diag, rates=rates))
+        print(hmc_bias_table(popn, x_inf, hmc, hmc_mass, laplace_device, waic=waic, loo=loo, diag=diag, rates=rates, gof_draws=gof_draws))
     if nuts:
-        print(nuts_bias_table(popn, x_inf, nuts, hmc_mass, laplace_device, waic=waic, loo=loo, diag=diag, rates=rates))
+        print(nuts_bias_table(popn, x_inf, nuts, hmc_mass, laplace_device, waic=waic, loo=loo, diag=diag, rates=rates, gof_draws=gof_draws))
     if ais:
         print(ais_evidence_table(popn, x_inf, ais, laplace_device, ais_mass))
     if smc:
@@ -106,7 +109,8 @@ def prox_table(popn, x):
     return "\n".join(lines)
 
 
-def hmc_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=False, loo=False, diag=False, rates=0):
+def hmc_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=False, loo=False, diag=False, rates=0,
+                   gof_draws=False):
     """n_draws kept HMC draws from x with the mass matrix `mass` ('laplace' or 'laplace_dense'): one line per neuron, bias
     posterior mean +- sd (and the Laplace standard error).  laplace_device: the Laplace factorisations (the dense mass
     matrix and the standard errors) run on the device.  waic / loo: the WAIC / PSIS-LOO table of the draws follows (waic_table, loo_table); diag: the convergence table
@@ -129,6 +133,8 @@ def hmc_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=
         ln = "%6d  %9.4f +- %-8.4f %6.0f  %6.2f  %6.4f" % (n, s['mean'][n], s['sd'][n], s['ess'][n], res['accept_rate'][n],
                                                           res['step_sz'][n])
         lines.append(ln + ("   %10.4f" % se[n] if se is not None else ""))
+    if gof_draws:
+        lines.append(gof_draws_table(popn, x, res['samples']))
     if waic:
         lines.append(waic_table(popn, x, res['samples']))
     if loo:
@@ -141,7 +147,8 @@ def hmc_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=
     return "\n".join(lines)
 
 
-def nuts_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=False, loo=False, diag=False, rates=0, **kw):
+def nuts_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=False, loo=False, diag=False, rates=0,
+                    gof_draws=False, **kw):
     """hmc_bias_table with the No-U-Turn sampler: the same columns ('accept' is the mean acceptance statistic after
     warm-up) plus the median tree depth of the kept transitions and the divergent transitions after warm-up.  kw: further
     arguments of sample_glms_nuts (n_warmup, max_depth, ...).  waic / loo: the WAIC / PSIS-LOO table of the draws follows (waic_table, loo_table); diag: the convergence table
@@ -168,6 +175,8 @@ def nuts_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic
                                                                     res['accept_rate'][n], res['step_sz'][n], depth[n],
                                                                     res['divergent'][n])
         lines.append(ln + ("   %10.4f" % se[n] if se is not None else ""))
+    if gof_draws:
+        lines.append(gof_draws_table(popn, x, res['samples']))
     if waic:
         lines.append(waic_table(popn, x, res['samples']))
     if loo:
@@ -187,6 +196,14 @@ def rates_table(popn, x, samples, win):
     t0 = time.time()
     res = predictive.rate_bands(popn, x, samples, win=win)
     return predictive.format_rate_table(res) + "\n(rate bands of %d draws in %.2f s)" % (res['n_draws'], time.time() - t0)
+
+
+def gof_draws_table(popn, x, samples):
+    """The time-rescaling KS distance over posterior draws (samples (S, N, P) of all neurons), discrete-time corrected."""
+    from theano_pyglm_amd.inference import gof
+    t0 = time.time()
+    res = gof.ks_time_rescaling_draws(popn, x, samples)
+    return gof.format_draws_table(res) + "\n(KS distance of %d draws in %.2f s)" % (res['n_draws'], time.time() - t0)
 
 
 def waic_table(popn, x, samples, block_chunks=40):
@@ -264,6 +281,12 @@ def parser():
                          'iterations and the non-zero groups per neuron')
     ap.add_argument('--gof', action='store_true',
                     help='after the fit: time-rescaling KS test of every neuron (rescaled inter-spike intervals against Exp(1))')
+    ap.add_argument('--gof-correct', action='store_true',
+                    help='with --gof: apply the discrete-time correction of Haslinger et al. (2010); the table is then a random '
+                         'function of the seed (0)')
+    ap.add_argument('--gof-draws', action='store_true',
+                    help='with --hmc N / --nuts N: the time-rescaling KS distance of every posterior draw (corrected), sorted and '
+                         'tested on the device; prints mean, 5 %% and 95 %% quantiles and the share of draws inside the band')
     ap.add_argument('--ppc', type=int, default=0, metavar='N',
                     help='after the fit: predictive spike counts of N replicates simulated from the fitted model on the device')
     ap.add_argument('--hmc', type=int, default=0, metavar='N',
@@ -308,7 +331,8 @@ def main(argv=None):
     run_synth_test(args.model, data, args.resultsDir, os.path.dirname(args.dataFile),
                    False if args.sequential else ('torch' if args.newton_cg else None), use_rop=args.newton_cg, gof=args.gof, ppc=args.ppc, hmc=args.hmc, ais=args.ais,
                    hmc_mass=args.hmc_mass, prox=args.prox, laplace_device=args.laplace_device, ais_mass=args.ais_mass, nuts=args.nuts, smc=args.smc,
-                   newton=args.newton, waic=args.waic, loo=args.loo, diag=args.diag, rates=args.rates)
+                   newton=args.newton, waic=args.waic, loo=args.loo, diag=args.diag, rates=args.rates,
+                   gof_correct=args.gof_correct, gof_draws=args.gof_draws)
 
 
 if __name__ == '__main__':

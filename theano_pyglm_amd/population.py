@@ -387,17 +387,20 @@ class Population(object):
         return out
 
     # -- goodness of fit -------------------------------------------------------------------
-    def compute_rescaled_intervals(self, vars):
+    def compute_rescaled_intervals(self, vars, correct=False, seed=0, draw=0):
         """Time rescaling (Brown et al. 2002) of every neuron's spike train under `vars`: the integrated rate between
         consecutive event bins, Exp(1) under the true model.  One forward pass and one segmented sum on the device per data
         sequence (pgl_rescale); no rate array comes back to the host.  Returns (taus, stats): taus[n] the intervals of
         neuron n, the data sequences one after the other (the interval before the first event of a sequence is censored);
         stats (N, 4) summed over the sequences: expected count, event bins, event bins holding more than one spike, 0.
-        A bin with several spikes is one event; the discrete-time correction of Haslinger et al. (2010) is not applied."""
+        A bin with several spikes is one event.  correct=True applies the discrete-time correction of Haslinger et al.
+        (2010) to the event bin's term (pgl_rescale_corr) at the uniforms of (seed, draw): the intervals are then a random
+        function of seed, the same bits for the same seed and draw; the default is the uncorrected sum."""
         parts = [[] for _ in range(self.N)]
         stats = np.zeros((self.N, 4))
         what = ("rescaled intervals", "are")
-        for tau, off, st in self._per_sequence(vars, what, lambda h, theta, Weff: h.rescale(theta, Weff)):
+        for tau, off, st in self._per_sequence(vars, what, (lambda h, theta, Weff: h.rescale_corr(theta, Weff, seed, draw)) if correct else
+                                              (lambda h, theta, Weff: h.rescale(theta, Weff))):
             for n in range(self.N):
                 parts[n].append(tau[off[n]:off[n + 1]])
             stats += st
