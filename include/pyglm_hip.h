@@ -98,7 +98,7 @@ typedef struct pgl_context* pgl_handle;
 
 /* What pgl_version() returns: it changes with every change of a signature or a struct below, and a binding refuses a
  * library that reports another number (theano_pyglm_amd/_lib.py: ABI_VERSION). */
-#define PGL_ABI_VERSION 114
+#define PGL_ABI_VERSION 115
 
 const char* pgl_last_error(void);
 int pgl_version(void);
@@ -874,6 +874,42 @@ int pgl_rescale_corr(pgl_handle h, const double* theta, const double* Weff, uint
 #define PGL_KS_NOUT 4
 int pgl_ks_uniform_dev(pgl_handle h, const double* d_tau, const int64_t* d_off, int64_t M, double* d_ks, double* d_zsorted);
 int pgl_ks_uniform(pgl_handle h, const double* tau, const int64_t* off, int64_t M, double* ks_out, double* zsorted_out);
+
+/* Independence of the rescaled intervals: the serial correlation of their normal scores at the lags 1 .. max_lag and a
+ * portmanteau statistic over the lags (the second half of the time-rescaling check; the KS distance above tests the marginal
+ * law only).  A SEGMENT is one neuron and is made of RUNS, one per data sequence: intervals of one run are consecutive in
+ * time, intervals of different runs are not neighbours.
+ *     run_off (R + 1 int64, non-decreasing from 0): run r is tau[run_off[r] .. run_off[r+1]);
+ *     seg_run (M + 1 int64, non-decreasing from 0): segment m holds the runs seg_run[m] .. seg_run[m+1];
+ *     n = the segment's number of intervals.  Empty runs and empty segments are legal.
+ * Score:  z = -expm1(-tau), q = z - 1/2.  |q| <= 0.425: Wichura's AS 241 (PPND16), central branch, on q -- evaluated as
+ *     -expm1((LN2_HI - tau) + LN2_LO) / 2 (the two halves of log 2 as doubles), the same number without the cancellation at
+ *     the median; the branch is chosen on the plain z - 0.5.  Otherwise the tail branch on r = z (q < 0) or r = exp(-tau)
+ *     (q > 0: the upper tail directly, not 1 - z), r clamped below at DBL_MIN: tau = 0, a subnormal tau and tau = +inf give
+ *     finite scores of magnitude about 37.5.  The coefficients are those of pgl_chain_diag's scores.
+ * Statistics:  m = (sum g_i) / n, d_i = g_i - m, c_0 = sum d_i^2; c_k = sum d_i d_{i+k} over the pairs whose two members lie
+ *     in the same run, n_k their number; r_k = c_k / c_0; v_k = n_k / (n (n + 2));  Q = sum over the lags with n_k >= 1 of
+ *     r_k^2 / v_k in ascending k (one run: Ljung-Box), dof = the number of those lags.  n_k = 0: r_k = NaN, left out of Q.
+ *     Under independence Q is approximately chi-square with dof degrees of freedom and r_k lies within z_{1-a/2} sqrt(v_k).
+ * Order of the sums (part of the rule): every sum runs over the segment's index i, cut into pieces of 256 consecutive i
+ *     counted from the segment's FIRST element; inside a piece the terms are added in ascending i, invalid pairs skipped;
+ *     the piece totals are added in ascending piece order; every product and every sum is rounded on its own (no fused
+ *     multiply-add).  The bits depend neither on the launch, nor on M, the other segments or max_lag: r_k is the same
+ *     number whatever max_lag >= k is, and a segment gives the same bits alone or among others.
+ * Voids:  any tau of the segment NaN or negative: every output but n is NaN.  n < 3 or c_0 == 0: r and Q are NaN, dof = 0.
+ * out (M, PGL_ACF_NHEAD + max_lag) = n, mean, c_0, Q, dof, 0 (reserved), r_1 .. r_max_lag per segment.
+ * scores (the length of tau): every g_i, the kernel's working array (required by the device entry; NULL allowed on the host).
+ * One workgroup per segment (k_acf_segment, recorded under PGL_OPT_RECORD_KERNELS like k_ks_segment); its running time does
+ * not depend on the values.  The device entry is asynchronous on the handle's stream and does not read the offsets; the host
+ * entry checks them (a decreasing one: PGL_ERR_ARG).  The handle supplies device and stream only.
+ * max_lag outside 1 .. PGL_ACF_MAX_LAG, M < 1, a NULL tau / run_off / seg_run / out (/ d_scores): PGL_ERR_ARG.
+ * (Rule and host mirror: csrc/pglm_acf.h.) */
+#define PGL_ACF_MAX_LAG 64
+#define PGL_ACF_NHEAD 6
+int pgl_rescale_acf_dev(pgl_handle h, const double* d_tau, const int64_t* d_run_off, const int64_t* d_seg_run, int64_t M,
+                        int max_lag, double* d_out, double* d_scores);
+int pgl_rescale_acf(pgl_handle h, const double* tau, const int64_t* run_off, const int64_t* seg_run, int64_t M, int max_lag,
+                    double* out, double* scores_out);
 
 /* Pointwise log-likelihood of a parameter draw, resolved in time, and its accumulation over posterior draws for WAIC
  * (Watanabe 2010; Vehtari, Gelman & Gabry 2017) and held-out predictive densities.  The reference computes the held-out

@@ -53,7 +53,7 @@ SYMBOLS = [
     'pgl_newton_state_doubles', 'pgl_newton_init_dev', 'pgl_newton_assemble_dev', 'pgl_newton_direction_dev',
     'pgl_newton_trial_dev', 'pgl_newton_search_step_dev',
     'pgl_rescale_count', 'pgl_rescale_dev', 'pgl_rescale',
-    'pgl_rescale_corr_dev', 'pgl_rescale_corr', 'pgl_ks_uniform_dev', 'pgl_ks_uniform',
+    'pgl_rescale_corr_dev', 'pgl_rescale_corr', 'pgl_ks_uniform_dev', 'pgl_ks_uniform', 'pgl_rescale_acf_dev', 'pgl_rescale_acf',
     'pgl_pointwise_count', 'pgl_pointwise_dev', 'pgl_pointwise',
     'pgl_rate_windows_count', 'pgl_rate_windows_dev', 'pgl_rate_windows',
     'pgl_psis_loo_dev', 'pgl_psis_loo',
@@ -62,7 +62,7 @@ SYMBOLS = [
 ]
 
 
-ABI_VERSION = 114                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
+ABI_VERSION = 115                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
 
 GEMM_NT, GEMM_MFMA_1, GEMM_MFMA_4, GEMM_KC_4_1_8, GEMM_KC_1_0_16 = range(5)   # PGL_GEMM_*: the kernel of pgl_gemm_dev
 
@@ -70,6 +70,9 @@ RW_NACC = 5                         # PGL_RW_NACC: planes of the rate-window acc
 RW_MAX_COUNT = 1024                 # PGL_RW_MAX_COUNT: the largest observed window count with a pit (more: NaN)
 RW_MAX_LAM = 700.0                  # the largest expected window count with a pit (more: NaN)
 KS_NOUT = 4                         # PGL_KS_NOUT: columns of ks_uniform's result -- D, D+, D-, n
+ACF_MAX_LAG = 64                    # PGL_ACF_MAX_LAG: the largest lag of rescale_acf
+ACF_NHEAD = 6                       # PGL_ACF_NHEAD: n, mean, c_0, Q, dof, 0 in front of r_1 .. r_L (csrc/pglm_acf.h)
+ACF_PIECE = 256                     # PGL_ACF_PIECE: the elements of a piece of its sums
 KS_TILE = 4096                      # PGL_KS_TILE: the doubles of a tile of the KS sort (csrc/pglm_gof.h)
 PSIS_NOUT = 4                       # PGL_PSIS_NOUT: planes of psis_loo's result -- elpd, khat, n_eff, tail length
 PSIS_MAX_DRAWS = 4096               # PGL_PSIS_MAX_DRAWS: the draws a workgroup's LDS holds; more: PGL_ERR_UNSUPPORTED
@@ -207,6 +210,8 @@ def load():
     lib.pgl_rescale_corr.argtypes = [vp, vp, vp, C.c_uint64, C.c_int64, vp, vp]
     lib.pgl_ks_uniform_dev.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
     lib.pgl_ks_uniform.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
+    lib.pgl_rescale_acf_dev.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int, vp, vp]
+    lib.pgl_rescale_acf.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int, vp, vp]
     lib.pgl_pointwise_count.argtypes = [vp, C.c_int, vp]
     lib.pgl_pointwise_dev.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int64]
     lib.pgl_pointwise.argtypes = [vp, vp, vp, C.c_int, vp]
@@ -760,6 +765,65 @@ class DeviceGlm(object):
         tt = t if t.size else np.zeros(1)
         _chk(self.lib.pgl_ks_uniform(self.h, _ptr(tt), _ptr(o), int(M), _ptr(ks), _ptr(z) if zsorted else None))
         return (ks, z[:t.size]) if zsorted else ks
+
+    # -- serial correlation of the normal scores of the rescaled intervals (pgl_rescale_acf*) ---------------------------
+    def rescale_acf(self, tau, run_off, seg_run, max_lag, out=None, scores=None):
+        """Lag-1 .. max_lag serial correlation of the normal scores of the segments of the torch device tensor tau (f64):
+        run_off (R + 1, int64) cuts tau into runs, seg_run (M + 1, int64) the runs into segments; pairs never cross a run
+        boundary.  -> out (M, 6 + max_lag) = n, mean, c_0, Q, dof, 0, r_1 .. r_L on tau's device, written into `out` where
+        given.  scores: True returns (out, g) with every normal score, a tensor of tau's length is written into, None uses a
+        fresh one.  Asynchronous on the handle's stream (pgl_rescale_acf_dev)."""
+        import torch
+        if not (isinstance(tau, torch.Tensor) and tau.is_cuda and tau.dtype == torch.float64 and tau.dim() == 1 and
+                tau.is_contiguous()):
+            raise ValueError("rescale_acf: tau must be a contiguous float64 device vector")
+        for name, o in (('run_off', run_off), ('seg_run', seg_run)):
+            if not (isinstance(o, torch.Tensor) and o.is_cuda and o.dtype == torch.int64 and o.dim() == 1 and
+                    o.is_contiguous() and o.numel() >= 1):
+                raise ValueError("rescale_acf: %s must be a contiguous int64 device vector" % name)
+        if seg_run.numel() < 2:
+            raise ValueError("rescale_acf: seg_run holds M + 1 >= 2 offsets")
+        L = int(max_lag)
+        if not 1 <= L <= ACF_MAX_LAG:
+            raise ValueError("rescale_acf: max_lag must lie in 1 .. %d" % ACF_MAX_LAG)
+        M = int(seg_run.numel()) - 1
+        n_tau = int(tau.numel())
+        src = tau if n_tau else torch.zeros(1, dtype=torch.float64, device=tau.device)     # (an empty tensor has no address)
+        if out is None:
+            out = torch.empty((M, ACF_NHEAD + L), dtype=torch.float64, device=tau.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and
+                  tuple(out.shape) == (M, ACF_NHEAD + L)):
+            raise ValueError("rescale_acf: out must be a contiguous float64 device tensor (%d, %d)" % (M, ACF_NHEAD + L))
+        if scores is None or scores is True:
+            g = torch.empty(max(n_tau, 1), dtype=torch.float64, device=tau.device)
+        else:
+            g = scores
+            if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == torch.float64 and g.is_contiguous() and
+                    g.numel() >= max(n_tau, 1)):
+                raise ValueError("rescale_acf: scores must be a contiguous float64 device vector of tau's length")
+        _chk(self.lib.pgl_rescale_acf_dev(self.h, C.c_void_p(src.data_ptr()), C.c_void_p(run_off.data_ptr()),
+                                          C.c_void_p(seg_run.data_ptr()), M, L, C.c_void_p(out.data_ptr()), C.c_void_p(g.data_ptr())))
+        return (out, g[:n_tau]) if scores is True else out
+
+    def rescale_acf_dev(self, d_tau, d_run_off, d_seg_run, M, max_lag, d_out, d_scores):
+        """Device-pointer form (integers): see pgl_rescale_acf_dev."""
+        _chk(self.lib.pgl_rescale_acf_dev(self.h, C.c_void_p(d_tau), C.c_void_p(d_run_off), C.c_void_p(d_seg_run), int(M),
+                                          int(max_lag), C.c_void_p(d_out), C.c_void_p(d_scores)))
+
+    def rescale_acf_host(self, tau, run_off, seg_run, max_lag, scores=False):
+        """The same with host arrays: -> out (M, 6 + max_lag), or (out, g) with scores=True (pgl_rescale_acf)."""
+        t = np.ascontiguousarray(tau, dtype=np.float64).ravel()
+        ro = np.ascontiguousarray(run_off, dtype=np.int64).ravel()
+        sr = np.ascontiguousarray(seg_run, dtype=np.int64).ravel()
+        if sr.size < 2 or sr[0] != 0 or int(sr[-1]) != ro.size - 1 or ro[0] != 0 or int(ro[-1]) != t.size:
+            raise ValueError("rescale_acf_host: seg_run (M + 1) from 0 to R, run_off (R + 1) from 0 to len(tau)")
+        M = sr.size - 1
+        out = np.empty((M, ACF_NHEAD + int(max_lag)))
+        g = np.empty(max(t.size, 1)) if scores else None
+        tt = t if t.size else np.zeros(1)
+        _chk(self.lib.pgl_rescale_acf(self.h, _ptr(tt), _ptr(ro), _ptr(sr), int(M), int(max_lag), _ptr(out),
+                                      _ptr(g) if scores else None))
+        return (out, g[:t.size]) if scores else out
 
     # -- pointwise log-likelihood of a draw, and its accumulation over draws (pgl_pointwise*) -------------
     def pointwise_count(self, block_chunks=1):

@@ -128,6 +128,7 @@ struct pgl_context {
     // the corrected intervals (pgl_rescale_corr_dev): the rate of every event's bin; pgl_ks_uniform_dev: the sorted values where
     // the caller wants none; pgl_ks_uniform: the device copies of its arrays
     DevBuf rs_qev, rs_tail, ks_work, ks_tau, ks_off, ks_out;
+    DevBuf acf_seg;                      // pgl_rescale_acf: the device copy of seg_run (the other arrays: the ks_* buffers)
     DevBuf psis_in, psis_out, psis_lw;   // pgl_psis_loo: the device copies of its host arrays
     DevBuf diag_in, diag_out;            // pgl_chain_diag: the same
     DevBuf pw_part, pw_out;              // pointwise ll (pgl_pointwise_dev): chunk sums; pgl_pointwise: the device copy of ll_blk_out
@@ -349,7 +350,7 @@ int pgl_destroy(pgl_handle h)
                       &h->spart, &h->sepC, &h->sepA, &h->sepAT, &h->sepD, &h->YfT, &h->Hb, &h->wpart, &h->QvT, &h->staA,
                       &h->Cbuf, &h->hvp_idx, &h->hvp_Weff, &h->hvp_ll, &h->hvp_v, &h->hvp_out,
                       &h->hess_part, &h->hess_out, &h->rs_pre, &h->rs_tot, &h->rs_cum, &h->rs_off, &h->rs_tau, &h->rs_stats,
-                      &h->rs_qev, &h->rs_tail, &h->ks_work, &h->ks_tau, &h->ks_off, &h->ks_out,
+                      &h->rs_qev, &h->rs_tail, &h->ks_work, &h->ks_tau, &h->ks_off, &h->ks_out, &h->acf_seg,
                       &h->pw_part, &h->pw_out, &h->rw_part, &h->rw_cnt, &h->rw_out, &h->psis_in, &h->psis_out, &h->psis_lw, &h->diag_in, &h->diag_out};
     for (DevBuf* b : bufs) release(*b);
     for (int s = 0; s < pgl_context::NEV; ++s)
@@ -1885,6 +1886,8 @@ static int enqueue_rescale(pgl_handle h, double* d_tau, const long long* d_off, 
                            unsigned long long seed = 0, long long draw = 0);
 static int enqueue_pointwise(pgl_handle h, int block_chunks, double* d_ll_blk, double* d_acc, long long draw);
 static int enqueue_rate_windows(pgl_handle h, long long win, double* d_lam, double* d_obs, double* d_acc, long long draw);
+static int enqueue_acf(pgl_handle h, const double* d_tau, const int64_t* d_run_off, const int64_t* d_seg_run, int64_t M, int max_lag,
+                       double* d_out, double* d_scores);
 
 int pgl_last_kernels(pgl_handle h, char* out, int cap)
 {
@@ -1907,7 +1910,8 @@ int pgl_last_kernels(pgl_handle h, char* out, int cap)
 // 6 the launches of pgl_rescale_dev (the forward launches of path 2, then the k_rescale_* kernels), 7 those of
 // pgl_pointwise_dev (the forward launches of path 2, then k_pw_chunk and k_pw_block), 8 those of pgl_rate_windows_dev (the
 // forward launches of path 2, then k_rw_piece and k_rw_window), 9 those of pgl_rescale_corr_dev (the forward launches of path 2,
-// then k_rcorr_chunk, k_rescale_scan and k_rcorr_finish).
+// then k_rcorr_chunk, k_rescale_scan and k_rcorr_finish), 10 the launch of pgl_rescale_acf_dev alone (no forward pass: the
+// shape is ignored).
 int pgl_plan_kernels(int N, int B, int R, int Dstim, long long nT, int stim, int n_lo, int count, int path, int opt_kernel,
                      int opt_f32, char* out, int cap)
 {
@@ -1939,7 +1943,8 @@ int pgl_plan_kernels(int N, int B, int R, int Dstim, long long nT, int stim, int
         }
     } else {
         g_dry = &names;
-        rc = (path == 2 || path == 6 || path == 7 || path == 8 || path == 9) ? enqueue_gibbs_forward(&c)
+        rc = (path == 10) ? enqueue_acf(&c, &dummy, nullptr, nullptr, 1, 1, &dummy, &dummy)
+           : (path == 2 || path == 6 || path == 7 || path == 8 || path == 9) ? enqueue_gibbs_forward(&c)
                          : enqueue_ll_grad(&c, n_lo, n_lo + count, nullptr, nullptr, &dummy, path == 0 ? &dummy : nullptr);
     }
     if (rc == PGL_OK && path == 6) rc = enqueue_rescale(&c, &dummy, nullptr, &dummy);
@@ -3007,6 +3012,60 @@ int pgl_ks_uniform(pgl_handle h, const double* tau, const int64_t* off, int64_t 
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(ks_out, h->ks_out.p, (size_t)M * PGL_KS_NOUT * 8, hipMemcpyDeviceToHost, h->stream));
     if (zsorted_out && total) HIPCHK(hipMemcpyAsync(zsorted_out, h->ks_work.p, total * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return PGL_OK;
+}
+
+// ---- the serial correlation of the normal scores of segmented, run-structured intervals (pglm_acf.h, pglm_acf.hip.h) ------
+static int enqueue_acf(pgl_handle h, const double* d_tau, const int64_t* d_run_off, const int64_t* d_seg_run, int64_t M, int max_lag,
+                       double* d_out, double* d_scores)
+{
+    AcfParams p;
+    p.tau = d_tau; p.run_off = (const long long*)d_run_off; p.seg_run = (const long long*)d_seg_run;
+    p.scores = d_scores; p.out = d_out; p.L = max_lag;
+    return launch_behind(h, "k_acf_segment", k_acf_segment, (unsigned)M, PGL_ACF_THREADS, p);
+}
+
+int pgl_rescale_acf_dev(pgl_handle h, const double* d_tau, const int64_t* d_run_off, const int64_t* d_seg_run, int64_t M,
+                        int max_lag, double* d_out, double* d_scores)
+{
+    if (!h) return fail(PGL_ERR_ARG, "null handle");
+    if (!d_tau || !d_run_off || !d_seg_run || !d_out || !d_scores) return fail(PGL_ERR_ARG, "null argument");
+    if (M < 1 || M > 0x7fffffff) return fail(PGL_ERR_ARG, "pgl_rescale_acf_dev: M must lie in 1 .. 2^31 - 1");
+    if (max_lag < 1 || max_lag > PGL_ACF_MAX_LAG) return fail(PGL_ERR_ARG, "pgl_rescale_acf_dev: max_lag must lie in 1 .. 64");
+    HIPCHK(hipSetDevice(h->device));
+    return enqueue_acf(h, d_tau, d_run_off, d_seg_run, M, max_lag, d_out, d_scores);
+}
+
+int pgl_rescale_acf(pgl_handle h, const double* tau, const int64_t* run_off, const int64_t* seg_run, int64_t M, int max_lag,
+                    double* out, double* scores_out)
+{
+    if (!h) return fail(PGL_ERR_ARG, "null handle");
+    if (!tau || !run_off || !seg_run || !out) return fail(PGL_ERR_ARG, "null argument");
+    if (M < 1 || M > 0x7fffffff) return fail(PGL_ERR_ARG, "pgl_rescale_acf: M must lie in 1 .. 2^31 - 1");
+    if (max_lag < 1 || max_lag > PGL_ACF_MAX_LAG) return fail(PGL_ERR_ARG, "pgl_rescale_acf: max_lag must lie in 1 .. 64");
+    if (seg_run[0] < 0) return fail(PGL_ERR_ARG, "pgl_rescale_acf: offsets must not decrease");
+    for (int64_t m = 0; m < M; ++m)
+        if (seg_run[m + 1] < seg_run[m]) return fail(PGL_ERR_ARG, "pgl_rescale_acf: offsets must not decrease");
+    const int64_t R = seg_run[M];
+    if (run_off[0] < 0) return fail(PGL_ERR_ARG, "pgl_rescale_acf: offsets must not decrease");
+    for (int64_t r = 0; r < R; ++r)
+        if (run_off[r + 1] < run_off[r]) return fail(PGL_ERR_ARG, "pgl_rescale_acf: offsets must not decrease");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t total = (size_t)run_off[R], tb = std::max<size_t>(total, 1) * 8, ob = (size_t)M * (PGL_ACF_NHEAD + max_lag) * 8;
+    ENSURE(h->ks_tau, tb);
+    ENSURE(h->ks_work, tb);
+    ENSURE(h->ks_off, ((size_t)R + 1) * 8);
+    ENSURE(h->acf_seg, ((size_t)M + 1) * 8);
+    ENSURE(h->ks_out, ob);
+    if (total) HIPCHK(hipMemcpyAsync(h->ks_tau.p, tau, total * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->ks_off.p, run_off, ((size_t)R + 1) * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->acf_seg.p, seg_run, ((size_t)M + 1) * 8, hipMemcpyHostToDevice, h->stream));
+    int rc = pgl_rescale_acf_dev(h, (const double*)h->ks_tau.p, (const int64_t*)h->ks_off.p, (const int64_t*)h->acf_seg.p, M, max_lag,
+                                 (double*)h->ks_out.p, (double*)h->ks_work.p);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(out, h->ks_out.p, ob, hipMemcpyDeviceToHost, h->stream));
+    if (scores_out && total) HIPCHK(hipMemcpyAsync(scores_out, h->ks_work.p, total * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return PGL_OK;
 }

@@ -109,21 +109,22 @@ PGL_DIAG_FN double pgl_diag_lerp(double a, double b, double g)
     return g < 0.5 ? fma(d, g, a) : fma(-d, 1.0 - g, b);
 }
 
-// ---- the normal score of an average rank r among S (AS 241, PPND16) -----------------------------------------------------
-PGL_DIAG_FN double pgl_diag_score(double r, double S)
+// ---- the normal score (AS 241, PPND16) -------------------------------------------------------------------------------------
+// The two branches of PPND16 in their probability-argument form, shared with the normal scores of pglm_acf.h: the centred
+// probability q = p - 1/2 with |q| <= 0.425, and the probability pt of the nearer tail (the magnitude of the quantile).
+PGL_DIAG_FN double pgl_ppnd16_central(double q)
 {
-    const double d = S + 0.25, q = (r - 0.5 * (S + 1.0)) / d;
-    if (fabs(q) <= 0.425) {
-        const double u = 0.180625 - q * q;
-        const double num = (((((((2.5090809287301226727e3 * u + 3.3430575583588128105e4) * u + 6.7265770927008700853e4) * u +
-                                4.5921953931549871457e4) * u + 1.3731693765509461125e4) * u + 1.9715909503065514427e3) * u +
-                             1.3314166789178437745e2) * u + 3.3871328727963666080e0);
-        const double den = (((((((5.2264952788528545610e3 * u + 2.8729085735721942674e4) * u + 3.9307895800092710610e4) * u +
-                                2.1213794301586595867e4) * u + 5.3941960214247511077e3) * u + 6.8718700749205790830e2) * u +
-                             4.2313330701600911252e1) * u + 1.0);
-        return q * num / den;
-    }
-    const double pt = q < 0.0 ? (r - 0.375) / d : (S - r + 0.625) / d;       // the probability of the nearer tail
+    const double u = 0.180625 - q * q;
+    const double num = (((((((2.5090809287301226727e3 * u + 3.3430575583588128105e4) * u + 6.7265770927008700853e4) * u +
+                            4.5921953931549871457e4) * u + 1.3731693765509461125e4) * u + 1.9715909503065514427e3) * u +
+                         1.3314166789178437745e2) * u + 3.3871328727963666080e0);
+    const double den = (((((((5.2264952788528545610e3 * u + 2.8729085735721942674e4) * u + 3.9307895800092710610e4) * u +
+                            2.1213794301586595867e4) * u + 5.3941960214247511077e3) * u + 6.8718700749205790830e2) * u +
+                         4.2313330701600911252e1) * u + 1.0);
+    return q * num / den;
+}
+PGL_DIAG_FN double pgl_ppnd16_tail(double pt)
+{
     double u = sqrt(-log(pt)), v;
     if (u <= 5.0) {
         u -= 1.6;
@@ -144,6 +145,16 @@ PGL_DIAG_FN double pgl_diag_score(double r, double S)
                              5.99832206555887937690e-1) * u + 1.0);
         v = num / den;
     }
+    return v;
+}
+
+// the normal score of an average rank r among S
+PGL_DIAG_FN double pgl_diag_score(double r, double S)
+{
+    const double d = S + 0.25, q = (r - 0.5 * (S + 1.0)) / d;
+    if (fabs(q) <= 0.425) return pgl_ppnd16_central(q);
+    const double pt = q < 0.0 ? (r - 0.375) / d : (S - r + 0.625) / d;       // the probability of the nearer tail
+    const double v = pgl_ppnd16_tail(pt);
     return q < 0.0 ? -v : v;
 }
 

@@ -42,7 +42,8 @@
 // folded over the draws the same way (k_rw_piece, k_rw_window, pglm_ratewin.hip.h).
 // The goodness of fit is finished on the device: the discrete-time correction of the event bin's term in the rescaled
 // intervals, and the KS distance of every neuron's intervals by a sorting network, one workgroup per segment (k_rcorr_*,
-// k_ks_segment, pglm_gof.hip.h).
+// k_ks_segment, pglm_gof.hip.h); the independence of those intervals -- the serial correlation of their normal scores, lag by
+// lag, with run boundaries between the data sequences -- is one workgroup per segment as well (k_acf_segment, pglm_acf.hip.h).
 // PSIS-LOO takes the matrix of those terms over the draws one column per workgroup: ranks, generalized-Pareto fit, smoothed
 // weights (k_psis_column, pglm_psis.hip.h).
 // The samplers' draws are judged the same way, one column of (chains x draws) per workgroup: ranks by counting, normal scores,
@@ -74,6 +75,7 @@
 #include "pglm_binwalk.hip.h"
 #include "pglm_rescale.hip.h"
 #include "pglm_gof.hip.h"
+#include "pglm_acf.hip.h"
 #include "pglm_pointwise.hip.h"
 #include "pglm_ratewin.hip.h"
 #include "pglm_psis.hip.h"

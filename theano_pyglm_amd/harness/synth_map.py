@@ -11,7 +11,8 @@ lock-step Newton-CG optimizer on device Hessian-vector products (inference/batch
 status, iterations and the number of non-zero presynaptic groups per neuron.
 --gof prints the time-rescaling KS table of the fitted model (inference/gof.py) after the fit; --gof-correct applies the
 discrete-time correction to it (a random function of its seed, 0).  With --hmc N or --nuts N, --gof-draws prints the KS
-distance over the posterior draws per neuron (corrected; sorted and tested on the device).
+distance over the posterior draws per neuron (corrected; sorted and tested on the device).  --gof-lags L adds the independence
+table (serial correlation of the normal scores at the lags 1 .. L, inference/gof.py) behind either.
 --ppc N prints the predictive spike-count table of N replicates simulated from the fitted model (inference/predictive.py).
 --hmc N draws N posterior samples of every neuron's parameters from the fit by lock-step HMC on the device
 (inference/batched_hmc.py) and prints the bias posterior mean +- sd per neuron, beside the Laplace standard error when
@@ -63,7 +64,7 @@ def initialize_test_harness(model_name, data, data_dir=None):
 
 def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False, gof=False, ppc=0, hmc=0, ais=0,
                    hmc_mass='laplace', prox=False, laplace_device=False, ais_mass='laplace', nuts=0, smc=0, newton=False, waic=False, loo=False, diag=False, rates=0,
-                   gof_correct=False, gof_draws=False):
+                   gof_correct=False, gof_draws=False, gof_lags=0):
     """test/synth_map.py:10-32."""
     popn, popn_true, x_true = initialize_test_harness(model_name, data, data_dir)
     x0 = popn.sample(rng)
@@ -81,13 +82,16 @@ def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, r
     if gof:
         from theano_pyglm_amd.inference.gof import ks_time_rescaling, format_table
         print(format_table(ks_time_rescaling(popn, x_inf, correct=True) if gof_correct else ks_time_rescaling(popn, x_inf)))
+        if gof_lags:
+            from theano_pyglm_amd.inference.gof import independence_time_rescaling, format_independence_table
+            print(format_independence_table(independence_time_rescaling(popn, x_inf, max_lag=gof_lags, correct=gof_correct)))
     if ppc:
         from theano_pyglm_amd.inference import predictive
         print(predictive.format_table(predictive.predictive_counts(popn, x_inf, ppc)))
     if hmc:
-        print(hmc_bias_table(popn, x_inf, hmc, hmc_mass, laplace_device, waic=waic, loo=loo, diag=diag, rates=rates, gof_draws=gof_draws))
+        print(hmc_bias_table(popn, x_inf, hmc, hmc_mass, laplace_device, waic=waic, loo=loo, diag=diag, rates=rates, gof_draws=gof_draws, gof_lags=gof_lags))
     if nuts:
-        print(nuts_bias_table(popn, x_inf, nuts, hmc_mass, laplace_device, waic=waic, loo=loo, diag=diag, rates=rates, gof_draws=gof_draws))
+        print(nuts_bias_table(popn, x_inf, nuts, hmc_mass, laplace_device, waic=waic, loo=loo, diag=diag, rates=rates, gof_draws=gof_draws, gof_lags=gof_lags))
     if ais:
         print(ais_evidence_table(popn, x_inf, ais, laplace_device, ais_mass))
     if smc:
@@ -110,7 +114,7 @@ def prox_table(popn, x):
 
 
 def hmc_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=False, loo=False, diag=False, rates=0,
-                   gof_draws=False):
+                   gof_draws=False, gof_lags=0):
     """n_draws kept HMC draws from x with the mass matrix `mass` ('laplace' or 'laplace_dense'): one line per neuron, bias
     posterior mean +- sd (and the Laplace standard error).  laplace_device: the Laplace factorisations (the dense mass
     matrix and the standard errors) run on the device.  waic / loo: the WAIC / PSIS-LOO table of the draws follows (waic_table, loo_table); diag: the convergence table
@@ -134,7 +138,7 @@ def hmc_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=
                                                           res['step_sz'][n])
         lines.append(ln + ("   %10.4f" % se[n] if se is not None else ""))
     if gof_draws:
-        lines.append(gof_draws_table(popn, x, res['samples']))
+        lines.append(gof_draws_table(popn, x, res['samples'], gof_lags))
     if waic:
         lines.append(waic_table(popn, x, res['samples']))
     if loo:
@@ -148,7 +152,7 @@ def hmc_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=
 
 
 def nuts_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=False, loo=False, diag=False, rates=0,
-                    gof_draws=False, **kw):
+                    gof_draws=False, gof_lags=0, **kw):
     """hmc_bias_table with the No-U-Turn sampler: the same columns ('accept' is the mean acceptance statistic after
     warm-up) plus the median tree depth of the kept transitions and the divergent transitions after warm-up.  kw: further
     arguments of sample_glms_nuts (n_warmup, max_depth, ...).  waic / loo: the WAIC / PSIS-LOO table of the draws follows (waic_table, loo_table); diag: the convergence table
@@ -176,7 +180,7 @@ def nuts_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic
                                                                     res['divergent'][n])
         lines.append(ln + ("   %10.4f" % se[n] if se is not None else ""))
     if gof_draws:
-        lines.append(gof_draws_table(popn, x, res['samples']))
+        lines.append(gof_draws_table(popn, x, res['samples'], gof_lags))
     if waic:
         lines.append(waic_table(popn, x, res['samples']))
     if loo:
@@ -198,12 +202,18 @@ def rates_table(popn, x, samples, win):
     return predictive.format_rate_table(res) + "\n(rate bands of %d draws in %.2f s)" % (res['n_draws'], time.time() - t0)
 
 
-def gof_draws_table(popn, x, samples):
-    """The time-rescaling KS distance over posterior draws (samples (S, N, P) of all neurons), discrete-time corrected."""
+def gof_draws_table(popn, x, samples, gof_lags=0):
+    """The time-rescaling KS distance over posterior draws (samples (S, N, P) of all neurons), discrete-time corrected; with
+    gof_lags the independence statistic of the same draws behind it."""
     from theano_pyglm_amd.inference import gof
     t0 = time.time()
     res = gof.ks_time_rescaling_draws(popn, x, samples)
-    return gof.format_draws_table(res) + "\n(KS distance of %d draws in %.2f s)" % (res['n_draws'], time.time() - t0)
+    out = gof.format_draws_table(res) + "\n(KS distance of %d draws in %.2f s)" % (res['n_draws'], time.time() - t0)
+    if gof_lags:
+        t0 = time.time()
+        ind = gof.independence_time_rescaling_draws(popn, x, samples, max_lag=gof_lags)
+        out += "\n" + gof.format_independence_draws_table(ind) + "\n(serial correlation of %d draws in %.2f s)" % (ind['n_draws'], time.time() - t0)
+    return out
 
 
 def waic_table(popn, x, samples, block_chunks=40):
@@ -284,6 +294,10 @@ def parser():
     ap.add_argument('--gof-correct', action='store_true',
                     help='with --gof: apply the discrete-time correction of Haslinger et al. (2010); the table is then a random '
                          'function of the seed (0)')
+    ap.add_argument('--gof-lags', type=int, default=0, metavar='L',
+                    help='with --gof: the independence table as well -- serial correlation of the normal scores of the rescaled '
+                         'intervals at the lags 1 .. L (at most 64) and the portmanteau p-value; honours --gof-correct; with '
+                         '--gof-draws the same over the posterior draws')
     ap.add_argument('--gof-draws', action='store_true',
                     help='with --hmc N / --nuts N: the time-rescaling KS distance of every posterior draw (corrected), sorted and '
                          'tested on the device; prints mean, 5 %% and 95 %% quantiles and the share of draws inside the band')
@@ -332,7 +346,7 @@ def main(argv=None):
                    False if args.sequential else ('torch' if args.newton_cg else None), use_rop=args.newton_cg, gof=args.gof, ppc=args.ppc, hmc=args.hmc, ais=args.ais,
                    hmc_mass=args.hmc_mass, prox=args.prox, laplace_device=args.laplace_device, ais_mass=args.ais_mass, nuts=args.nuts, smc=args.smc,
                    newton=args.newton, waic=args.waic, loo=args.loo, diag=args.diag, rates=args.rates,
-                   gof_correct=args.gof_correct, gof_draws=args.gof_draws)
+                   gof_correct=args.gof_correct, gof_draws=args.gof_draws, gof_lags=args.gof_lags)
 
 
 if __name__ == '__main__':
