@@ -210,3 +210,31 @@ def test_resolve_mass_laplace_routes(monkeypatch):
         minv, factor, dense_rows, _ = B.resolve_mass(popn, 'x', 'laplace_dense', 1, 4, 1e-6, factor_on_device=on_device)
         assert minv is None and factor is W and dense_rows is rows
     assert calls == [('minv', 'x', 1, 4, 1e-6), ('host', 'x', 1, 4, 1e-6), ('device', 'x', 1, 4, 1e-6)]
+
+
+# ---- the guarded line-search step (csrc/pglm_linesearch.h: pgl_ls_guarded_step) -----------------------------------
+REACH = ('converged', 'warning: take the trial', 'warning: take the best step', 'warning: fail',
+         'cut off by max_trials as the trial became the best step', 'non-finite f', 'non-finite dphi')
+
+
+@pytest.mark.parametrize('constants', [0, 1], ids=['newton-cg/newton', 'bfgs'])
+def test_guarded_step_direct_and_wrappers_agree(constants, tmp_path):
+    """Scripted searches on a quartic and on a function with a kink (tests/csrc/ls_guarded_host.c, built by gcc): on every
+    call the direct pgl_ls_guarded_step, the Newton-CG wrapper and the dense Newton wrapper agree on the decision, on the
+    step length and value of the point taken and on all 18 doubles of the line-search state; every way a search can end
+    is reached, and each search ends the way its script says."""
+    import ctypes
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    so = str(tmp_path / 'ls_guarded_host.so')
+    subprocess.check_call(['gcc', '-O2', '-Wall', '-Wextra', '-Werror', '-shared', '-fPIC', '-o', so,
+                           os.path.join(root, 'tests', 'csrc', 'ls_guarded_host.c'), '-lm'])
+    lib = ctypes.CDLL(so)
+    assert lib.lsg_nreach() == len(REACH)
+    reached = (ctypes.c_int * len(REACH))()
+    rc = lib.lsg_run(constants, reached)
+    assert rc == 0, "case %d: check %d failed" % (rc // 100 - 1, rc % 100)
+    missing = [name for name, n in zip(REACH, reached) if n == 0]
+    assert not missing, missing
+    assert sum(reached) == lib.lsg_ncases()

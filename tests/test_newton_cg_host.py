@@ -353,7 +353,7 @@ def test_ncg_symbols_version_and_kernels():
     sys.path.insert(0, os.path.join(ROOT, 'tools'))
     import reachable_kernels as RK
     built = RK.built_fused()
-    mine = dict((n, r) for n, r in built.items() if n.startswith('k_ncg_'))
+    mine = dict((n, r) for n, r in built.items() if n.startswith('k_ncg_') or n == 'k_row_trial')  # (the trial kernel is shared)
     assert len(mine) >= 4, sorted(mine)
     for n, r in mine.items():
         assert r['scratch'] == 0 and r['spill_vgpr'] == 0, (n, r)

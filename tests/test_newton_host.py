@@ -278,8 +278,8 @@ def test_newton_symbols_layout_and_kernels():
     sys.path.insert(0, os.path.join(ROOT, 'tools'))
     import reachable_kernels as RK
     built = RK.built_fused()
-    mine = dict((n, r) for n, r in built.items() if n.startswith('k_newton_') or n == 'k_chol_solve')
+    mine = dict((n, r) for n, r in built.items() if n.startswith('k_newton_') or n in ('k_chol_solve', 'k_row_trial'))
     assert sorted(mine) == ['k_chol_solve', 'k_newton_assemble', 'k_newton_direction', 'k_newton_init',
-                            'k_newton_search_step', 'k_newton_trial'], sorted(mine)
+                            'k_newton_search_step', 'k_row_trial'], sorted(mine)  # (k_row_trial: shared with Newton-CG)
     for n, r in mine.items():
         assert r['scratch'] == 0 and r['spill_vgpr'] == 0, (n, r)

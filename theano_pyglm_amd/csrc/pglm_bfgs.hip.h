@@ -251,47 +251,35 @@ __device__ __forceinline__ void pgl_bfgs_linesearch_row(const BfgsView& v, const
         const int r = rv;
         PglLs s;
         pgl_ls_load(v, r, &s);
-        const double stp = s.stp, stx_prev = s.stx;
         const double f = *ftj;
         // an infinite objective or slope ends the search like scipy's ("WARN": its fallback search fails on inf as well);
-        // NaN never arrives here (fit_glm's rule: 1e16 and a zero gradient, applied by the objective)
-        int rc = PGL_LS_WARNING;
-        if (f - f == 0.0 && dp - dp == 0.0)
-            rc = pgl_ls_step(&s, f, dp, PGL_LS_FTOL, PGL_LS_GTOL, PGL_LS_XTOL, PGL_LS_STPMIN, PGL_LS_STPMAX);
-        else s.moved = 0.0;
-        if (rc == PGL_LS_EVALUATE && s.nfev >= (double)max_trials) rc = PGL_LS_WARNING;
-        int src = 0;                                         // 1: take the trial, 2: take the saved best step
+        // NaN never arrives here (fit_glm's rule: 1e16 and a zero gradient, applied by the objective).
+        // (Xb / gb / fb hold the best step BEFORE this call: they are only overwritten on EVALUATE)
+        double alpha_acc, facc;                              // (not kept: the row moves to a saved point)
+        const int d = pgl_ls_guarded_step(&s, f, dp, v.fb[r], PGL_LS_FTOL, PGL_LS_GTOL, PGL_LS_XTOL, PGL_LS_STPMIN,
+                                          PGL_LS_STPMAX, max_trials, &alpha_acc, &facc);
         const int moved = s.moved != 0.0;
-        if (rc == PGL_LS_CONVERGED) src = 1;
-        else if (rc == PGL_LS_WARNING) {
-            // (Xb / gb / fb still hold the best step BEFORE this call -- they are only overwritten on EVALUATE -- and
-            //  stx_prev is its step length: s.stx is the trial's when it has just become the best step)
-            const bool okT = stp > 0.0 && f <= s.finit + stp * s.gtest && f < s.finit;
-            const bool okB = stx_prev > 0.0 && v.fb[r] <= s.finit + stx_prev * s.gtest && v.fb[r] < s.finit;
-            if (okT && (!okB || f <= v.fb[r])) src = 1;
-            else if (okB) src = 2;
-            if (src == 0) v.stall[r] = 1.0;
-        } else {
+        if (d == PGL_LS_EVALUATE) {
             pgl_ls_store(v, r, &s);
             v.alpha[r] = s.stp;
             if (moved) v.fb[r] = f;
-        }
+        } else if (d == PGL_LS_FAIL) v.stall[r] = 1.0;
         v.nfev[r] += 1.0;
-        dec[0] = rc; dec[1] = src; dec[2] = moved;
+        dec[0] = d; dec[1] = moved;
     }
     __syncthreads();
-    const int rc = dec[0], src = dec[1];
-    if (rc == PGL_LS_EVALUATE) {
-        if (dec[2])                                          // the trial is the best step so far: keep its point and gradient
+    const int src = dec[0];                                  // PGL_LS_TAKE_TRIAL: the trial, PGL_LS_TAKE_BEST: the saved best step
+    if (src == PGL_LS_EVALUATE) {
+        if (dec[1])                                          // the trial is the best step so far: keep its point and gradient
             for (int c = pgl_row_c0(tid, P); c < P; c += 256) {
                 v.Xb[o + c] = xt[c];
                 v.gb[o + c] = gt[c];
             }
         return;
     }
-    if (src == 0) return;
-    const double* xs = src == 1 ? xt : v.Xb + o;
-    const double* gs = src == 1 ? gt : v.gb + o;
+    if (src == PGL_LS_FAIL) return;
+    const double* xs = src == PGL_LS_TAKE_TRIAL ? xt : v.Xb + o;
+    const double* gs = src == PGL_LS_TAKE_TRIAL ? gt : v.gb + o;
     double sy = 0.0;
     for (int c = pgl_row_c0(tid, P); c < P; c += 256) {
         const double xn = xs[c], gn = gs[c];
@@ -304,7 +292,7 @@ __device__ __forceinline__ void pgl_bfgs_linesearch_row(const BfgsView& v, const
     }
     sy = pgl_blk_sum(sy, red);
     if (tid == 0) {
-        const double fn = src == 1 ? *ftj : v.fb[r];
+        const double fn = src == PGL_LS_TAKE_TRIAL ? *ftj : v.fb[r];
         v.fprev[r] = v.f[r];
         v.f[r] = fn;
         v.acc[r] = 1.0;
@@ -697,7 +685,7 @@ template <int NT>
 __global__ __launch_bounds__(NT) void k_bfgs_step(const BfgsView v, const BfgsStepArgs a)
 {
     __shared__ double red[12];
-    __shared__ int dec[3];
+    __shared__ int dec[2];
     __shared__ double part[(NT >= 512) ? NT / 64 : 1][64];
     const int j = blockIdx.x, r = a.rows ? a.rows[j] : j, tid = threadIdx.x, P = v.P;
     if (a.phases & PGL_STEP_LS) {

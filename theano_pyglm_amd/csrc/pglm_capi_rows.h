@@ -111,6 +111,8 @@ int pgl_bfgs_update_dev(pgl_handle h, double* d_state, int M, int P, double gtol
 // the address the device uses for a buffer of pinned host memory that a row kernel writes its flags into (looked up once)
 static int flags_device_pointer(pgl_handle h, double* flags_out, double** flags_dev)
 {
+    *flags_dev = nullptr;
+    if (!flags_out) return PGL_OK;                             // (optional everywhere: no flags wanted)
     for (int i = 0; i < 4; ++i)
         if (h->flags_host[i] == flags_out) {
             *flags_dev = h->flags_dev[i];
@@ -147,8 +149,8 @@ int pgl_bfgs_step_dev(pgl_handle h, double* d_state, int M, int P, const int* d_
     if (d_H && (ld < P || (ld & 1) || (reinterpret_cast<uintptr_t>(d_H) & 15)))
         return fail(PGL_ERR_ARG, "H: leading dimension even and >= P, base 16-byte aligned");
     HIPCHK(hipSetDevice(h->device));
-    double* flags_dev = nullptr;
-    if (flags_out && flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
+    double* flags_dev;
+    if (flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
     const BfgsView v = pgl_bfgs_view(d_state, M, P);
     a.rows = d_rows; a.Xt = d_Xt; a.ft = d_ll_f; a.gt = d_grad_g;
     a.have_prior = prior->kind >= 0 ? 1 : 0;
@@ -193,8 +195,8 @@ int pgl_ncg_init_dev(pgl_handle h, double* d_state, int M, int P, double* d_ll, 
     int rc = fill_prior(h, P, prior, q);
     if (rc) return rc;
     HIPCHK(hipSetDevice(h->device));
-    double* flags_dev = nullptr;
-    if (flags_out && flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
+    double* flags_dev;
+    if (flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
     return launch_rows(h, k_ncg_init, M, pgl_ncg_view(d_state, M, P), d_ll, d_grad, q, maxiter, d_V, flags_dev);
 }
 
@@ -206,34 +208,53 @@ int pgl_ncg_cg_step_dev(pgl_handle h, double* d_state, int M, int P, double* d_h
     int rc = fill_prior(h, P, prior, q);
     if (rc) return rc;
     HIPCHK(hipSetDevice(h->device));
-    double* flags_dev = nullptr;
-    if (flags_out && flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
+    double* flags_dev;
+    if (flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
     return launch_rows(h, k_ncg_cg_step, M, pgl_ncg_view(d_state, M, P), d_hv, q, d_V, flags_dev);
+}
+
+// what both optimisers' trial and search-step launches check and fill (pglm_rowsearch.hip.h)
+static int row_trial(pgl_handle h, const double* X, const double* d, const double* sc, int f_alpha, int f_phase, int M, int P,
+                     const int* d_rows, int L, double* d_Xt)
+{
+    if (!h || !X || !d_Xt || M <= 0 || P <= 0 || L <= 0 || L > M) return fail(PGL_ERR_ARG, "bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    return launch_rows(h, k_row_trial, L, X, d, sc + (size_t)f_alpha * M, sc + (size_t)f_phase * M, P, d_rows, d_Xt);
+}
+
+static int row_search_args(pgl_handle h, const double* d_state, int M, int P, const int* d_rows, int L, const double* d_Xt,
+                           double* d_ll_f, double* d_grad_g, const pgl_prior* prior, int maxiter, const int* d_pos_next,
+                           double* d_Xt_next, double* flags_out, RowSearchArgs& a)
+{
+    if (!h || !d_state || !d_Xt || !d_ll_f || !d_grad_g || M <= 0 || P <= 0 || L <= 0 || L > M)
+        return fail(PGL_ERR_ARG, "bad argument");
+    if (d_Xt_next == d_Xt) return fail(PGL_ERR_ARG, "the next trial points need a buffer of their own");
+    memset(&a, 0, sizeof(a));
+    int rc = fill_prior(h, P, prior, a.q);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    if (flags_device_pointer(h, flags_out, &a.flags)) return PGL_ERR_ARG;
+    a.rows = d_rows; a.Xt = d_Xt; a.ft = d_ll_f; a.gt = d_grad_g; a.maxiter = maxiter;
+    a.pos_next = d_pos_next; a.Xt_next = d_Xt_next;
+    return PGL_OK;
 }
 
 int pgl_ncg_trial_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, double* d_Xt)
 {
-    if (!h || !d_state || !d_Xt || M <= 0 || P <= 0 || L <= 0 || L > M) return fail(PGL_ERR_ARG, "bad argument");
-    HIPCHK(hipSetDevice(h->device));
-    return launch_rows(h, k_ncg_trial, L, pgl_ncg_view(d_state, M, P), d_rows, d_Xt);
+    const NcgView v = pgl_ncg_view(d_state, M, P);
+    return row_trial(h, d_state, v.xs, v.sc, PGL_NCG_F_ALPHA, PGL_NCG_F_PHASE, M, P, d_rows, L, d_Xt);
 }
 
 int pgl_ncg_search_step_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, const double* d_Xt,
                             double* d_ll_f, double* d_grad_g, const pgl_prior* prior, int maxiter, const int* d_pos_next,
                             double* d_Xt_next, double* d_V, double* flags_out)
 {
-    if (!h || !d_state || !d_Xt || !d_ll_f || !d_grad_g || !d_V || M <= 0 || P <= 0 || L <= 0 || L > M)
-        return fail(PGL_ERR_ARG, "bad argument");
-    if (d_Xt_next == d_Xt) return fail(PGL_ERR_ARG, "the next trial points need a buffer of their own");
-    NcgSearchArgs a;
-    memset(&a, 0, sizeof(a));
-    int rc = fill_prior(h, P, prior, a.q);
+    if (!d_V) return fail(PGL_ERR_ARG, "bad argument");
+    RowSearchArgs a;
+    int rc = row_search_args(h, d_state, M, P, d_rows, L, d_Xt, d_ll_f, d_grad_g, prior, maxiter, d_pos_next, d_Xt_next,
+                             flags_out, a);
     if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    double* flags_dev = nullptr;
-    if (flags_out && flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
-    a.rows = d_rows; a.Xt = d_Xt; a.ft = d_ll_f; a.gt = d_grad_g; a.maxiter = maxiter;
-    a.pos_next = d_pos_next; a.Xt_next = d_Xt_next; a.V = d_V; a.flags = flags_dev;
+    a.V = d_V;
     return launch_rows(h, k_ncg_search_step, L, pgl_ncg_view(d_state, M, P), a);
 }
 
@@ -354,8 +375,8 @@ int pgl_newton_init_dev(pgl_handle h, double* d_state, int M, int P, double* d_l
     int rc = fill_prior(h, P, prior, q);
     if (rc) return rc;
     HIPCHK(hipSetDevice(h->device));
-    double* flags_dev = nullptr;
-    if (flags_out && flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
+    double* flags_dev;
+    if (flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
     return launch_rows(h, k_newton_init, M, pgl_newton_view(d_state, M, P), d_ll, d_grad, q, gtol, maxiter, flags_dev);
 }
 
@@ -375,34 +396,26 @@ int pgl_newton_direction_dev(pgl_handle h, double* d_state, int M, int P, const 
 {
     if (!h || !d_state || !d_info || !d_p || M <= 0 || P <= 0 || L <= 0 || L > M) return fail(PGL_ERR_ARG, "bad argument");
     HIPCHK(hipSetDevice(h->device));
-    double* flags_dev = nullptr;
-    if (flags_out && flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
+    double* flags_dev;
+    if (flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
     return launch_rows(h, k_newton_direction, L, pgl_newton_view(d_state, M, P), d_rows, d_info, d_p, flags_dev);
 }
 
 int pgl_newton_trial_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, double* d_Xt)
 {
-    if (!h || !d_state || !d_Xt || M <= 0 || P <= 0 || L <= 0 || L > M) return fail(PGL_ERR_ARG, "bad argument");
-    HIPCHK(hipSetDevice(h->device));
-    return launch_rows(h, k_newton_trial, L, pgl_newton_view(d_state, M, P), d_rows, d_Xt);
+    const NewtonView v = pgl_newton_view(d_state, M, P);
+    return row_trial(h, d_state, v.p, v.sc, PGL_NEWTON_F_ALPHA, PGL_NEWTON_F_PHASE, M, P, d_rows, L, d_Xt);
 }
 
 int pgl_newton_search_step_dev(pgl_handle h, double* d_state, int M, int P, const int* d_rows, int L, const double* d_Xt,
                                double* d_ll_f, double* d_grad_g, const pgl_prior* prior, double gtol, int maxiter,
                                const int* d_pos_next, double* d_Xt_next, double* flags_out)
 {
-    if (!h || !d_state || !d_Xt || !d_ll_f || !d_grad_g || M <= 0 || P <= 0 || L <= 0 || L > M)
-        return fail(PGL_ERR_ARG, "bad argument");
-    if (d_Xt_next == d_Xt) return fail(PGL_ERR_ARG, "the next trial points need a buffer of their own");
-    NewtonSearchArgs a;
-    memset(&a, 0, sizeof(a));
-    int rc = fill_prior(h, P, prior, a.q);
+    RowSearchArgs a;
+    int rc = row_search_args(h, d_state, M, P, d_rows, L, d_Xt, d_ll_f, d_grad_g, prior, maxiter, d_pos_next, d_Xt_next,
+                             flags_out, a);
     if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    double* flags_dev = nullptr;
-    if (flags_out && flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
-    a.rows = d_rows; a.Xt = d_Xt; a.ft = d_ll_f; a.gt = d_grad_g; a.gtol = gtol; a.maxiter = maxiter;
-    a.pos_next = d_pos_next; a.Xt_next = d_Xt_next; a.flags = flags_dev;
+    a.gtol = gtol;
     return launch_rows(h, k_newton_search_step, L, pgl_newton_view(d_state, M, P), a);
 }
 
@@ -800,8 +813,8 @@ static int prox_args(pgl_handle h, double* d_state, int M, int P, double* d_ll, 
     if (rc) return rc;
     a.q.lam = 0.0;                                             // the per-row d_lam rules
     HIPCHK(hipSetDevice(h->device));
-    double* flags_dev = nullptr;
-    if (flags_out && flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
+    double* flags_dev;
+    if (flags_device_pointer(h, flags_out, &flags_dev)) return PGL_ERR_ARG;
     a.ll = d_ll; a.grad = d_grad; a.lam = d_lam; a.gtol = gtol; a.maxiter = maxiter; a.max_backtrack = max_backtrack;
     a.Xt = d_Xt; a.flags = flags_dev;
     return PGL_OK;

@@ -61,6 +61,7 @@
 #include "pglm_gibbs.hip.h"
 #include "pglm_stim.hip.h"
 #include "pglm_bfgs.hip.h"
+#include "pglm_rowsearch.hip.h"
 #include "pglm_ncg.hip.h"
 #include "pglm_newton.hip.h"
 #include "pglm_hmc.hip.h"

@@ -142,6 +142,7 @@ PGL_LS_FN double pgl_ls_interpolate(double* stx, double* fx, double* dx, double*
 PGL_LS_FN int pgl_ls_step(PglLs* s, double f, double g, double ftol, double gtol, double xtol, double stpmin,
                           double stpmax)
 {
+    (void)ftol;                                                             // (in s->gtest since pgl_ls_start)
     const double stp = s->stp;
     const double ftest = s->finit + stp * s->gtest;
     const int brackt = s->brackt != 0.0;
@@ -190,6 +191,43 @@ PGL_LS_FN int pgl_ls_step(PglLs* s, double f, double g, double ftol, double gtol
     s->stp = stpn;
     if (!(stpn == stpn) || stpn - stpn != 0.0) return PGL_LS_WARNING;       // NaN / inf step (scipy: "WARN")
     return PGL_LS_EVALUATE;
+}
+
+// outcome of pgl_ls_guarded_step (PGL_LS_EVALUATE, or the row's search is over)
+#define PGL_LS_TAKE_TRIAL 1 // the row takes the trial just evaluated
+#define PGL_LS_TAKE_BEST 2  // the row takes the best step saved before this call (the caller's point, gradient and value fb)
+#define PGL_LS_FAIL 3       // no acceptable point
+
+PGL_LS_FN int pgl_ls_finite(double x) { return x - x == 0.0; }
+
+// The guarded step every lock-step optimiser makes once the trial ls->stp has been evaluated (f, dphi = g_trial . d):
+// pgl_ls_step, except that a non-finite f or dphi and the max_trials-th trial end the search like a warning.  Where
+// DCSRCH gives up (scipy: "precision loss") the best sufficient-decrease point of this search is taken if there is one:
+// the trial itself, or the best step before this call -- fb is the caller's value there, judged by ITS step length, also
+// when the search is cut off on a call in which the trial became the best step.  TAKE_*: *alpha_acc and *facc are the
+// step length and the value of the point taken (untouched otherwise).  ls->moved is 1 only on PGL_LS_EVALUATE, when
+// the trial became the best step: the caller then saves its point, gradient and value.
+PGL_LS_FN int pgl_ls_guarded_step(PglLs* ls, double f, double dphi, double fb, double c1, double c2, double xtol,
+                                  double stpmin, double stpmax, int max_trials, double* alpha_acc, double* facc)
+{
+    const double stp = ls->stp, stx_prev = ls->stx;
+    int rc = PGL_LS_WARNING;
+    if (pgl_ls_finite(f) && pgl_ls_finite(dphi)) rc = pgl_ls_step(ls, f, dphi, c1, c2, xtol, stpmin, stpmax);
+    if (rc == PGL_LS_EVALUATE && ls->nfev < (double)max_trials) return PGL_LS_EVALUATE;
+    ls->moved = 0.0;
+    if (rc != PGL_LS_CONVERGED) {
+        const int okT = stp > 0.0 && f <= ls->finit + stp * ls->gtest && f < ls->finit;
+        const int okB = stx_prev > 0.0 && fb <= ls->finit + stx_prev * ls->gtest && fb < ls->finit;
+        if (!(okT && (!okB || f <= fb))) {
+            if (!okB) return PGL_LS_FAIL;
+            *alpha_acc = stx_prev;
+            *facc = fb;
+            return PGL_LS_TAKE_BEST;
+        }
+    }
+    *alpha_acc = stp;
+    *facc = f;
+    return PGL_LS_TAKE_TRIAL;
 }
 
 // the first trial step of a search: scipy's  min(1, 1.01 * 2 (f - f_prev) / slope), 1 when that is not positive

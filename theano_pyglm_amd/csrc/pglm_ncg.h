@@ -68,10 +68,10 @@
 #define PGL_NCG_CURV_FAIL 3     // non-finite curvature: status 3
 
 // outcome of pgl_ncg_search_step
-#define PGL_NCG_LS_EVALUATE 0   // evaluate at s->alpha next
-#define PGL_NCG_LS_TAKE_TRIAL 1 // the row takes the trial just evaluated (step length s->alpha_acc)
-#define PGL_NCG_LS_TAKE_BEST 2  // the row takes the best step saved so far (step length s->alpha_acc, value s->fb)
-#define PGL_NCG_LS_FAIL 3       // no acceptable point: status 2
+#define PGL_NCG_LS_EVALUATE PGL_LS_EVALUATE     // evaluate at s->alpha next
+#define PGL_NCG_LS_TAKE_TRIAL PGL_LS_TAKE_TRIAL // the row takes the trial just evaluated (step length s->alpha_acc)
+#define PGL_NCG_LS_TAKE_BEST PGL_LS_TAKE_BEST   // the row takes the best step saved so far (s->alpha_acc, value s->fb)
+#define PGL_NCG_LS_FAIL PGL_LS_FAIL             // no acceptable point: status 2
 
 #define PGL_NCG_NSCAL 16
 
@@ -88,7 +88,7 @@ typedef struct {
     double moved;               // 1: the trial just evaluated became the best step (the caller saves point and gradient)
 } PglNcg;
 
-PGL_NCG_FN int pgl_ncg_finite(double x) { return x - x == 0.0; }
+PGL_NCG_FN int pgl_ncg_finite(double x) { return pgl_ls_finite(x); }
 
 PGL_NCG_FN void pgl_ncg_finish(PglNcg* s, int status)
 {
@@ -188,42 +188,23 @@ PGL_NCG_FN int pgl_ncg_cg_end(PglNcg* s, PglLs* ls, double slope, double pnorm1)
     return PGL_NCG_SEARCH;
 }
 
-// The trial x + s->alpha pk has been evaluated: f (NaN rule applied), dphi = g_trial . pk.
+// The trial x + s->alpha pk has been evaluated: f (NaN rule applied), dphi = g_trial . pk.  pgl_ls_guarded_step on the
+// exact value at the best step (s->fb), mirrored into the row's own fields.
 PGL_NCG_FN int pgl_ncg_search_step(PglNcg* s, PglLs* ls, double f, double dphi)
 {
-    const double stp = ls->stp, stx_prev = ls->stx;
-    int rc = PGL_LS_WARNING;
+    double facc;                                         // (the caller has both values: f and s->fb)
     s->nfev += 1.0;
-    if (pgl_ncg_finite(f) && pgl_ncg_finite(dphi))
-        rc = pgl_ls_step(ls, f, dphi, PGL_NCG_C1, PGL_NCG_C2, PGL_NCG_LS_XTOL, PGL_NCG_STPMIN, PGL_NCG_STPMAX);
-    else ls->moved = 0.0;
-    if (rc == PGL_LS_EVALUATE && ls->nfev >= (double)PGL_NCG_MAX_TRIALS) rc = PGL_LS_WARNING;
+    const int d = pgl_ls_guarded_step(ls, f, dphi, s->fb, PGL_NCG_C1, PGL_NCG_C2, PGL_NCG_LS_XTOL, PGL_NCG_STPMIN,
+                                      PGL_NCG_STPMAX, PGL_NCG_MAX_TRIALS, &s->alpha_acc, &facc);
     s->moved = 0.0;
-    if (rc == PGL_LS_CONVERGED) {
-        s->alpha_acc = stp;
-        return PGL_NCG_LS_TAKE_TRIAL;
-    }
-    if (rc == PGL_LS_WARNING) {
-        // (fb still is the value at the best step BEFORE this call, stx_prev its step length)
-        const int okT = stp > 0.0 && f <= ls->finit + stp * ls->gtest && f < ls->finit;
-        const int okB = stx_prev > 0.0 && s->fb <= ls->finit + stx_prev * ls->gtest && s->fb < ls->finit;
-        if (okT && (!okB || f <= s->fb)) {
-            s->alpha_acc = stp;
-            return PGL_NCG_LS_TAKE_TRIAL;
+    if (d == PGL_LS_EVALUATE) {
+        s->alpha = ls->stp;
+        if (ls->moved != 0.0) {
+            s->fb = f;
+            s->moved = 1.0;
         }
-        if (okB) {
-            s->alpha_acc = stx_prev;
-            return PGL_NCG_LS_TAKE_BEST;
-        }
-        pgl_ncg_finish(s, PGL_NCG_PRLOSS);
-        return PGL_NCG_LS_FAIL;
-    }
-    s->alpha = ls->stp;
-    if (ls->moved != 0.0) {
-        s->fb = f;
-        s->moved = 1.0;
-    }
-    return PGL_NCG_LS_EVALUATE;
+    } else if (d == PGL_LS_FAIL) pgl_ncg_finish(s, PGL_NCG_PRLOSS);
+    return d;
 }
 
 // The row has taken the step alpha_acc pk to a point with value fnew: updnorm1 = |alpha_acc pk|_1.  Returns PGL_NCG_DONE

@@ -21,7 +21,8 @@ struct NcgView {
     double* ls;                               // (PGL_LS_NDOUBLES, M): line-search state, field-major
 };
 #define PGL_NCG_NVEC 7
-#define PGL_NCG_F_ALPHA 12                   // index of PglNcg::alpha in PGL_NCG_FIELDS
+#define PGL_NCG_F_PHASE 10                   // indices of PglNcg::phase, ::alpha in PGL_NCG_FIELDS
+#define PGL_NCG_F_ALPHA 12
 __host__ __device__ inline size_t pgl_ncg_doubles(int M, int P)
 {
     return (size_t)M * P * PGL_NCG_NVEC + (size_t)M * (PGL_NCG_NSCAL + PGL_LS_NDOUBLES);
@@ -46,33 +47,7 @@ struct NcgRow {
     int dec[2];
     double val;
 };
-__device__ __forceinline__ void pgl_ncg_load(const NcgView& v, int r, NcgRow* w)
-{
-#define PGL_NCG_LD(name, k) w->s.name = v.sc[(size_t)k * v.M + r];
-    PGL_NCG_FIELDS(PGL_NCG_LD)
-#undef PGL_NCG_LD
-#define PGL_NCG_LD(name, k) w->l.name = v.ls[(size_t)k * v.M + r];
-    PGL_LS_FIELDS(PGL_NCG_LD)
-#undef PGL_NCG_LD
-}
-__device__ __forceinline__ void pgl_ncg_store(const NcgView& v, int r, const NcgRow* w)
-{
-#define PGL_NCG_ST(name, k) v.sc[(size_t)k * v.M + r] = w->s.name;
-    PGL_NCG_FIELDS(PGL_NCG_ST)
-#undef PGL_NCG_ST
-#define PGL_NCG_ST(name, k) v.ls[(size_t)k * v.M + r] = w->l.name;
-    PGL_LS_FIELDS(PGL_NCG_ST)
-#undef PGL_NCG_ST
-}
-// end of a workgroup that has advanced its row: state back to memory, the row's phase to the driver's pinned flags
-__device__ __forceinline__ void pgl_ncg_leave(const NcgView& v, int r, const NcgRow* w, double* flags, const int tid)
-{
-    __syncthreads();
-    if (tid == 0) {
-        pgl_ncg_store(v, r, w);
-        if (flags) __hip_atomic_store(flags + r, w->s.phase, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
+PGL_ROW_STATE(NcgView, NcgRow, PGL_NCG_FIELDS)
 __device__ __forceinline__ void pgl_ncg_zero(double* __restrict__ a, const int P, const int tid)
 {
     for (int c = tid; c < P; c += 256) a[c] = 0.0;
@@ -141,7 +116,7 @@ __global__ __launch_bounds__(256) void k_ncg_init(const NcgView v, double* __res
     }
     __syncthreads();
     pgl_ncg_outer_begin_row(v, r, &w, maxiter, V + o, red, tid);
-    pgl_ncg_leave(v, r, &w, flags, tid);
+    pgl_row_leave(v, r, &w, flags, tid);
 }
 
 // One CG iteration of every row whose CG runs, after ONE product over all rows: Hv[row] = H_ll psupi comes in, is
@@ -154,7 +129,7 @@ __global__ __launch_bounds__(256) void k_ncg_cg_step(const NcgView v, double* __
     __shared__ NcgRow w;
     const int r = blockIdx.x, tid = threadIdx.x, P = v.P;
     const size_t o = (size_t)r * P;
-    if (tid == 0) pgl_ncg_load(v, r, &w);
+    if (tid == 0) pgl_row_load(v, r, &w);
     __syncthreads();
     if (w.s.phase != (double)PGL_NCG_CG) return;
     double* ap = Hv + o;
@@ -215,7 +190,7 @@ __global__ __launch_bounds__(256) void k_ncg_cg_step(const NcgView v, double* __
     const int d = w.dec[0];
     if (d == PGL_NCG_CURV_FAIL) {
         pgl_ncg_zero(Vr, P, tid);
-        pgl_ncg_leave(v, r, &w, flags, tid);
+        pgl_row_leave(v, r, &w, flags, tid);
         return;
     }
     const double alphai = w.s.alphai;
@@ -239,7 +214,7 @@ __global__ __launch_bounds__(256) void k_ncg_cg_step(const NcgView v, double* __
         const int go = w.dec[1];
         if (go < 0) {
             pgl_ncg_zero(Vr, P, tid);
-            pgl_ncg_leave(v, r, &w, flags, tid);
+            pgl_row_leave(v, r, &w, flags, tid);
             return;
         }
         const double betai = w.val;
@@ -255,76 +230,23 @@ __global__ __launch_bounds__(256) void k_ncg_cg_step(const NcgView v, double* __
         __syncthreads();
         pgl_ncg_cg_end_row(v, r, &w, Vr, red, tid);
     }
-    pgl_ncg_leave(v, r, &w, flags, tid);
+    pgl_row_leave(v, r, &w, flags, tid);
 }
 
-// trial points of the listed rows: Xt[j] = X[r] + alpha[r] pk[r], r = rows[j] (null: r = j)
-__global__ __launch_bounds__(256) void k_ncg_trial(const NcgView v, const int* __restrict__ rows, double* __restrict__ Xt)
-{
-    const int j = blockIdx.x, r = rows ? rows[j] : j;
-    const double a = v.sc[(size_t)PGL_NCG_F_ALPHA * v.M + r];
-    for (int c = threadIdx.x; c < v.P; c += 256)
-        Xt[(size_t)j * v.P + c] = v.X[(size_t)r * v.P + c] + a * v.xs[(size_t)r * v.P + c];
-}
-
-// One line-search step of every listed row whose search runs, after ONE ll+grad evaluation of their trial points
-// (Xt / ft / gt by list position): priors and NaN rules in place, phi' = g_trial . pk, the More'-Thuente step; then the next
-// trial point into the next launch's list position, or -- the row takes a point -- the convergence test and the whole
-// start of the next outer iteration (the accepted point carries its gradient), V[row] included.
-struct NcgSearchArgs {
-    const int* rows;
-    const double* Xt;
-    double* ft;
-    double* gt;
-    BfgsPrior q;
-    int maxiter;
-    const int* pos_next;
-    double* Xt_next;
-    double* V;
-    double* flags;
-};
-__global__ __launch_bounds__(256) void k_ncg_search_step(const NcgView v, const NcgSearchArgs a)
+// One line-search step of every listed row whose search runs (pgl_row_search_front along pk = xsupi); a row that takes a
+// point goes on here: the convergence test and the whole start of the next outer iteration (the accepted point carries
+// its gradient), V[row] included.
+__global__ __launch_bounds__(256) void k_ncg_search_step(const NcgView v, const RowSearchArgs a)
 {
     __shared__ double red[12];
     __shared__ NcgRow w;
     const int j = blockIdx.x, r = a.rows ? a.rows[j] : j, tid = threadIdx.x, P = v.P;
     const size_t o = (size_t)r * P;
-    if (tid == 0) pgl_ncg_load(v, r, &w);
-    __syncthreads();
-    if (w.s.phase != (double)PGL_NCG_SEARCH) return;
-    const double* __restrict__ xt = a.Xt + (size_t)j * P;
-    double* __restrict__ gt = a.gt + (size_t)j * P;
-    pgl_bfgs_objective_row(P, xt, gt, a.ft + j, a.q, red, tid);
-    __syncthreads();
-    double dp = 0.0;
-    for (int c = tid; c < P; c += 256) dp = fma(gt[c], v.xs[o + c], dp);
-    dp = pgl_blk_sum(dp, red);
-    if (tid == 0) w.dec[0] = pgl_ncg_search_step(&w.s, &w.l, a.ft[j], dp);
-    __syncthreads();
-    const int d = w.dec[0];
-    if (d == PGL_NCG_LS_FAIL) {
-        pgl_ncg_leave(v, r, &w, a.flags, tid);
-        return;
-    }
-    if (d == PGL_NCG_LS_EVALUATE) {
-        if (w.s.moved != 0.0)
-            for (int c = tid; c < P; c += 256) {
-                v.Xb[o + c] = xt[c];
-                v.gb[o + c] = gt[c];
-            }
-        if (a.Xt_next) {
-            const int jn = a.pos_next ? a.pos_next[r] : j;
-            if (jn >= 0) {
-                const double al = w.s.alpha;
-                for (int c = tid; c < P; c += 256) a.Xt_next[(size_t)jn * P + c] = v.X[o + c] + al * v.xs[o + c];
-            }
-        }
-        pgl_ncg_leave(v, r, &w, a.flags, tid);
-        return;
-    }
-    const bool trial = d == PGL_NCG_LS_TAKE_TRIAL;
-    const double* xsrc = trial ? xt : v.Xb + o;
-    const double* gsrc = trial ? gt : v.gb + o;
+    const double *xsrc, *gsrc;
+    const int d = pgl_row_search_front(
+        v, a, j, r, &w, v.xs + o, [](NcgRow* w, double f, double dp) { return pgl_ncg_search_step(&w->s, &w->l, f, dp); }, red,
+        tid, &xsrc, &gsrc);
+    if (d != PGL_LS_TAKE_TRIAL && d != PGL_LS_TAKE_BEST) return;
     const double al = w.s.alpha_acc;
     double un = 0.0;
     for (int c = tid; c < P; c += 256) {
@@ -333,8 +255,8 @@ __global__ __launch_bounds__(256) void k_ncg_search_step(const NcgView v, const 
         v.g[o + c] = gsrc[c];
     }
     un = pgl_blk_sum(un, red);
-    if (tid == 0) w.dec[1] = pgl_ncg_accept(&w.s, trial ? a.ft[j] : w.s.fb, un, P);
+    if (tid == 0) w.dec[1] = pgl_ncg_accept(&w.s, d == PGL_LS_TAKE_TRIAL ? a.ft[j] : w.s.fb, un, P);
     __syncthreads();
     if (w.dec[1] == PGL_NCG_CG) pgl_ncg_outer_begin_row(v, r, &w, a.maxiter, a.V + o, red, tid);
-    pgl_ncg_leave(v, r, &w, a.flags, tid);
+    pgl_row_leave(v, r, &w, a.flags, tid);
 }

@@ -65,10 +65,10 @@
 #define PGL_NEWTON_DIR_FAIL 3       // status 3
 
 // outcome of pgl_newton_search_step
-#define PGL_NEWTON_LS_EVALUATE 0    // evaluate at s->alpha next (ls->moved: the trial just evaluated became the best step)
-#define PGL_NEWTON_LS_TAKE_TRIAL 1  // the row takes the trial just evaluated
-#define PGL_NEWTON_LS_TAKE_BEST 2   // the row takes the best step saved so far (value *facc)
-#define PGL_NEWTON_LS_FAIL 3        // no acceptable point: status 2
+#define PGL_NEWTON_LS_EVALUATE PGL_LS_EVALUATE     // evaluate at s->alpha next (ls->moved: the trial became the best step)
+#define PGL_NEWTON_LS_TAKE_TRIAL PGL_LS_TAKE_TRIAL // the row takes the trial just evaluated
+#define PGL_NEWTON_LS_TAKE_BEST PGL_LS_TAKE_BEST   // the row takes the best step saved so far (value *facc)
+#define PGL_NEWTON_LS_FAIL PGL_LS_FAIL             // no acceptable point: status 2
 
 #define PGL_NEWTON_NSCAL 11
 
@@ -81,7 +81,7 @@ typedef struct {
     double status, phase;
 } PglNewton;
 
-PGL_NEWTON_FN int pgl_newton_finite(double x) { return x - x == 0.0; }
+PGL_NEWTON_FN int pgl_newton_finite(double x) { return pgl_ls_finite(x); }
 
 PGL_NEWTON_FN void pgl_newton_finish(PglNewton* s, int status)
 {
@@ -136,34 +136,19 @@ PGL_NEWTON_FN int pgl_newton_direction(PglNewton* s, PglLs* ls, int failed, doub
     return d;
 }
 
-// The trial x + s->alpha p has been evaluated: f (NaN rule applied), dphi = g_trial . p.  *facc: the value of the point
-// the row takes (TAKE_TRIAL: f, TAKE_BEST: the value at the best step before this call).
+// The trial x + s->alpha p has been evaluated: f (NaN rule applied), dphi = g_trial . p.  pgl_ls_guarded_step on the line
+// search's own value at the best step (ls->fx).  *facc: the value of the point the row takes (TAKE_TRIAL: f, TAKE_BEST:
+// the value at the best step before this call).
 PGL_NEWTON_FN int pgl_newton_search_step(PglNewton* s, PglLs* ls, double f, double dphi, double* facc)
 {
-    const double stp = ls->stp, stx_prev = ls->stx, fb = ls->fx;
-    int rc = PGL_LS_WARNING;
+    double alpha_acc;                                    // (not kept: the row moves to a saved point)
     s->nfev += 1.0;
-    if (pgl_newton_finite(f) && pgl_newton_finite(dphi))
-        rc = pgl_ls_step(ls, f, dphi, PGL_NEWTON_C1, PGL_NEWTON_C2, PGL_NEWTON_LS_XTOL, PGL_NEWTON_STPMIN, PGL_NEWTON_STPMAX);
-    else ls->moved = 0.0;
-    if (rc == PGL_LS_EVALUATE && ls->nfev >= (double)PGL_NEWTON_MAX_TRIALS) rc = PGL_LS_WARNING;
     *facc = f;
-    if (rc == PGL_LS_CONVERGED) return PGL_NEWTON_LS_TAKE_TRIAL;
-    if (rc == PGL_LS_WARNING) {
-        // (fb is the value at the best step BEFORE this call, stx_prev its step length: the caller's saved point)
-        const int okT = stp > 0.0 && f <= ls->finit + stp * ls->gtest && f < ls->finit;
-        const int okB = stx_prev > 0.0 && fb <= ls->finit + stx_prev * ls->gtest && fb < ls->finit;
-        ls->moved = 0.0;
-        if (okT && (!okB || f <= fb)) return PGL_NEWTON_LS_TAKE_TRIAL;
-        if (okB) {
-            *facc = fb;
-            return PGL_NEWTON_LS_TAKE_BEST;
-        }
-        pgl_newton_finish(s, PGL_NEWTON_PRLOSS);
-        return PGL_NEWTON_LS_FAIL;
-    }
-    s->alpha = ls->stp;
-    return PGL_NEWTON_LS_EVALUATE;
+    const int d = pgl_ls_guarded_step(ls, f, dphi, ls->fx, PGL_NEWTON_C1, PGL_NEWTON_C2, PGL_NEWTON_LS_XTOL,
+                                      PGL_NEWTON_STPMIN, PGL_NEWTON_STPMAX, PGL_NEWTON_MAX_TRIALS, &alpha_acc, facc);
+    if (d == PGL_LS_EVALUATE) s->alpha = ls->stp;
+    else if (d == PGL_LS_FAIL) pgl_newton_finish(s, PGL_NEWTON_PRLOSS);
+    return d;
 }
 
 // The row has moved to a point with value fnew and gradient maximum gmax.  Returns the phase: PGL_NEWTON_DONE (converged:

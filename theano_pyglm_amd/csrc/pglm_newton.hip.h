@@ -48,33 +48,7 @@ struct NewtonRow {
     int dec[2];
     double val;
 };
-__device__ __forceinline__ void pgl_newton_load(const NewtonView& v, int r, NewtonRow* w)
-{
-#define PGL_NEWTON_LD(name, k) w->s.name = v.sc[(size_t)k * v.M + r];
-    PGL_NEWTON_FIELDS(PGL_NEWTON_LD)
-#undef PGL_NEWTON_LD
-#define PGL_NEWTON_LD(name, k) w->l.name = v.ls[(size_t)k * v.M + r];
-    PGL_LS_FIELDS(PGL_NEWTON_LD)
-#undef PGL_NEWTON_LD
-}
-__device__ __forceinline__ void pgl_newton_store(const NewtonView& v, int r, const NewtonRow* w)
-{
-#define PGL_NEWTON_ST(name, k) v.sc[(size_t)k * v.M + r] = w->s.name;
-    PGL_NEWTON_FIELDS(PGL_NEWTON_ST)
-#undef PGL_NEWTON_ST
-#define PGL_NEWTON_ST(name, k) v.ls[(size_t)k * v.M + r] = w->l.name;
-    PGL_LS_FIELDS(PGL_NEWTON_ST)
-#undef PGL_NEWTON_ST
-}
-// end of a workgroup that has advanced its row: state back to memory, the row's phase to the driver's pinned flags
-__device__ __forceinline__ void pgl_newton_leave(const NewtonView& v, int r, const NewtonRow* w, double* flags, const int tid)
-{
-    __syncthreads();
-    if (tid == 0) {
-        pgl_newton_store(v, r, w);
-        if (flags) __hip_atomic_store(flags + r, w->s.phase, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
+PGL_ROW_STATE(NewtonView, NewtonRow, PGL_NEWTON_FIELDS)
 // max|a[c]| over a row, in every thread
 __device__ __forceinline__ double pgl_newton_absmax(const double* __restrict__ a, const int P, double* red, const int tid)
 {
@@ -99,7 +73,7 @@ __global__ __launch_bounds__(256) void k_newton_init(const NewtonView v, double*
         pgl_ls_start(&w.l, 1.0, ll[r], -1.0, PGL_NEWTON_C1, PGL_NEWTON_STPMIN, PGL_NEWTON_STPMAX);
         pgl_newton_init(&w.s, ll[r], gmax, gtol, maxiter);
     }
-    pgl_newton_leave(v, r, &w, flags, tid);
+    pgl_row_leave(v, r, &w, flags, tid);
 }
 
 // A = -H_ll - H_prior(X) + shift diag(-H_ll - H_prior) of the listed rows, in place on the lower triangle of H (L, P, ld)
@@ -159,7 +133,7 @@ __global__ __launch_bounds__(256) void k_newton_direction(const NewtonView v, co
     __shared__ NewtonRow w;
     const int j = blockIdx.x, r = rows ? rows[j] : j, tid = threadIdx.x, P = v.P;
     const size_t o = (size_t)r * P;
-    if (tid == 0) pgl_newton_load(v, r, &w);
+    if (tid == 0) pgl_row_load(v, r, &w);
     __syncthreads();
     if (w.s.phase != (double)PGL_NEWTON_HESS && w.s.phase != (double)PGL_NEWTON_REFACTOR) return;
     const double* pj = sol + (size_t)j * P;
@@ -178,79 +152,23 @@ __global__ __launch_bounds__(256) void k_newton_direction(const NewtonView v, co
         for (int c = tid; c < P; c += 256) v.p[o + c] = pj[c];
     else if (d == PGL_NEWTON_DIR_STEEPEST)
         for (int c = tid; c < P; c += 256) v.p[o + c] = -v.g[o + c];
-    pgl_newton_leave(v, r, &w, flags, tid);
+    pgl_row_leave(v, r, &w, flags, tid);
 }
 
-// points of the listed rows: Xt[j] = X[r] + alpha[r] p[r] for a row whose search runs, X[r] for any other (the points the
-// Hessian of a list is taken at), r = rows[j] (null: r = j)
-__global__ __launch_bounds__(256) void k_newton_trial(const NewtonView v, const int* __restrict__ rows, double* __restrict__ Xt)
-{
-    const int j = blockIdx.x, r = rows ? rows[j] : j;
-    const bool search = v.sc[(size_t)PGL_NEWTON_F_PHASE * v.M + r] == (double)PGL_NEWTON_SEARCH;
-    const double a = v.sc[(size_t)PGL_NEWTON_F_ALPHA * v.M + r];
-    for (int c = threadIdx.x; c < v.P; c += 256) {
-        const double xc = v.X[(size_t)r * v.P + c];
-        Xt[(size_t)j * v.P + c] = search ? xc + a * v.p[(size_t)r * v.P + c] : xc;
-    }
-}
-
-// One line-search step of every listed row whose search runs, after ONE ll+grad evaluation of their trial points
-// (Xt / ft / gt by list position): priors and NaN rules in place, phi' = g_trial . p, the More'-Thuente step; then the next
-// trial point into the next launch's list position, or -- the row takes a point -- the convergence test on its gradient.
-struct NewtonSearchArgs {
-    const int* rows;
-    const double* Xt;
-    double* ft;
-    double* gt;
-    BfgsPrior q;
-    double gtol;
-    int maxiter;
-    const int* pos_next;
-    double* Xt_next;
-    double* flags;
-};
-__global__ __launch_bounds__(256) void k_newton_search_step(const NewtonView v, const NewtonSearchArgs a)
+// One line-search step of every listed row whose search runs (pgl_row_search_front along p); a row that takes a point
+// goes on here: the convergence test on its gradient.
+__global__ __launch_bounds__(256) void k_newton_search_step(const NewtonView v, const RowSearchArgs a)
 {
     __shared__ double red[12];
     __shared__ NewtonRow w;
     const int j = blockIdx.x, r = a.rows ? a.rows[j] : j, tid = threadIdx.x, P = v.P;
     const size_t o = (size_t)r * P;
-    if (tid == 0) pgl_newton_load(v, r, &w);
-    __syncthreads();
-    if (w.s.phase != (double)PGL_NEWTON_SEARCH) return;
-    const double* __restrict__ xt = a.Xt + (size_t)j * P;
-    double* __restrict__ gt = a.gt + (size_t)j * P;
-    pgl_bfgs_objective_row(P, xt, gt, a.ft + j, a.q, red, tid);
-    __syncthreads();
-    double dp = 0.0;
-    for (int c = tid; c < P; c += 256) dp = fma(gt[c], v.p[o + c], dp);
-    dp = pgl_blk_sum(dp, red);
-    if (tid == 0) w.dec[0] = pgl_newton_search_step(&w.s, &w.l, a.ft[j], dp, &w.val);
-    __syncthreads();
-    const int d = w.dec[0];
-    if (d == PGL_NEWTON_LS_FAIL) {
-        pgl_newton_leave(v, r, &w, a.flags, tid);
-        return;
-    }
-    if (d == PGL_NEWTON_LS_EVALUATE) {
-        if (w.l.moved != 0.0)
-            for (int c = tid; c < P; c += 256) {
-                v.Xb[o + c] = xt[c];
-                v.gb[o + c] = gt[c];
-            }
-        if (a.Xt_next) {
-            const int jn = a.pos_next ? a.pos_next[r] : j;
-            if (jn >= 0) {
-                const double al = w.s.alpha;
-                for (int c = tid; c < P; c += 256) a.Xt_next[(size_t)jn * P + c] = v.X[o + c] + al * v.p[o + c];
-            }
-        }
-        pgl_newton_leave(v, r, &w, a.flags, tid);
-        return;
-    }
-    const bool trial = d == PGL_NEWTON_LS_TAKE_TRIAL;
-    const double* xsrc = trial ? xt : v.Xb + o;
-    const double* gsrc = trial ? gt : v.gb + o;
+    const double *xsrc, *gsrc;
+    const int d = pgl_row_search_front(
+        v, a, j, r, &w, v.p + o,
+        [](NewtonRow* w, double f, double dp) { return pgl_newton_search_step(&w->s, &w->l, f, dp, &w->val); }, red, tid, &xsrc,
+        &gsrc);
+    if (d != PGL_LS_TAKE_TRIAL && d != PGL_LS_TAKE_BEST) return;
     double gmax = 0.0;
     for (int c = tid; c < P; c += 256) {
         const double gc = gsrc[c];
@@ -260,5 +178,5 @@ __global__ __launch_bounds__(256) void k_newton_search_step(const NewtonView v, 
     }
     gmax = pgl_blk_max(gmax, red);
     if (tid == 0) pgl_newton_accept(&w.s, w.val, gmax, a.gtol, a.maxiter);
-    pgl_newton_leave(v, r, &w, a.flags, tid);
+    pgl_row_leave(v, r, &w, a.flags, tid);
 }

@@ -18,7 +18,7 @@ flags); no library kernel is on the path, except the sum over the data sequences
 The Hessians of a list live in two buffers of L * P * ld doubles (the work copy that the factor overwrites and the
 unshifted one); a list whose buffers would exceed `hess_budget_bytes` (default 4 GB) runs in slices.
 
-Served: exactly what batched_newton_cg serves (its _check): theta-row packings under a Gaussian or group-lasso prior, no
+Served: exactly what batched_newton_cg serves (lockstep._check): theta-row packings under a Gaussian or group-lasso prior, no
 time shard.
 """
 import time
@@ -26,8 +26,8 @@ import time
 import numpy as np
 
 from theano_pyglm_amd.inference.batched_bfgs import _Packing
-from theano_pyglm_amd.inference.batched_newton_cg import _check, _host_buffers, supported  # noqa: F401
-from theano_pyglm_amd.inference.lockstep import RangeEvaluator, session
+from theano_pyglm_amd.inference.lockstep import (RangeEvaluator, _check, _host_buffers, search_phase, send_list,  # noqa: F401
+                                                 session, supported, wait)
 
 PHASE_HESS, PHASE_SEARCH, PHASE_DONE, PHASE_REFACTOR = 0.0, 1.0, 2.0, 3.0
 # rows of the scalar block of the state (PglNewton, csrc/pglm_newton.h)
@@ -83,13 +83,8 @@ def _lockstep(population, torch, dev, stream, handles, x, maxiter, gtol, n_lo, n
     per = max(1, min(M, budget // (2 * P * ld * 8)))          # rows per slice: two buffers of `per` matrices
     Hraw = torch.empty((per, P, ld), dtype=f64, device=dev)
     Awork = torch.empty((per, P, ld), dtype=f64, device=dev)
-    counts = {'hess': 0, 'hess_rows': 0, 'factor': 0, 'factor_rows': 0, 'solve': 0, 'll_grad': 0, 'neuron_evaluations': 0,
-              'outer': 0, 'refactor_rows': 0}
+    counts = {'hess': 0, 'hess_rows': 0, 'factor': 0, 'factor_rows': 0, 'solve': 0, 'outer': 0, 'refactor_rows': 0}
     tm = {'hess': 0.0, 'factor': 0.0, 'solve': 0.0, 'eval': 0.0}
-
-    def wait():
-        done.record(stream)
-        done.synchronize()
 
     def timed(key, t0):
         if timings is not None:
@@ -97,25 +92,13 @@ def _lockstep(population, torch, dev, stream, handles, x, maxiter, gtol, n_lo, n
             tm[key] += time.perf_counter() - t0
 
     def send(rows):
-        """a list travels as ONE copy of [its rows | its neurons] (int32)"""
-        L = int(rows.size)
-        sg = stage.numpy()
-        sg[:L] = rows
-        sg[M:M + L] = rows + n_lo
-        lists.copy_(stage, non_blocking=True)
-        return L
+        return send_list(stage, lists, rows, n_lo, M)
 
     def evaluate(Xt, idx32, L):
         t0 = time.perf_counter()
-        tot = None
-        for h, full in zip(handles, whole.bufs):
-            buf = full[:L * (1 + P)]
-            h.ll_grad_list_dev(idx32.data_ptr(), L, Xt.data_ptr(), Weff.data_ptr(), buf.data_ptr(), buf[L:].data_ptr())
-            tot = buf if tot is None else tot.add_(buf)
-        counts['ll_grad'] += 1
-        counts['neuron_evaluations'] += L
+        out = whole.eval_list(Xt, idx32, L)
         timed('eval', t0)
-        return tot[:L], tot[L:]
+        return out
 
     def factor_solve_direction(L):
         """assemble, factor, solve and direction of the L listed rows: Awork[:L] holds the Hessians of ll"""
@@ -132,11 +115,11 @@ def _lockstep(population, torch, dev, stream, handles, x, maxiter, gtol, n_lo, n
         counts['solve'] += 1
         timed('solve', t0)
         h0.newton_direction_dev(st.data_ptr(), M, P, lists.data_ptr(), L, info.data_ptr(), b.data_ptr(), flags.data_ptr())
-        wait()
+        wait(stream, done)
 
     ll0, g0 = whole(X)
     h0.newton_init_dev(st.data_ptr(), M, P, ll0.data_ptr(), g0.data_ptr(), prm, gtol, maxiter, flags.data_ptr())
-    wait()
+    wait(stream, done)
     while np.any(fl != PHASE_DONE):
         counts['outer'] += 1
         # -- Newton directions of the rows that need a Hessian, a slice at a time
@@ -171,22 +154,13 @@ def _lockstep(population, torch, dev, stream, handles, x, maxiter, gtol, n_lo, n
                 factor_solve_direction(L)
                 again = np.nonzero(fl[pos] == PHASE_REFACTOR)[0]
         # -- line-search phase: the rows still searching, one evaluation per trial step
-        rows = np.nonzero(fl == PHASE_SEARCH)[0].astype(np.int32)
-        launch = 0
-        listed = None
-        while rows.size:
-            L = int(rows.size)
-            cur, nxt = Xts[launch & 1], Xts[(launch + 1) & 1]
-            if listed is None or listed.size != L:
-                send(rows)
-                listed = rows
-                h0.newton_trial_dev(st.data_ptr(), M, P, lists.data_ptr(), L, cur.data_ptr())
-            ft, gt = evaluate(cur, lists[M:M + L], L)
-            h0.newton_search_step_dev(st.data_ptr(), M, P, lists.data_ptr(), L, cur.data_ptr(), ft.data_ptr(), gt.data_ptr(),
-                                      prm, gtol, maxiter, 0, nxt.data_ptr(), flags.data_ptr())
-            wait()
-            launch += 1
-            rows = listed[fl[listed] == PHASE_SEARCH]
+        launch = search_phase(
+            fl, PHASE_SEARCH, M, n_lo, stage, lists, Xts, evaluate,
+            lambda L, cur: h0.newton_trial_dev(st.data_ptr(), M, P, lists.data_ptr(), L, cur.data_ptr()),
+            lambda L, cur, ft, gt, nxt: h0.newton_search_step_dev(
+                st.data_ptr(), M, P, lists.data_ptr(), L, cur.data_ptr(), ft.data_ptr(), gt.data_ptr(), prm, gtol, maxiter, 0,
+                nxt.data_ptr(), flags.data_ptr()),
+            stream, done)
         if verbose:
             print("lock-step Newton outer iteration %d: %d Hessians, %d trial launches, %d rows running"
                   % (counts['outer'], int(running.size), launch, int(np.sum(fl != PHASE_DONE))))
@@ -206,8 +180,8 @@ def _lockstep(population, torch, dev, stream, handles, x, maxiter, gtol, n_lo, n
                                  'hess_launches': counts['hess'], 'hess_rows': counts['hess_rows'],
                                  'factor_launches': counts['factor'], 'factor_rows': counts['factor_rows'],
                                  'solve_launches': counts['solve'], 'refactor_rows': counts['refactor_rows'],
-                                 'll_grad_launches': counts['ll_grad'] + whole.count,
-                                 'neuron_evaluations': counts['neuron_evaluations'] + M * whole.count,
+                                 'll_grad_launches': whole.list_count + whole.count,
+                                 'neuron_evaluations': whole.list_rows + M * whole.count,
                                  'rows_per_slice': int(per),
                                  'per_neuron': {'nit': [int(v) for v in nit], 'nhess': [int(v) for v in nhess],
                                                 'nfact': [int(v) for v in nfact], 'nfev': [int(v) for v in nfev],

@@ -25,39 +25,12 @@ a Gaussian or group-lasso prior).  Time-sharded populations are not (the driver 
 import numpy as np
 
 from theano_pyglm_amd.inference.batched_bfgs import _Packing
-from theano_pyglm_amd.inference.lockstep import RangeEvaluator, session
+from theano_pyglm_amd.inference.lockstep import (RangeEvaluator, _check, _host_buffers, search_phase, session,  # noqa: F401
+                                                 supported, wait)
 
 PHASE_CG, PHASE_SEARCH, PHASE_DONE = 0.0, 1.0, 2.0
 # rows of the scalar block of the state (PglNcg, csrc/pglm_ncg.h)
 SC_F, SC_NIT, SC_NHEV, SC_NFEV, SC_STATUS, SC_PHASE = 0, 6, 7, 8, 9, 10
-
-
-def supported(population):
-    return population.glm.hvp_packing() is None
-
-
-def _check(population):
-    bad = population.glm.hvp_packing()
-    if bad is not None:
-        raise ValueError("lock-step Newton-CG: Hessian-vector products are not implemented for the %s packing" % bad)
-    if getattr(population, '_time_shard', None) is not None:
-        raise ValueError("lock-step Newton-CG does not run on a time-sharded population (set_time_shard): "
-                         "products and evaluations are not all-reduced")
-
-
-_HOST_BUFFERS = {}
-
-
-def _host_buffers(torch, device_index, M):
-    """Pinned phase flags and list staging of a fit, kept between fits: {(device, M): (flags, staging)}."""
-    key = (int(device_index), int(M))
-    hb = _HOST_BUFFERS.get(key)
-    if hb is None:
-        if len(_HOST_BUFFERS) > 16:
-            _HOST_BUFFERS.clear()
-        hb = (torch.zeros(M, dtype=torch.float64).pin_memory(), torch.empty(3 * M, dtype=torch.int32).pin_memory())
-        _HOST_BUFFERS[key] = hb
-    return hb
 
 
 def fit_glms_newton_cg_torch(population, x, maxiter=225, n_lo=0, n_hi=None, verbose=False, on_outer=None):
@@ -101,25 +74,11 @@ def _lockstep(population, torch, dev, stream, handles, x, maxiter, n_lo, n_hi, M
     flags.fill_(PHASE_DONE)
     fl = flags.numpy()
     done = torch.cuda.Event()
-    counts = {'prepare': 0, 'apply': 0, 'll_grad': 0, 'neuron_evaluations': 0, 'outer': 0, 'cg_lengths': []}
-
-    def wait():
-        done.record(stream)
-        done.synchronize()
-
-    def evaluate(Xt, idx32, L):
-        tot = None
-        for h, full in zip(handles, whole.bufs):
-            buf = full[:L * (1 + P)]
-            h.ll_grad_list_dev(idx32.data_ptr(), L, Xt.data_ptr(), Weff.data_ptr(), buf.data_ptr(), buf[L:].data_ptr())
-            tot = buf if tot is None else tot.add_(buf)
-        counts['ll_grad'] += 1
-        counts['neuron_evaluations'] += L
-        return tot[:L], tot[L:]
+    counts = {'prepare': 0, 'apply': 0, 'outer': 0, 'cg_lengths': []}
 
     ll0, g0 = whole(X)
     h0.ncg_init_dev(st.data_ptr(), M, P, ll0.data_ptr(), g0.data_ptr(), prm, maxiter, V.data_ptr(), flags.data_ptr())
-    wait()
+    wait(stream, done)
     while np.any(fl != PHASE_DONE):
         counts['outer'] += 1
         # -- CG phase: one prepare at the current points, then one product over all rows per CG iteration
@@ -141,29 +100,16 @@ def _lockstep(population, torch, dev, stream, handles, x, maxiter, n_lo, n_hi, M
                     except PglError:
                         counts['apply_kernels'] = None
                 h0.ncg_cg_step_dev(st.data_ptr(), M, P, hvs[0].data_ptr(), prm, V.data_ptr(), flags.data_ptr())
-                wait()
+                wait(stream, done)
         counts['cg_lengths'].append(ncg)
         # -- line-search phase: the rows still searching, one evaluation per trial step
-        rows = np.nonzero(fl == PHASE_SEARCH)[0].astype(np.int32)
-        launch = 0
-        listed = None
-        while rows.size:
-            L = int(rows.size)
-            cur, nxt = Xts[launch & 1], Xts[(launch + 1) & 1]
-            if listed is None or listed.size != L:
-                # a new list travels as ONE copy of [its rows | its neurons] (int32); its trial points are recomputed
-                sg = stage.numpy()
-                sg[:L] = rows
-                sg[M:M + L] = rows + n_lo
-                lists.copy_(stage, non_blocking=True)
-                listed = rows
-                h0.ncg_trial_dev(st.data_ptr(), M, P, lists.data_ptr(), L, cur.data_ptr())
-            ft, gt = evaluate(cur, lists[M:M + L], L)
-            h0.ncg_search_step_dev(st.data_ptr(), M, P, lists.data_ptr(), L, cur.data_ptr(), ft.data_ptr(), gt.data_ptr(),
-                                   prm, maxiter, 0, nxt.data_ptr(), V.data_ptr(), flags.data_ptr())
-            wait()
-            launch += 1
-            rows = listed[fl[listed] == PHASE_SEARCH]
+        launch = search_phase(
+            fl, PHASE_SEARCH, M, n_lo, stage, lists, Xts, whole.eval_list,
+            lambda L, cur: h0.ncg_trial_dev(st.data_ptr(), M, P, lists.data_ptr(), L, cur.data_ptr()),
+            lambda L, cur, ft, gt, nxt: h0.ncg_search_step_dev(
+                st.data_ptr(), M, P, lists.data_ptr(), L, cur.data_ptr(), ft.data_ptr(), gt.data_ptr(), prm, maxiter, 0,
+                nxt.data_ptr(), V.data_ptr(), flags.data_ptr()),
+            stream, done)
         if verbose:
             print("lock-step Newton-CG outer iteration %d: %d CG iterations, %d trial launches, %d rows running"
                   % (counts['outer'], ncg, launch, int(np.sum(fl != PHASE_DONE))))
@@ -179,8 +125,8 @@ def _lockstep(population, torch, dev, stream, handles, x, maxiter, n_lo, n_hi, M
     status = sch[SC_STATUS].astype(int)
     population.last_fit_stats = {'optimizer': 'lock-step Newton-CG (hip row kernels)', 'outer_iterations': counts['outer'],
                                  'apply_launches': counts['apply'], 'prepare_launches': counts['prepare'],
-                                 'll_grad_launches': counts['ll_grad'] + whole.count,
-                                 'neuron_evaluations': counts['neuron_evaluations'] + M * whole.count,
+                                 'll_grad_launches': whole.list_count + whole.count,
+                                 'neuron_evaluations': whole.list_rows + M * whole.count,
                                  'cg_lengths': list(counts['cg_lengths']), 'apply_kernels': counts.get('apply_kernels'),
                                  'per_neuron': {'nit': [int(v) for v in nit], 'nhev': [int(v) for v in nhev],
                                                 'nfev': [int(v) for v in nfev], 'status': [int(v) for v in status]}}

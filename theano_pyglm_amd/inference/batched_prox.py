@@ -24,7 +24,7 @@ import numpy as np
 
 from theano_pyglm_amd.components.priors import GroupLasso
 from theano_pyglm_amd.inference.batched_bfgs import _Packing
-from theano_pyglm_amd.inference.lockstep import RangeEvaluator, session
+from theano_pyglm_amd.inference.lockstep import RangeEvaluator, _host_buffers, session
 
 PHASE_Y, PHASE_TRIAL, PHASE_DONE = 0.0, 1.0, 2.0
 # rows of the scalar block of the state (PglProx, csrc/pglm_prox.h)
@@ -33,9 +33,6 @@ FIELDS = ('f_x', 'F_x', 'f_y', 't', 'tk', 'iters', 'nfev', 'nbt', 'restarts', 'p
 SC = dict((n, i) for i, n in enumerate(FIELDS))
 NVEC = 5
 POLL = 4                                                       # launches between two looks at the flags
-
-_HOST_FLAGS = {}
-
 
 def supported(population):
     return population.glm.hvp_packing() is None and isinstance(population.glm.imp_model.prior, GroupLasso)
@@ -51,16 +48,6 @@ def _check(population):
     if getattr(population, '_time_shard', None) is not None:
         raise ValueError("lock-step proximal gradient does not run on a time-sharded population (set_time_shard): "
                          "evaluations are not all-reduced")
-
-
-def _flags(torch, device_index, M):
-    key = (int(device_index), int(M))
-    fl = _HOST_FLAGS.get(key)
-    if fl is None:
-        if len(_HOST_FLAGS) > 16:
-            _HOST_FLAGS.clear()
-        fl = _HOST_FLAGS[key] = torch.zeros(M, dtype=torch.float64).pin_memory()
-    return fl
 
 
 def _row_lams(population, lam, M):
@@ -119,7 +106,7 @@ def _lockstep(population, torch, dev, stream, handles, x, lam, maxiter, gtol, ma
     d_lam = torch.tensor(lam, dtype=f64, device=dev)
     Xt = torch.empty((M, P), dtype=f64, device=dev)
     evaluate = RangeEvaluator(torch, dev, handles, Weff, M, P, n_lo, n_hi)
-    flags = _flags(torch, dev.index, M)
+    flags = _host_buffers(torch, dev.index, M)[0]
     flags.fill_(PHASE_TRIAL)
     fl = flags.numpy()
     counts = {'row': 0, 'polls': 0}
