@@ -341,6 +341,46 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _dp(x):
+    """The device address every _dev method hands to the library: an integer (torch.Tensor.data_ptr(), say) or an object
+    with data_ptr() -- a torch tensor; None and 0 are NULL."""
+    if hasattr(x, 'data_ptr'):
+        x = x.data_ptr()
+    return C.c_void_p(x) if x else None
+
+
+def _dev_tensor(t, dtype, msg, ndim=None, min_ndim=0, numel=0, shape=None, strides=None, contiguous=True):
+    """t where it is a torch device tensor of this dtype ('float64', 'int64') with exactly `ndim` / at least `min_ndim` axes,
+    at least `numel` elements and exactly `shape` and `strides`, as far as each is given; ValueError(msg) where not."""
+    import torch
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == getattr(torch, dtype) and
+            (ndim is None or t.dim() == ndim) and t.dim() >= min_ndim and t.numel() >= numel and
+            (shape is None or tuple(t.shape) == tuple(shape)) and (strides is None or t.stride() == tuple(strides)) and
+            (not contiguous or t.is_contiguous())):
+        raise ValueError(msg)
+    return t
+
+
+def _out_tensor(out, shape, like, msg):
+    """The result tensor of a tensor form: a new float64 tensor of this shape on `like`'s device, or the caller's `out`
+    where it is a contiguous one of that shape."""
+    if out is None:
+        import torch
+        return torch.empty(shape, dtype=torch.float64, device=like.device)
+    return _dev_tensor(out, 'float64', msg, shape=shape)
+
+
+def _second_out(want, fresh, check, none_is_fresh=False):
+    """The optional second output of a tensor form: True -> fresh(), which the form returns beside the first; a tensor ->
+    check(tensor), written into; False -> none.  None is none as well (ks_uniform: the handle sorts in a buffer of its own),
+    or with none_is_fresh a fresh tensor that is not returned (rescale_acf, whose kernel always writes the scores)."""
+    if want is True or (want is None and none_is_fresh):
+        return fresh()
+    if want is None or (want is False and not none_is_fresh):
+        return None
+    return check(want)
+
+
 def simulate(X0, AW, nlin, dt, uniforms=None, seed=0):
     """Native Population.simulate (population.py:233-389); host code, needs no GPU.
     X0 (nT,N) background current, AW (N,R,N) [n_pre][tau][n_post].  Returns (S, X, n_exceptions)."""
@@ -409,17 +449,17 @@ def simulate_batch_dev(N, nT, R, nlin, dt, d_X0, d_AW, n_rep, d_counts, d_except
                        d_workspace=0, stream=0, device=0):
     """Device-pointer form (integers, e.g. torch.Tensor.data_ptr(); asynchronous on `stream`, 0 = the null stream);
     d_S / d_X = 0: counts and exceptions alone; see pgl_simulate_batch_dev."""
-    vp = lambda a: C.c_void_p(a) if a else None
     kind = int({'exp': NLIN_EXP, 'explinear': NLIN_EXPLINEAR}.get(nlin, nlin))
-    _chk(load().pgl_simulate_batch_dev(int(device), int(N), int(nT), int(R), kind, float(dt), vp(d_X0), vp(d_AW), int(n_rep),
-                                       int(rep0), int(seed), int(flags), vp(d_S), vp(d_X), vp(d_counts), vp(d_exceptions),
-                                       vp(d_workspace), vp(stream)))
+    _chk(load().pgl_simulate_batch_dev(int(device), int(N), int(nT), int(R), kind, float(dt), _dp(d_X0), _dp(d_AW),
+                                       int(n_rep), int(rep0), int(seed), int(flags), _dp(d_S), _dp(d_X), _dp(d_counts),
+                                       _dp(d_exceptions), _dp(d_workspace), _dp(stream)))
 
 
 class DeviceGlm(object):
     """One pgl_handle: the device-resident data of one data sequence
     (the Theano shared variables S / ir / stim of glm.py:17-18, impulse.py:41-42,
-    bkgd.py:70-71) plus the kernels that evaluate glm.ll and its gradient on it."""
+    bkgd.py:70-71) plus the kernels that evaluate glm.ll and its gradient on it.  Where a *_dev method's docstring
+    says "device pointer" or "integer", a torch device tensor serves as well (_dp)."""
 
     def __init__(self, N, nT, B, R, nlin, dt, device=0):
         self.lib = load()
@@ -546,16 +586,19 @@ class DeviceGlm(object):
         kernel: GEMM_NT, GEMM_MFMA_1, GEMM_MFMA_4, GEMM_KC_4_1_8 or GEMM_KC_1_0_16.  A, B, Cm: device addresses (int) of the
         first element; sa = (sam, sak, sAb), sb = (sbn, sbk, sBb), sc = (scm, scn, sCb), in doubles.  Asynchronous on the
         handle's stream; PglError where the kernel's preconditions do not hold (nothing is launched then)."""
-        _chk(self.lib.pgl_gemm_dev(self.h, int(kernel), C.c_void_p(A), int(sa[0]), int(sa[1]), int(sa[2]),
-                                   C.c_void_p(B), int(sb[0]), int(sb[1]), int(sb[2]),
-                                   C.c_void_p(Cm), int(sc[0]), int(sc[1]), int(sc[2]), int(M), int(N), int(K), int(batch)))
+        _chk(self.lib.pgl_gemm_dev(self.h, int(kernel), _dp(A), int(sa[0]), int(sa[1]), int(sa[2]), _dp(B), int(sb[0]),
+                                   int(sb[1]), int(sb[2]), _dp(Cm), int(sc[0]), int(sc[1]), int(sc[2]), int(M), int(N),
+                                   int(K), int(batch)))
+
+    def _draw(self, theta, Weff, rows=None):
+        """Host theta (rows, P) -- rows: every neuron's unless given -- and Weff (N, N) as contiguous float64 arrays."""
+        return _f64(theta, (self.N if rows is None else rows, self.P)), _f64(Weff, (self.N, self.N))
 
     # -- hot path -------------------------------------------------------------
     def ll_grad(self, theta, Weff, n_lo=0, n_hi=None, want_grad=True):
         n_hi = self.N if n_hi is None else n_hi
         npost = n_hi - n_lo
-        th = _f64(theta, (npost, self.P))
-        We = _f64(Weff, (self.N, self.N))
+        th, We = self._draw(theta, Weff, npost)
         ll = np.empty(npost)
         g = np.empty((npost, self.P)) if want_grad else None
         _chk(self.lib.pgl_ll_grad(self.h, int(n_lo), int(n_hi), _ptr(th), _ptr(We), _ptr(ll),
@@ -565,40 +608,35 @@ class DeviceGlm(object):
     def ll_grad_dev(self, d_theta, d_Weff, d_ll, d_grad, n_lo=0, n_hi=None):
         """Device-pointer form (integers, e.g. torch.Tensor.data_ptr()); asynchronous."""
         n_hi = self.N if n_hi is None else n_hi
-        _chk(self.lib.pgl_ll_grad_dev(self.h, int(n_lo), int(n_hi), C.c_void_p(d_theta),
-                                      C.c_void_p(d_Weff), C.c_void_p(d_ll),
-                                      C.c_void_p(d_grad) if d_grad else None))
+        _chk(self.lib.pgl_ll_grad_dev(self.h, int(n_lo), int(n_hi), _dp(d_theta), _dp(d_Weff), _dp(d_ll), _dp(d_grad)))
 
     def ll_grad_list_dev(self, d_idx, count, d_theta, d_Weff, d_ll, d_grad):
         """ll+grad of the `count` neurons listed in d_idx (device int32 pointer); row j of the device
         arrays belongs to neuron d_idx[j].  Asynchronous like ll_grad_dev."""
-        _chk(self.lib.pgl_ll_grad_list_dev(self.h, C.c_void_p(d_idx), int(count), C.c_void_p(d_theta),
-                                           C.c_void_p(d_Weff), C.c_void_p(d_ll),
-                                           C.c_void_p(d_grad) if d_grad else None))
+        _chk(self.lib.pgl_ll_grad_list_dev(self.h, _dp(d_idx), int(count), _dp(d_theta), _dp(d_Weff), _dp(d_ll),
+                                           _dp(d_grad)))
 
     # -- Hessian-vector products of ll (grads.py:68-95 hessian_rop_wrt_list) -------
     def hvp_prepare(self, d_theta, d_Weff, n_lo=0, n_hi=None, d_idx=0, count=None):
         """Curvature pass at theta (device pointers as integers; asynchronous): rows [n_lo, n_hi), or the `count` neurons
         listed in d_idx (device int32 pointer).  The curvature stays on the device for hvp_apply."""
         if d_idx:
-            _chk(self.lib.pgl_hvp_prepare_list_dev(self.h, C.c_void_p(d_idx), int(count), C.c_void_p(d_theta),
-                                                   C.c_void_p(d_Weff)))
+            _chk(self.lib.pgl_hvp_prepare_list_dev(self.h, _dp(d_idx), int(count), _dp(d_theta), _dp(d_Weff)))
             return
         n_hi = self.N if n_hi is None else n_hi
-        _chk(self.lib.pgl_hvp_prepare_dev(self.h, int(n_lo), int(n_hi), C.c_void_p(d_theta), C.c_void_p(d_Weff)))
+        _chk(self.lib.pgl_hvp_prepare_dev(self.h, int(n_lo), int(n_hi), _dp(d_theta), _dp(d_Weff)))
 
     def hvp_apply(self, d_v, d_hv):
         """d_hv = H . d_v for the prepared rows, (rows, P) each, theta layout (device pointers; asynchronous)."""
-        _chk(self.lib.pgl_hvp_apply_dev(self.h, C.c_void_p(d_v), C.c_void_p(d_hv)))
+        _chk(self.lib.pgl_hvp_apply_dev(self.h, _dp(d_v), _dp(d_hv)))
 
     def hvp(self, theta, v, Weff, n_lo=0, n_hi=None):
         """H . v of ll for rows [n_lo, n_hi) with host arrays: theta, v (rows, P), Weff (N, N) -> (rows, P).  Repeated
         calls with the same theta / Weff / range (a CG solve) reuse the curvature on the device."""
         n_hi = self.N if n_hi is None else n_hi
         npost = n_hi - n_lo
-        th = _f64(theta, (npost, self.P))
+        th, We = self._draw(theta, Weff, npost)
         vv = _f64(v, (npost, self.P))
-        We = _f64(Weff, (self.N, self.N))
         out = np.empty((npost, self.P))
         _chk(self.lib.pgl_hvp(self.h, int(n_lo), int(n_hi), _ptr(th), _ptr(vv), _ptr(We), _ptr(out)))
         return out
@@ -607,14 +645,13 @@ class DeviceGlm(object):
     def hess(self, d_H, ld=None):
         """d_H (rows, P, ld) = the Hessian of ll of every row of the last hvp_prepare, theta layout, both triangles (device
         pointer; asynchronous).  ld >= P, default P; the padding columns are not written."""
-        _chk(self.lib.pgl_hess_dev(self.h, C.c_void_p(d_H), int(self.P if ld is None else ld)))
+        _chk(self.lib.pgl_hess_dev(self.h, _dp(d_H), int(self.P if ld is None else ld)))
 
     def hessian(self, theta, Weff, n_lo=0, n_hi=None):
         """Hessian of ll for rows [n_lo, n_hi) with host arrays: theta (rows, P), Weff (N, N) -> (rows, P, P)."""
         n_hi = self.N if n_hi is None else n_hi
         npost = n_hi - n_lo
-        th = _f64(theta, (npost, self.P))
-        We = _f64(Weff, (self.N, self.N))
+        th, We = self._draw(theta, Weff, npost)
         out = np.empty((npost, self.P, self.P))
         _chk(self.lib.pgl_hess(self.h, int(n_lo), int(n_hi), _ptr(th), _ptr(We), _ptr(out)))
         return out
@@ -637,9 +674,7 @@ class DeviceGlm(object):
         scale = torch.empty((M, P), dtype=torch.float64, device=A.device)
         logdet = torch.empty(M, dtype=torch.float64, device=A.device)
         info = torch.empty(M, dtype=torch.int32, device=A.device)
-        _chk(self.lib.pgl_chol_factor_dev(self.h, C.c_void_p(A.data_ptr()), int(M), int(P), int(ld),
-                                          C.c_void_p(scale.data_ptr()), C.c_void_p(logdet.data_ptr()),
-                                          C.c_void_p(info.data_ptr())))
+        _chk(self.lib.pgl_chol_factor_dev(self.h, _dp(A), int(M), int(P), int(ld), _dp(scale), _dp(logdet), _dp(info)))
         return scale, logdet, info
 
     def tri_inverse(self, L, info):
@@ -650,8 +685,7 @@ class DeviceGlm(object):
                 tuple(info.shape) == (L.shape[0],)):
             raise ValueError("tri_inverse: info must be a contiguous int32 device tensor (M,)")
         M, P, ld = L.shape
-        _chk(self.lib.pgl_tri_inverse_dev(self.h, C.c_void_p(L.data_ptr()), int(M), int(P), int(ld),
-                                          C.c_void_p(info.data_ptr())))
+        _chk(self.lib.pgl_tri_inverse_dev(self.h, _dp(L), int(M), int(P), int(ld), _dp(info)))
 
     def chol_solve(self, Ls, scale, info, b, out=None):
         """x = A^-1 b for every matrix of the factor Ls (M, P, ld) with chol_factor's scale (M, P) and info (M,)
@@ -665,9 +699,7 @@ class DeviceGlm(object):
             if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous() and
                     tuple(t.shape) == shp):
                 raise ValueError("chol_solve: %s must be a contiguous %s device tensor %s" % (what, dt, shp))
-        _chk(self.lib.pgl_chol_solve_dev(self.h, C.c_void_p(Ls.data_ptr()), int(M), int(P), int(ld),
-                                         C.c_void_p(scale.data_ptr()), C.c_void_p(info.data_ptr()),
-                                         C.c_void_p(b.data_ptr()), C.c_void_p(out.data_ptr())))
+        _chk(self.lib.pgl_chol_solve_dev(self.h, _dp(Ls), int(M), int(P), int(ld), _dp(scale), _dp(info), _dp(b), _dp(out)))
         return out
 
     # -- time-rescaling goodness of fit (pgl_rescale*) ------------------------------
@@ -681,39 +713,36 @@ class DeviceGlm(object):
     def rescale_dev(self, d_theta, d_Weff, d_tau, d_off, d_stats):
         """Device-pointer form (integers; asynchronous): d_theta (N, P), d_Weff (N, N), d_off (N + 1) int64 = rescale_count(),
         d_tau (d_off[N]) out, d_stats (N, 4) out; see pgl_rescale_dev."""
-        _chk(self.lib.pgl_rescale_dev(self.h, C.c_void_p(d_theta), C.c_void_p(d_Weff), C.c_void_p(d_tau), C.c_void_p(d_off),
-                                      C.c_void_p(d_stats)))
+        _chk(self.lib.pgl_rescale_dev(self.h, _dp(d_theta), _dp(d_Weff), _dp(d_tau), _dp(d_off), _dp(d_stats)))
+
+    def _rescale(self, theta, Weff, call):
+        """(tau, off, stats) of rescale / rescale_corr; call(theta, Weff, tau, stats): the library call on their pointers."""
+        th, We = self._draw(theta, Weff)
+        off = self.rescale_count()
+        tau = np.empty(max(int(off[-1]), 1))
+        stats = np.empty((self.N, 4))
+        _chk(call(_ptr(th), _ptr(We), _ptr(tau), _ptr(stats)))
+        return tau[:int(off[-1])], off, stats
 
     def rescale(self, theta, Weff):
         """Rescaled inter-event intervals of every neuron over the current time range with host arrays: theta (N, P), Weff
         (N, N) -> (tau, off, stats): tau[off[n]:off[n + 1]] are neuron n's intervals, stats (N, 4) = expected count, event
         bins, event bins holding more than one spike, 0."""
-        th = _f64(theta, (self.N, self.P))
-        We = _f64(Weff, (self.N, self.N))
-        off = self.rescale_count()
-        tau = np.empty(max(int(off[-1]), 1))
-        stats = np.empty((self.N, 4))
-        _chk(self.lib.pgl_rescale(self.h, _ptr(th), _ptr(We), _ptr(tau), _ptr(stats)))
-        return tau[:int(off[-1])], off, stats
+        return self._rescale(theta, Weff, lambda th, We, tau, stats: self.lib.pgl_rescale(self.h, th, We, tau, stats))
 
     # -- discrete-time corrected intervals and the KS distance on the device (pgl_rescale_corr*, pgl_ks_uniform*) ----
     def rescale_corr_dev(self, d_theta, d_Weff, d_tau, d_off, d_stats, seed=0, draw=0):
         """rescale_dev with the discrete-time correction of the event bin's term at the uniforms of (seed, draw); see
         pgl_rescale_corr_dev.  The pointers are integers or torch device tensors."""
-        a = [C.c_void_p(x.data_ptr() if hasattr(x, 'data_ptr') else x) for x in (d_theta, d_Weff, d_tau, d_off, d_stats)]
-        _chk(self.lib.pgl_rescale_corr_dev(self.h, a[0], a[1], C.c_uint64(int(seed) & (2 ** 64 - 1)), int(draw), a[2], a[3], a[4]))
+        _chk(self.lib.pgl_rescale_corr_dev(self.h, _dp(d_theta), _dp(d_Weff), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                           int(draw), _dp(d_tau), _dp(d_off), _dp(d_stats)))
 
     def rescale_corr(self, theta, Weff, seed=0, draw=0):
         """rescale with the discrete-time correction: (tau', off, stats); tau' is a random function of seed and draw, the same
         bits for the same pair (pgl_rescale_corr)."""
-        th = _f64(theta, (self.N, self.P))
-        We = _f64(Weff, (self.N, self.N))
-        off = self.rescale_count()
-        tau = np.empty(max(int(off[-1]), 1))
-        stats = np.empty((self.N, 4))
-        _chk(self.lib.pgl_rescale_corr(self.h, _ptr(th), _ptr(We), C.c_uint64(int(seed) & (2 ** 64 - 1)), int(draw), _ptr(tau),
-                                       _ptr(stats)))
-        return tau[:int(off[-1])], off, stats
+        seed, draw = C.c_uint64(int(seed) & (2 ** 64 - 1)), int(draw)
+        return self._rescale(theta, Weff,
+                             lambda th, We, tau, stats: self.lib.pgl_rescale_corr(self.h, th, We, seed, draw, tau, stats))
 
     def ks_uniform(self, tau, off, out=None, zsorted=None):
         """KS distance from Exp(1) of the segments tau[off[m]:off[m + 1]] of the torch device tensors tau (f64) and off
@@ -722,36 +751,22 @@ class DeviceGlm(object):
         is written into, None lets the handle sort in a buffer of its own -- the call then waits once for the stream
         (pgl_ks_uniform_dev)."""
         import torch
-        if not (isinstance(tau, torch.Tensor) and tau.is_cuda and tau.dtype == torch.float64 and tau.dim() == 1 and
-                tau.is_contiguous()):
-            raise ValueError("ks_uniform: tau must be a contiguous float64 device vector")
-        if not (isinstance(off, torch.Tensor) and off.is_cuda and off.dtype == torch.int64 and off.dim() == 1 and
-                off.is_contiguous() and off.numel() >= 2):
-            raise ValueError("ks_uniform: off must be a contiguous int64 device vector (M + 1)")
+        _dev_tensor(tau, 'float64', "ks_uniform: tau must be a contiguous float64 device vector", ndim=1)
+        _dev_tensor(off, 'int64', "ks_uniform: off must be a contiguous int64 device vector (M + 1)", ndim=1, numel=2)
         M = int(off.numel()) - 1
         n_tau = int(tau.numel())
         src = tau if n_tau else torch.zeros(1, dtype=torch.float64, device=tau.device)     # (an empty tensor has no address)
-        if out is None:
-            out = torch.empty((M, KS_NOUT), dtype=torch.float64, device=tau.device)
-        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and
-                  tuple(out.shape) == (M, KS_NOUT)):
-            raise ValueError("ks_uniform: out must be a contiguous float64 device tensor (%d, %d)" % (M, KS_NOUT))
-        z = None
-        if zsorted is True:
-            z = torch.empty(max(int(tau.numel()), 1), dtype=torch.float64, device=tau.device)
-        elif zsorted is not None and zsorted is not False:
-            z = zsorted
-            if not (isinstance(z, torch.Tensor) and z.is_cuda and z.dtype == torch.float64 and z.is_contiguous() and
-                    z.numel() >= max(n_tau, 1)):
-                raise ValueError("ks_uniform: zsorted must be a contiguous float64 device vector of tau's length")
-        _chk(self.lib.pgl_ks_uniform_dev(self.h, C.c_void_p(src.data_ptr()), C.c_void_p(off.data_ptr()), M,
-                                         C.c_void_p(out.data_ptr()), C.c_void_p(z.data_ptr()) if z is not None else None))
+        out = _out_tensor(out, (M, KS_NOUT), tau,
+                          "ks_uniform: out must be a contiguous float64 device tensor (%d, %d)" % (M, KS_NOUT))
+        z = _second_out(zsorted, lambda: torch.empty(max(n_tau, 1), dtype=torch.float64, device=tau.device),
+                        lambda t: _dev_tensor(t, 'float64', numel=max(n_tau, 1), msg="ks_uniform: zsorted must be a contiguous "
+                                              "float64 device vector of tau's length"))
+        _chk(self.lib.pgl_ks_uniform_dev(self.h, _dp(src), _dp(off), M, _dp(out), _dp(z)))
         return (out, z[:n_tau]) if zsorted is True else out
 
     def ks_uniform_dev(self, d_tau, d_off, M, d_ks, d_zsorted=0):
-        """Device-pointer form (integers): see pgl_ks_uniform_dev."""
-        _chk(self.lib.pgl_ks_uniform_dev(self.h, C.c_void_p(d_tau), C.c_void_p(d_off), int(M), C.c_void_p(d_ks),
-                                         C.c_void_p(d_zsorted) if d_zsorted else None))
+        """Device-pointer form: see pgl_ks_uniform_dev."""
+        _chk(self.lib.pgl_ks_uniform_dev(self.h, _dp(d_tau), _dp(d_off), int(M), _dp(d_ks), _dp(d_zsorted)))
 
     def ks_uniform_host(self, tau, off, zsorted=False):
         """The same with host arrays: -> ks (M, 4), or (ks, z) with zsorted=True (pgl_ks_uniform)."""
@@ -774,13 +789,9 @@ class DeviceGlm(object):
         given.  scores: True returns (out, g) with every normal score, a tensor of tau's length is written into, None uses a
         fresh one.  Asynchronous on the handle's stream (pgl_rescale_acf_dev)."""
         import torch
-        if not (isinstance(tau, torch.Tensor) and tau.is_cuda and tau.dtype == torch.float64 and tau.dim() == 1 and
-                tau.is_contiguous()):
-            raise ValueError("rescale_acf: tau must be a contiguous float64 device vector")
+        _dev_tensor(tau, 'float64', "rescale_acf: tau must be a contiguous float64 device vector", ndim=1)
         for name, o in (('run_off', run_off), ('seg_run', seg_run)):
-            if not (isinstance(o, torch.Tensor) and o.is_cuda and o.dtype == torch.int64 and o.dim() == 1 and
-                    o.is_contiguous() and o.numel() >= 1):
-                raise ValueError("rescale_acf: %s must be a contiguous int64 device vector" % name)
+            _dev_tensor(o, 'int64', "rescale_acf: %s must be a contiguous int64 device vector" % name, ndim=1, numel=1)
         if seg_run.numel() < 2:
             raise ValueError("rescale_acf: seg_run holds M + 1 >= 2 offsets")
         L = int(max_lag)
@@ -789,26 +800,18 @@ class DeviceGlm(object):
         M = int(seg_run.numel()) - 1
         n_tau = int(tau.numel())
         src = tau if n_tau else torch.zeros(1, dtype=torch.float64, device=tau.device)     # (an empty tensor has no address)
-        if out is None:
-            out = torch.empty((M, ACF_NHEAD + L), dtype=torch.float64, device=tau.device)
-        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and
-                  tuple(out.shape) == (M, ACF_NHEAD + L)):
-            raise ValueError("rescale_acf: out must be a contiguous float64 device tensor (%d, %d)" % (M, ACF_NHEAD + L))
-        if scores is None or scores is True:
-            g = torch.empty(max(n_tau, 1), dtype=torch.float64, device=tau.device)
-        else:
-            g = scores
-            if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == torch.float64 and g.is_contiguous() and
-                    g.numel() >= max(n_tau, 1)):
-                raise ValueError("rescale_acf: scores must be a contiguous float64 device vector of tau's length")
-        _chk(self.lib.pgl_rescale_acf_dev(self.h, C.c_void_p(src.data_ptr()), C.c_void_p(run_off.data_ptr()),
-                                          C.c_void_p(seg_run.data_ptr()), M, L, C.c_void_p(out.data_ptr()), C.c_void_p(g.data_ptr())))
+        out = _out_tensor(out, (M, ACF_NHEAD + L), tau,
+                          "rescale_acf: out must be a contiguous float64 device tensor (%d, %d)" % (M, ACF_NHEAD + L))
+        g = _second_out(scores, lambda: torch.empty(max(n_tau, 1), dtype=torch.float64, device=tau.device),
+                        lambda t: _dev_tensor(t, 'float64', numel=max(n_tau, 1), msg="rescale_acf: scores must be a contiguous "
+                                              "float64 device vector of tau's length"), none_is_fresh=True)
+        _chk(self.lib.pgl_rescale_acf_dev(self.h, _dp(src), _dp(run_off), _dp(seg_run), M, L, _dp(out), _dp(g)))
         return (out, g[:n_tau]) if scores is True else out
 
     def rescale_acf_dev(self, d_tau, d_run_off, d_seg_run, M, max_lag, d_out, d_scores):
-        """Device-pointer form (integers): see pgl_rescale_acf_dev."""
-        _chk(self.lib.pgl_rescale_acf_dev(self.h, C.c_void_p(d_tau), C.c_void_p(d_run_off), C.c_void_p(d_seg_run), int(M),
-                                          int(max_lag), C.c_void_p(d_out), C.c_void_p(d_scores)))
+        """Device-pointer form: see pgl_rescale_acf_dev."""
+        _chk(self.lib.pgl_rescale_acf_dev(self.h, _dp(d_tau), _dp(d_run_off), _dp(d_seg_run), int(M), int(max_lag),
+                                          _dp(d_out), _dp(d_scores)))
 
     def rescale_acf_host(self, tau, run_off, seg_run, max_lag, scores=False):
         """The same with host arrays: -> out (M, 6 + max_lag), or (out, g) with scores=True (pgl_rescale_acf)."""
@@ -836,15 +839,13 @@ class DeviceGlm(object):
     def pointwise_dev(self, d_theta, d_Weff, block_chunks, d_ll_blk=0, d_acc=0, draw=0):
         """Device-pointer form (integers; asynchronous): d_theta (N, P), d_Weff (N, N), d_ll_blk (n_blocks, N) out or 0,
         d_acc (4, n_blocks, N) in/out or 0 with the index `draw` of this draw; see pgl_pointwise_dev."""
-        _chk(self.lib.pgl_pointwise_dev(self.h, C.c_void_p(d_theta), C.c_void_p(d_Weff), int(block_chunks),
-                                        C.c_void_p(d_ll_blk) if d_ll_blk else None, C.c_void_p(d_acc) if d_acc else None,
+        _chk(self.lib.pgl_pointwise_dev(self.h, _dp(d_theta), _dp(d_Weff), int(block_chunks), _dp(d_ll_blk), _dp(d_acc),
                                         int(draw)))
 
     def pointwise(self, theta, Weff, block_chunks=1):
         """Block sums of the log-likelihood terms of every neuron over the current time range with host arrays: theta
         (N, P), Weff (N, N) -> (n_blocks, N)."""
-        th = _f64(theta, (self.N, self.P))
-        We = _f64(Weff, (self.N, self.N))
+        th, We = self._draw(theta, Weff)
         out = np.empty((self.pointwise_count(block_chunks), self.N))
         _chk(self.lib.pgl_pointwise(self.h, _ptr(th), _ptr(We), int(block_chunks), _ptr(out)))
         return out
@@ -859,15 +860,13 @@ class DeviceGlm(object):
     def rate_windows_dev(self, d_theta, d_Weff, win, d_lam=0, d_obs=0, d_acc=0, draw=0):
         """Device-pointer form (integers; asynchronous): d_theta (N, P), d_Weff (N, N), d_lam and d_obs (n_win, N) out or 0,
         d_acc (RW_NACC, n_win, N) in/out or 0 with the index `draw` of this draw; see pgl_rate_windows_dev."""
-        _chk(self.lib.pgl_rate_windows_dev(self.h, C.c_void_p(d_theta) if d_theta else None, C.c_void_p(d_Weff) if d_Weff else None,
-                                           int(win), C.c_void_p(d_lam) if d_lam else None, C.c_void_p(d_obs) if d_obs else None,
-                                           C.c_void_p(d_acc) if d_acc else None, int(draw)))
+        _chk(self.lib.pgl_rate_windows_dev(self.h, _dp(d_theta), _dp(d_Weff), int(win), _dp(d_lam), _dp(d_obs), _dp(d_acc),
+                                           int(draw)))
 
     def rate_windows(self, theta, Weff, win):
         """Expected and observed spike counts of every neuron over windows of `win` bins of the current time range with host
         arrays: theta (N, P), Weff (N, N) -> (Lam, obs), each (n_win, N)."""
-        th = _f64(theta, (self.N, self.P))
-        We = _f64(Weff, (self.N, self.N))
+        th, We = self._draw(theta, Weff)
         n_win = self.rate_windows_count(win)
         lam = np.empty((n_win, self.N))
         obs = np.empty((n_win, self.N))
@@ -883,28 +882,18 @@ class DeviceGlm(object):
         weights=True also returns the log weights, a tensor of ll's shape and strides; weights=<tensor of ll's shape and
         strides> writes them there (it must not overlap ll).  Asynchronous on the handle's stream."""
         import torch
-        if not (isinstance(ll, torch.Tensor) and ll.is_cuda and ll.dtype == torch.float64 and ll.dim() >= 2 and ll.numel() > 0):
-            raise ValueError("psis_loo: a float64 device tensor (S, ...)")
+        _dev_tensor(ll, 'float64', "psis_loo: a float64 device tensor (S, ...)", min_ndim=2, numel=1, contiguous=False)
         S, shape = int(ll.shape[0]), tuple(ll.shape[1:])
         ncol = int(np.prod(shape))
         ld = int(ll.stride(0))
         if not ll[0].is_contiguous() or ld < ncol:
             raise ValueError("psis_loo: the trailing axes must be contiguous and the draw stride at least their size")
-        if out is None:
-            out = torch.empty((PSIS_NOUT,) + shape, dtype=torch.float64, device=ll.device)
-        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and
-                  tuple(out.shape) == (PSIS_NOUT,) + shape):
-            raise ValueError("psis_loo: out must be a contiguous float64 device tensor %s" % ((PSIS_NOUT,) + shape,))
-        lw = None
-        if weights is True:
-            lw = torch.empty_strided(tuple(ll.shape), tuple(ll.stride()), dtype=torch.float64, device=ll.device)
-        elif weights is not False and weights is not None:
-            lw = weights
-            if not (isinstance(lw, torch.Tensor) and lw.is_cuda and lw.dtype == torch.float64 and lw.shape == ll.shape and
-                    lw.stride() == ll.stride()):
-                raise ValueError("psis_loo: weights must be a float64 device tensor of ll's shape and strides")
-        _chk(self.lib.pgl_psis_loo_dev(self.h, C.c_void_p(ll.data_ptr()), S, ncol, ld, C.c_void_p(out.data_ptr()),
-                                       C.c_void_p(lw.data_ptr()) if lw is not None else None))
+        out = _out_tensor(out, (PSIS_NOUT,) + shape, ll,
+                          "psis_loo: out must be a contiguous float64 device tensor %s" % ((PSIS_NOUT,) + shape,))
+        lw = _second_out(weights, lambda: torch.empty_strided(tuple(ll.shape), ll.stride(), dtype=torch.float64, device=ll.device),
+                         lambda t: _dev_tensor(t, 'float64', "psis_loo: weights must be a float64 device tensor of ll's shape and "
+                                               "strides", shape=ll.shape, strides=ll.stride(), contiguous=False))
+        _chk(self.lib.pgl_psis_loo_dev(self.h, _dp(ll), S, ncol, ld, _dp(out), _dp(lw)))
         return out if lw is None else (out, lw)
 
     def psis_loo_host(self, ll, weights=False):
@@ -927,8 +916,8 @@ class DeviceGlm(object):
         in DIAG_ROWS order; `out`: a contiguous tensor of that shape to write into.  Asynchronous on the handle's stream."""
         import torch
         nc = int(n_chains)
-        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float64 and x.dim() >= 2 and x.numel() > 0):
-            raise ValueError("chain_diag: a float64 device tensor (n, n_chains * M, ...)")
+        _dev_tensor(x, 'float64', "chain_diag: a float64 device tensor (n, n_chains * M, ...)", min_ndim=2, numel=1,
+                    contiguous=False)
         if nc < 1 or x.shape[1] % nc:
             raise ValueError("chain_diag: axis 1 must hold n_chains blocks of rows")
         n, shape = int(x.shape[0]), (int(x.shape[1]) // nc,) + tuple(x.shape[2:])
@@ -938,12 +927,9 @@ class DeviceGlm(object):
         if nc > 1 and int(x.stride(0)) != nc * K:
             raise ValueError("chain_diag: with n_chains > 1 the draws must be contiguous")
         ld = int(x.stride(0)) // nc
-        if out is None:
-            out = torch.empty((DIAG_NOUT,) + shape, dtype=torch.float64, device=x.device)
-        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and
-                  tuple(out.shape) == (DIAG_NOUT,) + shape):
-            raise ValueError("chain_diag: out must be a contiguous float64 device tensor %s" % ((DIAG_NOUT,) + shape,))
-        _chk(self.lib.pgl_chain_diag_dev(self.h, C.c_void_p(x.data_ptr()), n, nc, K, ld, C.c_void_p(out.data_ptr())))
+        out = _out_tensor(out, (DIAG_NOUT,) + shape, x,
+                          "chain_diag: out must be a contiguous float64 device tensor %s" % ((DIAG_NOUT,) + shape,))
+        _chk(self.lib.pgl_chain_diag_dev(self.h, _dp(x), n, nc, K, ld, _dp(out)))
         return out
 
     def chain_diag_host(self, x, n_chains=1):
@@ -962,103 +948,87 @@ class DeviceGlm(object):
         return int(self.lib.pgl_bfgs_state_doubles(int(M), int(P)))
 
     def bfgs_trial_dev(self, d_state, M, P, d_rows, L, d_Xt):
-        _chk(self.lib.pgl_bfgs_trial_dev(self.h, C.c_void_p(d_state), int(M), int(P),
-                                         C.c_void_p(d_rows) if d_rows else None, int(L), C.c_void_p(d_Xt)))
+        _chk(self.lib.pgl_bfgs_trial_dev(self.h, _dp(d_state), int(M), int(P), _dp(d_rows), int(L), _dp(d_Xt)))
 
     # prior, here and below: a Prior or the tuple of _Packing.prior_params() (as_prior)
     def bfgs_objective_dev(self, L, P, d_Xt, d_ll_f, d_grad_g, prior):
-        _chk(self.lib.pgl_bfgs_objective_dev(self.h, int(L), int(P), C.c_void_p(d_Xt), C.c_void_p(d_ll_f),
-                                             C.c_void_p(d_grad_g), C.byref(as_prior(prior))))
+        _chk(self.lib.pgl_bfgs_objective_dev(self.h, int(L), int(P), _dp(d_Xt), _dp(d_ll_f), _dp(d_grad_g),
+                                             C.byref(as_prior(prior))))
 
     def bfgs_init_dev(self, d_state, M, P, gtol):
-        _chk(self.lib.pgl_bfgs_init_dev(self.h, C.c_void_p(d_state), int(M), int(P), float(gtol)))
+        _chk(self.lib.pgl_bfgs_init_dev(self.h, _dp(d_state), int(M), int(P), float(gtol)))
 
     def bfgs_linesearch_dev(self, d_state, M, P, d_rows, L, d_Xt, d_f, d_g, max_trials=100):
-        _chk(self.lib.pgl_bfgs_linesearch_dev(self.h, C.c_void_p(d_state), int(M), int(P),
-                                              C.c_void_p(d_rows) if d_rows else None, int(L), C.c_void_p(d_Xt),
-                                              C.c_void_p(d_f), C.c_void_p(d_g), int(max_trials)))
+        _chk(self.lib.pgl_bfgs_linesearch_dev(self.h, _dp(d_state), int(M), int(P), _dp(d_rows), int(L), _dp(d_Xt), _dp(d_f),
+                                              _dp(d_g), int(max_trials)))
 
     def bfgs_hmul_dev(self, d_state, M, P, d_rows, L, d_H, ld):
-        _chk(self.lib.pgl_bfgs_hmul_dev(self.h, C.c_void_p(d_state), int(M), int(P),
-                                        C.c_void_p(d_rows) if d_rows else None, int(L), C.c_void_p(d_H), int(ld)))
+        _chk(self.lib.pgl_bfgs_hmul_dev(self.h, _dp(d_state), int(M), int(P), _dp(d_rows), int(L), _dp(d_H), int(ld)))
 
     def bfgs_hmul_hist_dev(self, d_state, M, P, d_rows, L, d_hist, d_coef, Kmax, d_ab):
-        _chk(self.lib.pgl_bfgs_hmul_hist_dev(self.h, C.c_void_p(d_state), int(M), int(P),
-                                             C.c_void_p(d_rows) if d_rows else None, int(L), C.c_void_p(d_hist),
-                                             C.c_void_p(d_coef), int(Kmax), C.c_void_p(d_ab)))
+        _chk(self.lib.pgl_bfgs_hmul_hist_dev(self.h, _dp(d_state), int(M), int(P), _dp(d_rows), int(L), _dp(d_hist),
+                                             _dp(d_coef), int(Kmax), _dp(d_ab)))
 
     def bfgs_update_dev(self, d_state, M, P, gtol, maxiter, init_scaling=False, d_hist=0, d_coef=0, Kmax=0):
-        _chk(self.lib.pgl_bfgs_update_dev(self.h, C.c_void_p(d_state), int(M), int(P), float(gtol), int(maxiter),
-                                          1 if init_scaling else 0, C.c_void_p(d_hist) if d_hist else None,
-                                          C.c_void_p(d_coef) if d_coef else None, int(Kmax)))
+        _chk(self.lib.pgl_bfgs_update_dev(self.h, _dp(d_state), int(M), int(P), float(gtol), int(maxiter),
+                                          1 if init_scaling else 0, _dp(d_hist), _dp(d_coef), int(Kmax)))
 
     def bfgs_step_dev(self, d_state, M, P, d_rows, L, d_Xt, d_f, d_g, prior=None, max_trials=100, gtol=1e-5, maxiter=225,
                       init_scaling=False, d_hist=0, d_coef=0, Kmax=0, d_ab=0, hk_bound=0, d_H=0, ld=0, d_pos_next=0,
                       d_Xt_next=0, flags_out=0):
         """One whole optimiser iteration behind an evaluation (pgl_bfgs_step_dev).  prior: as for bfgs_objective_dev, or
         None when d_f / d_g already hold the objective and its gradient."""
-        vp = lambda a: C.c_void_p(a) if a else None
         pr = (-1, 0.0, 1.0, 1.0, 0.0, 1.0, 0.0) if prior is None else prior
-        _chk(self.lib.pgl_bfgs_step_dev(self.h, C.c_void_p(d_state), int(M), int(P), vp(d_rows), int(L), C.c_void_p(d_Xt),
-                                        C.c_void_p(d_f), C.c_void_p(d_g), C.byref(as_prior(pr)), int(max_trials), float(gtol), int(maxiter), 1 if init_scaling else 0, vp(d_hist),
-                                        vp(d_coef), int(Kmax), vp(d_ab), int(hk_bound), vp(d_H), int(ld), vp(d_pos_next),
-                                        vp(d_Xt_next), vp(flags_out)))
+        _chk(self.lib.pgl_bfgs_step_dev(self.h, _dp(d_state), int(M), int(P), _dp(d_rows), int(L), _dp(d_Xt), _dp(d_f),
+                                        _dp(d_g), C.byref(as_prior(pr)), int(max_trials), float(gtol), int(maxiter),
+                                        1 if init_scaling else 0, _dp(d_hist), _dp(d_coef), int(Kmax), _dp(d_ab),
+                                        int(hk_bound), _dp(d_H), int(ld), _dp(d_pos_next), _dp(d_Xt_next), _dp(flags_out)))
 
     # -- lock-step Newton-CG row kernels (pgl_ncg_*; inference/batched_newton_cg.py)
     def ncg_state_doubles(self, M, P):
         return int(self.lib.pgl_ncg_state_doubles(int(M), int(P)))
 
     def ncg_init_dev(self, d_state, M, P, d_ll, d_grad, prior, maxiter, d_V, flags_out=0):
-        _chk(self.lib.pgl_ncg_init_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_ll), C.c_void_p(d_grad),
-                                       C.byref(as_prior(prior)), int(maxiter), C.c_void_p(d_V),
-                                       C.c_void_p(flags_out) if flags_out else None))
+        _chk(self.lib.pgl_ncg_init_dev(self.h, _dp(d_state), int(M), int(P), _dp(d_ll), _dp(d_grad),
+                                       C.byref(as_prior(prior)), int(maxiter), _dp(d_V), _dp(flags_out)))
 
     def ncg_cg_step_dev(self, d_state, M, P, d_hv, prior, d_V, flags_out=0):
-        _chk(self.lib.pgl_ncg_cg_step_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_hv),
-                                          C.byref(as_prior(prior)), C.c_void_p(d_V),
-                                          C.c_void_p(flags_out) if flags_out else None))
+        _chk(self.lib.pgl_ncg_cg_step_dev(self.h, _dp(d_state), int(M), int(P), _dp(d_hv), C.byref(as_prior(prior)),
+                                          _dp(d_V), _dp(flags_out)))
 
     def ncg_trial_dev(self, d_state, M, P, d_rows, L, d_Xt):
-        _chk(self.lib.pgl_ncg_trial_dev(self.h, C.c_void_p(d_state), int(M), int(P),
-                                        C.c_void_p(d_rows) if d_rows else None, int(L), C.c_void_p(d_Xt)))
+        _chk(self.lib.pgl_ncg_trial_dev(self.h, _dp(d_state), int(M), int(P), _dp(d_rows), int(L), _dp(d_Xt)))
 
     def ncg_search_step_dev(self, d_state, M, P, d_rows, L, d_Xt, d_f, d_g, prior, maxiter, d_pos_next, d_Xt_next, d_V,
                             flags_out=0):
-        vp = lambda a: C.c_void_p(a) if a else None
-        _chk(self.lib.pgl_ncg_search_step_dev(self.h, C.c_void_p(d_state), int(M), int(P), vp(d_rows), int(L),
-                                              C.c_void_p(d_Xt), C.c_void_p(d_f), C.c_void_p(d_g), C.byref(as_prior(prior)),
-                                              int(maxiter), vp(d_pos_next), vp(d_Xt_next), C.c_void_p(d_V), vp(flags_out)))
+        _chk(self.lib.pgl_ncg_search_step_dev(self.h, _dp(d_state), int(M), int(P), _dp(d_rows), int(L), _dp(d_Xt), _dp(d_f),
+                                              _dp(d_g), C.byref(as_prior(prior)), int(maxiter), _dp(d_pos_next),
+                                              _dp(d_Xt_next), _dp(d_V), _dp(flags_out)))
 
     # -- lock-step dense Newton row kernels (pgl_newton_*; inference/batched_newton.py); device pointers
     def newton_state_doubles(self, M, P):
         return int(self.lib.pgl_newton_state_doubles(int(M), int(P)))
 
     def newton_init_dev(self, d_state, M, P, d_ll, d_grad, prior, gtol, maxiter, flags_out=0):
-        _chk(self.lib.pgl_newton_init_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_ll), C.c_void_p(d_grad),
-                                          C.byref(as_prior(prior)), float(gtol), int(maxiter),
-                                          C.c_void_p(flags_out) if flags_out else None))
+        _chk(self.lib.pgl_newton_init_dev(self.h, _dp(d_state), int(M), int(P), _dp(d_ll), _dp(d_grad),
+                                          C.byref(as_prior(prior)), float(gtol), int(maxiter), _dp(flags_out)))
 
     def newton_assemble_dev(self, d_state, M, P, d_rows, L, d_H, ld, prior, d_rhs=0):
-        vp = lambda a: C.c_void_p(a) if a else None
-        _chk(self.lib.pgl_newton_assemble_dev(self.h, C.c_void_p(d_state), int(M), int(P), vp(d_rows), int(L), C.c_void_p(d_H),
-                                              int(ld), C.byref(as_prior(prior)), vp(d_rhs)))
+        _chk(self.lib.pgl_newton_assemble_dev(self.h, _dp(d_state), int(M), int(P), _dp(d_rows), int(L), _dp(d_H), int(ld),
+                                              C.byref(as_prior(prior)), _dp(d_rhs)))
 
     def newton_direction_dev(self, d_state, M, P, d_rows, L, d_info, d_p, flags_out=0):
-        vp = lambda a: C.c_void_p(a) if a else None
-        _chk(self.lib.pgl_newton_direction_dev(self.h, C.c_void_p(d_state), int(M), int(P), vp(d_rows), int(L),
-                                               C.c_void_p(d_info), C.c_void_p(d_p), vp(flags_out)))
+        _chk(self.lib.pgl_newton_direction_dev(self.h, _dp(d_state), int(M), int(P), _dp(d_rows), int(L), _dp(d_info),
+                                               _dp(d_p), _dp(flags_out)))
 
     def newton_trial_dev(self, d_state, M, P, d_rows, L, d_Xt):
-        _chk(self.lib.pgl_newton_trial_dev(self.h, C.c_void_p(d_state), int(M), int(P),
-                                           C.c_void_p(d_rows) if d_rows else None, int(L), C.c_void_p(d_Xt)))
+        _chk(self.lib.pgl_newton_trial_dev(self.h, _dp(d_state), int(M), int(P), _dp(d_rows), int(L), _dp(d_Xt)))
 
     def newton_search_step_dev(self, d_state, M, P, d_rows, L, d_Xt, d_f, d_g, prior, gtol, maxiter, d_pos_next, d_Xt_next,
                                flags_out=0):
-        vp = lambda a: C.c_void_p(a) if a else None
-        _chk(self.lib.pgl_newton_search_step_dev(self.h, C.c_void_p(d_state), int(M), int(P), vp(d_rows), int(L),
-                                                 C.c_void_p(d_Xt), C.c_void_p(d_f), C.c_void_p(d_g),
-                                                 C.byref(as_prior(prior)), float(gtol), int(maxiter), vp(d_pos_next),
-                                                 vp(d_Xt_next), vp(flags_out)))
+        _chk(self.lib.pgl_newton_search_step_dev(self.h, _dp(d_state), int(M), int(P), _dp(d_rows), int(L), _dp(d_Xt),
+                                                 _dp(d_f), _dp(d_g), C.byref(as_prior(prior)), float(gtol), int(maxiter),
+                                                 _dp(d_pos_next), _dp(d_Xt_next), _dp(flags_out)))
 
     # -- lock-step HMC row kernels (pgl_hmc_*; inference/batched_hmc.py); device pointers.  n_chains = C: the run has R = C M
     # rows, chain c of neuron n_lo + m is row c M + m, and every call after init takes R as its M
@@ -1066,19 +1036,16 @@ class DeviceGlm(object):
         return int(self.lib.pgl_hmc_state_doubles(int(M), int(P)))
 
     def hmc_init_dev(self, d_state, M, P, n_lo, d_ll, d_grad, prior, step0, seed, n_chains=1):
-        _chk(self.lib.pgl_hmc_init_dev(self.h, C.c_void_p(d_state), int(M), int(n_chains), int(P), int(n_lo),
-                                       C.c_void_p(d_ll), C.c_void_p(d_grad), C.byref(as_prior(prior)), float(step0),
-                                       int(seed) & 0xffffffffffffffff))
+        _chk(self.lib.pgl_hmc_init_dev(self.h, _dp(d_state), int(M), int(n_chains), int(P), int(n_lo), _dp(d_ll),
+                                       _dp(d_grad), C.byref(as_prior(prior)), float(step0), int(seed) & 0xffffffffffffffff))
 
     def hmc_begin_dev(self, d_state, M, P, d_minv, d_Xt):
-        _chk(self.lib.pgl_hmc_begin_dev(self.h, C.c_void_p(d_state), int(M), int(P),
-                                        C.c_void_p(d_minv) if d_minv else None, C.c_void_p(d_Xt)))
+        _chk(self.lib.pgl_hmc_begin_dev(self.h, _dp(d_state), int(M), int(P), _dp(d_minv), _dp(d_Xt)))
 
     def hmc_leap_dev(self, d_state, M, P, d_minv, d_ll, d_grad, prior, last, n_warmup, d_Xt, d_sample_out=0):
-        _chk(self.lib.pgl_hmc_leap_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_minv) if d_minv else None,
-                                       C.c_void_p(d_ll), C.c_void_p(d_grad), C.byref(as_prior(prior)),
-                                       1 if last else 0, int(n_warmup), C.c_void_p(d_Xt),
-                                       C.c_void_p(d_sample_out) if d_sample_out else None))
+        _chk(self.lib.pgl_hmc_leap_dev(self.h, _dp(d_state), int(M), int(P), _dp(d_minv), _dp(d_ll), _dp(d_grad),
+                                       C.byref(as_prior(prior)), 1 if last else 0, int(n_warmup), _dp(d_Xt),
+                                       _dp(d_sample_out)))
 
     # -- NUTS row kernels (pgl_nuts_*; inference/batched_nuts.py).  d_minv (M, P) or d_W (M, P, P) or neither; device pointers;
     # n_chains as for hmc_init_dev (d_minv, d_W: one per row)
@@ -1087,20 +1054,16 @@ class DeviceGlm(object):
 
     def nuts_init_dev(self, d_state, M, P, max_depth, n_lo, d_ll, d_grad, prior, d_minv, d_W, d_step0, seed, n_warmup, thin,
                       n_keep, d_Xt, n_chains=1):
-        _chk(self.lib.pgl_nuts_init_dev(self.h, C.c_void_p(d_state), int(M), int(n_chains), int(P), int(max_depth), int(n_lo),
-                                        C.c_void_p(d_ll), C.c_void_p(d_grad), C.byref(as_prior(prior)),
-                                        C.c_void_p(d_minv) if d_minv else None, C.c_void_p(d_W) if d_W else None,
-                                        C.c_void_p(d_step0), int(seed) & 0xffffffffffffffff, int(n_warmup), int(thin),
-                                        int(n_keep), C.c_void_p(d_Xt)))
+        _chk(self.lib.pgl_nuts_init_dev(self.h, _dp(d_state), int(M), int(n_chains), int(P), int(max_depth), int(n_lo),
+                                        _dp(d_ll), _dp(d_grad), C.byref(as_prior(prior)), _dp(d_minv), _dp(d_W),
+                                        _dp(d_step0), int(seed) & 0xffffffffffffffff, int(n_warmup), int(thin), int(n_keep),
+                                        _dp(d_Xt)))
 
     def nuts_step_dev(self, d_state, M, P, max_depth, d_ll, d_grad, prior, d_minv, d_W, target_accept, n_warmup, thin, n_keep,
                       d_Xt, d_samples=0, d_stats=0):
-        _chk(self.lib.pgl_nuts_step_dev(self.h, C.c_void_p(d_state), int(M), int(P), int(max_depth), C.c_void_p(d_ll),
-                                        C.c_void_p(d_grad), C.byref(as_prior(prior)),
-                                        C.c_void_p(d_minv) if d_minv else None, C.c_void_p(d_W) if d_W else None,
-                                        float(target_accept), int(n_warmup), int(thin), int(n_keep), C.c_void_p(d_Xt),
-                                        C.c_void_p(d_samples) if d_samples else None,
-                                        C.c_void_p(d_stats) if d_stats else None))
+        _chk(self.lib.pgl_nuts_step_dev(self.h, _dp(d_state), int(M), int(P), int(max_depth), _dp(d_ll), _dp(d_grad),
+                                        C.byref(as_prior(prior)), _dp(d_minv), _dp(d_W), float(target_accept), int(n_warmup),
+                                        int(thin), int(n_keep), _dp(d_Xt), _dp(d_samples), _dp(d_stats)))
 
     # -- the warm-up mass adaptation (csrc/pglm_adapt.h) over the R rows of a run; d_adapt: adapt_state_doubles(R, P) zeroed
     # doubles; d_sched: mass_adapt.schedule_ints on the device
@@ -1108,31 +1071,27 @@ class DeviceGlm(object):
         return int(self.lib.pgl_adapt_state_doubles(int(R), int(P)))
 
     def mass_adapt_dev(self, d_state, R, P, d_adapt, d_sched, d_minv):
-        _chk(self.lib.pgl_mass_adapt_dev(self.h, C.c_void_p(d_state), int(R), int(P), C.c_void_p(d_adapt), C.c_void_p(d_sched),
-                                         C.c_void_p(d_minv)))
+        _chk(self.lib.pgl_mass_adapt_dev(self.h, _dp(d_state), int(R), int(P), _dp(d_adapt), _dp(d_sched), _dp(d_minv)))
 
     def nuts_adapt_step_dev(self, d_state, R, P, max_depth, d_ll, d_grad, prior, d_minv, d_adapt, d_sched, target_accept,
                             n_warmup, thin, n_keep, d_Xt, d_samples=0, d_stats=0):
-        _chk(self.lib.pgl_nuts_adapt_step_dev(self.h, C.c_void_p(d_state), int(R), int(P), int(max_depth), C.c_void_p(d_ll),
-                                              C.c_void_p(d_grad), C.byref(as_prior(prior)),
-                                              C.c_void_p(d_minv), C.c_void_p(d_adapt), C.c_void_p(d_sched),
-                                              float(target_accept), int(n_warmup), int(thin), int(n_keep), C.c_void_p(d_Xt),
-                                              C.c_void_p(d_samples) if d_samples else None,
-                                              C.c_void_p(d_stats) if d_stats else None))
+        _chk(self.lib.pgl_nuts_adapt_step_dev(self.h, _dp(d_state), int(R), int(P), int(max_depth), _dp(d_ll), _dp(d_grad),
+                                              C.byref(as_prior(prior)), _dp(d_minv), _dp(d_adapt), _dp(d_sched),
+                                              float(target_accept), int(n_warmup), int(thin), int(n_keep), _dp(d_Xt),
+                                              _dp(d_samples), _dp(d_stats)))
 
     # -- the same chain with a dense mass matrix (pgl_hmc_dense_*): d_W (M, P, P) lower-triangular factors of the inverse
     # mass matrices
     def tri_matvec_dev(self, d_W, M, P, trans, d_x, d_y):
-        _chk(self.lib.pgl_tri_matvec_dev(self.h, C.c_void_p(d_W), int(M), int(P), 1 if trans else 0, C.c_void_p(d_x),
-                                         C.c_void_p(d_y)))
+        _chk(self.lib.pgl_tri_matvec_dev(self.h, _dp(d_W), int(M), int(P), 1 if trans else 0, _dp(d_x), _dp(d_y)))
 
     def hmc_dense_begin_dev(self, d_state, M, P, d_W, d_Xt):
-        _chk(self.lib.pgl_hmc_dense_begin_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_W), C.c_void_p(d_Xt)))
+        _chk(self.lib.pgl_hmc_dense_begin_dev(self.h, _dp(d_state), int(M), int(P), _dp(d_W), _dp(d_Xt)))
 
     def hmc_dense_leap_dev(self, d_state, M, P, d_W, d_ll, d_grad, prior, last, n_warmup, d_Xt, d_sample_out=0):
-        _chk(self.lib.pgl_hmc_dense_leap_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_W), C.c_void_p(d_ll),
-                                             C.c_void_p(d_grad), C.byref(as_prior(prior)), 1 if last else 0, int(n_warmup),
-                                             C.c_void_p(d_Xt), C.c_void_p(d_sample_out) if d_sample_out else None))
+        _chk(self.lib.pgl_hmc_dense_leap_dev(self.h, _dp(d_state), int(M), int(P), _dp(d_W), _dp(d_ll), _dp(d_grad),
+                                             C.byref(as_prior(prior)), 1 if last else 0, int(n_warmup), _dp(d_Xt),
+                                             _dp(d_sample_out)))
 
     # -- lock-step proximal gradient row kernels for the group-lasso MAP (pgl_prox_*; inference/batched_prox.py).  prior:
     # kind 1, its lam unused (_prox_prior); d_lam: (M) device, one lam per row; flags_out: pinned host memory or 0
@@ -1140,14 +1099,14 @@ class DeviceGlm(object):
         return int(self.lib.pgl_prox_state_doubles(int(M), int(P)))
 
     def prox_init_dev(self, d_state, M, P, d_ll, d_grad, prior, d_lam, gtol, maxiter, d_Xt, flags_out=0):
-        _chk(self.lib.pgl_prox_init_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_ll), C.c_void_p(d_grad),
-                                        C.byref(_prox_prior(prior)), C.c_void_p(d_lam), float(gtol), int(maxiter),
-                                        C.c_void_p(d_Xt), C.c_void_p(flags_out) if flags_out else None))
+        _chk(self.lib.pgl_prox_init_dev(self.h, _dp(d_state), int(M), int(P), _dp(d_ll), _dp(d_grad),
+                                        C.byref(_prox_prior(prior)), _dp(d_lam), float(gtol), int(maxiter), _dp(d_Xt),
+                                        _dp(flags_out)))
 
     def prox_step_dev(self, d_state, M, P, d_ll, d_grad, prior, d_lam, gtol, maxiter, max_backtrack, d_Xt, flags_out=0):
-        _chk(self.lib.pgl_prox_step_dev(self.h, C.c_void_p(d_state), int(M), int(P), C.c_void_p(d_ll), C.c_void_p(d_grad),
-                                        C.byref(_prox_prior(prior)), C.c_void_p(d_lam), float(gtol), int(maxiter),
-                                        int(max_backtrack), C.c_void_p(d_Xt), C.c_void_p(flags_out) if flags_out else None))
+        _chk(self.lib.pgl_prox_step_dev(self.h, _dp(d_state), int(M), int(P), _dp(d_ll), _dp(d_grad),
+                                        C.byref(_prox_prior(prior)), _dp(d_lam), float(gtol), int(maxiter),
+                                        int(max_backtrack), _dp(d_Xt), _dp(flags_out)))
 
     # -- annealed importance sampling row kernels (pgl_ais_*; inference/batched_ais.py).  K particles x M neurons, rows
     # particle-major; prior: Gaussian only; device pointers
@@ -1155,44 +1114,38 @@ class DeviceGlm(object):
         return int(self.lib.pgl_ais_state_doubles(int(R), int(P)))
 
     def ais_init_dev(self, d_state, K, M, P, n_lo, particle0, prior, step0, seed, d_Xt):
-        _chk(self.lib.pgl_ais_init_dev(self.h, C.c_void_p(d_state), int(K), int(M), int(P), int(n_lo), int(particle0),
-                                       C.byref(as_prior(prior)), float(step0), int(seed) & 0xffffffffffffffff,
-                                       C.c_void_p(d_Xt)))
+        _chk(self.lib.pgl_ais_init_dev(self.h, _dp(d_state), int(K), int(M), int(P), int(n_lo), int(particle0),
+                                       C.byref(as_prior(prior)), float(step0), int(seed) & 0xffffffffffffffff, _dp(d_Xt)))
 
     def ais_start_dev(self, d_state, K, M, P, d_ll, d_grad, prior):
-        _chk(self.lib.pgl_ais_start_dev(self.h, C.c_void_p(d_state), int(K), int(M), int(P), C.c_void_p(d_ll),
-                                        C.c_void_p(d_grad), C.byref(as_prior(prior))))
+        _chk(self.lib.pgl_ais_start_dev(self.h, _dp(d_state), int(K), int(M), int(P), _dp(d_ll), _dp(d_grad),
+                                        C.byref(as_prior(prior))))
 
     def ais_temper_dev(self, d_state, K, M, P, prior, beta, d_step_row=0):
-        _chk(self.lib.pgl_ais_temper_dev(self.h, C.c_void_p(d_state), int(K), int(M), int(P), C.byref(as_prior(prior)),
-                                         float(beta), C.c_void_p(d_step_row) if d_step_row else None))
+        _chk(self.lib.pgl_ais_temper_dev(self.h, _dp(d_state), int(K), int(M), int(P), C.byref(as_prior(prior)), float(beta),
+                                         _dp(d_step_row)))
 
     def ais_begin_dev(self, d_state, K, M, P, d_minv, d_Xt):
-        _chk(self.lib.pgl_ais_begin_dev(self.h, C.c_void_p(d_state), int(K), int(M), int(P),
-                                        C.c_void_p(d_minv) if d_minv else None, C.c_void_p(d_Xt)))
+        _chk(self.lib.pgl_ais_begin_dev(self.h, _dp(d_state), int(K), int(M), int(P), _dp(d_minv), _dp(d_Xt)))
 
     def ais_leap_dev(self, d_state, K, M, P, d_minv, d_ll, d_grad, prior, last, adapt, d_Xt, d_acc_out=0, d_step_out=0):
-        vp = lambda a: C.c_void_p(a) if a else None
-        _chk(self.lib.pgl_ais_leap_dev(self.h, C.c_void_p(d_state), int(K), int(M), int(P), vp(d_minv), C.c_void_p(d_ll),
-                                       C.c_void_p(d_grad), C.byref(as_prior(prior)), 1 if last else 0, 1 if adapt else 0,
-                                       C.c_void_p(d_Xt), vp(d_acc_out), vp(d_step_out)))
+        _chk(self.lib.pgl_ais_leap_dev(self.h, _dp(d_state), int(K), int(M), int(P), _dp(d_minv), _dp(d_ll), _dp(d_grad),
+                                       C.byref(as_prior(prior)), 1 if last else 0, 1 if adapt else 0, _dp(d_Xt),
+                                       _dp(d_acc_out), _dp(d_step_out)))
 
     # -- the same run with a dense mass matrix (pgl_ais_dense_*): d_W (M, P, P) lower-triangular factors of the inverse mass
     # matrices, one per NEURON, shared by its K particles; d_x, d_y (K M, P) particle-major
     def tri_matvec_shared_dev(self, d_W, M, K, P, trans, d_x, d_y):
-        _chk(self.lib.pgl_tri_matvec_shared_dev(self.h, C.c_void_p(d_W), int(M), int(K), int(P), 1 if trans else 0,
-                                                C.c_void_p(d_x), C.c_void_p(d_y)))
+        _chk(self.lib.pgl_tri_matvec_shared_dev(self.h, _dp(d_W), int(M), int(K), int(P), 1 if trans else 0, _dp(d_x),
+                                                _dp(d_y)))
 
     def ais_dense_begin_dev(self, d_state, K, M, P, d_W, d_Xt):
-        _chk(self.lib.pgl_ais_dense_begin_dev(self.h, C.c_void_p(d_state), int(K), int(M), int(P), C.c_void_p(d_W),
-                                              C.c_void_p(d_Xt)))
+        _chk(self.lib.pgl_ais_dense_begin_dev(self.h, _dp(d_state), int(K), int(M), int(P), _dp(d_W), _dp(d_Xt)))
 
     def ais_dense_leap_dev(self, d_state, K, M, P, d_W, d_ll, d_grad, prior, last, adapt, d_Xt, d_acc_out=0, d_step_out=0):
-        vp = lambda a: C.c_void_p(a) if a else None
-        _chk(self.lib.pgl_ais_dense_leap_dev(self.h, C.c_void_p(d_state), int(K), int(M), int(P), C.c_void_p(d_W),
-                                             C.c_void_p(d_ll), C.c_void_p(d_grad), C.byref(as_prior(prior)),
-                                             1 if last else 0, 1 if adapt else 0, C.c_void_p(d_Xt), vp(d_acc_out),
-                                             vp(d_step_out)))
+        _chk(self.lib.pgl_ais_dense_leap_dev(self.h, _dp(d_state), int(K), int(M), int(P), _dp(d_W), _dp(d_ll), _dp(d_grad),
+                                             C.byref(as_prior(prior)), 1 if last else 0, 1 if adapt else 0, _dp(d_Xt),
+                                             _dp(d_acc_out), _dp(d_step_out)))
 
     # -- adaptive sequential Monte Carlo on the AIS rows (pgl_smc_*; inference/batched_smc.py): d_state the AIS block of
     # K M rows, d_smc the per-neuron block of smc_state_doubles(K, M, P, S) doubles, S the number of stage records
@@ -1200,11 +1153,11 @@ class DeviceGlm(object):
         return int(self.lib.pgl_smc_state_doubles(int(K), int(M), int(P), int(S)))
 
     def _smc(self, d_state, d_smc, K, M, P, S):
-        return (self.h, C.c_void_p(d_state), C.c_void_p(d_smc), int(K), int(M), int(P), int(S))
+        return (self.h, _dp(d_state), _dp(d_smc), int(K), int(M), int(P), int(S))
 
     def smc_init_dev(self, d_state, d_smc, K, M, P, S, n_lo, prior, step0, seed, d_Xt):
         _chk(self.lib.pgl_smc_init_dev(*self._smc(d_state, d_smc, K, M, P, S), int(n_lo), C.byref(as_prior(prior)),
-                                       float(step0), int(seed) & 0xffffffffffffffff, C.c_void_p(d_Xt)))
+                                       float(step0), int(seed) & 0xffffffffffffffff, _dp(d_Xt)))
 
     def smc_stage_dev(self, d_state, d_smc, K, M, P, S, prior, n_steps, cess, ess_min, delta_min, seed):
         _chk(self.lib.pgl_smc_stage_dev(*self._smc(d_state, d_smc, K, M, P, S), C.byref(as_prior(prior)), int(n_steps),
@@ -1214,21 +1167,18 @@ class DeviceGlm(object):
         _chk(self.lib.pgl_smc_gather_dev(*self._smc(d_state, d_smc, K, M, P, S), C.byref(as_prior(prior))))
 
     def smc_begin_dev(self, d_state, d_smc, K, M, P, S, d_minv, d_Xt):
-        _chk(self.lib.pgl_smc_begin_dev(*self._smc(d_state, d_smc, K, M, P, S), C.c_void_p(d_minv) if d_minv else None,
-                                        C.c_void_p(d_Xt)))
+        _chk(self.lib.pgl_smc_begin_dev(*self._smc(d_state, d_smc, K, M, P, S), _dp(d_minv), _dp(d_Xt)))
 
     def smc_leap_dev(self, d_state, d_smc, K, M, P, S, d_minv, d_ll, d_grad, prior, last, d_Xt):
-        _chk(self.lib.pgl_smc_leap_dev(*self._smc(d_state, d_smc, K, M, P, S), C.c_void_p(d_minv) if d_minv else None,
-                                       C.c_void_p(d_ll), C.c_void_p(d_grad), C.byref(as_prior(prior)), 1 if last else 0,
-                                       C.c_void_p(d_Xt)))
+        _chk(self.lib.pgl_smc_leap_dev(*self._smc(d_state, d_smc, K, M, P, S), _dp(d_minv), _dp(d_ll), _dp(d_grad),
+                                       C.byref(as_prior(prior)), 1 if last else 0, _dp(d_Xt)))
 
     def smc_dense_begin_dev(self, d_state, d_smc, K, M, P, S, d_W, d_Xt):
-        _chk(self.lib.pgl_smc_dense_begin_dev(*self._smc(d_state, d_smc, K, M, P, S), C.c_void_p(d_W), C.c_void_p(d_Xt)))
+        _chk(self.lib.pgl_smc_dense_begin_dev(*self._smc(d_state, d_smc, K, M, P, S), _dp(d_W), _dp(d_Xt)))
 
     def smc_dense_leap_dev(self, d_state, d_smc, K, M, P, S, d_W, d_ll, d_grad, prior, last, d_Xt):
-        _chk(self.lib.pgl_smc_dense_leap_dev(*self._smc(d_state, d_smc, K, M, P, S), C.c_void_p(d_W), C.c_void_p(d_ll),
-                                             C.c_void_p(d_grad), C.byref(as_prior(prior)), 1 if last else 0,
-                                             C.c_void_p(d_Xt)))
+        _chk(self.lib.pgl_smc_dense_leap_dev(*self._smc(d_state, d_smc, K, M, P, S), _dp(d_W), _dp(d_ll), _dp(d_grad),
+                                             C.byref(as_prior(prior)), 1 if last else 0, _dp(d_Xt)))
 
     def sync(self):
         _chk(self.lib.pgl_sync(self.h))
@@ -1332,8 +1282,7 @@ class DeviceGlm(object):
 
     # -- batched column Gibbs (all post-synaptic columns resident) ---------------
     def gibbs_prepare_all(self, theta, Weff):
-        th = _f64(theta, (self.N, self.P))
-        We = _f64(Weff, (self.N, self.N))
+        th, We = self._draw(theta, Weff)
         _chk(self.lib.pgl_gibbs_prepare_all(self.h, _ptr(th), _ptr(We)))
 
     def gibbs_ll_cols(self, n_post, n_pre, aw_cur, ws):

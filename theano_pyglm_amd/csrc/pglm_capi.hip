@@ -120,19 +120,19 @@ struct pgl_context {
     bool hvp_ok = false, hvp_fused = false, hvp_list = false;
     int hvp_n_lo = 0, hvp_count = 0;
     int64_t hvp_t_lo = 0, hvp_t_hi = 0;
-    DevBuf Cbuf, hvp_idx, hvp_Weff, hvp_ll, hvp_v, hvp_out;
-    DevBuf hess_part, hess_out;          // pgl_hess_dev: chunk partials of k_hess; pgl_hess: the device copy of H_out
-    // time rescaling (pgl_rescale_dev): in-chunk sums at the events, chunk totals and their prefix; pgl_rescale: the device
-    // copies of its offsets and results
-    DevBuf rs_pre, rs_tot, rs_cum, rs_off, rs_tau, rs_stats;
+    DevBuf Cbuf, hvp_idx, hvp_Weff, hvp_ll;
+    DevBuf hess_part;                    // pgl_hess_dev: chunk partials of k_hess
+    // time rescaling (pgl_rescale_dev): in-chunk sums at the events, chunk totals and their prefix
+    DevBuf rs_pre, rs_tot, rs_cum;
     // the corrected intervals (pgl_rescale_corr_dev): the rate of every event's bin; pgl_ks_uniform_dev: the sorted values where
-    // the caller wants none; pgl_ks_uniform: the device copies of its arrays
-    DevBuf rs_qev, rs_tail, ks_work, ks_tau, ks_off, ks_out;
-    DevBuf acf_seg;                      // pgl_rescale_acf: the device copy of seg_run (the other arrays: the ks_* buffers)
-    DevBuf psis_in, psis_out, psis_lw;   // pgl_psis_loo: the device copies of its host arrays
-    DevBuf diag_in, diag_out;            // pgl_chain_diag: the same
-    DevBuf pw_part, pw_out;              // pointwise ll (pgl_pointwise_dev): chunk sums; pgl_pointwise: the device copy of ll_blk_out
-    DevBuf rw_part, rw_cnt, rw_out;      // rate windows (pgl_rate_windows_dev): piece sums of rate and spike counts; pgl_rate_windows: the device copy of its two results
+    // the caller wants none (pgl_ks_uniform and pgl_rescale_acf: their sorted values / scores)
+    DevBuf rs_qev, rs_tail, ks_work;
+    DevBuf pw_part;                      // pointwise ll (pgl_pointwise_dev): chunk sums
+    DevBuf rw_part, rw_cnt;              // rate windows (pgl_rate_windows_dev): piece sums of rate and spike counts
+    // the host-array forms (pgl_hvp .. pgl_chain_diag): the device copies of their arrays, taken by index (stage_up).  Every
+    // such call ends in stage_end, so a slot holds nothing across calls and the forms share them
+    static constexpr int NSTAGE = 4;
+    DevBuf stage[NSTAGE];
     std::vector<double> hvp_host;        // pgl_hvp: theta and Weff of its last prepare (a CG solve repeats them: no new prepare)
 };
 
@@ -180,11 +180,46 @@ static bool img_room(const pgl_context* h, size_t want)
     reclaim = std::max(reclaim, h->imgs[lru].buf.cap);
     return want <= reclaim || want - reclaim <= free_b / 10 * 9;
 }
-#define ENSURE(buf, bytes)                       \
+// an error code of a step is the call's own
+#define PASS(call)                               \
     do {                                         \
-        int rc_ = ensure(buf, bytes);            \
+        int rc_ = (call);                        \
         if (rc_ != PGL_OK) return rc_;           \
     } while (0)
+#define ENSURE(buf, bytes) PASS(ensure(buf, bytes))
+
+// ---- what the host-array forms share: each is check, stage_up, its _dev form, stage_down, stage_end ----
+// room for `bytes` (one element at the least) in staging slot `slot`, and the host array `src` on its way there; src ==
+// nullptr: room alone, for a result.  No synchronise behind the copy: the caller's arrays live until the stage_end of the same
+// call.  Like ensure, the three do nothing in a dry run.
+static int stage_up(pgl_handle h, int slot, const void* src, size_t bytes)
+{
+    ENSURE(h->stage[slot], std::max<size_t>(bytes, 8));
+    if (src && bytes && !g_dry) HIPCHK(hipMemcpyAsync(h->stage[slot].p, src, bytes, hipMemcpyHostToDevice, h->stream));
+    return PGL_OK;
+}
+// a result on its way back; dst == nullptr: the caller wants none
+static int stage_down(pgl_handle h, void* dst, const void* d_src, size_t bytes)
+{
+    if (dst && bytes && !g_dry) HIPCHK(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, h->stream));
+    return PGL_OK;
+}
+static int stage_end(pgl_handle h)
+{
+    if (!g_dry) HIPCHK(hipStreamSynchronize(h->stream));
+    return PGL_OK;
+}
+// host theta of the rows [n_lo, n_hi) -> d_theta (h->theta: an evaluation's, h->gtheta: a draw's) and Weff (N, N) -> h->Weff,
+// on stage_up's terms
+static int upload_rows(pgl_handle h, DevBuf& d_theta, int n_lo, int n_hi, const double* theta, const double* Weff)
+{
+    const size_t tb = (size_t)(n_hi - n_lo) * (1 + (size_t)h->Dstim + h->Kimp) * 8, wb = (size_t)h->N * h->N * 8;
+    ENSURE(d_theta, tb);
+    ENSURE(h->Weff, wb);
+    HIPCHK(hipMemcpyAsync(d_theta.p, theta, tb, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->Weff.p, Weff, wb, hipMemcpyHostToDevice, h->stream));
+    return PGL_OK;
+}
 
 // the planner (Plan, Slice, the k-tile lists, make_plan, select_plans, hvp_select) and the launch layer (dry_record,
 // launch_kernel, dispatch, the launchers of the fused kernels): both need the context above
@@ -348,11 +383,10 @@ int pgl_destroy(pgl_handle h)
                       &h->wsmall, &h->part, &h->outK, &h->lam, &h->wcol, &h->thetan, &h->GX, &h->gtheta,
                       &h->gargs, &h->gpart, &h->gout, &h->ghs, &h->gfs, &h->zf, &h->zfT, &h->sbt, &h->Yf, &h->Qb, &h->Qf,
                       &h->spart, &h->sepC, &h->sepA, &h->sepAT, &h->sepD, &h->YfT, &h->Hb, &h->wpart, &h->QvT, &h->staA,
-                      &h->Cbuf, &h->hvp_idx, &h->hvp_Weff, &h->hvp_ll, &h->hvp_v, &h->hvp_out,
-                      &h->hess_part, &h->hess_out, &h->rs_pre, &h->rs_tot, &h->rs_cum, &h->rs_off, &h->rs_tau, &h->rs_stats,
-                      &h->rs_qev, &h->rs_tail, &h->ks_work, &h->ks_tau, &h->ks_off, &h->ks_out, &h->acf_seg,
-                      &h->pw_part, &h->pw_out, &h->rw_part, &h->rw_cnt, &h->rw_out, &h->psis_in, &h->psis_out, &h->psis_lw, &h->diag_in, &h->diag_out};
+                      &h->Cbuf, &h->hvp_idx, &h->hvp_Weff, &h->hvp_ll, &h->hess_part, &h->rs_pre, &h->rs_tot, &h->rs_cum,
+                      &h->rs_qev, &h->rs_tail, &h->ks_work, &h->pw_part, &h->rw_part, &h->rw_cnt};
     for (DevBuf* b : bufs) release(*b);
+    for (DevBuf& b : h->stage) release(b);
     for (int s = 0; s < pgl_context::NEV; ++s)
         for (int i = 0; i < 4; ++i)
             if (h->evr[s][i]) (void)hipEventDestroy(h->evr[s][i]);
@@ -1688,33 +1722,24 @@ int pgl_hvp(pgl_handle h, int n_lo, int n_hi, const double* theta, const double*
     if (!theta || !v || !Weff || !hv_out) return fail(PGL_ERR_ARG, "null argument");
     if (n_lo < 0 || n_hi > h->N || n_lo >= n_hi) return fail(PGL_ERR_ARG, "bad neuron range");
     HIPCHK(hipSetDevice(h->device));
-    const size_t P = 1 + (size_t)h->Dstim + h->Kimp;
-    const size_t np = (size_t)(n_hi - n_lo);
-    ENSURE(h->theta, np * P * 8);
-    ENSURE(h->Weff, (size_t)h->N * h->N * 8);
-    ENSURE(h->hvp_v, np * P * 8);
-    ENSURE(h->hvp_out, np * P * 8);
-    HIPCHK(hipMemcpyAsync(h->hvp_v.p, v, np * P * 8, hipMemcpyHostToDevice, h->stream));
+    const size_t np = (size_t)(n_hi - n_lo), nP = np * (1 + (size_t)h->Dstim + h->Kimp), nW = (size_t)h->N * h->N;
+    PASS(stage_up(h, 0, v, nP * 8));
+    PASS(stage_up(h, 1, nullptr, nP * 8));
     // the products of one CG solve share theta: the curvature of an identical (range, time range, theta, Weff) is kept
-    const size_t nW = (size_t)h->N * h->N;
     const bool same = h->hvp_ok && !h->hvp_list && h->hvp_n_lo == n_lo && h->hvp_count == (int)np && h->hvp_t_lo == h->t_lo &&
-                      h->hvp_t_hi == h->t_hi && h->hvp_host.size() == np * P + nW &&
-                      std::memcmp(h->hvp_host.data(), theta, np * P * 8) == 0 &&
-                      std::memcmp(h->hvp_host.data() + np * P, Weff, nW * 8) == 0;
+                      h->hvp_t_hi == h->t_hi && h->hvp_host.size() == nP + nW &&
+                      std::memcmp(h->hvp_host.data(), theta, nP * 8) == 0 &&
+                      std::memcmp(h->hvp_host.data() + nP, Weff, nW * 8) == 0;
     if (!same) {
         h->hvp_host.clear();
-        HIPCHK(hipMemcpyAsync(h->theta.p, theta, np * P * 8, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->Weff.p, Weff, nW * 8, hipMemcpyHostToDevice, h->stream));
-        rc = pgl_hvp_prepare_dev(h, n_lo, n_hi, (const double*)h->theta.p, (const double*)h->Weff.p);
-        if (rc) return rc;
-        h->hvp_host.assign(theta, theta + np * P);
+        PASS(upload_rows(h, h->theta, n_lo, n_hi, theta, Weff));
+        PASS(pgl_hvp_prepare_dev(h, n_lo, n_hi, (const double*)h->theta.p, (const double*)h->Weff.p));
+        h->hvp_host.assign(theta, theta + nP);
         h->hvp_host.insert(h->hvp_host.end(), Weff, Weff + nW);
     }
-    rc = pgl_hvp_apply_dev(h, (const double*)h->hvp_v.p, (double*)h->hvp_out.p);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(hv_out, h->hvp_out.p, np * P * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return PGL_OK;
+    PASS(pgl_hvp_apply_dev(h, (const double*)h->stage[0].p, (double*)h->stage[1].p));
+    PASS(stage_down(h, hv_out, h->stage[1].p, nP * 8));
+    return stage_end(h);
 }
 
 // ---- dense Hessians of ll (hessian_wrt_list, pyglm/utils/grads.py:30-66) ----
@@ -1781,20 +1806,13 @@ int pgl_hess(pgl_handle h, int n_lo, int n_hi, const double* theta, const double
     if (!theta || !Weff || !H_out) return fail(PGL_ERR_ARG, "null argument");
     if (n_lo < 0 || n_hi > h->N || n_lo >= n_hi) return fail(PGL_ERR_ARG, "bad neuron range");
     HIPCHK(hipSetDevice(h->device));
-    const size_t P = 1 + (size_t)h->Dstim + h->Kimp;
-    const size_t np = (size_t)(n_hi - n_lo);
-    ENSURE(h->theta, np * P * 8);
-    ENSURE(h->Weff, (size_t)h->N * h->N * 8);
-    HIPCHK(hipMemcpyAsync(h->theta.p, theta, np * P * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->Weff.p, Weff, (size_t)h->N * h->N * 8, hipMemcpyHostToDevice, h->stream));
-    rc = pgl_hvp_prepare_dev(h, n_lo, n_hi, (const double*)h->theta.p, (const double*)h->Weff.p);
-    if (rc) return rc;
-    ENSURE(h->hess_out, np * P * P * 8);
-    rc = pgl_hess_dev(h, (double*)h->hess_out.p, (int)P);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(H_out, h->hess_out.p, np * P * P * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return PGL_OK;
+    const size_t P = 1 + (size_t)h->Dstim + h->Kimp, bytes = (size_t)(n_hi - n_lo) * P * P * 8;
+    PASS(upload_rows(h, h->theta, n_lo, n_hi, theta, Weff));
+    PASS(pgl_hvp_prepare_dev(h, n_lo, n_hi, (const double*)h->theta.p, (const double*)h->Weff.p));
+    PASS(stage_up(h, 0, nullptr, bytes));
+    PASS(pgl_hess_dev(h, (double*)h->stage[0].p, (int)P));
+    PASS(stage_down(h, H_out, h->stage[0].p, bytes));
+    return stage_end(h);
 }
 
 // the lock-step entry points, BFGS bookkeeping through proximal gradient (inside extern "C")
@@ -1816,22 +1834,15 @@ int pgl_ll_grad(pgl_handle h, int n_lo, int n_hi, const double* theta, const dou
     if (!theta || !Weff || !ll_out) return fail(PGL_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(h->device));
     if (n_lo < 0 || n_hi > h->N || n_lo >= n_hi) return fail(PGL_ERR_ARG, "bad neuron range");
-    const size_t P = 1 + (size_t)h->Dstim + h->Kimp;
-    const size_t np = (size_t)(n_hi - n_lo);
-    ENSURE(h->theta, np * P * 8);
-    ENSURE(h->Weff, (size_t)h->N * h->N * 8);
+    const size_t np = (size_t)(n_hi - n_lo), gb = np * (1 + (size_t)h->Dstim + h->Kimp) * 8;
+    PASS(upload_rows(h, h->theta, n_lo, n_hi, theta, Weff));
     ENSURE(h->ll, np * 8);
-    if (grad_out) ENSURE(h->grad, np * P * 8);
-    HIPCHK(hipMemcpyAsync(h->theta.p, theta, np * P * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->Weff.p, Weff, (size_t)h->N * h->N * 8, hipMemcpyHostToDevice, h->stream));
-    rc = enqueue_ll_grad(h, n_lo, n_hi, (const double*)h->theta.p, (const double*)h->Weff.p,
-                         (double*)h->ll.p, grad_out ? (double*)h->grad.p : nullptr);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(ll_out, h->ll.p, np * 8, hipMemcpyDeviceToHost, h->stream));
-    if (grad_out)
-        HIPCHK(hipMemcpyAsync(grad_out, h->grad.p, np * P * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return PGL_OK;
+    if (grad_out) ENSURE(h->grad, gb);
+    PASS(enqueue_ll_grad(h, n_lo, n_hi, (const double*)h->theta.p, (const double*)h->Weff.p,
+                         (double*)h->ll.p, grad_out ? (double*)h->grad.p : nullptr));
+    PASS(stage_down(h, ll_out, h->ll.p, np * 8));
+    PASS(stage_down(h, grad_out, h->grad.p, gb));
+    return stage_end(h);
 }
 
 int pgl_last_timing(pgl_handle h, double* fused_ms, double* total_ms)
@@ -2168,13 +2179,9 @@ int pgl_gibbs_update(pgl_handle h, int n_pre, double delta)
 // host theta (N, P) / Weff (N, N) of one draw -> h->gtheta / h->Weff, the device is current
 static int upload_draw(pgl_handle h, const double* theta, const double* Weff)
 {
-    const size_t tb = (size_t)h->N * (1 + (size_t)h->Dstim + h->Kimp) * 8, wb = (size_t)h->N * h->N * 8;
-    ENSURE(h->gtheta, tb);
-    ENSURE(h->Weff, wb);
-    HIPCHK(hipMemcpyAsync(h->gtheta.p, theta, tb, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->Weff.p, Weff, wb, hipMemcpyHostToDevice, h->stream));
-    // the caller's (pageable) theta / Weff may be temporaries that die when this call returns: the uploads
-    // must have left host memory by then, whatever the runtime does with pageable sources
+    PASS(upload_rows(h, h->gtheta, 0, h->N, theta, Weff));
+    // pgl_gibbs_prepare_all returns with the work enqueued, and the caller's (pageable) theta / Weff may be temporaries that
+    // die then: the uploads must have left host memory, whatever the runtime does with pageable sources
     HIPCHK(hipStreamSynchronize(h->stream));
     return PGL_OK;
 }
@@ -2976,7 +2983,7 @@ int pgl_ks_uniform_dev(pgl_handle h, const double* d_tau, const int64_t* d_off, 
 {
     if (!h) return fail(PGL_ERR_ARG, "null handle");
     if (!d_tau || !d_off || !d_ks) return fail(PGL_ERR_ARG, "null argument");
-    if (M < 1 || M > 0x7fffffff) return fail(PGL_ERR_ARG, "pgl_ks_uniform_dev: M must lie in 1 .. 2^31 - 1");
+    if (pgl_gof_bad_count(M)) return fail(PGL_ERR_ARG, "pgl_ks_uniform_dev: M must lie in 1 .. 2^31 - 1");
     HIPCHK(hipSetDevice(h->device));
     if (!d_zsorted) {
         // the network sorts in place: room for every z.  The one place where the call waits for the device
@@ -2996,24 +3003,19 @@ int pgl_ks_uniform(pgl_handle h, const double* tau, const int64_t* off, int64_t 
 {
     if (!h) return fail(PGL_ERR_ARG, "null handle");
     if (!tau || !off || !ks_out) return fail(PGL_ERR_ARG, "null argument");
-    if (M < 1 || M > 0x7fffffff) return fail(PGL_ERR_ARG, "pgl_ks_uniform: M must lie in 1 .. 2^31 - 1");
-    for (int64_t m = 0; m < M; ++m)
-        if (off[m + 1] < off[m] || off[0] < 0) return fail(PGL_ERR_ARG, "pgl_ks_uniform: offsets must not decrease");
+    if (pgl_gof_bad_count(M)) return fail(PGL_ERR_ARG, "pgl_ks_uniform: M must lie in 1 .. 2^31 - 1");
+    if (pgl_gof_bad_offsets((const long long*)off, M)) return fail(PGL_ERR_ARG, "pgl_ks_uniform: offsets must not decrease");
     HIPCHK(hipSetDevice(h->device));
-    const size_t total = (size_t)off[M], tb = std::max<size_t>(total, 1) * 8;
-    ENSURE(h->ks_tau, tb);
-    ENSURE(h->ks_work, tb);
-    ENSURE(h->ks_off, ((size_t)M + 1) * 8);
-    ENSURE(h->ks_out, (size_t)M * PGL_KS_NOUT * 8);
-    if (total) HIPCHK(hipMemcpyAsync(h->ks_tau.p, tau, total * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->ks_off.p, off, ((size_t)M + 1) * 8, hipMemcpyHostToDevice, h->stream));
-    int rc = pgl_ks_uniform_dev(h, (const double*)h->ks_tau.p, (const int64_t*)h->ks_off.p, M, (double*)h->ks_out.p,
-                                (double*)h->ks_work.p);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(ks_out, h->ks_out.p, (size_t)M * PGL_KS_NOUT * 8, hipMemcpyDeviceToHost, h->stream));
-    if (zsorted_out && total) HIPCHK(hipMemcpyAsync(zsorted_out, h->ks_work.p, total * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return PGL_OK;
+    const size_t tb = (size_t)off[M] * 8, ob = (size_t)M * PGL_KS_NOUT * 8;
+    PASS(stage_up(h, 0, tau, tb));
+    PASS(stage_up(h, 1, off, ((size_t)M + 1) * 8));
+    PASS(stage_up(h, 2, nullptr, ob));
+    ENSURE(h->ks_work, std::max<size_t>(tb, 8));
+    PASS(pgl_ks_uniform_dev(h, (const double*)h->stage[0].p, (const int64_t*)h->stage[1].p, M, (double*)h->stage[2].p,
+                            (double*)h->ks_work.p));
+    PASS(stage_down(h, ks_out, h->stage[2].p, ob));
+    PASS(stage_down(h, zsorted_out, h->ks_work.p, tb));
+    return stage_end(h);
 }
 
 // ---- the serial correlation of the normal scores of segmented, run-structured intervals (pglm_acf.h, pglm_acf.hip.h) ------
@@ -3031,7 +3033,7 @@ int pgl_rescale_acf_dev(pgl_handle h, const double* d_tau, const int64_t* d_run_
 {
     if (!h) return fail(PGL_ERR_ARG, "null handle");
     if (!d_tau || !d_run_off || !d_seg_run || !d_out || !d_scores) return fail(PGL_ERR_ARG, "null argument");
-    if (M < 1 || M > 0x7fffffff) return fail(PGL_ERR_ARG, "pgl_rescale_acf_dev: M must lie in 1 .. 2^31 - 1");
+    if (pgl_gof_bad_count(M)) return fail(PGL_ERR_ARG, "pgl_rescale_acf_dev: M must lie in 1 .. 2^31 - 1");
     if (max_lag < 1 || max_lag > PGL_ACF_MAX_LAG) return fail(PGL_ERR_ARG, "pgl_rescale_acf_dev: max_lag must lie in 1 .. 64");
     HIPCHK(hipSetDevice(h->device));
     return enqueue_acf(h, d_tau, d_run_off, d_seg_run, M, max_lag, d_out, d_scores);
@@ -3042,32 +3044,23 @@ int pgl_rescale_acf(pgl_handle h, const double* tau, const int64_t* run_off, con
 {
     if (!h) return fail(PGL_ERR_ARG, "null handle");
     if (!tau || !run_off || !seg_run || !out) return fail(PGL_ERR_ARG, "null argument");
-    if (M < 1 || M > 0x7fffffff) return fail(PGL_ERR_ARG, "pgl_rescale_acf: M must lie in 1 .. 2^31 - 1");
+    if (pgl_gof_bad_count(M)) return fail(PGL_ERR_ARG, "pgl_rescale_acf: M must lie in 1 .. 2^31 - 1");
     if (max_lag < 1 || max_lag > PGL_ACF_MAX_LAG) return fail(PGL_ERR_ARG, "pgl_rescale_acf: max_lag must lie in 1 .. 64");
-    if (seg_run[0] < 0) return fail(PGL_ERR_ARG, "pgl_rescale_acf: offsets must not decrease");
-    for (int64_t m = 0; m < M; ++m)
-        if (seg_run[m + 1] < seg_run[m]) return fail(PGL_ERR_ARG, "pgl_rescale_acf: offsets must not decrease");
-    const int64_t R = seg_run[M];
-    if (run_off[0] < 0) return fail(PGL_ERR_ARG, "pgl_rescale_acf: offsets must not decrease");
-    for (int64_t r = 0; r < R; ++r)
-        if (run_off[r + 1] < run_off[r]) return fail(PGL_ERR_ARG, "pgl_rescale_acf: offsets must not decrease");
+    // (the runs of the segments first: their count R is the last of seg_run)
+    if (pgl_gof_bad_offsets((const long long*)seg_run, M) || pgl_gof_bad_offsets((const long long*)run_off, seg_run[M]))
+        return fail(PGL_ERR_ARG, "pgl_rescale_acf: offsets must not decrease");
     HIPCHK(hipSetDevice(h->device));
-    const size_t total = (size_t)run_off[R], tb = std::max<size_t>(total, 1) * 8, ob = (size_t)M * (PGL_ACF_NHEAD + max_lag) * 8;
-    ENSURE(h->ks_tau, tb);
-    ENSURE(h->ks_work, tb);
-    ENSURE(h->ks_off, ((size_t)R + 1) * 8);
-    ENSURE(h->acf_seg, ((size_t)M + 1) * 8);
-    ENSURE(h->ks_out, ob);
-    if (total) HIPCHK(hipMemcpyAsync(h->ks_tau.p, tau, total * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->ks_off.p, run_off, ((size_t)R + 1) * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->acf_seg.p, seg_run, ((size_t)M + 1) * 8, hipMemcpyHostToDevice, h->stream));
-    int rc = pgl_rescale_acf_dev(h, (const double*)h->ks_tau.p, (const int64_t*)h->ks_off.p, (const int64_t*)h->acf_seg.p, M, max_lag,
-                                 (double*)h->ks_out.p, (double*)h->ks_work.p);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out, h->ks_out.p, ob, hipMemcpyDeviceToHost, h->stream));
-    if (scores_out && total) HIPCHK(hipMemcpyAsync(scores_out, h->ks_work.p, total * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return PGL_OK;
+    const size_t R = (size_t)seg_run[M], tb = (size_t)run_off[R] * 8, ob = (size_t)M * (PGL_ACF_NHEAD + max_lag) * 8;
+    PASS(stage_up(h, 0, tau, tb));
+    PASS(stage_up(h, 1, run_off, (R + 1) * 8));
+    PASS(stage_up(h, 2, seg_run, ((size_t)M + 1) * 8));
+    PASS(stage_up(h, 3, nullptr, ob));
+    ENSURE(h->ks_work, std::max<size_t>(tb, 8));
+    PASS(pgl_rescale_acf_dev(h, (const double*)h->stage[0].p, (const int64_t*)h->stage[1].p, (const int64_t*)h->stage[2].p, M, max_lag,
+                             (double*)h->stage[3].p, (double*)h->ks_work.p));
+    PASS(stage_down(h, out, h->stage[3].p, ob));
+    PASS(stage_down(h, scores_out, h->ks_work.p, tb));
+    return stage_end(h);
 }
 
 int pgl_rescale(pgl_handle h, const double* theta, const double* Weff, double* tau_out, double* stats_out)
@@ -3087,20 +3080,16 @@ static int rescale_host(pgl_handle h, const double* theta, const double* Weff, d
     std::vector<int64_t> off((size_t)N + 1);
     rc = pgl_rescale_count(h, off.data());
     if (rc) return rc;
-    const size_t ntau = (size_t)off[(size_t)N];
-    ENSURE(h->rs_off, ((size_t)N + 1) * 8);
-    ENSURE(h->rs_tau, std::max<size_t>(ntau, 1) * 8);
-    ENSURE(h->rs_stats, (size_t)N * 4 * 8);
-    HIPCHK(hipMemcpyAsync(h->rs_off.p, off.data(), ((size_t)N + 1) * 8, hipMemcpyHostToDevice, h->stream));
-    rc = upload_draw(h, theta, Weff);                 // (its synchronise covers the offsets too)
-    if (rc) return rc;
-    rc = rescale_dev(h, (const double*)h->gtheta.p, (const double*)h->Weff.p, (double*)h->rs_tau.p,
-                     (const int64_t*)h->rs_off.p, (double*)h->rs_stats.p, corr, seed, draw);
-    if (rc) return rc;
-    if (ntau) HIPCHK(hipMemcpyAsync(tau_out, h->rs_tau.p, ntau * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(stats_out, h->rs_stats.p, (size_t)N * 4 * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return PGL_OK;
+    const size_t tb = (size_t)off[(size_t)N] * 8, sb = (size_t)N * 4 * 8;
+    PASS(stage_up(h, 0, off.data(), ((size_t)N + 1) * 8));
+    PASS(stage_up(h, 1, nullptr, tb));
+    PASS(stage_up(h, 2, nullptr, sb));
+    PASS(upload_draw(h, theta, Weff));
+    PASS(rescale_dev(h, (const double*)h->gtheta.p, (const double*)h->Weff.p, (double*)h->stage[1].p,
+                     (const int64_t*)h->stage[0].p, (double*)h->stage[2].p, corr, seed, draw));
+    PASS(stage_down(h, tau_out, h->stage[1].p, tb));
+    PASS(stage_down(h, stats_out, h->stage[2].p, sb));
+    return stage_end(h);
 }
 
 // ---- pointwise log-likelihood: block sums of the ll terms of a draw (pglm_pointwise.hip.h) ------------------------------
@@ -3155,15 +3144,12 @@ int pgl_pointwise(pgl_handle h, const double* theta, const double* Weff, int blo
     if (rc) return rc;
     HIPCHK(hipSetDevice(h->device));
     const size_t bytes = (size_t)n_blocks * h->N * 8;
-    ENSURE(h->pw_out, bytes);
-    rc = upload_draw(h, theta, Weff);
-    if (rc) return rc;
-    rc = pgl_pointwise_dev(h, (const double*)h->gtheta.p, (const double*)h->Weff.p, block_chunks, (double*)h->pw_out.p,
-                           nullptr, 0);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(ll_blk_out, h->pw_out.p, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return PGL_OK;
+    PASS(stage_up(h, 0, nullptr, bytes));
+    PASS(upload_draw(h, theta, Weff));
+    PASS(pgl_pointwise_dev(h, (const double*)h->gtheta.p, (const double*)h->Weff.p, block_chunks, (double*)h->stage[0].p,
+                           nullptr, 0));
+    PASS(stage_down(h, ll_blk_out, h->stage[0].p, bytes));
+    return stage_end(h);
 }
 
 // ---- rate windows: expected and observed counts over time windows, folded over draws (pglm_ratewin.hip.h) ----------------
@@ -3236,19 +3222,15 @@ int pgl_rate_windows(pgl_handle h, const double* theta, const double* Weff, int6
     rc = pgl_rate_windows_count(h, win, &n_win);
     if (rc) return rc;
     HIPCHK(hipSetDevice(h->device));
-    const int N = h->N;
-    const size_t bytes = (size_t)n_win * N * 8;
-    ENSURE(h->rw_out, 2 * bytes);
-    rc = upload_draw(h, theta, Weff);
-    if (rc) return rc;
-    double* d_lam = (double*)h->rw_out.p;
-    rc = pgl_rate_windows_dev(h, (const double*)h->gtheta.p, (const double*)h->Weff.p, win, d_lam, d_lam + (size_t)n_win * N,
-                              nullptr, 0);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(lam_out, d_lam, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(obs_out, d_lam + (size_t)n_win * N, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return PGL_OK;
+    const size_t bytes = (size_t)n_win * h->N * 8;
+    PASS(stage_up(h, 0, nullptr, 2 * bytes));
+    PASS(upload_draw(h, theta, Weff));
+    double* d_lam = (double*)h->stage[0].p;
+    double* d_obs = d_lam + (size_t)n_win * h->N;
+    PASS(pgl_rate_windows_dev(h, (const double*)h->gtheta.p, (const double*)h->Weff.p, win, d_lam, d_obs, nullptr, 0));
+    PASS(stage_down(h, lam_out, d_lam, bytes));
+    PASS(stage_down(h, obs_out, d_obs, bytes));
+    return stage_end(h);
 }
 
 // ---- PSIS-LOO of the columns of a pointwise matrix (pglm_psis.hip.h) ---------------------------------------------------
@@ -3272,17 +3254,13 @@ int pgl_psis_loo(pgl_handle h, const double* ll, int64_t S, int64_t C, double* o
     if (S > PGL_PSIS_MAX_DRAWS) return pgl_psis_loo_dev(h, ll, S, C, C, out, lw);       // (its error, before any copy)
     HIPCHK(hipSetDevice(h->device));
     const size_t bytes = (size_t)S * C * 8, obytes = (size_t)PGL_PSIS_NOUT * C * 8;
-    ENSURE(h->psis_in, bytes);
-    ENSURE(h->psis_out, obytes);
-    if (lw) ENSURE(h->psis_lw, bytes);
-    HIPCHK(hipMemcpyAsync(h->psis_in.p, ll, bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));          // (pageable source)
-    int rc = pgl_psis_loo_dev(h, (const double*)h->psis_in.p, S, C, C, (double*)h->psis_out.p, lw ? (double*)h->psis_lw.p : nullptr);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out, h->psis_out.p, obytes, hipMemcpyDeviceToHost, h->stream));
-    if (lw) HIPCHK(hipMemcpyAsync(lw, h->psis_lw.p, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return PGL_OK;
+    PASS(stage_up(h, 0, ll, bytes));
+    PASS(stage_up(h, 1, nullptr, obytes));
+    if (lw) PASS(stage_up(h, 2, nullptr, bytes));
+    PASS(pgl_psis_loo_dev(h, (const double*)h->stage[0].p, S, C, C, (double*)h->stage[1].p, lw ? (double*)h->stage[2].p : nullptr));
+    PASS(stage_down(h, out, h->stage[1].p, obytes));
+    PASS(stage_down(h, lw, h->stage[2].p, bytes));
+    return stage_end(h);
 }
 
 // ---- convergence diagnostics of the columns of a samplers' tensor (pglm_diag.hip.h) ----------------------------------------
@@ -3311,15 +3289,11 @@ int pgl_chain_diag(pgl_handle h, const double* x, int64_t n, int64_t C, int64_t 
         return pgl_chain_diag_dev(h, x, n, C, K, K, out);                                // (its error, before any copy)
     HIPCHK(hipSetDevice(h->device));
     const size_t bytes = (size_t)n * C * K * 8, obytes = (size_t)PGL_DIAG_NOUT * K * 8;
-    ENSURE(h->diag_in, bytes);
-    ENSURE(h->diag_out, obytes);
-    HIPCHK(hipMemcpyAsync(h->diag_in.p, x, bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));          // (pageable source)
-    int rc = pgl_chain_diag_dev(h, (const double*)h->diag_in.p, n, C, K, K, (double*)h->diag_out.p);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out, h->diag_out.p, obytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return PGL_OK;
+    PASS(stage_up(h, 0, x, bytes));
+    PASS(stage_up(h, 1, nullptr, obytes));
+    PASS(pgl_chain_diag_dev(h, (const double*)h->stage[0].p, n, C, K, K, (double*)h->stage[1].p));
+    PASS(stage_down(h, out, h->stage[1].p, obytes));
+    return stage_end(h);
 }
 
 int pgl_state(pgl_handle h, int n, const double* theta_n, const double* Weff_col, double* lam_out,

@@ -135,4 +135,19 @@ PGL_GOF_FN void pgl_gof_ks_segment(const double* tau, long long n, double* zs, d
     pgl_gof_ks_sorted(zs, n, out);
 }
 
+// ---- the argument rules of the segmented entry points (pgl_ks_uniform*, pgl_rescale_acf*); each caller turns a nonzero
+// answer into its own message
+// the segment count M, one workgroup each along a grid's x: 1 .. 2^31 - 1.  0: fine, 1: not
+PGL_GOF_FN int pgl_gof_bad_count(long long M) { return M < 1 || M > 0x7fffffffLL; }
+
+// the offsets off[0 .. n] of n segments start at or above 0 and do not decrease.  0: fine; else 1 + the first index that
+// breaks the rule -- 1: off[0] < 0, 1 + i: off[i] < off[i - 1]
+PGL_GOF_FN long long pgl_gof_bad_offsets(const long long* off, long long n)
+{
+    if (off[0] < 0) return 1;
+    for (long long i = 1; i <= n; ++i)
+        if (off[i] < off[i - 1]) return 1 + i;
+    return 0;
+}
+
 #endif
