@@ -98,7 +98,7 @@ typedef struct pgl_context* pgl_handle;
 
 /* What pgl_version() returns: it changes with every change of a signature or a struct below, and a binding refuses a
  * library that reports another number (theano_pyglm_amd/_lib.py: ABI_VERSION). */
-#define PGL_ABI_VERSION 115
+#define PGL_ABI_VERSION 116
 
 const char* pgl_last_error(void);
 int pgl_version(void);
@@ -1018,6 +1018,36 @@ int pgl_rate_windows(pgl_handle h, const double* theta, const double* Weff, int6
 #define PGL_PSIS_MAX_DRAWS 4096
 int pgl_psis_loo_dev(pgl_handle h, const double* d_ll, int64_t S, int64_t C, int64_t ld, double* d_out, double* d_lw);
 int pgl_psis_loo(pgl_handle h, const double* ll, int64_t S, int64_t C, double* out, double* lw);
+
+/* Wald statistics of the coupling groups from the factor of the Laplace covariance: which couplings are there (the per-pair
+ * Granger-causality test of Kim, Putrino, Ghosh & Brown 2011 in its Wald form; inference/connectivity.py: coupling_tests).
+ * The reference has no such test.  d_W (M, P, ld): row m lower triangular with W_m W_m^T = A_m^-1, as laplace_from_factor
+ * leaves it; only the entries j <= i are read (the strict upper triangle and the columns P .. ld-1 may hold anything).
+ * d_theta (M, P); group g of a row is the B entries from o = first + g B (theta rows [bias, w_stim (Ds), w_ir (N groups of B)]:
+ * first = 1 + Ds, G = N); d_c (B) a contrast.  For every row and group
+ *     S = W_g W_g^T  (the group's B x B block of the covariance),  y = S^-1 w_g  by an unpivoted Cholesky factorisation,
+ *     T = w_g^T y,  lin = c^T w_g,  var = c^T S c
+ * and d_out (M, G, PGL_WALD_NOUT) = T, lin, var, info: info = 0, or a + 1 for the first pivot a of S that is not finite or
+ * <= 0 -- then T, lin and var of that group alone are NaN.  Under H0: w_g = 0 and the quadratic approximation T is chi-square
+ * with B degrees of freedom.  d_u: NULL, or (G M, P) with row g M + m (the particle-major order of pgl_tri_matvec_shared_dev
+ * with K = G) = W_g^T y, zero from column o + B on: theta_m - W_m u is the restricted one-step point with group g at
+ * zero.  Whole rows are written; a group with info != 0 has NaN in the columns below o + B.  d_info (M) int32 as
+ * pgl_chol_factor_dev leaves it: a row with d_info[m] != 0 gets NaN in d_out (and d_u) and its W and theta are not read.
+ * The order of every sum is part of the rule (csrc/pglm_wald.h: columns by lane k mod 64, ascending, a binary tree over the
+ * lanes, no fused multiply-add) and depends on (o, B) alone: a group gives the same bits alone or among others, two calls
+ * give the same bits, and the gcc build of the rule (tests/csrc/wald_host.c) gives the device's bits.
+ * One wave per group, four groups per workgroup, on a grid of (blocks of groups, rows) (k_wald_groups<B>): the group's rows of
+ * W are read once along the rows for S; with d_u they are read a second time by the same wave.  f64 throughout, no atomics,
+ * no scratch, asynchronous on the handle's stream; the handle supplies device and stream only.
+ * M, G, B <= 0, ld < P, first < 0, first + G B > P or a NULL pointer other than d_u: PGL_ERR_ARG;  B > PGL_WALD_MAX_B or
+ * M > 65535: PGL_ERR_UNSUPPORTED.
+ * wald_groups: the same with host pointers, W (M, P, ld), u (G M, P) or NULL. */
+#define PGL_WALD_MAX_B 16
+#define PGL_WALD_NOUT 4
+int pgl_wald_groups_dev(pgl_handle h, const double* d_W, int M, int P, int ld, const double* d_theta, int first, int G, int B,
+                        const double* d_c, const int* d_info, double* d_out, double* d_u);
+int pgl_wald_groups(pgl_handle h, const double* W, int M, int P, int ld, const double* theta, int first, int G, int B, const double* c,
+                    const int* info, double* out, double* u);
 
 /* Convergence diagnostics of posterior draws (Vehtari, Gelman, Simpson, Carpenter & Buerkner 2021): rank-normalised and folded
  * split-R-hat, bulk and tail effective sample size, the Monte-Carlo standard error of the mean, and the pooled moments and

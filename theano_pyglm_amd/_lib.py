@@ -57,12 +57,13 @@ SYMBOLS = [
     'pgl_pointwise_count', 'pgl_pointwise_dev', 'pgl_pointwise',
     'pgl_rate_windows_count', 'pgl_rate_windows_dev', 'pgl_rate_windows',
     'pgl_psis_loo_dev', 'pgl_psis_loo',
+    'pgl_wald_groups_dev', 'pgl_wald_groups',
     'pgl_chain_diag_dev', 'pgl_chain_diag',
     'pgl_simulate_streams', 'pgl_simulate_batch', 'pgl_simulate_batch_dev', 'pgl_simulate_batch_plan',
 ]
 
 
-ABI_VERSION = 115                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
+ABI_VERSION = 116                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
 
 GEMM_NT, GEMM_MFMA_1, GEMM_MFMA_4, GEMM_KC_4_1_8, GEMM_KC_1_0_16 = range(5)   # PGL_GEMM_*: the kernel of pgl_gemm_dev
 
@@ -76,6 +77,8 @@ ACF_PIECE = 256                     # PGL_ACF_PIECE: the elements of a piece of 
 KS_TILE = 4096                      # PGL_KS_TILE: the doubles of a tile of the KS sort (csrc/pglm_gof.h)
 PSIS_NOUT = 4                       # PGL_PSIS_NOUT: planes of psis_loo's result -- elpd, khat, n_eff, tail length
 PSIS_MAX_DRAWS = 4096               # PGL_PSIS_MAX_DRAWS: the draws a workgroup's LDS holds; more: PGL_ERR_UNSUPPORTED
+WALD_MAX_B = 16                     # PGL_WALD_MAX_B: the largest coupling group wald_groups serves; more: PGL_ERR_UNSUPPORTED
+WALD_NOUT = 4                       # PGL_WALD_NOUT: T, lin, var, info per group (csrc/pglm_wald.h)
 DIAG_MAX_DRAWS = 4096               # PGL_DIAG_MAX_DRAWS: the pooled draws (chains x draws) chain_diag's workgroup holds
 DIAG_ROWS = ('mean', 'sd', 'median', 'q025', 'q975', 'rhat_plain', 'rhat', 'ess_bulk', 'ess_tail', 'ess_mean', 'mcse_mean',
              'lag_bulk', 'lag_q05', 'lag_q95', 'lag_mean')          # the rows of chain_diag's result, in PGL_DIAG_* order
@@ -220,6 +223,8 @@ def load():
     lib.pgl_rate_windows.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
     lib.pgl_psis_loo_dev.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp]
     lib.pgl_psis_loo.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp]
+    lib.pgl_wald_groups_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    lib.pgl_wald_groups.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.pgl_chain_diag_dev.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp]
     lib.pgl_chain_diag.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp]
     # the lock-step methods; pr: const pgl_prior*
@@ -906,6 +911,49 @@ class DeviceGlm(object):
         lw = np.empty(a.shape) if weights else None
         _chk(self.lib.pgl_psis_loo(self.h, _ptr(a), int(S), int(np.prod(shape)), _ptr(out), _ptr(lw) if weights else None))
         return (out, lw) if weights else out
+
+    # -- Wald statistics of the coupling groups from the factor of the Laplace covariance (pgl_wald_groups*) -----------
+    def wald_groups(self, W, theta, first, G, B, c, info, out=None, u=False):
+        """T, lin, var, info of the G groups of B weights from column `first` of every row (pgl_wald_groups_dev; the rule:
+        csrc/pglm_wald.h).  Torch device tensors: W (M, P, ld) f64, ld >= P, row m lower triangular in its first P columns
+        with W W^T the Laplace covariance, theta (M, P) f64, c (B,) f64, info (M,) int32 (chol_factor's).
+        Returns out (M, G, 4) on W's device, written into `out` where given; u=True also returns (G * M, P) = W_g^T S^-1 w_g,
+        row g * M + m, u=<tensor of that shape> writes it there.  Asynchronous on the handle's stream."""
+        torch = self._stack(W, 'wald_groups')
+        M, P, ld = (int(v) for v in W.shape)
+        G, B, first = int(G), int(B), int(first)
+        _dev_tensor(theta, 'float64', "wald_groups: theta must be a contiguous float64 device tensor (M, P)", shape=(M, P))
+        _dev_tensor(c, 'float64', "wald_groups: c must be a contiguous float64 device tensor (B,)", shape=(B,))
+        _dev_tensor(info, 'int32', "wald_groups: info must be a contiguous int32 device tensor (M,)", shape=(M,))
+        out = _out_tensor(out, (M, G, WALD_NOUT), W, "wald_groups: out must be a contiguous float64 device tensor (M, G, 4)")
+        du = _second_out(u, lambda: torch.empty((G * M, P), dtype=torch.float64, device=W.device),
+                         lambda t: _dev_tensor(t, 'float64', "wald_groups: u must be a contiguous float64 device tensor (G * M, P)",
+                                               shape=(G * M, P)))
+        _chk(self.lib.pgl_wald_groups_dev(self.h, _dp(W), M, P, ld, _dp(theta), first, G, B, _dp(c), _dp(info), _dp(out), _dp(du)))
+        return out if du is None else (out, du)
+
+    def wald_groups_dev(self, d_W, M, P, ld, d_theta, first, G, B, d_c, d_info, d_out, d_u=0):
+        """Device-pointer form (integers or tensors; d_u = 0: no directions): see pgl_wald_groups_dev."""
+        _chk(self.lib.pgl_wald_groups_dev(self.h, _dp(d_W), int(M), int(P), int(ld), _dp(d_theta), int(first), int(G), int(B),
+                                          _dp(d_c), _dp(d_info), _dp(d_out), _dp(d_u)))
+
+    def wald_groups_host(self, W, theta, first, G, B, c, info=None, u=False):
+        """The same with host arrays: W (M, P, ld), theta (M, P), c (B,), info (M,) or None for zeros -> out (M, G, 4), or
+        (out, u) with u=True (pgl_wald_groups)."""
+        Wc = np.ascontiguousarray(W, dtype=np.float64)
+        if Wc.ndim != 3:
+            raise ValueError("wald_groups_host: W (M, P, ld)")
+        M, P, ld = Wc.shape
+        th = _f64(theta, (M, P))
+        cc = _f64(c, (int(B),))
+        inf = np.zeros(M, dtype=np.int32) if info is None else np.ascontiguousarray(info, dtype=np.int32)
+        if inf.shape != (M,):
+            raise ValueError("wald_groups_host: info (M,)")
+        out = np.empty((M, int(G), WALD_NOUT))
+        uu = np.empty((int(G) * M, P)) if u else None
+        _chk(self.lib.pgl_wald_groups(self.h, _ptr(Wc), M, P, ld, _ptr(th), int(first), int(G), int(B), _ptr(cc), _ptr(inf),
+                                      _ptr(out), _ptr(uu)))
+        return (out, uu) if u else out
 
     # -- convergence diagnostics of the columns of a samplers' tensor (pgl_chain_diag*) ------------------
     def chain_diag(self, x, n_chains=1, out=None):

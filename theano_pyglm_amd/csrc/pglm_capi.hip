@@ -131,7 +131,7 @@ struct pgl_context {
     DevBuf rw_part, rw_cnt;              // rate windows (pgl_rate_windows_dev): piece sums of rate and spike counts
     // the host-array forms (pgl_hvp .. pgl_chain_diag): the device copies of their arrays, taken by index (stage_up).  Every
     // such call ends in stage_end, so a slot holds nothing across calls and the forms share them
-    static constexpr int NSTAGE = 4;
+    static constexpr int NSTAGE = 6;     // (pgl_wald_groups moves six arrays)
     DevBuf stage[NSTAGE];
     std::vector<double> hvp_host;        // pgl_hvp: theta and Weff of its last prepare (a CG solve repeats them: no new prepare)
 };
@@ -3260,6 +3260,54 @@ int pgl_psis_loo(pgl_handle h, const double* ll, int64_t S, int64_t C, double* o
     PASS(pgl_psis_loo_dev(h, (const double*)h->stage[0].p, S, C, C, (double*)h->stage[1].p, lw ? (double*)h->stage[2].p : nullptr));
     PASS(stage_down(h, out, h->stage[1].p, obytes));
     PASS(stage_down(h, lw, h->stage[2].p, bytes));
+    return stage_end(h);
+}
+
+// ---- Wald statistics of the coupling groups from the factor of the Laplace covariance (pglm_wald.hip.h) -------------------
+static int wald_check(pgl_handle h, const void* W, int M, int P, int ld, const void* theta, int first, int G, int B, const void* c,
+                      const void* info, const void* out)
+{
+    if (!h) return fail(PGL_ERR_ARG, "null handle");
+    if (!W || !theta || !c || !info || !out) return fail(PGL_ERR_ARG, "pgl_wald_groups: null argument");
+    if (M <= 0 || G <= 0 || B <= 0 || P <= 0 || ld < P || first < 0 || (long long)first + (long long)G * B > P)
+        return fail(PGL_ERR_ARG, "pgl_wald_groups: M, G, B >= 1, ld >= P, first >= 0 and first + G B <= P");
+    if (B > PGL_WALD_MAX_B)
+        return fail(PGL_ERR_UNSUPPORTED, "pgl_wald_groups: groups of more than PGL_WALD_MAX_B = " + std::to_string(PGL_WALD_MAX_B) +
+                                         " weights");
+    if (M > 65535) return fail(PGL_ERR_UNSUPPORTED, "pgl_wald_groups: at most 65535 rows per call");
+    return PGL_OK;
+}
+
+int pgl_wald_groups_dev(pgl_handle h, const double* d_W, int M, int P, int ld, const double* d_theta, int first, int G, int B,
+                        const double* d_c, const int* d_info, double* d_out, double* d_u)
+{
+    PASS(wald_check(h, d_W, M, P, ld, d_theta, first, G, B, d_c, d_info, d_out));
+    HIPCHK(hipSetDevice(h->device));
+    WaldParams p;
+    p.W = d_W; p.theta = d_theta; p.c = d_c; p.info = d_info; p.out = d_out; p.u = d_u;
+    p.P = P; p.ld = ld; p.M = M; p.first = first; p.G = G;
+    wald_launch(B, p, h->stream);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+int pgl_wald_groups(pgl_handle h, const double* W, int M, int P, int ld, const double* theta, int first, int G, int B, const double* c,
+                    const int* info, double* out, double* u)
+{
+    PASS(wald_check(h, W, M, P, ld, theta, first, G, B, c, info, out));
+    HIPCHK(hipSetDevice(h->device));
+    const size_t wb = (size_t)M * P * ld * 8, tb = (size_t)M * P * 8, ob = (size_t)M * G * PGL_WALD_NOUT * 8, ub = (size_t)G * M * P * 8;
+    PASS(stage_up(h, 0, W, wb));
+    PASS(stage_up(h, 1, theta, tb));
+    PASS(stage_up(h, 2, c, (size_t)B * 8));
+    PASS(stage_up(h, 3, info, (size_t)M * 4));
+    PASS(stage_up(h, 4, nullptr, ob));
+    if (u) PASS(stage_up(h, 5, nullptr, ub));
+    PASS(pgl_wald_groups_dev(h, (const double*)h->stage[0].p, M, P, ld, (const double*)h->stage[1].p, first, G, B,
+                             (const double*)h->stage[2].p, (const int*)h->stage[3].p, (double*)h->stage[4].p,
+                             u ? (double*)h->stage[5].p : nullptr));
+    PASS(stage_down(h, out, h->stage[4].p, ob));
+    PASS(stage_down(h, u, h->stage[5].p, ub));
     return stage_end(h);
 }
 

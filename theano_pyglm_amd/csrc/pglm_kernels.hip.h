@@ -46,6 +46,8 @@
 // lag, with run boundaries between the data sequences -- is one workgroup per segment as well (k_acf_segment, pglm_acf.hip.h).
 // PSIS-LOO takes the matrix of those terms over the draws one column per workgroup: ranks, generalized-Pareto fit, smoothed
 // weights (k_psis_column, pglm_psis.hip.h).
+// The couplings are tested from the factor of the Laplace covariance: one wave per group of B weights forms the group's
+// block of the covariance and its Wald statistic (k_wald_groups, pglm_wald.hip.h).
 // The samplers' draws are judged the same way, one column of (chains x draws) per workgroup: ranks by counting, normal scores,
 // split-R-hat, autocovariances in batches of lags and Geyer's sequence (k_diag_column, pglm_diag.hip.h).
 #pragma once
@@ -80,5 +82,6 @@
 #include "pglm_pointwise.hip.h"
 #include "pglm_ratewin.hip.h"
 #include "pglm_psis.hip.h"
+#include "pglm_wald.hip.h"
 #include "pglm_diag.hip.h"
 #include "pglm_simulate.hip.h"

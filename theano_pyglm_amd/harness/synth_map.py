@@ -34,6 +34,10 @@ outside the draws' [min, max] (inference/predictive.py: rate_bands over windows 
 --diag (with --hmc N or --nuts N, N >= 8) prints the convergence diagnostics of those draws per neuron: the worst rank-normalised
 R-hat, the smallest bulk and tail ESS, and the number of parameters with rhat > 1.01 or ess_bulk < 100 per chain
 (inference/diagnostics.py: k_diag_column on the draws where the sampler keeps them).
+--coupling-test [ALPHA] prints, after the fit, the number of couplings that the per-pair Wald tests find at the false discovery
+rate ALPHA (default 0.05; inference/connectivity.py) and, where the data carry the true model, the true- and false-positive
+rates against the true adjacency and the area under the ROC of the statistic; --coupling-lr adds the median and maximum of
+|lr1 - T| / max(T, 1), the check of the quadratic approximation.
 """
 import argparse
 import os
@@ -64,7 +68,7 @@ def initialize_test_harness(model_name, data, data_dir=None):
 
 def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False, gof=False, ppc=0, hmc=0, ais=0,
                    hmc_mass='laplace', prox=False, laplace_device=False, ais_mass='laplace', nuts=0, smc=0, newton=False, waic=False, loo=False, diag=False, rates=0,
-                   gof_correct=False, gof_draws=False, gof_lags=0):
+                   gof_correct=False, gof_draws=False, gof_lags=0, coupling_test=None, coupling_lr=False):
     """test/synth_map.py:10-32."""
     popn, popn_true, x_true = initialize_test_harness(model_name, data, data_dir)
     x0 = popn.sample(rng)
@@ -85,6 +89,8 @@ def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, r
         if gof_lags:
             from theano_pyglm_amd.inference.gof import independence_time_rescaling, format_independence_table
             print(format_independence_table(independence_time_rescaling(popn, x_inf, max_lag=gof_lags, correct=gof_correct)))
+    if coupling_test is not None:
+        print(coupling_table(popn, x_inf, coupling_test, coupling_lr, popn_true, x_true))
     if ppc:
         from theano_pyglm_amd.inference import predictive
         print(predictive.format_table(predictive.predictive_counts(popn, x_inf, ppc)))
@@ -97,6 +103,19 @@ def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, r
     if smc:
         print(smc_evidence_table(popn, x_inf, smc, laplace_device, ais_mass))
     return x_inf, ll_inf, wall
+
+
+def coupling_table(popn, x, alpha=0.05, one_step_lr=False, popn_true=None, x_true=None):
+    """connectivity.format_table of the per-pair Wald tests at x; with the true model, against its adjacency (a coupling is
+    there where the true effective weight W_eff[pre, post] is not zero)."""
+    import numpy as np
+    from theano_pyglm_amd.inference import connectivity
+    t0 = time.time()
+    res = connectivity.coupling_tests(popn, x, alpha=alpha, one_step_lr=one_step_lr)
+    truth = None
+    if popn_true is not None and x_true is not None:
+        truth = (np.asarray(popn_true.W_eff(x_true)) != 0.0).T                 # [post, pre]
+    return connectivity.format_table(res, alpha, truth) + "\n(coupling tests in %.2f s)" % (time.time() - t0)
 
 
 def prox_table(popn, x):
@@ -335,6 +354,12 @@ def parser():
     ap.add_argument('--loo', action='store_true',
                     help='with --hmc N or --nuts N: PSIS-LOO of every neuron from those draws, with the khat diagnostic per '
                          'block (the matrix of pointwise terms stays on the device; beside or instead of --waic)')
+    ap.add_argument('--coupling-test', type=float, nargs='?', const=0.05, default=None, metavar='ALPHA',
+                    help='after the fit: per-pair Wald tests of the couplings with Benjamini-Hochberg control at ALPHA (default '
+                         '0.05); with the true model in the data, true- and false-positive rates and the area under the ROC')
+    ap.add_argument('--coupling-lr', action='store_true',
+                    help='with --coupling-test: the one-step likelihood ratio beside the Wald statistic, median and maximum of '
+                         '|lr1 - T| / max(T, 1)')
     return ap
 
 
@@ -346,7 +371,8 @@ def main(argv=None):
                    False if args.sequential else ('torch' if args.newton_cg else None), use_rop=args.newton_cg, gof=args.gof, ppc=args.ppc, hmc=args.hmc, ais=args.ais,
                    hmc_mass=args.hmc_mass, prox=args.prox, laplace_device=args.laplace_device, ais_mass=args.ais_mass, nuts=args.nuts, smc=args.smc,
                    newton=args.newton, waic=args.waic, loo=args.loo, diag=args.diag, rates=args.rates,
-                   gof_correct=args.gof_correct, gof_draws=args.gof_draws, gof_lags=args.gof_lags)
+                   gof_correct=args.gof_correct, gof_draws=args.gof_draws, gof_lags=args.gof_lags,
+                   coupling_test=args.coupling_test, coupling_lr=args.coupling_lr)
 
 
 if __name__ == '__main__':
