@@ -98,7 +98,7 @@ typedef struct pgl_context* pgl_handle;
 
 /* What pgl_version() returns: it changes with every change of a signature or a struct below, and a binding refuses a
  * library that reports another number (theano_pyglm_amd/_lib.py: ABI_VERSION). */
-#define PGL_ABI_VERSION 116
+#define PGL_ABI_VERSION 117
 
 const char* pgl_last_error(void);
 int pgl_version(void);
@@ -1076,6 +1076,41 @@ int pgl_wald_groups(pgl_handle h, const double* W, int M, int P, int ld, const d
 #define PGL_DIAG_MAX_DRAWS 4096
 int pgl_chain_diag_dev(pgl_handle h, const double* d_x, int64_t n, int64_t C, int64_t K, int64_t ld, double* d_out);
 int pgl_chain_diag(pgl_handle h, const double* x, int64_t n, int64_t C, int64_t K, double* out);
+
+/* Posterior bands of the filters: the curves h(tau) = sum_b basis[tau, b] w_b of the groups of B weights of the theta rows,
+ * summarised over the draws of a samplers' tensor d_samples (n_keep, C M, P) -- draw i of chain c of row m at
+ * ((i C + c) M + m) P, pooled s = c n_keep + i as pgl_chain_diag pools them, S = C n_keep -- where it lies: the counterpart of
+ * the reference's average_list_of_dicts / std_list_of_dicts over eval_state (utils/avg_dicts.py) for the curves
+ * plot_imp_responses draws as mean +- 2 sd, plus quantiles and a simultaneous credible band.  Group g of a row is the B entries
+ * from o = first + g B.  Theta rows are [bias, w_stim (D groups of B_stim, dimension-major), w_ir (N groups of B_imp,
+ * presynaptic-neuron-major)]: the impulse responses are first = 1 + D B_stim, G = N, B = B_imp with the impulse basis, the
+ * stimulus filters first = 1, G = D, B = B_stim with the stimulus basis.  d_basis (R, B) row-major; d_c (B) a contrast (the
+ * effective weight: c_b = dt sum_t basis[t, b]); level in (0, 1).  The rule of one (row, group) is csrc/pglm_filters.h's:
+ *   per lag   mean, sd (S - 1), and q_lo, median, q_hi at (1 - level) / 2, 1 / 2, (1 + level) / 2 by numpy.percentile's linear
+ *             rule on the sorted values; a lag whose curve overflows in some draw is NaN;
+ *   band      d_s = max over the lags with sd > 0 of |h_s - mean| / sd; c_sim = the ceil(level S)-th smallest d_s: at least a
+ *             share `level` of the draws lies within mean +- c_sim sd at every lag at once;
+ *   weight    omega_s = sum_b c[b] w_s[b]: its mean, sd and the three quantiles, and p_pos = #{omega_s > 0} / S.
+ * d_out (M, G, R, PGL_FILT_NLAG) = mean, sd, q_lo, median, q_hi;  d_grp (M, G, PGL_FILT_NGRP) = c_sim, the five figures of
+ * omega, p_pos, info.  info = 0, or 1 where a weight of the group is not finite in some draw: every other output of that group
+ * alone is NaN.  Every sum has a fixed order (pieces of 256 consecutive draws, ascending, the pieces in order; no fused
+ * multiply-add) that depends on (S, B, R, o) alone: a group gives the same bits alone or among others, two calls give the same
+ * bits, and the gcc build of the rule (tests/csrc/filters_host.c) gives the device's bits.
+ * One workgroup per (group, row) (k_filter_bands<B>): the group's weights are read once into LDS where they fit beside the
+ * sort buffer (S B + next_pow2(S) <= 18 432 doubles) and re-read per lag through L2 otherwise; the S values of a lag are sorted
+ * by a bitonic network in LDS.  f64 throughout, no atomics, no scratch, asynchronous on the handle's stream; the handle supplies
+ * device and stream only.
+ * n_keep, C, M, G, B, R <= 0, S < 2, first < 0, first + G B > P, level outside (0, 1) or a NULL pointer: PGL_ERR_ARG;
+ * S > PGL_FILT_MAX_DRAWS, B > PGL_FILT_MAX_B or M > 65535: PGL_ERR_UNSUPPORTED; nothing is launched.
+ * filter_bands: the same with host pointers, all arrays contiguous. */
+#define PGL_FILT_MAX_B 16
+#define PGL_FILT_MAX_DRAWS 4096
+#define PGL_FILT_NLAG 5
+#define PGL_FILT_NGRP 8
+int pgl_filter_bands_dev(pgl_handle h, const double* d_samples, int64_t n_keep, int64_t C, int M, int P, int first, int G, int B,
+                         const double* d_basis, int R, const double* d_c, double level, double* d_out, double* d_grp);
+int pgl_filter_bands(pgl_handle h, const double* samples, int64_t n_keep, int64_t C, int M, int P, int first, int G, int B,
+                     const double* basis, int R, const double* c, double level, double* out, double* grp);
 
 /* Spike-triggered average, pyglm/utils/sta.py:6-85 (used by smart_init.py:28-98 and 100-158):
  *   A[i,l,d] = sum_t S[t,n_i] * istim[t-l,d] / sum_t S[t,n_i],  l = 0..L-1, terms with t-l < 0 dropped,

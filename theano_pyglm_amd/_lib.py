@@ -59,11 +59,12 @@ SYMBOLS = [
     'pgl_psis_loo_dev', 'pgl_psis_loo',
     'pgl_wald_groups_dev', 'pgl_wald_groups',
     'pgl_chain_diag_dev', 'pgl_chain_diag',
+    'pgl_filter_bands_dev', 'pgl_filter_bands',
     'pgl_simulate_streams', 'pgl_simulate_batch', 'pgl_simulate_batch_dev', 'pgl_simulate_batch_plan',
 ]
 
 
-ABI_VERSION = 116                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
+ABI_VERSION = 117                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
 
 GEMM_NT, GEMM_MFMA_1, GEMM_MFMA_4, GEMM_KC_4_1_8, GEMM_KC_1_0_16 = range(5)   # PGL_GEMM_*: the kernel of pgl_gemm_dev
 
@@ -83,6 +84,10 @@ DIAG_MAX_DRAWS = 4096               # PGL_DIAG_MAX_DRAWS: the pooled draws (chai
 DIAG_ROWS = ('mean', 'sd', 'median', 'q025', 'q975', 'rhat_plain', 'rhat', 'ess_bulk', 'ess_tail', 'ess_mean', 'mcse_mean',
              'lag_bulk', 'lag_q05', 'lag_q95', 'lag_mean')          # the rows of chain_diag's result, in PGL_DIAG_* order
 DIAG_NOUT = len(DIAG_ROWS)          # PGL_DIAG_NOUT
+FILT_MAX_B = 16                     # PGL_FILT_MAX_B: the largest group of weights filter_bands serves
+FILT_MAX_DRAWS = 4096               # PGL_FILT_MAX_DRAWS: the pooled draws filter_bands' workgroup sorts in LDS
+FILT_LAG_COLS = ('mean', 'sd', 'q_lo', 'median', 'q_hi')            # the PGL_FILT_NLAG figures per lag (csrc/pglm_filters.h)
+FILT_GRP_COLS = ('c_sim', 'weight_mean', 'weight_sd', 'weight_q_lo', 'weight_median', 'weight_q_hi', 'p_pos', 'info')   # PGL_FILT_NGRP
 
 
 class PglError(RuntimeError):
@@ -227,6 +232,8 @@ def load():
     lib.pgl_wald_groups.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.pgl_chain_diag_dev.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp]
     lib.pgl_chain_diag.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp]
+    lib.pgl_filter_bands_dev.argtypes = lib.pgl_filter_bands.argtypes = \
+        [vp, vp, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_double, vp, vp]
     # the lock-step methods; pr: const pgl_prior*
     lib.pgl_bfgs_state_doubles.argtypes = [C.c_int, C.c_int]
     lib.pgl_bfgs_init_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double]
@@ -990,6 +997,55 @@ class DeviceGlm(object):
         out = np.empty((DIAG_NOUT,) + shape)
         _chk(self.lib.pgl_chain_diag(self.h, _ptr(a), int(a.shape[0]), nc, int(np.prod(shape)), _ptr(out)))
         return out
+
+    # -- posterior bands of the filters from the samplers' draws (pgl_filter_bands*) ----------------------
+    def filter_bands(self, samples, n_chains, first, G, basis, c, level, out=None, grp=None):
+        """The bands of the G groups of B weights from column `first` of every theta row over the draws of the torch device
+        tensor samples (n, n_chains * M, P) f64, contiguous, as the lock-step samplers keep it (pgl_filter_bands_dev; the
+        rule: csrc/pglm_filters.h).  basis (R, B) and c (B,) contiguous f64 device tensors.  Returns (out (M, G, R, 5) in
+        FILT_LAG_COLS order, grp (M, G, 8) in FILT_GRP_COLS order) on the samples' device, written into `out` / `grp` where
+        given.  Asynchronous on the handle's stream."""
+        nc = int(n_chains)
+        _dev_tensor(samples, 'float64', "filter_bands: samples must be a contiguous float64 device tensor (n, n_chains * M, P)",
+                    ndim=3, numel=1)
+        if nc < 1 or samples.shape[1] % nc:
+            raise ValueError("filter_bands: axis 1 must hold n_chains blocks of rows")
+        n, M, P = int(samples.shape[0]), int(samples.shape[1]) // nc, int(samples.shape[2])
+        _dev_tensor(basis, 'float64', "filter_bands: basis must be a contiguous float64 device tensor (R, B)", ndim=2, numel=1)
+        R, B = (int(v) for v in basis.shape)
+        G, first = int(G), int(first)
+        _dev_tensor(c, 'float64', "filter_bands: c must be a contiguous float64 device tensor (B,)", shape=(B,))
+        out = _out_tensor(out, (M, G, R, len(FILT_LAG_COLS)), samples,
+                          "filter_bands: out must be a contiguous float64 device tensor (M, G, R, 5)")
+        grp = _out_tensor(grp, (M, G, len(FILT_GRP_COLS)), samples,
+                          "filter_bands: grp must be a contiguous float64 device tensor (M, G, 8)")
+        _chk(self.lib.pgl_filter_bands_dev(self.h, _dp(samples), n, nc, M, P, first, G, B, _dp(basis), R, _dp(c), float(level),
+                                           _dp(out), _dp(grp)))
+        return out, grp
+
+    def filter_bands_dev(self, d_samples, n, C_, M, P, first, G, B, d_basis, R, d_c, level, d_out, d_grp):
+        """Device-pointer form (integers or tensors): see pgl_filter_bands_dev."""
+        _chk(self.lib.pgl_filter_bands_dev(self.h, _dp(d_samples), int(n), int(C_), int(M), int(P), int(first), int(G), int(B),
+                                           _dp(d_basis), int(R), _dp(d_c), float(level), _dp(d_out), _dp(d_grp)))
+
+    def filter_bands_host(self, samples, n_chains, first, G, basis, c, level):
+        """The same with host arrays: samples (n, n_chains * M, P), basis (R, B), c (B,) -> (out (M, G, R, 5), grp (M, G, 8))
+        (pgl_filter_bands)."""
+        a = np.ascontiguousarray(samples, dtype=np.float64)
+        nc = int(n_chains)
+        if a.ndim != 3 or a.size == 0 or nc < 1 or a.shape[1] % nc:
+            raise ValueError("filter_bands_host: samples (n, n_chains * M, P)")
+        n, M, P = a.shape[0], a.shape[1] // nc, a.shape[2]
+        bs = np.ascontiguousarray(basis, dtype=np.float64)
+        if bs.ndim != 2 or bs.size == 0:
+            raise ValueError("filter_bands_host: basis (R, B)")
+        R, B = bs.shape
+        cc = _f64(c, (B,))
+        out = np.empty((M, int(G), R, len(FILT_LAG_COLS)))
+        grp = np.empty((M, int(G), len(FILT_GRP_COLS)))
+        _chk(self.lib.pgl_filter_bands(self.h, _ptr(a), int(n), nc, int(M), int(P), int(first), int(G), int(B), _ptr(bs), int(R),
+                                       _ptr(cc), float(level), _ptr(out), _ptr(grp)))
+        return out, grp
 
     # -- lock-step optimiser bookkeeping (device pointers as integers; asynchronous on the handle's stream) --
     def bfgs_state_doubles(self, M, P):

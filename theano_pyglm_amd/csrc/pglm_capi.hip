@@ -308,6 +308,35 @@ static int sim_launch(const SimParams& sp, int n_rep, int threads, size_t lds, h
     return PGL_OK;
 }
 
+// one workgroup per (group, row) (k_filter_bands, pglm_filters.hip.h); above 64 KiB of LDS the instantiation opts in once
+template <int B>
+static hipError_t filt_launch_b(const FiltParams& p, size_t lds, hipStream_t stream)
+{
+    if (lds + 512 > 65536) {                                   // (the static LDS of the kernel is 392 bytes)
+        const hipError_t e = ensure_dyn_lds(k_filter_bands<B>, lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_filter_bands<B>, dim3((unsigned)p.G, (unsigned)p.M), dim3(PGL_FILT_THREADS), lds, stream, p);
+    return hipGetLastError();
+}
+
+// B in 1 .. PGL_FILT_MAX_B and n C in 2 .. PGL_FILT_MAX_DRAWS (filt_check); fills Spad and resident
+static hipError_t filt_launch(int B, FiltParams p, hipStream_t stream)
+{
+    const long long S = (long long)p.n * p.C;
+    p.Spad = filt_pad(S);
+    p.resident = filt_resident(S, B);
+    const size_t lds = filt_lds_bytes(S, B);
+    switch (B) {
+#define PGL_FILT_CASE(b) case b: return filt_launch_b<b>(p, lds, stream);
+        PGL_FILT_CASE(1) PGL_FILT_CASE(2) PGL_FILT_CASE(3) PGL_FILT_CASE(4) PGL_FILT_CASE(5) PGL_FILT_CASE(6) PGL_FILT_CASE(7)
+        PGL_FILT_CASE(8) PGL_FILT_CASE(9) PGL_FILT_CASE(10) PGL_FILT_CASE(11) PGL_FILT_CASE(12) PGL_FILT_CASE(13)
+        PGL_FILT_CASE(14) PGL_FILT_CASE(15) PGL_FILT_CASE(16)
+#undef PGL_FILT_CASE
+    }
+    return hipErrorInvalidValue;
+}
+
 // one workgroup of 256 threads per row on the handle's stream: the launch shape of every row kernel of the lock-step methods
 template <typename... Params, typename... Args>
 static int launch_rows(pgl_handle h, void (*kernel)(Params...), int rows, Args&&... args)
@@ -3341,6 +3370,56 @@ int pgl_chain_diag(pgl_handle h, const double* x, int64_t n, int64_t C, int64_t 
     PASS(stage_up(h, 1, nullptr, obytes));
     PASS(pgl_chain_diag_dev(h, (const double*)h->stage[0].p, n, C, K, K, (double*)h->stage[1].p));
     PASS(stage_down(h, out, h->stage[1].p, obytes));
+    return stage_end(h);
+}
+
+// ---- posterior bands of the filters from the samplers' draws (pglm_filters.hip.h) -----------------------------------------
+static int filt_check(pgl_handle h, const void* x, int64_t n, int64_t C, int M, int P, int first, int G, int B, const void* basis,
+                      int R, const void* c, double level, const void* out, const void* grp)
+{
+    if (!h) return fail(PGL_ERR_ARG, "null handle");
+    if (!x || !basis || !c || !out || !grp) return fail(PGL_ERR_ARG, "pgl_filter_bands: null argument");
+    if (n < 1 || C < 1 || M <= 0 || G <= 0 || B <= 0 || R <= 0 || P <= 0 || first < 0 || (long long)first + (long long)G * B > P)
+        return fail(PGL_ERR_ARG, "pgl_filter_bands: n, C, M, G, B, R >= 1, first >= 0 and first + G B <= P");
+    if (n == 1 && C == 1) return fail(PGL_ERR_ARG, "pgl_filter_bands: at least 2 pooled draws");
+    if (n > PGL_FILT_MAX_DRAWS || C > PGL_FILT_MAX_DRAWS || n * C > PGL_FILT_MAX_DRAWS)
+        return fail(PGL_ERR_UNSUPPORTED, "pgl_filter_bands: more than PGL_FILT_MAX_DRAWS = " + std::to_string(PGL_FILT_MAX_DRAWS) +
+                                         " pooled draws do not fit a workgroup's LDS");
+    if (!(level > 0.0 && level < 1.0)) return fail(PGL_ERR_ARG, "pgl_filter_bands: level in (0, 1)");
+    if (B > PGL_FILT_MAX_B)
+        return fail(PGL_ERR_UNSUPPORTED, "pgl_filter_bands: groups of more than PGL_FILT_MAX_B = " + std::to_string(PGL_FILT_MAX_B) +
+                                         " weights");
+    if (M > 65535) return fail(PGL_ERR_UNSUPPORTED, "pgl_filter_bands: at most 65535 rows per call");
+    return PGL_OK;
+}
+
+int pgl_filter_bands_dev(pgl_handle h, const double* d_samples, int64_t n_keep, int64_t C, int M, int P, int first, int G, int B,
+                         const double* d_basis, int R, const double* d_c, double level, double* d_out, double* d_grp)
+{
+    PASS(filt_check(h, d_samples, n_keep, C, M, P, first, G, B, d_basis, R, d_c, level, d_out, d_grp));
+    HIPCHK(hipSetDevice(h->device));
+    FiltParams p;
+    p.x = d_samples; p.basis = d_basis; p.c = d_c; p.out = d_out; p.grp = d_grp; p.level = level;
+    p.P = P; p.n = (int)n_keep; p.C = (int)C; p.M = M; p.first = first; p.G = G; p.R = R; p.Spad = 0; p.resident = 0;
+    HIPCHK(filt_launch(B, p, h->stream));
+    return PGL_OK;
+}
+
+int pgl_filter_bands(pgl_handle h, const double* samples, int64_t n_keep, int64_t C, int M, int P, int first, int G, int B,
+                     const double* basis, int R, const double* c, double level, double* out, double* grp)
+{
+    PASS(filt_check(h, samples, n_keep, C, M, P, first, G, B, basis, R, c, level, out, grp));
+    HIPCHK(hipSetDevice(h->device));
+    const size_t xb = (size_t)n_keep * C * M * P * 8, ob = (size_t)M * G * R * PGL_FILT_NLAG * 8, gb = (size_t)M * G * PGL_FILT_NGRP * 8;
+    PASS(stage_up(h, 0, samples, xb));
+    PASS(stage_up(h, 1, basis, (size_t)R * B * 8));
+    PASS(stage_up(h, 2, c, (size_t)B * 8));
+    PASS(stage_up(h, 3, nullptr, ob));
+    PASS(stage_up(h, 4, nullptr, gb));
+    PASS(pgl_filter_bands_dev(h, (const double*)h->stage[0].p, n_keep, C, M, P, first, G, B, (const double*)h->stage[1].p, R,
+                              (const double*)h->stage[2].p, level, (double*)h->stage[3].p, (double*)h->stage[4].p));
+    PASS(stage_down(h, out, h->stage[3].p, ob));
+    PASS(stage_down(h, grp, h->stage[4].p, gb));
     return stage_end(h);
 }
 

@@ -50,6 +50,9 @@
 // block of the covariance and its Wald statistic (k_wald_groups, pglm_wald.hip.h).
 // The samplers' draws are judged the same way, one column of (chains x draws) per workgroup: ranks by counting, normal scores,
 // split-R-hat, autocovariances in batches of lags and Geyer's sequence (k_diag_column, pglm_diag.hip.h).
+// The same draws become the filters with their uncertainty, one (group of B weights, row) per workgroup: the curve of every
+// draw lag by lag, moments in a fixed order, quantiles from a sorting network in LDS, a simultaneous band (k_filter_bands,
+// pglm_filters.hip.h).
 #pragma once
 //
 // The kernels live in one header per family; this file is the translation unit's table of contents.
@@ -84,4 +87,5 @@
 #include "pglm_psis.hip.h"
 #include "pglm_wald.hip.h"
 #include "pglm_diag.hip.h"
+#include "pglm_filters.hip.h"
 #include "pglm_simulate.hip.h"

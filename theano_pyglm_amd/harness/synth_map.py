@@ -34,6 +34,9 @@ outside the draws' [min, max] (inference/predictive.py: rate_bands over windows 
 --diag (with --hmc N or --nuts N, N >= 8) prints the convergence diagnostics of those draws per neuron: the worst rank-normalised
 R-hat, the smallest bulk and tail ESS, and the number of parameters with rhat > 1.01 or ess_bulk < 100 per chain
 (inference/diagnostics.py: k_diag_column on the draws where the sampler keeps them).
+--filters [LEVEL] (with --hmc N or --nuts N) prints the posterior bands of the impulse responses of those draws per neuron: the
+presynaptic neurons whose simultaneous credible band excludes zero, the largest |effective weight| / sd and, against a true
+model, the true / false positives (inference/filters.py: k_filter_bands on the draws where the sampler keeps them).
 --coupling-test [ALPHA] prints, after the fit, the number of couplings that the per-pair Wald tests find at the false discovery
 rate ALPHA (default 0.05; inference/connectivity.py) and, where the data carry the true model, the true- and false-positive
 rates against the true adjacency and the area under the ROC of the statistic; --coupling-lr adds the median and maximum of
@@ -68,7 +71,7 @@ def initialize_test_harness(model_name, data, data_dir=None):
 
 def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False, gof=False, ppc=0, hmc=0, ais=0,
                    hmc_mass='laplace', prox=False, laplace_device=False, ais_mass='laplace', nuts=0, smc=0, newton=False, waic=False, loo=False, diag=False, rates=0,
-                   gof_correct=False, gof_draws=False, gof_lags=0, coupling_test=None, coupling_lr=False):
+                   gof_correct=False, gof_draws=False, gof_lags=0, coupling_test=None, coupling_lr=False, filters=None):
     """test/synth_map.py:10-32."""
     popn, popn_true, x_true = initialize_test_harness(model_name, data, data_dir)
     x0 = popn.sample(rng)
@@ -95,14 +98,24 @@ def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, r
         from theano_pyglm_amd.inference import predictive
         print(predictive.format_table(predictive.predictive_counts(popn, x_inf, ppc)))
     if hmc:
-        print(hmc_bias_table(popn, x_inf, hmc, hmc_mass, laplace_device, waic=waic, loo=loo, diag=diag, rates=rates, gof_draws=gof_draws, gof_lags=gof_lags))
+        print(hmc_bias_table(popn, x_inf, hmc, hmc_mass, laplace_device, waic=waic, loo=loo, diag=diag, rates=rates, gof_draws=gof_draws, gof_lags=gof_lags,
+                             filters=filters, truth=true_adjacency(popn_true, x_true)))
     if nuts:
-        print(nuts_bias_table(popn, x_inf, nuts, hmc_mass, laplace_device, waic=waic, loo=loo, diag=diag, rates=rates, gof_draws=gof_draws, gof_lags=gof_lags))
+        print(nuts_bias_table(popn, x_inf, nuts, hmc_mass, laplace_device, waic=waic, loo=loo, diag=diag, rates=rates, gof_draws=gof_draws, gof_lags=gof_lags,
+                              filters=filters, truth=true_adjacency(popn_true, x_true)))
     if ais:
         print(ais_evidence_table(popn, x_inf, ais, laplace_device, ais_mass))
     if smc:
         print(smc_evidence_table(popn, x_inf, smc, laplace_device, ais_mass))
     return x_inf, ll_inf, wall
+
+
+def true_adjacency(popn_true, x_true):
+    """truth[post, pre] of the true model, or None without one: a coupling is there where W_eff[pre, post] is not zero"""
+    import numpy as np
+    if popn_true is None or x_true is None:
+        return None
+    return (np.asarray(popn_true.W_eff(x_true)) != 0.0).T
 
 
 def coupling_table(popn, x, alpha=0.05, one_step_lr=False, popn_true=None, x_true=None):
@@ -133,16 +146,18 @@ def prox_table(popn, x):
 
 
 def hmc_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=False, loo=False, diag=False, rates=0,
-                   gof_draws=False, gof_lags=0):
+                   gof_draws=False, gof_lags=0, filters=None, truth=None):
     """n_draws kept HMC draws from x with the mass matrix `mass` ('laplace' or 'laplace_dense'): one line per neuron, bias
     posterior mean +- sd (and the Laplace standard error).  laplace_device: the Laplace factorisations (the dense mass
     matrix and the standard errors) run on the device.  waic / loo: the WAIC / PSIS-LOO table of the draws follows (waic_table, loo_table); diag: the convergence table
-    (diagnostics.worst_table of the sampler's 'summary')."""
+    (diagnostics.worst_table of the sampler's 'summary'); filters: a level -- the table of the posterior bands of the impulse
+    responses follows (filters.band_table of the sampler's 'filters', against truth[post, pre] where given)."""
     from theano_pyglm_amd.inference import batched_hmc
     from theano_pyglm_amd.inference.laplace import laplace_glms
     t0 = time.time()
     res = batched_hmc.sample_glms_hmc(popn, x, n_draws, mass=mass,
-                                      factor_on_device=laplace_device and mass == 'laplace_dense', diagnostics=diag)
+                                      factor_on_device=laplace_device and mass == 'laplace_dense', diagnostics=diag,
+                                      filters=filters if filters is not None else False)
     wall = time.time() - t0
     s = batched_hmc.summarize(res['samples'][:, :, 0])
     try:
@@ -167,21 +182,25 @@ def hmc_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=
     if diag:
         from theano_pyglm_amd.inference.diagnostics import worst_table
         lines.append(worst_table(res['summary'], res['samples'].shape[0] if res['samples'].ndim == 4 else 1))
+    if filters is not None:
+        from theano_pyglm_amd.inference.filters import band_table
+        lines.append(band_table(res['filters'], truth=truth))
     return "\n".join(lines)
 
 
 def nuts_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic=False, loo=False, diag=False, rates=0,
-                    gof_draws=False, gof_lags=0, **kw):
+                    gof_draws=False, gof_lags=0, filters=None, truth=None, **kw):
     """hmc_bias_table with the No-U-Turn sampler: the same columns ('accept' is the mean acceptance statistic after
     warm-up) plus the median tree depth of the kept transitions and the divergent transitions after warm-up.  kw: further
     arguments of sample_glms_nuts (n_warmup, max_depth, ...).  waic / loo: the WAIC / PSIS-LOO table of the draws follows (waic_table, loo_table); diag: the convergence table
-    (diagnostics.worst_table of the sampler's 'summary')."""
+    (diagnostics.worst_table of the sampler's 'summary'); filters, truth: as hmc_bias_table."""
     import numpy as np
     from theano_pyglm_amd.inference import batched_nuts
     from theano_pyglm_amd.inference.laplace import laplace_glms
     t0 = time.time()
     res = batched_nuts.sample_glms_nuts(popn, x, n_draws, mass=mass,
-                                        factor_on_device=laplace_device and mass == 'laplace_dense', diagnostics=diag, **kw)
+                                        factor_on_device=laplace_device and mass == 'laplace_dense', diagnostics=diag,
+                                        filters=filters if filters is not None else False, **kw)
     wall = time.time() - t0
     s = batched_nuts.summarize(res['samples'][:, :, 0])
     try:
@@ -209,6 +228,9 @@ def nuts_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic
     if diag:
         from theano_pyglm_amd.inference.diagnostics import worst_table
         lines.append(worst_table(res['summary'], res['samples'].shape[0] if res['samples'].ndim == 4 else 1))
+    if filters is not None:
+        from theano_pyglm_amd.inference.filters import band_table
+        lines.append(band_table(res['filters'], truth=truth))
     return "\n".join(lines)
 
 
@@ -357,6 +379,11 @@ def parser():
     ap.add_argument('--coupling-test', type=float, nargs='?', const=0.05, default=None, metavar='ALPHA',
                     help='after the fit: per-pair Wald tests of the couplings with Benjamini-Hochberg control at ALPHA (default '
                          '0.05); with the true model in the data, true- and false-positive rates and the area under the ROC')
+    ap.add_argument('--filters', type=float, nargs='?', const=0.95, default=None, metavar='LEVEL',
+                    help='with --hmc N or --nuts N: the posterior bands of the impulse responses from those draws on the device '
+                         '(inference/filters.py): per neuron the presynaptic neurons whose simultaneous band at LEVEL (default '
+                         '0.95) excludes zero, the largest |effective weight| / sd, and against a true model the true / false '
+                         'positives')
     ap.add_argument('--coupling-lr', action='store_true',
                     help='with --coupling-test: the one-step likelihood ratio beside the Wald statistic, median and maximum of '
                          '|lr1 - T| / max(T, 1)')
@@ -372,7 +399,7 @@ def main(argv=None):
                    hmc_mass=args.hmc_mass, prox=args.prox, laplace_device=args.laplace_device, ais_mass=args.ais_mass, nuts=args.nuts, smc=args.smc,
                    newton=args.newton, waic=args.waic, loo=args.loo, diag=args.diag, rates=args.rates,
                    gof_correct=args.gof_correct, gof_draws=args.gof_draws, gof_lags=args.gof_lags,
-                   coupling_test=args.coupling_test, coupling_lr=args.coupling_lr)
+                   coupling_test=args.coupling_test, coupling_lr=args.coupling_lr, filters=args.filters)
 
 
 if __name__ == '__main__':

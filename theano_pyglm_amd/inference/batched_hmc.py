@@ -224,7 +224,8 @@ def split_chains(a, M, n_chains, axis):
 
 
 def sample_glms_hmc(population, x, n_samples, n_warmup=200, n_leapfrog=10, step_sz=0.1, thin=1, mass=None, seed=0,
-                    n_lo=0, n_hi=None, mass_floor=1e-8, factor_on_device=False, n_chains=1, init_jitter=0.0, diagnostics=False):
+                    n_lo=0, n_hi=None, mass_floor=1e-8, factor_on_device=False, n_chains=1, init_jitter=0.0, diagnostics=False,
+                    filters=False):
     """Posterior samples of the parameter rows of neurons [n_lo, n_hi) given the rest of x, started at x.
 
     n_warmup transitions adapt every row's step size and are dropped; then n_samples * thin transitions, every thin-th
@@ -252,6 +253,8 @@ def sample_glms_hmc(population, x, n_samples, n_warmup=200, n_leapfrog=10, step_
     diagnostics=True (n_samples >= 8): the result gains 'summary', the convergence diagnostics of every parameter -- arrays
     (M, P) under the keys of diagnostics.chain_diagnostics plus 'route' -- computed by k_diag_column on the device tensor of
     the draws before it is copied (inference/diagnostics.py); the draws themselves are the same bits either way.
+    filters=True (or a level in (0, 1); True: 0.95): the result gains 'filters', the posterior bands of the impulse responses
+    and stimulus filters (inference/filters.py: filter_bands' dict), queued the same way (k_filter_bands).
     population.last_fit_stats records the launch counts, the host synchronisations inside the chain, 'mass' ('identity',
     'diagonal', 'adapted diagonal' or 'dense') and 'mass_setup_s' (the Hessian and the host factorisation; 0 for 'adapt')."""
     _check(population)
@@ -266,7 +269,7 @@ def sample_glms_hmc(population, x, n_samples, n_warmup=200, n_leapfrog=10, step_
     minv, factor, dense_rows, setup_s = resolve_mass(population, x, mass, n_lo, n_hi, mass_floor, factor_on_device)
     with session(population) as (torch, dev, stream, handles):
         out = _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, n_leapfrog, step_sz, thin, minv,
-                     int(seed), n_lo, n_hi, M, factor, n_chains, init_jitter, bool(diagnostics))
+                     int(seed), n_lo, n_hi, M, factor, n_chains, init_jitter, bool(diagnostics), filters)
     if dense_rows is not None:
         out['dense_rows'] = dense_rows
     population.last_fit_stats['mass_setup_s'] = setup_s
@@ -274,7 +277,7 @@ def sample_glms_hmc(population, x, n_samples, n_warmup=200, n_leapfrog=10, step_
 
 
 def _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, n_leapfrog, step_sz, thin, mass, seed, n_lo, n_hi,
-           M, factor=None, n_chains=1, init_jitter=0.0, diagnostics=False):
+           M, factor=None, n_chains=1, init_jitter=0.0, diagnostics=False, filters=False):
     from theano_pyglm_amd.inference.mass_adapt import adapt_windows, schedule_ints
     pk = _Packing(population, torch, handles, (n_lo, n_hi))
     assert pk.identity                                        # (hvp_packing() is None: the row IS the theta row)
@@ -350,6 +353,9 @@ def _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, n_le
     if diagnostics:                                           # on the draws where they lie, behind the last transition
         from theano_pyglm_amd.inference.diagnostics import queue_summary, finish_summary
         diag_rows = queue_summary(h0, samples, C)
+    if filters:
+        from theano_pyglm_amd.inference.filters import queue_bands, finish_bands, filters_level
+        bands = queue_bands(population, h0, torch, samples, C, filters_level(filters))
     wait()
     sch = sc.cpu().numpy()
     out = {'samples': split_chains(samples.cpu().numpy(), M, C, 1),
@@ -360,6 +366,8 @@ def _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, n_le
         out['adapt_windows'] = windows
     if diagnostics:
         out['summary'] = finish_summary(diag_rows, out['samples'], C)
+    if filters:
+        out['filters'] = finish_bands(population, bands, samples, C, filters_level(filters))
     # ('row' counts the begin / leap CALLS of the C ABI; a dense call is three small launches, a diagonal one is one)
     population.last_fit_stats = {'sampler': 'lock-step HMC (hip row kernels)', 'transitions': n_total,
                                  'mass': 'dense' if Wd is not None else ('adapted diagonal' if adapt else

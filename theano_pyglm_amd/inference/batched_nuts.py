@@ -34,7 +34,8 @@ POLL = 8                                                      # launches between
 
 
 def sample_glms_nuts(population, x, n_samples, n_warmup=200, max_depth=8, step_sz=0.1, target_accept=0.8, thin=1, mass=None,
-                     seed=0, n_lo=0, n_hi=None, factor_on_device=False, mass_floor=1e-8, n_chains=1, init_jitter=0.0, diagnostics=False):
+                     seed=0, n_lo=0, n_hi=None, factor_on_device=False, mass_floor=1e-8, n_chains=1, init_jitter=0.0, diagnostics=False,
+                     filters=False):
     """Posterior samples of the parameter rows of neurons [n_lo, n_hi) given the rest of x, started at x.
 
     n_warmup transitions adapt every row's step size (dual averaging towards target_accept) and are dropped; then
@@ -49,7 +50,8 @@ def sample_glms_nuts(population, x, n_samples, n_warmup=200, max_depth=8, step_s
     (= 'step_sz'), 'launches' (evaluation + step launches: the largest number of leapfrog steps of any row, plus fewer
     than 2 POLL because the done flags are read every POLL launches and one window late) and 'idle_row_evaluations' (the
     sum over rows of launches - the row's leapfrog steps).  x is not changed.
-    diagnostics=True: as sample_glms_hmc -- 'summary', from k_diag_column on the device tensor of the draws."""
+    diagnostics=True: as sample_glms_hmc -- 'summary', from k_diag_column on the device tensor of the draws.
+    filters=True (or a level): as sample_glms_hmc -- 'filters', from k_filter_bands on the same tensor."""
     _check(population)
     n_samples, n_warmup, max_depth, thin = int(n_samples), int(n_warmup), int(max_depth), int(thin)
     if n_samples <= 0 or n_warmup < 0 or thin <= 0:
@@ -70,7 +72,7 @@ def sample_glms_nuts(population, x, n_samples, n_warmup=200, max_depth=8, step_s
     with session(population) as (torch, dev, stream, handles):
         out = _chain(population, torch, dev, stream, handles, x, n_samples, n_warmup, max_depth, step_sz,
                      float(target_accept), thin, mass, int(seed), n_lo, n_hi, M, factor, n_chains, init_jitter,
-                     bool(diagnostics))
+                     bool(diagnostics), filters)
     if dense_rows is not None:
         out['dense_rows'] = dense_rows
     population.last_fit_stats['mass_setup_s'] = setup_s
@@ -78,7 +80,7 @@ def sample_glms_nuts(population, x, n_samples, n_warmup=200, max_depth=8, step_s
 
 
 def _chain(population, torch, dev, stream, handles, x, n_keep, n_warmup, D, step_sz, delta, thin, mass, seed, n_lo, n_hi, M,
-           factor, n_chains=1, init_jitter=0.0, diagnostics=False):
+           factor, n_chains=1, init_jitter=0.0, diagnostics=False, filters=False):
     from theano_pyglm_amd.inference.mass_adapt import adapt_windows, schedule_ints
     pk = _Packing(population, torch, handles, (n_lo, n_hi))
     assert pk.identity                                        # (hvp_packing() is None: the row IS the theta row)
@@ -145,6 +147,9 @@ def _chain(population, torch, dev, stream, handles, x, n_keep, n_warmup, D, step
     if diagnostics:                                           # (every row is done: the draws are complete on the device)
         from theano_pyglm_amd.inference.diagnostics import queue_summary, finish_summary
         diag_rows = queue_summary(h0, samples, C)
+    if filters:
+        from theano_pyglm_amd.inference.filters import queue_bands, finish_bands, filters_level
+        bands = queue_bands(population, h0, torch, samples, C, filters_level(filters))
     stream.synchronize()
     sch = sc.cpu().numpy()
     sth = stats.cpu().numpy()
@@ -161,6 +166,8 @@ def _chain(population, torch, dev, stream, handles, x, n_keep, n_warmup, D, step
         out['adapt_windows'] = windows
     if diagnostics:
         out['summary'] = finish_summary(diag_rows, out['samples'], C)
+    if filters:
+        out['filters'] = finish_bands(population, bands, samples, C, filters_level(filters))
     assert np.all(sch[SC_DONE] != 0.0) and np.all(sch[SC_T] == n_warmup + n_keep * thin)
     population.last_fit_stats = {'sampler': 'NUTS (hip row kernels)', 'transitions': n_warmup + n_keep * thin,
                                  'mass': 'dense' if Wd is not None else ('adapted diagonal' if adapt else
