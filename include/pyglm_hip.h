@@ -98,7 +98,7 @@ typedef struct pgl_context* pgl_handle;
 
 /* What pgl_version() returns: it changes with every change of a signature or a struct below, and a binding refuses a
  * library that reports another number (theano_pyglm_amd/_lib.py: ABI_VERSION). */
-#define PGL_ABI_VERSION 117
+#define PGL_ABI_VERSION 118
 
 const char* pgl_last_error(void);
 int pgl_version(void);
@@ -1214,6 +1214,57 @@ int pgl_simulate_batch_dev(int device, int N, int64_t nT, int R, int nlin, doubl
                            const double* d_AW, int n_rep, int rep0, uint64_t seed, int flags, uint8_t* d_S, double* d_X,
                            int64_t* d_counts, int64_t* d_exceptions, double* d_workspace, void* stream);
 int pgl_simulate_batch_plan(int N, int R, int flags, int* ring_in_lds, long long* workspace_bytes_per_rep);
+
+/* Clamped simulation: every neuron simulated with only its OWN spikes fed back, the other neurons held at their recorded
+ * spikes -- the single-neuron prediction given the population activity (Pillow et al. 2008).  The rules are plain C in
+ * csrc/pglm_condsim.h.
+ *
+ * Clamped currents.  Xc[t, q] = X0[t, q], then the recorded spikes of the other neurons in a fixed order: bins
+ * s = max(0, t - R) .. t - 1 ascending, inside a bin the presynaptic neurons p != q ascending, AW[p, t - s - 1, q] added once per
+ * spike of the recorded count (repeated addition, no multiply).  X0 (nT, N) and AW (N, R, N) [n_pre][tau][n_post] as for
+ * pgl_simulate_batch.  The recorded spikes come as event lists sorted by (bin, pre): ev_pre (E) int32, ev_cnt (E) uint8 >= 1,
+ * bin_off (nT + 1) int64 (bin s owns events bin_off[s] .. bin_off[s + 1] - 1; E = bin_off[nT], E = 0 allowed).
+ *
+ * One chain (replicate r, neuron n): pgl_simulate_streams' loop for a neuron that is alone, on the threshold stream
+ * thr(seed, r, n, k) above.  Per bin: x = Xc[t, n] + AW[n, t - s - 1, n] for every own scattered spike at a bin s in
+ * t - R .. t - 1, ascending s, once per spike; acc += nlin(x) * dt; rounds while acc > thr: S[t, n] += 1; a round that starts with
+ * S[t, n] >= 10 is dropped and counted as an exception OF THAT NEURON (the cap is the neuron's own, as if it were alone: in
+ * pgl_simulate_streams any neuron at 10 drops the round of all; the tenth spike is recorded and not scattered, as there);
+ * otherwise the spike is scattered, acc -= thr (clamped at 0), a new threshold is drawn.  Whenever pgl_simulate_streams(N,
+ * X = Xc, AW with only its [n, :, n] entries kept, rep = r, seed) reports 0 exceptions, its column n is this chain spike for
+ * spike.
+ *
+ * Accumulators.  Windows of win bins from bin 0 (the last may be short), n_win = ceil(nT / win); acc (6, n_win, N) int64 over
+ * the replicates: sum c, sum c^2, #(c < obs), #(c = obs), min c, max c, with c the replicate's count of the window and
+ * obs (n_win, N) int64 the recorded one.  accumulate = 0 initialises acc, exceptions and fallbacks; accumulate != 0 continues
+ * them: a call over rep0 .. rep0 + n_rep - 1 followed by a continuing call over the next range equals one call over both.
+ * Integer atomics (the result does not depend on the order); no f64 atomics.
+ *
+ * cond_currents[_dev]: Xc (nT, N) out.  simulate_cond[_dev]: exceptions (N) int64 summed over the replicates; counts
+ *     (n_rep, N) int64, S (n_rep, nT, N) uint8 (tests) and fallbacks (1) int64 may be NULL.  A chain keeps its own spike bins
+ *     of the last R bins in a queue of 32 entries; a chain with more moves to a ring of R doubles in the workspace for the
+ *     rest of its bins (fallbacks counts those chains) -- the result does not depend on the queue; flags bit 0 starts every
+ *     chain on the ring.  d_workspace: pgl_simulate_cond_workspace(N, R, n_rep) = N R n_rep 8 bytes, required.  The _dev forms
+ *     take device pointers and are asynchronous on `stream`.  N <= 1024; R <= 4096 (more: PGL_ERR_UNSUPPORTED); bad arguments:
+ *     PGL_ERR_ARG.  The host-pointer form of the currents checks the event lists.
+ *     N ceil(n_rep / 64) workgroups must not exceed 2^31 - 1 (PGL_ERR_ARG).
+ * simulate_cond_streams: host reference of one replicate (no GPU needed), S (nT, N) uint8, exceptions_out (N), closest_call_out
+ *     as pgl_simulate_streams (both may be NULL).  It serves the shapes the device entries serve and refuses the same ones
+ *     (dt > 0, N <= 1024, R <= 4096). */
+int pgl_simulate_cond_streams(int N, int64_t nT, int R, int nlin, double dt, const double* Xc, const double* AW, int rep,
+                              uint64_t seed, uint8_t* S, int64_t* exceptions_out, double* closest_call_out);
+int pgl_cond_currents_dev(int device, int N, int64_t nT, int R, const double* d_X0, const double* d_AW, const int32_t* d_ev_pre,
+                          const uint8_t* d_ev_cnt, const int64_t* d_bin_off, double* d_Xc, void* stream);
+int pgl_cond_currents(int device, int N, int64_t nT, int R, const double* X0, const double* AW, const int32_t* ev_pre,
+                      const uint8_t* ev_cnt, const int64_t* bin_off, double* Xc_out);
+long long pgl_simulate_cond_workspace(int N, int R, int n_rep);
+int pgl_simulate_cond_dev(int device, int N, int64_t nT, int R, int nlin, double dt, const double* d_Xc, const double* d_AW,
+                          const int64_t* d_obs, int64_t win, int n_rep, int rep0, uint64_t seed, int flags, int accumulate,
+                          int64_t* d_acc, int64_t* d_exceptions, int64_t* d_counts, uint8_t* d_S, int64_t* d_fallbacks,
+                          double* d_workspace, void* stream);
+int pgl_simulate_cond(int device, int N, int64_t nT, int R, int nlin, double dt, const double* Xc, const double* AW,
+                      const int64_t* obs, int64_t win, int n_rep, int rep0, uint64_t seed, int flags, int accumulate,
+                      int64_t* acc, int64_t* exceptions, int64_t* counts_out, uint8_t* S_out, int64_t* fallbacks);
 
 /* Timing of the most recent pgl_ll_grad[_dev] call, measured with HIP events on the
  * handle's stream: ms of the fused kernel alone and of the whole call (prep +

@@ -61,10 +61,12 @@ SYMBOLS = [
     'pgl_chain_diag_dev', 'pgl_chain_diag',
     'pgl_filter_bands_dev', 'pgl_filter_bands',
     'pgl_simulate_streams', 'pgl_simulate_batch', 'pgl_simulate_batch_dev', 'pgl_simulate_batch_plan',
+    'pgl_simulate_cond_streams', 'pgl_cond_currents_dev', 'pgl_cond_currents', 'pgl_simulate_cond_workspace',
+    'pgl_simulate_cond_dev', 'pgl_simulate_cond',
 ]
 
 
-ABI_VERSION = 117                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
+ABI_VERSION = 118                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
 
 GEMM_NT, GEMM_MFMA_1, GEMM_MFMA_4, GEMM_KC_4_1_8, GEMM_KC_1_0_16 = range(5)   # PGL_GEMM_*: the kernel of pgl_gemm_dev
 
@@ -87,6 +89,10 @@ DIAG_NOUT = len(DIAG_ROWS)          # PGL_DIAG_NOUT
 FILT_MAX_B = 16                     # PGL_FILT_MAX_B: the largest group of weights filter_bands serves
 FILT_MAX_DRAWS = 4096               # PGL_FILT_MAX_DRAWS: the pooled draws filter_bands' workgroup sorts in LDS
 FILT_LAG_COLS = ('mean', 'sd', 'q_lo', 'median', 'q_hi')            # the PGL_FILT_NLAG figures per lag (csrc/pglm_filters.h)
+CS_NACC = 6                         # PGL_CS_NACC: planes of the clamped simulation's accumulator (csrc/pglm_condsim.h)
+CS_PLANES = ('sum', 'sum_sq', 'n_less', 'n_equal', 'min', 'max')
+CS_QUEUE = 32                       # PGL_CS_QUEUE: own spike bins a chain of k_simulate_cond keeps before it moves to a ring
+CS_MAX_R = 4096                     # PGL_CS_MAX_R: taps of self-history simulate_cond serves; more: PGL_ERR_UNSUPPORTED
 FILT_GRP_COLS = ('c_sim', 'weight_mean', 'weight_sd', 'weight_q_lo', 'weight_median', 'weight_q_hi', 'p_pos', 'info')   # PGL_FILT_NGRP
 
 
@@ -322,10 +328,20 @@ def load():
     lib.pgl_simulate_batch.argtypes = sim
     lib.pgl_simulate_batch_dev.argtypes = sim + [vp, vp]
     lib.pgl_simulate_batch_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
+    lib.pgl_simulate_cond_streams.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_double, vp, vp, C.c_int, C.c_uint64,
+                                              vp, vp, vp]
+    lib.pgl_cond_currents_dev.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    lib.pgl_cond_currents.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int, vp, vp, vp, vp, vp, vp]
+    lib.pgl_simulate_cond_workspace.argtypes = [C.c_int, C.c_int, C.c_int]
+    cond = [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_double, vp, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_uint64,
+            C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    lib.pgl_simulate_cond.argtypes = cond
+    lib.pgl_simulate_cond_dev.argtypes = cond + [vp, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name in ('pgl_bfgs_state_doubles', 'pgl_ncg_state_doubles', 'pgl_newton_state_doubles', 'pgl_hmc_state_doubles',
-                    'pgl_ais_state_doubles', 'pgl_prox_state_doubles', 'pgl_nuts_state_doubles', 'pgl_adapt_state_doubles', 'pgl_smc_state_doubles'):
+                    'pgl_ais_state_doubles', 'pgl_prox_state_doubles', 'pgl_nuts_state_doubles', 'pgl_adapt_state_doubles', 'pgl_smc_state_doubles',
+                    'pgl_simulate_cond_workspace'):
             fn.restype = C.c_longlong
         elif name not in ('pgl_last_error',):
             fn.restype = C.c_int
@@ -465,6 +481,99 @@ def simulate_batch_dev(N, nT, R, nlin, dt, d_X0, d_AW, n_rep, d_counts, d_except
     _chk(load().pgl_simulate_batch_dev(int(device), int(N), int(nT), int(R), kind, float(dt), _dp(d_X0), _dp(d_AW),
                                        int(n_rep), int(rep0), int(seed), int(flags), _dp(d_S), _dp(d_X), _dp(d_counts),
                                        _dp(d_exceptions), _dp(d_workspace), _dp(stream)))
+
+
+def spike_events(S):
+    """The event lists of recorded spikes S (nT, N) as the clamped simulation takes them: (ev_pre (E) int32, ev_cnt (E) uint8,
+    bin_off (nT + 1) int64), sorted by (bin, pre).  Counts above 255 in a bin are refused."""
+    S = np.asarray(S)
+    if S.ndim != 2 or np.any(S < 0) or np.any(S > 255) or np.any(S != np.floor(S)):
+        raise ValueError("S must be (nT, N) integer counts in 0 .. 255")
+    t, pre = np.nonzero(S)                                    # row-major: sorted by (bin, pre)
+    bin_off = np.zeros(S.shape[0] + 1, dtype=np.int64)
+    np.cumsum(np.bincount(t, minlength=S.shape[0]), out=bin_off[1:])
+    return pre.astype(np.int32), S[t, pre].astype(np.uint8), bin_off
+
+
+def window_counts(S, win):
+    """(n_win, N) int64 counts of S (nT, N) over windows of `win` bins from bin 0 (the last one may be short)."""
+    S = np.asarray(S)
+    return np.add.reduceat(S.astype(np.int64), np.arange(0, S.shape[0], int(win)), axis=0)
+
+
+def simulate_cond_streams(Xc, AW, nlin, dt, rep=0, seed=0):
+    """Host reference of one replicate of the clamped simulation (pgl_simulate_cond_streams; needs no GPU).  Xc (nT, N) clamped
+    currents, AW (N, R, N) of which only [n, :, n] is read.  Returns (S uint8 (nT, N), exceptions (N) int64, closest_call)."""
+    lib = load()
+    Xc, AW, kind = _sim_args(Xc, AW, nlin)
+    nT, N = Xc.shape
+    S = np.empty((nT, N), dtype=np.uint8)
+    exc = np.zeros(N, dtype=np.int64)
+    closest = C.c_double(0.0)
+    _chk(lib.pgl_simulate_cond_streams(N, nT, AW.shape[1], kind, float(dt), _ptr(Xc), _ptr(AW), int(rep), int(seed), _ptr(S),
+                                       _ptr(exc), C.byref(closest)))
+    return S, exc, float(closest.value)
+
+
+def cond_currents(X0, AW, ev_pre, ev_cnt, bin_off, device=0):
+    """Xc (nT, N) on the device from host arrays (pgl_cond_currents); the events as spike_events gives them."""
+    X0, AW, _ = _sim_args(X0, AW, 0)
+    nT, N = X0.shape
+    ev_pre = np.ascontiguousarray(ev_pre, dtype=np.int32)
+    ev_cnt = np.ascontiguousarray(ev_cnt, dtype=np.uint8)
+    bin_off = np.ascontiguousarray(bin_off, dtype=np.int64)
+    if bin_off.shape != (nT + 1,) or ev_pre.shape != ev_cnt.shape or ev_pre.ndim != 1 or ev_pre.size != bin_off[-1]:
+        raise ValueError("bin_off must be (nT + 1) and ev_pre / ev_cnt (bin_off[nT])")
+    Xc = np.empty((nT, N))
+    _chk(load().pgl_cond_currents(int(device), N, nT, AW.shape[1], _ptr(X0), _ptr(AW), _ptr(ev_pre), _ptr(ev_cnt),
+                                  _ptr(bin_off), _ptr(Xc)))
+    return Xc
+
+
+def cond_currents_dev(N, nT, R, d_X0, d_AW, d_ev_pre, d_ev_cnt, d_bin_off, d_Xc, stream=0, device=0):
+    _chk(load().pgl_cond_currents_dev(int(device), int(N), int(nT), int(R), _dp(d_X0), _dp(d_AW), _dp(d_ev_pre), _dp(d_ev_cnt),
+                                      _dp(d_bin_off), _dp(d_Xc), _dp(stream)))
+
+
+def simulate_cond_workspace(N, R, n_rep):
+    """bytes of d_workspace of simulate_cond_dev: the fallback rings, N R n_rep doubles"""
+    return int(load().pgl_simulate_cond_workspace(int(N), int(R), int(n_rep)))
+
+
+def simulate_cond(Xc, AW, nlin, dt, obs, win, n_rep, seed=0, rep0=0, flags=0, acc=None, exceptions=None, fallbacks=None,
+                  counts=False, spikes=False, device=0):
+    """n_rep clamped replicates on the device from host arrays (pgl_simulate_cond), stream indices rep0 .. rep0 + n_rep - 1.
+    obs (n_win, N) recorded window counts.  acc / exceptions / fallbacks of an earlier call continue it (all three, or none).
+    Returns a dict: acc (6, n_win, N) int64, exceptions (N), fallbacks (int), counts (n_rep, N) or None, S (n_rep, nT, N) uint8
+    or None."""
+    Xc, AW, kind = _sim_args(Xc, AW, nlin)
+    nT, N = Xc.shape
+    n_rep, win = int(n_rep), int(win)
+    n_win = -(-nT // win) if win > 0 else 0
+    obs = np.ascontiguousarray(obs, dtype=np.int64)
+    if obs.shape != (n_win, N):
+        raise ValueError("obs must be (n_win, N) = %s" % ((n_win, N),))
+    cont = acc is not None
+    acc = np.array(acc, dtype=np.int64, order='C') if cont else np.empty((CS_NACC, n_win, N), dtype=np.int64)
+    if acc.shape != (CS_NACC, n_win, N):
+        raise ValueError("acc must be (6, n_win, N)")
+    exc = np.array(exceptions, dtype=np.int64, order='C') if cont else np.empty(N, dtype=np.int64)
+    fb = np.array([fallbacks if cont else 0], dtype=np.int64)
+    cnt = np.empty((max(n_rep, 0), N), dtype=np.int64) if counts else None
+    S = np.empty((max(n_rep, 0), nT, N), dtype=np.uint8) if spikes else None
+    _chk(load().pgl_simulate_cond(int(device), N, nT, AW.shape[1], kind, float(dt), _ptr(Xc), _ptr(AW), _ptr(obs), win, n_rep,
+                                  int(rep0), int(seed), int(flags), int(cont), _ptr(acc), _ptr(exc), _ptr(cnt), _ptr(S), _ptr(fb)))
+    return {'acc': acc, 'exceptions': exc, 'fallbacks': int(fb[0]), 'counts': cnt, 'S': S}
+
+
+def simulate_cond_dev(N, nT, R, nlin, dt, d_Xc, d_AW, d_obs, win, n_rep, d_acc, d_exceptions, d_workspace, seed=0, rep0=0,
+                      flags=0, accumulate=False, d_counts=0, d_S=0, d_fallbacks=0, stream=0, device=0):
+    """Device-pointer form (pgl_simulate_cond_dev; asynchronous on `stream`, 0 = the null stream)."""
+    kind = int({'exp': NLIN_EXP, 'explinear': NLIN_EXPLINEAR}.get(nlin, nlin))
+    _chk(load().pgl_simulate_cond_dev(int(device), int(N), int(nT), int(R), kind, float(dt), _dp(d_Xc), _dp(d_AW), _dp(d_obs),
+                                      int(win), int(n_rep), int(rep0), int(seed), int(flags), int(bool(accumulate)), _dp(d_acc),
+                                      _dp(d_exceptions), _dp(d_counts), _dp(d_S), _dp(d_fallbacks), _dp(d_workspace),
+                                      _dp(stream)))
 
 
 class DeviceGlm(object):

@@ -2726,6 +2726,193 @@ int pgl_simulate_batch(int device, int N, int64_t nT, int R, int nlin, double dt
     return done(PGL_OK);
 }
 
+// ---- clamped simulation: every neuron given the others' recorded spikes (pglm_condsim.h, pglm_condsim.hip.h) ----
+static int cond_sim_check(int N, int64_t nT, int R, int nlin, double dt, int64_t win, int n_rep, int rep0);
+
+// Host reference of one replicate: the chain rule of the header, neuron by neuron.
+int pgl_simulate_cond_streams(int N, int64_t nT, int R, int nlin, double dt, const double* Xc, const double* AW, int rep,
+                              uint64_t seed, uint8_t* S, int64_t* exceptions_out, double* closest_call_out)
+{
+    // (the shapes the device entries serve, so that every call they accept has its reference and no other)
+    int rc = cond_sim_check(N, nT, R, nlin, dt, 1, 1, rep);
+    if (rc) return rc;
+    if (!Xc || !AW || !S) return fail(PGL_ERR_ARG, "null argument");
+    std::vector<double> x((size_t)nT), h((size_t)R);
+    double closest = __builtin_huge_val();
+    for (int n = 0; n < N; ++n) {
+        for (int64_t t = 0; t < nT; ++t) x[t] = Xc[(size_t)t * N + n];
+        for (int tau = 0; tau < R; ++tau) h[tau] = AW[((size_t)n * R + tau) * N + n];
+        const long long e = pgl_cs_chain(nT, R, nlin, dt, x.data(), h.data(), seed, (pgl_cs_u64)rep, (pgl_cs_u64)n, S + n, N,
+                                         &closest);
+        if (exceptions_out) exceptions_out[n] = e;
+    }
+    if (closest_call_out) *closest_call_out = closest;
+    return PGL_OK;
+}
+
+static int cond_check(int N, int64_t nT, int R)
+{
+    if (N <= 0 || nT <= 0 || R <= 0) return fail(PGL_ERR_ARG, "bad argument");
+    if (N > PGL_SIM_MAXN) return fail(PGL_ERR_ARG, "N > 1024 neurons");
+    if ((long long)R * N > (1 << 27)) return fail(PGL_ERR_ARG, "R * N too large");
+    return PGL_OK;
+}
+
+int pgl_cond_currents_dev(int device, int N, int64_t nT, int R, const double* d_X0, const double* d_AW, const int32_t* d_ev_pre,
+                          const uint8_t* d_ev_cnt, const int64_t* d_bin_off, double* d_Xc, void* stream)
+{
+    int rc = cond_check(N, nT, R);
+    if (rc) return rc;
+    if (!d_X0 || !d_AW || !d_bin_off || !d_Xc) return fail(PGL_ERR_ARG, "null argument");
+    rc = sim_device(device);
+    if (rc) return rc;
+    const long long n = (long long)nT * N;
+    const int blocks = (int)std::min<long long>((n + 255) / 256, 1 << 20);
+    hipLaunchKernelGGL(k_cond_currents, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_X0, d_AW, (const int*)d_ev_pre,
+                       (const unsigned char*)d_ev_cnt, (const long long*)d_bin_off, d_Xc, (long long)nT, N, R);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+// bin_off of a host caller: ascending from 0, every event of a neuron 0 .. N - 1 with a count >= 1, sorted by (bin, pre)
+static int cond_events_check(int N, int64_t nT, const int32_t* ev_pre, const uint8_t* ev_cnt, const int64_t* bin_off)
+{
+    if (!bin_off || bin_off[0] != 0) return fail(PGL_ERR_ARG, "bin_off must start at 0");
+    for (int64_t t = 0; t < nT; ++t) {
+        if (bin_off[t + 1] < bin_off[t]) return fail(PGL_ERR_ARG, "bin_off must ascend");
+        for (int64_t e = bin_off[t]; e < bin_off[t + 1]; ++e) {
+            if (!ev_pre || !ev_cnt || ev_pre[e] < 0 || ev_pre[e] >= N || ev_cnt[e] == 0 || (e > bin_off[t] && ev_pre[e] <= ev_pre[e - 1]))
+                return fail(PGL_ERR_ARG, "events must be sorted by (bin, pre) with pre in 0 .. N - 1 and counts >= 1");
+        }
+    }
+    return PGL_OK;
+}
+
+int pgl_cond_currents(int device, int N, int64_t nT, int R, const double* X0, const double* AW, const int32_t* ev_pre,
+                      const uint8_t* ev_cnt, const int64_t* bin_off, double* Xc_out)
+{
+    int rc = cond_check(N, nT, R);
+    if (rc) return rc;
+    if (!X0 || !AW || !bin_off || !Xc_out) return fail(PGL_ERR_ARG, "null argument");
+    rc = cond_events_check(N, nT, ev_pre, ev_cnt, bin_off);
+    if (rc) return rc;
+    rc = sim_device(device);
+    if (rc) return rc;
+    const size_t nx = (size_t)nT * N, naw = (size_t)N * R * N, E = (size_t)bin_off[nT];
+    DevBuf dX0, dAW, dP, dC, dO, dXc;
+    const auto done = [&](int r) {
+        release(dX0); release(dAW); release(dP); release(dC); release(dO); release(dXc);
+        return r;
+    };
+    if (ensure(dX0, nx * 8) || ensure(dAW, naw * 8) || ensure(dP, (E + 1) * 4) || ensure(dC, E + 1) ||
+        ensure(dO, (size_t)(nT + 1) * 8) || ensure(dXc, nx * 8))
+        return done(PGL_ERR_HIP);
+    if (hipMemcpy(dX0.p, X0, nx * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dAW.p, AW, naw * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        (E && hipMemcpy(dP.p, ev_pre, E * 4, hipMemcpyHostToDevice) != hipSuccess) ||
+        (E && hipMemcpy(dC.p, ev_cnt, E, hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemcpy(dO.p, bin_off, (size_t)(nT + 1) * 8, hipMemcpyHostToDevice) != hipSuccess)
+        return done(fail(PGL_ERR_HIP, "cond_currents: upload failed"));
+    rc = pgl_cond_currents_dev(device, N, nT, R, (const double*)dX0.p, (const double*)dAW.p, (const int32_t*)dP.p,
+                               (const uint8_t*)dC.p, (const int64_t*)dO.p, (double*)dXc.p, nullptr);
+    if (rc) return done(rc);
+    hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return done(fail(PGL_ERR_HIP, std::string("cond_currents: ") + hipGetErrorString(e)));
+    if (hipMemcpy(Xc_out, dXc.p, nx * 8, hipMemcpyDeviceToHost) != hipSuccess)
+        return done(fail(PGL_ERR_HIP, "cond_currents: download failed"));
+    return done(PGL_OK);
+}
+
+static int cond_sim_check(int N, int64_t nT, int R, int nlin, double dt, int64_t win, int n_rep, int rep0)
+{
+    int rc = sim_check(N, nT, R, nlin, dt, n_rep, rep0);
+    if (rc) return rc;
+    if (win <= 0) return fail(PGL_ERR_ARG, "win must be at least 1");
+    if ((long long)rep0 + n_rep > 0x7fffffffLL) return fail(PGL_ERR_ARG, "rep0 + n_rep too large");
+    // (one workgroup per (neuron, 64 replicates): the grid must fit its 32-bit dimension)
+    if ((long long)N * (((long long)n_rep + 63) / 64) > 0x7fffffffLL) return fail(PGL_ERR_ARG, "N * ceil(n_rep / 64) workgroups exceed 2^31 - 1");
+    if (R > PGL_CS_MAX_R) return fail(PGL_ERR_UNSUPPORTED, "R > 4096 taps of self-history");
+    return PGL_OK;
+}
+
+long long pgl_simulate_cond_workspace(int N, int R, int n_rep)
+{
+    if (N <= 0 || R <= 0 || n_rep <= 0) return 0;
+    return (long long)N * R * n_rep * 8;
+}
+
+int pgl_simulate_cond_dev(int device, int N, int64_t nT, int R, int nlin, double dt, const double* d_Xc, const double* d_AW,
+                          const int64_t* d_obs, int64_t win, int n_rep, int rep0, uint64_t seed, int flags, int accumulate,
+                          int64_t* d_acc, int64_t* d_exceptions, int64_t* d_counts, uint8_t* d_S, int64_t* d_fallbacks,
+                          double* d_workspace, void* stream)
+{
+    int rc = cond_sim_check(N, nT, R, nlin, dt, win, n_rep, rep0);
+    if (rc) return rc;
+    if (!d_Xc || !d_AW || !d_obs || !d_acc || !d_exceptions || !d_workspace) return fail(PGL_ERR_ARG, "null argument");
+    rc = sim_device(device);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    CondSimParams cp;
+    cp.Xc = d_Xc; cp.AW = d_AW; cp.obs = (const long long*)d_obs; cp.ring = d_workspace; cp.acc = (long long*)d_acc;
+    cp.exc = (long long*)d_exceptions; cp.counts = (long long*)d_counts; cp.S = d_S; cp.fallbacks = (long long*)d_fallbacks;
+    cp.nT = nT; cp.win = win; cp.n_win = pgl_cs_windows(nT, win); cp.N = N; cp.R = R; cp.n_rep = n_rep; cp.rep0 = rep0;
+    cp.flags = flags; cp.seed = seed; cp.dt = dt;
+    if (!accumulate) {
+        const long long plane = cp.n_win * N;
+        hipLaunchKernelGGL(k_cond_acc_init, dim3((unsigned)((std::max<long long>(plane, N) + 255) / 256)), dim3(256), 0, s,
+                           cp.acc, cp.exc, cp.fallbacks, plane, N);
+        HIPCHK(hipGetLastError());
+    }
+    const unsigned blocks = (unsigned)N * (unsigned)((n_rep + 63) / 64);
+    if (nlin == PGL_NLIN_EXPLINEAR)
+        hipLaunchKernelGGL(k_simulate_cond<1>, dim3(blocks), dim3(64), (size_t)R * 8, s, cp);
+    else
+        hipLaunchKernelGGL(k_simulate_cond<0>, dim3(blocks), dim3(64), (size_t)R * 8, s, cp);
+    HIPCHK(hipGetLastError());
+    return PGL_OK;
+}
+
+int pgl_simulate_cond(int device, int N, int64_t nT, int R, int nlin, double dt, const double* Xc, const double* AW,
+                      const int64_t* obs, int64_t win, int n_rep, int rep0, uint64_t seed, int flags, int accumulate,
+                      int64_t* acc, int64_t* exceptions, int64_t* counts_out, uint8_t* S_out, int64_t* fallbacks)
+{
+    int rc = cond_sim_check(N, nT, R, nlin, dt, win, n_rep, rep0);
+    if (rc) return rc;
+    if (!Xc || !AW || !obs || !acc || !exceptions) return fail(PGL_ERR_ARG, "null argument");
+    rc = sim_device(device);
+    if (rc) return rc;
+    const size_t nx = (size_t)nT * N, naw = (size_t)N * R * N, nw = (size_t)pgl_cs_windows(nT, win) * N, nout = (size_t)n_rep * nx;
+    DevBuf dXc, dAW, dO, dA, dE, dC, dS, dF, dW;
+    const auto done = [&](int r) {
+        release(dXc); release(dAW); release(dO); release(dA); release(dE); release(dC); release(dS); release(dF); release(dW);
+        return r;
+    };
+    if (ensure(dXc, nx * 8) || ensure(dAW, naw * 8) || ensure(dO, nw * 8) || ensure(dA, PGL_CS_NACC * nw * 8) ||
+        ensure(dE, (size_t)N * 8) || ensure(dF, 8) || ensure(dW, (size_t)pgl_simulate_cond_workspace(N, R, n_rep)) ||
+        (counts_out && ensure(dC, (size_t)n_rep * N * 8)) || (S_out && ensure(dS, nout)))
+        return done(PGL_ERR_HIP);
+    if (hipMemcpy(dXc.p, Xc, nx * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dAW.p, AW, naw * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dO.p, obs, nw * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        (accumulate && (hipMemcpy(dA.p, acc, PGL_CS_NACC * nw * 8, hipMemcpyHostToDevice) != hipSuccess ||
+                        hipMemcpy(dE.p, exceptions, (size_t)N * 8, hipMemcpyHostToDevice) != hipSuccess ||
+                        (fallbacks && hipMemcpy(dF.p, fallbacks, 8, hipMemcpyHostToDevice) != hipSuccess))))
+        return done(fail(PGL_ERR_HIP, "simulate_cond: upload failed"));
+    rc = pgl_simulate_cond_dev(device, N, nT, R, nlin, dt, (const double*)dXc.p, (const double*)dAW.p, (const int64_t*)dO.p, win,
+                               n_rep, rep0, seed, flags, accumulate, (int64_t*)dA.p, (int64_t*)dE.p, (int64_t*)dC.p,
+                               (uint8_t*)dS.p, fallbacks ? (int64_t*)dF.p : nullptr, (double*)dW.p, nullptr);
+    if (rc) return done(rc);
+    hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return done(fail(PGL_ERR_HIP, std::string("simulate_cond: ") + hipGetErrorString(e)));
+    if (hipMemcpy(acc, dA.p, PGL_CS_NACC * nw * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(exceptions, dE.p, (size_t)N * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+        (fallbacks && hipMemcpy(fallbacks, dF.p, 8, hipMemcpyDeviceToHost) != hipSuccess) ||
+        (counts_out && hipMemcpy(counts_out, dC.p, (size_t)n_rep * N * 8, hipMemcpyDeviceToHost) != hipSuccess) ||
+        (S_out && hipMemcpy(S_out, dS.p, nout, hipMemcpyDeviceToHost) != hipSuccess))
+        return done(fail(PGL_ERR_HIP, "simulate_cond: download failed"));
+    return done(PGL_OK);
+}
+
 // Leading singular pairs of a batch of (L x D) matrices (k_lsp_*, pglm_stim.hip.h).  Host arrays; everything in between on
 // the device with the library's own kernels.
 int pgl_leading_singular_pairs(pgl_handle h, const double* A, int n, int L, int D, double* U, double* sigma, double* V)

@@ -53,6 +53,8 @@
 // The same draws become the filters with their uncertainty, one (group of B weights, row) per workgroup: the curve of every
 // draw lag by lag, moments in a fixed order, quantiles from a sorting network in LDS, a simultaneous band (k_filter_bands,
 // pglm_filters.hip.h).
+// The clamped simulation holds the other neurons at their recorded spikes: the chains (replicate, neuron) decouple, one wave
+// per (neuron, 64 replicates) with the self-history in a per-lane queue (k_cond_currents, k_simulate_cond, pglm_condsim.hip.h).
 #pragma once
 //
 // The kernels live in one header per family; this file is the translation unit's table of contents.
@@ -89,3 +91,4 @@
 #include "pglm_diag.hip.h"
 #include "pglm_filters.hip.h"
 #include "pglm_simulate.hip.h"
+#include "pglm_condsim.hip.h"

@@ -14,6 +14,10 @@ discrete-time correction to it (a random function of its seed, 0).  With --hmc N
 distance over the posterior draws per neuron (corrected; sorted and tested on the device).  --gof-lags L adds the independence
 table (serial correlation of the normal scores at the lags 1 .. L, inference/gof.py) behind either.
 --ppc N prints the predictive spike-count table of N replicates simulated from the fitted model (inference/predictive.py).
+--cond-ppc N [WIN] prints the clamped predictive check of N replicates per neuron over windows of WIN bins (default 50): every
+neuron simulated with its own spikes fed back and the other neurons held at their recorded spikes (inference/predictive.py:
+conditional_counts) -- the largest |pearson| and its window, the KS distance of the pit values, the share of windows whose
+observed count lies outside the replicates' [min, max].
 --hmc N draws N posterior samples of every neuron's parameters from the fit by lock-step HMC on the device
 (inference/batched_hmc.py) and prints the bias posterior mean +- sd per neuron, beside the Laplace standard error when
 the model's packing has one.
@@ -71,7 +75,7 @@ def initialize_test_harness(model_name, data, data_dir=None):
 
 def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False, gof=False, ppc=0, hmc=0, ais=0,
                    hmc_mass='laplace', prox=False, laplace_device=False, ais_mass='laplace', nuts=0, smc=0, newton=False, waic=False, loo=False, diag=False, rates=0,
-                   gof_correct=False, gof_draws=False, gof_lags=0, coupling_test=None, coupling_lr=False, filters=None):
+                   gof_correct=False, gof_draws=False, gof_lags=0, coupling_test=None, coupling_lr=False, filters=None, cond_ppc=None):
     """test/synth_map.py:10-32."""
     popn, popn_true, x_true = initialize_test_harness(model_name, data, data_dir)
     x0 = popn.sample(rng)
@@ -97,6 +101,8 @@ def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, r
     if ppc:
         from theano_pyglm_amd.inference import predictive
         print(predictive.format_table(predictive.predictive_counts(popn, x_inf, ppc)))
+    if cond_ppc:
+        print(cond_ppc_table(popn, x_inf, cond_ppc))
     if hmc:
         print(hmc_bias_table(popn, x_inf, hmc, hmc_mass, laplace_device, waic=waic, loo=loo, diag=diag, rates=rates, gof_draws=gof_draws, gof_lags=gof_lags,
                              filters=filters, truth=true_adjacency(popn_true, x_true)))
@@ -234,6 +240,14 @@ def nuts_bias_table(popn, x, n_draws, mass='laplace', laplace_device=False, waic
     return "\n".join(lines)
 
 
+def cond_ppc_table(popn, x, cond_ppc):
+    """The clamped predictive check of --cond-ppc N [WIN]: N replicates of every neuron given the recorded spikes of the others,
+    over windows of WIN bins (default 50), formatted like --rates."""
+    from theano_pyglm_amd.inference import predictive
+    n_rep, win = (list(cond_ppc) + [50])[:2]
+    return predictive.format_cond_table(predictive.conditional_counts(popn, x, n_rep=n_rep, win=win))
+
+
 def rates_table(popn, x, samples, win):
     """The windowed predictive residuals of posterior draws (samples (S, N, P) of all neurons) over windows of `win` bins:
     predictive.format_rate_table of predictive.rate_bands."""
@@ -314,6 +328,14 @@ def smc_evidence_table(popn, x, n_particles, laplace_device=False, mass='laplace
     return "\n".join(lines)
 
 
+class _CondPpc(argparse.Action):
+    """--cond-ppc N [WIN]: one or two positive integers"""
+    def __call__(self, ap, namespace, values, option_string=None):
+        if len(values) > 2 or min(values) < 1:
+            ap.error("--cond-ppc takes N [WIN]: one or two integers, each at least 1")
+        setattr(namespace, self.dest, values)
+
+
 def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('-m', '--model', default='standard_glm')
@@ -344,6 +366,9 @@ def parser():
                          'tested on the device; prints mean, 5 %% and 95 %% quantiles and the share of draws inside the band')
     ap.add_argument('--ppc', type=int, default=0, metavar='N',
                     help='after the fit: predictive spike counts of N replicates simulated from the fitted model on the device')
+    ap.add_argument('--cond-ppc', type=int, nargs='+', default=None, metavar='N', action=_CondPpc,
+                    help='N [WIN]: after the fit, the clamped predictive check of N replicates per neuron over windows of WIN bins '
+                         '(default 50): each neuron simulated on the device given the recorded spikes of the others')
     ap.add_argument('--hmc', type=int, default=0, metavar='N',
                     help='after the fit: N posterior draws per neuron by lock-step HMC on the device; prints the bias mean +- sd')
     ap.add_argument('--nuts', type=int, default=0, metavar='N',
@@ -399,7 +424,8 @@ def main(argv=None):
                    hmc_mass=args.hmc_mass, prox=args.prox, laplace_device=args.laplace_device, ais_mass=args.ais_mass, nuts=args.nuts, smc=args.smc,
                    newton=args.newton, waic=args.waic, loo=args.loo, diag=args.diag, rates=args.rates,
                    gof_correct=args.gof_correct, gof_draws=args.gof_draws, gof_lags=args.gof_lags,
-                   coupling_test=args.coupling_test, coupling_lr=args.coupling_lr, filters=args.filters)
+                   coupling_test=args.coupling_test, coupling_lr=args.coupling_lr, filters=args.filters,
+                   cond_ppc=args.cond_ppc)
 
 
 if __name__ == '__main__':
