@@ -87,6 +87,10 @@ typedef struct pgl_context* pgl_handle;
                                    * k_gibbs_ll_cols, k_gibbs_reduce_cols / k_gibbs_update_cols) to the record, which setting the option
                                    * clears; 0 (default) = off */
 
+#define PGL_OPT_DECODE_CUT 89  /* dev / test: the 256-bin chunks a workgroup of k_dec_forward and the 64-bin tiles a workgroup of
+                                * k_dec_backward take (0 or 1 = one, the default; at most 64).  The results are the same bits at
+                                * every value: each element has one thread and a fixed order of additions. */
+
 /* Development switches (not part of the drop-in surface; results stay valid unless stated): 99 = debug word: bits 16..20 force
  * the sub-block loop of k_gibbs_rate_cols (1 .. 16; bits 8..11 are the older 4-bit field of the same, bit 12 switches the
  * shared-presynaptic path off), the low bits are timing ablations with invalid results; 95 = 2 keeps the narrow post
@@ -98,7 +102,7 @@ typedef struct pgl_context* pgl_handle;
 
 /* What pgl_version() returns: it changes with every change of a signature or a struct below, and a binding refuses a
  * library that reports another number (theano_pyglm_amd/_lib.py: ABI_VERSION). */
-#define PGL_ABI_VERSION 118
+#define PGL_ABI_VERSION 119
 
 const char* pgl_last_error(void);
 int pgl_version(void);
@@ -1266,6 +1270,60 @@ int pgl_simulate_cond(int device, int N, int64_t nT, int R, int nlin, double dt,
                       const int64_t* obs, int64_t win, int n_rep, int rep0, uint64_t seed, int flags, int accumulate,
                       int64_t* acc, int64_t* exceptions, int64_t* counts_out, uint8_t* S_out, int64_t* fallbacks);
 
+/* Stimulus decoding: the MAP stimulus given the spikes (the decoding half of Pillow et al., Nature 454 (2008) 995-999; the
+ * reference has no counterpart: its graph has no derivative with respect to the stimulus).  The objective, its gradient and
+ * its Hessian-vector products with respect to the stimulus, the parameters and the spikes fixed.  Rule and host mirror:
+ * csrc/pglm_decode.h, kernels: csrc/pglm_decode.hip.h.
+ * Served: a stimulus set by pgl_set_stimulus with the identity spatial basis in layout 1 (BasisStimulus: D dimensions, B
+ * temporal basis functions over Rt taps, feature column d B + b), both nonlinearities, the whole recording.  No stimulus,
+ * caller-supplied feature columns, layout 0 or a spatial basis ('spatiotemporal' dense), a separable stimulus and a time range
+ * (pgl_set_time_range: a time shard) return PGL_ERR_UNSUPPORTED.
+ * The unknown u (Tu, D) lives on the stimulus grid, dt_stim = q dt with an integer q >= 1:
+ *     s = L u            s[t] = (1 - r / q) u[i] + (r / q) u[i + 1] for t = q i + r, s[t] = u[Tu - 1] for i >= Tu - 1
+ *     K[tau, d, n]     = sum_b basis_t[tau, b] w_stim[n, d B + b],   tau = 0 .. Rt - 1
+ *     I[t, n]          = sum_d sum_tau K[tau, d, n] s[t - 1 - tau, d]          (strictly causal, s = 0 before bin 0)
+ *     x = c + I,  c[t, n] = bias_n + GX0[t, n]: the currents of the recorded spikes at theta with the stimulus weights zero
+ *     F(u)             = sum_t sum_n [S log lam(x) - dt lam(x)] + log p(u)     (the all-f64 rate function of pgl_rescale_dev)
+ *     r[t, n]          = S (log lam)'(x) - dt lam'(x)       exp: S - dt e^x;  explinear: (S / lam - dt) sig(x)
+ *     cc[t, n]         = the c_t of pgl_hvp_* above, with its limits
+ *     g_s[t', d]       = sum_n sum_tau K[tau, d, n] r[t' + 1 + tau, n]         (rows past nT are zero)
+ *     grad F           = L^T g_s + grad log p(u)
+ *     H v              = L^T K^T (cc o (K L v)) + hess log p . v
+ * Prior (pgl_decode_prior), per stimulus dimension Gaussian with mean mu and the tridiagonal precision (1 / sigma^2) I +
+ * (1 / rho^2) Dt^T Dt, Dt the first differences in time; rho = inf (or <= 0) gives the iid prior; the normalising constant is
+ * dropped:   log p(u) = sum_d [ -1/2 sum_i (u_i - mu)^2 / sigma^2 - 1/2 sum_{i < Tu-1} (u_{i+1} - u_i)^2 / rho^2 ].
+ *   pgl_decode_prepare_dev   d_theta (N, P), d_Weff (N, N): builds K (Rt D N doubles), runs the forward-only pass at theta with
+ *       the stimulus block written as zeros and keeps c in a buffer of its own (nT N doubles; later forward passes overwrite
+ *       GX).  New spikes / basis / stimulus invalidate it.  The handle's own copy of theta (its stimulus block now zeros) and
+ *       GX (now the currents WITHOUT the stimulus) are overwritten: what pgl_gibbs_prepare_all left there before is gone.
+ *   pgl_decode_eval_dev      d_u (Tu, D) -> d_F[3] = {F, log likelihood, log prior} and d_grad_u (Tu, D) or NULL.  r and cc stay
+ *       on the device (2 nT N doubles).  Launches: k_dec_interp, k_dec_forward<nlin, 0>, k_dec_sum and, with a gradient,
+ *       k_dec_backward, k_dec_interp_t.  The ll terms are added per (256-bin chunk, neuron), then the chunks in order, then the
+ *       neurons in order; nothing is atomic: two calls give the same bits.
+ *   pgl_decode_hvp_dev       d_v, d_hv (Tu, D): H v at the point, Tu, q and prior of the last eval (none since the last prepare:
+ *       PGL_ERR_STATE).  Launches: k_dec_interp, k_dec_forward<nlin, 1>, k_dec_backward, k_dec_interp_t.
+ *   pgl_decode_prepare / pgl_decode_eval / pgl_decode_hvp   the same with host arrays.  They move Tu D doubles each way, so
+ *       they take the columns D of the caller's arrays (and pgl_decode_hvp the rows Tu): D other than the stimulus dimensions
+ *       of the handle, or Tu other than the last evaluation's, is PGL_ERR_ARG and nothing is copied.
+ *   pgl_decode_host          the whole rule on the host, no GPU and no handle: c, S (nT, N) (spike counts as doubles),
+ *       basis_t (Rt, B), theta (N, P) with P >= 1 + D B, u (Tu, D) -> F[3], grad_u (or NULL) and, where v is given, hv.
+ * The _dev forms are asynchronous on the handle's stream.  Tu < 1, q < 1, sigma <= 0 or a NULL pointer: PGL_ERR_ARG; eval before
+ * prepare: PGL_ERR_STATE. */
+typedef struct {
+    double mu, sigma, rho;
+} pgl_decode_prior;
+int pgl_decode_prepare_dev(pgl_handle h, const double* d_theta, const double* d_Weff);
+int pgl_decode_eval_dev(pgl_handle h, const double* d_u, int64_t Tu, int q, const pgl_decode_prior* prior, double* d_F,
+                        double* d_grad_u);
+int pgl_decode_hvp_dev(pgl_handle h, const double* d_v, double* d_hv);
+int pgl_decode_prepare(pgl_handle h, const double* theta, const double* Weff);
+int pgl_decode_eval(pgl_handle h, const double* u, int64_t Tu, int D, int q, const pgl_decode_prior* prior, double* F_out,
+                    double* grad_u_out);
+int pgl_decode_hvp(pgl_handle h, const double* v, int64_t Tu, int D, double* hv_out);
+int pgl_decode_host(int N, int64_t nT, int nlin, double dt, const double* c, const double* S, const double* basis_t, int Rt, int B,
+                    int D, const double* theta, int P, const double* u, int64_t Tu, int q, const pgl_decode_prior* prior,
+                    const double* v, double* F_out, double* grad_u_out, double* hv_out);
+
 /* Timing of the most recent pgl_ll_grad[_dev] call, measured with HIP events on the
  * handle's stream: ms of the fused kernel alone and of the whole call (prep +
  * fused + finalize).  For the _dev form call after pgl_sync. */
@@ -1298,7 +1356,12 @@ int pgl_set_stream(pgl_handle h, void* stream);
  * 6 the launches of pgl_rescale_dev (those of path 2, then k_rescale_chunk<nlin>, k_rescale_scan, k_rescale_finish; the dry
  * run's context has nlin = PGL_NLIN_EXP), 7 the launches of pgl_pointwise_dev (those of path 2, then k_pw_chunk<nlin>,
  * k_pw_block), 8 the launches of pgl_rate_windows_dev at win = 50 (those of path 2, then k_rw_piece<nlin>, k_rw_window),
- * 9 the launches of pgl_rescale_corr_dev (those of path 2, then k_rcorr_chunk<nlin>, k_rescale_scan, k_rcorr_finish).
+ * 9 the launches of pgl_rescale_corr_dev (those of path 2, then k_rcorr_chunk<nlin>, k_rescale_scan, k_rcorr_finish),
+ * 11 the launches of pgl_decode_prepare_dev and of a pgl_decode_eval_dev with a gradient behind it (k_dec_filters, those of
+ * path 2, k_dec_offset; k_dec_interp, k_dec_forward<nlin, 0>, k_dec_sum, k_dec_backward, k_dec_interp_t; the dry run reads
+ * Dstim as one stimulus dimension of Dstim basis functions over R taps; Dstim = 0 or stim >= 1: PGL_ERR_UNSUPPORTED, as the
+ * call), 12 the launches of pgl_decode_hvp_dev behind such an eval (k_dec_interp, k_dec_forward<nlin, 1>, k_dec_backward,
+ * k_dec_interp_t).
  * Paths 3 / 4 / 5 with stim >= 1 return PGL_ERR_UNSUPPORTED, as the calls themselves.
  * The reference has no counterpart (Theano picks its own C implementations); tests hold every reachable instantiation to
  * zero bytes of scratch. */

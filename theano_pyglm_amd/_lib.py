@@ -63,10 +63,11 @@ SYMBOLS = [
     'pgl_simulate_streams', 'pgl_simulate_batch', 'pgl_simulate_batch_dev', 'pgl_simulate_batch_plan',
     'pgl_simulate_cond_streams', 'pgl_cond_currents_dev', 'pgl_cond_currents', 'pgl_simulate_cond_workspace',
     'pgl_simulate_cond_dev', 'pgl_simulate_cond',
+    'pgl_decode_prepare_dev', 'pgl_decode_eval_dev', 'pgl_decode_hvp_dev', 'pgl_decode_prepare', 'pgl_decode_eval', 'pgl_decode_hvp', 'pgl_decode_host',
 ]
 
 
-ABI_VERSION = 118                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
+ABI_VERSION = 119                   # PGL_ABI_VERSION of include/pyglm_hip.h: load() refuses a library that reports another
 
 GEMM_NT, GEMM_MFMA_1, GEMM_MFMA_4, GEMM_KC_4_1_8, GEMM_KC_1_0_16 = range(5)   # PGL_GEMM_*: the kernel of pgl_gemm_dev
 
@@ -93,6 +94,8 @@ CS_NACC = 6                         # PGL_CS_NACC: planes of the clamped simulat
 CS_PLANES = ('sum', 'sum_sq', 'n_less', 'n_equal', 'min', 'max')
 CS_QUEUE = 32                       # PGL_CS_QUEUE: own spike bins a chain of k_simulate_cond keeps before it moves to a ring
 CS_MAX_R = 4096                     # PGL_CS_MAX_R: taps of self-history simulate_cond serves; more: PGL_ERR_UNSUPPORTED
+DEC_NF = 3                          # PGL_DEC_NF: F, log likelihood, log prior of decode_eval (csrc/pglm_decode.h)
+OPT_DECODE_CUT = 89                 # PGL_OPT_DECODE_CUT: chunks / tiles a workgroup of the decoding kernels takes (same bits)
 FILT_GRP_COLS = ('c_sim', 'weight_mean', 'weight_sd', 'weight_q_lo', 'weight_median', 'weight_q_hi', 'p_pos', 'info')   # PGL_FILT_NGRP
 
 
@@ -104,6 +107,20 @@ class Prior(C.Structure):
     """pgl_prior of include/pyglm_hip.h."""
     _fields_ = [('kind', C.c_int), ('mu_b', C.c_double), ('sg_b', C.c_double), ('stim_sigma', C.c_double),
                 ('mu', C.c_double), ('sigma', C.c_double), ('lam', C.c_double)]
+
+
+class DecodePrior(C.Structure):
+    """pgl_decode_prior of include/pyglm_hip.h: per stimulus dimension Gaussian with mean mu and precision I / sigma^2 +
+    Dt^T Dt / rho^2 (Dt: first differences in time); rho = inf: iid."""
+    _fields_ = [('mu', C.c_double), ('sigma', C.c_double), ('rho', C.c_double)]
+
+
+def as_decode_prior(p):
+    """A DecodePrior from a DecodePrior or from (mu, sigma, rho)."""
+    if isinstance(p, DecodePrior):
+        return p
+    mu, sigma, rho = p
+    return DecodePrior(float(mu), float(sigma), float(rho))
 
 
 def as_prior(p):
@@ -337,6 +354,15 @@ def load():
             C.c_int, C.c_int, vp, vp, vp, vp, vp]
     lib.pgl_simulate_cond.argtypes = cond
     lib.pgl_simulate_cond_dev.argtypes = cond + [vp, vp]
+    dpr = C.POINTER(DecodePrior)
+    lib.pgl_decode_prepare_dev.argtypes = [vp, vp, vp]
+    lib.pgl_decode_eval_dev.argtypes = [vp, vp, C.c_int64, C.c_int, dpr, vp, vp]
+    lib.pgl_decode_hvp_dev.argtypes = [vp, vp, vp]
+    lib.pgl_decode_prepare.argtypes = [vp, vp, vp]
+    lib.pgl_decode_eval.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_int, dpr, vp, vp]
+    lib.pgl_decode_hvp.argtypes = [vp, vp, C.c_int64, C.c_int, vp]
+    lib.pgl_decode_host.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_double, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp,
+                                    C.c_int64, C.c_int, dpr, vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name in ('pgl_bfgs_state_doubles', 'pgl_ncg_state_doubles', 'pgl_newton_state_doubles', 'pgl_hmc_state_doubles',
@@ -576,6 +602,29 @@ def simulate_cond_dev(N, nT, R, nlin, dt, d_Xc, d_AW, d_obs, win, n_rep, d_acc, 
                                       _dp(stream)))
 
 
+def decode_host(c, S, basis_t, D, theta, nlin, dt, u, q, prior, v=None, want_grad=True):
+    """The decoding rule on the host (pgl_decode_host: plain C, no GPU): c, S (nT, N), basis_t (Rt, B), theta (N, P) with the
+    stimulus weights in columns 1 .. D B, u (Tu, D), prior (mu, sigma, rho) -> (F (3,): F, log likelihood, log prior; grad
+    (Tu, D) or None; H v (Tu, D) where v is given, else None)."""
+    c = _f64(c)
+    nT, N = c.shape
+    S = _f64(S, (nT, N))
+    bt = _f64(basis_t)
+    th = _f64(theta)
+    u = _f64(u)
+    if u.ndim != 2 or u.shape[1] != D:
+        raise ValueError("u must be (Tu, D)")
+    vv = None if v is None else _f64(v, u.shape)
+    F = np.empty(DEC_NF)
+    g = np.empty(u.shape) if want_grad else None
+    hv = None if v is None else np.empty(u.shape)
+    pr = as_decode_prior(prior)
+    _chk(load().pgl_decode_host(N, nT, int({'exp': NLIN_EXP, 'explinear': NLIN_EXPLINEAR}.get(nlin, nlin)), float(dt), _ptr(c),
+                                _ptr(S), _ptr(bt), bt.shape[0], bt.shape[1], int(D), _ptr(th), th.shape[1], _ptr(u), u.shape[0],
+                                int(q), C.byref(pr), _ptr(vv), _ptr(F), _ptr(g), _ptr(hv)))
+    return F, g, hv
+
+
 class DeviceGlm(object):
     """One pgl_handle: the device-resident data of one data sequence
     (the Theano shared variables S / ir / stim of glm.py:17-18, impulse.py:41-42,
@@ -587,6 +636,7 @@ class DeviceGlm(object):
         self.N, self.nT, self.B, self.R, self.dt = int(N), int(nT), int(B), int(R), float(dt)
         self.nlin = {'exp': NLIN_EXP, 'explinear': NLIN_EXPLINEAR}.get(nlin, nlin)
         self.Dstim = 0
+        self.dec_D = None                  # stimulus dimensions of a 'basis' stimulus (set_stimulus): what decode_* serves
         h = C.c_void_p()
         _chk(self.lib.pgl_create(self.N, self.nT, self.B, self.R, int(self.nlin), self.dt,
                                  int(device), C.byref(h)))
@@ -635,12 +685,14 @@ class DeviceGlm(object):
         if fstim is None:
             _chk(self.lib.pgl_set_stim_features(self.h, None, 0))
             self.Dstim = 0
+            self.dec_D = None
             return
         f = _f64(fstim)
         if f.ndim != 2 or f.shape[0] != self.nT:
             raise ValueError("fstim must be (nT,Dstim)")
         _chk(self.lib.pgl_set_stim_features(self.h, _ptr(f), int(f.shape[1])))
         self.Dstim = int(f.shape[1])
+        self.dec_D = None
 
     def set_stimulus(self, stim, dt_stim, basis_t, basis_x=None, layout=0):
         """Build the dense stimulus feature columns on the device from the raw stimulus
@@ -655,6 +707,7 @@ class DeviceGlm(object):
                                        _ptr(bx), int(Bx), _ptr(bt), bt.shape[0], bt.shape[1],
                                        int(layout)))
         self.Dstim = int(Bx * bt.shape[1])
+        self.dec_D = int(stim.shape[1]) if bx is None and int(layout) == 1 else None
 
     def set_stimulus_separable(self, stim, dt_stim, basis_t, basis_x=None):
         """Rank-1 (w_t (x) w_x) stimulus kept separable on the device; theta rows become
@@ -669,6 +722,7 @@ class DeviceGlm(object):
                                                  float(dt_stim), _ptr(bx), int(Bx), _ptr(bt), bt.shape[0],
                                                  bt.shape[1]))
         self.Dstim = int(Bx + bt.shape[1])
+        self.dec_D = None
 
     def get_stim_features(self):
         out = np.empty((self.nT, self.Dstim))
@@ -993,6 +1047,58 @@ class DeviceGlm(object):
         obs = np.empty((n_win, self.N))
         _chk(self.lib.pgl_rate_windows(self.h, _ptr(th), _ptr(We), int(win), _ptr(lam), _ptr(obs)))
         return lam, obs
+
+    # -- stimulus decoding: F(u), its gradient and Hessian-vector products w.r.t. the stimulus (pgl_decode_*) ------------
+    def _decode_array(self, a, name, Tu=None):
+        """a as a contiguous float64 (Tu, D) array, D the stimulus dimensions of the 'basis' stimulus on the handle; ValueError
+        where its shape is another (the library moves Tu * D doubles each way)."""
+        a = _f64(a)
+        if self.dec_D is None:
+            raise ValueError("stimulus decoding needs a 'basis' stimulus on the handle (set_stimulus with basis_x=None, layout=1)")
+        if a.ndim != 2 or a.shape[1] != self.dec_D or (Tu is not None and a.shape[0] != Tu):
+            raise ValueError("%s must be (Tu, D) = (%s, %d), got %s" % (name, 'Tu' if Tu is None else Tu, self.dec_D, a.shape))
+        return a
+
+    def decode_prepare(self, theta, Weff):
+        """Builds the filters K and the offset c = bias + the currents of the recorded spikes at the host arrays theta (N, P),
+        Weff (N, N) and keeps them on the device for decode_eval / decode_hvp; see pgl_decode_prepare.  A 'basis' stimulus
+        only.  The handle's copy of theta and its currents GX are overwritten."""
+        th, We = self._draw(theta, Weff)
+        _chk(self.lib.pgl_decode_prepare(self.h, _ptr(th), _ptr(We)))
+        self._dec_Tu = None
+
+    def decode_prepare_dev(self, d_theta, d_Weff):
+        """Device-pointer form (integers; asynchronous): d_theta (N, P), d_Weff (N, N)."""
+        _chk(self.lib.pgl_decode_prepare_dev(self.h, _dp(d_theta), _dp(d_Weff)))
+        self._dec_Tu = None
+
+    def decode_eval_dev(self, d_u, Tu, q, prior, d_F, d_grad_u=0):
+        """Device-pointer form (integers; asynchronous): d_u (Tu, D) -> d_F (3,) and d_grad_u (Tu, D) or 0; prior: (mu, sigma,
+        rho) or a DecodePrior; see pgl_decode_eval_dev.  The caller answers for the shapes."""
+        pr = as_decode_prior(prior)
+        _chk(self.lib.pgl_decode_eval_dev(self.h, _dp(d_u), int(Tu), int(q), C.byref(pr), _dp(d_F), _dp(d_grad_u)))
+        self._dec_Tu = int(Tu)
+
+    def decode_hvp_dev(self, d_v, d_hv):
+        """d_hv = H d_v at the point, Tu, q and prior of the last decode_eval[_dev] (device pointers; asynchronous)."""
+        _chk(self.lib.pgl_decode_hvp_dev(self.h, _dp(d_v), _dp(d_hv)))
+
+    def decode_eval(self, u, q, prior, want_grad=True):
+        """(F (3,): F, log likelihood, log prior; grad (Tu, D) or None) at the host array u (Tu, D) behind decode_prepare."""
+        u = self._decode_array(u, 'u')
+        F = np.empty(DEC_NF)
+        g = np.empty(u.shape) if want_grad else None
+        pr = as_decode_prior(prior)
+        _chk(self.lib.pgl_decode_eval(self.h, _ptr(u), u.shape[0], u.shape[1], int(q), C.byref(pr), _ptr(F), _ptr(g)))
+        self._dec_Tu = u.shape[0]
+        return F, g
+
+    def decode_hvp(self, v):
+        """H v (Tu, D) at the point of the last decode_eval, host arrays."""
+        v = self._decode_array(v, 'v', getattr(self, '_dec_Tu', None))
+        out = np.empty(v.shape)
+        _chk(self.lib.pgl_decode_hvp(self.h, _ptr(v), v.shape[0], v.shape[1], _ptr(out)))
+        return out
 
     # -- PSIS-LOO of the columns of a pointwise matrix over draws (pgl_psis_loo*) -----------------------
     def psis_loo(self, ll, out=None, weights=False):

@@ -129,6 +129,15 @@ struct pgl_context {
     DevBuf rs_qev, rs_tail, ks_work;
     DevBuf pw_part;                      // pointwise ll (pgl_pointwise_dev): chunk sums
     DevBuf rw_part, rw_cnt;              // rate windows (pgl_rate_windows_dev): piece sums of rate and spike counts
+    // stimulus decoding (pgl_decode_*): dec_stim -- the stimulus came through pgl_set_stimulus with the identity spatial basis
+    // in layout 1, its temporal basis (dec_Rt, dec_B) is kept in dec_basis and D = dec_D; dec_ok -- K and the offset c of the
+    // last prepare stand (new spikes / basis / stimulus: they fall); dec_point -- r and cc of an eval since then, with its Tu,
+    // q and prior
+    bool dec_stim = false, dec_ok = false, dec_point = false;
+    int dec_Rt = 0, dec_B = 0, dec_D = 0, dec_q = 0, opt_dec_cut = 0;
+    int64_t dec_Tu = 0;
+    PglDecPrior dec_prior = {0.0, 1.0, 0.0};
+    DevBuf dec_basis, dec_K, dec_c, dec_r, dec_cc, dec_y, dec_s, dec_gs, dec_part, dec_col;
     // the host-array forms (pgl_hvp .. pgl_chain_diag): the device copies of their arrays, taken by index (stage_up).  Every
     // such call ends in stage_end, so a slot holds nothing across calls and the forms share them
     static constexpr int NSTAGE = 6;     // (pgl_wald_groups moves six arrays)
@@ -164,6 +173,7 @@ static int find_img(const pgl_context* h, int key, int tile0, int ntiles)
 static void invalidate_images(pgl_context* h)
 {
     h->hvp_ok = false;                            // (new spikes / basis / stimulus: the prepared curvature is stale too)
+    h->dec_ok = h->dec_point = false;             // (and the decoder's filters and offset)
     for (int i = 0; i < pgl_context::NIMG; ++i) h->imgs[i].key = 0;
 }
 // can a new image set of `want` bytes be placed (in a free slot, or over the least recently used one)?
@@ -413,7 +423,8 @@ int pgl_destroy(pgl_handle h)
                       &h->gargs, &h->gpart, &h->gout, &h->ghs, &h->gfs, &h->zf, &h->zfT, &h->sbt, &h->Yf, &h->Qb, &h->Qf,
                       &h->spart, &h->sepC, &h->sepA, &h->sepAT, &h->sepD, &h->YfT, &h->Hb, &h->wpart, &h->QvT, &h->staA,
                       &h->Cbuf, &h->hvp_idx, &h->hvp_Weff, &h->hvp_ll, &h->hess_part, &h->rs_pre, &h->rs_tot, &h->rs_cum,
-                      &h->rs_qev, &h->rs_tail, &h->ks_work, &h->pw_part, &h->rw_part, &h->rw_cnt};
+                      &h->rs_qev, &h->rs_tail, &h->ks_work, &h->pw_part, &h->rw_part, &h->rw_cnt, &h->dec_basis, &h->dec_K,
+                      &h->dec_c, &h->dec_r, &h->dec_cc, &h->dec_y, &h->dec_s, &h->dec_gs, &h->dec_part, &h->dec_col};
     for (DevBuf* b : bufs) release(*b);
     for (DevBuf& b : h->stage) release(b);
     for (int s = 0; s < pgl_context::NEV; ++s)
@@ -447,7 +458,8 @@ int pgl_set_option(pgl_handle h, int option, int value)
     case 99: h->opt_dbg = value; return PGL_OK;
     case 98: h->opt_ptw = value; return PGL_OK;
     case 97: if (value < 0 || value > 16) return fail(PGL_ERR_ARG, "finalize waves: 0 (auto) .. 16"); h->opt_finw = value; return PGL_OK;
-    case 90: h->opt_tri_rows = value; return PGL_OK;         // dev: 1 = the triangular products of the dense-mass HMC on one workgroup per row (A/B)
+    case PGL_OPT_DECODE_CUT: if (value < 0 || value > 64) return fail(PGL_ERR_ARG, "decode cut: 0 .. 64"); h->opt_dec_cut = value; return PGL_OK;
+    case 90: h->opt_tri_rows = value; return PGL_OK;        // dev: 1 = the triangular products of the dense-mass HMC on one workgroup per row (A/B)
     case 91: h->opt_pbmajor = value; return PGL_OK;          // dev: 1 = chunk-major grid for wide populations (A/B)
     case 92: h->opt_hlp = value; return PGL_OK;              // dev: 1 = no helper waves in the two-pass kernel (A/B)
     case 93: h->opt_slice_cols = value; return PGL_OK;      // dev: feature columns per slice of the 3-phase path (0 = 640)
@@ -628,6 +640,7 @@ int pgl_set_stim_features(pgl_handle h, const double* fstim, int Dstim)
     h->Dstim = Dstim;
     h->Ktot = h->Kimp + Dstim;
     h->sep = false;
+    h->dec_stim = false;
     h->gibbs_npost = -1;
     invalidate_images(h);
     h->gx_xs = 0;
@@ -680,6 +693,14 @@ int pgl_set_stimulus(pgl_handle h, const double* stim, int64_t Tstim, int D, dou
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     cleanup();
     if (e != hipSuccess) return fail(PGL_ERR_HIP, std::string("pgl_set_stimulus: ") + hipGetErrorString(e));
+    // what pgl_decode_* needs of a 'basis' stimulus: its temporal basis
+    h->dec_stim = !basis_x && layout == 1;
+    if (h->dec_stim) {
+        ENSURE(h->dec_basis, (size_t)Rt * Bt * 8);
+        HIPCHK(hipMemcpyAsync(h->dec_basis.p, basis_t, (size_t)Rt * Bt * 8, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        h->dec_Rt = Rt; h->dec_B = Bt; h->dec_D = D;
+    }
     h->Dstim = Dstim;
     h->Ktot = h->Kimp + Dstim;
     h->sep = false;
@@ -812,6 +833,7 @@ int pgl_set_stimulus_separable(pgl_handle h, const double* stim, int64_t Tstim, 
     if (rc) return rc;
     if (e != hipSuccess) return fail(PGL_ERR_HIP, std::string("pgl_set_stimulus_separable: ") + hipGetErrorString(e));
     h->sep = true;
+    h->dec_stim = false;
     h->sepBt = Bt; h->sepBx = Bx; h->sepRt = Rt; h->sepT = Tstim; h->sep_dt_stim = dt_stim;
     {
         int rc2 = build_frame_table(h, basis_t, Rt, Bt, dt_stim);
@@ -1926,6 +1948,10 @@ static int enqueue_rescale(pgl_handle h, double* d_tau, const long long* d_off, 
                            unsigned long long seed = 0, long long draw = 0);
 static int enqueue_pointwise(pgl_handle h, int block_chunks, double* d_ll_blk, double* d_acc, long long draw);
 static int enqueue_rate_windows(pgl_handle h, long long win, double* d_lam, double* d_obs, double* d_acc, long long draw);
+static int enqueue_decode_prepare(pgl_handle h);
+static int enqueue_decode_eval(pgl_handle h, const double* d_u, int64_t Tu, int q, const PglDecPrior& prior, double* d_F,
+                               double* d_grad_u);
+static int enqueue_decode_hvp(pgl_handle h, const double* d_v, double* d_hv);
 static int enqueue_acf(pgl_handle h, const double* d_tau, const int64_t* d_run_off, const int64_t* d_seg_run, int64_t M, int max_lag,
                        double* d_out, double* d_scores);
 
@@ -1951,7 +1977,8 @@ int pgl_last_kernels(pgl_handle h, char* out, int cap)
 // pgl_pointwise_dev (the forward launches of path 2, then k_pw_chunk and k_pw_block), 8 those of pgl_rate_windows_dev (the
 // forward launches of path 2, then k_rw_piece and k_rw_window), 9 those of pgl_rescale_corr_dev (the forward launches of path 2,
 // then k_rcorr_chunk, k_rescale_scan and k_rcorr_finish), 10 the launch of pgl_rescale_acf_dev alone (no forward pass: the
-// shape is ignored).
+// shape is ignored), 11 the launches of pgl_decode_prepare_dev and a pgl_decode_eval_dev with a gradient behind it, 12 those of
+// pgl_decode_hvp_dev behind them (Dstim read as one stimulus dimension of Dstim basis functions over R taps).
 int pgl_plan_kernels(int N, int B, int R, int Dstim, long long nT, int stim, int n_lo, int count, int path, int opt_kernel,
                      int opt_f32, char* out, int cap)
 {
@@ -1981,6 +2008,19 @@ int pgl_plan_kernels(int N, int B, int R, int Dstim, long long nT, int stim, int
             g_dry = &names;
             rc = (path == 4) ? enqueue_hvp_apply(&c, nullptr, &dummy) : enqueue_hess(&c, &dummy, 1 + Dstim + c.Kimp);
         }
+    } else if (path == 11 || path == 12) {
+        // pgl_decode_prepare_dev + pgl_decode_eval_dev (11), pgl_decode_hvp_dev behind them (12): Dstim basis functions of one
+        // stimulus dimension over R taps
+        if (c.sep) return fail(PGL_ERR_UNSUPPORTED, "stimulus decoding with a separable stimulus");
+        if (Dstim < 1) return fail(PGL_ERR_UNSUPPORTED, "stimulus decoding needs a 'basis' stimulus");
+        c.dec_stim = true; c.dec_Rt = R; c.dec_B = Dstim; c.dec_D = 1;
+        const PglDecPrior prior = {0.0, 1.0, 0.0};
+        std::vector<std::string> before;
+        g_dry = (path == 11) ? &names : &before;
+        rc = enqueue_decode_prepare(&c);
+        if (rc == PGL_OK) rc = enqueue_decode_eval(&c, &dummy, 1, 1, prior, &dummy, &dummy);
+        g_dry = &names;
+        if (rc == PGL_OK && path == 12) rc = enqueue_decode_hvp(&c, &dummy, &dummy);
     } else {
         g_dry = &names;
         rc = (path == 10) ? enqueue_acf(&c, &dummy, nullptr, nullptr, 1, 1, &dummy, &dummy)
@@ -3608,6 +3648,245 @@ int pgl_filter_bands(pgl_handle h, const double* samples, int64_t n_keep, int64_
     PASS(stage_down(h, out, h->stage[3].p, ob));
     PASS(stage_down(h, grp, h->stage[4].p, gb));
     return stage_end(h);
+}
+
+// ---- stimulus decoding: F(u), its gradient and its Hessian-vector products with respect to the stimulus (pglm_decode.hip.h) ---
+static int dec_served(const pgl_context* h)
+{
+    if (h->sep) return fail(PGL_ERR_UNSUPPORTED, "stimulus decoding with a separable stimulus");
+    if (!h->dec_stim || h->Dstim == 0)
+        return fail(PGL_ERR_UNSUPPORTED, "stimulus decoding needs a 'basis' stimulus (pgl_set_stimulus with the identity spatial "
+                                         "basis in layout 1)");
+    if (h->t_lo != 0 || h->t_hi != h->nT) return fail(PGL_ERR_UNSUPPORTED, "stimulus decoding of a time range");
+    if ((long long)h->nT * std::max(h->N, h->dec_D) > (1LL << 38))
+        return fail(PGL_ERR_UNSUPPORTED, "recording too long for the decoding kernels");
+    return PGL_OK;
+}
+static unsigned dec_blocks(long long n) { return (unsigned)((n + 255) / 256); }
+static DecAux dec_aux(const pgl_context* h, int64_t Tu, int q, const PglDecPrior& prior)
+{
+    DecAux a;
+    a.a = a.b = nullptr; a.out = a.col = nullptr;
+    a.nT = h->nT; a.Tu = Tu; a.nchunks = (h->nT + PGL_DEC_CHUNK - 1) / PGL_DEC_CHUNK;
+    a.N = h->N; a.D = h->dec_D; a.B = h->dec_B; a.P = 1 + h->Dstim + h->Kimp; a.Rt = h->dec_Rt; a.q = q;
+    a.xs = g_dry ? 16 * ((h->N + 15) / 16) : h->gx_xs;
+    a.prior = prior; a.center = 0.0;
+    return a;
+}
+static DecParams dec_params(const pgl_context* h)
+{
+    DecParams p;
+    p.src = bin_source(h);
+    p.K = (const double*)h->dec_K.p; p.c = (const double*)h->dec_c.p; p.s = (const double*)h->dec_s.p; p.yin = nullptr;
+    p.r = (double*)h->dec_r.p; p.cc = (double*)h->dec_cc.p; p.y = (double*)h->dec_y.p; p.part = (double*)h->dec_part.p;
+    p.gs = (double*)h->dec_gs.p;
+    p.nT = h->nT; p.N = h->N; p.Rt = h->dec_Rt; p.D = h->dec_D; p.cut = std::max(h->opt_dec_cut, 1); p.dt = h->dt;
+    return p;
+}
+static int dec_forward(pgl_handle h, int mode, const DecParams& p)
+{
+    const bool el = h->nlin == PGL_NLIN_EXPLINEAR;
+    const long long nchunks = (h->nT + PGL_DEC_CHUNK - 1) / PGL_DEC_CHUNK, nslabs = (h->N + PGL_DEC_NS - 1) / PGL_DEC_NS;
+    const unsigned blocks = (unsigned)((nchunks + p.cut - 1) / p.cut * nslabs);
+    if (mode == 0)
+        return launch_behind(h, el ? "k_dec_forward<1, 0>" : "k_dec_forward<0, 0>", el ? k_dec_forward<1, 0> : k_dec_forward<0, 0>,
+                             blocks, 256, p);
+    return launch_behind(h, el ? "k_dec_forward<1, 1>" : "k_dec_forward<0, 1>", el ? k_dec_forward<1, 1> : k_dec_forward<0, 1>, blocks,
+                         256, p);
+}
+// g_s = K^T yin, then out (Tu, D) = L^T g_s + the prior's part at x
+static int dec_backward(pgl_handle h, DecParams p, const double* yin, DecAux a, const double* x, double center, double* out)
+{
+    p.yin = yin;
+    const long long ntiles = (h->nT + PGL_DEC_TB - 1) / PGL_DEC_TB;
+    PASS(launch_behind(h, "k_dec_backward", k_dec_backward, (unsigned)((ntiles + p.cut - 1) / p.cut), 256, p));
+    a.a = p.gs; a.b = x; a.out = out; a.center = center;
+    return launch_behind(h, "k_dec_interp_t", k_dec_interp_t, dec_blocks(a.Tu * a.D), 256, a);
+}
+
+// theta / Weff of the draw in h->gtheta / h->Weff.  The dry run of the dispatch runs this too: see launch_behind.
+static int enqueue_decode_prepare(pgl_handle h)
+{
+    PASS(dec_served(h));
+    const int N = h->N, D = h->dec_D, Rt = h->dec_Rt;
+    ENSURE(h->dec_K, (size_t)Rt * D * N * 8);
+    ENSURE(h->dec_c, (size_t)h->nT * N * 8);
+    const PglDecPrior none = {0.0, 1.0, 0.0};
+    DecAux a = dec_aux(h, 1, 1, none);
+    a.a = (const double*)h->dec_basis.p; a.b = (const double*)h->gtheta.p; a.out = (double*)h->dec_K.p;
+    PASS(launch_behind(h, "k_dec_filters", k_dec_filters, dec_blocks((long long)Rt * D * N), 256, a));
+    // the stimulus block of the handle's copy of theta written as zeros: the forward pass leaves the currents of the spikes
+    if (!g_dry) HIPCHK(hipMemset2DAsync((char*)h->gtheta.p + 8, (size_t)a.P * 8, 0, (size_t)h->Dstim * 8, (size_t)N, h->stream));
+    PASS(enqueue_gibbs_forward(h));
+    a = dec_aux(h, 1, 1, none);                                             // (the row stride of GX is known now)
+    a.a = (const double*)h->GX.p; a.b = (const double*)h->gtheta.p; a.out = (double*)h->dec_c.p;
+    PASS(launch_behind(h, "k_dec_offset", k_dec_offset, dec_blocks((long long)h->nT * N), 256, a));
+    h->dec_ok = true;
+    h->dec_point = false;
+    return PGL_OK;
+}
+
+static int enqueue_decode_eval(pgl_handle h, const double* d_u, int64_t Tu, int q, const PglDecPrior& prior, double* d_F,
+                               double* d_grad_u)
+{
+    PASS(dec_served(h));
+    if (!h->dec_ok) return fail(PGL_ERR_STATE, "pgl_decode_eval before pgl_decode_prepare (or after new spikes / basis / stimulus)");
+    const size_t plane = (size_t)h->nT * h->N * 8, frames = (size_t)h->nT * h->dec_D * 8;
+    DecAux a = dec_aux(h, Tu, q, prior);
+    ENSURE(h->dec_s, frames);
+    ENSURE(h->dec_gs, frames);
+    ENSURE(h->dec_r, plane);
+    ENSURE(h->dec_cc, plane);
+    ENSURE(h->dec_part, (size_t)a.nchunks * h->N * 8);
+    ENSURE(h->dec_col, (size_t)h->N * 8);
+    a.a = d_u; a.out = (double*)h->dec_s.p;
+    PASS(launch_behind(h, "k_dec_interp", k_dec_interp, dec_blocks((long long)h->nT * a.D), 256, a));
+    const DecParams p = dec_params(h);
+    PASS(dec_forward(h, 0, p));
+    a.a = p.part; a.b = d_u; a.out = d_F; a.col = (double*)h->dec_col.p;
+    PASS(launch_behind(h, "k_dec_sum", k_dec_sum, 1, 256, a));
+    if (d_grad_u) PASS(dec_backward(h, p, p.r, a, d_u, prior.mu, d_grad_u));
+    h->dec_Tu = Tu; h->dec_q = q; h->dec_prior = prior;
+    h->dec_point = true;
+    return PGL_OK;
+}
+
+static int enqueue_decode_hvp(pgl_handle h, const double* d_v, double* d_hv)
+{
+    PASS(dec_served(h));
+    if (!h->dec_ok || !h->dec_point) return fail(PGL_ERR_STATE, "pgl_decode_hvp before pgl_decode_eval");
+    DecAux a = dec_aux(h, h->dec_Tu, h->dec_q, h->dec_prior);
+    ENSURE(h->dec_y, (size_t)h->nT * h->N * 8);
+    a.a = d_v; a.out = (double*)h->dec_s.p;
+    PASS(launch_behind(h, "k_dec_interp", k_dec_interp, dec_blocks((long long)h->nT * a.D), 256, a));
+    const DecParams p = dec_params(h);
+    PASS(dec_forward(h, 1, p));
+    return dec_backward(h, p, p.y, a, d_v, 0.0, d_hv);
+}
+
+int pgl_decode_prepare_dev(pgl_handle h, const double* d_theta, const double* d_Weff)
+{
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if (!d_theta || !d_Weff) return fail(PGL_ERR_ARG, "null argument");
+    PASS(dec_served(h));
+    HIPCHK(hipSetDevice(h->device));
+    const size_t tb = (size_t)h->N * (1 + (size_t)h->Dstim + h->Kimp) * 8, wb = (size_t)h->N * h->N * 8;
+    ENSURE(h->gtheta, tb);
+    ENSURE(h->Weff, wb);
+    if (d_theta != h->gtheta.p) HIPCHK(hipMemcpyAsync(h->gtheta.p, d_theta, tb, hipMemcpyDeviceToDevice, h->stream));
+    if (d_Weff != h->Weff.p) HIPCHK(hipMemcpyAsync(h->Weff.p, d_Weff, wb, hipMemcpyDeviceToDevice, h->stream));
+    return enqueue_decode_prepare(h);
+}
+
+static int dec_eval_check(pgl_handle h, const void* u, int64_t Tu, int q, const pgl_decode_prior* prior, const void* F)
+{
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if (!u || !prior || !F) return fail(PGL_ERR_ARG, "null argument");
+    if (Tu < 1 || q < 1) return fail(PGL_ERR_ARG, "stimulus decoding: Tu and q must be at least 1");
+    if (!(prior->sigma > 0.0) || prior->mu != prior->mu || prior->rho != prior->rho)
+        return fail(PGL_ERR_ARG, "stimulus decoding: the prior needs sigma > 0 and numbers for mu and rho");
+    if (Tu > (1LL << 38) / std::max(h->dec_D, 1)) return fail(PGL_ERR_UNSUPPORTED, "stimulus too long for the decoding kernels");
+    return dec_served(h);
+}
+
+int pgl_decode_eval_dev(pgl_handle h, const double* d_u, int64_t Tu, int q, const pgl_decode_prior* prior, double* d_F,
+                        double* d_grad_u)
+{
+    PASS(dec_eval_check(h, d_u, Tu, q, prior, d_F));
+    HIPCHK(hipSetDevice(h->device));
+    const PglDecPrior pr = {prior->mu, prior->sigma, prior->rho};
+    return enqueue_decode_eval(h, d_u, Tu, q, pr, d_F, d_grad_u);
+}
+
+int pgl_decode_hvp_dev(pgl_handle h, const double* d_v, double* d_hv)
+{
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if (!d_v || !d_hv) return fail(PGL_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(h->device));
+    return enqueue_decode_hvp(h, d_v, d_hv);
+}
+
+int pgl_decode_prepare(pgl_handle h, const double* theta, const double* Weff)
+{
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if (!theta || !Weff) return fail(PGL_ERR_ARG, "null argument");
+    PASS(dec_served(h));
+    HIPCHK(hipSetDevice(h->device));
+    PASS(upload_draw(h, theta, Weff));
+    return pgl_decode_prepare_dev(h, (const double*)h->gtheta.p, (const double*)h->Weff.p);
+}
+
+// D: the columns of the caller's arrays, which must be the stimulus dimensions of the handle -- the host forms move Tu * D doubles
+static int dec_host_dims(const pgl_context* h, int D)
+{
+    if (D != h->dec_D)
+        return fail(PGL_ERR_ARG, "stimulus decoding: the stimulus has " + std::to_string(D) + " columns, the handle's stimulus " +
+                                     std::to_string(h->dec_D) + " dimensions");
+    return PGL_OK;
+}
+
+int pgl_decode_eval(pgl_handle h, const double* u, int64_t Tu, int D, int q, const pgl_decode_prior* prior, double* F_out,
+                    double* grad_u_out)
+{
+    PASS(dec_eval_check(h, u, Tu, q, prior, F_out));
+    PASS(dec_host_dims(h, D));
+    HIPCHK(hipSetDevice(h->device));
+    const size_t ub = (size_t)Tu * h->dec_D * 8;
+    PASS(stage_up(h, 0, u, ub));
+    PASS(stage_up(h, 1, nullptr, PGL_DEC_NF * 8));
+    PASS(stage_up(h, 2, nullptr, ub));
+    PASS(pgl_decode_eval_dev(h, (const double*)h->stage[0].p, Tu, q, prior, (double*)h->stage[1].p,
+                             grad_u_out ? (double*)h->stage[2].p : nullptr));
+    PASS(stage_down(h, F_out, h->stage[1].p, PGL_DEC_NF * 8));
+    PASS(stage_down(h, grad_u_out, h->stage[2].p, ub));
+    return stage_end(h);
+}
+
+int pgl_decode_hvp(pgl_handle h, const double* v, int64_t Tu, int D, double* hv_out)
+{
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if (!v || !hv_out) return fail(PGL_ERR_ARG, "null argument");
+    PASS(dec_served(h));
+    if (!h->dec_ok || !h->dec_point) return fail(PGL_ERR_STATE, "pgl_decode_hvp before pgl_decode_eval");
+    PASS(dec_host_dims(h, D));
+    if (Tu != h->dec_Tu)
+        return fail(PGL_ERR_ARG, "stimulus decoding: the direction has " + std::to_string(Tu) + " frames, the last evaluation had " +
+                                     std::to_string(h->dec_Tu));
+    HIPCHK(hipSetDevice(h->device));
+    const size_t ub = (size_t)h->dec_Tu * h->dec_D * 8;
+    PASS(stage_up(h, 0, v, ub));
+    PASS(stage_up(h, 1, nullptr, ub));
+    PASS(pgl_decode_hvp_dev(h, (const double*)h->stage[0].p, (double*)h->stage[1].p));
+    PASS(stage_down(h, hv_out, h->stage[1].p, ub));
+    return stage_end(h);
+}
+
+// the rule on the host (csrc/pglm_decode.h), no GPU: what tests/csrc/decode_host.c compiles with gcc
+int pgl_decode_host(int N, int64_t nT, int nlin, double dt, const double* c, const double* S, const double* basis_t, int Rt, int B,
+                    int D, const double* theta, int P, const double* u, int64_t Tu, int q, const pgl_decode_prior* prior,
+                    const double* v, double* F_out, double* grad_u_out, double* hv_out)
+{
+    if (!c || !S || !basis_t || !theta || !u || !prior || !F_out) return fail(PGL_ERR_ARG, "null argument");
+    if (N < 1 || nT < 1 || Rt < 1 || B < 1 || D < 1 || P < 1 + D * B || Tu < 1 || q < 1 || !(dt > 0) || !(prior->sigma > 0.0) ||
+        (nlin != PGL_NLIN_EXP && nlin != PGL_NLIN_EXPLINEAR) || (v && !hv_out))
+        return fail(PGL_ERR_ARG, "bad decoding problem");
+    const PglDecPrior pr = {prior->mu, prior->sigma, prior->rho};
+    std::vector<double> K((size_t)Rt * D * N), r((size_t)nT * N), cc((size_t)nT * N), s((size_t)nT * D), gs((size_t)nT * D);
+    for (int tau = 0; tau < Rt; ++tau)
+        for (int d = 0; d < D; ++d)
+            for (int n = 0; n < N; ++n) K[((size_t)tau * D + d) * N + n] = pgl_dec_filter_at(basis_t, B, theta, P, tau, d, n);
+    pgl_dec_eval_host(nT, N, nlin, dt, c, S, K.data(), Rt, D, u, Tu, q, &pr, F_out, grad_u_out, r.data(), cc.data(), s.data(),
+                      gs.data());
+    if (v) {
+        std::vector<double> y((size_t)nT * N);
+        pgl_dec_hvp_host(nT, N, cc.data(), K.data(), Rt, D, v, Tu, q, &pr, hv_out, s.data(), y.data(), gs.data());
+    }
+    return PGL_OK;
 }
 
 int pgl_state(pgl_handle h, int n, const double* theta_n, const double* Weff_col, double* lam_out,

@@ -55,6 +55,9 @@
 // pglm_filters.hip.h).
 // The clamped simulation holds the other neurons at their recorded spikes: the chains (replicate, neuron) decouple, one wave
 // per (neuron, 64 replicates) with the self-history in a per-lane queue (k_cond_currents, k_simulate_cond, pglm_condsim.hip.h).
+// Decoding turns the question round: the MAP stimulus given the spikes.  The objective, its gradient and its Hessian-vector
+// products with respect to the stimulus are the adjoint pair of the feature build, two convolutions over (nT, N) around the
+// rate and curvature functions (k_dec_forward, k_dec_backward, pglm_decode.hip.h).
 #pragma once
 //
 // The kernels live in one header per family; this file is the translation unit's table of contents.
@@ -92,3 +95,4 @@
 #include "pglm_filters.hip.h"
 #include "pglm_simulate.hip.h"
 #include "pglm_condsim.hip.h"
+#include "pglm_decode.hip.h"

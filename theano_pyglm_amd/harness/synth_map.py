@@ -18,6 +18,9 @@ table (serial correlation of the normal scores at the lags 1 .. L, inference/gof
 neuron simulated with its own spikes fed back and the other neurons held at their recorded spikes (inference/predictive.py:
 conditional_counts) -- the largest |pearson| and its window, the KS distance of the pit values, the share of windows whose
 observed count lies outside the replicates' [min, max].
+--decode decodes the data set's own stimulus from its spikes under the fitted model (inference/decode.py: the MAP stimulus under
+a Gaussian prior, --decode-sigma and --decode-rho) and prints F at the decoded and at the recorded stimulus and the correlation
+of the two per stimulus dimension.
 --hmc N draws N posterior samples of every neuron's parameters from the fit by lock-step HMC on the device
 (inference/batched_hmc.py) and prints the bias posterior mean +- sd per neuron, beside the Laplace standard error when
 the model's packing has one.
@@ -51,6 +54,8 @@ import os
 import pickle
 import time
 
+import numpy as np
+
 from theano_pyglm_amd.inference.coord_descent import coord_descent
 from theano_pyglm_amd.models.model_factory import make_model, stabilize_sparsity
 from theano_pyglm_amd.population import Population
@@ -75,7 +80,7 @@ def initialize_test_harness(model_name, data, data_dir=None):
 
 def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, rng=None, use_rop=False, gof=False, ppc=0, hmc=0, ais=0,
                    hmc_mass='laplace', prox=False, laplace_device=False, ais_mass='laplace', nuts=0, smc=0, newton=False, waic=False, loo=False, diag=False, rates=0,
-                   gof_correct=False, gof_draws=False, gof_lags=0, coupling_test=None, coupling_lr=False, filters=None, cond_ppc=None):
+                   gof_correct=False, gof_draws=False, gof_lags=0, coupling_test=None, coupling_lr=False, filters=None, cond_ppc=None, decode=None):
     """test/synth_map.py:10-32."""
     popn, popn_true, x_true = initialize_test_harness(model_name, data, data_dir)
     x0 = popn.sample(rng)
@@ -103,6 +108,8 @@ def run_synth_test(model_name, data, results_dir, data_dir=None, batched=None, r
         print(predictive.format_table(predictive.predictive_counts(popn, x_inf, ppc)))
     if cond_ppc:
         print(cond_ppc_table(popn, x_inf, cond_ppc))
+    if decode:
+        print(decode_table(popn, x_inf, *decode))
     if hmc:
         print(hmc_bias_table(popn, x_inf, hmc, hmc_mass, laplace_device, waic=waic, loo=loo, diag=diag, rates=rates, gof_draws=gof_draws, gof_lags=gof_lags,
                              filters=filters, truth=true_adjacency(popn_true, x_true)))
@@ -328,6 +335,24 @@ def smc_evidence_table(popn, x, n_particles, laplace_device=False, mass='laplace
     return "\n".join(lines)
 
 
+def decode_table(popn, x, sigma=1.0, rho=np.inf):
+    """The lines of --decode: the MAP stimulus of the current data given its spikes and the fitted parameters."""
+    from theano_pyglm_amd.inference.decode import decode_stimulus
+    stim = np.asarray(popn._current['stim'], dtype=float)
+    stim = stim[:, None] if stim.ndim == 1 else stim
+    res = decode_stimulus(popn, x, sigma=sigma, rho=rho)
+    F_rec = popn.compute_stimulus_ll_grad(x, stim, sigma=sigma, rho=rho)[0]
+    lines = ["stimulus decoding (%s; sigma = %g, rho = %g): status %d, max |grad| = %.2e, %d evaluations, %d products"
+             % (res['route'], sigma, rho, res['status'], res['grad_max'], res['n_eval'], res['n_hvp']),
+             "  F at the decoded stimulus   %.6f  (log lik %.6f, log prior %.6f)" % (res['F'], res['log_lik'], res['log_prior']),
+             "  F at the recorded stimulus  %.6f  (log lik %.6f, log prior %.6f)" % (F_rec[0], F_rec[1], F_rec[2])]
+    for d in range(stim.shape[1]):
+        a, b = res['stim'][:, d], stim[:, d]
+        r = float(np.corrcoef(a, b)[0, 1]) if np.std(a) > 0 and np.std(b) > 0 else float('nan')
+        lines.append("  stimulus dimension %d: correlation of decoded and recorded %.4f" % (d, r))
+    return "\n".join(lines)
+
+
 class _CondPpc(argparse.Action):
     """--cond-ppc N [WIN]: one or two positive integers"""
     def __call__(self, ap, namespace, values, option_string=None):
@@ -369,6 +394,11 @@ def parser():
     ap.add_argument('--cond-ppc', type=int, nargs='+', default=None, metavar='N', action=_CondPpc,
                     help='N [WIN]: after the fit, the clamped predictive check of N replicates per neuron over windows of WIN bins '
                          '(default 50): each neuron simulated on the device given the recorded spikes of the others')
+    ap.add_argument('--decode', action='store_true',
+                    help="after the fit: decode the data set's own stimulus from its spikes on the device (a 'basis' stimulus)")
+    ap.add_argument('--decode-sigma', type=float, default=1.0, help='standard deviation of the decoding prior (default 1)')
+    ap.add_argument('--decode-rho', type=float, default=float('inf'),
+                    help='scale of the first differences in the decoding prior (default inf: iid)')
     ap.add_argument('--hmc', type=int, default=0, metavar='N',
                     help='after the fit: N posterior draws per neuron by lock-step HMC on the device; prints the bias mean +- sd')
     ap.add_argument('--nuts', type=int, default=0, metavar='N',
@@ -425,7 +455,7 @@ def main(argv=None):
                    newton=args.newton, waic=args.waic, loo=args.loo, diag=args.diag, rates=args.rates,
                    gof_correct=args.gof_correct, gof_draws=args.gof_draws, gof_lags=args.gof_lags,
                    coupling_test=args.coupling_test, coupling_lr=args.coupling_lr, filters=args.filters,
-                   cond_ppc=args.cond_ppc)
+                   cond_ppc=args.cond_ppc, decode=(args.decode_sigma, args.decode_rho) if args.decode else None)
 
 
 if __name__ == '__main__':

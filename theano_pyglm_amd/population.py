@@ -430,6 +430,43 @@ class Population(object):
             return np.zeros((0, self.N)), np.zeros((0, self.N))
         return np.concatenate([lam for lam, _ in pairs], axis=0), np.concatenate([obs for _, obs in pairs], axis=0)
 
+    # -- stimulus decoding -------------------------------------------------------------------
+    def _decode_point(self, vars, stim, mu, sigma, rho):
+        """The device handle of the current data prepared at `vars` and evaluated at the stimulus `stim` (Tu, D)."""
+        from theano_pyglm_amd.inference.decode import _served
+        bk, data, q = _served(self)
+        self._check_vars(vars)
+        stim = self._stimulus_array(stim, bk.n_vars // bk.B, 'stim')
+        h = self._handle(data)
+        h.decode_prepare(self.theta_matrix(vars), self.W_eff(vars))
+        return h, h.decode_eval(stim, q, (mu, sigma, rho))
+
+    @staticmethod
+    def _stimulus_array(a, D, name):
+        """a as a float (Tu, D) array; a vector is one stimulus dimension.  ValueError where its columns are not the model's D."""
+        a = np.asarray(a, dtype=float)
+        if a.ndim == 1:
+            a = a[:, None]
+        if a.ndim != 2 or a.shape[1] != D:
+            raise ValueError("%s must be (Tu, D) with D = %d stimulus dimensions, got %s" % (name, D, a.shape))
+        return a
+
+    def compute_stimulus_ll_grad(self, vars, stim, mu=0.0, sigma=1.0, rho=np.inf):
+        """The decoding objective of the current data at the stimulus `stim` (Tu, D) on the stimulus grid, the spikes and `vars`
+        fixed: returns (F (3,): log posterior of the stimulus up to a constant, log likelihood, log prior; its gradient with
+        respect to the stimulus (Tu, D)), computed on the device (pgl_decode_eval).  The prior per stimulus dimension is
+        Gaussian with mean mu and precision I / sigma^2 + Dt^T Dt / rho^2.  A 'basis' stimulus with dt_stim an integer
+        multiple of dt only; other backgrounds and a time-sharded population raise ValueError."""
+        return self._decode_point(vars, stim, mu, sigma, rho)[1]
+
+    def compute_stimulus_hvp(self, vars, stim, v, mu=0.0, sigma=1.0, rho=np.inf):
+        """The Hessian of that objective at `stim` times the direction v (Tu, D) (pgl_decode_hvp)."""
+        from theano_pyglm_amd.inference.decode import _served
+        bk = _served(self)[0]
+        v = self._stimulus_array(v, bk.n_vars // bk.B, 'v')
+        h, _ = self._decode_point(vars, stim, mu, sigma, rho)
+        return h.decode_hvp(v)
+
     # -- state ---------------------------------------------------------------------------
     def eval_state(self, vars):
         """population.py:88-120: rates, currents and component state of every neuron."""
